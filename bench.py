@@ -126,6 +126,34 @@ def build_identity() -> dict:
   return out
 
 
+DUMP_WHOLE_MAX = 1 << 22  # --dump-outputs: an output of at most this many elements is written whole, a larger one as a sample of this many
+
+
+def dump_outputs(out_dir: str, result, names=("out", "lse")) -> dict:
+  """`--dump-outputs DIR`: what the timed path returned in its last timed step (a tensor, or a tuple of them: O, then LSE), each as DIR/<name>.npy in
+  float32 (bf16 / fp16 widen exactly).  An output of more than DUMP_WHOLE_MAX elements is written as the values at a fixed sample of its flattened
+  indices: np.unique(default_rng(0).integers(0, numel, DUMP_WHOLE_MAX)), so the same shape gives the same positions in every run and every build
+  (at most 16 MB per array).  Returns what was written, for the result line."""
+  import numpy as np
+
+  tensors = [result] if torch.is_tensor(result) else [t for t in result if torch.is_tensor(t)]
+  assert len(tensors) <= len(names), len(tensors)
+  os.makedirs(out_dir, exist_ok=True)
+  written = {}
+  for name, t in zip(names, tensors):
+    desc = {"file": f"{name}.npy", "shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", "")}
+    if t.numel() <= DUMP_WHOLE_MAX:
+      arr = t.detach().float().cpu().numpy()
+      desc["saved"] = "whole"
+    else:
+      idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), size=DUMP_WHOLE_MAX))
+      arr = t.detach().reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+      desc["saved"] = f"sample of {idx.size} flattened indices: np.unique(np.random.default_rng(0).integers(0, {t.numel()}, {DUMP_WHOLE_MAX}))"
+    np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+    written[name] = desc
+  return {"dir": out_dir, "arrays": written}
+
+
 def planned_kernel(w: dict, q, k, v, mask, scale: float) -> dict:
   """The launch plan of this workload's call, from the C-ABI (ffpa_attn_fwd_plan / ffpa_attn_fwd_kernel): the kernel the roofline
   object is about is whatever the library says it launches — no copy of the dispatch rule lives here."""
@@ -509,7 +537,9 @@ def varlen_decode_main(args) -> None:
 
   telemetry = DeviceTelemetry(0)
 
-  def timed(fn, telem=False):
+  last_result = []
+
+  def timed(fn, telem=False, keep=False):
     for _ in range(args.warmup):
       fn()
     torch.cuda.synchronize()
@@ -520,7 +550,10 @@ def varlen_decode_main(args) -> None:
     t0 = time.perf_counter()
     for i in range(args.steps):
       starts[i].record()
-      fn()
+      if keep and i == args.steps - 1:
+        last_result[:] = [fn()]  # (--dump-outputs: what the last timed step returned)
+      else:
+        fn()
       ends[i].record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
@@ -528,7 +561,9 @@ def varlen_decode_main(args) -> None:
       telemetry.stop()
     return elapsed, sorted(a.elapsed_time(b) for a, b in zip(starts, ends))
 
-  elapsed, kernel_ms = timed(step, telem=True)
+  elapsed, kernel_ms = timed(step, telem=True, keep=True)
+  dumped = dump_outputs(args.dump_outputs, last_result[0]) if args.dump_outputs else None
+  last_result.clear()
   device = telemetry.summary()
   kernel_ms_avg = sum(kernel_ms) / len(kernel_ms)
   plan = {}
@@ -574,6 +609,8 @@ def varlen_decode_main(args) -> None:
     "roofline": roof, "device": device, "steady_state": steady, "build": build,
     "plan": {k_: plan[k_] for k_ in ("row_tiles", "block_rows", "block_keys", "workgroups", "splits")},
   }
+  if dumped is not None:
+    line["dump_outputs"] = dumped
   if not args.no_sdpa:  # (the comparison legs; --no-sdpa: none of them — the profiler passes)
     legs = {}
     for what, kw in (("one_kv_range", dict(num_splits=1)), ("one_workgroup_per_query_head", dict(flags=hip.FLAG_NO_PACK_GQA)), ("no_nt_hint", dict(flags=hip.FLAG_NO_KV_STREAM))):
@@ -652,7 +689,9 @@ def varlen_main(args) -> None:
 
   telemetry = DeviceTelemetry(0)
 
-  def timed(fn):
+  last_result = []
+
+  def timed(fn, keep=False):
     for _ in range(args.warmup):
       fn()
     torch.cuda.synchronize()
@@ -662,14 +701,19 @@ def varlen_main(args) -> None:
     t0 = time.perf_counter()
     for i in range(args.steps):
       starts[i].record()
-      fn()
+      if keep and i == args.steps - 1:
+        last_result[:] = [fn()]  # (--dump-outputs: what the last timed step returned)
+      else:
+        fn()
       ends[i].record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     telemetry.stop()
     return elapsed, sorted(a.elapsed_time(b) for a, b in zip(starts, ends))
 
-  elapsed, kernel_ms = timed(step)
+  elapsed, kernel_ms = timed(step, keep=True)
+  dumped = dump_outputs(args.dump_outputs, last_result[0]) if args.dump_outputs else None
+  last_result.clear()
   device = telemetry.summary()
   kernel_ms_avg = sum(kernel_ms) / len(kernel_ms)
   value = flops * args.steps / elapsed / 1e12
@@ -717,6 +761,8 @@ def varlen_main(args) -> None:
     "roofline": roof, "device": device, "steady_state": steady, "build": build,
     "plan": {k_: plan[k_] for k_ in ("row_tiles", "block_rows", "block_keys", "workgroups")},
   }
+  if dumped is not None:
+    line["dump_outputs"] = dumped
   # the same batch as a loop of dense calls, one per sequence — and its outputs against the packed call's (same tile, same recurrence: the bits where the
   # dense plan is the plain tile; rounding where it pairs / splits / takes another tile)
   out = step()
@@ -990,9 +1036,15 @@ def main() -> None:
   ap.add_argument("--no-steady", action="store_true", help="N = 1: skip the steady-state leg (the step again after >= 150 ms of continuous load, outside the timed region)")
   ap.add_argument("--sweep", action="store_true", help="the reference bench's case table for --sweep-dims in one process (python -m ffpa_attn.bench)")
   ap.add_argument("--sweep-dims", default="320,512,1024")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32; "
+                  "outputs larger than 4 Mi elements as a fixed seeded sample): inputs are seeded, so two builds can be compared output for output")
   ap.add_argument("--stub-backend", default="", help="(tests) run the launch / barrier / reduction plumbing on CPU over this torch.distributed "
                   "backend (gloo) with a sleep for a step: no GPU, no kernel, NOT a benchmark")
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be >= 1 and --warmup >= 0")
+  if args.dump_outputs and (args.sweep or args.stub_backend):
+    ap.error("--dump-outputs needs the timed path of one workload (not --sweep / --stub-backend)")
 
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
     # no launcher around us: be our own (the torchrun form keeps working: it sets WORLD_SIZE)
@@ -1104,7 +1156,10 @@ def main() -> None:
     t0 = time.perf_counter()
     for i in range(args.steps):
       starts[i].record()  # the kernel is launched on torch's current stream; so are these events
-      fn()
+      if i == args.steps - 1:
+        last_result[:] = [fn()]  # (--dump-outputs: what the last timed step returned)
+      else:
+        fn()
       ends[i].record()
     torch.cuda.synchronize()
     local = time.perf_counter() - t0
@@ -1124,7 +1179,10 @@ def main() -> None:
     return total, per_rank, sorted(a.elapsed_time(b) for a, b in zip(starts, ends))
 
   telemetry = DeviceTelemetry(local_rank)
+  last_result = []
   elapsed, per_rank_tflops, kernel_ms = timed(step)
+  dumped = dump_outputs(args.dump_outputs, last_result[0]) if (args.dump_outputs and rank == 0) else None
+  last_result.clear()
   device = telemetry.summary()  # (of the first timed region: the bench line's own)
   kernel_ms_avg = sum(kernel_ms) / len(kernel_ms)
   value = flops_global * args.steps / elapsed / 1e12
@@ -1308,6 +1366,8 @@ def main() -> None:
       "build": build,
       "plan": {k_: plan.get(k_) for k_ in ("variant", "block_rows", "block_keys", "splits")},
     }
+    if dumped is not None:
+      line["dump_outputs"] = dumped
     if per_rank_tflops is not None:
       line["per_rank_tflops"] = per_rank_tflops
       line["rccl_world_size"] = world

@@ -88,3 +88,35 @@ def test_packed_decode_line_is_priced_against_hbm_and_names_its_launch():
   legs = line["other_launches"]
   assert legs["one_kv_range"]["splits"] == 1 and legs["one_workgroup_per_query_head"]["workgroups"] % (32 * 32) == 0 and ", NT>" not in legs["no_nt_hint"]["kernel"]
   assert line["per_sequence_loop"]["max_abs_diff_vs_packed"] < 4e-3 and line["max_abs_err_vs_sdpa"] < 1e-2
+
+
+@pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a GPU")
+def test_dump_outputs_are_the_timed_paths_result_and_repeat_run_to_run(tmp_path):
+  """`--dump-outputs DIR`: the last timed step's O as float32 (a seeded sample: the cross workload's O has 16 Mi elements), identical in two runs of the same
+  command, and the values SDPA gives at the same positions for the same seed-0 inputs; the packed decode call dumps its O and LSE whole."""
+  import numpy as np
+
+  flags = ("--gpus", "1", "--workload", "cross", "--steps", "3", "--warmup", "1", "--no-sdpa", "--no-cpu-baseline", "--no-live-traffic", "--no-steady", "--no-ref-protocol")
+  runs = [_bench(*flags, "--dump-outputs", str(tmp_path / d)) for d in ("a", "b")]
+  assert all(r["steps"] == 3 and r["ms_per_step"] > 0 for r in runs)
+  desc = runs[0]["dump_outputs"]["arrays"]
+  assert list(desc) == ["out"] and desc["out"]["shape"] == [1, 32, 1024, 512] and desc["out"]["saved"].startswith("sample")
+  a, b = np.load(tmp_path / "a" / "out.npy"), np.load(tmp_path / "b" / "out.npy")
+  assert a.dtype == np.float32 and np.array_equal(a, b)
+  dev = torch.device("cuda:0")
+  torch.manual_seed(0)
+  q = torch.randn(1, 32, 1024, 512, dtype=torch.bfloat16, device=dev)
+  k = torch.randn(1, 32, 8192, 512, dtype=torch.bfloat16, device=dev)
+  v = torch.randn(1, 32, 8192, 512, dtype=torch.bfloat16, device=dev)
+  ref = torch.nn.functional.scaled_dot_product_attention(q, k, v).float().reshape(-1).cpu().numpy()
+  idx = np.unique(np.random.default_rng(0).integers(0, ref.size, size=1 << 22))  # (the bench's draw: DUMP_WHOLE_MAX integers)
+  assert idx.size == a.size
+  err = np.abs(a - ref[idx])
+  assert (err <= 2.0 ** -7 * np.abs(ref[idx]) + 2e-3).all() and err.mean() < 0.05 * np.abs(ref[idx]).mean(), (err.max(), err.mean())
+
+  line = _bench("--gpus", "1", "--workload", "varlen_decode", "--steps", "2", "--warmup", "1", "--no-sdpa", "--no-cpu-baseline", "--no-live-traffic", "--no-steady",
+                "--dump-outputs", str(tmp_path / "c"))
+  desc = line["dump_outputs"]["arrays"]
+  assert desc["out"]["shape"] == [32, 32, 512] and desc["out"]["saved"] == "whole" and desc["lse"]["saved"] == "whole"
+  o, lse = np.load(tmp_path / "c" / "out.npy"), np.load(tmp_path / "c" / "lse.npy")
+  assert o.shape == (32, 32, 512) and np.isfinite(o).all() and np.isfinite(lse).all() and lse.dtype == np.float32

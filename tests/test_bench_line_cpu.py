@@ -38,3 +38,26 @@ def test_committed_r04_profiles_name_their_binary():
   for f in files:
     prov = json.load(open(f)).get("provenance", {})
     assert len(prov.get("lib_sha16", "")) == 16 and prov.get("git_head") and prov.get("bench_kernel"), f
+
+
+def test_dump_outputs_writes_float32_whole_or_a_fixed_sample(tmp_path):
+  """`--dump-outputs`: a small output whole (shape kept), a large one as the same seeded sample of positions every time, float32, <= 16 MB per array."""
+  import numpy as np
+  import torch
+
+  bench = _bench()
+  small = torch.randn(2, 3, 5, 7, dtype=torch.bfloat16)
+  lse = torch.randn(2, 3, 5, dtype=torch.float32)
+  got = bench.dump_outputs(str(tmp_path / "a"), (small, lse))
+  assert set(got["arrays"]) == {"out", "lse"} and got["arrays"]["out"]["saved"] == "whole"
+  o = np.load(tmp_path / "a" / "out.npy")
+  assert o.dtype == np.float32 and o.shape == (2, 3, 5, 7) and np.array_equal(o, small.float().numpy())
+  assert np.array_equal(np.load(tmp_path / "a" / "lse.npy"), lse.numpy())
+
+  big = torch.arange(bench.DUMP_WHOLE_MAX * 3, dtype=torch.float32).reshape(3, -1)
+  for d in ("b", "c"):
+    bench.dump_outputs(str(tmp_path / d), big)
+  b, c = np.load(tmp_path / "b" / "out.npy"), np.load(tmp_path / "c" / "out.npy")
+  assert b.dtype == np.float32 and b.nbytes <= 16 << 20 and np.array_equal(b, c)
+  assert b.size > bench.DUMP_WHOLE_MAX // 2 and (np.diff(b) > 0).all() and b.max() < big.numel()  # distinct positions in index order, the values at them
+  assert not (tmp_path / "b" / "lse.npy").exists()
