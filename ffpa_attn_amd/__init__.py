@@ -10,6 +10,7 @@ from .flops import attention_fwd_flops, attention_valid_pairs
 from .functional import FFPAAttnMeta
 from .decode import DecodeStep
 from .interface import ffpa_attn_func, ffpa_attn_varlen_func
+from .kvcache import ffpa_attn_with_kvcache
 
 
 
@@ -91,6 +92,7 @@ __version__ = "0.5.0"  # = the library's ffpa_attn_version() ("ffpa-attn-amd 0.5
 __all__ = [
   "ffpa_attn_func",
   "ffpa_attn_varlen_func",
+  "ffpa_attn_with_kvcache",
   "install_alias",
   "DecodeStep",
   "Backend",

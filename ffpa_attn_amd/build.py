@@ -180,6 +180,16 @@ def build(force: bool = False, jobs: int | None = None, save_temps: bool = True,
       tmp = os.path.join(OBJ_DIR, f"temps_d{d}")
       os.makedirs(tmp, exist_ok=True)
       tasks.append((obj, [hipcc, *CXXFLAGS, *product, *extra, f"-DFFPA_INST_D={d}", "-c", os.path.join(CSRC, "ffpa_varlen_inst.hip"), "-o", obj], tmp))
+  # the paged-KV twin of the packed-sequence kernel (ffpa_paged_inst.hip): a TU of its own per head dim, so that the dense and packed objects stay what they were
+  for d in VARLEN_HEAD_DIMS:
+    obj = os.path.join(OBJ_DIR, f"ffpa_paged_d{d}.o")
+    objs.append(obj)
+    if test_lib:
+      test_objs.append(obj)
+    if stale(obj):
+      tmp = os.path.join(OBJ_DIR, f"temps_d{d}")
+      os.makedirs(tmp, exist_ok=True)
+      tasks.append((obj, [hipcc, *CXXFLAGS, *product, *extra, f"-DFFPA_INST_D={d}", "-c", os.path.join(CSRC, "ffpa_paged_inst.hip"), "-o", obj], tmp))
   capi = os.path.join(OBJ_DIR, "ffpa_capi.o")
   objs.append(capi)
   if stale(capi):
@@ -231,8 +241,9 @@ def build_variant(tag: str, defs: list[str], jobs: int | None = None, head_dims:
     # the untouched head dims come from the main build (whose objects a round-end clean_dev() may have removed: rebuilt then)
     missing = [d for d in HEAD_DIMS if d not in head_dims and not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_fwd_d{d}.o"))]
     missing += [d for d in VARLEN_HEAD_DIMS if not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_varlen_d{d}.o"))]
+    missing += [d for d in VARLEN_HEAD_DIMS if not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_paged_d{d}.o"))]
     build(force=bool(missing), verbose=False)
-  elif any(not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_varlen_d{d}.o")) for d in VARLEN_HEAD_DIMS):
+  elif any(not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_{k}_d{d}.o")) for d in VARLEN_HEAD_DIMS for k in ("varlen", "paged")):
     build(force=True, verbose=False)
   tasks, objs = [], []
   for d in HEAD_DIMS:
@@ -243,6 +254,7 @@ def build_variant(tag: str, defs: list[str], jobs: int | None = None, head_dims:
     objs.append(obj)
     tasks.append([hipcc, *CXXFLAGS, *defs, f"-DFFPA_INST_D={d}", "-c", os.path.join(CSRC, "ffpa_fwd_inst.hip"), "-o", obj])
   objs += [os.path.join(OBJ_DIR, f"ffpa_varlen_d{d}.o") for d in VARLEN_HEAD_DIMS]  # (the packed-sequence kernels: the main build's, never a variant's)
+  objs += [os.path.join(OBJ_DIR, f"ffpa_paged_d{d}.o") for d in VARLEN_HEAD_DIMS]  # (and their paged twins)
   capi = os.path.join(odir, "ffpa_capi.o")
   objs.append(capi)
   tasks.append([hipcc, *CXXFLAGS, *defs, "-c", os.path.join(CSRC, "ffpa_capi.hip"), "-o", capi])  # (the plan must see the same tunables as the kernels)

@@ -19,6 +19,7 @@
 #include "ffpa_fwd_m16_kernel.h"  // (FFPA_M16_MIN_D: the head dims whose prefill launches run the 16x16x32 build)
 #include "ffpa_varlen_merge.h"   // (stage 2 of a KV-split packed-sequence launch)
 #include "ffpa_launch.h"
+#include "ffpa_paged.h"         // (the paged-KV twin of the packed-sequence kernel)
 
 namespace {
 
@@ -58,6 +59,14 @@ const VarlenEntry kVarlenDims[] = {
     FFPA_FOR_EACH_VARLEN_HEAD_DIM(FFPA_ROW)
 #undef FFPA_ROW
 };
+// ... and its paged-KV twin (ffpa_paged_inst.hip), the same head dims: entry i serves kVarlenDims[i].d
+typedef int (*paged_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, hipStream_t);
+const paged_fn kPagedDims[] = {
+#define FFPA_ROW(D) &ffpa::launch_paged_d##D,
+    FFPA_FOR_EACH_VARLEN_HEAD_DIM(FFPA_ROW)
+#undef FFPA_ROW
+};
+static_assert(sizeof(kPagedDims) / sizeof(kPagedDims[0]) == sizeof(kVarlenDims) / sizeof(kVarlenDims[0]), "one paged launcher per packed head dim");
 
 // Head dims are instantiated in multiples of 64; any multiple of 8 up to 1024 runs on the next instantiation with the
 // columns past the caller's head dim read as zeros and never stored (the reference pads to its compiled multiples on
@@ -924,8 +933,9 @@ struct VarlenPlan {
 };
 
 // Validation shared by the launch and the queries; fills the plan.  Head dims below the first 16x16x32 instantiation run on it (columns past the
-// caller's head dim read as zeros and are never stored, as in the dense call).
-int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out) {
+// caller's head dim read as zeros and are never stored, as in the dense call).  `paged`: the plan of the paged-KV kernel — 64-key tiles where the packed kernel
+// takes 128 (D = 256 / 320), everything else the same rule.
+int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = false) {
   if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
   if (p->struct_size != sizeof(ffpa_varlen_fwd_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
     return fail(FFPA_ERR_BAD_ABI, "ffpa_varlen_fwd_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size,
@@ -945,7 +955,7 @@ int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out) {
   if (ve == nullptr) return fail(FFPA_ERR_BAD_HEADDIM, "headdim not support! D=%d", p->head_dim);
   out->ve = ve;
   out->br = 128 / (dk <= 512 ? 1 : 2);
-  out->bc = ffpa::m16_block_keys(dk, false);
+  out->bc = ffpa::m16_block_keys(dk, paged);
   // short query sequences under GQA — decode (one token per sequence), speculative decoding / multi-token prediction / small prefill chunks (a few) —: the group's
   // heads x the sequence's tokens ride in the rows of ONE tile per (sequence, KV head), head-major (VarlenArgs::pack) — the K / V stream of a group is read once, not
   // once per query head, and the tile's MFMA rows are `group` times better used.  Packed when every sequence's rows fit one tile: group x max_seqlen_q <= block rows.
@@ -1062,15 +1072,38 @@ int check_strides2(const char* name, const int64_t s[2]) {
   return FFPA_OK;
 }
 
-}  // namespace
+// The paged call's own arguments (ffpa_paged_kv), checked behind the packed call's plan and before anything touches the device.
+int check_paged(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv) {
+  if (kv == nullptr) return fail(FFPA_ERR_NULL_POINTER, "paged kv is NULL");
+  if (kv->struct_size != sizeof(ffpa_paged_kv))
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_paged_kv ABI mismatch: size %u (want %zu)", kv->struct_size, sizeof(ffpa_paged_kv));
+  if (kv->block_table == nullptr) return fail(FFPA_ERR_NULL_POINTER, "block_table must be non-NULL");
+  if (p->seqused_kv == nullptr) return fail(FFPA_ERR_NULL_POINTER, "seqused_kv must be non-NULL: it gives the paged call's key lengths");
+  if (reinterpret_cast<uintptr_t>(kv->block_table) & 3u) return fail(FFPA_ERR_MISALIGNED, "block_table must be 4-byte aligned");
+  if (kv->page_size <= 0 || kv->page_size % 64 != 0) return fail(FFPA_ERR_BAD_SHAPE, "page_size=%d is not a positive multiple of 64", kv->page_size);
+  if (kv->pages_per_row <= 0 || kv->num_pages <= 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "pages_per_row=%d / num_pages=%d must be positive", kv->pages_per_row, kv->num_pages);
+  if ((int64_t)kv->pages_per_row * kv->page_size > 0x7fffffffLL)
+    return fail(FFPA_ERR_BAD_SHAPE, "pages_per_row x page_size = %lld keys per sequence is too large", (long long)kv->pages_per_row * kv->page_size);
+  if (kv->bt_stride < kv->pages_per_row)
+    return fail(FFPA_ERR_BAD_STRIDE, "bt_stride=%lld is smaller than pages_per_row=%d", (long long)kv->bt_stride, kv->pages_per_row);
+  for (const int64_t st : {kv->k_page_stride, kv->v_page_stride}) {
+    if (st < 0) return fail(FFPA_ERR_BAD_STRIDE, "page stride %lld is negative", (long long)st);
+    if (st % 8 != 0) return fail(FFPA_ERR_BAD_STRIDE, "page stride %lld is not a multiple of 8 elements (16 bytes)", (long long)st);
+  }
+  return FFPA_OK;
+}
 
-int ffpa_attn_varlen_fwd(const ffpa_varlen_fwd_params* p, void* stream) {
+// The packed call and its paged twin (kv != NULL: k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read)
+int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream) {
+  const bool paged = kv != nullptr;
   VarlenPlan pl;
-  int rc = varlen_plan(p, &pl);
+  int rc = varlen_plan(p, &pl, paged);
   if (rc != FFPA_OK) return rc;
+  if (paged && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
   if (!p->q || !p->k || !p->v || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
-  if (!p->cu_seqlens_q || !p->cu_seqlens_kv) return fail(FFPA_ERR_NULL_POINTER, "cu_seqlens_q / cu_seqlens_kv must be non-NULL");
-  if ((reinterpret_cast<uintptr_t>(p->cu_seqlens_q) & 3u) || (reinterpret_cast<uintptr_t>(p->cu_seqlens_kv) & 3u) || (reinterpret_cast<uintptr_t>(p->seqused_kv) & 3u))
+  if (!p->cu_seqlens_q || (!paged && !p->cu_seqlens_kv)) return fail(FFPA_ERR_NULL_POINTER, "cu_seqlens_q / cu_seqlens_kv must be non-NULL");
+  if ((reinterpret_cast<uintptr_t>(p->cu_seqlens_q) & 3u) || (!paged && (reinterpret_cast<uintptr_t>(p->cu_seqlens_kv) & 3u)) || (reinterpret_cast<uintptr_t>(p->seqused_kv) & 3u))
     return fail(FFPA_ERR_MISALIGNED, "cu_seqlens_q / cu_seqlens_kv / seqused_kv must be 4-byte aligned");
   if (!aligned16(p->q) || !aligned16(p->k) || !aligned16(p->v) || !aligned16(p->o))
     return fail(FFPA_ERR_MISALIGNED, "q/k/v/o base pointers must be 16-byte aligned");
@@ -1141,7 +1174,7 @@ int ffpa_attn_varlen_fwd(const ffpa_varlen_fwd_params* p, void* stream) {
 
   ffpa::VarlenArgs va;
   va.cu_q = p->cu_seqlens_q;
-  va.cu_k = p->cu_seqlens_kv;
+  va.cu_k = paged ? nullptr : p->cu_seqlens_kv;
   va.lse_stride_h = p->lse_stride_head;
   // heads of one KV group that walk a sequence side by side (ffpa_fwd_m16_varlen_kernel; pick_head_chunk: whole chunks per XCD, never across KV groups — MHA and
   // head counts that do not divide into eight chunks run plain head-major order)
@@ -1171,7 +1204,21 @@ int ffpa_attn_varlen_fwd(const ffpa_varlen_fwd_params* p, void* stream) {
     va.ws_split_rows = (int64_t)p->heads_q * p->total_q;
   }
 
-  int st = pl.ve->launch(p->dtype, pl.nt, a, va, static_cast<hipStream_t>(stream));
+  int st;
+  if (paged) {
+    ffpa::PagedArgs pa;
+    pa.table = kv->block_table;
+    pa.bt_stride = kv->bt_stride;
+    pa.k_page_stride = kv->k_page_stride;
+    pa.v_page_stride = kv->v_page_stride;
+    pa.cap = kv->pages_per_row * kv->page_size;
+    pa.page_size = kv->page_size;
+    pa.tiles_per_page = kv->page_size / pl.bc;
+    pa.num_pages = kv->num_pages;
+    st = kPagedDims[pl.ve - kVarlenDims](p->dtype, pl.nt, a, va, pa, static_cast<hipStream_t>(stream));
+  } else {
+    st = pl.ve->launch(p->dtype, pl.nt, a, va, static_cast<hipStream_t>(stream));
+  }
   if (st == 0 && pl.splits > 1) {
     const dim3 grid((unsigned)((int64_t)p->heads_q * p->total_q), (unsigned)(p->head_dim + 255) / 256);
     if (p->dtype == FFPA_DTYPE_BF16)
@@ -1186,10 +1233,13 @@ int ffpa_attn_varlen_fwd(const ffpa_varlen_fwd_params* p, void* stream) {
   return FFPA_OK;
 }
 
-int ffpa_attn_varlen_fwd_plan(const ffpa_varlen_fwd_params* params, int out[5]) {
-  VarlenPlan pl;
-  const int rc = varlen_plan(params, &pl);
-  if (rc != FFPA_OK) return rc;
+}  // namespace
+
+int ffpa_attn_varlen_fwd(const ffpa_varlen_fwd_params* p, void* stream) { return varlen_launch(p, nullptr, stream); }
+
+namespace {
+
+int plan_out(const VarlenPlan& pl, int out[5]) {
   if (out == nullptr) return fail(FFPA_ERR_NULL_POINTER, "out is NULL");
   out[0] = pl.nqt;
   out[1] = pl.br;
@@ -1199,25 +1249,67 @@ int ffpa_attn_varlen_fwd_plan(const ffpa_varlen_fwd_params* params, int out[5]) 
   return FFPA_OK;
 }
 
-size_t ffpa_attn_varlen_fwd_workspace_bytes(const ffpa_varlen_fwd_params* params) {
+size_t workspace_bytes(const ffpa_varlen_fwd_params* params, bool paged) {
   if (params == nullptr || params->struct_size != sizeof(ffpa_varlen_fwd_params)) return 0;
   // size for the split count the heuristic would pick with unlimited scratch
   ffpa_varlen_fwd_params q = *params;
   q.workspace = reinterpret_cast<void*>(16);
   q.workspace_bytes = ~0ull;
   VarlenPlan pl;
-  if (varlen_plan(&q, &pl) != FFPA_OK) return 0;
+  if (varlen_plan(&q, &pl, paged) != FFPA_OK) return 0;
   return pl.ws_bytes;
 }
+
+int kernel_name(const ffpa_varlen_fwd_params* params, const VarlenPlan& pl, bool paged, char* buf, size_t n) {
+  if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
+  snprintf(buf, n, "ffpa_fwd_m16_%s_kernel<%s, %d%s>%s%s", paged ? "paged" : "varlen", params->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d,
+           pl.nt ? ", NT" : "", pl.pack ? " (GQA heads packed into rows)" : "", pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
+  return FFPA_OK;
+}
+
+}  // namespace
+
+int ffpa_attn_varlen_fwd_plan(const ffpa_varlen_fwd_params* params, int out[5]) {
+  VarlenPlan pl;
+  const int rc = varlen_plan(params, &pl);
+  if (rc != FFPA_OK) return rc;
+  return plan_out(pl, out);
+}
+
+size_t ffpa_attn_varlen_fwd_workspace_bytes(const ffpa_varlen_fwd_params* params) { return workspace_bytes(params, false); }
 
 int ffpa_attn_varlen_fwd_kernel(const ffpa_varlen_fwd_params* params, char* buf, size_t n) {
   VarlenPlan pl;
   const int rc = varlen_plan(params, &pl);
   if (rc != FFPA_OK) return rc;
-  if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
-  snprintf(buf, n, "ffpa_fwd_m16_varlen_kernel<%s, %d%s>%s%s", params->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d, pl.nt ? ", NT" : "",
-           pl.pack ? " (GQA heads packed into rows)" : "", pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
-  return FFPA_OK;
+  return kernel_name(params, pl, false, buf, n);
+}
+
+// ---- the paged-KV twin (include/ffpa_attn.h: ffpa_paged_kv)
+int ffpa_attn_varlen_paged_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream) {
+  if (kv == nullptr) return fail(FFPA_ERR_NULL_POINTER, "paged kv is NULL");
+  return varlen_launch(p, kv, stream);
+}
+
+size_t ffpa_attn_varlen_paged_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv) {
+  if (kv == nullptr || kv->struct_size != sizeof(ffpa_paged_kv)) return 0;
+  return workspace_bytes(p, true);
+}
+
+int ffpa_attn_varlen_paged_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, int out[5]) {
+  VarlenPlan pl;
+  int rc = varlen_plan(p, &pl, true);
+  if (rc != FFPA_OK) return rc;
+  if ((rc = check_paged(p, kv)) != FFPA_OK) return rc;
+  return plan_out(pl, out);
+}
+
+int ffpa_attn_varlen_paged_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, char* buf, size_t n) {
+  VarlenPlan pl;
+  int rc = varlen_plan(p, &pl, true);
+  if (rc != FFPA_OK) return rc;
+  if ((rc = check_paged(p, kv)) != FFPA_OK) return rc;
+  return kernel_name(p, pl, true, buf, n);
 }
 
 int ffpa_attn_query(int what) {

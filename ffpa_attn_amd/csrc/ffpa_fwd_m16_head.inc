@@ -12,7 +12,11 @@
   // 32 qb .. + 32 and columns dh * D/2 .. of both contractions; the two partial S^T tiles of a row block are summed through LDS.
   constexpr int ND = (D <= 512) ? 1 : 2;
   constexpr int DW = D / ND;    // columns owned by one wave
+#ifdef FFPA_M16_PAGED
+  constexpr int BC = m16_block_keys(D, true), BR = 128 / ND;  // (the paged kernel: 64-key tiles at D = 256 / 320 too — a 64-key page holds a whole tile)
+#else
   constexpr int BC = m16_block_keys(D, kBias), BR = 128 / ND;
+#endif
   constexpr int KS = DW / 32;   // QK contraction steps per wave
   constexpr int NKB = BC / 16;  // 16-key S^T blocks per tile
   constexpr int NKS = BC / 32;  // PV contraction steps per tile

@@ -4,6 +4,16 @@
 // The K / V piece form (FFPA_M16_DMA16; FFPA_M16_MFMA in ffpa_fwd_m16_head.inc: the MFMA wrappers with a piece riding on them) and three expressions of the epilogue are the enclosing kernel's (macros, defined next to FFPA_M16_TILE_DONE): FFPA_M16_ROW_INV(l) = 1 / row sum, FFPA_M16_ROW_OUT(x, rh) = an
 // accumulator scaled by it and rounded to T, FFPA_M16_LSE_INDEX(row) = where row `row` of this (batch, head) lives in the LSE tensor, FFPA_M16_WS_ROW(row) = its row in the KV-split workspace (this split's partial), FFPA_M16_Q_ROW_OFF(row) / FFPA_M16_O_ROW_OFF(row) = the row's element offset inside this (batch, head) of q / o — the dense kernels expand them to the text that
 // stood here (their objects rebuild byte-identical), the packed-sequence kernel (ffpa_fwd_m16_varlen_kernel) to its own LSE layout and its empty-row contract.
+// Where a K / V tile comes from is the enclosing kernel's too when it defines FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) (kind 0: K, 1: V, 2: the L2 touch)
+// and the hooks around it — FFPA_M16_KV_BEGIN(t0) in front of the first piece, FFPA_M16_KV_STEP(k0) at the top of a KV step, FFPA_M16_KV_STEP_END() in front of
+// barrier B (the paged kernel, ffpa_paged_inst.hip); by default the tile's rows are contiguous from `slice` and the hooks are empty.
+#ifndef FFPA_M16_KV_SRC
+#define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) tile_src<BC>(slice, row_bytes, key0, a.Nkv, rb_valid)
+#define FFPA_M16_KV_BEGIN(t0_)
+#define FFPA_M16_KV_STEP(k0_)
+#define FFPA_M16_KV_STEP_END()
+#define FFPA_M16_KV_DEFAULT_HOOKS
+#endif
   const int b = bh / a.Hq;
   const int hq = bh - b * a.Hq;
   const int hkv = hq / a.group;
@@ -75,7 +85,7 @@
   }
   auto issue_k = [&](auto ic, int key0) {
     constexpr int i = decltype(ic)::value;
-    const TileSrc ts = tile_src<BC>(Kg, k_row_bytes, key0, a.Nkv, rb_valid);
+    const TileSrc ts = FFPA_M16_KV_SRC(0, Kg, k_row_bytes, key0);
     if constexpr (kRowDma) {
       lds_dma_row<(16 * (i >> 2) + (i & 3)) * RB, 0>(ts.rsrc, k_lds, kvo[i & 3], kro[i]);
     } else {
@@ -84,7 +94,7 @@
   };
   auto issue_v = [&](auto ic, int key0) {
     constexpr int i = decltype(ic)::value;
-    const TileSrc ts = tile_src<BC>(Vg, v_row_bytes, key0, a.Nkv, rb_valid);
+    const TileSrc ts = FFPA_M16_KV_SRC(1, Vg, v_row_bytes, key0);
     if constexpr (kRowDma) {
       lds_dma_row<(16 * (i >> 2) + (i & 3)) * RB, 0>(ts.rsrc, v_lds, vvo[i & 3], vro[i]);
     } else {
@@ -97,12 +107,12 @@
   constexpr bool kFuse = !kRowDma;  // DMA pieces ride on the MFMA in front of them (the scalar row form of the D = 512 bias / mask / dropout builds issues its own pieces)
   auto issue_k_on = [&](auto ic, int key0, auto kindc, f32x4& d, v8 fa, v8 fb) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
-    const TileSrc ts = tile_src<BC>(Kg, k_row_bytes, key0, a.Nkv, rb_valid);
+    const TileSrc ts = FFPA_M16_KV_SRC(0, Kg, k_row_bytes, key0);
     M::template with_dma<decltype(kindc)::value, (kKS && i >= kH ? 2 * PPW + (i - kH) : i) * 1024>(d, fa, fb, ts.rsrc, k_lds, krel[kRowDma ? 0 : i], 0u);
   };
   auto issue_v_on = [&](auto ic, int key0, auto kindc, f32x4& d, v8 fa, v8 fb) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
-    const TileSrc ts = tile_src<BC>(Vg, v_row_bytes, key0, a.Nkv, rb_valid);
+    const TileSrc ts = FFPA_M16_KV_SRC(1, Vg, v_row_bytes, key0);
     M::template with_dma<decltype(kindc)::value, i * 1024>(d, fa, fb, ts.rsrc, v_lds, vrel[kRowDma ? 0 : i], 0u);
   };
 
@@ -144,7 +154,7 @@
                                             (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pf_base64));
   const uint32_t pf_row_bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pf_k ? k_row_bytes : v_row_bytes));
   auto issue_prefetch = [&](int key0) {
-    const TileSrc ts = tile_src<BC>(pf_base, pf_row_bytes, key0, a.Nkv, rb_valid);
+    const TileSrc ts = FFPA_M16_KV_SRC(2, pf_base, pf_row_bytes, key0);
     asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "+v"(pf_junk) : "v"(pf_off), "s"(ts.rsrc) : "memory");
   };
 
@@ -328,6 +338,7 @@
       }
     }
   }
+  FFPA_M16_KV_BEGIN(t0)
   if (nt > t0) {
     static_for<PPW>([&](auto ic) { issue_k(ic, t0 * BC); });
     if constexpr (MK == 1) {
@@ -421,6 +432,7 @@
     }
     for (int j = t0; j < nt; ++j) {
       const int k0 = j * BC;
+      FFPA_M16_KV_STEP(k0)
       if constexpr (MK == 3) {
         // the ring's half that the walk has left behind takes the keys 1024 ... 2048 ahead (nobody reads them before 31 more steps — every barrier
         // in between publishes them —, nobody still reads what they replace: keys below k0).  The loads are the compiler's: its wait in front of the
@@ -700,6 +712,7 @@
       }
       FFPA_TSTAMP(4);  // PV loop
       // barrier B: every wave is done reading V(j); K2(j+1) has landed and is visible (the K1(j+2) pieces behind it stay in flight)
+      FFPA_M16_KV_STEP_END()
       if (pf_on) {  // (wave-uniform)
         issue_prefetch(k0 + FFPA_M16_PF_DIST * BC);
         dma_wait_except<ppWaitB + 1>();
@@ -739,6 +752,7 @@
   FFPA_LDS const char* const xb_nd2 = Xb + (qb * 2) * 4096 + lane * 16;       // the row block's two areas (wave dh = 0 first)
   for (int j = t0; j < nt; ++j) {
     const int k0 = j * BC;
+    FFPA_M16_KV_STEP(k0)
 
 
     // ================= S^T = K.Q^T =================
@@ -1190,6 +1204,7 @@
 
     FFPA_TSTAMP(4);  // PV loop
     // barrier B: every wave is done reading V(j); K(j+1) has landed and is visible
+    FFPA_M16_KV_STEP_END()
     if (pf_on) {  // (wave-uniform)
       issue_prefetch(k0 + FFPA_M16_PF_DIST * BC);
       dma_wait_except<1>();
@@ -1288,3 +1303,10 @@
     }
 #endif
   }
+#ifdef FFPA_M16_KV_DEFAULT_HOOKS
+#undef FFPA_M16_KV_DEFAULT_HOOKS
+#undef FFPA_M16_KV_STEP_END
+#undef FFPA_M16_KV_STEP
+#undef FFPA_M16_KV_BEGIN
+#undef FFPA_M16_KV_SRC
+#endif

@@ -1,0 +1,30 @@
+// ffpa_paged.h — the paged-KV twin of the packed-sequence kernel: its arguments and the per-head-dim launchers (ffpa_paged_inst.hip, one object per D) the
+// C-ABI dispatches through (ffpa_attn_varlen_paged_fwd, ffpa_capi.hip).  A header of its own so that the dense and packed objects see nothing of it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace ffpa {
+struct FwdArgs;
+struct VarlenArgs;
+
+// Where a sequence's keys live (include/ffpa_attn.h: ffpa_paged_kv): key j of sequence i is row j % page_size of page table[i * bt_stride + j / page_size];
+// page p of K starts p * k_page_stride elements past FwdArgs::k (V likewise), rows and heads inside a page have FwdArgs' row / head strides.
+struct PagedArgs {
+  const int* table;        // [batch][bt_stride] page ids
+  int64_t bt_stride;       // entries between two sequences' rows
+  int64_t k_page_stride;   // elements between two pages of K
+  int64_t v_page_stride;   // ... of V
+  int cap;                 // keys a sequence can hold: pages_per_row * page_size (Nkv_i = min(seqused_k[i], cap))
+  int page_size;           // keys per page: a multiple of the kernel's tile (64)
+  int tiles_per_page;      // page_size / block keys
+  int num_pages;           // pages in the pool: ids are clamped to [0, num_pages)
+};
+
+#define FFPA_DECL(D) int launch_paged_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, hipStream_t stream);
+FFPA_DECL(128) FFPA_DECL(192) FFPA_DECL(256) FFPA_DECL(320) FFPA_DECL(384) FFPA_DECL(448) FFPA_DECL(512)
+FFPA_DECL(576) FFPA_DECL(640) FFPA_DECL(704) FFPA_DECL(768) FFPA_DECL(832) FFPA_DECL(896) FFPA_DECL(960) FFPA_DECL(1024)
+#undef FFPA_DECL
+
+}  // namespace ffpa

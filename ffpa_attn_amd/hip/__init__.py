@@ -31,7 +31,7 @@ _PKG = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_PKG, "libffpa_attn_hip.so")
 TEST_LIB_PATH = os.path.join(_PKG, "libffpa_attn_hip_test.so")  # product kernels + the register-staged SAFE twins (tests only)
 
-ABI_VERSION = 6  # 5: + the packed-sequence entry points (ffpa_attn_varlen_fwd ...); 6: + KV splits inside the packed call
+ABI_VERSION = 7  # 5: + the packed-sequence entry points (ffpa_attn_varlen_fwd ...); 6: + KV splits inside the packed call; 7: + the paged-KV call
 
 # enum ffpa_status (include/ffpa_attn.h)
 _STATUS_EXC = {
@@ -158,6 +158,23 @@ class FfpaVarlenFwdParams(ctypes.Structure):
   ]
 
 
+class FfpaPagedKv(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_paged_kv`` (include/ffpa_attn.h): where the paged call's keys live."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("block_table", ctypes.c_void_p),
+    ("bt_stride", ctypes.c_int64),
+    ("pages_per_row", ctypes.c_int32),
+    ("page_size", ctypes.c_int32),
+    ("num_pages", ctypes.c_int32),
+    ("reserved2", ctypes.c_int32),
+    ("k_page_stride", ctypes.c_int64),
+    ("v_page_stride", ctypes.c_int64),
+  ]
+
+
 _lib = None
 _debug_lib = None
 _lib_lock = threading.Lock()
@@ -173,6 +190,10 @@ EXPORTS = (
   "ffpa_attn_varlen_fwd_plan",
   "ffpa_attn_varlen_fwd_kernel",
   "ffpa_attn_varlen_fwd_workspace_bytes",
+  "ffpa_attn_varlen_paged_fwd",
+  "ffpa_attn_varlen_paged_fwd_plan",
+  "ffpa_attn_varlen_paged_fwd_kernel",
+  "ffpa_attn_varlen_paged_fwd_workspace_bytes",
   "ffpa_attn_query",
   "ffpa_attn_fwd_tile_config",
   "ffpa_attn_last_error",
@@ -221,6 +242,16 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
       lib.ffpa_attn_varlen_fwd_workspace_bytes.restype = ctypes.c_size_t
       lib.ffpa_attn_varlen_fwd_kernel.argtypes = [ctypes.POINTER(FfpaVarlenFwdParams), ctypes.c_char_p, ctypes.c_size_t]
       lib.ffpa_attn_varlen_fwd_kernel.restype = ctypes.c_int
+    if path is None or hasattr(lib, "ffpa_attn_varlen_paged_fwd"):  # (ditto: before the paged-KV call)
+      _pp = [ctypes.POINTER(FfpaVarlenFwdParams), ctypes.POINTER(FfpaPagedKv)]
+      lib.ffpa_attn_varlen_paged_fwd.argtypes = _pp + [ctypes.c_void_p]
+      lib.ffpa_attn_varlen_paged_fwd.restype = ctypes.c_int
+      lib.ffpa_attn_varlen_paged_fwd_plan.argtypes = _pp + [ctypes.POINTER(ctypes.c_int)]
+      lib.ffpa_attn_varlen_paged_fwd_plan.restype = ctypes.c_int
+      lib.ffpa_attn_varlen_paged_fwd_workspace_bytes.argtypes = _pp
+      lib.ffpa_attn_varlen_paged_fwd_workspace_bytes.restype = ctypes.c_size_t
+      lib.ffpa_attn_varlen_paged_fwd_kernel.argtypes = _pp + [ctypes.c_char_p, ctypes.c_size_t]
+      lib.ffpa_attn_varlen_paged_fwd_kernel.restype = ctypes.c_int
     lib.ffpa_attn_query.argtypes = [ctypes.c_int]
     lib.ffpa_attn_query.restype = ctypes.c_int
     lib.ffpa_attn_fwd_tile_config.argtypes = [
@@ -856,7 +887,7 @@ def _varlen_params(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: in
   p.abi_version = ABI_VERSION
   p.q, p.k, p.v, p.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr()
   p.lse = lse.data_ptr() if lse is not None else None
-  p.cu_seqlens_q, p.cu_seqlens_kv = cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr()
+  p.cu_seqlens_q, p.cu_seqlens_kv = cu_seqlens_q.data_ptr(), (cu_seqlens_k.data_ptr() if cu_seqlens_k is not None else None)
   p.seqused_kv = seqused_k.data_ptr() if seqused_k is not None else None
   p.batch = cu_seqlens_q.numel() - 1
   p.heads_q, p.heads_kv, p.head_dim = q.size(1), k.size(1), q.size(2)
@@ -878,21 +909,26 @@ def _varlen_params(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: in
 _VARLEN_SCRATCH: "dict[tuple, int]" = {}
 
 
-def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int) -> int:
+def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaPagedKv | None" = None) -> int:
   if p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC:
     return 0
-  key = (id(lib), device_index, p.dtype, p.batch, p.heads_q, p.heads_kv, p.head_dim, p.max_seqlen_q, p.max_seqlen_kv, p.total_q, p.causal, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS"))
+  key = (id(lib), device_index, p.dtype, p.batch, p.heads_q, p.heads_kv, p.head_dim, p.max_seqlen_q, p.max_seqlen_kv, p.total_q, p.causal, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS"),
+         kv is not None)
   hit = _VARLEN_SCRATCH.get(key)
   if hit is None:
     if len(_VARLEN_SCRATCH) >= 512:
       _VARLEN_SCRATCH.clear()
-    hit = _VARLEN_SCRATCH[key] = int(lib.ffpa_attn_varlen_fwd_workspace_bytes(ctypes.byref(p)))
+    if kv is None:
+      hit = int(lib.ffpa_attn_varlen_fwd_workspace_bytes(ctypes.byref(p)))
+    else:
+      hit = int(lib.ffpa_attn_varlen_paged_fwd_workspace_bytes(ctypes.byref(p), ctypes.byref(kv)))
+    _VARLEN_SCRATCH[key] = hit
   return hit
 
 
 def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor, max_seqlen_q: int,
                    max_seqlen_k: int, causal: bool, softmax_scale: float, *, rescale_threshold: float = -1.0, return_lse: bool = True, flags: int = 0,
-                   plan_out: "dict | None" = None, seqused_k: "torch.Tensor | None" = None, num_splits: int = 0):
+                   plan_out: "dict | None" = None, seqused_k: "torch.Tensor | None" = None, num_splits: int = 0, block_table: "torch.Tensor | None" = None):
   """One launch of the packed-sequence kernel: ``q [T_q, Hq, D]``, ``k`` / ``v [T_k, Hkv, D]``, int32 device ``cu_seqlens_*`` ``[B + 1]`` ->
   ``(o [T_q, Hq, D], lse [Hq, T_q] fp32 | None)``.  Nothing is read back to the host and nothing synchronises: the call captures into a HIP graph.
   Rows without a visible key: O = 0, LSE = -inf.
@@ -904,7 +940,15 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
 
   ``num_splits``: 0 = the library decides (launches that leave most of the chip idle — a decode batch of a few long sequences, a prefill chunk of one long
   prompt with a few heads per GPU — split every row tile's KV range over several workgroups and merge fp32 partials in a second kernel of the same call: equal
-  to the unsplit launch to rounding, not to the bit), 1 = never, n = at most n.  ``FFPA_HIP_DETERMINISTIC=1`` / ``FLAG_DETERMINISTIC``: never."""
+  to the unsplit launch to rounding, not to the bit), 1 = never, n = at most n.  ``FFPA_HIP_DETERMINISTIC=1`` / ``FLAG_DETERMINISTIC``: never.
+
+  ``block_table`` (int32 device ``[B, pages_per_row]``): a PAGED KV cache — ``k`` / ``v`` are page pools ``[num_pages, page_size, Hkv, D]`` (``page_size`` a multiple
+  of 64), key j of sequence i is row ``j % page_size`` of page ``block_table[i, j // page_size]``; ``seqused_k`` is required and gives the lengths (clamped to
+  ``pages_per_row * page_size``), ``cu_seqlens_k`` is ignored (may be None).  One launch of the paged twin of the packed kernel (``ffpa_attn_varlen_paged_fwd``):
+  no gather, nothing read back to the host, graph-capturable; replays follow ``seqused_k`` / ``block_table`` written in place."""
+  if block_table is not None:
+    return _paged_forward(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, causal, softmax_scale,
+                          rescale_threshold=rescale_threshold, return_lse=return_lse, flags=flags, plan_out=plan_out, num_splits=num_splits)
   if not q.is_cuda:
     raise NotImplementedError(f"ffpa_attn::_varlen_fwd_hip has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
@@ -967,11 +1011,101 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
   return o, lse
 
 
+def _paged_kv(block_table: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> FfpaPagedKv:
+  kv = FfpaPagedKv()
+  kv.struct_size = ctypes.sizeof(FfpaPagedKv)
+  kv.block_table = block_table.data_ptr()
+  kv.bt_stride = block_table.stride(0)
+  kv.pages_per_row = block_table.size(1)
+  kv.page_size = k.size(1)
+  kv.num_pages = k.size(0)
+  kv.k_page_stride, kv.v_page_stride = k.stride(0), v.stride(0)
+  return kv
+
+
+def _paged_pool(t: torch.Tensor) -> torch.Tensor:
+  """[num_pages, page_size, H, D] with head-dim stride 1, page / row / head strides multiples of 8 elements, non-overlapping rows, 16-byte aligned — else a copy."""
+  ok = t.stride(-1) == 1 and all(t.stride(i) % 8 == 0 for i in range(3)) and t.data_ptr() % 16 == 0 and t.stride(1) >= t.size(3)
+  return t if ok else t.contiguous()
+
+
+def _paged_forward(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q: int, max_seqlen_k: int, causal: bool, softmax_scale: float, *,
+                   rescale_threshold: float = -1.0, return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
+  name = "ffpa_attn::_paged_fwd_hip"
+  if not q.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
+  lib = load_library()
+  if q.dtype not in _DTYPE or k.dtype != q.dtype or v.dtype != q.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q/k/v of one dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
+  if q.dim() != 3 or k.dim() != 4 or v.dim() != 4:
+    raise ValueError(f"{name}: q must be packed [T, Hq, D] and k / v paged [num_pages, page_size, Hkv, D]")
+  if k.shape != v.shape or k.size(3) != q.size(2):
+    raise ValueError(f"{name}: k {tuple(k.shape)} and v {tuple(v.shape)} must share their shape and q's head dim ({q.size(2)})")
+  if k.size(2) == 0 or q.size(1) % k.size(2) != 0:
+    raise ValueError(f"{name}: query num_heads ({q.size(1)}) must be a multiple of key/value num_heads ({k.size(2)})")
+  if k.size(1) <= 0 or k.size(1) % 64 != 0:
+    raise ValueError(f"{name}: page_size ({k.size(1)}) must be a positive multiple of 64")
+  if cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.device != q.device:
+    raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor of length batch + 1 on q's device")
+  batch = cu_seqlens_q.numel() - 1
+  if seqused_k is None:
+    raise ValueError(f"{name}: seqused_k is required with a block_table (it gives the key lengths)")
+  if seqused_k.dtype != torch.int32 or seqused_k.dim() != 1 or seqused_k.numel() != batch or seqused_k.device != q.device:
+    raise ValueError(f"{name}: seqused_k must be a 1-D int32 tensor of length batch on q's device")
+  if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != batch or block_table.size(1) == 0 or block_table.device != q.device:
+    raise ValueError(f"{name}: block_table must be a 2-D int32 tensor [batch, pages_per_seq] (pages_per_seq >= 1) on q's device")
+  if k.device != q.device or v.device != q.device:
+    raise ValueError(f"{name}: q/k/v must be on one device, got {q.device}, {k.device}, {v.device}")
+  Tq, Hq, D = q.shape
+  Dp = (D + 7) // 8 * 8  # rows must be whole 16-byte slots: only a head dim that is not a multiple of 8 is padded (copies the pools)
+  if Dp != D:
+    pad = (0, Dp - D)
+    q, k, v = (torch.nn.functional.pad(t, pad) for t in (q, k, v))
+  if k.size(0) == 0:
+    # an empty pool: no key anywhere (ids clamp into this one zero page; its rows are never more than a page)
+    k = v = q.new_zeros((1, k.size(1), k.size(2), Dp))
+  q, k, v = _packed_rows(q), _paged_pool(k), _paged_pool(v)
+  if block_table.stride(1) != 1 or block_table.data_ptr() % 4 != 0:
+    block_table = block_table.contiguous()
+  cu_seqlens_q, seqused_k = cu_seqlens_q.contiguous(), seqused_k.contiguous()
+  o = torch.empty((Tq, Hq, Dp), dtype=q.dtype, device=q.device)
+  lse = torch.empty((Hq, Tq), dtype=torch.float32, device=q.device) if return_lse else None
+  if Tq == 0 or max_seqlen_q <= 0:
+    return (o[..., :D] if Dp != D else o), lse
+  # (the packed call's parameters on the pool: k_stride / v_stride = {row, head} inside a page)
+  p = _varlen_params(q, k[0], v[0], o, lse, cu_seqlens_q, None, max_seqlen_q, max_seqlen_k, causal, softmax_scale, rescale_threshold, flags, seqused_k, num_splits)
+  p.k, p.v = k.data_ptr(), v.data_ptr()
+  kv = _paged_kv(block_table, k, v)
+  with torch.cuda.device(q.device):
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    ws_bytes = _varlen_scratch(lib, p, q.device.index or 0, kv)
+    workspace = None
+    if ws_bytes:
+      workspace = _workspace(q.device, stream, ws_bytes)
+      p.workspace = workspace.data_ptr()
+      p.workspace_bytes = ws_bytes
+    if plan_out is not None:
+      plan = (ctypes.c_int * 5)()
+      if lib.ffpa_attn_varlen_paged_fwd_plan(ctypes.byref(p), ctypes.byref(kv), plan) == 0:
+        plan_out.update(row_tiles=plan[0], block_rows=plan[1], block_keys=plan[2], workgroups=plan[3], splits=plan[4])
+      kname = ctypes.create_string_buffer(200)
+      if lib.ffpa_attn_varlen_paged_fwd_kernel(ctypes.byref(p), ctypes.byref(kv), kname, len(kname)) == 0:
+        plan_out["kernel"] = kname.value.decode()
+    rc = lib.ffpa_attn_varlen_paged_fwd(ctypes.byref(p), ctypes.byref(kv), ctypes.c_void_p(stream))
+  if rc != 0:
+    raise _STATUS_EXC.get(rc, RuntimeError)(f"ffpa_attn_varlen_paged_fwd: {lib.ffpa_attn_last_error().decode()} (status {rc})")
+  if Dp != D:
+    o = o[..., :D].contiguous()
+  return o, lse
+
+
 def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: int, max_seqlen_k: int, head_dim: int, *,
-                       dtype: torch.dtype = torch.bfloat16, causal: bool = False, flags: int = 0, total_q: int = 0, num_splits: int = 0) -> dict:
+                       dtype: torch.dtype = torch.bfloat16, causal: bool = False, flags: int = 0, total_q: int = 0, num_splits: int = 0,
+                       page_size: int = 0) -> dict:
   """The packed-sequence launch for a shape class, without launching (placeholder pointers): row tiles per (sequence, head), tile, workgroups, KV ranges per
   sequence, kernel name.  ``total_q`` (rows of q) > 0: the plan of a call that hands the library its scratch (``varlen_forward`` does) — KV splits included;
-  0: the plan without scratch (never split)."""
+  0: the plan without scratch (never split).  ``page_size`` > 0: the paged call's plan (``ffpa_attn_varlen_paged_fwd``, a table of one page per sequence row
+  covering max_seqlen_k)."""
   lib = load_library()
   d8 = (int(head_dim) + 7) // 8 * 8
   p = FfpaVarlenFwdParams()
@@ -992,11 +1126,24 @@ def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: in
   if total_q > 0:
     p.workspace, p.workspace_bytes = 16, 0xFFFFFFFFFFFFFFFF
   plan = (ctypes.c_int * 5)()
-  rc = lib.ffpa_attn_varlen_fwd_plan(ctypes.byref(p), plan)
-  if rc != 0:
-    raise _STATUS_EXC.get(rc, RuntimeError)(lib.ffpa_attn_last_error().decode())
   name = ctypes.create_string_buffer(200)
-  lib.ffpa_attn_varlen_fwd_kernel(ctypes.byref(p), name, len(name))
+  if page_size:
+    p.seqused_kv = 16
+    kv = FfpaPagedKv()
+    kv.struct_size = ctypes.sizeof(FfpaPagedKv)
+    kv.block_table = 16
+    kv.pages_per_row = max(1, -(-int(max_seqlen_k) // int(page_size)))
+    kv.bt_stride, kv.page_size, kv.num_pages = kv.pages_per_row, int(page_size), int(batch) * kv.pages_per_row
+    kv.k_page_stride = kv.v_page_stride = int(page_size) * heads_kv * d8
+    rc = lib.ffpa_attn_varlen_paged_fwd_plan(ctypes.byref(p), ctypes.byref(kv), plan)
+    if rc != 0:
+      raise _STATUS_EXC.get(rc, RuntimeError)(lib.ffpa_attn_last_error().decode())
+    lib.ffpa_attn_varlen_paged_fwd_kernel(ctypes.byref(p), ctypes.byref(kv), name, len(name))
+  else:
+    rc = lib.ffpa_attn_varlen_fwd_plan(ctypes.byref(p), plan)
+    if rc != 0:
+      raise _STATUS_EXC.get(rc, RuntimeError)(lib.ffpa_attn_last_error().decode())
+    lib.ffpa_attn_varlen_fwd_kernel(ctypes.byref(p), name, len(name))
   out = {"row_tiles": plan[0], "block_rows": plan[1], "block_keys": plan[2], "workgroups": plan[3], "kernel": name.value.decode()}
   if total_q > 0:
     out["splits"] = plan[4]
@@ -1018,5 +1165,25 @@ def _varlen_fwd_hip_torch_op(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, 
 
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_varlen_fwd_hip")
 def _varlen_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, softmax_scale, causal, rescale_threshold=-1.0, seqused_k=None):
+  total_q, heads, head_dim = q.shape
+  return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
+
+
+# The paged-KV call (ffpa_attn_with_kvcache(block_table=...)): its own op, so that the packed op's schema stays the reference's
+torch.library.define(
+  f"{_OP_NAMESPACE}::_paged_fwd_hip",
+  "(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor seqused_k, Tensor block_table, int max_seqlen_q, int max_seqlen_k, "
+  "float softmax_scale, int causal, float rescale_threshold=-1.0, int num_splits=0) -> (Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_paged_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _paged_fwd_hip_torch_op(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, softmax_scale, causal, rescale_threshold=-1.0, num_splits=0):
+  return _paged_forward(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, bool(causal), softmax_scale,
+                        rescale_threshold=rescale_threshold, return_lse=True, num_splits=num_splits)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_paged_fwd_hip")
+def _paged_fwd_hip_fake(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, softmax_scale, causal, rescale_threshold=-1.0, num_splits=0):
   total_q, heads, head_dim = q.shape
   return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)

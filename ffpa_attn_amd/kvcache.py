@@ -1,0 +1,133 @@
+"""``ffpa_attn_with_kvcache`` — FlashAttention's ``flash_attn_with_kvcache`` call (its signature and argument order) over a KV cache, contiguous or PAGED.
+
+A serving engine keeps K and V either as one slab of fixed capacity per sequence (``k_cache [B, capacity, Hkv, D]``) or in a pool of fixed-size pages
+(``k_cache [num_pages, page_size, Hkv, D]`` + ``block_table [B, pages_per_seq]``: vLLM, SGLang).  Both run as ONE launch of the packed-sequence kernel with the
+lengths (``cache_seqlens``) read on the device: the contiguous cache through its ``seqused_k`` path (``hip.varlen_forward``), the paged cache through the paged
+twin of that kernel (``ffpa_attn::_paged_fwd_hip`` -> ``ffpa_attn_varlen_paged_fwd``), which reads every K / V tile from its page — no gather into a contiguous
+copy.  Nothing is read back to the host, so a call captures into a HIP graph, and replays follow ``cache_seqlens`` / ``block_table`` written in place.
+
+Inference only: appending new keys (``k`` / ``v``), rotary embedding, ``cache_batch_idx``, ``cache_leftpad``, local windows, softcap and ALiBi have no kernel-side
+implementation here and raise ``NotImplementedError`` naming the option; a tensor that requires grad raises (there is no backward).
+"""
+
+from __future__ import annotations
+
+import torch
+
+_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def _unsupported(k, v, rotary_cos, rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes) -> list[str]:
+  names = []
+  for name, value in (("k", k), ("v", v), ("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin), ("cache_batch_idx", cache_batch_idx),
+                      ("cache_leftpad", cache_leftpad)):
+    if value is not None:
+      names.append(name)
+  if window_size is None or tuple(window_size) != (-1, -1):
+    names.append("window_size")
+  if softcap not in (None, 0, 0.0):
+    names.append("softcap")
+  if alibi_slopes is not None:
+    names.append("alibi_slopes")
+  return names
+
+
+def ffpa_attn_with_kvcache(
+  q: torch.Tensor,
+  k_cache: torch.Tensor,
+  v_cache: torch.Tensor,
+  k: torch.Tensor | None = None,
+  v: torch.Tensor | None = None,
+  rotary_cos: torch.Tensor | None = None,
+  rotary_sin: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor | None" = None,
+  cache_batch_idx: torch.Tensor | None = None,
+  cache_leftpad: torch.Tensor | None = None,
+  block_table: torch.Tensor | None = None,
+  softmax_scale: float | None = None,
+  causal: bool = False,
+  window_size: tuple = (-1, -1),
+  softcap: float = 0.0,
+  rotary_interleaved: bool = True,
+  alibi_slopes: torch.Tensor | None = None,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+):
+  """Attention of ``q [B, Sq, Hq, D]`` against a KV cache: ``k_cache`` / ``v_cache [B, capacity, Hkv, D]`` without ``block_table``, or the page pools
+  ``[num_pages, page_size, Hkv, D]`` with an int32 ``block_table [B, pages_per_seq]`` (``page_size`` a multiple of 64; key j of sequence b is row
+  ``j % page_size`` of page ``block_table[b, j // page_size]``).  ``cache_seqlens``: an int, or an int32 ``[B]`` device tensor, of keys per sequence (None = the
+  whole capacity).  ``causal`` is bottom-right aligned: query i of a sequence of ``Sq`` queries and ``L`` keys sees keys ``j <= i + L - Sq``.  GQA when
+  ``Hq % Hkv == 0``.  ``num_splits``: 0 = the library decides, 1 = never split the keys, n = at most n ranges.  Returns ``out [B, Sq, Hq, D]`` — and the
+  fp32 ``softmax_lse [B, Hq, Sq]`` with ``return_softmax_lse``.  Rows that see no key come out as 0 (LSE -inf)."""
+  bad = _unsupported(k, v, rotary_cos, rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes)
+  if bad:
+    raise NotImplementedError(f"ffpa_attn_with_kvcache does not support: {', '.join(bad)} (attention over an existing cache only; no append, rotary, "
+                              "leftpad, batch index, local window, softcap or ALiBi)")
+  for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"ffpa_attn_with_kvcache: {name} must be a tensor, got {type(t).__name__}")
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"ffpa_attn_with_kvcache is inference only: {name} requires grad and there is no backward")
+  if q.dtype not in _DTYPES or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+    raise TypeError(f"ffpa_attn_with_kvcache only supports fp16/bf16 q/k_cache/v_cache of one dtype, got {q.dtype}, {k_cache.dtype}, {v_cache.dtype}")
+  if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+    raise ValueError("ffpa_attn_with_kvcache: q must be [B, Sq, Hq, D] and k_cache / v_cache 4-D")
+  if k_cache.shape != v_cache.shape:
+    raise ValueError(f"ffpa_attn_with_kvcache: k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} must share their shape")
+  B, Sq, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  if k_cache.size(3) != D:
+    raise ValueError(f"ffpa_attn_with_kvcache: head dim of the cache ({k_cache.size(3)}) differs from q's ({D})")
+  if D % 8 != 0 or D > 1024 or D <= 0:
+    raise ValueError(f"ffpa_attn_with_kvcache: head dim {D} is not a multiple of 8 in [8, 1024]")
+  if Hkv == 0 or Hq % Hkv != 0:
+    raise ValueError(f"ffpa_attn_with_kvcache: query num_heads ({Hq}) must be a multiple of key/value num_heads ({Hkv})")
+  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+    raise ValueError(f"ffpa_attn_with_kvcache: num_splits must be a non-negative int, got {num_splits!r}")
+  if block_table is not None:
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B:
+      raise ValueError(f"ffpa_attn_with_kvcache: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
+    if block_table.size(1) == 0:
+      raise ValueError("ffpa_attn_with_kvcache: block_table needs at least one page per sequence")
+    page_size = k_cache.size(1)
+    if page_size <= 0 or page_size % 64 != 0:
+      raise ValueError(f"ffpa_attn_with_kvcache: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
+    if block_table.device != q.device:
+      raise ValueError(f"ffpa_attn_with_kvcache: block_table must be on q's device, got {block_table.device} and {q.device}")
+    capacity = block_table.size(1) * page_size
+  else:
+    if k_cache.size(0) != B:
+      raise ValueError(f"ffpa_attn_with_kvcache: k_cache [B, capacity, Hkv, D] must have q's batch ({B}), got {k_cache.size(0)}")
+    capacity = k_cache.size(1)
+  if k_cache.device != q.device or v_cache.device != q.device:
+    raise ValueError(f"ffpa_attn_with_kvcache: q / k_cache / v_cache must be on one device, got {q.device}, {k_cache.device}, {v_cache.device}")
+  if cache_seqlens is None:
+    seqused = torch.full((B,), capacity, dtype=torch.int32, device=q.device)
+  elif isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
+    if cache_seqlens < 0:
+      raise ValueError(f"ffpa_attn_with_kvcache: cache_seqlens must be non-negative, got {cache_seqlens}")
+    seqused = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
+  elif isinstance(cache_seqlens, torch.Tensor):
+    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
+      raise ValueError(f"ffpa_attn_with_kvcache: cache_seqlens must be an int or an int32 tensor [batch={B}] on q's device")
+    seqused = cache_seqlens
+  else:
+    raise TypeError(f"ffpa_attn_with_kvcache: cache_seqlens must be an int or an int32 tensor, got {type(cache_seqlens).__name__}")
+  scale = float(softmax_scale) if softmax_scale is not None else D ** -0.5
+
+  from . import hip  # (registers the ffpa_attn ops)
+
+  qp = q.reshape(B * Sq, Hq, D)
+  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device) if Sq > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
+  if block_table is not None:
+    o, lse = torch.ops.ffpa_attn._paged_fwd_hip(qp, k_cache, v_cache, cu_q, seqused, block_table, Sq, capacity, scale, 1 if causal else 0, -1.0, num_splits)
+  else:
+    # the contiguous cache is the packed call's seqused_k case: sequence b's keys are rows b * capacity ... of the cache viewed as [B * capacity, Hkv, D]
+    kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
+    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
+    o, lse = hip.varlen_forward(qp, kp, vp, cu_q, cu_k, Sq, capacity, bool(causal), scale, return_lse=return_softmax_lse, seqused_k=seqused,
+                                num_splits=num_splits)
+  out = o.view(B, Sq, Hq, D)
+  if not return_softmax_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define FFPA_ATTN_ABI_VERSION 6 /* 5: + the packed-sequence entry points (ffpa_attn_varlen_fwd ...); 6: + KV splits inside the packed call (its workspace fields, ffpa_attn_varlen_fwd_workspace_bytes, plan out[4]) */
+#define FFPA_ATTN_ABI_VERSION 7 /* 5: + the packed-sequence entry points (ffpa_attn_varlen_fwd ...); 6: + KV splits inside the packed call (its workspace fields, ffpa_attn_varlen_fwd_workspace_bytes, plan out[4]); 7: + the paged-KV call (ffpa_paged_kv, ffpa_attn_varlen_paged_fwd ...) */
 
 /* status codes (0 == success).  The Python host maps them onto the exception
  * classes the reference raises (TORCH_CHECK -> RuntimeError,
@@ -313,6 +313,37 @@ int ffpa_attn_varlen_fwd_plan(const ffpa_varlen_fwd_params* params, int out[5]);
 
 /* The kernel it runs, as text ("ffpa_fwd_m16_varlen_kernel<bf16, 512>").  Returns an ffpa_status. */
 int ffpa_attn_varlen_fwd_kernel(const ffpa_varlen_fwd_params* params, char* buf, size_t n);
+
+/*
+ * PAGED KV CACHE (ABI 7) — vLLM / SGLang / FlashAttention's flash_attn_with_kvcache(..., block_table=...): K and V live in a pool of fixed-size pages, and
+ * every sequence has a row of page ids.  The packed call above with these changes:
+ *   p->k / p->v are the page pools: page p of K starts at k + p * k_page_stride elements (V likewise); inside a page, rows and heads have p->k_stride /
+ *        p->v_stride = {row, head}.  Key j of sequence i is row j % page_size of page block_table[i * bt_stride + j / page_size].
+ *   p->seqused_kv is REQUIRED: sequence i has Nkv_i = min(seqused_kv[i], pages_per_row * page_size) keys.
+ *   p->cu_seqlens_kv may be NULL and is ignored; p->max_seqlen_kv stays a launch-side hint (>= the longest Nkv_i).
+ * page_size must be a multiple of 64: the paged kernel's tiles hold 64 keys (32 at D > 512), so a tile never straddles two pages.  Page ids are clamped to
+ * [0, num_pages) on the device (a bad table gives a wrong answer, not a fault); entries past a sequence's last used page are never read.  Same bits as the
+ * packed call on the gathered keys wherever the tile is the same (every head dim but 256 / 320, where the packed call takes 128-key tiles).
+ */
+typedef struct ffpa_paged_kv {
+  uint32_t struct_size;        /* sizeof(ffpa_paged_kv), checked */
+  uint32_t reserved;           /* 0 */
+  const int32_t* block_table;  /* device, [batch][bt_stride]: sequence i's page ids in key order */
+  int64_t bt_stride;           /* elements between two sequences' rows (>= pages_per_row) */
+  int32_t pages_per_row;       /* usable entries per row: Nkv_i is clamped to pages_per_row * page_size */
+  int32_t page_size;           /* keys per page: a multiple of 64 */
+  int32_t num_pages;           /* pages in the pool (ids are clamped to it) */
+  int32_t reserved2;
+  int64_t k_page_stride, v_page_stride; /* elements between two pages; multiples of 8 */
+} ffpa_paged_kv;
+
+/* Launch the paged forward on `stream` of the CURRENT device.  Asynchronous; returns an ffpa_status. */
+int ffpa_attn_varlen_paged_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream);
+
+/* As ffpa_attn_varlen_fwd_workspace_bytes / _plan / _kernel, for the paged call ("ffpa_fwd_m16_paged_kernel<bf16, 512>"). */
+size_t ffpa_attn_varlen_paged_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv);
+int ffpa_attn_varlen_paged_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, int out[5]);
+int ffpa_attn_varlen_paged_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, char* buf, size_t n);
 
 /* Capability / build queries.  Replaces the module attributes
  * CUDA_FWD_AVAILABLE, F16_ACC_AVAILABLE, ... (csrc/cuffpa/ffpa_api.cc:283-305). */
