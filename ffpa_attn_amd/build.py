@@ -102,7 +102,7 @@ def _prune_temps() -> None:
   import glob
   import gzip
 
-  for tdir in glob.glob(os.path.join(OBJ_DIR, "temps_d*")):
+  for tdir in glob.glob(os.path.join(OBJ_DIR, "temps_d*")) + glob.glob(os.path.join(OBJ_DIR, "temps_append")):
     for path in glob.glob(os.path.join(tdir, "*")):
       if path.endswith("gfx950.s"):
         with open(path, "rb") as src, gzip.open(path + ".gz", "wb", compresslevel=6) as dst:
@@ -190,6 +190,16 @@ def build(force: bool = False, jobs: int | None = None, save_temps: bool = True,
       tmp = os.path.join(OBJ_DIR, f"temps_d{d}")
       os.makedirs(tmp, exist_ok=True)
       tasks.append((obj, [hipcc, *CXXFLAGS, *product, *extra, f"-DFFPA_INST_D={d}", "-c", os.path.join(CSRC, "ffpa_paged_inst.hip"), "-o", obj], tmp))
+  # the KV-cache append + rotary launch (ffpa_kvcache_append.hip): one small TU, every dtype / rotary form; its assembly lands in temps_append (the attention
+  # ISA rules read temps_d<D> only: this kernel has no inline asm)
+  append = os.path.join(OBJ_DIR, "ffpa_kvcache_append.o")
+  objs.append(append)
+  if test_lib:
+    test_objs.append(append)
+  if stale(append):
+    tmp = os.path.join(OBJ_DIR, "temps_append")
+    os.makedirs(tmp, exist_ok=True)
+    tasks.append((append, [hipcc, *CXXFLAGS, *product, *extra, "-c", os.path.join(CSRC, "ffpa_kvcache_append.hip"), "-o", append], tmp))
   capi = os.path.join(OBJ_DIR, "ffpa_capi.o")
   objs.append(capi)
   if stale(capi):
@@ -242,8 +252,10 @@ def build_variant(tag: str, defs: list[str], jobs: int | None = None, head_dims:
     missing = [d for d in HEAD_DIMS if d not in head_dims and not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_fwd_d{d}.o"))]
     missing += [d for d in VARLEN_HEAD_DIMS if not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_varlen_d{d}.o"))]
     missing += [d for d in VARLEN_HEAD_DIMS if not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_paged_d{d}.o"))]
+    missing += [] if os.path.exists(os.path.join(OBJ_DIR, "ffpa_kvcache_append.o")) else ["kvcache_append"]
     build(force=bool(missing), verbose=False)
-  elif any(not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_{k}_d{d}.o")) for d in VARLEN_HEAD_DIMS for k in ("varlen", "paged")):
+  elif any(not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_{k}_d{d}.o")) for d in VARLEN_HEAD_DIMS for k in ("varlen", "paged")) or \
+      not os.path.exists(os.path.join(OBJ_DIR, "ffpa_kvcache_append.o")):
     build(force=True, verbose=False)
   tasks, objs = [], []
   for d in HEAD_DIMS:
@@ -255,6 +267,7 @@ def build_variant(tag: str, defs: list[str], jobs: int | None = None, head_dims:
     tasks.append([hipcc, *CXXFLAGS, *defs, f"-DFFPA_INST_D={d}", "-c", os.path.join(CSRC, "ffpa_fwd_inst.hip"), "-o", obj])
   objs += [os.path.join(OBJ_DIR, f"ffpa_varlen_d{d}.o") for d in VARLEN_HEAD_DIMS]  # (the packed-sequence kernels: the main build's, never a variant's)
   objs += [os.path.join(OBJ_DIR, f"ffpa_paged_d{d}.o") for d in VARLEN_HEAD_DIMS]  # (and their paged twins)
+  objs.append(os.path.join(OBJ_DIR, "ffpa_kvcache_append.o"))  # (and the KV-cache append)
   capi = os.path.join(odir, "ffpa_capi.o")
   objs.append(capi)
   tasks.append([hipcc, *CXXFLAGS, *defs, "-c", os.path.join(CSRC, "ffpa_capi.hip"), "-o", capi])  # (the plan must see the same tunables as the kernels)

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 
 #include "ffpa_attn.h"
@@ -20,6 +21,7 @@
 #include "ffpa_varlen_merge.h"   // (stage 2 of a KV-split packed-sequence launch)
 #include "ffpa_launch.h"
 #include "ffpa_paged.h"         // (the paged-KV twin of the packed-sequence kernel)
+#include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
 
 namespace {
 
@@ -1072,13 +1074,11 @@ int check_strides2(const char* name, const int64_t s[2]) {
   return FFPA_OK;
 }
 
-// The paged call's own arguments (ffpa_paged_kv), checked behind the packed call's plan and before anything touches the device.
-int check_paged(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv) {
-  if (kv == nullptr) return fail(FFPA_ERR_NULL_POINTER, "paged kv is NULL");
+// A page pool (ffpa_paged_kv): the paged attention call's and the KV-cache append's
+int check_pool(const ffpa_paged_kv* kv) {
   if (kv->struct_size != sizeof(ffpa_paged_kv))
     return fail(FFPA_ERR_BAD_ABI, "ffpa_paged_kv ABI mismatch: size %u (want %zu)", kv->struct_size, sizeof(ffpa_paged_kv));
   if (kv->block_table == nullptr) return fail(FFPA_ERR_NULL_POINTER, "block_table must be non-NULL");
-  if (p->seqused_kv == nullptr) return fail(FFPA_ERR_NULL_POINTER, "seqused_kv must be non-NULL: it gives the paged call's key lengths");
   if (reinterpret_cast<uintptr_t>(kv->block_table) & 3u) return fail(FFPA_ERR_MISALIGNED, "block_table must be 4-byte aligned");
   if (kv->page_size <= 0 || kv->page_size % 64 != 0) return fail(FFPA_ERR_BAD_SHAPE, "page_size=%d is not a positive multiple of 64", kv->page_size);
   if (kv->pages_per_row <= 0 || kv->num_pages <= 0)
@@ -1092,6 +1092,15 @@ int check_paged(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv) {
     if (st % 8 != 0) return fail(FFPA_ERR_BAD_STRIDE, "page stride %lld is not a multiple of 8 elements (16 bytes)", (long long)st);
   }
   return FFPA_OK;
+}
+
+// The paged call's own arguments (ffpa_paged_kv), checked behind the packed call's plan and before anything touches the device.
+int check_paged(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv) {
+  if (kv == nullptr) return fail(FFPA_ERR_NULL_POINTER, "paged kv is NULL");
+  // (the order of the checks is the paged call's: struct size, block_table, seqused_kv, then the rest of the pool)
+  if (kv->struct_size == sizeof(ffpa_paged_kv) && kv->block_table != nullptr && p->seqused_kv == nullptr)
+    return fail(FFPA_ERR_NULL_POINTER, "seqused_kv must be non-NULL: it gives the paged call's key lengths");
+  return check_pool(kv);
 }
 
 // The packed call and its paged twin (kv != NULL: k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read)
@@ -1310,6 +1319,98 @@ int ffpa_attn_varlen_paged_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffp
   if (rc != FFPA_OK) return rc;
   if ((rc = check_paged(p, kv)) != FFPA_OK) return rc;
   return kernel_name(p, pl, true, buf, n);
+}
+
+// ---- the KV-cache append + rotary (include/ffpa_attn.h: ffpa_kv_append_params)
+namespace {
+
+int check_strides3(const char* name, const int64_t s[3]) {
+  for (int i = 0; i < 3; ++i) {
+    if (s[i] < 0) return fail(FFPA_ERR_BAD_STRIDE, "%s stride[%d]=%lld is negative", name, i, (long long)s[i]);
+    if (s[i] % 8 != 0) return fail(FFPA_ERR_BAD_STRIDE, "%s stride[%d]=%lld is not a multiple of 8 elements (16 bytes)", name, i, (long long)s[i]);
+  }
+  return FFPA_OK;
+}
+
+}  // namespace
+
+int ffpa_attn_kvcache_append(const ffpa_kv_append_params* p, const ffpa_paged_kv* kv, void* stream) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_kv_append_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_kv_append_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size, sizeof(ffpa_kv_append_params),
+                p->abi_version, FFPA_ATTN_ABI_VERSION);
+  if (p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
+  if (p->batch <= 0 || p->heads_q <= 0 || p->heads_kv <= 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "non-positive dimension: batch=%d Hq=%d Hkv=%d", p->batch, p->heads_q, p->heads_kv);
+  if (p->heads_q % p->heads_kv != 0) return fail(FFPA_ERR_BAD_SHAPE, "num_heads: Hq=%d is not a multiple of Hkv=%d", p->heads_q, p->heads_kv);
+  if (p->head_dim <= 0 || p->head_dim % 8 != 0 || p->head_dim > 1024)
+    return fail(FFPA_ERR_BAD_HEADDIM, "headdim not support! D=%d (supported: multiples of 8 in [8, 1024])", p->head_dim);
+  if (p->seqlen_q < 0 || p->seqlen_new < 0) return fail(FFPA_ERR_BAD_SHAPE, "seqlen_q=%d / seqlen_new=%d must not be negative", p->seqlen_q, p->seqlen_new);
+  int rc;
+  int cap = p->capacity;
+  if (kv != nullptr) {
+    if ((rc = check_pool(kv)) != FFPA_OK) return rc;
+    cap = kv->pages_per_row * kv->page_size;
+  } else if (cap <= 0) {
+    return fail(FFPA_ERR_BAD_SHAPE, "capacity=%d of the contiguous cache must be positive", cap);
+  }
+  const int rd = p->rotary_dim;
+  if (rd < 0 || rd % 16 != 0 || rd > p->head_dim)
+    return fail(FFPA_ERR_BAD_SHAPE, "rotary_dim=%d must be a multiple of 16 in [0, head_dim=%d]", rd, p->head_dim);
+  if (rd > 0 && p->seqlen_ro < cap) return fail(FFPA_ERR_BAD_SHAPE, "seqlen_ro=%d rows of rotary_cos / rotary_sin is less than the capacity %d", p->seqlen_ro, cap);
+  const bool use_q = rd > 0 && p->seqlen_q > 0, use_kv = p->seqlen_new > 0;
+  const bool use_rot = rd > 0 && (use_q || use_kv);  // (the tables are read for every rotated q row AND every appended K row)
+  if (!p->k_cache || !p->v_cache || !p->seqused || !p->cache_seqlens)
+    return fail(FFPA_ERR_NULL_POINTER, "k_cache / v_cache / seqused / cache_seqlens must be non-NULL");
+  if (use_kv && (!p->k || !p->v)) return fail(FFPA_ERR_NULL_POINTER, "k / v must be non-NULL when seqlen_new > 0");
+  if (use_rot && (!p->rotary_cos || !p->rotary_sin))
+    return fail(FFPA_ERR_NULL_POINTER, "rotary_cos / rotary_sin must be non-NULL when rotary_dim > 0");
+  if (use_q && (!p->q || !p->q_rot)) return fail(FFPA_ERR_NULL_POINTER, "q / q_rot must be non-NULL when rotary_dim > 0 and seqlen_q > 0");
+  if (p->seqused == p->cache_seqlens) return fail(FFPA_ERR_BAD_SHAPE, "seqused must not be cache_seqlens (the kernel reads one while it writes the other)");
+  if ((reinterpret_cast<uintptr_t>(p->seqused) & 3u) || (reinterpret_cast<uintptr_t>(p->cache_seqlens) & 3u))
+    return fail(FFPA_ERR_MISALIGNED, "seqused / cache_seqlens must be 4-byte aligned");
+  if (!aligned16(p->k_cache) || !aligned16(p->v_cache) || (use_kv && (!aligned16(p->k) || !aligned16(p->v))) ||
+      (use_q && (!aligned16(p->q) || !aligned16(p->q_rot))) || (use_rot && (!aligned16(p->rotary_cos) || !aligned16(p->rotary_sin))))
+    return fail(FFPA_ERR_MISALIGNED, "q / k / v / caches / q_rot / rotary_cos / rotary_sin base pointers must be 16-byte aligned");
+  if ((rc = check_strides3("k_cache", p->k_cache_stride)) || (rc = check_strides3("v_cache", p->v_cache_stride))) return rc;
+  if (use_kv && ((rc = check_strides3("k", p->k_stride)) || (rc = check_strides3("v", p->v_stride)))) return rc;
+  if (use_q && ((rc = check_strides3("q", p->q_stride)) || (rc = check_strides3("q_rot", p->q_rot_stride)))) return rc;
+  const int rows = std::max(1, std::max(p->seqlen_new, rd > 0 ? p->seqlen_q : 0));
+  if ((int64_t)p->batch * rows > 0x7fffffffLL) return fail(FFPA_ERR_BAD_SHAPE, "grid of %lld token rows is too large", (long long)p->batch * rows);
+  if ((rc = check_device()) != FFPA_OK) return rc;
+
+  ffpa::KvAppendArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = p->q, a.k = p->k, a.v = p->v;
+  a.kc = p->k_cache, a.vc = p->v_cache, a.q_rot = p->q_rot;
+  a.used = p->seqused, a.seqlens = p->cache_seqlens;
+  a.cos = p->rotary_cos, a.sin = p->rotary_sin;
+  for (int i = 0; i < 3; ++i) a.sq[i] = p->q_stride[i], a.sk[i] = p->k_stride[i], a.sv[i] = p->v_stride[i], a.sqr[i] = p->q_rot_stride[i];
+  a.skc[0] = p->k_cache_stride[1], a.skc[1] = p->k_cache_stride[2];
+  a.svc[0] = p->v_cache_stride[1], a.svc[1] = p->v_cache_stride[2];
+  if (kv != nullptr) {
+    a.table = kv->block_table, a.bt_stride = kv->bt_stride;
+    a.kc_page_stride = kv->k_page_stride, a.vc_page_stride = kv->v_page_stride;
+    a.page_size = kv->page_size, a.num_pages = kv->num_pages;
+  } else {
+    // one page per sequence: the slab of sequence b
+    a.kc_page_stride = p->k_cache_stride[0], a.vc_page_stride = p->v_cache_stride[0];
+    a.page_size = cap, a.num_pages = p->batch;
+  }
+  a.B = p->batch, a.Hq = p->heads_q, a.Hkv = p->heads_kv, a.D = p->head_dim, a.Sq = p->seqlen_q, a.Snew = p->seqlen_new;
+  a.cap = cap, a.seqlen_ro = p->seqlen_ro, a.rd = rd, a.causal = p->causal ? 1 : 0, a.T = rows;
+  const bool interleaved = rd == 0 || p->rotary_interleaved != 0;
+  a.units = interleaved ? p->head_dim / 8 : rd / 16 + (p->head_dim - rd) / 8;
+  a.slots = 256 / a.units;
+  const int heads = rd > 0 ? std::max(p->heads_q, p->heads_kv) : p->heads_kv;
+  // workgroups per token row: as few as let a lane walk kAppendHeadsPerLane heads with one set of cos / sin registers — but a decode batch has few token
+  // rows (32 x 1 token: 32 workgroups on 256 CUs at D = 512), so spread the heads over up to one per lane until the grid covers the CUs
+  const int per_wg = a.slots * ffpa::kAppendHeadsPerLane;
+  const int64_t fill = ((int64_t)device_cu_count() + (int64_t)p->batch * rows - 1) / ((int64_t)p->batch * rows);
+  const int grid_y = std::max((heads + per_wg - 1) / per_wg, (int)std::min<int64_t>((heads + a.slots - 1) / a.slots, fill));
+  const int st = ffpa::launch_kv_append(p->dtype, interleaved, a, (unsigned)grid_y, static_cast<hipStream_t>(stream));
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "kv append launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
 }
 
 int ffpa_attn_query(int what) {

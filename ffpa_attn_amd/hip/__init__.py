@@ -175,6 +175,43 @@ class FfpaPagedKv(ctypes.Structure):
   ]
 
 
+class FfpaKvAppendParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_kv_append_params`` (include/ffpa_attn.h): the KV-cache append + rotary call."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("abi_version", ctypes.c_uint32),
+    ("q", ctypes.c_void_p),
+    ("k", ctypes.c_void_p),
+    ("v", ctypes.c_void_p),
+    ("k_cache", ctypes.c_void_p),
+    ("v_cache", ctypes.c_void_p),
+    ("q_rot", ctypes.c_void_p),
+    ("seqused", ctypes.c_void_p),
+    ("cache_seqlens", ctypes.c_void_p),
+    ("rotary_cos", ctypes.c_void_p),
+    ("rotary_sin", ctypes.c_void_p),
+    ("batch", ctypes.c_int32),
+    ("heads_q", ctypes.c_int32),
+    ("heads_kv", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("seqlen_q", ctypes.c_int32),
+    ("seqlen_new", ctypes.c_int32),
+    ("capacity", ctypes.c_int32),
+    ("seqlen_ro", ctypes.c_int32),
+    ("q_stride", ctypes.c_int64 * 3),
+    ("k_stride", ctypes.c_int64 * 3),
+    ("v_stride", ctypes.c_int64 * 3),
+    ("q_rot_stride", ctypes.c_int64 * 3),
+    ("k_cache_stride", ctypes.c_int64 * 3),
+    ("v_cache_stride", ctypes.c_int64 * 3),
+    ("rotary_dim", ctypes.c_int32),
+    ("rotary_interleaved", ctypes.c_int32),
+    ("causal", ctypes.c_int32),
+    ("dtype", ctypes.c_int32),
+  ]
+
+
 _lib = None
 _debug_lib = None
 _lib_lock = threading.Lock()
@@ -194,6 +231,7 @@ EXPORTS = (
   "ffpa_attn_varlen_paged_fwd_plan",
   "ffpa_attn_varlen_paged_fwd_kernel",
   "ffpa_attn_varlen_paged_fwd_workspace_bytes",
+  "ffpa_attn_kvcache_append",
   "ffpa_attn_query",
   "ffpa_attn_fwd_tile_config",
   "ffpa_attn_last_error",
@@ -252,6 +290,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
       lib.ffpa_attn_varlen_paged_fwd_workspace_bytes.restype = ctypes.c_size_t
       lib.ffpa_attn_varlen_paged_fwd_kernel.argtypes = _pp + [ctypes.c_char_p, ctypes.c_size_t]
       lib.ffpa_attn_varlen_paged_fwd_kernel.restype = ctypes.c_int
+    if path is None or hasattr(lib, "ffpa_attn_kvcache_append"):  # (ditto: before the KV-cache append)
+      lib.ffpa_attn_kvcache_append.argtypes = [ctypes.POINTER(FfpaKvAppendParams), ctypes.POINTER(FfpaPagedKv), ctypes.c_void_p]
+      lib.ffpa_attn_kvcache_append.restype = ctypes.c_int
     lib.ffpa_attn_query.argtypes = [ctypes.c_int]
     lib.ffpa_attn_query.restype = ctypes.c_int
     lib.ffpa_attn_fwd_tile_config.argtypes = [
@@ -1187,3 +1228,94 @@ def _paged_fwd_hip_torch_op(q, k, v, cu_seqlens_q, seqused_k, block_table, max_s
 def _paged_fwd_hip_fake(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, softmax_scale, causal, rescale_threshold=-1.0, num_splits=0):
   total_q, heads, head_dim = q.shape
   return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
+
+
+# The KV-cache append + rotary (ffpa_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)): the prepare launch in front of the attention launch
+def _rows16(t: torch.Tensor) -> bool:
+  """head-dim stride 1, every other stride a multiple of 8 elements, a 16-byte aligned base: what the append kernel's 16-byte loads and stores need"""
+  return t.stride(-1) == 1 and all(st % 8 == 0 for st in t.stride()[:-1]) and t.data_ptr() % 16 == 0
+
+
+def kvcache_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: "torch.Tensor | None", v: "torch.Tensor | None", cache_seqlens: torch.Tensor,
+                   block_table: "torch.Tensor | None" = None, rotary_cos: "torch.Tensor | None" = None, rotary_sin: "torch.Tensor | None" = None,
+                   rotary_interleaved: bool = True, causal: bool = False):
+  """One launch of ``ffpa_attn_kvcache_append``: ``k`` / ``v [B, Snew, Hkv, D]`` written into the caches in place at ``cache_seqlens[b] + i`` (``k`` rotated when
+  ``rotary_cos`` / ``rotary_sin [seqlen_ro, rotary_dim / 2]`` are given), -> ``(q_rot, seqused)``: ``q [B, Sq, Hq, D]`` rotated (an empty tensor without rotary) and
+  the int32 ``[B]`` post-append lengths ``min(max(cache_seqlens, 0) + Snew, capacity)``.  Contiguous caches ``[B, capacity, Hkv, D]``, or page pools
+  ``[num_pages, page_size, Hkv, D]`` with ``block_table``.  Asynchronous, nothing read back to the host."""
+  name = "ffpa_attn::_kvcache_append_hip"
+  if not q.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
+  lib = load_library()
+  B, Sq, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  rot = rotary_cos is not None
+  q_rot = torch.empty((B, Sq, Hq, D) if rot else (0,), dtype=q.dtype, device=q.device)
+  seqused = torch.empty((B,), dtype=torch.int32, device=q.device)
+  if B == 0:
+    return q_rot, seqused
+  for nm, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+    if not _rows16(t):
+      raise ValueError(f"{name}: {nm} is written in place and needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base")
+  if k is None:
+    k = v = q.new_empty((B, 0, Hkv, D))
+  k = k if _rows16(k) else k.contiguous()
+  v = v if _rows16(v) else v.contiguous()
+  if rot and not _rows16(q):
+    q = q.contiguous()
+  cache_seqlens = cache_seqlens.contiguous()
+  p = FfpaKvAppendParams()
+  p.struct_size = ctypes.sizeof(FfpaKvAppendParams)
+  p.abi_version = ABI_VERSION
+  p.k_cache, p.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
+  p.seqused, p.cache_seqlens = seqused.data_ptr(), cache_seqlens.data_ptr()
+  p.batch, p.heads_q, p.heads_kv, p.head_dim = B, Hq, Hkv, D
+  p.seqlen_q, p.seqlen_new = Sq, k.size(1)
+  p.k_cache_stride[:] = list(k_cache.stride()[:3])
+  p.v_cache_stride[:] = list(v_cache.stride()[:3])
+  if k.size(1) > 0:
+    p.k, p.v = k.data_ptr(), v.data_ptr()
+    p.k_stride[:] = list(k.stride()[:3])
+    p.v_stride[:] = list(v.stride()[:3])
+  if rot:
+    p.q, p.q_rot = q.data_ptr(), q_rot.data_ptr()
+    p.q_stride[:] = list(q.stride()[:3])
+    p.q_rot_stride[:] = list(q_rot.stride()[:3])
+    p.rotary_cos, p.rotary_sin = rotary_cos.data_ptr(), rotary_sin.data_ptr()
+    p.seqlen_ro = rotary_cos.size(0)
+    p.rotary_dim = 2 * rotary_cos.size(1)
+    p.rotary_interleaved = 1 if rotary_interleaved else 0
+  p.causal = 1 if causal else 0
+  p.dtype = _DTYPE[q.dtype]
+  kv = None
+  if block_table is not None:
+    if block_table.stride(1) != 1 or block_table.data_ptr() % 4 != 0:
+      block_table = block_table.contiguous()
+    kv = _paged_kv(block_table, k_cache, v_cache)
+  else:
+    p.capacity = k_cache.size(1)
+  with torch.cuda.device(q.device):
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    rc = lib.ffpa_attn_kvcache_append(ctypes.byref(p), ctypes.byref(kv) if kv is not None else None, ctypes.c_void_p(stream))
+  if rc != 0:
+    raise _STATUS_EXC.get(rc, RuntimeError)(f"ffpa_attn_kvcache_append: {lib.ffpa_attn_last_error().decode()} (status {rc})")
+  return q_rot, seqused
+
+
+# k_cache / v_cache are written in place: the schema says so (Tensor(a!) / Tensor(b!)), so that functionalization and torch.compile see the writes
+torch.library.define(
+  f"{_OP_NAMESPACE}::_kvcache_append_hip",
+  "(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k, Tensor? v, Tensor cache_seqlens, Tensor? block_table, Tensor? rotary_cos, "
+  "Tensor? rotary_sin, bool rotary_interleaved, bool causal) -> (Tensor q_rot, Tensor seqused)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_kvcache_append_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _kvcache_append_hip_torch_op(q, k_cache, v_cache, k, v, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, causal):
+  return kvcache_append(q, k_cache, v_cache, k, v, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, causal)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_kvcache_append_hip")
+def _kvcache_append_hip_fake(q, k_cache, v_cache, k, v, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, causal):
+  q_rot = q.new_empty(tuple(q.shape) if rotary_cos is not None else (0,))
+  return q_rot, q.new_empty((q.size(0),), dtype=torch.int32)

@@ -6,8 +6,14 @@ lengths (``cache_seqlens``) read on the device: the contiguous cache through its
 twin of that kernel (``ffpa_attn::_paged_fwd_hip`` -> ``ffpa_attn_varlen_paged_fwd``), which reads every K / V tile from its page — no gather into a contiguous
 copy.  Nothing is read back to the host, so a call captures into a HIP graph, and replays follow ``cache_seqlens`` / ``block_table`` written in place.
 
-Inference only: appending new keys (``k`` / ``v``), rotary embedding, ``cache_batch_idx``, ``cache_leftpad``, local windows, softcap and ALiBi have no kernel-side
-implementation here and raise ``NotImplementedError`` naming the option; a tensor that requires grad raises (there is no backward).
+With ``k`` / ``v`` (and optionally ``rotary_cos`` / ``rotary_sin``) the step's new keys are appended first, FlashAttention's decode call: ONE more launch on the
+same stream in front of the attention launch (``ffpa_attn::_kvcache_append_hip`` -> ``ffpa_attn_kvcache_append``) writes key i of sequence b in place at
+position ``cache_seqlens[b] + i`` (K rotated), the rotated copy of q, and the lengths ``cache_seqlens + Snew`` the attention launch reads.  Still no host
+synchronisation: the two launches capture into one HIP graph.  ``cache_seqlens`` itself is not advanced (the caller does that, as with FlashAttention).
+
+Inference only: ``cache_batch_idx``, ``cache_leftpad``, local windows, softcap and ALiBi have no kernel-side implementation here and raise
+``NotImplementedError`` naming the option — as do ``k`` without ``v`` (or ``v`` without ``k``) and rotary tables without ``k`` / ``v`` or one without the other;
+a tensor that requires grad raises (there is no backward).
 """
 
 from __future__ import annotations
@@ -19,9 +25,11 @@ _DTYPES = (torch.float16, torch.bfloat16)
 
 def _unsupported(k, v, rotary_cos, rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes) -> list[str]:
   names = []
-  for name, value in (("k", k), ("v", v), ("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin), ("cache_batch_idx", cache_batch_idx),
-                      ("cache_leftpad", cache_leftpad)):
-    if value is not None:
+  append = k is not None and v is not None
+  rotary = rotary_cos is not None and rotary_sin is not None
+  for name, value, ok in (("k", k, append), ("v", v, append), ("rotary_cos", rotary_cos, rotary and append), ("rotary_sin", rotary_sin, rotary and append),
+                          ("cache_batch_idx", cache_batch_idx, False), ("cache_leftpad", cache_leftpad, False)):
+    if value is not None and not ok:
       names.append(name)
   if window_size is None or tuple(window_size) != (-1, -1):
     names.append("window_size")
@@ -30,6 +38,45 @@ def _unsupported(k, v, rotary_cos, rotary_sin, cache_batch_idx, cache_leftpad, w
   if alibi_slopes is not None:
     names.append("alibi_slopes")
   return names
+
+
+def _check_append(q, k_cache, k, v, rotary_cos, rotary_sin, capacity: int) -> None:
+  """Host-side checks of the new keys and the rotary tables (shapes, dtypes, devices: nothing read from the device)."""
+  B, Sq, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  for name, t in (("k", k), ("v", v)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"ffpa_attn_with_kvcache: {name} must be a tensor, got {type(t).__name__}")
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"ffpa_attn_with_kvcache is inference only: {name} requires grad and there is no backward")
+    if t.dtype != q.dtype:
+      raise TypeError(f"ffpa_attn_with_kvcache: {name} must have the cache's dtype {q.dtype}, got {t.dtype}")
+    if t.device != q.device:
+      raise ValueError(f"ffpa_attn_with_kvcache: {name} must be on q's device, got {t.device} and {q.device}")
+    if t.dim() != 4 or t.size(0) != B or t.size(2) != Hkv or t.size(3) != D:
+      raise ValueError(f"ffpa_attn_with_kvcache: {name} must be [B={B}, Snew, Hkv={Hkv}, D={D}], got {tuple(t.shape)}")
+    if t.stride(-1) != 1:
+      raise ValueError(f"ffpa_attn_with_kvcache: {name} must have a contiguous last dimension")
+  if k.shape != v.shape:
+    raise ValueError(f"ffpa_attn_with_kvcache: k {tuple(k.shape)} and v {tuple(v.shape)} must share their shape")
+  if rotary_cos is None:
+    return
+  for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"ffpa_attn_with_kvcache: {name} must be a tensor, got {type(t).__name__}")
+    if t.dtype != q.dtype:
+      raise TypeError(f"ffpa_attn_with_kvcache: {name} must have q's dtype {q.dtype}, got {t.dtype}")
+    if t.device != q.device:
+      raise ValueError(f"ffpa_attn_with_kvcache: {name} must be on q's device, got {t.device} and {q.device}")
+    if t.dim() != 2 or not t.is_contiguous():
+      raise ValueError(f"ffpa_attn_with_kvcache: {name} must be a contiguous [seqlen_ro, rotary_dim / 2] tensor, got {tuple(t.shape)}")
+  if rotary_cos.shape != rotary_sin.shape:
+    raise ValueError(f"ffpa_attn_with_kvcache: rotary_cos {tuple(rotary_cos.shape)} and rotary_sin {tuple(rotary_sin.shape)} must share their shape")
+  rotary_dim = 2 * rotary_cos.size(1)
+  if rotary_dim == 0 or rotary_dim % 16 != 0 or rotary_dim > D:
+    raise ValueError(f"ffpa_attn_with_kvcache: rotary_dim ({rotary_dim}) must be a positive multiple of 16 and at most the head dim ({D})")
+  if rotary_cos.size(0) < capacity:
+    raise ValueError(f"ffpa_attn_with_kvcache: rotary_cos / rotary_sin have {rotary_cos.size(0)} rows (seqlen_ro), fewer than the cache capacity {capacity}")
 
 
 def ffpa_attn_with_kvcache(
@@ -58,11 +105,19 @@ def ffpa_attn_with_kvcache(
   ``j % page_size`` of page ``block_table[b, j // page_size]``).  ``cache_seqlens``: an int, or an int32 ``[B]`` device tensor, of keys per sequence (None = the
   whole capacity).  ``causal`` is bottom-right aligned: query i of a sequence of ``Sq`` queries and ``L`` keys sees keys ``j <= i + L - Sq``.  GQA when
   ``Hq % Hkv == 0``.  ``num_splits``: 0 = the library decides, 1 = never split the keys, n = at most n ranges.  Returns ``out [B, Sq, Hq, D]`` — and the
-  fp32 ``softmax_lse [B, Hq, Sq]`` with ``return_softmax_lse``.  Rows that see no key come out as 0 (LSE -inf)."""
+  fp32 ``softmax_lse [B, Hq, Sq]`` with ``return_softmax_lse``.  Rows that see no key come out as 0 (LSE -inf).
+
+  ``k`` / ``v [B, Snew, Hkv, D]`` (the cache's dtype, last dim contiguous; ``cache_seqlens`` required): key i of sequence b is written in place at position
+  ``pos = cache_seqlens[b] + i`` (row ``pos`` of ``k_cache[b]``, or row ``pos % page_size`` of page ``block_table[b, pos // page_size]``; positions at or past the
+  capacity are dropped, negative lengths act as 0), then attention runs over ``min(cache_seqlens[b] + Snew, capacity)`` keys.  ``cache_seqlens`` is not modified.
+  Two sequences that append into one shared page race: the caller's problem, as with FlashAttention.  ``rotary_cos`` / ``rotary_sin [seqlen_ro, rotary_dim / 2]``
+  (q's dtype, contiguous, ``rotary_dim`` a multiple of 16 <= D, ``seqlen_ro`` >= the capacity): the first ``rotary_dim`` dims of the new keys (stored rotated) and of
+  q (a rotated copy attends; q is not modified) are rotated — key i at position ``cache_seqlens[b] + i``, query token i at ``cache_seqlens[b] + i`` when
+  ``causal``, at ``cache_seqlens[b]`` otherwise; ``rotary_interleaved`` pairs dims (2j, 2j + 1), else (j, j + rotary_dim / 2) (GPT-NeoX).  V is never rotated."""
   bad = _unsupported(k, v, rotary_cos, rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes)
   if bad:
-    raise NotImplementedError(f"ffpa_attn_with_kvcache does not support: {', '.join(bad)} (attention over an existing cache only; no append, rotary, "
-                              "leftpad, batch index, local window, softcap or ALiBi)")
+    raise NotImplementedError(f"ffpa_attn_with_kvcache does not support: {', '.join(bad)} (k and v only together, rotary_cos and rotary_sin only together "
+                              "and with k / v; no leftpad, batch index, local window, softcap or ALiBi)")
   for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
     if not isinstance(t, torch.Tensor):
       raise TypeError(f"ffpa_attn_with_kvcache: {name} must be a tensor, got {type(t).__name__}")
@@ -116,6 +171,16 @@ def ffpa_attn_with_kvcache(
   scale = float(softmax_scale) if softmax_scale is not None else D ** -0.5
 
   from . import hip  # (registers the ffpa_attn ops)
+
+  if k is not None:
+    if cache_seqlens is None:
+      raise ValueError("ffpa_attn_with_kvcache: cache_seqlens is required with k / v (it gives where the new keys go)")
+    _check_append(q, k_cache, k, v, rotary_cos, rotary_sin, capacity)
+    # the prepare launch: new keys into the cache (in place), rotated q, post-append lengths — read by the attention launch below on the same stream
+    q_rot, seqused = torch.ops.ffpa_attn._kvcache_append_hip(q, k_cache, v_cache, k, v, seqused, block_table, rotary_cos, rotary_sin, bool(rotary_interleaved),
+                                                             bool(causal))
+    if rotary_cos is not None:
+      q = q_rot
 
   qp = q.reshape(B * Sq, Hq, D)
   cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device) if Sq > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define FFPA_ATTN_ABI_VERSION 7 /* 5: + the packed-sequence entry points (ffpa_attn_varlen_fwd ...); 6: + KV splits inside the packed call (its workspace fields, ffpa_attn_varlen_fwd_workspace_bytes, plan out[4]); 7: + the paged-KV call (ffpa_paged_kv, ffpa_attn_varlen_paged_fwd ...) */
+#define FFPA_ATTN_ABI_VERSION 7 /* 5: + the packed-sequence entry points (ffpa_attn_varlen_fwd ...); 6: + KV splits inside the packed call (its workspace fields, ffpa_attn_varlen_fwd_workspace_bytes, plan out[4]); 7: + the paged-KV call (ffpa_paged_kv, ffpa_attn_varlen_paged_fwd ...), + the KV-cache append (ffpa_kv_append_params, ffpa_attn_kvcache_append: its own size-checked struct, no existing layout changed) */
 
 /* status codes (0 == success).  The Python host maps them onto the exception
  * classes the reference raises (TORCH_CHECK -> RuntimeError,
@@ -344,6 +344,65 @@ int ffpa_attn_varlen_paged_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged
 size_t ffpa_attn_varlen_paged_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv);
 int ffpa_attn_varlen_paged_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, int out[5]);
 int ffpa_attn_varlen_paged_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, char* buf, size_t n);
+
+/*
+ * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
+ * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
+ *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position
+ *     pos = max(cache_seqlens[b], 0) + i: row pos of sequence b in a contiguous cache (kv == NULL: k_cache / v_cache [batch, capacity, heads_kv, D] by
+ *     k_cache_stride / v_cache_stride = {batch, row, head}), or row pos % page_size of page block_table[b * bt_stride + pos / page_size] of a paged pool (kv != NULL:
+ *     the pools of ffpa_attn_varlen_paged_fwd, the batch stride is ignored, pages by kv->k_page_stride / v_page_stride, ids clamped to [0, num_pages)).
+ *     A position >= capacity (contiguous: `capacity`; paged: pages_per_row * page_size) is dropped.  Two sequences that append into one shared page race: the
+ *     caller's problem, as with FlashAttention.
+ *   * rotary_dim > 0: the first rotary_dim dims of the new keys are stored rotated, and q ([batch, seqlen_q, heads_q, D] by q_stride) is written rotated to q_rot
+ *     (by q_rot_stride; q is not modified); dims from rotary_dim on are copied; v is never rotated.  Key i sits at position pos, query token i at
+ *     max(cache_seqlens[b], 0) + i when causal, at max(cache_seqlens[b], 0) otherwise; positions are clamped to seqlen_ro - 1.  rotary_cos / rotary_sin:
+ *     [seqlen_ro, rotary_dim / 2] contiguous in q's dtype; interleaved pairs dims (2j, 2j + 1), else (j, j + rotary_dim / 2) (GPT-NeoX).  fp32 arithmetic
+ *     (x cos - y sin, x sin + y cos), one rounding to the dtype.
+ *   * seqused[b] = min(max(cache_seqlens[b], 0) + seqlen_new, capacity): the lengths the attention launch that follows reads (its seqused_kv).
+ *     cache_seqlens itself is not modified; seqused must be another buffer.
+ * Every row moves as 16-byte loads and stores: D, rotary_dim / 2 and every stride are multiples of 8 elements, the bases 16-byte aligned.
+ */
+typedef struct ffpa_kv_append_params {
+  uint32_t struct_size; /* sizeof(ffpa_kv_append_params), checked */
+  uint32_t abi_version; /* FFPA_ATTN_ABI_VERSION                   */
+
+  const void* q;          /* [batch, seqlen_q, heads_q, D]; read only with rotary_dim > 0 */
+  const void* k;          /* [batch, seqlen_new, heads_kv, D]; may be NULL when seqlen_new == 0 */
+  const void* v;
+  void* k_cache;          /* written in place */
+  void* v_cache;
+  void* q_rot;            /* out, [batch, seqlen_q, heads_q, D]: rotated q (rotary_dim > 0 only, else may be NULL) */
+  int32_t* seqused;       /* out, device [batch] */
+  const int32_t* cache_seqlens; /* device [batch], not modified */
+  const void* rotary_cos; /* [seqlen_ro, rotary_dim / 2]; rotary_dim > 0 only */
+  const void* rotary_sin;
+
+  int32_t batch;
+  int32_t heads_q;
+  int32_t heads_kv;
+  int32_t head_dim;   /* a multiple of 8 in [8, 1024] */
+  int32_t seqlen_q;   /* >= 0 */
+  int32_t seqlen_new; /* >= 0; 0 = nothing appended (seqused still written) */
+  int32_t capacity;   /* keys a sequence's contiguous cache holds; ignored when paged */
+  int32_t seqlen_ro;  /* rows of rotary_cos / rotary_sin (>= the capacity) */
+
+  int64_t q_stride[3];       /* elements: batch, row, head (head-dim stride 1) */
+  int64_t k_stride[3];
+  int64_t v_stride[3];
+  int64_t q_rot_stride[3];
+  int64_t k_cache_stride[3]; /* batch (ignored when paged), row, head */
+  int64_t v_cache_stride[3];
+
+  int32_t rotary_dim;         /* 0 = no rotary; else a multiple of 16 <= head_dim */
+  int32_t rotary_interleaved; /* 1: pairs (2j, 2j + 1); 0: pairs (j, j + rotary_dim / 2) */
+  int32_t causal;             /* query positions: see above */
+  int32_t dtype;              /* enum ffpa_dtype: q, k, v, the caches, q_rot, cos / sin */
+} ffpa_kv_append_params;
+
+/* Launch the append on `stream` of the CURRENT device (kv: the paged pool, NULL = contiguous cache).  Asynchronous: no allocation, no synchronisation; every
+ * bad argument returns a status before any device work.  Returns an ffpa_status. */
+int ffpa_attn_kvcache_append(const ffpa_kv_append_params* p, const ffpa_paged_kv* kv, void* stream);
 
 /* Capability / build queries.  Replaces the module attributes
  * CUDA_FWD_AVAILABLE, F16_ACC_AVAILABLE, ... (csrc/cuffpa/ffpa_api.cc:283-305). */
