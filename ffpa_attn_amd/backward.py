@@ -61,22 +61,26 @@ def _aten_efficient_backward(grad_out, q, k, v, o, lse, causal, scale, attn_bias
 
 
 def _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_bias, want_bias_grad,
-                                budget_bytes: int = 1 << 30, dropout=None):
-  """dV = P^T dO;  dS = P o (dO V^T - rowsum(dO o O));  dQ = scale dS K;  dK = scale dS^T Q, with
-  P = exp(scale QK^T + bias - LSE) recomputed per block of query rows in fp32."""
+                                budget_bytes: int = 1 << 30, dropout=None, dlse=None):
+  """dV = P^T dO;  dS = P o (dO V^T - rowsum(dO o O) + dLSE);  dQ = scale dS K;  dK = scale dS^T Q, with
+  P = exp(scale QK^T + bias - LSE) recomputed per block of query rows in fp32 (float64 inputs: in float64).
+  ``dlse`` [B, Hq, Nq] (or None): the gradient of the LSE output, d LSE / d S = P; rows whose LSE is -inf ignore it."""
   B, Hq, Nq, D = q.shape
   Hkv, Nkv = k.size(1), k.size(2)
   group = Hq // Hkv
-  kx = (k.repeat_interleave(group, dim=1) if group > 1 else k).float()
-  vx = (v.repeat_interleave(group, dim=1) if group > 1 else v).float()
-  go = grad_out.float()
-  delta = (go * o.float()).sum(-1)
-  dq = torch.empty_like(q, dtype=torch.float32)
+  acc = torch.promote_types(q.dtype, torch.float32)
+  kx = (k.repeat_interleave(group, dim=1) if group > 1 else k).to(acc)
+  vx = (v.repeat_interleave(group, dim=1) if group > 1 else v).to(acc)
+  go = grad_out.to(acc)
+  delta = (go * o.to(acc)).sum(-1)
+  if dlse is not None:
+    delta = delta - torch.where(torch.isfinite(lse), dlse.to(acc), 0.0)  # (P = 0 on a -inf row: its dlse must not turn 0 * inf into NaN)
+  dq = torch.empty_like(q, dtype=acc)
   dk = torch.zeros_like(kx)
   dv = torch.zeros_like(vx)
   dbias_full = None
   if want_bias_grad and attn_bias is not None:
-    dbias_full = torch.zeros(B, Hq, Nq, Nkv, dtype=torch.float32, device=q.device)
+    dbias_full = torch.zeros(B, Hq, Nq, Nkv, dtype=acc, device=q.device)
   chunk = max(16, min(Nq, budget_bytes // max(1, B * Hq * Nkv * 4 * (3 if dropout is None else 12))))
   if dropout is not None:
     from .philox import dropout_keep_mask
@@ -87,11 +91,11 @@ def _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_b
   cols = torch.arange(Nkv, device=q.device).view(1, -1)
   for r0 in range(0, Nq, chunk):
     r1 = min(Nq, r0 + chunk)
-    qc = q[:, :, r0:r1].float()
+    qc = q[:, :, r0:r1].to(acc)
     s = (qc @ kx.transpose(-1, -2)) * scale
     if attn_bias is not None:
       bc = attn_bias if attn_bias.size(2) == 1 else attn_bias[:, :, r0:r1]
-      s = s + bc.float()
+      s = s + bc.to(acc)
     if causal:
       rows = torch.arange(r0, r1, device=q.device).view(-1, 1)
       s = s.masked_fill(cols > rows + (Nkv - Nq), float("-inf"))
@@ -105,7 +109,7 @@ def _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_b
       # forward: O = (keep o round(P) / (1-p)) V / l with the row sum undropped; d/dP of that
       rows_i = torch.arange(r0, r1, device=q.device).view(1, 1, -1, 1)
       idx = (bh * Nq + rows_i) * Nkv + cols.view(1, 1, 1, -1)
-      keep = dropout_keep_mask(seed, offset, idx, p_drop).to(torch.float32) * keep_scale
+      keep = dropout_keep_mask(seed, offset, idx, p_drop).to(acc) * keep_scale
       dv += (p * keep).transpose(-1, -2) @ goc
       dp = (goc @ vx.transpose(-1, -2)) * keep
     ds = p * (dp - delta[:, :, r0:r1, None])
@@ -118,6 +122,10 @@ def _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_b
     dbias = dbias_full.sum_to_size(attn_bias.shape).to(attn_bias.dtype)
   return dq.to(q.dtype), _reduce_groups(dk, k, group), _reduce_groups(dv, v, group), dbias
 
+
+# aten's efficient-attention backward on ROCm serves head dims up to 512.  Past that the op does not refuse the call: it returns NaN
+# gradients (measured on MI355X for D = 576, 768, 1024 by tests/test_backward_f64_gpu.py), so those head dims never reach it.
+ATEN_MAX_HEAD_DIM = 512
 
 # (dtype, head_dim) -> False once the aten op has said it cannot serve that head dim / dtype at all.  Only such
 # capability refusals are remembered; a failure that may be specific to one call (bias layout, alignment, out of
@@ -152,14 +160,22 @@ def _additive_bias(attn_bias, dtype):
 
 
 def attention_backward(grad_out, q, k, v, o, lse, *, causal: bool, scale: float, attn_bias=None,
-                       want_bias_grad: bool = False, force: str | None = None, dropout=None):
+                       want_bias_grad: bool = False, force: str | None = None, dropout=None, dlse=None):
   """``(dq, dk, dv, d_attn_bias)`` for the forward ``o, lse = ffpa(q, k, v)``.  ``force`` = ``"aten"`` /
-  ``"recompute"`` pins one implementation (tests); otherwise aten first, recompute if it refuses."""
+  ``"recompute"`` pins one implementation (tests); otherwise aten first (head dims up to ``ATEN_MAX_HEAD_DIM``), recompute if it refuses.  ``dlse`` (the
+  gradient of a loss that used the LSE, ``[B, Hq, Nq]``) always takes the recompute: aten's op has no such input."""
   key = (q.dtype, q.size(-1))
   attn_bias = _additive_bias(attn_bias, q.dtype)
-  if dropout is not None:
-    # the fused aten backward would regenerate a DIFFERENT mask on ROCm: rebuild the kernel's own (philox.py)
-    return _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_bias, want_bias_grad, dropout=dropout)
+  if dropout is not None or dlse is not None:
+    # dropout: the fused aten backward would regenerate a DIFFERENT mask on ROCm: rebuild the kernel's own (philox.py).
+    # dlse: aten computes rowsum(dO o O) itself and takes no LSE gradient; a correction on top would recompute P anyway.
+    if force == "aten" and dlse is not None:
+      raise NotImplementedError("attention_backward: the aten backward takes no LSE gradient")
+    return _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_bias, want_bias_grad, dropout=dropout, dlse=dlse)
+  if q.size(-1) > ATEN_MAX_HEAD_DIM:
+    if force == "aten":
+      raise NotImplementedError(f"attention_backward: aten's efficient-attention backward returns NaN for head_dim {q.size(-1)} > {ATEN_MAX_HEAD_DIM}")
+    return _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_bias, want_bias_grad)
   if force != "recompute" and not _aten_unsupported.get(key, False):
     try:
       return _aten_efficient_backward(grad_out, q, k, v, o, lse, causal, scale, attn_bias, want_bias_grad)

@@ -188,7 +188,8 @@ def ffpa_attn_varlen_func(
   ``N_q - N_k`` rows of a causal sequence with more queries than keys — come out as ``O = 0`` and ``LSE = -inf``
   (``tests/test_ffpa_cute_sm100.py:1117-1183``).  ``max_seqlen_q`` must be >= the longest query sequence (rows past it are not computed).
   ``dropout_p`` must be 0 and every FlashAttention-varlen extension (``window_size``, ``softcap``, ``seqused_k``, ``block_table`` ...) raises
-  ``NotImplementedError``, as in the reference.  Returns ``out [T_q, H_q, D]`` — and ``lse [H_q, T_q]`` fp32 with ``return_lse=True``."""
+  ``NotImplementedError``, as in the reference.  Returns ``out [T_q, H_q, D]`` — and ``lse [H_q, T_q]`` fp32 with ``return_lse=True``.  The LSE is
+  differentiable; a loss that uses it routes the backward through the recompute path (``backward.py``) instead of aten's efficient-attention backward."""
   from .varlen import varlen_apply
 
   return varlen_apply(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=dropout_p, softmax_scale=softmax_scale,
