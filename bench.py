@@ -1,6 +1,7 @@
 """bench.py — the reference's headline benchmark (and its whole forward case matrix) on MI355X.
 
     python bench.py                                  # BASELINE metric: cfg2 = B1 H32 N8192 D512 bf16, 1 GPU
+    python bench.py --full                           # ... and everything else this script measures about it (below)
     python bench.py --workload cfg3 | cfg4_mask | cfg4_offset0 | cross | gqa | attn_mask | dropout | non_aligned | decode | ...
     python bench.py --sweep [--sweep-dims 320,512,1024]   # the reference bench's one-shot case table (one process, one table per head dim)
     python bench.py --gpus N [--workload cfg5] [--gather]  # N > 1 without a launcher: spawns its own N ranks (free port, RCCL)
@@ -20,11 +21,15 @@ block is BORN sharded (per-unit seeds, nothing replicated), no data-path collect
   * --workload cfg5: the fixed global problem B=8 H=32 N=8192 D=512 (256 units) is split over the ranks ->
     "scaling": "strong"; per-rank TFLOPS are listed next to the aggregate;
   * --gather puts the gather of O a caller wanting the full tensor on every rank would pay INTO the timed step, in --gather-chunks pieces
-    sent point-to-point over RCCL while the next piece computes (sharding.attend_and_gather_units); without it the same K steps are timed a
-    second time with the gather, after the contract figure and under a watchdog (guarded_extra_leg), and reported as "with_gather".
+    sent point-to-point over RCCL while the next piece computes (sharding.attend_and_gather_units); without it, with --full, the same K steps are
+    timed a second time with the gather, after the contract figure and under a watchdog (guarded_extra_leg), and reported as "with_gather".
 Timing: barrier + synchronize on both sides of exactly K steps, max over ranks.
 
-Rank 0 prints ONE JSON line.  `roofline` is the dominant kernel against the dense bf16 MFMA peak (HBM peak for the
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the contract's
+keys, `config`, the `device` telemetry sampled over the timed region and, N > 1, the per-rank figures.  Everything else below runs only
+with --full, after the timed region: `roofline`, `steady_state`, `build`, `plan`, `ref_protocol`, the SDPA comparison, `cpu_baseline`,
+the legs of single workloads (`decode_step`, `graph_replay`, `other_launches`, `per_sequence_loop`) and, N > 1, `with_gather`.
+`roofline` is the dominant kernel against the dense bf16 MFMA peak (HBM peak for the
 decode workload), its average launch duration measured by HIP events on the launch stream; `roofline.traffic` is the
 HBM bytes per launch from the committed rocprofv3 PMC pass of the same command (`traffic_source` names the file; null
 when no such pass is committed) — a profile artefact, not a measurement of this very run.  `cpu_baseline` is the
@@ -244,7 +249,7 @@ def live_traffic(workload: str, timeout_s: float = 150.0):
   try:
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
       cmd = [prof, "--kernel-trace", "--output-format", "csv", "--pmc", counter, "-d", out, "-o", counter.lower(), "--", sys.executable, os.path.abspath(__file__),
-             "--workload", workload, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-sdpa", "--no-steady", "--no-ref-protocol", "--no-live-traffic"]
+             "--workload", workload, "--steps", "3", "--warmup", "1"]  # (a plain run: the kernel launches only for the warm-up and the steps)
       pr = subprocess.Popen(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
       try:
         rc = pr.wait(timeout=timeout_s / 2)
@@ -565,6 +570,20 @@ def varlen_decode_main(args) -> None:
   dumped = dump_outputs(args.dump_outputs, last_result[0]) if args.dump_outputs else None
   last_result.clear()
   device = telemetry.summary()
+  line = {
+    "metric": f"attention fwd TFLOPS + max-abs-err vs SDPA, bf16 packed decode batch {nseq} x 1 token, KV {min(lens)} ... {max(lens)} (sum {tk}) Hq={Hq}/Hkv={Hkv} D={D} [varlen_decode]",
+    "value": round(flops * args.steps / elapsed / 1e12, 3), "unit": "TFLOPS", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+    "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+    "config": {"workload": f"varlen_decode: {w['note']}; T_k={tk} Hq={Hq} Hkv={Hkv} D={D} bf16", "global_batch": nseq, "seq_len": 1, "parallelism": "single GPU",
+               "flops_model": "4*Hq*D*sum_i nkv_i", "step": "hip.varlen_forward (ffpa_attn::_varlen_fwd_hip)"},
+    "device": device,
+  }
+  if dumped is not None:
+    line["dump_outputs"] = dumped
+  if not args.full:
+    print(json.dumps(line), flush=True)
+    return
+  # --full: everything below adds to the line
   kernel_ms_avg = sum(kernel_ms) / len(kernel_ms)
   plan = {}
   out, lse = step(plan_out=plan)
@@ -600,17 +619,8 @@ def varlen_decode_main(args) -> None:
           "what": "HIP events around one step (the split kernel + its merge kernel); traffic: the split kernel's dispatches"}
   if note is not None:
     roof["traffic_live_failed"] = note
-  line = {
-    "metric": f"attention fwd TFLOPS + max-abs-err vs SDPA, bf16 packed decode batch {nseq} x 1 token, KV {min(lens)} ... {max(lens)} (sum {tk}) Hq={Hq}/Hkv={Hkv} D={D} [varlen_decode]",
-    "value": round(flops * args.steps / elapsed / 1e12, 3), "unit": "TFLOPS", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-    "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-    "config": {"workload": f"varlen_decode: {w['note']}; T_k={tk} Hq={Hq} Hkv={Hkv} D={D} bf16", "global_batch": nseq, "seq_len": 1, "parallelism": "single GPU",
-               "flops_model": "4*Hq*D*sum_i nkv_i", "step": "hip.varlen_forward (ffpa_attn::_varlen_fwd_hip)"},
-    "roofline": roof, "device": device, "steady_state": steady, "build": build,
-    "plan": {k_: plan[k_] for k_ in ("row_tiles", "block_rows", "block_keys", "workgroups", "splits")},
-  }
-  if dumped is not None:
-    line["dump_outputs"] = dumped
+  line.update({"roofline": roof, "steady_state": steady, "build": build,
+               "plan": {k_: plan[k_] for k_ in ("row_tiles", "block_rows", "block_keys", "workgroups", "splits")}})
   if not args.no_sdpa:  # (the comparison legs; --no-sdpa: none of them — the profiler passes)
     legs = {}
     for what, kw in (("one_kv_range", dict(num_splits=1)), ("one_workgroup_per_query_head", dict(flags=hip.FLAG_NO_PACK_GQA)), ("no_nt_hint", dict(flags=hip.FLAG_NO_KV_STREAM))):
@@ -715,8 +725,22 @@ def varlen_main(args) -> None:
   dumped = dump_outputs(args.dump_outputs, last_result[0]) if args.dump_outputs else None
   last_result.clear()
   device = telemetry.summary()
-  kernel_ms_avg = sum(kernel_ms) / len(kernel_ms)
   value = flops * args.steps / elapsed / 1e12
+  line = {
+    "metric": f"attention fwd TFLOPS + max-abs-err vs SDPA, bf16 packed sequences {lens} Hq={Hq}/Hkv={Hkv} D={D} causal [varlen]",
+    "value": round(value, 2), "unit": "TFLOPS", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+    "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+    "config": {"workload": f"varlen: {w['note']}; T={total} Hq={Hq} Hkv={Hkv} D={D} bf16", "global_batch": len(lens), "seq_len": max_len, "parallelism": "single GPU",
+               "flops_model": "4*Hq*D*sum_i n_i (n_i + 1) / 2", "step": "ffpa_attn_varlen_func"},
+    "device": device,
+  }
+  if dumped is not None:
+    line["dump_outputs"] = dumped
+  if not args.full:
+    print(json.dumps(line), flush=True)
+    return
+  # --full: everything below adds to the line
+  kernel_ms_avg = sum(kernel_ms) / len(kernel_ms)
   steady = None
   if not args.no_steady:
     n_pre, n_timed = max(20, int(150.0 / kernel_ms_avg)), max(20, min(400, int(60.0 / kernel_ms_avg)))
@@ -752,17 +776,7 @@ def varlen_main(args) -> None:
     roof["traffic_live_failed"] = note
   if device.get("peak_tflops_from_device"):
     roof["frac_of_device_peak"] = round(achieved / device["peak_tflops_from_device"], 4)
-  line = {
-    "metric": f"attention fwd TFLOPS + max-abs-err vs SDPA, bf16 packed sequences {lens} Hq={Hq}/Hkv={Hkv} D={D} causal [varlen]",
-    "value": round(value, 2), "unit": "TFLOPS", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-    "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-    "config": {"workload": f"varlen: {w['note']}; T={total} Hq={Hq} Hkv={Hkv} D={D} bf16", "global_batch": len(lens), "seq_len": max_len, "parallelism": "single GPU",
-               "flops_model": "4*Hq*D*sum_i n_i (n_i + 1) / 2", "step": "ffpa_attn_varlen_func"},
-    "roofline": roof, "device": device, "steady_state": steady, "build": build,
-    "plan": {k_: plan[k_] for k_ in ("row_tiles", "block_rows", "block_keys", "workgroups")},
-  }
-  if dumped is not None:
-    line["dump_outputs"] = dumped
+  line.update({"roofline": roof, "steady_state": steady, "build": build, "plan": {k_: plan[k_] for k_ in ("row_tiles", "block_rows", "block_keys", "workgroups")}})
   # the same batch as a loop of dense calls, one per sequence — and its outputs against the packed call's (same tile, same recurrence: the bits where the
   # dense plan is the plain tile; rounding where it pairs / splits / takes another tile)
   out = step()
@@ -836,8 +850,8 @@ def stub_main(args, world: int, rank: int) -> None:
     dist.all_gather(got, mine)
     every = [float(x.item()) for x in got]
   with_gather = None
-  if world > 1:
-    # the gather leg's plumbing with a stand-in for the kernel: the REAL sharding.attend_and_gather_units (transport probe, agreed piece count, point-to-point
+  if args.full and world > 1:
+    # (--full) the gather leg's plumbing with a stand-in for the kernel: the REAL sharding.attend_and_gather_units (transport probe, agreed piece count, point-to-point
     # sends into the final slices) on small CPU tensors, and the report the line carries about it
     from ffpa_attn_amd import sharding
 
@@ -1027,13 +1041,16 @@ def main() -> None:
   ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
   ap.add_argument("--gather", action="store_true", help="include an RCCL all_gather of O in the timed step (N > 1)")
   ap.add_argument("--gather-chunks", type=int, default=4, help="--gather: pieces the local block is attended / gathered in (overlap)")
-  ap.add_argument("--no-cpu-baseline", action="store_true")
-  ap.add_argument("--no-sdpa", action="store_true", help="skip the SDPA-on-GPU accuracy / speed comparison")
-  ap.add_argument("--no-ref-protocol", action="store_true", help="skip the reference bench's own timing protocol (2 warm-ups + 10 iterations)")
-  ap.add_argument("--no-gather-extra", action="store_true", help="N > 1: skip the second timed region that adds the all_gather of O")
+  ap.add_argument("--full", action="store_true", help="after the line's own figure, measure everything else: roofline (its traffic from two rocprofv3 PMC passes), "
+                  "steady-state / graph-replay / other-launch legs, launch plan, build identity, the reference's timing protocol, errors and speed vs SDPA, the CPU "
+                  "baseline; N > 1: the gather leg.  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+  ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+  ap.add_argument("--no-sdpa", action="store_true", help="--full: skip the SDPA-on-GPU accuracy / speed comparison")
+  ap.add_argument("--no-ref-protocol", action="store_true", help="--full: skip the reference bench's own timing protocol (2 warm-ups + 10 iterations)")
+  ap.add_argument("--no-gather-extra", action="store_true", help="--full, N > 1: skip the second timed region that adds the all_gather of O")
   ap.add_argument("--gather-extra-timeout", type=float, default=180.0, help="N > 1: seconds the gather leg may take before every rank gives up on it and rank 0 prints the line without it")
-  ap.add_argument("--no-live-traffic", action="store_true", help="N = 1: do not measure roofline.traffic with two rocprofv3 PMC passes of this run (quote the committed profile instead)")
-  ap.add_argument("--no-steady", action="store_true", help="N = 1: skip the steady-state leg (the step again after >= 150 ms of continuous load, outside the timed region)")
+  ap.add_argument("--no-live-traffic", action="store_true", help="--full, N = 1: do not measure roofline.traffic with two rocprofv3 PMC passes of this run (quote the committed profile instead)")
+  ap.add_argument("--no-steady", action="store_true", help="--full, N = 1: skip the steady-state leg (the step again after >= 150 ms of continuous load, outside the timed region)")
   ap.add_argument("--sweep", action="store_true", help="the reference bench's case table for --sweep-dims in one process (python -m ffpa_attn.bench)")
   ap.add_argument("--sweep-dims", default="320,512,1024")
   ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32; "
@@ -1095,7 +1112,7 @@ def main() -> None:
     local_units = u1 - u0
     flops_local = valid_pairs_flops(w, 1) // Hkv * local_units  # FLOPs are uniform over the units
     flops_global = valid_pairs_flops(w, global_B)
-    want_gather_extra = world > 1 and not args.gather and not args.no_gather_extra
+    want_gather_extra = args.full and world > 1 and not args.gather and not args.no_gather_extra
     gathered = torch.empty((n_units, grp, Nq, D), dtype=torch.bfloat16, device=dev) if (world > 1 and (args.gather or want_gather_extra)) else None
     api_kw = dict(is_causal=w["causal"], dropout_p=w["dropout"])
     gather_stats = {}
@@ -1131,7 +1148,7 @@ def main() -> None:
       def step():
         return ffpa_attn_func(q, k, v, attn_mask=mask, dropout_p=w["dropout"], is_causal=w["causal"], enable_gqa=Hq != Hkv)
 
-      if w["bound"] == "hbm" and w["dropout"] == 0.0:
+      if args.full and w["bound"] == "hbm" and w["dropout"] == 0.0:
         # the same step through the product's graph-replayed form (ffpa_attn_amd.DecodeStep: the call captured once, one hipGraphLaunch per step): timed next to
         # the contract figure (`decode_step` in the line).  Measured (profiles/r06_decode_step.txt): it takes 19 us of HOST time off a call (33 -> 14) and 15 us off
         # a caller that synchronises per token; a back-to-back launch loop like the timed region is GPU-bound either way (a replay costs the GPU ~ 3 us of launch).
@@ -1186,6 +1203,48 @@ def main() -> None:
   device = telemetry.summary()  # (of the first timed region: the bench line's own)
   kernel_ms_avg = sum(kernel_ms) / len(kernel_ms)
   value = flops_global * args.steps / elapsed / 1e12
+  line = None
+  if rank == 0:
+    shape = f"B={global_B} Hq={Hq} Hkv={Hkv} Nq={Nq} Nkv={Nkv} D={D}"
+    line = {
+      "metric": metric_name(name, w),
+      "value": round(value, 2),
+      "unit": "TFLOPS",
+      "n_gpus": world,
+      "steps": args.steps,
+      "warmup": args.warmup,
+      "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+      "higher_is_better": True,
+      "scaling": "strong" if strong else "weak",
+      "vs_baseline": None,  # BASELINE.md holds no published MI355X number for this metric
+      "dtype": "bf16",
+      "data": "synthetic",
+      "config": {
+        "workload": f"{name}: {shape} bf16 attention forward" + (f" ({w['note']})" if w["note"] else ""),
+        "global_batch": global_B,
+        "seq_len": Nq,
+        "parallelism": (f"(batch,kv-head) units born sharded x{world}: {Hkv * global_B} units, {Hkv * global_B / world:g} per rank, no data-path collective"
+                        if sharded else "single GPU") + (f" + gather of O on every rank in <= {args.gather_chunks} pieces overlapped with compute" if (sharded and world > 1 and args.gather) else ""),
+        "flops_model": "4*B*Hq*D*valid_pairs",
+        "step": "hip.ffpa_attn_forward_hip(causal=True, causal_offset=0)" if w["via"] == "op_offset0" else
+                ("sharding.attend_units -> ffpa_attn_func" if sharded else "ffpa_attn_func"),
+      },
+      "device": device,
+    }
+    if dumped is not None:
+      line["dump_outputs"] = dumped
+    if per_rank_tflops is not None:
+      line["per_rank_tflops"] = per_rank_tflops
+      line["rccl_world_size"] = world
+      line["frac_of_mfma_peak_aggregate"] = round(value / (MFMA_BF16_PEAK_TFLOPS * world), 4)
+      line["timed_step_includes_gather"] = bool(args.gather)
+  if not args.full:
+    if line is not None:
+      print(json.dumps(line), flush=True)
+    if dist is not None:
+      dist.destroy_process_group()
+    return
+  # --full: everything below adds to the line; none of it feeds `value` or `ms_per_step`
   steady = None
   if world == 1 and not args.no_steady and not args.stub_backend:
     # Context for `value`, never `value` itself: a GPU coming out of idle runs its first ~ 10 - 25 ms of work slower than it does under
@@ -1333,46 +1392,15 @@ def main() -> None:
     roof["traffic_stale"] = bool(traffic_stale)
     if traffic_live_note is not None:
       roof["traffic_live_failed"] = traffic_live_note  # (the figure above is then the committed profile's, if its library is this one)
-    shape = f"B={global_B} Hq={Hq} Hkv={Hkv} Nq={Nq} Nkv={Nkv} D={D}"
-    line = {
-      "metric": metric_name(name, w),
-      "value": round(value, 2),
-      "unit": "TFLOPS",
-      "n_gpus": world,
-      "steps": args.steps,
-      "warmup": args.warmup,
-      "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-      "higher_is_better": True,
-      "scaling": "strong" if strong else "weak",
-      "vs_baseline": None,  # BASELINE.md holds no published MI355X number for this metric
-      "dtype": "bf16",
-      "data": "synthetic",
-      "config": {
-        "workload": f"{name}: {shape} bf16 attention forward" + (f" ({w['note']})" if w["note"] else ""),
-        "global_batch": global_B,
-        "seq_len": Nq,
-        "parallelism": (f"(batch,kv-head) units born sharded x{world}: {Hkv * global_B} units, {Hkv * global_B / world:g} per rank, no data-path collective"
-                        if sharded else "single GPU") + (f" + gather of O on every rank in <= {args.gather_chunks} pieces overlapped with compute" if (sharded and world > 1 and args.gather) else ""),
-        "flops_model": "4*B*Hq*D*valid_pairs",
-        "step": "hip.ffpa_attn_forward_hip(causal=True, causal_offset=0)" if w["via"] == "op_offset0" else
-                ("sharding.attend_units -> ffpa_attn_func" if sharded else "ffpa_attn_func"),
-      },
+    line.update({
       "roofline": roof,
-      "device": device,
       "steady_state": steady,
       **({"decode_step": decode_step} if decode_step is not None else {}),
       **({"other_launches": other_launches} if other_launches is not None else {}),
       **({"graph_replay": graph_replay} if graph_replay is not None else {}),
       "build": build,
       "plan": {k_: plan.get(k_) for k_ in ("variant", "block_rows", "block_keys", "splits")},
-    }
-    if dumped is not None:
-      line["dump_outputs"] = dumped
-    if per_rank_tflops is not None:
-      line["per_rank_tflops"] = per_rank_tflops
-      line["rccl_world_size"] = world
-      line["frac_of_mfma_peak_aggregate"] = round(value / (MFMA_BF16_PEAK_TFLOPS * world), 4)
-      line["timed_step_includes_gather"] = bool(args.gather)
+    })
     if world == 1 and not sharded and not args.no_ref_protocol:
       # the reference bench's protocol: 2 warm-ups, 10 iterations, perf_counter around a synchronize (cli/_runner_fwd.py:84-103)
       for _ in range(2):
@@ -1398,8 +1426,6 @@ def main() -> None:
                                "bit-for-bit against the oracle in tests/test_fwd_gpu.py")
     if world == 1 and not args.no_cpu_baseline:
       line["cpu_baseline"] = cpu_baseline(w)
-  else:
-    line = None
 
   def emit(extra=None):
     if line is not None:

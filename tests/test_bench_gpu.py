@@ -1,5 +1,6 @@
-"""bench.py as the driver runs it, on one GPU: one JSON line with the contract's keys, the roofline and CPU-baseline objects, what the device
-said about itself, and the steady-state leg.  No throughput is asserted — only that the line is whole and self-consistent."""
+"""bench.py on one GPU: a plain run's one JSON line holds the contract's keys and nothing measured after the timed region; with --full the line
+also has the roofline and CPU-baseline objects, what the device said about itself, and the steady-state leg.  No throughput is asserted — only
+that the line is whole and self-consistent."""
 
 import json
 import os
@@ -25,9 +26,26 @@ def _bench(*flags):
   return json.loads(lines[0])
 
 
+FULL_ONLY = ("roofline", "steady_state", "build", "plan", "ref_protocol", "cpu_baseline", "max_abs_err_vs_sdpa", "sdpa_gpu_ms", "decode_step", "graph_replay",
+             "other_launches", "per_sequence_loop", "with_gather")
+
+
+@pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a GPU")
+def test_plain_run_prints_the_headline_and_nothing_measured_after_it():
+  """Without --full a run sets up, warms up, times the steps and prints the line: the contract's keys, and no leg that runs after the timed region."""
+  for workload, steps, warmup in (("cfg2", 3, 1), ("varlen", 3, 1), ("varlen_decode", 4, 2)):
+    line = _bench("--gpus", "1", "--workload", workload, "--steps", str(steps), "--warmup", str(warmup))
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "device"):
+      assert key in line, (workload, key)
+    assert not [k_ for k_ in FULL_ONLY if k_ in line], (workload, sorted(line))
+    assert line["steps"] == steps and line["warmup"] == warmup and line["unit"] == "TFLOPS" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+  assert line["device"]["cus"] == torch.cuda.get_device_properties(0).multi_processor_count
+
+
 @pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a GPU")
 def test_bench_line_of_a_short_workload_is_whole():
-  line = _bench("--gpus", "1", "--workload", "cross", "--steps", "4", "--warmup", "2", "--no-sdpa")
+  line = _bench("--gpus", "1", "--workload", "cross", "--steps", "4", "--warmup", "2", "--full", "--no-sdpa")
   for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline", "device", "steady_state", "build", "plan"):
     assert key in line, key
@@ -60,7 +78,7 @@ def test_bench_line_of_a_short_workload_is_whole():
 def test_decode_line_is_priced_against_hbm_and_carries_the_graph_replay_leg():
   """The decode workload's roofline is the HBM one; its step is launch-bound from Python, so the line also says what the same step does when it is
   captured into a HIP graph and replayed (one step per graph, and 32 — a token's layers)."""
-  line = _bench("--gpus", "1", "--workload", "decode", "--steps", "10", "--warmup", "3", "--no-sdpa", "--no-cpu-baseline", "--no-live-traffic")
+  line = _bench("--gpus", "1", "--workload", "decode", "--steps", "10", "--warmup", "3", "--full", "--no-sdpa", "--no-cpu-baseline", "--no-live-traffic")
   roof = line["roofline"]
   assert roof["bound"] == "hbm" and roof["unit"] == "GB/s" and roof["peak"] == 8000.0 and 0.0 < roof["frac"] < 1.0
   assert roof["kernel"].startswith("ffpa_fwd_split_d_kernel<bf16, 512")
@@ -77,7 +95,7 @@ def test_decode_line_is_priced_against_hbm_and_carries_the_graph_replay_leg():
 def test_packed_decode_line_is_priced_against_hbm_and_names_its_launch():
   """`--workload varlen_decode`: a packed decode batch (one token per sequence, ragged KV lengths, GQA) — the HBM roofline of one step, the launch the library
   picked (heads packed into tile rows, KV ranges split and merged, the non-temporal fetch) and the same call without each of them beside it."""
-  line = _bench("--gpus", "1", "--workload", "varlen_decode", "--steps", "4", "--warmup", "2", "--no-live-traffic")
+  line = _bench("--gpus", "1", "--workload", "varlen_decode", "--steps", "4", "--warmup", "2", "--full", "--no-live-traffic")
   for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline",
               "device", "steady_state", "build", "plan", "other_launches", "per_sequence_loop"):
     assert key in line, key

@@ -31,7 +31,7 @@ def test_bench_plumbing_at_the_scaling_curves_world_sizes():
   """The driver takes the scaling curve at N = 1, 2, 4, 8: the launch / barrier / max-over-ranks plumbing at 4 and 8 ranks (gloo stand-in; the
   data path needs GPUs and is covered at world size 2 in tests/test_sharding.py and on the GPU box)."""
   for n in (4, 8):
-    r = _run(["--gpus", str(n), "--stub-backend", "gloo", "--steps", "2", "--warmup", "1"])
+    r = _run(["--gpus", str(n), "--stub-backend", "gloo", "--steps", "2", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -42,10 +42,18 @@ def test_bench_plumbing_at_the_scaling_curves_world_sizes():
     assert g["transport"] == "p2p" and g["chunks"] == 2 and g["chunks_requested"] == 4 and g["equal_to_plain_gather"] is True, g
     assert g["received_bytes_per_rank"] == g["shard_bytes"] * (n - 1) and g["expected_ms_one_shard_per_link"] > 0 and g["alone_ms"] > 0 and "alone_over_expected" in g, g
   # the fallback transport, pinned through the environment (what the probe selects on a node without RCCL point-to-point)
-  r = _run(["--gpus", "4", "--stub-backend", "gloo", "--steps", "2", "--warmup", "1"], env={"FFPA_SHARDING_TRANSPORT": "all_gather"})
+  r = _run(["--gpus", "4", "--stub-backend", "gloo", "--steps", "2", "--warmup", "1", "--full"], env={"FFPA_SHARDING_TRANSPORT": "all_gather"})
   assert r.returncode == 0, r.stderr[-2000:]
   g = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["with_gather"]
   assert g["transport"] == "all_gather" and g["equal_to_plain_gather"] is True and "all_gather_into_tensor" in g["what"], g
+
+
+def test_the_gather_leg_runs_only_with_full():
+  """The gather of O is timed after the contract figure only under --full: a plain run at N > 1 prints the sharded step's line alone."""
+  r = _run(["--gpus", "2", "--stub-backend", "gloo", "--steps", "2", "--warmup", "1"])
+  assert r.returncode == 0, r.stderr[-2000:]
+  lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+  assert len(lines) == 1 and "with_gather" not in json.loads(lines[0]), r.stdout
 
 
 def test_bench_under_a_launcher_does_not_spawn_and_checks_the_world_size():

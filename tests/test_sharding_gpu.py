@@ -113,7 +113,7 @@ def test_two_ranks_over_rccl_reproduce_the_one_rank_result_bit_for_bit():
 # (`pytest -m gpu -k two_ranks` on a 2-GPU box runs exactly the N > 1 tests)
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (runs on the driver's multi-GPU node)")
 def test_two_ranks_bench_launches_itself_over_rccl():
-  """`python bench.py --gpus 2 --workload cfg5` — the command the scaling curve is taken with — as a subprocess: one JSON line, RCCL world
+  """`python bench.py --gpus 2 --workload cfg5 --full` — the command the scaling curve is taken with, plus --full for its gather leg — as a subprocess: one JSON line, RCCL world
   size 2, one TFLOPS figure per rank, the kernel-only figure and the figure with the all_gather of O inside the step.  (No number is
   asserted: the plumbing must not be what fails when the curve is taken.)"""
   import json
@@ -124,7 +124,7 @@ def test_two_ranks_bench_launches_itself_over_rccl():
   env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
   for k_ in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
     env.pop(k_, None)
-  out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "cfg5", "--steps", "2", "--warmup", "1"],
+  out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "cfg5", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=RANKS_TIMEOUT_S + 180, env=env)
   assert out.returncode == 0, out.stderr[-2000:]
   lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

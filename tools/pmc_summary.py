@@ -70,7 +70,7 @@ def main():
         seen.add(r["Dispatch_Id"])
         durs.append(dur)
   res = {
-      "source": "rocprofv3 --kernel-trace --pmc <counters> -- python bench.py --workload W --steps 3 --warmup 1 --no-cpu-baseline --no-sdpa "
+      "source": "rocprofv3 --kernel-trace --pmc <counters> -- python bench.py --workload W --steps 3 --warmup 1 --full --no-cpu-baseline --no-sdpa --no-steady "
                 "(one pass per counter group, tools/gpu_round.sh stage wprof), MI355X. " + note,
       "units": "SQ_WAVE_CYCLES/SQ_WAIT_*/SQ_ACTIVE_INST_* are quad-cycles; SQ_VALU_MFMA_BUSY_CYCLES are cycles (=32 x N_mfma); "
                "GRBM_GUI_ACTIVE is summed over 8 XCDs; FETCH_SIZE / WRITE_SIZE in KiB, FETCH_SIZE reads 1/2 of a wide coalesced stream on gfx950 "
