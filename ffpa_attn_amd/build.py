@@ -102,7 +102,7 @@ def _prune_temps() -> None:
   import glob
   import gzip
 
-  for tdir in glob.glob(os.path.join(OBJ_DIR, "temps_d*")) + glob.glob(os.path.join(OBJ_DIR, "temps_append")):
+  for tdir in glob.glob(os.path.join(OBJ_DIR, "temps_d*")) + glob.glob(os.path.join(OBJ_DIR, "temps_append")) + glob.glob(os.path.join(OBJ_DIR, "temps_merge")):
     for path in glob.glob(os.path.join(tdir, "*")):
       if path.endswith("gfx950.s"):
         with open(path, "rb") as src, gzip.open(path + ".gz", "wb", compresslevel=6) as dst:
@@ -200,6 +200,15 @@ def build(force: bool = False, jobs: int | None = None, save_temps: bool = True,
     tmp = os.path.join(OBJ_DIR, "temps_append")
     os.makedirs(tmp, exist_ok=True)
     tasks.append((append, [hipcc, *CXXFLAGS, *product, *extra, "-c", os.path.join(CSRC, "ffpa_kvcache_append.hip"), "-o", append], tmp))
+  # the merge of two attention states (ffpa_merge_states.hip, the cascade's last launch): one small TU, both dtypes; its assembly lands in temps_merge
+  merge = os.path.join(OBJ_DIR, "ffpa_merge_states.o")
+  objs.append(merge)
+  if test_lib:
+    test_objs.append(merge)
+  if stale(merge):
+    tmp = os.path.join(OBJ_DIR, "temps_merge")
+    os.makedirs(tmp, exist_ok=True)
+    tasks.append((merge, [hipcc, *CXXFLAGS, *product, *extra, "-c", os.path.join(CSRC, "ffpa_merge_states.hip"), "-o", merge], tmp))
   capi = os.path.join(OBJ_DIR, "ffpa_capi.o")
   objs.append(capi)
   if stale(capi):
@@ -253,9 +262,10 @@ def build_variant(tag: str, defs: list[str], jobs: int | None = None, head_dims:
     missing += [d for d in VARLEN_HEAD_DIMS if not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_varlen_d{d}.o"))]
     missing += [d for d in VARLEN_HEAD_DIMS if not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_paged_d{d}.o"))]
     missing += [] if os.path.exists(os.path.join(OBJ_DIR, "ffpa_kvcache_append.o")) else ["kvcache_append"]
+    missing += [] if os.path.exists(os.path.join(OBJ_DIR, "ffpa_merge_states.o")) else ["merge_states"]
     build(force=bool(missing), verbose=False)
   elif any(not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_{k}_d{d}.o")) for d in VARLEN_HEAD_DIMS for k in ("varlen", "paged")) or \
-      not os.path.exists(os.path.join(OBJ_DIR, "ffpa_kvcache_append.o")):
+      not os.path.exists(os.path.join(OBJ_DIR, "ffpa_kvcache_append.o")) or not os.path.exists(os.path.join(OBJ_DIR, "ffpa_merge_states.o")):
     build(force=True, verbose=False)
   tasks, objs = [], []
   for d in HEAD_DIMS:
@@ -268,6 +278,7 @@ def build_variant(tag: str, defs: list[str], jobs: int | None = None, head_dims:
   objs += [os.path.join(OBJ_DIR, f"ffpa_varlen_d{d}.o") for d in VARLEN_HEAD_DIMS]  # (the packed-sequence kernels: the main build's, never a variant's)
   objs += [os.path.join(OBJ_DIR, f"ffpa_paged_d{d}.o") for d in VARLEN_HEAD_DIMS]  # (and their paged twins)
   objs.append(os.path.join(OBJ_DIR, "ffpa_kvcache_append.o"))  # (and the KV-cache append)
+  objs.append(os.path.join(OBJ_DIR, "ffpa_merge_states.o"))  # (and the merge of two attention states)
   capi = os.path.join(odir, "ffpa_capi.o")
   objs.append(capi)
   tasks.append([hipcc, *CXXFLAGS, *defs, "-c", os.path.join(CSRC, "ffpa_capi.hip"), "-o", capi])  # (the plan must see the same tunables as the kernels)

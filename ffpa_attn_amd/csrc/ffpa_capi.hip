@@ -22,6 +22,7 @@
 #include "ffpa_launch.h"
 #include "ffpa_paged.h"         // (the paged-KV twin of the packed-sequence kernel)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
+#include "ffpa_merge_states.h"    // (the merge of two attention states)
 
 namespace {
 
@@ -1410,6 +1411,56 @@ int ffpa_attn_kvcache_append(const ffpa_kv_append_params* p, const ffpa_paged_kv
   const int grid_y = std::max((heads + per_wg - 1) / per_wg, (int)std::min<int64_t>((heads + a.slots - 1) / a.slots, fill));
   const int st = ffpa::launch_kv_append(p->dtype, interleaved, a, (unsigned)grid_y, static_cast<hipStream_t>(stream));
   if (st != 0) return fail(FFPA_ERR_LAUNCH, "kv append launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
+}
+
+// ---- the merge of two attention states (include/ffpa_attn.h: ffpa_merge_states_params)
+int ffpa_attn_merge_states(const ffpa_merge_states_params* p, void* stream) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_merge_states_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_merge_states_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size,
+                sizeof(ffpa_merge_states_params), p->abi_version, FFPA_ATTN_ABI_VERSION);
+  if (p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
+  if (p->tokens < 0 || p->heads < 0) return fail(FFPA_ERR_BAD_SHAPE, "tokens=%d / heads=%d must not be negative", p->tokens, p->heads);
+  if (p->head_dim <= 0 || p->head_dim % 8 != 0 || p->head_dim > 1024)
+    return fail(FFPA_ERR_BAD_HEADDIM, "headdim not support! D=%d (supported: multiples of 8 in [8, 1024])", p->head_dim);
+  if (!p->o_a || !p->o_b || !p->o || !p->lse_a || !p->lse_b) return fail(FFPA_ERR_NULL_POINTER, "o_a / o_b / o / lse_a / lse_b must be non-NULL");
+  if (!aligned16(p->o_a) || !aligned16(p->o_b) || !aligned16(p->o)) return fail(FFPA_ERR_MISALIGNED, "o_a / o_b / o base pointers must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(p->lse_a) & 3u) || (reinterpret_cast<uintptr_t>(p->lse_b) & 3u) || (reinterpret_cast<uintptr_t>(p->lse) & 3u))
+    return fail(FFPA_ERR_MISALIGNED, "lse_a / lse_b / lse must be 4-byte aligned");
+  int rc;
+  if ((rc = check_strides2("o_a", p->o_a_stride)) || (rc = check_strides2("o_b", p->o_b_stride)) || (rc = check_strides2("o", p->o_stride))) return rc;
+  if (p->lse_a_stride_head < 0 || p->lse_b_stride_head < 0 || (p->lse != nullptr && p->lse_stride_head < 0))
+    return fail(FFPA_ERR_BAD_STRIDE, "lse head strides must not be negative (lse_a %lld, lse_b %lld, lse %lld)", (long long)p->lse_a_stride_head,
+                (long long)p->lse_b_stride_head, (long long)p->lse_stride_head);
+  // (the output's rows must not overlap: two lanes would store one element)
+  if (p->heads > 1 && p->tokens > 1) {
+    const int64_t lo = std::min(p->o_stride[0], p->o_stride[1]), hi = std::max(p->o_stride[0], p->o_stride[1]);
+    const int64_t inner = lo == p->o_stride[0] ? p->tokens : p->heads;
+    if (lo < p->head_dim || hi < lo * inner) return fail(FFPA_ERR_BAD_STRIDE, "o strides {%lld, %lld} overlap its rows", (long long)p->o_stride[0], (long long)p->o_stride[1]);
+  } else if ((p->heads > 1 && p->o_stride[1] < p->head_dim) || (p->tokens > 1 && p->o_stride[0] < p->head_dim)) {
+    return fail(FFPA_ERR_BAD_STRIDE, "o strides {%lld, %lld} overlap its rows", (long long)p->o_stride[0], (long long)p->o_stride[1]);
+  }
+  if (p->lse != nullptr && p->heads > 1 && p->lse_stride_head < p->tokens)
+    return fail(FFPA_ERR_BAD_STRIDE, "lse head stride %lld is less than tokens=%d (its rows would overlap)", (long long)p->lse_stride_head, p->tokens);
+  if (p->tokens == 0 || p->heads == 0) return FFPA_OK;
+  if ((rc = check_device()) != FFPA_OK) return rc;
+
+  ffpa::MergeStatesArgs a;
+  memset(&a, 0, sizeof(a));
+  a.oa = p->o_a, a.ob = p->o_b, a.o = p->o;
+  a.la = p->lse_a, a.lb = p->lse_b, a.l = p->lse;
+  for (int i = 0; i < 2; ++i) a.soa[i] = p->o_a_stride[i], a.sob[i] = p->o_b_stride[i], a.so[i] = p->o_stride[i];
+  a.sla = p->lse_a_stride_head, a.slb = p->lse_b_stride_head, a.sl = p->lse_stride_head;
+  a.T = p->tokens, a.H = p->heads, a.D = p->head_dim;
+  // one 16-byte chunk per lane: 256-lane workgroups once there are chunks for one on every CU (T x H x D / 8 >= 256 x CUs), 64-lane ones below that (16 rows x
+  // 32 heads at D 512 = 32768 chunks: 512 workgroups of 64 on 256 CUs instead of 128 of 256), at most 8 workgroups per CU (a grid-stride loop does the rest)
+  const int64_t chunks = (int64_t)p->tokens * p->heads * (p->head_dim / 8);
+  const int64_t cus = device_cu_count();
+  const unsigned threads = chunks >= 256 * cus ? 256u : 64u;
+  const int64_t blocks = std::min<int64_t>((chunks + threads - 1) / threads, 8 * cus);
+  const int st = ffpa::launch_merge_states(p->dtype, a, (unsigned)blocks, threads, static_cast<hipStream_t>(stream));
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "merge states launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
   return FFPA_OK;
 }
 

@@ -212,6 +212,31 @@ class FfpaKvAppendParams(ctypes.Structure):
   ]
 
 
+class FfpaMergeStatesParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_merge_states_params`` (include/ffpa_attn.h): the merge of two attention states."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("abi_version", ctypes.c_uint32),
+    ("o_a", ctypes.c_void_p),
+    ("o_b", ctypes.c_void_p),
+    ("o", ctypes.c_void_p),
+    ("lse_a", ctypes.c_void_p),
+    ("lse_b", ctypes.c_void_p),
+    ("lse", ctypes.c_void_p),
+    ("tokens", ctypes.c_int32),
+    ("heads", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("dtype", ctypes.c_int32),
+    ("o_a_stride", ctypes.c_int64 * 2),
+    ("o_b_stride", ctypes.c_int64 * 2),
+    ("o_stride", ctypes.c_int64 * 2),
+    ("lse_a_stride_head", ctypes.c_int64),
+    ("lse_b_stride_head", ctypes.c_int64),
+    ("lse_stride_head", ctypes.c_int64),
+  ]
+
+
 _lib = None
 _debug_lib = None
 _lib_lock = threading.Lock()
@@ -232,6 +257,7 @@ EXPORTS = (
   "ffpa_attn_varlen_paged_fwd_kernel",
   "ffpa_attn_varlen_paged_fwd_workspace_bytes",
   "ffpa_attn_kvcache_append",
+  "ffpa_attn_merge_states",
   "ffpa_attn_query",
   "ffpa_attn_fwd_tile_config",
   "ffpa_attn_last_error",
@@ -293,6 +319,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     if path is None or hasattr(lib, "ffpa_attn_kvcache_append"):  # (ditto: before the KV-cache append)
       lib.ffpa_attn_kvcache_append.argtypes = [ctypes.POINTER(FfpaKvAppendParams), ctypes.POINTER(FfpaPagedKv), ctypes.c_void_p]
       lib.ffpa_attn_kvcache_append.restype = ctypes.c_int
+    if path is None or hasattr(lib, "ffpa_attn_merge_states"):  # (ditto: before the merge of two attention states)
+      lib.ffpa_attn_merge_states.argtypes = [ctypes.POINTER(FfpaMergeStatesParams), ctypes.c_void_p]
+      lib.ffpa_attn_merge_states.restype = ctypes.c_int
     lib.ffpa_attn_query.argtypes = [ctypes.c_int]
     lib.ffpa_attn_query.restype = ctypes.c_int
     lib.ffpa_attn_fwd_tile_config.argtypes = [
@@ -1319,3 +1348,85 @@ def _kvcache_append_hip_torch_op(q, k_cache, v_cache, k, v, cache_seqlens, block
 def _kvcache_append_hip_fake(q, k_cache, v_cache, k, v, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, causal):
   q_rot = q.new_empty(tuple(q.shape) if rotary_cos is not None else (0,))
   return q_rot, q.new_empty((q.size(0),), dtype=torch.int32)
+
+
+# The merge of two attention states (ffpa_merge_attn_states; the last launch of ffpa_attn_with_kvcache_cascade)
+def check_merge_states(o_a: torch.Tensor, lse_a: torch.Tensor, o_b: torch.Tensor, lse_b: torch.Tensor, name: str = "ffpa_merge_attn_states") -> None:
+  """Host-side checks of a merge (types, shapes, dtypes, devices: nothing read from the device).  ``o_x [T, H, D]`` fp16 / bf16, ``lse_x [H, T]`` fp32."""
+  for nm, t in (("o_a", o_a), ("lse_a", lse_a), ("o_b", o_b), ("lse_b", lse_b)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+  if o_a.dtype not in _DTYPE or o_b.dtype != o_a.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 o_a / o_b of one dtype, got {o_a.dtype}, {o_b.dtype}")
+  if lse_a.dtype != torch.float32 or lse_b.dtype != torch.float32:
+    raise TypeError(f"{name}: lse_a / lse_b must be float32, got {lse_a.dtype}, {lse_b.dtype}")
+  if o_a.dim() != 3 or o_a.shape != o_b.shape:
+    raise ValueError(f"{name}: o_a {tuple(o_a.shape)} and o_b {tuple(o_b.shape)} must be [tokens, heads, head_dim] of one shape")
+  T, H, D = o_a.shape
+  if D % 8 != 0 or D <= 0 or D > 1024:
+    raise ValueError(f"{name}: head dim {D} is not a multiple of 8 in [8, 1024]")
+  for nm, t in (("lse_a", lse_a), ("lse_b", lse_b)):
+    if tuple(t.shape) != (H, T):
+      raise ValueError(f"{name}: {nm} must be [heads={H}, tokens={T}], got {tuple(t.shape)}")
+  dev = o_a.device
+  for nm, t in (("o_b", o_b), ("lse_a", lse_a), ("lse_b", lse_b)):
+    if t.device != dev:
+      raise ValueError(f"{name}: {nm} must be on o_a's device, got {t.device} and {dev}")
+
+
+def _merge_rows(t: torch.Tensor) -> torch.Tensor:
+  """[T, H, D] with head-dim stride 1, token / head strides multiples of 8 elements and a 16-byte aligned base — else a copy."""
+  ok = t.stride(-1) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.stride(0) >= 0 and t.stride(1) >= 0 and t.data_ptr() % 16 == 0
+  return t if ok else t.contiguous()
+
+
+def merge_states(o_a: torch.Tensor, lse_a: torch.Tensor, o_b: torch.Tensor, lse_b: torch.Tensor, return_lse: bool = True):
+  """One launch of ``ffpa_attn_merge_states``: ``(o [T, H, D], lse [H, T] fp32 | None)`` — the attention over the union of the two key sets whose attentions are
+  ``(o_a, lse_a)`` and ``(o_b, lse_b)``.  Asynchronous, nothing read back to the host."""
+  name = "ffpa_attn::_merge_states_hip"
+  check_merge_states(o_a, lse_a, o_b, lse_b, name)
+  if not o_a.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{o_a.device.type}' (the HIP kernel needs a GPU tensor)")
+  lib = load_library()
+  T, H, D = o_a.shape
+  o = torch.empty((T, H, D), dtype=o_a.dtype, device=o_a.device)
+  lse = torch.empty((H, T), dtype=torch.float32, device=o_a.device) if return_lse else None
+  if T == 0 or H == 0:
+    return o, lse
+  o_a, o_b = _merge_rows(o_a), _merge_rows(o_b)
+  lse_a = lse_a if lse_a.stride(1) == 1 and lse_a.stride(0) >= 0 else lse_a.contiguous()
+  lse_b = lse_b if lse_b.stride(1) == 1 and lse_b.stride(0) >= 0 else lse_b.contiguous()
+  p = FfpaMergeStatesParams()
+  p.struct_size = ctypes.sizeof(FfpaMergeStatesParams)
+  p.abi_version = ABI_VERSION
+  p.o_a, p.o_b, p.o = o_a.data_ptr(), o_b.data_ptr(), o.data_ptr()
+  p.lse_a, p.lse_b = lse_a.data_ptr(), lse_b.data_ptr()
+  p.lse = lse.data_ptr() if lse is not None else None
+  p.tokens, p.heads, p.head_dim = T, H, D
+  p.dtype = _DTYPE[o.dtype]
+  p.o_a_stride[:] = list(o_a.stride()[:2])
+  p.o_b_stride[:] = list(o_b.stride()[:2])
+  p.o_stride[:] = list(o.stride()[:2])
+  p.lse_a_stride_head, p.lse_b_stride_head = lse_a.stride(0), lse_b.stride(0)
+  p.lse_stride_head = lse.stride(0) if lse is not None else 0
+  with torch.cuda.device(o.device):
+    stream = torch.cuda.current_stream(o.device).cuda_stream
+    rc = lib.ffpa_attn_merge_states(ctypes.byref(p), ctypes.c_void_p(stream))
+  if rc != 0:
+    raise _STATUS_EXC.get(rc, RuntimeError)(f"ffpa_attn_merge_states: {lib.ffpa_attn_last_error().decode()} (status {rc})")
+  return o, lse
+
+
+torch.library.define(f"{_OP_NAMESPACE}::_merge_states_hip", "(Tensor o_a, Tensor lse_a, Tensor o_b, Tensor lse_b) -> (Tensor o, Tensor lse)")
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_merge_states_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _merge_states_hip_torch_op(o_a, lse_a, o_b, lse_b):
+  return merge_states(o_a, lse_a, o_b, lse_b)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_merge_states_hip")
+def _merge_states_hip_fake(o_a, lse_a, o_b, lse_b):
+  check_merge_states(o_a, lse_a, o_b, lse_b, "ffpa_attn::_merge_states_hip")
+  T, H, D = o_a.shape
+  return o_a.new_empty((T, H, D)), o_a.new_empty((H, T), dtype=torch.float32)

@@ -79,41 +79,9 @@ def _check_append(q, k_cache, k, v, rotary_cos, rotary_sin, capacity: int) -> No
     raise ValueError(f"ffpa_attn_with_kvcache: rotary_cos / rotary_sin have {rotary_cos.size(0)} rows (seqlen_ro), fewer than the cache capacity {capacity}")
 
 
-def ffpa_attn_with_kvcache(
-  q: torch.Tensor,
-  k_cache: torch.Tensor,
-  v_cache: torch.Tensor,
-  k: torch.Tensor | None = None,
-  v: torch.Tensor | None = None,
-  rotary_cos: torch.Tensor | None = None,
-  rotary_sin: torch.Tensor | None = None,
-  cache_seqlens: "int | torch.Tensor | None" = None,
-  cache_batch_idx: torch.Tensor | None = None,
-  cache_leftpad: torch.Tensor | None = None,
-  block_table: torch.Tensor | None = None,
-  softmax_scale: float | None = None,
-  causal: bool = False,
-  window_size: tuple = (-1, -1),
-  softcap: float = 0.0,
-  rotary_interleaved: bool = True,
-  alibi_slopes: torch.Tensor | None = None,
-  num_splits: int = 0,
-  return_softmax_lse: bool = False,
-):
-  """Attention of ``q [B, Sq, Hq, D]`` against a KV cache: ``k_cache`` / ``v_cache [B, capacity, Hkv, D]`` without ``block_table``, or the page pools
-  ``[num_pages, page_size, Hkv, D]`` with an int32 ``block_table [B, pages_per_seq]`` (``page_size`` a multiple of 64; key j of sequence b is row
-  ``j % page_size`` of page ``block_table[b, j // page_size]``).  ``cache_seqlens``: an int, or an int32 ``[B]`` device tensor, of keys per sequence (None = the
-  whole capacity).  ``causal`` is bottom-right aligned: query i of a sequence of ``Sq`` queries and ``L`` keys sees keys ``j <= i + L - Sq``.  GQA when
-  ``Hq % Hkv == 0``.  ``num_splits``: 0 = the library decides, 1 = never split the keys, n = at most n ranges.  Returns ``out [B, Sq, Hq, D]`` — and the
-  fp32 ``softmax_lse [B, Hq, Sq]`` with ``return_softmax_lse``.  Rows that see no key come out as 0 (LSE -inf).
-
-  ``k`` / ``v [B, Snew, Hkv, D]`` (the cache's dtype, last dim contiguous; ``cache_seqlens`` required): key i of sequence b is written in place at position
-  ``pos = cache_seqlens[b] + i`` (row ``pos`` of ``k_cache[b]``, or row ``pos % page_size`` of page ``block_table[b, pos // page_size]``; positions at or past the
-  capacity are dropped, negative lengths act as 0), then attention runs over ``min(cache_seqlens[b] + Snew, capacity)`` keys.  ``cache_seqlens`` is not modified.
-  Two sequences that append into one shared page race: the caller's problem, as with FlashAttention.  ``rotary_cos`` / ``rotary_sin [seqlen_ro, rotary_dim / 2]``
-  (q's dtype, contiguous, ``rotary_dim`` a multiple of 16 <= D, ``seqlen_ro`` >= the capacity): the first ``rotary_dim`` dims of the new keys (stored rotated) and of
-  q (a rotated copy attends; q is not modified) are rotated — key i at position ``cache_seqlens[b] + i``, query token i at ``cache_seqlens[b] + i`` when
-  ``causal``, at ``cache_seqlens[b]`` otherwise; ``rotary_interleaved`` pairs dims (2j, 2j + 1), else (j, j + rotary_dim / 2) (GPT-NeoX).  V is never rotated."""
+def _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, cache_batch_idx, cache_leftpad, block_table, softmax_scale, window_size,
+              softcap, alibi_slopes, num_splits):
+  """Every host-side check of ffpa_attn_with_kvcache (nothing read from the device, nothing launched) -> (capacity, seqused, softmax scale)."""
   bad = _unsupported(k, v, rotary_cos, rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes)
   if bad:
     raise NotImplementedError(f"ffpa_attn_with_kvcache does not support: {', '.join(bad)} (k and v only together, rotary_cos and rotary_sin only together "
@@ -170,18 +138,32 @@ def ffpa_attn_with_kvcache(
     raise TypeError(f"ffpa_attn_with_kvcache: cache_seqlens must be an int or an int32 tensor, got {type(cache_seqlens).__name__}")
   scale = float(softmax_scale) if softmax_scale is not None else D ** -0.5
 
-  from . import hip  # (registers the ffpa_attn ops)
-
   if k is not None:
     if cache_seqlens is None:
       raise ValueError("ffpa_attn_with_kvcache: cache_seqlens is required with k / v (it gives where the new keys go)")
     _check_append(q, k_cache, k, v, rotary_cos, rotary_sin, capacity)
+  return capacity, seqused, scale
+
+
+def _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal):
+  """The prepare launch (with k / v): new keys into the cache (in place), rotated q, post-append lengths -> (q to attend with, key lengths)."""
+  from . import hip  # (registers the ffpa_attn ops)
+
+  if k is not None:
     # the prepare launch: new keys into the cache (in place), rotated q, post-append lengths — read by the attention launch below on the same stream
     q_rot, seqused = torch.ops.ffpa_attn._kvcache_append_hip(q, k_cache, v_cache, k, v, seqused, block_table, rotary_cos, rotary_sin, bool(rotary_interleaved),
                                                              bool(causal))
     if rotary_cos is not None:
       q = q_rot
+  return q, seqused
 
+
+def _attend(q, k_cache, v_cache, seqused, block_table, capacity, scale, causal, num_splits, return_lse):
+  """The attention launch of ffpa_attn_with_kvcache -> packed ``(o [B * Sq, Hq, D], lse [Hq, B * Sq] | None)``."""
+  from . import hip
+
+  B, Sq, Hq, D = q.shape
+  Hkv = k_cache.size(2)
   qp = q.reshape(B * Sq, Hq, D)
   cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device) if Sq > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
   if block_table is not None:
@@ -190,9 +172,202 @@ def ffpa_attn_with_kvcache(
     # the contiguous cache is the packed call's seqused_k case: sequence b's keys are rows b * capacity ... of the cache viewed as [B * capacity, Hkv, D]
     kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
     cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
-    o, lse = hip.varlen_forward(qp, kp, vp, cu_q, cu_k, Sq, capacity, bool(causal), scale, return_lse=return_softmax_lse, seqused_k=seqused,
+    o, lse = hip.varlen_forward(qp, kp, vp, cu_q, cu_k, Sq, capacity, bool(causal), scale, return_lse=return_lse, seqused_k=seqused,
                                 num_splits=num_splits)
+  return o, lse
+
+
+def ffpa_attn_with_kvcache(
+  q: torch.Tensor,
+  k_cache: torch.Tensor,
+  v_cache: torch.Tensor,
+  k: torch.Tensor | None = None,
+  v: torch.Tensor | None = None,
+  rotary_cos: torch.Tensor | None = None,
+  rotary_sin: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor | None" = None,
+  cache_batch_idx: torch.Tensor | None = None,
+  cache_leftpad: torch.Tensor | None = None,
+  block_table: torch.Tensor | None = None,
+  softmax_scale: float | None = None,
+  causal: bool = False,
+  window_size: tuple = (-1, -1),
+  softcap: float = 0.0,
+  rotary_interleaved: bool = True,
+  alibi_slopes: torch.Tensor | None = None,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+):
+  """Attention of ``q [B, Sq, Hq, D]`` against a KV cache: ``k_cache`` / ``v_cache [B, capacity, Hkv, D]`` without ``block_table``, or the page pools
+  ``[num_pages, page_size, Hkv, D]`` with an int32 ``block_table [B, pages_per_seq]`` (``page_size`` a multiple of 64; key j of sequence b is row
+  ``j % page_size`` of page ``block_table[b, j // page_size]``).  ``cache_seqlens``: an int, or an int32 ``[B]`` device tensor, of keys per sequence (None = the
+  whole capacity).  ``causal`` is bottom-right aligned: query i of a sequence of ``Sq`` queries and ``L`` keys sees keys ``j <= i + L - Sq``.  GQA when
+  ``Hq % Hkv == 0``.  ``num_splits``: 0 = the library decides, 1 = never split the keys, n = at most n ranges.  Returns ``out [B, Sq, Hq, D]`` — and the
+  fp32 ``softmax_lse [B, Hq, Sq]`` with ``return_softmax_lse``.  Rows that see no key come out as 0 (LSE -inf).
+
+  ``k`` / ``v [B, Snew, Hkv, D]`` (the cache's dtype, last dim contiguous; ``cache_seqlens`` required): key i of sequence b is written in place at position
+  ``pos = cache_seqlens[b] + i`` (row ``pos`` of ``k_cache[b]``, or row ``pos % page_size`` of page ``block_table[b, pos // page_size]``; positions at or past the
+  capacity are dropped, negative lengths act as 0), then attention runs over ``min(cache_seqlens[b] + Snew, capacity)`` keys.  ``cache_seqlens`` is not modified.
+  Two sequences that append into one shared page race: the caller's problem, as with FlashAttention.  ``rotary_cos`` / ``rotary_sin [seqlen_ro, rotary_dim / 2]``
+  (q's dtype, contiguous, ``rotary_dim`` a multiple of 16 <= D, ``seqlen_ro`` >= the capacity): the first ``rotary_dim`` dims of the new keys (stored rotated) and of
+  q (a rotated copy attends; q is not modified) are rotated — key i at position ``cache_seqlens[b] + i``, query token i at ``cache_seqlens[b] + i`` when
+  ``causal``, at ``cache_seqlens[b]`` otherwise; ``rotary_interleaved`` pairs dims (2j, 2j + 1), else (j, j + rotary_dim / 2) (GPT-NeoX).  V is never rotated."""
+  capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, cache_batch_idx, cache_leftpad, block_table,
+                                       softmax_scale, window_size, softcap, alibi_slopes, num_splits)
+  q, seqused = _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal)
+  B, Sq, Hq, D = q.shape
+  o, lse = _attend(q, k_cache, v_cache, seqused, block_table, capacity, scale, causal, num_splits, return_softmax_lse)
   out = o.view(B, Sq, Hq, D)
   if not return_softmax_lse:
     return out
   return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+# ---- cascade (shared-prefix) attention: ffpa_attn_with_kvcache_cascade
+# cascade=None takes the cascade where the K + V re-reads it saves — (B - 1) * P keys x Hkv x D x 2 (K and V) x 2 bytes, the copies of the prefix the plain
+# launch streams for sequences 1 .. B - 1 — reach _CASCADE_MIN_SAVED_BYTES.  Fitted to the interleaved A/B of tools/gpu_cascade_ab.py on MI355X
+# (profiles/r09_cascade_ab.json, "grid" rows: paged, page 64, D 512 GQA 32 / 8 and D 1024 GQA 16 / 4, B 4 / 16 / 64, Sq 1 / 4, P 2k / 8k / 32k, suffixes
+# 128 ... 2k).  All 24 shapes that save >= 1536 MiB won, in graph replay AND launched eagerly (1.16 ... 9.0 x).  Of the 12 that save <= 480 MiB, 11 lost in at
+# least one of the two (0.41 ... 1.00 x: the cascade's extra launches, ~ 25 us replayed and ~ 80 us from Python, outweigh what the Infinity Cache leaves of the
+# re-reads); the twelfth, B 16 Sq 1 P 2k D 512 (480 MiB), won narrowly (1.19 x / 1.03 x) while its Sq 4 twin lost (0.89 x / 0.85 x).  The threshold sits
+# between 480 and 1536 MiB.  The rule stays inside what was measured: paged caches, GQA groups of 4 or more, Sq <= 4, D >= 512.  Page size and groups above 4
+# are an extrapolation along the saved-bytes axis, checked by the "check" rows of the same profile (page 256; group 8).  Contiguous caches, MHA / small
+# groups, Sq > 4 and D < 512 were not measured and stay plain under None; cascade=True forces the cascade there.
+_CASCADE_MIN_SAVED_BYTES = 1 << 30
+_CASCADE_MAX_SEQLEN_Q = 4
+_CASCADE_MIN_HEAD_DIM = 512
+_CASCADE_MIN_GROUP = 4
+
+
+def cascade_rule(batch: int, seqlen_q: int, heads_q: int, heads_kv: int, head_dim: int, shared_prefix_len: int, page_size: int) -> bool:
+  """The host-side rule of ``ffpa_attn_with_kvcache_cascade(cascade=None)``: True where the cascade (prefix pass + suffix pass + merge) is expected faster than
+  the plain launch — the re-reads it saves reach 1 GiB — inside the measured envelope (``page_size`` > 0: a paged cache; ``heads_q / heads_kv`` >= 4; Sq <= 4;
+  D >= 512).  A batch of one, or no shared prefix, is always plain."""
+  if batch <= 1 or shared_prefix_len <= 0:
+    return False
+  if seqlen_q < 1 or seqlen_q > _CASCADE_MAX_SEQLEN_Q or head_dim < _CASCADE_MIN_HEAD_DIM:
+    return False
+  if page_size <= 0 or heads_kv <= 0 or heads_q // heads_kv < _CASCADE_MIN_GROUP:
+    return False
+  saved = (batch - 1) * shared_prefix_len * heads_kv * head_dim * 2 * 2
+  return saved >= _CASCADE_MIN_SAVED_BYTES
+
+
+def _merge(o_a, lse_a, o_b, lse_b):
+  return torch.ops.ffpa_attn._merge_states_hip(o_a, lse_a, o_b, lse_b)
+
+
+def ffpa_merge_attn_states(o_a: torch.Tensor, lse_a: torch.Tensor, o_b: torch.Tensor, lse_b: torch.Tensor):
+  """Merge two attention states of the same queries over two disjoint key sets (FlashInfer's / vLLM's ``merge_attn_states``): ``o_a`` / ``o_b [T, H, D]`` (bf16 or
+  fp16, one dtype; D a multiple of 8 up to 1024) with their fp32 ``lse_a`` / ``lse_b [H, T]`` (natural log; the layout ``ffpa_attn_varlen_func`` returns; any head
+  stride) -> ``(o [T, H, D], lse [H, T])``, the attention over the union of the key sets.  Per row, in fp32: ``m = max(lse_a, lse_b)``, ``w = exp(lse - m)``,
+  ``o = (w_a o_a + w_b o_b) / (w_a + w_b)`` rounded once, ``lse = m + ln(w_a + w_b)``.  A side whose LSE is -inf contributes nothing (a NaN in its O does not
+  leak); both -inf gives ``o = 0``, ``lse = -inf``.  One HIP launch, nothing read back to the host.  Inference only: a tensor that requires grad (with grad
+  mode on) raises ``NotImplementedError``."""
+  from . import hip
+
+  for name, t in (("o_a", o_a), ("lse_a", lse_a), ("o_b", o_b), ("lse_b", lse_b)):
+    if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"ffpa_merge_attn_states is inference only: {name} requires grad and there is no backward")
+  hip.check_merge_states(o_a, lse_a, o_b, lse_b)
+  return _merge(o_a, lse_a, o_b, lse_b)
+
+
+def ffpa_attn_with_kvcache_cascade(
+  q: torch.Tensor,
+  k_cache: torch.Tensor,
+  v_cache: torch.Tensor,
+  k: torch.Tensor | None = None,
+  v: torch.Tensor | None = None,
+  rotary_cos: torch.Tensor | None = None,
+  rotary_sin: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor | None" = None,
+  block_table: torch.Tensor | None = None,
+  *,
+  shared_prefix_len: int,
+  softmax_scale: float | None = None,
+  causal: bool = False,
+  rotary_interleaved: bool = True,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  cascade: "bool | None" = None,
+):
+  """``ffpa_attn_with_kvcache`` for a batch whose sequences share their first ``shared_prefix_len`` (P) keys — parallel sampling, beam search, a shared system
+  prompt under prefix caching — as CASCADE attention: the prefix is read once per KV head for the whole batch instead of once per sequence.  Three launches
+  (four with ``k`` / ``v``), nothing read back to the host, so a call captures into one HIP graph:
+
+  1. (with ``k`` / ``v``) the append of ``ffpa_attn_with_kvcache`` on the full table: its rotated q and post-append lengths feed both passes;
+  2. PREFIX pass: all ``B * Sq`` query tokens as ONE sequence against keys ``[0, P)`` of sequence 0 — pages ``block_table[0, :P / page_size]``, or rows
+     ``[0, P)`` of ``k_cache[0]`` — not causal;
+  3. SUFFIX pass: the plain launch on ``block_table[:, P / page_size:]`` (a contiguous cache: every slab from row P on, no copy) with lengths
+     ``max(len_b - P, 0)`` computed on the device, under the caller's ``causal`` (exact: the alignment is bottom-right);
+  4. the merge of the two (O, LSE) states (``ffpa_merge_attn_states``).
+
+  Everything else — arguments, shapes, returns, checks — is ``ffpa_attn_with_kvcache``'s.  Contracts (not checked: they would need a host read):
+  keys ``[0, P)`` are the same for every sequence (the same pages in every row of ``block_table``, the same rows in every slab) and are read from sequence 0
+  only; every sequence holds at least P keys; appended keys land at or past P (a write into shared pages is the caller's race, as in FlashAttention); under
+  ``causal`` every sequence's suffix holds at least its ``Sq`` query tokens.  A paged cache needs P to be a multiple of ``page_size``.
+
+  ``cascade``: False = exactly ``ffpa_attn_with_kvcache`` (the same launch, the same bits); True = the cascade (P = 0, or P = the capacity, leaves one key set:
+  the plain launch); None = ``cascade_rule`` — measured on MI355X, it takes the cascade only where it won.  The cascade differs from the plain launch by
+  rounding only: two normalised partial states merged in fp32 instead of one pass."""
+  if isinstance(shared_prefix_len, bool) or not isinstance(shared_prefix_len, int):
+    raise TypeError(f"ffpa_attn_with_kvcache_cascade: shared_prefix_len must be an int, got {type(shared_prefix_len).__name__}")
+  if shared_prefix_len < 0:
+    raise ValueError(f"ffpa_attn_with_kvcache_cascade: shared_prefix_len must be non-negative, got {shared_prefix_len}")
+  if cascade is not None and not isinstance(cascade, bool):
+    raise TypeError(f"ffpa_attn_with_kvcache_cascade: cascade must be True, False or None, got {cascade!r}")
+  capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, None, None, block_table, softmax_scale, (-1, -1), 0.0,
+                                       None, num_splits)
+  P = shared_prefix_len
+  B, Sq, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  page_size = k_cache.size(1) if block_table is not None else 0
+  if P > capacity:
+    raise ValueError(f"ffpa_attn_with_kvcache_cascade: shared_prefix_len ({P}) exceeds the cache capacity ({capacity})")
+  if block_table is not None and P % page_size != 0:
+    raise ValueError(f"ffpa_attn_with_kvcache_cascade: shared_prefix_len ({P}) must be a multiple of page_size ({page_size}) in a paged cache")
+  if cascade is False:
+    return ffpa_attn_with_kvcache(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, block_table=block_table, softmax_scale=softmax_scale,
+                                  causal=causal, rotary_interleaved=rotary_interleaved, num_splits=num_splits, return_softmax_lse=return_softmax_lse)
+  use = cascade_rule(B, Sq, Hq, Hkv, D, P, page_size) if cascade is None else True
+  use = use and 0 < P < capacity and B * Sq > 0
+  q, seqused = _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal)
+  if not use:
+    o, lse = _attend(q, k_cache, v_cache, seqused, block_table, capacity, scale, causal, num_splits, return_softmax_lse)
+  else:
+    o, lse = _cascade(q, k_cache, v_cache, seqused, block_table, capacity, P, scale, causal, num_splits)
+  out = o.view(B, Sq, Hq, D)
+  if not return_softmax_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+def _cascade(q, k_cache, v_cache, seqused, block_table, capacity, P, scale, causal, num_splits):
+  """The prefix pass, the suffix pass and the merge -> packed ``(o [B * Sq, Hq, D], lse [Hq, B * Sq])``.  0 < P < capacity, B * Sq > 0."""
+  from . import hip
+
+  B, Sq, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  dev = q.device
+  T = B * Sq
+  qp = q.reshape(T, Hq, D)
+  # the prefix pass: one sequence of T query tokens against keys [0, P) of sequence 0 (lengths and boundaries made on the device: nothing crosses to the host)
+  cu_pre = torch.arange(0, 2 * T, T, dtype=torch.int32, device=dev)
+  # the suffix pass: keys from P on, lengths len_b - P (clamped to what the suffix can hold, as the plain launch clamps to the capacity)
+  used_suf = (seqused - P).clamp(0, capacity - P)
+  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=dev)
+  if block_table is not None:
+    pp = P // k_cache.size(1)
+    used_pre = torch.full((1,), P, dtype=torch.int32, device=dev)
+    o_p, lse_p = torch.ops.ffpa_attn._paged_fwd_hip(qp, k_cache, v_cache, cu_pre, used_pre, block_table[:1, :pp], T, P, scale, 0, -1.0, num_splits)
+    o_s, lse_s = torch.ops.ffpa_attn._paged_fwd_hip(qp, k_cache, v_cache, cu_q, used_suf, block_table[:, pp:], Sq, capacity - P, scale, 1 if causal else 0, -1.0,
+                                                    num_splits)
+  else:
+    cu_kp = torch.arange(0, 2 * P, P, dtype=torch.int32, device=dev)
+    o_p, lse_p = hip.varlen_forward(qp, k_cache[0, :P], v_cache[0, :P], cu_pre, cu_kp, T, P, False, scale, num_splits=num_splits)
+    # sequence b's suffix: rows b * capacity + P ... of the cache viewed as [B * capacity, Hkv, D] — the same boundaries as the plain launch, shifted by P rows
+    kp, vp = k_cache.reshape(B * capacity, Hkv, D)[P:], v_cache.reshape(B * capacity, Hkv, D)[P:]
+    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=dev)
+    o_s, lse_s = hip.varlen_forward(qp, kp, vp, cu_q, cu_k, Sq, capacity - P, bool(causal), scale, seqused_k=used_suf, num_splits=num_splits)
+  return _merge(o_p, lse_p, o_s, lse_s)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define FFPA_ATTN_ABI_VERSION 7 /* 5: + the packed-sequence entry points (ffpa_attn_varlen_fwd ...); 6: + KV splits inside the packed call (its workspace fields, ffpa_attn_varlen_fwd_workspace_bytes, plan out[4]); 7: + the paged-KV call (ffpa_paged_kv, ffpa_attn_varlen_paged_fwd ...), + the KV-cache append (ffpa_kv_append_params, ffpa_attn_kvcache_append: its own size-checked struct, no existing layout changed) */
+#define FFPA_ATTN_ABI_VERSION 7 /* 5: + the packed-sequence entry points (ffpa_attn_varlen_fwd ...); 6: + KV splits inside the packed call (its workspace fields, ffpa_attn_varlen_fwd_workspace_bytes, plan out[4]); 7: + the paged-KV call (ffpa_paged_kv, ffpa_attn_varlen_paged_fwd ...), + the KV-cache append (ffpa_kv_append_params, ffpa_attn_kvcache_append: its own size-checked struct, no existing layout changed), + the merge of two attention states (ffpa_merge_states_params, ffpa_attn_merge_states: likewise) */
 
 /* status codes (0 == success).  The Python host maps them onto the exception
  * classes the reference raises (TORCH_CHECK -> RuntimeError,
@@ -403,6 +403,45 @@ typedef struct ffpa_kv_append_params {
 /* Launch the append on `stream` of the CURRENT device (kv: the paged pool, NULL = contiguous cache).  Asynchronous: no allocation, no synchronisation; every
  * bad argument returns a status before any device work.  Returns an ffpa_status. */
 int ffpa_attn_kvcache_append(const ffpa_kv_append_params* p, const ffpa_paged_kv* kv, void* stream);
+
+/*
+ * MERGE OF TWO ATTENTION STATES (FlashInfer's / vLLM's merge_attn_states) — the last launch of a cascade (shared-prefix) attention step: two attentions of the
+ * same queries over two disjoint key sets, each normalised on its own, combined into the attention over the union.  Per (token t, head h) row, in fp32:
+ *     m = max(lse_a, lse_b),  w_x = exp(lse_x - m),  O = (w_a O_a + w_b O_b) / (w_a + w_b),  LSE = m + ln(w_a + w_b)
+ * with ONE rounding of O to the dtype.  A side whose LSE is -inf (it saw no key) has weight 0 and its O is not read into the sum (a NaN there does not leak);
+ * both sides -inf gives O = 0, LSE = -inf — the packed call's empty-row contract.
+ *   * o_a, o_b, o: [tokens, heads, head_dim] by {token, head} element strides (head-dim stride 1), one dtype (bf16 / fp16); head_dim a multiple of 8 in [8, 1024];
+ *     every stride a multiple of 8 elements and every base 16-byte aligned (16-byte loads and stores).
+ *   * lse_a, lse_b, lse: fp32 [heads, tokens] by a head stride (token stride 1) — the layout ffpa_attn_varlen_fwd stores; natural-log units.  lse may be NULL.
+ * The outputs must not overlap the inputs.
+ */
+typedef struct ffpa_merge_states_params {
+  uint32_t struct_size; /* sizeof(ffpa_merge_states_params), checked */
+  uint32_t abi_version; /* FFPA_ATTN_ABI_VERSION                      */
+
+  const void* o_a;      /* [tokens, heads, head_dim] */
+  const void* o_b;
+  void* o;              /* out */
+  const float* lse_a;   /* [heads, tokens] fp32 */
+  const float* lse_b;
+  float* lse;           /* out, may be NULL */
+
+  int32_t tokens;       /* >= 0 (0: nothing to do) */
+  int32_t heads;        /* >= 0 (0: nothing to do) */
+  int32_t head_dim;     /* a multiple of 8 in [8, 1024] */
+  int32_t dtype;        /* enum ffpa_dtype: o_a, o_b, o */
+
+  int64_t o_a_stride[2]; /* elements: token, head */
+  int64_t o_b_stride[2];
+  int64_t o_stride[2];
+  int64_t lse_a_stride_head; /* elements */
+  int64_t lse_b_stride_head;
+  int64_t lse_stride_head;   /* >= tokens when heads > 1 (rows of the output do not overlap); ignored when lse == NULL */
+} ffpa_merge_states_params;
+
+/* Launch the merge on `stream` of the CURRENT device.  Asynchronous: no allocation, no synchronisation; every bad argument returns a status before any device
+ * work.  Returns an ffpa_status. */
+int ffpa_attn_merge_states(const ffpa_merge_states_params* p, void* stream);
 
 /* Capability / build queries.  Replaces the module attributes
  * CUDA_FWD_AVAILABLE, F16_ACC_AVAILABLE, ... (csrc/cuffpa/ffpa_api.cc:283-305). */
