@@ -13,6 +13,7 @@ Usage:  python -m ffpa_attn_amd.build [--force] [--jobs N] [--no-test-lib]
 from __future__ import annotations
 
 import argparse
+import collections
 import os
 import re
 import shutil
@@ -46,6 +47,44 @@ CXXFLAGS = [
   f"-I{INCLUDE}",
   f"-I{CSRC}",
 ]
+
+# One row per translation unit: source under csrc/, object under csrc/build/, its own -D defines, the directory its -save-temps output lands in (None: not kept;
+# the attention ISA rules read every *.s of temps_d<D>, so the packed and paged kernels' assembly lands next to the dense TU's), the head dim it instantiates,
+# and which library links it.  The rows are in link order.
+Unit = collections.namedtuple("Unit", "src obj defs temps dim product test")
+
+
+def _units() -> list[Unit]:
+  units = []
+  for d in HEAD_DIMS:
+    inst = [f"-DFFPA_INST_D={d}"]
+    safe = d in SAFE_HEAD_DIMS  # (the test library links the twin that carries the SAFE kernels instead)
+    units.append(Unit("ffpa_fwd_inst.hip", f"ffpa_fwd_d{d}.o", inst, f"temps_d{d}", d, True, not safe))
+    if safe:
+      units.append(Unit("ffpa_fwd_inst.hip", f"ffpa_fwd_d{d}_test.o", inst + ["-DFFPA_INST_SAFE=1"], None, d, False, True))
+  # the packed-sequence kernel and its paged-KV twin: a TU of their own per head dim of the 16x16x32 build
+  for kind in ("varlen", "paged"):
+    units += [Unit(f"ffpa_{kind}_inst.hip", f"ffpa_{kind}_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d in VARLEN_HEAD_DIMS]
+  # the KV-cache append + rotary launch (every dtype / rotary form) and the merge of two attention states (the cascade's last launch): one small TU each, no
+  # inline asm — their assembly lands in directories the attention ISA rules do not read
+  units.append(Unit("ffpa_kvcache_append.hip", "ffpa_kvcache_append.o", [], "temps_append", None, True, True))
+  units.append(Unit("ffpa_merge_states.hip", "ffpa_merge_states.o", [], "temps_merge", None, True, True))
+  units.append(Unit("ffpa_capi.hip", "ffpa_capi.o", [], None, None, True, False))
+  units.append(Unit("ffpa_capi.hip", "ffpa_capi_test.o", ["-DFFPA_INST_SAFE=1"], None, None, False, True))
+  return units
+
+
+UNITS = _units()
+# the product define: the kernel headers then refuse any developer switch that is not at its shipped default
+PRODUCT_DEFS = ["-DFFPA_PRODUCT_BUILD=1"]
+
+
+def _compile_cmd(hipcc: str, u: Unit, defs: list[str], obj: str, save_temps: bool = False) -> list[str]:
+  return [hipcc, *CXXFLAGS, *defs, *(["-save-temps"] if save_temps and u.temps else []), *u.defs, "-c", os.path.join(CSRC, u.src), "-o", obj]
+
+
+def _link(hipcc: str, lib: str, objs: list[str]) -> None:
+  _run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib, *objs, "-Wl,-rpath,/opt/rocm/lib"])
 
 
 def _hipcc() -> str:
@@ -102,7 +141,7 @@ def _prune_temps() -> None:
   import glob
   import gzip
 
-  for tdir in glob.glob(os.path.join(OBJ_DIR, "temps_d*")) + glob.glob(os.path.join(OBJ_DIR, "temps_append")) + glob.glob(os.path.join(OBJ_DIR, "temps_merge")):
+  for tdir in glob.glob(os.path.join(OBJ_DIR, "temps_*")):
     for path in glob.glob(os.path.join(tdir, "*")):
       if path.endswith("gfx950.s"):
         with open(path, "rb") as src, gzip.open(path + ".gz", "wb", compresslevel=6) as dst:
@@ -146,78 +185,14 @@ def build(force: bool = False, jobs: int | None = None, save_temps: bool = True,
   os.makedirs(OBJ_DIR, exist_ok=True)
   jobs = jobs or max(1, (os.cpu_count() or 4))
   tasks: list[tuple[str, list[str], str | None]] = []
-  objs: list[str] = []
-  test_objs: list[str] = []
-  extra = ["-save-temps"] if save_temps else []  # temps land in the compile's cwd (one dir per TU)
-
-  def stale(obj: str) -> bool:
-    return force or not os.path.exists(obj) or os.path.getmtime(obj) < newest
-
-  # the product define: the kernel headers then refuse any developer switch that is not at its shipped default
-  product = ["-DFFPA_PRODUCT_BUILD=1"]
-  for d in HEAD_DIMS:
-    obj = os.path.join(OBJ_DIR, f"ffpa_fwd_d{d}.o")
-    objs.append(obj)
-    if stale(obj):
-      tmp = os.path.join(OBJ_DIR, f"temps_d{d}")
-      os.makedirs(tmp, exist_ok=True)
-      tasks.append((obj, [hipcc, *CXXFLAGS, *product, *extra, f"-DFFPA_INST_D={d}", "-c", os.path.join(CSRC, "ffpa_fwd_inst.hip"), "-o", obj], tmp))
-    if test_lib and d in SAFE_HEAD_DIMS:
-      tobj = os.path.join(OBJ_DIR, f"ffpa_fwd_d{d}_test.o")
-      test_objs.append(tobj)
-      if stale(tobj):
-        tasks.append((tobj, [hipcc, *CXXFLAGS, *product, f"-DFFPA_INST_D={d}", "-DFFPA_INST_SAFE=1", "-c", os.path.join(CSRC, "ffpa_fwd_inst.hip"), "-o", tobj], None))
-    elif test_lib:
-      test_objs.append(obj)
-  # the packed-sequence kernel (ffpa_varlen_inst.hip): a TU of its own per head dim of the 16x16x32 build, so that the dense kernels' objects stay what they were;
-  # its device assembly lands next to the dense TU's (temps_d<D>: the ISA rules read every *.s of a head dim)
-  for d in VARLEN_HEAD_DIMS:
-    obj = os.path.join(OBJ_DIR, f"ffpa_varlen_d{d}.o")
-    objs.append(obj)
-    if test_lib:
-      test_objs.append(obj)
-    if stale(obj):
-      tmp = os.path.join(OBJ_DIR, f"temps_d{d}")
-      os.makedirs(tmp, exist_ok=True)
-      tasks.append((obj, [hipcc, *CXXFLAGS, *product, *extra, f"-DFFPA_INST_D={d}", "-c", os.path.join(CSRC, "ffpa_varlen_inst.hip"), "-o", obj], tmp))
-  # the paged-KV twin of the packed-sequence kernel (ffpa_paged_inst.hip): a TU of its own per head dim, so that the dense and packed objects stay what they were
-  for d in VARLEN_HEAD_DIMS:
-    obj = os.path.join(OBJ_DIR, f"ffpa_paged_d{d}.o")
-    objs.append(obj)
-    if test_lib:
-      test_objs.append(obj)
-    if stale(obj):
-      tmp = os.path.join(OBJ_DIR, f"temps_d{d}")
-      os.makedirs(tmp, exist_ok=True)
-      tasks.append((obj, [hipcc, *CXXFLAGS, *product, *extra, f"-DFFPA_INST_D={d}", "-c", os.path.join(CSRC, "ffpa_paged_inst.hip"), "-o", obj], tmp))
-  # the KV-cache append + rotary launch (ffpa_kvcache_append.hip): one small TU, every dtype / rotary form; its assembly lands in temps_append (the attention
-  # ISA rules read temps_d<D> only: this kernel has no inline asm)
-  append = os.path.join(OBJ_DIR, "ffpa_kvcache_append.o")
-  objs.append(append)
-  if test_lib:
-    test_objs.append(append)
-  if stale(append):
-    tmp = os.path.join(OBJ_DIR, "temps_append")
-    os.makedirs(tmp, exist_ok=True)
-    tasks.append((append, [hipcc, *CXXFLAGS, *product, *extra, "-c", os.path.join(CSRC, "ffpa_kvcache_append.hip"), "-o", append], tmp))
-  # the merge of two attention states (ffpa_merge_states.hip, the cascade's last launch): one small TU, both dtypes; its assembly lands in temps_merge
-  merge = os.path.join(OBJ_DIR, "ffpa_merge_states.o")
-  objs.append(merge)
-  if test_lib:
-    test_objs.append(merge)
-  if stale(merge):
-    tmp = os.path.join(OBJ_DIR, "temps_merge")
-    os.makedirs(tmp, exist_ok=True)
-    tasks.append((merge, [hipcc, *CXXFLAGS, *product, *extra, "-c", os.path.join(CSRC, "ffpa_merge_states.hip"), "-o", merge], tmp))
-  capi = os.path.join(OBJ_DIR, "ffpa_capi.o")
-  objs.append(capi)
-  if stale(capi):
-    tasks.append((capi, [hipcc, *CXXFLAGS, *product, "-c", os.path.join(CSRC, "ffpa_capi.hip"), "-o", capi], None))
-  if test_lib:
-    tcapi = os.path.join(OBJ_DIR, "ffpa_capi_test.o")
-    test_objs.append(tcapi)
-    if stale(tcapi):
-      tasks.append((tcapi, [hipcc, *CXXFLAGS, *product, "-DFFPA_INST_SAFE=1", "-c", os.path.join(CSRC, "ffpa_capi.hip"), "-o", tcapi], None))
+  units = [u for u in UNITS if u.product or test_lib]
+  for u in units:
+    obj = os.path.join(OBJ_DIR, u.obj)
+    if force or not os.path.exists(obj) or os.path.getmtime(obj) < newest:
+      tmp = os.path.join(OBJ_DIR, u.temps) if save_temps and u.temps else None  # temps land in the compile's cwd (one dir per TU)
+      if tmp:
+        os.makedirs(tmp, exist_ok=True)
+      tasks.append((obj, _compile_cmd(hipcc, u, PRODUCT_DEFS, obj, save_temps), tmp))
   if verbose:
     print(f"[ffpa_attn_amd.build] compiling {len(tasks)} objects for {ARCH} with {jobs} jobs", flush=True)
   # longest jobs first (head dims >= 320 carry the 16x16x32 builds as well: 2 - 3 x the compile time of the small ones)
@@ -231,9 +206,9 @@ def build(force: bool = False, jobs: int | None = None, save_temps: bool = True,
   if save_temps:
     _check_isa(verbose)
     _prune_temps()
-  _run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB_PATH, *objs, "-Wl,-rpath,/opt/rocm/lib"])
+  _link(hipcc, LIB_PATH, [os.path.join(OBJ_DIR, u.obj) for u in units if u.product])
   if test_lib:
-    _run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", TEST_LIB_PATH, *test_objs, "-Wl,-rpath,/opt/rocm/lib"])
+    _link(hipcc, TEST_LIB_PATH, [os.path.join(OBJ_DIR, u.obj) for u in units if u.test])
   if verbose:
     print(f"[ffpa_attn_amd.build] linked {LIB_PATH}" + (f" and {TEST_LIB_PATH}" if test_lib else ""), flush=True)
   return LIB_PATH
@@ -256,35 +231,21 @@ def build_variant(tag: str, defs: list[str], jobs: int | None = None, head_dims:
   same_defs = os.path.exists(stamp) and open(stamp).read() == key
   if same_defs and os.path.exists(lib) and os.path.getmtime(lib) >= newest:
     return lib
-  if head_dims:
-    # the untouched head dims come from the main build (whose objects a round-end clean_dev() may have removed: rebuilt then)
-    missing = [d for d in HEAD_DIMS if d not in head_dims and not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_fwd_d{d}.o"))]
-    missing += [d for d in VARLEN_HEAD_DIMS if not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_varlen_d{d}.o"))]
-    missing += [d for d in VARLEN_HEAD_DIMS if not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_paged_d{d}.o"))]
-    missing += [] if os.path.exists(os.path.join(OBJ_DIR, "ffpa_kvcache_append.o")) else ["kvcache_append"]
-    missing += [] if os.path.exists(os.path.join(OBJ_DIR, "ffpa_merge_states.o")) else ["merge_states"]
-    build(force=bool(missing), verbose=False)
-  elif any(not os.path.exists(os.path.join(OBJ_DIR, f"ffpa_{k}_d{d}.o")) for d in VARLEN_HEAD_DIMS for k in ("varlen", "paged")) or \
-      not os.path.exists(os.path.join(OBJ_DIR, "ffpa_kvcache_append.o")) or not os.path.exists(os.path.join(OBJ_DIR, "ffpa_merge_states.o")):
-    build(force=True, verbose=False)
-  tasks, objs = [], []
-  for d in HEAD_DIMS:
-    if head_dims and d not in head_dims:
-      objs.append(os.path.join(OBJ_DIR, f"ffpa_fwd_d{d}.o"))
-      continue
-    obj = os.path.join(odir, f"ffpa_fwd_d{d}.o")
-    objs.append(obj)
-    tasks.append([hipcc, *CXXFLAGS, *defs, f"-DFFPA_INST_D={d}", "-c", os.path.join(CSRC, "ffpa_fwd_inst.hip"), "-o", obj])
-  objs += [os.path.join(OBJ_DIR, f"ffpa_varlen_d{d}.o") for d in VARLEN_HEAD_DIMS]  # (the packed-sequence kernels: the main build's, never a variant's)
-  objs += [os.path.join(OBJ_DIR, f"ffpa_paged_d{d}.o") for d in VARLEN_HEAD_DIMS]  # (and their paged twins)
-  objs.append(os.path.join(OBJ_DIR, "ffpa_kvcache_append.o"))  # (and the KV-cache append)
-  objs.append(os.path.join(OBJ_DIR, "ffpa_merge_states.o"))  # (and the merge of two attention states)
-  capi = os.path.join(odir, "ffpa_capi.o")
-  objs.append(capi)
-  tasks.append([hipcc, *CXXFLAGS, *defs, "-c", os.path.join(CSRC, "ffpa_capi.hip"), "-o", capi])  # (the plan must see the same tunables as the kernels)
+  # what the variant compiles itself: the dense TUs of its head dims and the C-ABI object (the plan must see the same tunables as the kernels); everything else —
+  # the untouched head dims, the packed-sequence kernels and their paged twins, the KV-cache append, the state merge — is the main build's object, never a
+  # variant's (a round-end clean_dev() may have removed them: rebuilt then)
+  def own(u: Unit) -> bool:
+    return u.src == "ffpa_capi.hip" or (u.src == "ffpa_fwd_inst.hip" and (not head_dims or u.dim in head_dims))
+
+  units = [u for u in UNITS if u.product]
+  missing = any(not own(u) and not os.path.exists(os.path.join(OBJ_DIR, u.obj)) for u in units)
+  if head_dims or missing:
+    build(force=missing, verbose=False)
+  objs = [os.path.join(odir if own(u) else OBJ_DIR, u.obj) for u in units]
+  tasks = [_compile_cmd(hipcc, u, defs, os.path.join(odir, u.obj)) for u in units if own(u)]
   with ThreadPoolExecutor(max_workers=jobs or (os.cpu_count() or 4)) as pool:
     list(pool.map(_run, tasks))
-  _run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib, *objs, "-Wl,-rpath,/opt/rocm/lib"])
+  _link(hipcc, lib, objs)
   with open(stamp, "w") as f:
     f.write(key)
   return lib

@@ -554,20 +554,35 @@ Plan make_plan(const ffpa_fwd_params* p, const DimEntry* de) {
   return pl;
 }
 
-// Shape / dtype checks shared by the launch and the queries.  Returns FFPA_OK or a status.
-int check_basic(const ffpa_fwd_params* p, const DimEntry** de_out) {
+// Shape checks shared by the launch and the queries; `launch`: with the launch's own pointer / dtype / head-ratio checks, each at the place in the order the call
+// has always reported it.  Returns FFPA_OK or a status.
+int check_basic(const ffpa_fwd_params* p, const DimEntry** de_out, bool launch = false) {
   if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
   if (p->struct_size != sizeof(ffpa_fwd_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
     return fail(FFPA_ERR_BAD_ABI, "ffpa_fwd_params ABI mismatch: size %u (want %zu), version %u (want %d)",
                 p->struct_size, sizeof(ffpa_fwd_params), p->abi_version, FFPA_ATTN_ABI_VERSION);
+  if (launch && (!p->q || !p->k || !p->v || !p->o)) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
+  if (launch && p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16)
+    return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
   if (p->batch <= 0 || p->heads_q <= 0 || p->heads_kv <= 0 || p->seqlen_q <= 0 || p->seqlen_kv <= 0)
     return fail(FFPA_ERR_BAD_SHAPE, "non-positive dimension: B=%d Hq=%d Hkv=%d Nq=%d Nkv=%d", p->batch, p->heads_q,
                 p->heads_kv, p->seqlen_q, p->seqlen_kv);
+  if (launch && p->heads_q % p->heads_kv != 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "num_heads: Hq=%d is not a multiple of Hkv=%d", p->heads_q, p->heads_kv);
   const DimEntry* de = find_dim(p->head_dim);
   if (de == nullptr)
     return fail(FFPA_ERR_BAD_HEADDIM, "headdim not support! D=%d (supported: multiples of 8 in [8, 1024])", p->head_dim);
   *de_out = de;
   return FFPA_OK;
+}
+
+// "Plan as if the caller had unlimited scratch": what the *_workspace_bytes / *_split_tickets queries size for (either parameter struct)
+template <typename P>
+P with_unlimited_scratch(const P& params) {
+  P q = params;
+  q.workspace = reinterpret_cast<void*>(16);
+  q.workspace_bytes = ~0ull;
+  return q;
 }
 
 // Dropout keeps the element of Philox word w when u(w) = ((float)w + 1.0f) * 2^-32 > p (prefill.cuh:437-440).  u is monotone in w
@@ -586,8 +601,8 @@ uint32_t dropout_keep_threshold(float p) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-int check_strides(const char* name, const int64_t s[3]) {
-  for (int i = 0; i < 3; ++i) {
+int check_strides(const char* name, const int64_t* s, int n) {
+  for (int i = 0; i < n; ++i) {
     if (s[i] < 0) return fail(FFPA_ERR_BAD_STRIDE, "%s stride[%d]=%lld is negative", name, i, (long long)s[i]);
     if (s[i] % 8 != 0)
       return fail(FFPA_ERR_BAD_STRIDE, "%s stride[%d]=%lld is not a multiple of 8 elements (16 bytes)", name, i,
@@ -596,31 +611,70 @@ int check_strides(const char* name, const int64_t s[3]) {
   return FFPA_OK;
 }
 
+// The softmax scale as the 16x16x32 build takes it: it folds the scale into its exponent (needs scale > 0) and takes additive biases in units of 1 / scale: a zero
+// scale (scores = bias) reaches it as "Q = 0, scale = 1", a negative one as "-Q, |scale|" — the same scores
+void fold_scale(ffpa::FwdArgs& a, float softmax_scale) {
+  if (softmax_scale == 0.f) {
+    a.scale_log2 = 1.4426950408889634f;
+    a.q_mode = 1;
+  } else {
+    const float mag = fabsf(softmax_scale);  // a negative scale: (-Q, |scale|) — exact, and the kernel's fused exponent needs scale > 0
+    a.scale_log2 = mag * 1.4426950408889634f;
+    a.inv_scale = (float)(1.0 / (double)mag);
+    if (softmax_scale < 0.f) a.q_mode = 2;
+  }
+}
+
+// XCDs per head (xcd_logical_id, ffpa_common.h).  One XCD per head keeps a head's K/V stream in one L2; but then eight heads are in flight chip-wide,
+// and once their K + V no longer fit the Infinity Cache the second and later rounds of a head's row tiles come from HBM instead (config 3: eight heads x
+// 32 MiB = the whole 256 MiB).  Launches with at least two rounds of row tiles per head and XCD (`share`: the caller's side of that rule) therefore share a head
+// between the smallest power-of-two number of XCDs that brings the K + V in flight under 200 MiB (measured, profiles/r03_xcd_group.txt).  The packed call prices
+// the longest sequence the caller announces.
+int pick_xcd_group(unsigned flags, bool share, int64_t seqlen_kv, int head_dim) {
+  int g = 1;
+  const unsigned forced = (flags >> 8) & 7u;
+  if (forced != 0) {
+    g = 1 << (forced - 1 > 3 ? 3 : forced - 1);
+  } else if (share) {
+    const double kv_mib = 2.0 * (double)seqlen_kv * (double)head_dim * 2.0 / 1048576.0;  // K + V of one (batch, kv head)
+    while (g < 8 && (8 / g) * kv_mib > 200.0) g *= 2;
+  }
+  return g;
+}
+
+// The split-D tiles (D > 512) give a DMA piece less than a microsecond to land (32-key steps, single K / V buffers): their launches touch the
+// tile two steps ahead (ffpa_fwd_m16_kernel.h, "L2 prefetch").  Measured, same library with and without (profiles/r03_l2_prefetch.txt):
+// D = 576 ... 1024: + 3 ... 9 % (D = 768: +- 0), every shape tried (self, cross, GQA, batch 4, causal, key bias); D <= 512: - 1 ... 2 %, off.
+int pick_l2_prefetch(unsigned flags, bool split_d_tiles) {
+  return (flags & FFPA_FLAG_NO_L2_PREFETCH) ? 0 : ((flags & FFPA_FLAG_L2_PREFETCH) || split_d_tiles) ? 1 : 0;
+}
+
+// What a launcher of ffpa_launch.h returned (0, -1 ... -4, or a hipError_t) as a status + message.  lds >= 0: the message names the LDS size the launch asked
+// for; safe_d > 0: -3 is "this build does not exist" for head dim safe_d (the dense call, whose debug twins are built for a few head dims only).
+int launch_status(int st, int lds, int safe_d) {
+  if (st == 0) return FFPA_OK;
+  if (st == -3 && safe_d > 0) return fail(FFPA_ERR_UNSUPPORTED, "debug safe-path kernel is not built for D=%d / this dtype", safe_d);
+  if (st == -2) {
+    char size[16] = "";
+    if (lds >= 0) snprintf(size, sizeof(size), "=%d", lds);
+    return fail(FFPA_ERR_LAUNCH, "hipFuncSetAttribute(MaxDynamicSharedMemorySize%s) failed (is this a gfx950?)", size);
+  }
+  if (st < 0) return fail(FFPA_ERR_LAUNCH, "launch setup failed (%d)", st);
+  return fail(FFPA_ERR_LAUNCH, "kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+}
+
 }  // namespace
 
 extern "C" {
 
 int ffpa_attn_fwd(const ffpa_fwd_params* p, void* stream) {
-  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
-  if (p->struct_size != sizeof(ffpa_fwd_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
-    return fail(FFPA_ERR_BAD_ABI, "ffpa_fwd_params ABI mismatch: size %u (want %zu), version %u (want %d)",
-                p->struct_size, sizeof(ffpa_fwd_params), p->abi_version, FFPA_ATTN_ABI_VERSION);
-  if (!p->q || !p->k || !p->v || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
-  if (p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16)
-    return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
-  if (p->batch <= 0 || p->heads_q <= 0 || p->heads_kv <= 0 || p->seqlen_q <= 0 || p->seqlen_kv <= 0)
-    return fail(FFPA_ERR_BAD_SHAPE, "non-positive dimension: B=%d Hq=%d Hkv=%d Nq=%d Nkv=%d", p->batch, p->heads_q,
-                p->heads_kv, p->seqlen_q, p->seqlen_kv);
-  if (p->heads_q % p->heads_kv != 0)
-    return fail(FFPA_ERR_BAD_SHAPE, "num_heads: Hq=%d is not a multiple of Hkv=%d", p->heads_q, p->heads_kv);
-  const DimEntry* de = find_dim(p->head_dim);
-  if (de == nullptr)
-    return fail(FFPA_ERR_BAD_HEADDIM, "headdim not support! D=%d (supported: multiples of 8 in [8, 1024])", p->head_dim);
+  const DimEntry* de = nullptr;
+  int rc = check_basic(p, &de, true);
+  if (rc != FFPA_OK) return rc;
   if (!aligned16(p->q) || !aligned16(p->k) || !aligned16(p->v) || !aligned16(p->o))
     return fail(FFPA_ERR_MISALIGNED, "q/k/v/o base pointers must be 16-byte aligned");
-  int rc;
-  if ((rc = check_strides("q", p->q_stride)) || (rc = check_strides("k", p->k_stride)) ||
-      (rc = check_strides("v", p->v_stride)) || (rc = check_strides("o", p->o_stride)))
+  if ((rc = check_strides("q", p->q_stride, 3)) || (rc = check_strides("k", p->k_stride, 3)) ||
+      (rc = check_strides("v", p->v_stride, 3)) || (rc = check_strides("o", p->o_stride, 3)))
     return rc;
   // K / V tiles are fetched with 32-bit buffer offsets relative to the tile's first row: one tile (<= 128
   // rows) must span < 4 GiB; the slice itself may be of any size
@@ -654,7 +708,6 @@ int ffpa_attn_fwd(const ffpa_fwd_params* p, void* stream) {
     return fail(FFPA_ERR_MISALIGNED, "split_tickets must be 4-byte aligned");
   if ((rc = check_device()) != FFPA_OK) return rc;
   const Plan pl = make_plan(p, de);
-  const int lds = pl.lds;
   const int64_t nqt = pl.nqt;
   const int64_t grid = (int64_t)p->batch * p->heads_q * (pl.pair ? (nqt + 1) / 2 : nqt) * pl.splits;
   if (grid > 0x7fffffffLL) return fail(FFPA_ERR_BAD_SHAPE, "grid of %lld workgroups is too large", (long long)grid);
@@ -689,19 +742,7 @@ int ffpa_attn_fwd(const ffpa_fwd_params* p, void* stream) {
   a.causal_offset = p->causal_offset;
   a.scale_log2 = p->softmax_scale * 1.4426950408889634f;  // FFPA_M_LOG2E, csrc/cuffpa/common.cuh:9-18
   a.inv_scale = 1.f;
-  if (pl.m16) {
-    // the 16x16x32 build folds the scale into its exponent (needs scale > 0) and takes additive biases in units of 1 / scale: a zero scale
-    // (scores = bias) reaches it as "Q = 0, scale = 1", a negative one as "-Q, |scale|" — the same scores
-    if (p->softmax_scale == 0.f) {
-      a.scale_log2 = 1.4426950408889634f;
-      a.q_mode = 1;
-    } else {
-      const float mag = fabsf(p->softmax_scale);  // a negative scale: (-Q, |scale|) — exact, and the kernel's fused exponent needs scale > 0
-      a.scale_log2 = mag * 1.4426950408889634f;
-      a.inv_scale = (float)(1.0 / (double)mag);
-      if (p->softmax_scale < 0.f) a.q_mode = 2;
-    }
-  }
+  if (pl.m16) fold_scale(a, p->softmax_scale);
   a.thr = p->rescale_threshold < 0.f ? 8.0f : p->rescale_threshold;
   a.flags = p->flags & 0x7fffffffu;  // (bit 31 is the launch side's own: kFlagStreamKV)
   {
@@ -759,25 +800,9 @@ int ffpa_attn_fwd(const ffpa_fwd_params* p, void* stream) {
   a.dropout_p = p->dropout_p;
   a.keep_scale = p->dropout_p > 0.f ? 1.f / (1.f - p->dropout_p) : 1.f;
   a.keep_threshold = dropout_keep_threshold(p->dropout_p);
-  // XCDs per head (xcd_logical_id, ffpa_common.h).  One XCD per head keeps a head's K/V stream in one L2; but then eight heads are in flight chip-wide,
-  // and once their K + V no longer fit the Infinity Cache the second and later rounds of a head's row tiles come from HBM instead (config 3: eight heads x
-  // 32 MiB = the whole 256 MiB).  Prefill launches with at least two rounds of row tiles per head and XCD therefore share a head between the smallest
-  // power-of-two number of XCDs that brings the K + V in flight under 200 MiB (measured, profiles/r03_xcd_group.txt).
-  {
-    int g = 1;
-    const unsigned forced = (p->flags >> 8) & 7u;
-    if (forced != 0) {
-      g = 1 << (forced - 1 > 3 ? 3 : forced - 1);
-    } else if (pl.m16 && pl.splits == 1 && (int64_t)pl.nqt * (p->heads_q / p->heads_kv) >= 64) {
-      const double kv_mib = 2.0 * (double)p->seqlen_kv * (double)p->head_dim * 2.0 / 1048576.0;  // K + V of one (batch, kv head)
-      while (g < 8 && (8 / g) * kv_mib > 200.0) g *= 2;
-    }
-    a.xcd_group = g;
-  }
-  // The split-D tiles (D > 512) give a DMA piece less than a microsecond to land (32-key steps, single K / V buffers): their launches touch the
-  // tile two steps ahead (ffpa_fwd_m16_kernel.h, "L2 prefetch").  Measured, same library with and without (profiles/r03_l2_prefetch.txt):
-  // D = 576 ... 1024: + 3 ... 9 % (D = 768: +- 0), every shape tried (self, cross, GQA, batch 4, causal, key bias); D <= 512: - 1 ... 2 %, off.
-  a.l2_prefetch = (p->flags & FFPA_FLAG_NO_L2_PREFETCH) ? 0 : ((p->flags & FFPA_FLAG_L2_PREFETCH) || (pl.m16 && kernel_head_dim(p->head_dim) > 512)) ? 1 : 0;
+  // (prefill launches of the 16x16x32 build with at least two rounds of row tiles per head and XCD share a head between XCDs)
+  a.xcd_group = pick_xcd_group(p->flags, pl.m16 && pl.splits == 1 && (int64_t)pl.nqt * (p->heads_q / p->heads_kv) >= 64, p->seqlen_kv, p->head_dim);
+  a.l2_prefetch = pick_l2_prefetch(p->flags, pl.m16 && kernel_head_dim(p->head_dim) > 512);
   a.philox_seed = p->philox_seed;
   a.philox_offset = p->philox_offset;
   if (pl.splits > 1) {
@@ -807,37 +832,27 @@ int ffpa_attn_fwd(const ffpa_fwd_params* p, void* stream) {
   }
   if (st == 0 && pl.splits > 1 && a.tickets == nullptr) {
     const unsigned rows = (unsigned)((int64_t)p->batch * p->heads_q * p->seqlen_q);
-    if (p->dtype == FFPA_DTYPE_BF16)
-      hipLaunchKernelGGL(ffpa::ffpa_fwd_merge_kernel<__bf16>, dim3(rows, (unsigned)(p->head_dim + 255) / 256), dim3(64), 0, static_cast<hipStream_t>(stream), a, kernel_head_dim(p->head_dim));
-    else
-      hipLaunchKernelGGL(ffpa::ffpa_fwd_merge_kernel<_Float16>, dim3(rows, (unsigned)(p->head_dim + 255) / 256), dim3(64), 0, static_cast<hipStream_t>(stream), a, kernel_head_dim(p->head_dim));
-    st = (int)hipGetLastError();
+    st = ffpa::dispatch_dtype(p->dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL(ffpa::ffpa_fwd_merge_kernel<T>, dim3(rows, (unsigned)(p->head_dim + 255) / 256), dim3(64), 0, static_cast<hipStream_t>(stream), a, kernel_head_dim(p->head_dim));
+      return (int)hipGetLastError();
+    });
   }
-  if (st == -3) return fail(FFPA_ERR_UNSUPPORTED, "debug safe-path kernel is not built for D=%d / this dtype", p->head_dim);
-  if (st == -2)
-    return fail(FFPA_ERR_LAUNCH, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed (is this a gfx950?)", lds);
-  if (st < 0) return fail(FFPA_ERR_LAUNCH, "launch setup failed (%d)", st);
-  if (st != 0)
-    return fail(FFPA_ERR_LAUNCH, "kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
-  return FFPA_OK;
+  return launch_status(st, pl.lds, p->head_dim);
 }
 
 size_t ffpa_attn_fwd_workspace_bytes(const ffpa_fwd_params* params) {
   const DimEntry* de = nullptr;
   if (check_basic(params, &de) != FFPA_OK) return 0;
   // size for the split count the heuristic would pick with unlimited scratch
-  ffpa_fwd_params q = *params;
-  q.workspace = reinterpret_cast<void*>(16);
-  q.workspace_bytes = ~0ull;
+  const ffpa_fwd_params q = with_unlimited_scratch(*params);
   return make_plan(&q, de).ws_bytes;
 }
 
 size_t ffpa_attn_fwd_split_tickets(const ffpa_fwd_params* params) {
   const DimEntry* de = nullptr;
   if (check_basic(params, &de) != FFPA_OK) return 0;
-  ffpa_fwd_params q = *params;
-  q.workspace = reinterpret_cast<void*>(16);
-  q.workspace_bytes = ~0ull;
+  const ffpa_fwd_params q = with_unlimited_scratch(*params);
   const Plan pl = make_plan(&q, de);
   return (pl.splits > 1 && pl.variant == 1) ? (size_t)params->batch * params->heads_q * pl.nqt : 0;
 }
@@ -867,17 +882,15 @@ int ffpa_attn_mask_kv_bounds(const void* bias, int bias_dtype, const int64_t bia
   const bool vec = bias_stride[3] == 1 && nkv % w == 0 && reinterpret_cast<uintptr_t>(bias) % 16 == 0 &&
                    bias_stride[0] % w == 0 && bias_stride[1] % w == 0 && bias_stride[2] % w == 0;
   const dim3 g((unsigned)grid), blk(256);
-  if (vec) {
-    if (bias_dtype == FFPA_BIAS_FP32) hipLaunchKernelGGL(ffpa::ffpa_mask_kv_bounds_vec_kernel<float>, g, blk, smem, st, m);
-    else if (bias_dtype == FFPA_BIAS_BOOL8) hipLaunchKernelGGL(ffpa::ffpa_mask_kv_bounds_vec_kernel<uint8_t>, g, blk, smem, st, m);
-    else if (bias_dtype == FFPA_BIAS_BF16) hipLaunchKernelGGL(ffpa::ffpa_mask_kv_bounds_vec_kernel<__bf16>, g, blk, smem, st, m);
-    else hipLaunchKernelGGL(ffpa::ffpa_mask_kv_bounds_vec_kernel<_Float16>, g, blk, smem, st, m);
-  } else {
-    if (bias_dtype == FFPA_BIAS_FP32) hipLaunchKernelGGL(ffpa::ffpa_mask_kv_bounds_kernel<float>, g, blk, smem, st, m);
-    else if (bias_dtype == FFPA_BIAS_BOOL8) hipLaunchKernelGGL(ffpa::ffpa_mask_kv_bounds_kernel<uint8_t>, g, blk, smem, st, m);
-    else if (bias_dtype == FFPA_BIAS_BF16) hipLaunchKernelGGL(ffpa::ffpa_mask_kv_bounds_kernel<__bf16>, g, blk, smem, st, m);
-    else hipLaunchKernelGGL(ffpa::ffpa_mask_kv_bounds_kernel<_Float16>, g, blk, smem, st, m);
-  }
+  auto launch = [&](auto t) {
+    using B = typename decltype(t)::type;
+    if (vec) hipLaunchKernelGGL(ffpa::ffpa_mask_kv_bounds_vec_kernel<B>, g, blk, smem, st, m);
+    else hipLaunchKernelGGL(ffpa::ffpa_mask_kv_bounds_kernel<B>, g, blk, smem, st, m);
+  };
+  if (bias_dtype == FFPA_BIAS_FP32) launch(ffpa::TypeTag<float>{});
+  else if (bias_dtype == FFPA_BIAS_BOOL8) launch(ffpa::TypeTag<uint8_t>{});
+  else if (bias_dtype == FFPA_BIAS_BF16) launch(ffpa::TypeTag<__bf16>{});
+  else launch(ffpa::TypeTag<_Float16>{});
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(FFPA_ERR_LAUNCH, "mask bounds launch failed: %s", hipGetErrorString(e));
   return FFPA_OK;
@@ -1067,14 +1080,6 @@ int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = f
   return FFPA_OK;
 }
 
-int check_strides2(const char* name, const int64_t s[2]) {
-  for (int i = 0; i < 2; ++i) {
-    if (s[i] < 0) return fail(FFPA_ERR_BAD_STRIDE, "%s stride[%d]=%lld is negative", name, i, (long long)s[i]);
-    if (s[i] % 8 != 0) return fail(FFPA_ERR_BAD_STRIDE, "%s stride[%d]=%lld is not a multiple of 8 elements (16 bytes)", name, i, (long long)s[i]);
-  }
-  return FFPA_OK;
-}
-
 // A page pool (ffpa_paged_kv): the paged attention call's and the KV-cache append's
 int check_pool(const ffpa_paged_kv* kv) {
   if (kv->struct_size != sizeof(ffpa_paged_kv))
@@ -1117,8 +1122,8 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
     return fail(FFPA_ERR_MISALIGNED, "cu_seqlens_q / cu_seqlens_kv / seqused_kv must be 4-byte aligned");
   if (!aligned16(p->q) || !aligned16(p->k) || !aligned16(p->v) || !aligned16(p->o))
     return fail(FFPA_ERR_MISALIGNED, "q/k/v/o base pointers must be 16-byte aligned");
-  if ((rc = check_strides2("q", p->q_stride)) || (rc = check_strides2("k", p->k_stride)) || (rc = check_strides2("v", p->v_stride)) ||
-      (rc = check_strides2("o", p->o_stride)))
+  if ((rc = check_strides("q", p->q_stride, 2)) || (rc = check_strides("k", p->k_stride, 2)) || (rc = check_strides("v", p->v_stride, 2)) ||
+      (rc = check_strides("o", p->o_stride, 2)))
     return rc;
   for (const int64_t* st : {p->k_stride, p->v_stride}) {
     if (st[0] < p->head_dim || st[0] >= (1LL << 24))
@@ -1152,35 +1157,15 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
   a.nqt = pl.nqt;
   a.total_wg = (int)pl.grid;
   a.causal = p->causal ? 1 : 0;
-  // the 16x16x32 build folds the scale into its exponent (needs scale > 0): a zero scale reaches it as "Q = 0, scale = 1", a negative one as "-Q, |scale|" (ffpa_attn_fwd)
   a.inv_scale = 1.f;
-  if (p->softmax_scale == 0.f) {
-    a.scale_log2 = 1.4426950408889634f;
-    a.q_mode = 1;
-  } else {
-    const float mag = fabsf(p->softmax_scale);
-    a.scale_log2 = mag * 1.4426950408889634f;
-    a.inv_scale = (float)(1.0 / (double)mag);
-    if (p->softmax_scale < 0.f) a.q_mode = 2;
-  }
+  fold_scale(a, p->softmax_scale);
   a.thr = p->rescale_threshold < 0.f ? 8.0f : p->rescale_threshold;
   a.flags = p->flags & (FFPA_FLAG_NO_XCD_REMAP);
   a.nsplit = 1;
   a.tiles_per_split = 0x7fffffff / 2;  // (never the binding limit: the KV axis is not split)
   a.keep_scale = 1.f;
-  {
-    // XCDs per head: the dense call's rule (ffpa_attn_fwd), priced on the longest sequence the caller announces
-    int g = 1;
-    const unsigned forced = (p->flags >> 8) & 7u;
-    if (forced != 0) {
-      g = 1 << (forced - 1 > 3 ? 3 : forced - 1);
-    } else if ((int64_t)pl.nqt * (p->heads_q / p->heads_kv) >= 64) {
-      const double kv_mib = 2.0 * (double)p->max_seqlen_kv * (double)p->head_dim * 2.0 / 1048576.0;
-      while (g < 8 && (8 / g) * kv_mib > 200.0) g *= 2;
-    }
-    a.xcd_group = g;
-  }
-  a.l2_prefetch = (p->flags & FFPA_FLAG_NO_L2_PREFETCH) ? 0 : ((p->flags & FFPA_FLAG_L2_PREFETCH) || pl.ve->d > 512) ? 1 : 0;
+  a.xcd_group = pick_xcd_group(p->flags, (int64_t)pl.nqt * (p->heads_q / p->heads_kv) >= 64, p->max_seqlen_kv, p->head_dim);
+  a.l2_prefetch = pick_l2_prefetch(p->flags, pl.ve->d > 512);
 
   ffpa::VarlenArgs va;
   va.cu_q = p->cu_seqlens_q;
@@ -1231,16 +1216,13 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
   }
   if (st == 0 && pl.splits > 1) {
     const dim3 grid((unsigned)((int64_t)p->heads_q * p->total_q), (unsigned)(p->head_dim + 255) / 256);
-    if (p->dtype == FFPA_DTYPE_BF16)
-      hipLaunchKernelGGL(ffpa::ffpa_varlen_merge_kernel<__bf16>, grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, va, pl.ve->d, p->batch, p->o_stride[1]);
-    else
-      hipLaunchKernelGGL(ffpa::ffpa_varlen_merge_kernel<_Float16>, grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, va, pl.ve->d, p->batch, p->o_stride[1]);
-    st = (int)hipGetLastError();
+    st = ffpa::dispatch_dtype(p->dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL(ffpa::ffpa_varlen_merge_kernel<T>, grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, va, pl.ve->d, p->batch, p->o_stride[1]);
+      return (int)hipGetLastError();
+    });
   }
-  if (st == -2) return fail(FFPA_ERR_LAUNCH, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (is this a gfx950?)");
-  if (st < 0) return fail(FFPA_ERR_LAUNCH, "launch setup failed (%d)", st);
-  if (st != 0) return fail(FFPA_ERR_LAUNCH, "kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
-  return FFPA_OK;
+  return launch_status(st, -1, 0);
 }
 
 }  // namespace
@@ -1262,9 +1244,7 @@ int plan_out(const VarlenPlan& pl, int out[5]) {
 size_t workspace_bytes(const ffpa_varlen_fwd_params* params, bool paged) {
   if (params == nullptr || params->struct_size != sizeof(ffpa_varlen_fwd_params)) return 0;
   // size for the split count the heuristic would pick with unlimited scratch
-  ffpa_varlen_fwd_params q = *params;
-  q.workspace = reinterpret_cast<void*>(16);
-  q.workspace_bytes = ~0ull;
+  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*params);
   VarlenPlan pl;
   if (varlen_plan(&q, &pl, paged) != FFPA_OK) return 0;
   return pl.ws_bytes;
@@ -1323,18 +1303,6 @@ int ffpa_attn_varlen_paged_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffp
 }
 
 // ---- the KV-cache append + rotary (include/ffpa_attn.h: ffpa_kv_append_params)
-namespace {
-
-int check_strides3(const char* name, const int64_t s[3]) {
-  for (int i = 0; i < 3; ++i) {
-    if (s[i] < 0) return fail(FFPA_ERR_BAD_STRIDE, "%s stride[%d]=%lld is negative", name, i, (long long)s[i]);
-    if (s[i] % 8 != 0) return fail(FFPA_ERR_BAD_STRIDE, "%s stride[%d]=%lld is not a multiple of 8 elements (16 bytes)", name, i, (long long)s[i]);
-  }
-  return FFPA_OK;
-}
-
-}  // namespace
-
 int ffpa_attn_kvcache_append(const ffpa_kv_append_params* p, const ffpa_paged_kv* kv, void* stream) {
   if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
   if (p->struct_size != sizeof(ffpa_kv_append_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
@@ -1373,9 +1341,9 @@ int ffpa_attn_kvcache_append(const ffpa_kv_append_params* p, const ffpa_paged_kv
   if (!aligned16(p->k_cache) || !aligned16(p->v_cache) || (use_kv && (!aligned16(p->k) || !aligned16(p->v))) ||
       (use_q && (!aligned16(p->q) || !aligned16(p->q_rot))) || (use_rot && (!aligned16(p->rotary_cos) || !aligned16(p->rotary_sin))))
     return fail(FFPA_ERR_MISALIGNED, "q / k / v / caches / q_rot / rotary_cos / rotary_sin base pointers must be 16-byte aligned");
-  if ((rc = check_strides3("k_cache", p->k_cache_stride)) || (rc = check_strides3("v_cache", p->v_cache_stride))) return rc;
-  if (use_kv && ((rc = check_strides3("k", p->k_stride)) || (rc = check_strides3("v", p->v_stride)))) return rc;
-  if (use_q && ((rc = check_strides3("q", p->q_stride)) || (rc = check_strides3("q_rot", p->q_rot_stride)))) return rc;
+  if ((rc = check_strides("k_cache", p->k_cache_stride, 3)) || (rc = check_strides("v_cache", p->v_cache_stride, 3))) return rc;
+  if (use_kv && ((rc = check_strides("k", p->k_stride, 3)) || (rc = check_strides("v", p->v_stride, 3)))) return rc;
+  if (use_q && ((rc = check_strides("q", p->q_stride, 3)) || (rc = check_strides("q_rot", p->q_rot_stride, 3)))) return rc;
   const int rows = std::max(1, std::max(p->seqlen_new, rd > 0 ? p->seqlen_q : 0));
   if ((int64_t)p->batch * rows > 0x7fffffffLL) return fail(FFPA_ERR_BAD_SHAPE, "grid of %lld token rows is too large", (long long)p->batch * rows);
   if ((rc = check_device()) != FFPA_OK) return rc;
@@ -1429,7 +1397,7 @@ int ffpa_attn_merge_states(const ffpa_merge_states_params* p, void* stream) {
   if ((reinterpret_cast<uintptr_t>(p->lse_a) & 3u) || (reinterpret_cast<uintptr_t>(p->lse_b) & 3u) || (reinterpret_cast<uintptr_t>(p->lse) & 3u))
     return fail(FFPA_ERR_MISALIGNED, "lse_a / lse_b / lse must be 4-byte aligned");
   int rc;
-  if ((rc = check_strides2("o_a", p->o_a_stride)) || (rc = check_strides2("o_b", p->o_b_stride)) || (rc = check_strides2("o", p->o_stride))) return rc;
+  if ((rc = check_strides("o_a", p->o_a_stride, 2)) || (rc = check_strides("o_b", p->o_b_stride, 2)) || (rc = check_strides("o", p->o_stride, 2))) return rc;
   if (p->lse_a_stride_head < 0 || p->lse_b_stride_head < 0 || (p->lse != nullptr && p->lse_stride_head < 0))
     return fail(FFPA_ERR_BAD_STRIDE, "lse head strides must not be negative (lse_a %lld, lse_b %lld, lse %lld)", (long long)p->lse_a_stride_head,
                 (long long)p->lse_b_stride_head, (long long)p->lse_stride_head);

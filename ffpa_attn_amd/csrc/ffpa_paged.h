@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "ffpa_launch.h"
+
 namespace ffpa {
 struct FwdArgs;
 struct VarlenArgs;
@@ -23,8 +25,7 @@ struct PagedArgs {
 };
 
 #define FFPA_DECL(D) int launch_paged_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, hipStream_t stream);
-FFPA_DECL(128) FFPA_DECL(192) FFPA_DECL(256) FFPA_DECL(320) FFPA_DECL(384) FFPA_DECL(448) FFPA_DECL(512)
-FFPA_DECL(576) FFPA_DECL(640) FFPA_DECL(704) FFPA_DECL(768) FFPA_DECL(832) FFPA_DECL(896) FFPA_DECL(960) FFPA_DECL(1024)
+FFPA_FOR_EACH_VARLEN_HEAD_DIM(FFPA_DECL)
 #undef FFPA_DECL
 
 }  // namespace ffpa

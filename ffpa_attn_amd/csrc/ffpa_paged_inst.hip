@@ -1,10 +1,9 @@
 // ffpa_paged_inst.hip — the paged-KV twin of the packed-sequence kernel (ffpa_fwd_m16_paged_kernel), one translation unit per head dim (compiled with
 // -DFFPA_INST_D=<D>, D a multiple of 64 in [128, 1024]; bf16 + fp16 in the same TU).  A TU of its own so that the dense and packed objects
 // (ffpa_fwd_inst.hip, ffpa_varlen_inst.hip) stay exactly what they were.  Entry point: ffpa_attn_varlen_paged_fwd (ffpa_capi.hip).
-#include <atomic>
-
 #include "ffpa_fwd_kernel.h"
 #include "ffpa_fwd_m16_kernel.h"
+#include "ffpa_launch_kernel.h"
 #include "ffpa_paged.h"
 
 #ifndef FFPA_INST_D
@@ -128,28 +127,14 @@ template <typename T, int D, bool NT>
 static int launch_paged(const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, hipStream_t stream) {
   constexpr int BC = m16_block_keys(D, true);
   constexpr int LDS = 2 * BC * D * 2 + m16_exchange_bytes(D, 0);
-  auto kern = ffpa_fwd_m16_paged_kernel<T, D, NT>;
-  static std::atomic<bool> attr_done[64];  // write-once per device (setting the attribute twice is harmless)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return -1;
-  if (dev < 0 || dev >= 64 || !attr_done[dev].load(std::memory_order_acquire)) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      (void)hipGetLastError();
-      return -2;
-    }
-    if (dev >= 0 && dev < 64) attr_done[dev].store(true, std::memory_order_release);
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)a.total_wg), dim3(256), LDS, stream, a, va, pa);
-  return (int)hipGetLastError();
+  return launch_kernel<ffpa_fwd_m16_paged_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa);
 }
 
-#define FFPA_CAT2(a, b) a##b
-#define FFPA_CAT(a, b) FFPA_CAT2(a, b)
-
 int FFPA_CAT(launch_paged_d, FFPA_INST_D)(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, hipStream_t stream) {
-  if (dtype == 0) return nt ? launch_paged<__bf16, FFPA_INST_D, true>(a, va, pa, stream) : launch_paged<__bf16, FFPA_INST_D, false>(a, va, pa, stream);
-  if (dtype == 1) return nt ? launch_paged<_Float16, FFPA_INST_D, true>(a, va, pa, stream) : launch_paged<_Float16, FFPA_INST_D, false>(a, va, pa, stream);
-  return -4;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return nt ? launch_paged<T, FFPA_INST_D, true>(a, va, pa, stream) : launch_paged<T, FFPA_INST_D, false>(a, va, pa, stream);
+  });
 }
 
 }  // namespace ffpa

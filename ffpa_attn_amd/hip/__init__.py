@@ -241,28 +241,34 @@ _lib = None
 _debug_lib = None
 _lib_lock = threading.Lock()
 
-EXPORTS = (
-  "ffpa_attn_fwd",
-  "ffpa_attn_fwd_workspace_bytes",
-  "ffpa_attn_fwd_split_tickets",
-  "ffpa_attn_mask_kv_bounds",
-  "ffpa_attn_fwd_plan",
-  "ffpa_attn_fwd_kernel",
-  "ffpa_attn_varlen_fwd",
-  "ffpa_attn_varlen_fwd_plan",
-  "ffpa_attn_varlen_fwd_kernel",
-  "ffpa_attn_varlen_fwd_workspace_bytes",
-  "ffpa_attn_varlen_paged_fwd",
-  "ffpa_attn_varlen_paged_fwd_plan",
-  "ffpa_attn_varlen_paged_fwd_kernel",
-  "ffpa_attn_varlen_paged_fwd_workspace_bytes",
-  "ffpa_attn_kvcache_append",
-  "ffpa_attn_merge_states",
-  "ffpa_attn_query",
-  "ffpa_attn_fwd_tile_config",
-  "ffpa_attn_last_error",
-  "ffpa_attn_version",
+_P = ctypes.POINTER
+_INT, _SIZE, _VOID, _STR = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_char_p
+_VARLEN, _PAGED = [_P(FfpaVarlenFwdParams)], [_P(FfpaVarlenFwdParams), _P(FfpaPagedKv)]
+# Every function include/ffpa_attn.h declares: (symbol, argtypes, restype, since).  ``since``: the ABI version that added it (0: there from the start) — the
+# default library has them all; one loaded by path (developer A/B runs load a saved build of an older commit) may lack those with since > 0.
+_BINDINGS = (
+  ("ffpa_attn_fwd", [_P(FfpaFwdParams), _VOID], _INT, 0),
+  ("ffpa_attn_fwd_workspace_bytes", [_P(FfpaFwdParams)], _SIZE, 0),
+  ("ffpa_attn_fwd_split_tickets", [_P(FfpaFwdParams)], _SIZE, 4),
+  ("ffpa_attn_mask_kv_bounds", [_VOID, _INT, _P(ctypes.c_int64), _INT, _INT, _INT, _INT, _VOID, _VOID], _INT, 0),
+  ("ffpa_attn_fwd_plan", [_P(FfpaFwdParams), _P(_INT)], _INT, 0),
+  ("ffpa_attn_fwd_kernel", [_P(FfpaFwdParams), _STR, _SIZE], _INT, 3),
+  ("ffpa_attn_varlen_fwd", _VARLEN + [_VOID], _INT, 5),
+  ("ffpa_attn_varlen_fwd_plan", _VARLEN + [_P(_INT)], _INT, 5),
+  ("ffpa_attn_varlen_fwd_kernel", _VARLEN + [_STR, _SIZE], _INT, 5),
+  ("ffpa_attn_varlen_fwd_workspace_bytes", _VARLEN, _SIZE, 5),
+  ("ffpa_attn_varlen_paged_fwd", _PAGED + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_paged_fwd_plan", _PAGED + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_paged_fwd_kernel", _PAGED + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_paged_fwd_workspace_bytes", _PAGED, _SIZE, 7),
+  ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
+  ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
+  ("ffpa_attn_query", [_INT], _INT, 0),
+  ("ffpa_attn_fwd_tile_config", [_INT, _P(_INT), _P(_INT), _P(_INT)], _INT, 0),
+  ("ffpa_attn_last_error", [], _STR, 0),
+  ("ffpa_attn_version", [], _STR, 0),
 )
+EXPORTS = tuple(b[0] for b in _BINDINGS)
 
 
 def load_library(path: str | None = None) -> ctypes.CDLL:
@@ -282,56 +288,11 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "kernel): build it with `python -m ffpa_attn_amd.build` (needs hipcc, targets gfx950)."
       )
     lib = ctypes.CDLL(p)
-    lib.ffpa_attn_fwd.argtypes = [ctypes.POINTER(FfpaFwdParams), ctypes.c_void_p]
-    lib.ffpa_attn_fwd.restype = ctypes.c_int
-    lib.ffpa_attn_mask_kv_bounds.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    lib.ffpa_attn_mask_kv_bounds.restype = ctypes.c_int
-    lib.ffpa_attn_fwd_workspace_bytes.argtypes = [ctypes.POINTER(FfpaFwdParams)]
-    lib.ffpa_attn_fwd_workspace_bytes.restype = ctypes.c_size_t
-    if path is None or hasattr(lib, "ffpa_attn_fwd_split_tickets"):
-      lib.ffpa_attn_fwd_split_tickets.argtypes = [ctypes.POINTER(FfpaFwdParams)]
-      lib.ffpa_attn_fwd_split_tickets.restype = ctypes.c_size_t
-    lib.ffpa_attn_fwd_plan.argtypes = [ctypes.POINTER(FfpaFwdParams), ctypes.POINTER(ctypes.c_int)]
-    lib.ffpa_attn_fwd_plan.restype = ctypes.c_int
-    if path is None or hasattr(lib, "ffpa_attn_fwd_kernel"):  # (developer A/B runs may load a saved build of an older commit by path)
-      lib.ffpa_attn_fwd_kernel.argtypes = [ctypes.POINTER(FfpaFwdParams), ctypes.c_char_p, ctypes.c_size_t]
-      lib.ffpa_attn_fwd_kernel.restype = ctypes.c_int
-    if path is None or hasattr(lib, "ffpa_attn_varlen_fwd"):  # (ditto: a saved build from before the packed-sequence entry points)
-      lib.ffpa_attn_varlen_fwd.argtypes = [ctypes.POINTER(FfpaVarlenFwdParams), ctypes.c_void_p]
-      lib.ffpa_attn_varlen_fwd.restype = ctypes.c_int
-      lib.ffpa_attn_varlen_fwd_plan.argtypes = [ctypes.POINTER(FfpaVarlenFwdParams), ctypes.POINTER(ctypes.c_int)]
-      lib.ffpa_attn_varlen_fwd_plan.restype = ctypes.c_int
-      lib.ffpa_attn_varlen_fwd_workspace_bytes.argtypes = [ctypes.POINTER(FfpaVarlenFwdParams)]
-      lib.ffpa_attn_varlen_fwd_workspace_bytes.restype = ctypes.c_size_t
-      lib.ffpa_attn_varlen_fwd_kernel.argtypes = [ctypes.POINTER(FfpaVarlenFwdParams), ctypes.c_char_p, ctypes.c_size_t]
-      lib.ffpa_attn_varlen_fwd_kernel.restype = ctypes.c_int
-    if path is None or hasattr(lib, "ffpa_attn_varlen_paged_fwd"):  # (ditto: before the paged-KV call)
-      _pp = [ctypes.POINTER(FfpaVarlenFwdParams), ctypes.POINTER(FfpaPagedKv)]
-      lib.ffpa_attn_varlen_paged_fwd.argtypes = _pp + [ctypes.c_void_p]
-      lib.ffpa_attn_varlen_paged_fwd.restype = ctypes.c_int
-      lib.ffpa_attn_varlen_paged_fwd_plan.argtypes = _pp + [ctypes.POINTER(ctypes.c_int)]
-      lib.ffpa_attn_varlen_paged_fwd_plan.restype = ctypes.c_int
-      lib.ffpa_attn_varlen_paged_fwd_workspace_bytes.argtypes = _pp
-      lib.ffpa_attn_varlen_paged_fwd_workspace_bytes.restype = ctypes.c_size_t
-      lib.ffpa_attn_varlen_paged_fwd_kernel.argtypes = _pp + [ctypes.c_char_p, ctypes.c_size_t]
-      lib.ffpa_attn_varlen_paged_fwd_kernel.restype = ctypes.c_int
-    if path is None or hasattr(lib, "ffpa_attn_kvcache_append"):  # (ditto: before the KV-cache append)
-      lib.ffpa_attn_kvcache_append.argtypes = [ctypes.POINTER(FfpaKvAppendParams), ctypes.POINTER(FfpaPagedKv), ctypes.c_void_p]
-      lib.ffpa_attn_kvcache_append.restype = ctypes.c_int
-    if path is None or hasattr(lib, "ffpa_attn_merge_states"):  # (ditto: before the merge of two attention states)
-      lib.ffpa_attn_merge_states.argtypes = [ctypes.POINTER(FfpaMergeStatesParams), ctypes.c_void_p]
-      lib.ffpa_attn_merge_states.restype = ctypes.c_int
-    lib.ffpa_attn_query.argtypes = [ctypes.c_int]
-    lib.ffpa_attn_query.restype = ctypes.c_int
-    lib.ffpa_attn_fwd_tile_config.argtypes = [
-      ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)
-    ]
-    lib.ffpa_attn_fwd_tile_config.restype = ctypes.c_int
-    lib.ffpa_attn_last_error.argtypes = []
-    lib.ffpa_attn_last_error.restype = ctypes.c_char_p
-    lib.ffpa_attn_version.argtypes = []
-    lib.ffpa_attn_version.restype = ctypes.c_char_p
+    for symbol, argtypes, restype, since in _BINDINGS:
+      if path is not None and since > 0 and not hasattr(lib, symbol):
+        continue
+      fn = getattr(lib, symbol)
+      fn.argtypes, fn.restype = argtypes, restype
     if lib.ffpa_attn_query(0) != ABI_VERSION and path is None:
       raise RuntimeError(f"ffpa_attn_amd: {p} has ABI {lib.ffpa_attn_query(0)}, expected {ABI_VERSION}")
     if path is None:
@@ -386,14 +347,77 @@ def __getattr__(name: str):
   raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
+# ---- what every call of the library does, once: a stamped parameter struct, the status -> exception raise, the call on the current stream, the scratch hand-over,
+# the plan read-out.  Plain functions: ``forward`` / ``varlen_forward`` run once per decoded token.
+def _stamped(cls):
+  """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` rides next to a versioned struct), the ABI version — filled in."""
+  p = cls()
+  p.struct_size = ctypes.sizeof(cls)
+  if cls is not FfpaPagedKv:
+    p.abi_version = ABI_VERSION
+  return p
+
+
+def _raise_status(lib, rc: int, call: "str | None" = None):
+  """The exception class of a non-zero ``ffpa_status`` with the library's message (``call``: the entry point, for the launches)."""
+  msg = lib.ffpa_attn_last_error().decode()
+  raise _STATUS_EXC.get(rc, RuntimeError)(f"{call}: {msg} (status {rc})" if call else msg)
+
+
+def _call_on_stream(fn, device: torch.device, *args) -> int:
+  """``fn(*args, stream)`` with ``device`` current and its current stream as the last argument."""
+  with torch.cuda.device(device):
+    return fn(*args, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+
+
+def _deterministic_flag() -> int:
+  return FLAG_DETERMINISTIC if os.environ.get("FFPA_HIP_DETERMINISTIC", "0").lower() not in ("0", "", "off", "false", "no") else 0
+
+
+def _read_plan(lib, plan_fn, kernel_fn, keys: tuple, args: tuple, strict: bool = False) -> dict:
+  """``{key: plan[i]}`` + ``kernel`` from a ``*_plan`` / ``*_kernel`` pair of exports; a query that fails leaves its keys out, or raises with ``strict``."""
+  plan = (ctypes.c_int * len(keys))()
+  rc = plan_fn(*args, plan)
+  if rc != 0 and strict:
+    _raise_status(lib, rc)
+  out = dict(zip(keys, plan)) if rc == 0 else {}
+  name = ctypes.create_string_buffer(200)
+  if kernel_fn is not None and kernel_fn(*args, name, len(name)) == 0:
+    out["kernel"] = name.value.decode()
+  return out
+
+
+_FWD_PLAN_KEYS = ("variant", "block_rows", "block_keys", "splits")
+_VARLEN_PLAN_KEYS = ("row_tiles", "block_rows", "block_keys", "workgroups", "splits")
+
+
 def tile_config(head_dim: int) -> dict:
   """Rows per workgroup / keys per tile / LDS bytes the kernel uses for ``head_dim``."""
   lib = load_library()
   br, bc, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
   rc = lib.ffpa_attn_fwd_tile_config(int(head_dim), ctypes.byref(br), ctypes.byref(bc), ctypes.byref(lds))
   if rc != 0:
-    raise _STATUS_EXC.get(rc, RuntimeError)(lib.ffpa_attn_last_error().decode())
+    _raise_status(lib, rc)
   return {"block_rows": br.value, "block_keys": bc.value, "lds_bytes": lds.value}
+
+
+def _fwd_params(dtype: torch.dtype, batch: int, heads_q: int, heads_kv: int, seqlen_q: int, seqlen_kv: int, head_dim: int, strides, causal: bool, causal_offset: int,
+                softmax_scale: float, rescale_threshold: float, dropout_p: float, flags: int, num_splits: int) -> FfpaFwdParams:
+  """``ffpa_fwd_params`` without its pointers: the shape class, ``strides`` = the batch / head / row element strides of q, k, v, o, and the scalars.  The launch adds
+  the tensors' addresses (bias, mask ranges, scratch, Philox state), a plan query placeholders."""
+  p = _stamped(FfpaFwdParams)
+  p.batch, p.heads_q, p.heads_kv = batch, heads_q, heads_kv
+  p.seqlen_q, p.seqlen_kv, p.head_dim = seqlen_q, seqlen_kv, head_dim
+  p.q_stride[:], p.k_stride[:], p.v_stride[:], p.o_stride[:] = strides
+  p.dtype = _DTYPE[dtype]
+  p.causal = 1 if causal else 0
+  p.causal_offset = int(causal_offset)
+  p.softmax_scale = float(softmax_scale)
+  p.rescale_threshold = float(rescale_threshold)
+  p.dropout_p = float(dropout_p)
+  p.flags = int(flags)
+  p.num_splits = int(num_splits)
+  return p
 
 
 def launch_plan(batch: int, heads_q: int, heads_kv: int, seqlen_q: int, seqlen_kv: int, head_dim: int, *, dtype: torch.dtype = torch.bfloat16,
@@ -405,42 +429,21 @@ def launch_plan(batch: int, heads_q: int, heads_kv: int, seqlen_q: int, seqlen_k
   pieces to run the plan of the whole (``sharding.attend_and_gather_units``) asks here."""
   lib = load_library()
   d8 = (int(head_dim) + 7) // 8 * 8
-  p = FfpaFwdParams()
-  p.struct_size = ctypes.sizeof(FfpaFwdParams)
-  p.abi_version = ABI_VERSION
+  batch, heads_q, heads_kv, seqlen_q, seqlen_kv = int(batch), int(heads_q), int(heads_kv), int(seqlen_q), int(seqlen_kv)
+  strides = [(h * n * d8, n * d8, d8) for h, n in ((heads_q, seqlen_q), (heads_kv, seqlen_kv), (heads_kv, seqlen_kv), (heads_q, seqlen_q))]
+  p = _fwd_params(dtype, batch, heads_q, heads_kv, seqlen_q, seqlen_kv, d8, strides, causal, seqlen_kv - seqlen_q, float(head_dim) ** -0.5, -1.0, dropout_p, flags, num_splits)
   p.q = p.k = p.v = p.o = 16
-  p.batch, p.heads_q, p.heads_kv, p.seqlen_q, p.seqlen_kv, p.head_dim = int(batch), int(heads_q), int(heads_kv), int(seqlen_q), int(seqlen_kv), d8
-  for name, h, n in (("q_stride", heads_q, seqlen_q), ("k_stride", heads_kv, seqlen_kv), ("v_stride", heads_kv, seqlen_kv), ("o_stride", heads_q, seqlen_q)):
-    getattr(p, name)[:] = [h * n * d8, n * d8, d8]
-  p.dtype = _DTYPE[dtype]
-  p.causal = 1 if causal else 0
-  p.causal_offset = int(seqlen_kv) - int(seqlen_q)
-  p.softmax_scale = float(head_dim) ** -0.5
-  p.rescale_threshold = -1.0
-  p.dropout_p = float(dropout_p)
-  p.flags = int(flags)
-  p.num_splits = int(num_splits)
   if bias_dtype is not None:
     p.bias = 16
     p.bias_dtype = _BIAS_DTYPE[bias_dtype]
-    p.bias_stride[:] = [0, 0, int(seqlen_kv), 1]
+    p.bias_stride[:] = [0, 0, seqlen_kv, 1]
   if num_splits != 1:
     p.workspace, p.workspace_bytes = 16, (1 << 62)
-  plan = (ctypes.c_int * 4)()
-  name = ctypes.create_string_buffer(160)
-
-  def ask():
-    rc = lib.ffpa_attn_fwd_plan(ctypes.byref(p), plan)
-    if rc != 0:
-      raise _STATUS_EXC.get(rc, RuntimeError)(lib.ffpa_attn_last_error().decode())
-    lib.ffpa_attn_fwd_kernel(ctypes.byref(p), name, len(name))
-
+  query = (lib, lib.ffpa_attn_fwd_plan, lib.ffpa_attn_fwd_kernel, _FWD_PLAN_KEYS, (ctypes.byref(p),), True)
   if device is not None and torch.cuda.is_available():
     with torch.cuda.device(device):
-      ask()
-  else:
-    ask()
-  return {"variant": plan[0], "block_rows": plan[1], "block_keys": plan[2], "splits": plan[3], "kernel": name.value.decode()}
+      return _read_plan(*query)
+  return _read_plan(*query)
 
 
 def padded_head_dim(d: int) -> int:
@@ -450,14 +453,36 @@ def padded_head_dim(d: int) -> int:
   return ((d + 63) // 64) * 64
 
 
-def _dense_rows(t: torch.Tensor) -> torch.Tensor:
-  """Make ``t`` satisfy the layout contract: headdim stride 1, all other strides multiples of
-  8 elements, 16-byte aligned base (split_d.cuh:137-142 assumed dense [B,H,N,D]; here arbitrary
-  batch/head/row strides are honoured and only pathological views are copied)."""
-  ok = t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
-  if ok and t.dim() == 4 and t.size(2) > 1 and t.stride(2) < t.size(3):
+def _layout_ok(t: torch.Tensor, row_dim: "int | None" = None) -> bool:
+  """The layout contract of every tensor the kernels read or write through 16-byte accesses: head-dim stride 1, every other stride a (non-negative) multiple of
+  8 elements, a 16-byte aligned base — and, with ``row_dim``, rows along that axis that do not overlap (split_d.cuh:137-142 assumed dense [B,H,N,D]; here
+  arbitrary batch / head / row strides are honoured)."""
+  ok = t.stride(-1) == 1 and all(s % 8 == 0 and s >= 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
+  if ok and row_dim is not None and t.size(row_dim) > 1 and t.stride(row_dim) < t.size(-1):
     ok = False  # overlapping rows
-  return t if ok else t.contiguous()
+  return ok
+
+
+def _rows(t: torch.Tensor, row_dim: "int | None" = None) -> torch.Tensor:
+  """``t`` if it satisfies the layout contract, else a dense copy (only pathological views are copied)."""
+  if t.is_contiguous():
+    return t  # (a dense tensor is its own dense copy: nothing to decide, and the decode path's tensors are dense)
+  return t if _layout_ok(t, row_dim) else t.contiguous()
+
+
+def _pad_head_dim(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
+  """Rows must be whole 16-byte slots: only a head dim that is not a multiple of 8 is padded (copies) -> ``(q, k, v, padded head dim)``; the call slices its
+  output back with ``_unpad_head_dim``."""
+  D = q.size(-1)
+  Dp = (D + 7) // 8 * 8
+  if Dp != D:
+    pad = (0, Dp - D)
+    q, k, v = (torch.nn.functional.pad(t, pad) for t in (q, k, v))
+  return q, k, v, Dp
+
+
+def _unpad_head_dim(o: torch.Tensor, D: int) -> torch.Tensor:
+  return o[..., :D].contiguous() if o.size(-1) != D else o  # the ops' contract (and their fake impls): a dense tensor of the caller's head dim
 
 
 def mask_kv_bounds(attn_bias: torch.Tensor, nq: int, nkv: int) -> torch.Tensor:
@@ -473,11 +498,10 @@ def mask_kv_bounds(attn_bias: torch.Tensor, nq: int, nkv: int) -> torch.Tensor:
     lib = load_library()
     out = torch.empty((bb, hb, nblk, 4), dtype=torch.int32, device=attn_bias.device)
     strides = (ctypes.c_int64 * 4)(*[attn_bias.stride(d) if attn_bias.size(d) > 1 else 0 for d in range(4)])
-    with torch.cuda.device(attn_bias.device):
-      rc = lib.ffpa_attn_mask_kv_bounds(ctypes.c_void_p(attn_bias.data_ptr()), _BIAS_DTYPE[attn_bias.dtype], strides, bb, hb, nq, nkv,
-                                        ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(attn_bias.device).cuda_stream))
+    rc = _call_on_stream(lib.ffpa_attn_mask_kv_bounds, attn_bias.device, ctypes.c_void_p(attn_bias.data_ptr()), _BIAS_DTYPE[attn_bias.dtype], strides, bb, hb, nq, nkv,
+                         ctypes.c_void_p(out.data_ptr()))
     if rc != 0:
-      raise _STATUS_EXC.get(rc, RuntimeError)(lib.ffpa_attn_last_error().decode())
+      _raise_status(lib, rc)
     return out
   is_bool = attn_bias.dtype in (torch.bool, torch.uint8)
   vis = attn_bias.ne(0) if is_bool else ~torch.isneginf(attn_bias)      # [Bb, Hb, Nq|1, Nkv|1]
@@ -620,6 +644,16 @@ def _workspace(device: torch.device, stream: int, nbytes: int) -> torch.Tensor:
   return t
 
 
+def _hand_over_workspace(p, device: torch.device, stream: int, nbytes: int) -> "torch.Tensor | None":
+  """Point ``p.workspace`` at ``nbytes`` of this stream's scratch; the caller holds the returned tensor in a local until its launch has been enqueued."""
+  if not nbytes:
+    return None
+  workspace = _workspace(device, stream, nbytes)
+  p.workspace = workspace.data_ptr()
+  p.workspace_bytes = nbytes
+  return workspace
+
+
 # What a launch needs besides its tensors — workspace bytes and ticket count — is a function of the shape class only (ffpa_capi.hip make_plan): asked
 # once per class, not once per call (two ctypes round trips less per decode token).  The class names everything make_plan prices with (the mask KIND too: the
 # wide-row tile of D = 320 is for boolean masks only, and another tile is another number of workgroups); the library clamps the split count to the scratch it is
@@ -715,10 +749,7 @@ def forward(
   out_shape = (B, Hq, Nq)
   if causal_offset is None:
     causal_offset = Nkv - Nq
-  Dp = (D + 7) // 8 * 8  # rows must be whole 16-byte slots: only a head dim that is not a multiple of 8 is padded (copies)
-  if Dp != D:
-    pad = (0, Dp - D)
-    q, k, v = (torch.nn.functional.pad(t, pad) for t in (q, k, v))
+  q, k, v, Dp = _pad_head_dim(q, k, v)
   group = Hq // Hkv if Hkv and Hq % Hkv == 0 else 1
   has_bias = attn_bias is not None and attn_bias.numel() > 0
   packed = causal_row_mod == 0 and group > 1 and Nq <= 7 and group * Nq <= 32 and not has_bias and dropout_p == 0.0
@@ -727,19 +758,19 @@ def forward(
     q = q.contiguous().view(B, Hkv, group * Nq, Dp)
     causal_row_mod = Nq
     Hq, Nq = Hkv, group * Nq
-  q, k, v = _dense_rows(q), _dense_rows(k), _dense_rows(v)
+  q, k, v = _rows(q, 2), _rows(k, 2), _rows(v, 2)
   o = torch.empty((B, Hq, Nq, Dp), dtype=q.dtype, device=q.device)
   lse = torch.empty((B, Hq, Nq), dtype=torch.float32, device=q.device) if return_lse else None
+  if num_splits == 0 and Nq > 32 and os.environ.get("FFPA_HIP_PREFILL_SPLITS", "1").lower() in ("0", "off", "false", "no"):
+    # opt-out of the KV-split rules for PREFILL launches (under-filled / part of a round / ragged round: ffpa_capi.hip make_plan): they allocate fp32
+    # scratch of splits x B x Hq x Nq x (D + 1) x 4 bytes per call (up to kMaxAutoWorkspaceBytes = 1 GiB) and make the bits of a (batch, head) slice depend on
+    # how many heads share the launch (fp32 partials + LSE merge: equal to rounding, not to the bit).  Short-query (decode) launches keep their rule.
+    num_splits = 1
 
-  p = FfpaFwdParams()
-  p.struct_size = ctypes.sizeof(FfpaFwdParams)
-  p.abi_version = ABI_VERSION
+  p = _fwd_params(q.dtype, B, Hq, Hkv, Nq, Nkv, Dp, [t.stride()[:3] for t in (q, k, v, o)], causal, causal_offset, softmax_scale, rescale_threshold, dropout_p,
+                  int(flags) | _deterministic_flag(), num_splits)
   p.q, p.k, p.v, p.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr()
   p.lse = lse.data_ptr() if lse is not None else None
-  p.batch, p.heads_q, p.heads_kv = B, Hq, Hkv
-  p.seqlen_q, p.seqlen_kv, p.head_dim = Nq, Nkv, Dp
-  for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", o)):
-    getattr(p, name)[:] = list(t.stride()[:3])
   if attn_bias is not None and attn_bias.numel() > 0:
     if attn_bias.dim() != 4:
       raise ValueError("attn_bias must be 4-D [B|1, Hq|1, Nq|1, Nkv|1]")
@@ -770,23 +801,7 @@ def forward(
         raise ValueError("kv_bounds batch / head dims must be 1 or match q, on q's device")
       p.kv_bounds = kv_bounds.data_ptr()
       p.kv_bounds_stride[:] = [kv_bounds.stride(0) if kv_bounds.size(0) > 1 else 0, kv_bounds.stride(1) if kv_bounds.size(1) > 1 else 0]
-  else:
-    p.bias = None
-    p.bias_dtype = 0
-  if num_splits == 0 and Nq > 32 and os.environ.get("FFPA_HIP_PREFILL_SPLITS", "1").lower() in ("0", "off", "false", "no"):
-    # opt-out of the KV-split rules for PREFILL launches (under-filled / part of a round / ragged round: ffpa_capi.hip make_plan): they allocate fp32
-    # scratch of splits x B x Hq x Nq x (D + 1) x 4 bytes per call (up to kMaxAutoWorkspaceBytes = 1 GiB) and make the bits of a (batch, head) slice depend on
-    # how many heads share the launch (fp32 partials + LSE merge: equal to rounding, not to the bit).  Short-query (decode) launches keep their rule.
-    num_splits = 1
-  p.dtype = _DTYPE[q.dtype]
-  p.causal = 1 if causal else 0
-  p.causal_offset = int(causal_offset)
   p.causal_row_mod = int(causal_row_mod)
-  p.num_splits = int(num_splits)
-  p.softmax_scale = float(softmax_scale)
-  p.rescale_threshold = float(rescale_threshold)
-  p.dropout_p = float(dropout_p)
-  p.flags = int(flags) | (FLAG_DETERMINISTIC if os.environ.get("FFPA_HIP_DETERMINISTIC", "0").lower() not in ("0", "", "off", "false", "no") else 0)
   p.philox_seed = int(philox_seed) & 0xFFFFFFFFFFFFFFFF
   p.philox_offset = int(philox_offset) & 0xFFFFFFFFFFFFFFFF
 
@@ -796,33 +811,25 @@ def forward(
     if merge_in_launch is None:
       merge_in_launch = os.environ.get("FFPA_HIP_MERGE_IN_LAUNCH", "0") not in ("0", "")
     ws_bytes, n_tickets = _plan_scratch(lib, p, num_splits, bool(merge_in_launch), q.device.index or 0)
-    workspace = None
-    if ws_bytes:
-      workspace = _workspace(q.device, stream, ws_bytes)  # (held in a local until the launch below has been enqueued)
-      p.workspace = workspace.data_ptr()
-      p.workspace_bytes = ws_bytes
-      if n_tickets:
-        tickets = _split_tickets(q.device, stream, n_tickets)
-        p.split_tickets = tickets.data_ptr()
+    workspace = _hand_over_workspace(p, q.device, stream, ws_bytes)  # (held in a local until the launch below has been enqueued)
+    if workspace is not None and n_tickets:
+      tickets = _split_tickets(q.device, stream, n_tickets)
+      p.split_tickets = tickets.data_ptr()
     if plan_out is not None:
-      plan = (ctypes.c_int * 4)()
-      if lib.ffpa_attn_fwd_plan(ctypes.byref(p), plan) == 0:
-        plan_out.update(variant=plan[0], block_rows=plan[1], block_keys=plan[2], splits=plan[3], packed=bool(packed))
-      name = ctypes.create_string_buffer(160)
-      if hasattr(lib, "ffpa_attn_fwd_kernel") and lib.ffpa_attn_fwd_kernel(ctypes.byref(p), name, len(name)) == 0:
-        plan_out["kernel"] = name.value.decode()
+      plan = _read_plan(lib, lib.ffpa_attn_fwd_plan, getattr(lib, "ffpa_attn_fwd_kernel", None), _FWD_PLAN_KEYS, (ctypes.byref(p),))
+      if "variant" in plan:
+        plan["packed"] = bool(packed)
+      plan_out.update(plan)
     rc = lib.ffpa_attn_fwd(ctypes.byref(p), ctypes.c_void_p(stream))
   if rc != 0:
     if tickets is not None:
       tickets.zero_()  # a launch that did not complete may have left counters behind: the next call must start from zeros
-    raise _STATUS_EXC.get(rc, RuntimeError)(f"ffpa_attn_fwd: {lib.ffpa_attn_last_error().decode()} (status {rc})")
+    _raise_status(lib, rc, "ffpa_attn_fwd")
   del tickets
   if packed:
     o = o.view(*out_shape, Dp)
     lse = lse.view(out_shape) if lse is not None else None
-  if Dp != D:
-    o = o[..., :D].contiguous()  # the op's contract (and its fake impl): a dense [B, Hq, Nq, D]
-  return o, lse
+  return _unpad_head_dim(o, D), lse
 
 
 # ----------------------------------------------------------------------------------
@@ -942,44 +949,51 @@ def ffpa_attn_forward_hip(
 # Packed sequences (ffpa_attn_varlen_func): the launch wrapper and its torch.library op.  Replaces the reference's
 # ffpa_attn::_varlen_fwd_cute (src/ffpa_attn/cute/__init__.py:792-880), which only its CuTe-DSL backend serves.
 # ----------------------------------------------------------------------------------
-def _packed_rows(t: torch.Tensor) -> torch.Tensor:
-  """[T, H, D] with head-dim stride 1, row / head strides multiples of 8 elements, non-overlapping rows and a 16-byte aligned base — else a copy."""
-  ok = t.stride(-1) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
-  if ok and t.size(0) > 1 and t.stride(0) < t.size(2):
-    ok = False
-  return t if ok else t.contiguous()
-
-
-def _varlen_params(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_seqlen_k: int, causal: bool, softmax_scale: float,
-                   rescale_threshold: float, flags: int, seqused_k=None, num_splits: int = 0) -> FfpaVarlenFwdParams:
-  p = FfpaVarlenFwdParams()
-  p.struct_size = ctypes.sizeof(FfpaVarlenFwdParams)
-  p.abi_version = ABI_VERSION
-  p.q, p.k, p.v, p.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr()
-  p.lse = lse.data_ptr() if lse is not None else None
-  p.cu_seqlens_q, p.cu_seqlens_kv = cu_seqlens_q.data_ptr(), (cu_seqlens_k.data_ptr() if cu_seqlens_k is not None else None)
-  p.seqused_kv = seqused_k.data_ptr() if seqused_k is not None else None
-  p.batch = cu_seqlens_q.numel() - 1
-  p.heads_q, p.heads_kv, p.head_dim = q.size(1), k.size(1), q.size(2)
+def _varlen_params(dtype: torch.dtype, batch: int, heads_q: int, heads_kv: int, head_dim: int, max_seqlen_q: int, max_seqlen_k: int, total_q: int, strides, causal: bool,
+                   softmax_scale: float, rescale_threshold: float, flags: int, num_splits: int) -> FfpaVarlenFwdParams:
+  """``ffpa_varlen_fwd_params`` without its pointers: the shape class, ``strides`` = the row / head element strides of q, k, v, o, and the scalars.  The launch adds
+  the tensors' addresses (and its scratch), a plan query placeholders."""
+  p = _stamped(FfpaVarlenFwdParams)
+  p.batch, p.heads_q, p.heads_kv, p.head_dim = batch, heads_q, heads_kv, head_dim
   p.max_seqlen_q, p.max_seqlen_kv = int(max_seqlen_q), int(max_seqlen_k)
-  for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", o)):
-    getattr(p, name)[:] = [t.stride(0), t.stride(1)]
-  p.lse_stride_head = lse.stride(0) if lse is not None else 0
-  p.dtype = _DTYPE[q.dtype]
+  p.q_stride[:], p.k_stride[:], p.v_stride[:], p.o_stride[:] = strides
+  p.dtype = _DTYPE[dtype]
   p.causal = 1 if causal else 0
   p.softmax_scale = float(softmax_scale)
   p.rescale_threshold = float(rescale_threshold)
-  p.flags = int(flags) | (FLAG_DETERMINISTIC if os.environ.get("FFPA_HIP_DETERMINISTIC", "0").lower() not in ("0", "", "off", "false", "no") else 0)
+  p.flags = int(flags)
   p.num_splits = int(num_splits)
-  p.total_q = q.size(0)
+  p.total_q = total_q
   return p
+
+
+def _paged_kv(block_table: int, bt_stride: int, pages_per_row: int, page_size: int, num_pages: int, k_page_stride: int, v_page_stride: int) -> FfpaPagedKv:
+  """``ffpa_paged_kv``: the block table's address and row stride, the pool's geometry and its K / V page strides (elements)."""
+  kv = _stamped(FfpaPagedKv)
+  kv.block_table, kv.bt_stride, kv.pages_per_row = block_table, bt_stride, pages_per_row
+  kv.page_size, kv.num_pages = page_size, num_pages
+  kv.k_page_stride, kv.v_page_stride = k_page_stride, v_page_stride
+  return kv
+
+
+def _paged_kv_of(block_table: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> "tuple[FfpaPagedKv, torch.Tensor]":
+  """``ffpa_paged_kv`` of a block table ``[B, pages_per_row]`` over the pools ``k`` / ``v [num_pages, page_size, Hkv, D]`` -> ``(kv, the table it points at)``: a table whose
+  rows are not dense is copied, and the caller keeps that copy alive until its launch has been enqueued."""
+  if block_table.stride(1) != 1 or block_table.data_ptr() % 4 != 0:
+    block_table = block_table.contiguous()
+  return _paged_kv(block_table.data_ptr(), block_table.stride(0), block_table.size(1), k.size(1), k.size(0), k.stride(0), v.stride(0)), block_table
+
+
+def _varlen_fn(lib, kv: "FfpaPagedKv | None", suffix: str = ""):
+  """The packed call's export — or, with ``kv``, its paged twin's — of this suffix ("" the launch, "_plan", "_kernel", "_workspace_bytes")"""
+  return getattr(lib, ("ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd") + suffix)
 
 
 # Scratch of a KV-split packed launch: a function of the shape class (ffpa_capi.hip varlen_plan), asked once per class
 _VARLEN_SCRATCH: "dict[tuple, int]" = {}
 
 
-def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaPagedKv | None" = None) -> int:
+def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaPagedKv | None", args: tuple) -> int:
   if p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC:
     return 0
   key = (id(lib), device_index, p.dtype, p.batch, p.heads_q, p.heads_kv, p.head_dim, p.max_seqlen_q, p.max_seqlen_kv, p.total_q, p.causal, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS"),
@@ -988,15 +1002,11 @@ def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaP
   if hit is None:
     if len(_VARLEN_SCRATCH) >= 512:
       _VARLEN_SCRATCH.clear()
-    if kv is None:
-      hit = int(lib.ffpa_attn_varlen_fwd_workspace_bytes(ctypes.byref(p)))
-    else:
-      hit = int(lib.ffpa_attn_varlen_paged_fwd_workspace_bytes(ctypes.byref(p), ctypes.byref(kv)))
-    _VARLEN_SCRATCH[key] = hit
+    hit = _VARLEN_SCRATCH[key] = int(_varlen_fn(lib, kv, "_workspace_bytes")(*args))
   return hit
 
 
-def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor, max_seqlen_q: int,
+def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: "torch.Tensor | None", max_seqlen_q: int,
                    max_seqlen_k: int, causal: bool, softmax_scale: float, *, rescale_threshold: float = -1.0, return_lse: bool = True, flags: int = 0,
                    plan_out: "dict | None" = None, seqused_k: "torch.Tensor | None" = None, num_splits: int = 0, block_table: "torch.Tensor | None" = None):
   """One launch of the packed-sequence kernel: ``q [T_q, Hq, D]``, ``k`` / ``v [T_k, Hkv, D]``, int32 device ``cu_seqlens_*`` ``[B + 1]`` ->
@@ -1016,157 +1026,85 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
   of 64), key j of sequence i is row ``j % page_size`` of page ``block_table[i, j // page_size]``; ``seqused_k`` is required and gives the lengths (clamped to
   ``pages_per_row * page_size``), ``cu_seqlens_k`` is ignored (may be None).  One launch of the paged twin of the packed kernel (``ffpa_attn_varlen_paged_fwd``):
   no gather, nothing read back to the host, graph-capturable; replays follow ``seqused_k`` / ``block_table`` written in place."""
-  if block_table is not None:
-    return _paged_forward(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, causal, softmax_scale,
-                          rescale_threshold=rescale_threshold, return_lse=return_lse, flags=flags, plan_out=plan_out, num_splits=num_splits)
-  if not q.is_cuda:
-    raise NotImplementedError(f"ffpa_attn::_varlen_fwd_hip has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
-  lib = load_library()
-  if q.dtype not in _DTYPE or k.dtype != q.dtype or v.dtype != q.dtype:
-    raise TypeError(f"ffpa_attn::_varlen_fwd_hip only supports fp16/bf16 q/k/v of one dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
-  if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
-    raise ValueError("ffpa_attn::_varlen_fwd_hip: q/k/v must be 3-D packed [T, H, D] tensors")
-  if k.shape != v.shape or k.size(2) != q.size(2):
-    raise ValueError(f"ffpa_attn::_varlen_fwd_hip: k {tuple(k.shape)} and v {tuple(v.shape)} must share their shape and q's head dim ({q.size(2)})")
-  if k.size(1) == 0 or q.size(1) % k.size(1) != 0:
-    raise ValueError(f"ffpa_attn::_varlen_fwd_hip: query num_heads ({q.size(1)}) must be a multiple of key/value num_heads ({k.size(1)})")
-  for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
-    if cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 2:
-      raise ValueError(f"ffpa_attn::_varlen_fwd_hip: {name} must be a 1-D int32 tensor of length batch + 1")
-    if cu.device != q.device:
-      raise ValueError(f"ffpa_attn::_varlen_fwd_hip: {name} must be on q's device, got {cu.device} and {q.device}")
-  if cu_seqlens_q.numel() != cu_seqlens_k.numel():
-    raise ValueError("ffpa_attn::_varlen_fwd_hip: cu_seqlens_q and cu_seqlens_k must have one length")
-  if seqused_k is not None:
-    if seqused_k.dtype != torch.int32 or seqused_k.dim() != 1 or seqused_k.numel() != cu_seqlens_k.numel() - 1 or seqused_k.device != q.device:
-      raise ValueError("ffpa_attn::_varlen_fwd_hip: seqused_k must be a 1-D int32 tensor of length batch on q's device")
-    seqused_k = seqused_k.contiguous()
-  if k.device != q.device or v.device != q.device:
-    raise ValueError(f"ffpa_attn::_varlen_fwd_hip: q/k/v must be on one device, got {q.device}, {k.device}, {v.device}")
-  Tq, Hq, D = q.shape
-  Dp = (D + 7) // 8 * 8  # rows must be whole 16-byte slots: only a head dim that is not a multiple of 8 is padded (copies)
-  if Dp != D:
-    pad = (0, Dp - D)
-    q, k, v = (torch.nn.functional.pad(t, pad) for t in (q, k, v))
-  if k.size(0) == 0:
-    # no key row anywhere: every output row is the empty row (O = 0, LSE = -inf).  The C-ABI wants non-NULL bases; nothing is read through them
-    k = v = q.new_zeros((1, k.size(1), Dp))
-  q, k, v = _packed_rows(q), _packed_rows(k), _packed_rows(v)
-  cu_seqlens_q, cu_seqlens_k = cu_seqlens_q.contiguous(), cu_seqlens_k.contiguous()
-  o = torch.empty((Tq, Hq, Dp), dtype=q.dtype, device=q.device)
-  lse = torch.empty((Hq, Tq), dtype=torch.float32, device=q.device) if return_lse else None
-  if Tq == 0 or max_seqlen_q <= 0:
-    return (o[..., :D] if Dp != D else o), lse  # (nothing to compute: no query row in any sequence)
-  p = _varlen_params(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, rescale_threshold, flags, seqused_k, num_splits)
-  with torch.cuda.device(q.device):
-    stream = torch.cuda.current_stream(q.device).cuda_stream
-    ws_bytes = _varlen_scratch(lib, p, q.device.index or 0)
-    workspace = None
-    if ws_bytes:
-      workspace = _workspace(q.device, stream, ws_bytes)  # (held in a local until the launch below has been enqueued)
-      p.workspace = workspace.data_ptr()
-      p.workspace_bytes = ws_bytes
-    if plan_out is not None:
-      plan = (ctypes.c_int * 5)()
-      if lib.ffpa_attn_varlen_fwd_plan(ctypes.byref(p), plan) == 0:
-        plan_out.update(row_tiles=plan[0], block_rows=plan[1], block_keys=plan[2], workgroups=plan[3], splits=plan[4])
-      name = ctypes.create_string_buffer(200)
-      if lib.ffpa_attn_varlen_fwd_kernel(ctypes.byref(p), name, len(name)) == 0:
-        plan_out["kernel"] = name.value.decode()
-    rc = lib.ffpa_attn_varlen_fwd(ctypes.byref(p), ctypes.c_void_p(stream))
-  if rc != 0:
-    raise _STATUS_EXC.get(rc, RuntimeError)(f"ffpa_attn_varlen_fwd: {lib.ffpa_attn_last_error().decode()} (status {rc})")
-  if Dp != D:
-    o = o[..., :D].contiguous()
-  return o, lse
-
-
-def _paged_kv(block_table: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> FfpaPagedKv:
-  kv = FfpaPagedKv()
-  kv.struct_size = ctypes.sizeof(FfpaPagedKv)
-  kv.block_table = block_table.data_ptr()
-  kv.bt_stride = block_table.stride(0)
-  kv.pages_per_row = block_table.size(1)
-  kv.page_size = k.size(1)
-  kv.num_pages = k.size(0)
-  kv.k_page_stride, kv.v_page_stride = k.stride(0), v.stride(0)
-  return kv
-
-
-def _paged_pool(t: torch.Tensor) -> torch.Tensor:
-  """[num_pages, page_size, H, D] with head-dim stride 1, page / row / head strides multiples of 8 elements, non-overlapping rows, 16-byte aligned — else a copy."""
-  ok = t.stride(-1) == 1 and all(t.stride(i) % 8 == 0 for i in range(3)) and t.data_ptr() % 16 == 0 and t.stride(1) >= t.size(3)
-  return t if ok else t.contiguous()
-
-
-def _paged_forward(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q: int, max_seqlen_k: int, causal: bool, softmax_scale: float, *,
-                   rescale_threshold: float = -1.0, return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
-  name = "ffpa_attn::_paged_fwd_hip"
+  paged = block_table is not None
+  name = "ffpa_attn::_paged_fwd_hip" if paged else "ffpa_attn::_varlen_fwd_hip"
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
   if q.dtype not in _DTYPE or k.dtype != q.dtype or v.dtype != q.dtype:
     raise TypeError(f"{name} only supports fp16/bf16 q/k/v of one dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
-  if q.dim() != 3 or k.dim() != 4 or v.dim() != 4:
-    raise ValueError(f"{name}: q must be packed [T, Hq, D] and k / v paged [num_pages, page_size, Hkv, D]")
-  if k.shape != v.shape or k.size(3) != q.size(2):
+  if paged:
+    if q.dim() != 3 or k.dim() != 4 or v.dim() != 4:
+      raise ValueError(f"{name}: q must be packed [T, Hq, D] and k / v paged [num_pages, page_size, Hkv, D]")
+  elif q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+    raise ValueError(f"{name}: q/k/v must be 3-D packed [T, H, D] tensors")
+  if k.shape != v.shape or k.size(-1) != q.size(2):
     raise ValueError(f"{name}: k {tuple(k.shape)} and v {tuple(v.shape)} must share their shape and q's head dim ({q.size(2)})")
-  if k.size(2) == 0 or q.size(1) % k.size(2) != 0:
-    raise ValueError(f"{name}: query num_heads ({q.size(1)}) must be a multiple of key/value num_heads ({k.size(2)})")
-  if k.size(1) <= 0 or k.size(1) % 64 != 0:
-    raise ValueError(f"{name}: page_size ({k.size(1)}) must be a positive multiple of 64")
-  if cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.device != q.device:
-    raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor of length batch + 1 on q's device")
-  batch = cu_seqlens_q.numel() - 1
-  if seqused_k is None:
-    raise ValueError(f"{name}: seqused_k is required with a block_table (it gives the key lengths)")
-  if seqused_k.dtype != torch.int32 or seqused_k.dim() != 1 or seqused_k.numel() != batch or seqused_k.device != q.device:
-    raise ValueError(f"{name}: seqused_k must be a 1-D int32 tensor of length batch on q's device")
-  if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != batch or block_table.size(1) == 0 or block_table.device != q.device:
-    raise ValueError(f"{name}: block_table must be a 2-D int32 tensor [batch, pages_per_seq] (pages_per_seq >= 1) on q's device")
+  if k.size(-2) == 0 or q.size(1) % k.size(-2) != 0:
+    raise ValueError(f"{name}: query num_heads ({q.size(1)}) must be a multiple of key/value num_heads ({k.size(-2)})")
+  if paged:
+    if k.size(1) <= 0 or k.size(1) % 64 != 0:
+      raise ValueError(f"{name}: page_size ({k.size(1)}) must be a positive multiple of 64")
+    if cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.device != q.device:
+      raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor of length batch + 1 on q's device")
+    batch = cu_seqlens_q.numel() - 1
+    if seqused_k is None:
+      raise ValueError(f"{name}: seqused_k is required with a block_table (it gives the key lengths)")
+    if seqused_k.dtype != torch.int32 or seqused_k.dim() != 1 or seqused_k.numel() != batch or seqused_k.device != q.device:
+      raise ValueError(f"{name}: seqused_k must be a 1-D int32 tensor of length batch on q's device")
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != batch or block_table.size(1) == 0 or block_table.device != q.device:
+      raise ValueError(f"{name}: block_table must be a 2-D int32 tensor [batch, pages_per_seq] (pages_per_seq >= 1) on q's device")
+    cu_seqlens_k = None  # (not read: the lengths are seqused_k's)
+  else:
+    for nm, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+      if cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 2:
+        raise ValueError(f"{name}: {nm} must be a 1-D int32 tensor of length batch + 1")
+      if cu.device != q.device:
+        raise ValueError(f"{name}: {nm} must be on q's device, got {cu.device} and {q.device}")
+    if cu_seqlens_q.numel() != cu_seqlens_k.numel():
+      raise ValueError(f"{name}: cu_seqlens_q and cu_seqlens_k must have one length")
+    if seqused_k is not None and (seqused_k.dtype != torch.int32 or seqused_k.dim() != 1 or seqused_k.numel() != cu_seqlens_k.numel() - 1 or seqused_k.device != q.device):
+      raise ValueError(f"{name}: seqused_k must be a 1-D int32 tensor of length batch on q's device")
+    cu_seqlens_k = cu_seqlens_k.contiguous()
   if k.device != q.device or v.device != q.device:
     raise ValueError(f"{name}: q/k/v must be on one device, got {q.device}, {k.device}, {v.device}")
   Tq, Hq, D = q.shape
-  Dp = (D + 7) // 8 * 8  # rows must be whole 16-byte slots: only a head dim that is not a multiple of 8 is padded (copies the pools)
-  if Dp != D:
-    pad = (0, Dp - D)
-    q, k, v = (torch.nn.functional.pad(t, pad) for t in (q, k, v))
+  q, k, v, Dp = _pad_head_dim(q, k, v)  # (a paged call: copies the pools)
   if k.size(0) == 0:
-    # an empty pool: no key anywhere (ids clamp into this one zero page; its rows are never more than a page)
-    k = v = q.new_zeros((1, k.size(1), k.size(2), Dp))
-  q, k, v = _packed_rows(q), _paged_pool(k), _paged_pool(v)
-  if block_table.stride(1) != 1 or block_table.data_ptr() % 4 != 0:
-    block_table = block_table.contiguous()
-  cu_seqlens_q, seqused_k = cu_seqlens_q.contiguous(), seqused_k.contiguous()
+    # no key row anywhere (an empty pool: ids clamp into this one zero page): every output row is the empty row (O = 0, LSE = -inf).  The C-ABI wants non-NULL
+    # bases; nothing is read through them
+    k = v = q.new_zeros((1, *k.shape[1:-1], Dp))
+  q, k, v = _rows(q, 0), _rows(k, -3), _rows(v, -3)  # (k / v: [T, H, D] rows or [num_pages, page_size, H, D] pools — the row axis is the third from the end)
+  cu_seqlens_q = cu_seqlens_q.contiguous()
+  if seqused_k is not None:
+    seqused_k = seqused_k.contiguous()
   o = torch.empty((Tq, Hq, Dp), dtype=q.dtype, device=q.device)
   lse = torch.empty((Hq, Tq), dtype=torch.float32, device=q.device) if return_lse else None
   if Tq == 0 or max_seqlen_q <= 0:
-    return (o[..., :D] if Dp != D else o), lse
-  # (the packed call's parameters on the pool: k_stride / v_stride = {row, head} inside a page)
-  p = _varlen_params(q, k[0], v[0], o, lse, cu_seqlens_q, None, max_seqlen_q, max_seqlen_k, causal, softmax_scale, rescale_threshold, flags, seqused_k, num_splits)
-  p.k, p.v = k.data_ptr(), v.data_ptr()
-  kv = _paged_kv(block_table, k, v)
+    return (o[..., :D] if Dp != D else o), lse  # (nothing to compute: no query row in any sequence)
+  # (a pool's k_stride / v_stride are {row, head} inside a page)
+  p = _varlen_params(q.dtype, cu_seqlens_q.numel() - 1, Hq, k.size(-2), Dp, max_seqlen_q, max_seqlen_k, Tq, [t.stride()[-3:-1] for t in (q, k, v, o)], causal, softmax_scale,
+                     rescale_threshold, int(flags) | _deterministic_flag(), num_splits)
+  p.q, p.k, p.v, p.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr()
+  p.lse = lse.data_ptr() if lse is not None else None
+  p.lse_stride_head = lse.stride(0) if lse is not None else 0
+  p.cu_seqlens_q = cu_seqlens_q.data_ptr()
+  p.cu_seqlens_kv = cu_seqlens_k.data_ptr() if cu_seqlens_k is not None else None
+  p.seqused_kv = seqused_k.data_ptr() if seqused_k is not None else None
+  kv = None
+  args = (ctypes.byref(p),)
+  if paged:
+    kv, block_table = _paged_kv_of(block_table, k, v)
+    args = (ctypes.byref(p), ctypes.byref(kv))
   with torch.cuda.device(q.device):
     stream = torch.cuda.current_stream(q.device).cuda_stream
-    ws_bytes = _varlen_scratch(lib, p, q.device.index or 0, kv)
-    workspace = None
-    if ws_bytes:
-      workspace = _workspace(q.device, stream, ws_bytes)
-      p.workspace = workspace.data_ptr()
-      p.workspace_bytes = ws_bytes
+    workspace = _hand_over_workspace(p, q.device, stream, _varlen_scratch(lib, p, q.device.index or 0, kv, args))  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
-      plan = (ctypes.c_int * 5)()
-      if lib.ffpa_attn_varlen_paged_fwd_plan(ctypes.byref(p), ctypes.byref(kv), plan) == 0:
-        plan_out.update(row_tiles=plan[0], block_rows=plan[1], block_keys=plan[2], workgroups=plan[3], splits=plan[4])
-      kname = ctypes.create_string_buffer(200)
-      if lib.ffpa_attn_varlen_paged_fwd_kernel(ctypes.byref(p), ctypes.byref(kv), kname, len(kname)) == 0:
-        plan_out["kernel"] = kname.value.decode()
-    rc = lib.ffpa_attn_varlen_paged_fwd(ctypes.byref(p), ctypes.byref(kv), ctypes.c_void_p(stream))
+      plan_out.update(_read_plan(lib, _varlen_fn(lib, kv, "_plan"), _varlen_fn(lib, kv, "_kernel"), _VARLEN_PLAN_KEYS, args))
+    rc = _varlen_fn(lib, kv)(*args, ctypes.c_void_p(stream))
   if rc != 0:
-    raise _STATUS_EXC.get(rc, RuntimeError)(f"ffpa_attn_varlen_paged_fwd: {lib.ffpa_attn_last_error().decode()} (status {rc})")
-  if Dp != D:
-    o = o[..., :D].contiguous()
-  return o, lse
+    _raise_status(lib, rc, "ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd")
+  return _unpad_head_dim(o, D), lse
 
 
 def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: int, max_seqlen_k: int, head_dim: int, *,
@@ -1178,45 +1116,21 @@ def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: in
   covering max_seqlen_k)."""
   lib = load_library()
   d8 = (int(head_dim) + 7) // 8 * 8
-  p = FfpaVarlenFwdParams()
-  p.struct_size = ctypes.sizeof(FfpaVarlenFwdParams)
-  p.abi_version = ABI_VERSION
+  strides = [(h * d8, d8) for h in (heads_q, heads_kv, heads_kv, heads_q)]
+  p = _varlen_params(dtype, int(batch), int(heads_q), int(heads_kv), d8, max_seqlen_q, max_seqlen_k, int(total_q), strides, causal, float(head_dim) ** -0.5, -1.0, flags, num_splits)
   p.q = p.k = p.v = p.o = p.cu_seqlens_q = p.cu_seqlens_kv = 16
-  p.batch, p.heads_q, p.heads_kv, p.head_dim = int(batch), int(heads_q), int(heads_kv), d8
-  p.max_seqlen_q, p.max_seqlen_kv = int(max_seqlen_q), int(max_seqlen_k)
-  for name, h in (("q_stride", heads_q), ("k_stride", heads_kv), ("v_stride", heads_kv), ("o_stride", heads_q)):
-    getattr(p, name)[:] = [h * d8, d8]
-  p.dtype = _DTYPE[dtype]
-  p.causal = 1 if causal else 0
-  p.softmax_scale = float(head_dim) ** -0.5
-  p.rescale_threshold = -1.0
-  p.flags = int(flags)
-  p.num_splits = int(num_splits)
-  p.total_q = int(total_q)
   if total_q > 0:
     p.workspace, p.workspace_bytes = 16, 0xFFFFFFFFFFFFFFFF
-  plan = (ctypes.c_int * 5)()
-  name = ctypes.create_string_buffer(200)
+  kv = None
+  args = (ctypes.byref(p),)
   if page_size:
     p.seqused_kv = 16
-    kv = FfpaPagedKv()
-    kv.struct_size = ctypes.sizeof(FfpaPagedKv)
-    kv.block_table = 16
-    kv.pages_per_row = max(1, -(-int(max_seqlen_k) // int(page_size)))
-    kv.bt_stride, kv.page_size, kv.num_pages = kv.pages_per_row, int(page_size), int(batch) * kv.pages_per_row
-    kv.k_page_stride = kv.v_page_stride = int(page_size) * heads_kv * d8
-    rc = lib.ffpa_attn_varlen_paged_fwd_plan(ctypes.byref(p), ctypes.byref(kv), plan)
-    if rc != 0:
-      raise _STATUS_EXC.get(rc, RuntimeError)(lib.ffpa_attn_last_error().decode())
-    lib.ffpa_attn_varlen_paged_fwd_kernel(ctypes.byref(p), ctypes.byref(kv), name, len(name))
-  else:
-    rc = lib.ffpa_attn_varlen_fwd_plan(ctypes.byref(p), plan)
-    if rc != 0:
-      raise _STATUS_EXC.get(rc, RuntimeError)(lib.ffpa_attn_last_error().decode())
-    lib.ffpa_attn_varlen_fwd_kernel(ctypes.byref(p), name, len(name))
-  out = {"row_tiles": plan[0], "block_rows": plan[1], "block_keys": plan[2], "workgroups": plan[3], "kernel": name.value.decode()}
-  if total_q > 0:
-    out["splits"] = plan[4]
+    pages_per_row = max(1, -(-int(max_seqlen_k) // int(page_size)))
+    kv = _paged_kv(16, pages_per_row, pages_per_row, int(page_size), int(batch) * pages_per_row, int(page_size) * heads_kv * d8, int(page_size) * heads_kv * d8)
+    args = (ctypes.byref(p), ctypes.byref(kv))
+  out = _read_plan(lib, _varlen_fn(lib, kv, "_plan"), _varlen_fn(lib, kv, "_kernel"), _VARLEN_PLAN_KEYS, args, strict=True)
+  if total_q <= 0:
+    del out["splits"]
   return out
 
 
@@ -1249,8 +1163,8 @@ torch.library.define(
 
 @torch.library.impl(f"{_OP_NAMESPACE}::_paged_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
 def _paged_fwd_hip_torch_op(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, softmax_scale, causal, rescale_threshold=-1.0, num_splits=0):
-  return _paged_forward(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, bool(causal), softmax_scale,
-                        rescale_threshold=rescale_threshold, return_lse=True, num_splits=num_splits)
+  return varlen_forward(q, k, v, cu_seqlens_q, None, max_seqlen_q, max_seqlen_k, bool(causal), softmax_scale,
+                        rescale_threshold=rescale_threshold, return_lse=True, seqused_k=seqused_k, num_splits=num_splits, block_table=block_table)
 
 
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_paged_fwd_hip")
@@ -1260,11 +1174,6 @@ def _paged_fwd_hip_fake(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqle
 
 
 # The KV-cache append + rotary (ffpa_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)): the prepare launch in front of the attention launch
-def _rows16(t: torch.Tensor) -> bool:
-  """head-dim stride 1, every other stride a multiple of 8 elements, a 16-byte aligned base: what the append kernel's 16-byte loads and stores need"""
-  return t.stride(-1) == 1 and all(st % 8 == 0 for st in t.stride()[:-1]) and t.data_ptr() % 16 == 0
-
-
 def kvcache_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: "torch.Tensor | None", v: "torch.Tensor | None", cache_seqlens: torch.Tensor,
                    block_table: "torch.Tensor | None" = None, rotary_cos: "torch.Tensor | None" = None, rotary_sin: "torch.Tensor | None" = None,
                    rotary_interleaved: bool = True, causal: bool = False):
@@ -1284,18 +1193,15 @@ def kvcache_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor
   if B == 0:
     return q_rot, seqused
   for nm, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-    if not _rows16(t):
+    if not _layout_ok(t):
       raise ValueError(f"{name}: {nm} is written in place and needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base")
   if k is None:
     k = v = q.new_empty((B, 0, Hkv, D))
-  k = k if _rows16(k) else k.contiguous()
-  v = v if _rows16(v) else v.contiguous()
-  if rot and not _rows16(q):
-    q = q.contiguous()
+  k, v = _rows(k), _rows(v)
+  if rot:
+    q = _rows(q)
   cache_seqlens = cache_seqlens.contiguous()
-  p = FfpaKvAppendParams()
-  p.struct_size = ctypes.sizeof(FfpaKvAppendParams)
-  p.abi_version = ABI_VERSION
+  p = _stamped(FfpaKvAppendParams)
   p.k_cache, p.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
   p.seqused, p.cache_seqlens = seqused.data_ptr(), cache_seqlens.data_ptr()
   p.batch, p.heads_q, p.heads_kv, p.head_dim = B, Hq, Hkv, D
@@ -1318,16 +1224,12 @@ def kvcache_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor
   p.dtype = _DTYPE[q.dtype]
   kv = None
   if block_table is not None:
-    if block_table.stride(1) != 1 or block_table.data_ptr() % 4 != 0:
-      block_table = block_table.contiguous()
-    kv = _paged_kv(block_table, k_cache, v_cache)
+    kv, block_table = _paged_kv_of(block_table, k_cache, v_cache)
   else:
     p.capacity = k_cache.size(1)
-  with torch.cuda.device(q.device):
-    stream = torch.cuda.current_stream(q.device).cuda_stream
-    rc = lib.ffpa_attn_kvcache_append(ctypes.byref(p), ctypes.byref(kv) if kv is not None else None, ctypes.c_void_p(stream))
+  rc = _call_on_stream(lib.ffpa_attn_kvcache_append, q.device, ctypes.byref(p), ctypes.byref(kv) if kv is not None else None)
   if rc != 0:
-    raise _STATUS_EXC.get(rc, RuntimeError)(f"ffpa_attn_kvcache_append: {lib.ffpa_attn_last_error().decode()} (status {rc})")
+    _raise_status(lib, rc, "ffpa_attn_kvcache_append")
   return q_rot, seqused
 
 
@@ -1374,12 +1276,6 @@ def check_merge_states(o_a: torch.Tensor, lse_a: torch.Tensor, o_b: torch.Tensor
       raise ValueError(f"{name}: {nm} must be on o_a's device, got {t.device} and {dev}")
 
 
-def _merge_rows(t: torch.Tensor) -> torch.Tensor:
-  """[T, H, D] with head-dim stride 1, token / head strides multiples of 8 elements and a 16-byte aligned base — else a copy."""
-  ok = t.stride(-1) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.stride(0) >= 0 and t.stride(1) >= 0 and t.data_ptr() % 16 == 0
-  return t if ok else t.contiguous()
-
-
 def merge_states(o_a: torch.Tensor, lse_a: torch.Tensor, o_b: torch.Tensor, lse_b: torch.Tensor, return_lse: bool = True):
   """One launch of ``ffpa_attn_merge_states``: ``(o [T, H, D], lse [H, T] fp32 | None)`` — the attention over the union of the two key sets whose attentions are
   ``(o_a, lse_a)`` and ``(o_b, lse_b)``.  Asynchronous, nothing read back to the host."""
@@ -1393,12 +1289,10 @@ def merge_states(o_a: torch.Tensor, lse_a: torch.Tensor, o_b: torch.Tensor, lse_
   lse = torch.empty((H, T), dtype=torch.float32, device=o_a.device) if return_lse else None
   if T == 0 or H == 0:
     return o, lse
-  o_a, o_b = _merge_rows(o_a), _merge_rows(o_b)
+  o_a, o_b = _rows(o_a), _rows(o_b)
   lse_a = lse_a if lse_a.stride(1) == 1 and lse_a.stride(0) >= 0 else lse_a.contiguous()
   lse_b = lse_b if lse_b.stride(1) == 1 and lse_b.stride(0) >= 0 else lse_b.contiguous()
-  p = FfpaMergeStatesParams()
-  p.struct_size = ctypes.sizeof(FfpaMergeStatesParams)
-  p.abi_version = ABI_VERSION
+  p = _stamped(FfpaMergeStatesParams)
   p.o_a, p.o_b, p.o = o_a.data_ptr(), o_b.data_ptr(), o.data_ptr()
   p.lse_a, p.lse_b = lse_a.data_ptr(), lse_b.data_ptr()
   p.lse = lse.data_ptr() if lse is not None else None
@@ -1409,11 +1303,9 @@ def merge_states(o_a: torch.Tensor, lse_a: torch.Tensor, o_b: torch.Tensor, lse_
   p.o_stride[:] = list(o.stride()[:2])
   p.lse_a_stride_head, p.lse_b_stride_head = lse_a.stride(0), lse_b.stride(0)
   p.lse_stride_head = lse.stride(0) if lse is not None else 0
-  with torch.cuda.device(o.device):
-    stream = torch.cuda.current_stream(o.device).cuda_stream
-    rc = lib.ffpa_attn_merge_states(ctypes.byref(p), ctypes.c_void_p(stream))
+  rc = _call_on_stream(lib.ffpa_attn_merge_states, o.device, ctypes.byref(p))
   if rc != 0:
-    raise _STATUS_EXC.get(rc, RuntimeError)(f"ffpa_attn_merge_states: {lib.ffpa_attn_last_error().decode()} (status {rc})")
+    _raise_status(lib, rc, "ffpa_attn_merge_states")
   return o, lse
 
 

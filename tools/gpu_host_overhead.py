@@ -5,7 +5,8 @@
 Each call is timed with perf_counter WITHOUT synchronising (the call returns once the launch is enqueued; the queue is drained between batches so
 that it never fills and blocks), median over 2000 calls, for: the inference path (round 5: no autograd node, no dispatcher round trip, no LSE tensor,
 workspace kept per stream, plan scratch asked once per shape class), the same call behind the autograd node (an input requires a gradient: the
-registered op + autograd.Function, LSE allocated and saved), and the bare C-ABI launch wrapper `hip.forward`.
+registered op + autograd.Function, LSE allocated and saved), the bare C-ABI launch wrapper `hip.forward`, and the packed call's wrapper `hip.varlen_forward`
+on the same step (one token per sequence), without and with a block table.
 """
 import os
 import statistics
@@ -48,6 +49,22 @@ def main():
       ("ffpa_attn_func, inference path", lambda: ffpa_attn_func(q, k, v, enable_gqa=gqa)),
       ("ffpa_attn_func, autograd path (q.requires_grad)", lambda: ffpa_attn_func(qg, k, v, enable_gqa=gqa)),
       ("hip.forward (launch wrapper alone, no LSE)", lambda: hip.forward(q, k, v, None, False, D ** -0.5, return_lse=False)),
+    ]
+    # the packed call on the same decode step — one token per sequence, the cache as packed rows [B * Nkv, Hkv, D] with its lengths on the device — and its
+    # paged twin on the same memory viewed as a pool of 256-key pages
+    qr = q.view(B, Hq, D)
+    kr, vr = (t.transpose(1, 2).reshape(B * Nkv, Hkv, D) for t in (k, v))
+    cu_q = torch.arange(B + 1, dtype=torch.int32, device="cuda")
+    cu_k = cu_q * Nkv
+    used = torch.full((B,), Nkv, dtype=torch.int32, device="cuda")
+    page = 256
+    table = torch.arange(B * Nkv // page, dtype=torch.int32, device="cuda").view(B, Nkv // page)
+    kp, vp = kr.view(-1, page, Hkv, D), vr.view(-1, page, Hkv, D)
+    rows += [
+      ("hip.varlen_forward, one token per sequence (no LSE)",
+       lambda: hip.varlen_forward(qr, kr, vr, cu_q, cu_k, 1, Nkv, False, D ** -0.5, return_lse=False, seqused_k=used)),
+      ("hip.varlen_forward, the same with a block table (paged KV)",
+       lambda: hip.varlen_forward(qr, kp, vp, cu_q, None, 1, Nkv, False, D ** -0.5, return_lse=False, seqused_k=used, block_table=table)),
     ]
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for _ in range(50):
