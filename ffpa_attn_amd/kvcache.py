@@ -205,6 +205,14 @@ def ffpa_attn_with_kvcache(
   ``Hq % Hkv == 0``.  ``num_splits``: 0 = the library decides, 1 = never split the keys, n = at most n ranges.  Returns ``out [B, Sq, Hq, D]`` — and the
   fp32 ``softmax_lse [B, Hq, Sq]`` with ``return_softmax_lse``.  Rows that see no key come out as 0 (LSE -inf).
 
+  Layouts.  Strided views are read in place wherever the head dim has stride 1, every other stride is a multiple of 8 elements and the base is 16-byte
+  aligned: K and V as the halves of one pool (``kv[:, 0]`` / ``kv[:, 1]`` of ``[num_pages, 2, page_size, Hkv, D]``, or ``kv[0]`` / ``kv[1]``), head-major pools
+  viewed page-row-major, rows wider than D, q / k / v as slices of a fused QKV buffer; a ``block_table`` needs unit column stride (any row stride) and is copied
+  otherwise, ``cache_seqlens`` is copied when strided.  A pool or cache outside that contract is copied for the attention launch (the right answer, at the
+  price of the copy); the append writes in place and raises ``ValueError`` for it instead.  A CONTIGUOUS cache runs as ``[B * capacity, Hkv, D]``: one that is
+  not viewable that way (``kv[:, 0]`` of ``[B, 2, capacity, Hkv, D]``, head-major slabs) is appended to in place and then copied for the attention launch
+  — a documented copy, not an error; batch-padded (``cache[:B]``) and ``[2, B, ...]`` caches are viewable and are not copied.
+
   ``k`` / ``v [B, Snew, Hkv, D]`` (the cache's dtype, last dim contiguous; ``cache_seqlens`` required): key i of sequence b is written in place at position
   ``pos = cache_seqlens[b] + i`` (row ``pos`` of ``k_cache[b]``, or row ``pos % page_size`` of page ``block_table[b, pos // page_size]``; positions at or past the
   capacity are dropped, negative lengths act as 0), then attention runs over ``min(cache_seqlens[b] + Snew, capacity)`` keys.  ``cache_seqlens`` is not modified.
