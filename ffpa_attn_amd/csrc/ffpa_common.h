@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include <utility>
 
 #define FFPA_M0_CLOBBER , "m0"  // the LDS-DMA asm writes M0 behind the compiler's back and says so
@@ -35,6 +36,59 @@ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
+}
+
+// An additive bias element in the unit a kernel adds it in (`unit`: log2 e for the scaled score, 1 / softmax_scale for the S^T accumulators of the 16x16x32
+// build).  A finite value must stay finite — `finfo(dtype).min` is what additive padding masks are filled with, precisely so that a row whose every key
+// carries it is NOT the NaN row of -inf — but finfo(bf16).min and finfo(float32).min times either unit overflow fp32, and the 16x16x32 build's exponent
+// fma(x, sc, -fl(sc max x)) leaves a residual of up to half an ulp of the row maximum behind: harmless below 2^22 (a quarter), fatal for 16-bit P above
+// 2^40.  So every finite value below -2^21 enters as ONE saturated score, -2^100: a power of two (sc x is exact: the residual is 0), far below any score
+// a visible key can have (p = 0 next to one, as the value itself would give), and it absorbs q.k as fp32(s + finfo.min) does: a row whose keys all carry
+// such values comes out as the plain mean of V, SDPA's answer.  -inf stays -inf (the row without a visible key stays NaN).  fp16 has no finite value below
+// the floor: its conversions stay as they were.
+// Written without a compare: max(A, B) with
+//   A = min(saturated, b 2^-30): the saturated score for every finite b (|b| 2^-30 < 2^98), -inf for -inf;
+//   B = fma(min(b - floor, 0), 2^110, b unit): b unit, exactly, at and above the floor; at most -2^108 (or -inf) below it, where b - floor <= -1 / 4.
+// A compare-and-select costs the bias + dropout build at D = 512 — 256 VGPRs, its scalar registers already spilling to lanes — a mask register pair per
+// element: a second scratch reload inside its MFMA loop, or a ninth lane spill in the build without dropout (tests/test_isa_rules.py).  (A NaN bias element
+// comes out as the saturated score.)
+constexpr float kBiasFloor = -2097152.f;       // -2^21
+constexpr float kBiasSaturated = -0x1p100f;
+template <typename BT>
+__device__ __forceinline__ float bias_term(BT raw, float unit) {
+  const float b = (float)raw;
+  if constexpr (std::is_same<BT, _Float16>::value) return b * unit;
+  else return fmaxf(fminf(kBiasSaturated, b * 0x1p-30f), __builtin_fmaf(fminf(b - kBiasFloor, 0.f), 0x1p110f, b * unit));
+}
+
+// The LSE of a row whose running maximum is the saturated score.  ln(row sum) cannot sit next to -2^100 in fp32, and a launch that splits the KV axis merges
+// its partials by their LSEs: such a row's LSE is therefore written as saturated / l — finite, below -2^60, and the merge weighs the splits of such a row
+// by w_s = max LSE / LSE_s = l_s / max l (merge_weight), its merged LSE is max LSE / sum w = saturated / sum l (merged_lse).  Next to a split that holds an
+// ordinary key these partials weigh exp(-2^70 ...) = 0, as they must.  kBias = false (a build without an additive bias): the expression as it always was.
+constexpr float kLseSaturated = -0x1p60f;
+template <bool kBias>
+__device__ __forceinline__ float row_lse(float m_log2, float l) {
+  if constexpr (kBias) {
+    if (m_log2 < kLseSaturated && m_log2 > -INFINITY) return kBiasSaturated / l;
+  }
+  return __builtin_fmaf(m_log2, 0.6931471805599453f, __logf(l));
+}
+__device__ __forceinline__ float merge_weight(float lse_s, float mx) {
+  if (mx == -INFINITY) return 0.f;
+  return mx < kLseSaturated ? mx / lse_s : __expf(lse_s - mx);
+}
+__device__ __forceinline__ float merged_lse(float mx, float wsum) {
+  if (mx == -INFINITY) return -INFINITY;
+  return mx < kLseSaturated ? mx / wsum : mx + __logf(wsum);
+}
+
+// Four at once (the conversions inside the KV loop of the 16x16x32 build).
+template <typename V4>
+__device__ __forceinline__ f32x4 bias_term4(V4 raw, float unit) {
+  f32x4 w;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) w[r] = bias_term(raw[r], unit);
+  return w;
 }
 
 #define FFPA_LDS __attribute__((address_space(3)))

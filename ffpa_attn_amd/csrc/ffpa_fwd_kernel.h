@@ -92,7 +92,7 @@ __device__ __forceinline__ void add_bias_block(float (&x)[16], const void* bias,
   for (int r = 0; r < 16; ++r) {
     int key = key_base + r;
     key = key < nkv ? key : nkv - 1;
-    x[r] += (float)bp[key * stride_key] * 1.4426950408889634f;
+    x[r] += bias_term(bp[key * stride_key], 1.4426950408889634f);
   }
 }
 
@@ -108,7 +108,7 @@ __device__ __forceinline__ void add_bias_block_vec(float (&x)[16], const void* b
 #pragma unroll
   for (int i = 0; i < 16 / W; ++i)
 #pragma unroll
-    for (int t = 0; t < W; ++t) x[W * i + t] += (float)raw[i][t] * 1.4426950408889634f;
+    for (int t = 0; t < W; ++t) x[W * i + t] += bias_term(raw[i][t], 1.4426950408889634f);
 }
 
 // Boolean mask (FFPA_BIAS_BOOL8: one byte per score, non-zero = visible): what the reference's host turns into an additive
@@ -181,7 +181,7 @@ __device__ __forceinline__ void split_arrive_and_merge(const FwdArgs& a, int D, 
     float wsum = 0.f;
     if (act)
       for (int s = lane; s < a.nsplit; s += 64) {
-        const float w = (mx == -INFINITY) ? 0.f : __expf(a.ws_lse[s * rows + row] - mx);
+        const float w = merge_weight(a.ws_lse[s * rows + row], mx);
         wsh[s] = w;
         wsum += w;
       }
@@ -217,7 +217,7 @@ __device__ __forceinline__ void split_arrive_and_merge(const FwdArgs& a, int D, 
         for (int e = 0; e < 4; ++e) w4[e] = (T)(acc[e] * inv);
         *(typename Elem<T>::v4*)(op + d) = w4;
       }
-      if (a.lse != nullptr && lane == 0) a.lse[row] = (mx == -INFINITY) ? -INFINITY : mx + __logf(wsum);
+      if (a.lse != nullptr && lane == 0) a.lse[row] = merged_lse(mx, wsum);
     }
     __syncthreads();  // the weights are free for the next round
   }
@@ -725,11 +725,11 @@ __global__ __launch_bounds__(256) void ffpa_fwd_split_d_kernel(const FwdArgs a) 
           if (a.bias_dtype == 2) {
             const b8 t = __builtin_bit_cast(b8, braw[2 * kb + w]);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += (float)t[e] * 1.4426950408889634f;
+            for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += bias_term(t[e], 1.4426950408889634f);
           } else {
             const h8 t = __builtin_bit_cast(h8, braw[2 * kb + w]);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += (float)t[e] * 1.4426950408889634f;
+            for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += bias_term(t[e], 1.4426950408889634f);
           }
         }
     } else if (!MASK) {
@@ -757,11 +757,11 @@ __global__ __launch_bounds__(256) void ffpa_fwd_split_d_kernel(const FwdArgs a) 
           if (a.bias_dtype == 2) {
             const b8 t = __builtin_bit_cast(b8, raw);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += (float)t[e] * 1.4426950408889634f;
+            for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += bias_term(t[e], 1.4426950408889634f);
           } else {
             const h8 t = __builtin_bit_cast(h8, raw);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += (float)t[e] * 1.4426950408889634f;
+            for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += bias_term(t[e], 1.4426950408889634f);
           }
         }
     } else if (a.bias_lds > 0 && !mask_free) {
@@ -777,7 +777,7 @@ __global__ __launch_bounds__(256) void ffpa_fwd_split_d_kernel(const FwdArgs a) 
           for (int i = 0; i < 4; ++i) {
             const f32x4 t = *(FFPA_LDS const f32x4*)(bp + 16 * i);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) x[kb][4 * i + e] += t[e] * 1.4426950408889634f;
+            for (int e = 0; e < 4; ++e) x[kb][4 * i + e] += bias_term(t[e], 1.4426950408889634f);
           }
         } else {
           FFPA_LDS const char* bp = Bl + key * 2;
@@ -787,11 +787,11 @@ __global__ __launch_bounds__(256) void ffpa_fwd_split_d_kernel(const FwdArgs a) 
             if (a.bias_dtype == 2) {
               const b8 t = __builtin_bit_cast(b8, raw);
 #pragma unroll
-              for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += (float)t[e] * 1.4426950408889634f;
+              for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += bias_term(t[e], 1.4426950408889634f);
             } else {
               const h8 t = __builtin_bit_cast(h8, raw);
 #pragma unroll
-              for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += (float)t[e] * 1.4426950408889634f;
+              for (int e = 0; e < 8; ++e) x[kb][8 * w + e] += bias_term(t[e], 1.4426950408889634f);
             }
           }
         }
@@ -980,7 +980,7 @@ __global__ __launch_bounds__(256) void ffpa_fwd_split_d_kernel(const FwdArgs a) 
           else *(f32x4*)(wp + db * 32 + 8 * i) = w;
         }
       if (h == 0 && dh == 0) {
-        const float lse_part = dead ? -INFINITY : __builtin_fmaf(m_run, 0.6931471805599453f, __logf(l_tot));  // (explicit: see ffpa_fwd_m16_kernel.h)
+        const float lse_part = dead ? -INFINITY : row_lse<MASK>(m_run, l_tot);  // (explicit: see ffpa_fwd_m16_kernel.h)
         if (a.tickets != nullptr) __hip_atomic_store(&a.ws_lse[prow], lse_part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else a.ws_lse[prow] = lse_part;
       }
@@ -1012,7 +1012,7 @@ __global__ __launch_bounds__(256) void ffpa_fwd_split_d_kernel(const FwdArgs a) 
         }
       if (a.lse != nullptr && h == 0 && dh == 0) {
         // natural-log LSE = ln(l) + m*ln2 (prefill.cuh:1063-1073)
-        a.lse[((int64_t)b * a.Hq + hq) * a.Nq + qrow] = __builtin_fmaf(m_run, 0.6931471805599453f, __logf(l_tot));
+        a.lse[((int64_t)b * a.Hq + hq) * a.Nq + qrow] = row_lse<MASK>(m_run, l_tot);
       }
     }
   }
@@ -1038,7 +1038,7 @@ __global__ __launch_bounds__(64) void ffpa_fwd_merge_kernel(const FwdArgs a, int
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
   float wsum = 0.f;
   for (int s = lane; s < a.nsplit; s += 64) {
-    const float w = (mx == -INFINITY) ? 0.f : __expf(a.ws_lse[s * rows + row] - mx);
+    const float w = merge_weight(a.ws_lse[s * rows + row], mx);
     wsh[s] = w;
     wsum += w;
   }
@@ -1079,7 +1079,7 @@ __global__ __launch_bounds__(64) void ffpa_fwd_merge_kernel(const FwdArgs a, int
     for (int e = 0; e < 4; ++e) w4[e] = (T)(acc[e] * inv);
     *(typename Elem<T>::v4*)(op + d) = w4;
   }
-  if (a.lse != nullptr && lane == 0 && blockIdx.y == 0) a.lse[row] = (mx == -INFINITY) ? -INFINITY : mx + __logf(wsum);
+  if (a.lse != nullptr && lane == 0 && blockIdx.y == 0) a.lse[row] = merged_lse(mx, wsum);
 }
 
 }  // namespace ffpa

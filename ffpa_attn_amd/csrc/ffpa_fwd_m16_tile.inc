@@ -331,8 +331,7 @@
         float w = 0.f;
         if (i < a.Nkv) {
           const int64_t e = src0 + i * a.sbias[3];
-          w = a.bias_dtype == 3 ? ((const float*)a.bias)[e] : a.bias_dtype == 2 ? (float)((const __bf16*)a.bias)[e] : (float)((const _Float16*)a.bias)[e];
-          w *= a.inv_scale;
+          w = bias_term(a.bias_dtype == 3 ? ((const float*)a.bias)[e] : a.bias_dtype == 2 ? (float)((const __bf16*)a.bias)[e] : (float)((const _Float16*)a.bias)[e], a.inv_scale);
         }
         *(FFPA_LDS float*)(Bl + 4 * i) = w;
       }
@@ -445,8 +444,7 @@
             float w = 0.f;
             if (key < a.Nkv) {
               const int64_t e = src0 + key * a.sbias[3];
-              w = a.bias_dtype == 3 ? ((const float*)a.bias)[e] : a.bias_dtype == 2 ? (float)((const __bf16*)a.bias)[e] : (float)((const _Float16*)a.bias)[e];
-              w *= a.inv_scale;
+              w = bias_term(a.bias_dtype == 3 ? ((const float*)a.bias)[e] : a.bias_dtype == 2 ? (float)((const __bf16*)a.bias)[e] : (float)((const _Float16*)a.bias)[e], a.inv_scale);
             }
             *(FFPA_LDS float*)(Bl + (((uint32_t)key & ring_mask) << 2)) = w;
           }
@@ -781,12 +779,10 @@
               f32x4 w;
               if (a.bias_dtype == 2) {
                 const b4 t = *(FFPA_LDS const b4*)(bp + 32 * kb);
-  #pragma unroll
-                for (int r = 0; r < 4; ++r) w[r] = (float)t[r] * a.inv_scale;
+                w = bias_term4(t, a.inv_scale);
               } else {
                 const h4 t = *(FFPA_LDS const h4*)(bp + 32 * kb);
-  #pragma unroll
-                for (int r = 0; r < 4; ++r) w[r] = (float)t[r] * a.inv_scale;
+                w = bias_term4(t, a.inv_scale);
               }
               sacc[kb][0] = w;
               sacc[kb][1] = w;
@@ -808,15 +804,14 @@
   #pragma unroll
               for (int kb = 0; kb < NKB; ++kb)
   #pragma unroll
-                for (int rh = 0; rh < 2; ++rh) sacc[kb][rh] = *(FFPA_LDS const f32x4*)(baddr[kb] + rh * half_rows) * a.inv_scale;
+                for (int rh = 0; rh < 2; ++rh) sacc[kb][rh] = bias_term4(*(FFPA_LDS const f32x4*)(baddr[kb] + rh * half_rows), a.inv_scale);
             } else if (a.bias_dtype == 2) {
   #pragma unroll
               for (int kb = 0; kb < NKB; ++kb)
   #pragma unroll
                 for (int rh = 0; rh < 2; ++rh) {
                   const b4 w = *(FFPA_LDS const b4*)(baddr[kb] + rh * half_rows);
-  #pragma unroll
-                  for (int r = 0; r < 4; ++r) sacc[kb][rh][r] = (float)w[r] * a.inv_scale;
+                  sacc[kb][rh] = bias_term4(w, a.inv_scale);
                 }
             } else {
   #pragma unroll
@@ -824,8 +819,7 @@
   #pragma unroll
                 for (int rh = 0; rh < 2; ++rh) {
                   const h4 w = *(FFPA_LDS const h4*)(baddr[kb] + rh * half_rows);
-  #pragma unroll
-                  for (int r = 0; r < 4; ++r) sacc[kb][rh][r] = (float)w[r] * a.inv_scale;
+                  sacc[kb][rh] = bias_term4(w, a.inv_scale);
                 }
             }
           } else if constexpr (MK == 1) {  // element-wise from global memory: any strides, any dtype (boolean: 0 / -inf)
@@ -841,7 +835,7 @@
                   const int64_t e = brow + key * a.sbias[3];
                   float w;
                   if (a.bias_dtype == 4) w = ((const uint8_t*)a.bias)[e] != 0 ? 0.f : -INFINITY;
-                  else w = (a.bias_dtype == 3 ? ((const float*)a.bias)[e] : a.bias_dtype == 2 ? (float)((const __bf16*)a.bias)[e] : (float)((const _Float16*)a.bias)[e]) * a.inv_scale;
+                  else w = bias_term(a.bias_dtype == 3 ? ((const float*)a.bias)[e] : a.bias_dtype == 2 ? (float)((const __bf16*)a.bias)[e] : (float)((const _Float16*)a.bias)[e], a.inv_scale);
                   sacc[kb][rh][r] = w;
                 }
             }
@@ -1256,7 +1250,7 @@
       }
       // (one explicit FMA: left to -ffp-contract, builds of this kernel differed in whether they fused it — 1 ulp of the partial's LSE, which the merge
       // turns into an output ulp here and there; every build must produce the same bits for the same scores)
-      if (c == 0 && dh == 0) a.ws_lse[prow] = dead ? -INFINITY : __builtin_fmaf(m_run[rh], 0.6931471805599453f, __logf(l_tot[rh]));
+      if (c == 0 && dh == 0) a.ws_lse[prow] = dead ? -INFINITY : row_lse<kBias>(m_run[rh], l_tot[rh]);
     }
     FFPA_M16_TILE_DONE;
   }
@@ -1299,7 +1293,7 @@
     if (a.lse != nullptr && c == 0 && dh == 0) {
 #pragma unroll
       for (int rh = 0; rh < 2; ++rh)
-        if (qrow[rh] < a.Nq) a.lse[FFPA_M16_LSE_INDEX(qrow[rh])] = __builtin_fmaf(m_run[rh], 0.6931471805599453f, __logf(l_tot[rh]));
+        if (qrow[rh] < a.Nq) a.lse[FFPA_M16_LSE_INDEX(qrow[rh])] = row_lse<kBias>(m_run[rh], l_tot[rh]);
     }
 #endif
   }

@@ -123,7 +123,8 @@ def ffpa_attn_func(
   ``query`` is ``[B, Hq, Nq, D]``; ``key`` / ``value`` are ``[B, Hkv, Nkv, D]`` (``Hq % Hkv == 0``,
   pass ``enable_gqa=True`` when they differ); fp16 or bf16.  ``attn_mask`` follows SDPA
   (bool = keep, float = additive, broadcastable to ``[B, Hq, Nq, Nkv]``) and excludes
-  ``is_causal``.  ``is_causal=True`` masks ``key > row + (Nkv - Nq)`` (queries aligned to the KV
+  ``is_causal``.  Finite mask values, ``finfo(dtype).min`` included, behave as in SDPA:
+  only ``-inf`` or ``False`` hides a key.  ``is_causal=True`` masks ``key > row + (Nkv - Nq)`` (queries aligned to the KV
   tail — FlashAttention's convention, NOT SDPA's top-left one) and requires ``Nkv >= Nq``.
   ``scale`` defaults to ``1/sqrt(D)``.
 

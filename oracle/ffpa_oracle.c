@@ -158,6 +158,8 @@ static inline int dropout_keeps(uint64_t seed, uint64_t element, float p) {
 
 #define FFPA_LOG2E 1.4426950408889634f
 #define FFPA_LN2 0.6931471805599453f
+#define FFPA_BIAS_FLOOR (-2097152.f)     /* -2^21 */
+#define FFPA_BIAS_SATURATED (-0x1p100f)
 
 /*
  * Dense contiguous tensors: q [B,Hq,Nq,D], k/v [B,Hkv,Nkv,D], o [B,Hq,Nq,D] (16-bit, dtype 0 = bf16,
@@ -239,7 +241,9 @@ int ffpa_oracle_fwd_ex(const uint16_t* q, const uint16_t* k, const uint16_t* v, 
               if (bias) {
                 const float bv = bias[(size_t)b * bias_stride[0] + (size_t)hq * bias_stride[1] +
                                       (size_t)r * bias_stride[2] + (size_t)key * bias_stride[3]];
-                xv += bv * FFPA_LOG2E;
+                /* a finite value below -2^21 (finfo(bf16).min, finfo(float32).min: their product with log2 e overflows) enters as one saturated finite score,
+                 * as in the kernels (bias_term, csrc/ffpa_common.h): -inf stays -inf */
+                xv += (bv < FFPA_BIAS_FLOOR && bv > -INFINITY) ? FFPA_BIAS_SATURATED : bv * FFPA_LOG2E;
               }
               if ((long)key > lim) xv = -INFINITY;
               x[j] = xv;
