@@ -10,7 +10,7 @@ from .flops import attention_fwd_flops, attention_valid_pairs
 from .functional import FFPAAttnMeta
 from .decode import DecodeStep
 from .interface import ffpa_attn_func, ffpa_attn_varlen_func
-from .kvcache import ffpa_attn_with_kvcache, ffpa_attn_with_kvcache_cascade, ffpa_merge_attn_states
+from .kvcache import ffpa_attn_with_kvcache, ffpa_attn_with_kvcache_cascade, ffpa_attn_with_kvcache_tree, ffpa_merge_attn_states, pack_tree_mask
 
 
 
@@ -94,6 +94,8 @@ __all__ = [
   "ffpa_attn_varlen_func",
   "ffpa_attn_with_kvcache",
   "ffpa_attn_with_kvcache_cascade",
+  "ffpa_attn_with_kvcache_tree",
+  "pack_tree_mask",
   "ffpa_merge_attn_states",
   "install_alias",
   "DecodeStep",

@@ -1109,13 +1109,30 @@ int check_paged(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv) {
   return check_pool(kv);
 }
 
-// The packed call and its paged twin (kv != NULL: k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read)
-int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream) {
+// The tree call's own argument (ffpa_tree_mask), checked behind the packed call's plan (and the paged pool) and before anything touches the device.
+int check_tree(const ffpa_varlen_fwd_params* p, const ffpa_tree_mask* tree) {
+  if (tree == nullptr) return fail(FFPA_ERR_NULL_POINTER, "tree mask is NULL");
+  if (tree->struct_size != sizeof(ffpa_tree_mask))
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_tree_mask ABI mismatch: size %u (want %zu)", tree->struct_size, sizeof(ffpa_tree_mask));
+  if (tree->bits == nullptr) return fail(FFPA_ERR_NULL_POINTER, "tree mask bits must be non-NULL");
+  if (reinterpret_cast<uintptr_t>(tree->bits) & 7u) return fail(FFPA_ERR_MISALIGNED, "tree mask bits must be 8-byte aligned");
+  if (tree->tokens < 1 || tree->tokens > 64) return fail(FFPA_ERR_BAD_SHAPE, "tree mask tokens=%d is outside [1, 64] (one 64-bit word per token)", tree->tokens);
+  if (p->max_seqlen_q > tree->tokens)
+    return fail(FFPA_ERR_BAD_SHAPE, "max_seqlen_q=%d exceeds the tree mask's tokens=%d", p->max_seqlen_q, tree->tokens);
+  if (tree->batch_stride != 0 && tree->batch_stride < tree->tokens)
+    return fail(FFPA_ERR_BAD_STRIDE, "tree mask batch_stride=%lld is neither 0 (one tree for the batch) nor >= tokens=%d", (long long)tree->batch_stride, tree->tokens);
+  return FFPA_OK;
+}
+
+// The packed call and its paged twin (kv != NULL: k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read); `tree`: under a tree mask
+// (ffpa_attn_varlen_tree_fwd — the causal launch's plan and tile walk; the *_tree_kernel builds, whose element test reads the mask words)
+int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream, const ffpa_tree_mask* tree = nullptr, bool with_tree = false) {
   const bool paged = kv != nullptr;
   VarlenPlan pl;
   int rc = varlen_plan(p, &pl, paged);
   if (rc != FFPA_OK) return rc;
   if (paged && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
+  if (with_tree && (rc = check_tree(p, tree)) != FFPA_OK) return rc;
   if (!p->q || !p->k || !p->v || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
   if (!p->cu_seqlens_q || (!paged && !p->cu_seqlens_kv)) return fail(FFPA_ERR_NULL_POINTER, "cu_seqlens_q / cu_seqlens_kv must be non-NULL");
   if ((reinterpret_cast<uintptr_t>(p->cu_seqlens_q) & 3u) || (!paged && (reinterpret_cast<uintptr_t>(p->cu_seqlens_kv) & 3u)) || (reinterpret_cast<uintptr_t>(p->seqused_kv) & 3u))
@@ -1168,6 +1185,7 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
   a.l2_prefetch = pick_l2_prefetch(p->flags, pl.ve->d > 512);
 
   ffpa::VarlenArgs va;
+  memset(&va, 0, sizeof(va));
   va.cu_q = p->cu_seqlens_q;
   va.cu_k = paged ? nullptr : p->cu_seqlens_kv;
   va.lse_stride_h = p->lse_stride_head;
@@ -1186,6 +1204,14 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
     a.so[1] = p->o_stride[1] * pl.pack, a.so[2] = p->o_stride[1];
     if (p->max_seqlen_q == 1) a.causal = 0;  // (a single token sees every key of its sequence; more tokens: the kernel sets causal_row_mod per sequence)
     va.head_chunk = 1;  // (the rows of a tile ARE the group: KV heads share nothing)
+  }
+  if (with_tree) {
+    // the causal launch's walk with causal_offset = Nkv_i - ntok_i (the kernel, per sequence): the last token's limit is the last key, so every tile is walked and
+    // the KV ranges share out all of them; one token per sequence keeps the flag here — its word may hide its own key
+    a.causal = 1;
+    va.tree_bits = tree->bits;
+    va.tree_stride = tree->batch_stride;
+    va.tree_tokens = tree->tokens;
   }
 
   va.compact_tiles = pl.compact;
@@ -1250,9 +1276,9 @@ size_t workspace_bytes(const ffpa_varlen_fwd_params* params, bool paged) {
   return pl.ws_bytes;
 }
 
-int kernel_name(const ffpa_varlen_fwd_params* params, const VarlenPlan& pl, bool paged, char* buf, size_t n) {
+int kernel_name(const ffpa_varlen_fwd_params* params, const VarlenPlan& pl, bool paged, char* buf, size_t n, bool tree = false) {
   if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
-  snprintf(buf, n, "ffpa_fwd_m16_%s_kernel<%s, %d%s>%s%s", paged ? "paged" : "varlen", params->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d,
+  snprintf(buf, n, "ffpa_fwd_m16_%s%s_kernel<%s, %d%s>%s%s", paged ? "paged" : "varlen", tree ? "_tree" : "", params->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d,
            pl.nt ? ", NT" : "", pl.pack ? " (GQA heads packed into rows)" : "", pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
   return FFPA_OK;
 }
@@ -1300,6 +1326,41 @@ int ffpa_attn_varlen_paged_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffp
   if (rc != FFPA_OK) return rc;
   if ((rc = check_paged(p, kv)) != FFPA_OK) return rc;
   return kernel_name(p, pl, true, buf, n);
+}
+
+// ---- the tree-mask call (include/ffpa_attn.h: ffpa_tree_mask): the packed call or its paged twin, the causal launch's plan
+int ffpa_attn_varlen_tree_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, void* stream) {
+  return varlen_launch(p, kv, stream, tree, true);
+}
+
+namespace {
+
+int tree_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, VarlenPlan* pl) {
+  int rc = varlen_plan(p, pl, kv != nullptr);
+  if (rc != FFPA_OK) return rc;
+  if (kv != nullptr && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
+  return check_tree(p, tree);
+}
+
+}  // namespace
+
+size_t ffpa_attn_varlen_tree_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree) {
+  if (tree == nullptr || tree->struct_size != sizeof(ffpa_tree_mask) || (kv != nullptr && kv->struct_size != sizeof(ffpa_paged_kv))) return 0;
+  return workspace_bytes(p, kv != nullptr);
+}
+
+int ffpa_attn_varlen_tree_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, int out[5]) {
+  VarlenPlan pl;
+  const int rc = tree_plan(p, kv, tree, &pl);
+  if (rc != FFPA_OK) return rc;
+  return plan_out(pl, out);
+}
+
+int ffpa_attn_varlen_tree_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, char* buf, size_t n) {
+  VarlenPlan pl;
+  const int rc = tree_plan(p, kv, tree, &pl);
+  if (rc != FFPA_OK) return rc;
+  return kernel_name(p, pl, kv != nullptr, buf, n, true);
 }
 
 // ---- the KV-cache append + rotary (include/ffpa_attn.h: ffpa_kv_append_params)

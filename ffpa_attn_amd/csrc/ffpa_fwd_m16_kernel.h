@@ -276,6 +276,14 @@ __device__ __forceinline__ void row4_reduce1(float& t) {
   const auto s2 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   t = op(__uint_as_float(s2[0]), __uint_as_float(s2[1]));
 }
+// Tree mask (VarlenArgs::tree_bits): the visibility of a lane's 4 consecutive keys whose first one is draft key `first` (= key - (Nkv - tokens); negative: keys of
+// the prefix, visible to every token) under the token's 64-bit `word` — bit r of the result = key first + r is visible.  Keys at or past draft key 64 lie past
+// the sequence's last key (tokens <= 64): the caller's tail test hides them, whatever comes out here.
+__device__ __forceinline__ uint32_t m16_tree_nibble(uint64_t word, int first) {
+  const int lead = first < -4 ? 4 : -first;  // keys of the prefix in front of draft key 0 (first < 0): their bits are ones
+  return first >= 0 ? (uint32_t)(word >> (first & 63)) : (((uint32_t)word << (lead & 7)) | ((1u << (lead & 7)) - 1u));
+}
+
 // LDS images of the K / V tiles: row-major [BC][D], 16-byte slot s of row `key` stored at slot s ^ swizzle(key) (applied on the
 // DMA's per-lane source offset).  K fragments are fetched by ds_read_b128 whose 16-lane groups hold 16 different keys and two
 // neighbouring slots; V^T fragments by ds_read_b64_tr_b16 whose 32-lane halves hold 8 keys x 32 bytes.  Row strides that are whole
@@ -332,7 +340,11 @@ __global__ __launch_bounds__(256) void ffpa_fwd_m16_kernel(const FwdArgs a) {
 #define FFPA_M16_WS_ROW(row) ((((int64_t)split * a.B + b) * a.Hq + hq) * a.Nq + (row))
 #define FFPA_M16_Q_ROW_OFF(row) ((int64_t)(row) * a.sq[2])
 #define FFPA_M16_O_ROW_OFF(row) ((int64_t)(row) * a.so[2])
+#define FFPA_M16_TREE_ON false  // (no tree mask: the hooks fold away)
+#define FFPA_M16_TREE_WORD(tok, pin) 0ull
 #include "ffpa_fwd_m16_tile.inc"
+#undef FFPA_M16_TREE_WORD
+#undef FFPA_M16_TREE_ON
 #undef FFPA_M16_O_ROW_OFF
 #undef FFPA_M16_Q_ROW_OFF
 #undef FFPA_M16_WS_ROW
@@ -373,7 +385,11 @@ __global__ __launch_bounds__(256) void ffpa_fwd_m16_pair_kernel(const FwdArgs a)
 #define FFPA_M16_WS_ROW(row) ((((int64_t)split * a.B + b) * a.Hq + hq) * a.Nq + (row))
 #define FFPA_M16_Q_ROW_OFF(row) ((int64_t)(row) * a.sq[2])
 #define FFPA_M16_O_ROW_OFF(row) ((int64_t)(row) * a.so[2])
+#define FFPA_M16_TREE_ON false  // (no tree mask: the hooks fold away)
+#define FFPA_M16_TREE_WORD(tok, pin) 0ull
 #include "ffpa_fwd_m16_tile.inc"
+#undef FFPA_M16_TREE_WORD
+#undef FFPA_M16_TREE_ON
 #undef FFPA_M16_O_ROW_OFF
 #undef FFPA_M16_Q_ROW_OFF
 #undef FFPA_M16_WS_ROW
@@ -420,37 +436,36 @@ struct VarlenArgs {
   // by the rows there are, not by its longest sequence (8 sequences of 256 ... 4864 tokens: 304 slots per head of which 128 hold rows -> 136).  Slot -> (sequence,
   // row tile) on the device: the waves scan the sequences' tile counts 64 at a time (one load per lane, a wave prefix sum, a ballot); same order as the full grid.
   int compact_tiles;
+  // TREE MASK (ffpa_attn_varlen_tree_fwd: the verification step of tree speculative decoding): tree_tokens > 0 = the last ntok_i keys of sequence i — its draft
+  // keys — are visible to token t iff bit j of tree_bits[i * tree_stride + t] is set (j = key - (Nkv_i - ntok_i)); every key in front of them is visible to every
+  // token.  The launch runs under the causal flag (the tile walk, the KV ranges and the workgroup order are the causal launch's, whose last row sees the last key);
+  // only the element test of the tiles that hold a draft key differs (FFPA_M16_TREE_ON / FFPA_M16_TREE_WORD below).  Launches with tree_tokens != 0 run the *_tree_kernel builds.  tree_stride: words between two
+  // sequences, 0 = one tree for the batch.  tree_tokens = the words per sequence (1 ... 64; a token index is clamped to it).  0 = no tree.
+  const uint64_t* tree_bits;
+  int64_t tree_stride;
+  int tree_tokens;
 };
+// the tree hook of the tile text for the kernels that carry a VarlenArgs `va` and a sequence index `seq`: the word of a token (whether a kernel tests words at all is
+// a constant of its build: ffpa_fwd_m16_varlen_body.inc; the dense and paired kernels say "no tree")
+#define FFPA_M16_VARLEN_TREE_WORD(tok, pin) va.tree_bits[(int64_t)(seq + (pin)) * va.tree_stride + ((tok) < va.tree_tokens ? (tok) : va.tree_tokens - 1)]
 
 // NT: the decode-batch build — every K / V piece carries the non-temporal hint (each byte has ONE reader and the batch's K + V do not fit the caches: the launch
 // side's rule, ffpa_capi.hip; LDS-DMA from HBM 5.9 -> 7.3 TB/s with it, profiles/r04_kv_stream.txt) — otherwise the same kernel.
 template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_varlen_kernel(const FwdArgs a_in, const VarlenArgs va) {
-  constexpr int MK = 0;  // no attn_bias, no mask ranges: what the reference's packed entry point accepts
-  constexpr bool DROP = false;
-#define FFPA_M16_MFMA std::conditional_t<NT, Mfma16Nt<T>, Mfma16<T>>
-#define FFPA_M16_DMA16 LdsDma16<NT>::template at
-#include "ffpa_fwd_m16_head.inc"
-#include "ffpa_fwd_m16_varlen_seq.inc"
-#define FFPA_M16_TILE_DONE return
-#define FFPA_M16_ROW_INV(l) ((l) > 0.f ? __builtin_amdgcn_rcpf(l) : 0.f)
-#define FFPA_M16_ROW_OUT(x, rh) (l_tot[rh] > 0.f ? (T)((x) * inv[rh]) : (T)0.f)  // (the select BEHIND product + conversion: those stay the dense kernel's one instruction — fp16: v_fma_mixlo, one rounding — and its bits)
-#define FFPA_M16_LSE_INDEX(row) (va.pack ? (int64_t)(hq * va.pack + (row) / ntok) * va.lse_stride_h + q_lo + (row) % ntok : (int64_t)hq * va.lse_stride_h + q_lo + (row))
-// (the KV-split workspace of the packed call: [split, query head, token] rows — ffpa_varlen_merge_kernel reads them back by (head, token))
-#define FFPA_M16_WS_ROW(row) ((int64_t)split * va.ws_split_rows + (va.pack ? (int64_t)(hq * va.pack + (row) / ntok) * va.ws_head_rows + q_lo + (row) % ntok : (int64_t)hq * va.ws_head_rows + q_lo + (row)))
-// (packed rows: a.sq[2] / a.so[2] are the HEAD strides of q / o, a token is q_tok_stride / o_tok_stride further; rows are tokens: ntok-independent)
-#define FFPA_M16_Q_ROW_OFF(row) (va.pack ? (int64_t)((row) / ntok) * a.sq[2] + (int64_t)((row) % ntok) * va.q_tok_stride : (int64_t)(row) * a.sq[2])
-#define FFPA_M16_O_ROW_OFF(row) (va.pack ? (int64_t)((row) / ntok) * a.so[2] + (int64_t)((row) % ntok) * va.o_tok_stride : (int64_t)(row) * a.so[2])
-#include "ffpa_fwd_m16_tile.inc"
-#undef FFPA_M16_O_ROW_OFF
-#undef FFPA_M16_Q_ROW_OFF
-#undef FFPA_M16_WS_ROW
-#undef FFPA_M16_LSE_INDEX
-#undef FFPA_M16_ROW_OUT
-#undef FFPA_M16_ROW_INV
-#undef FFPA_M16_TILE_DONE
-#undef FFPA_M16_DMA16
-#undef FFPA_M16_MFMA
+#define FFPA_M16_VARLEN_TREE false
+#include "ffpa_fwd_m16_varlen_body.inc"
+#undef FFPA_M16_VARLEN_TREE
+}
+
+// The same kernel under a TREE MASK (VarlenArgs::tree_bits; ffpa_attn_varlen_tree_fwd): a kernel of its own from the same text, so that the launches without a
+// mask run exactly the code they ran before (with the test folded into ONE kernel behind a run-time flag the causal KV-cache call measured slower than the
+// parent commit's: profiles/r12_tree_mask.md section 5).
+template <typename T, int D, bool NT = false>
+__global__ __launch_bounds__(256) void ffpa_fwd_m16_varlen_tree_kernel(const FwdArgs a_in, const VarlenArgs va) {
+#define FFPA_M16_VARLEN_TREE true
+#include "ffpa_fwd_m16_varlen_body.inc"
+#undef FFPA_M16_VARLEN_TREE
 }
 
 }  // namespace ffpa

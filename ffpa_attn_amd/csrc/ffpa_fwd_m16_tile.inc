@@ -7,6 +7,10 @@
 // Where a K / V tile comes from is the enclosing kernel's too when it defines FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) (kind 0: K, 1: V, 2: the L2 touch)
 // and the hooks around it — FFPA_M16_KV_BEGIN(t0) in front of the first piece, FFPA_M16_KV_STEP(k0) at the top of a KV step, FFPA_M16_KV_STEP_END() in front of
 // barrier B (the paged kernel, ffpa_paged_inst.hip); by default the tile's rows are contiguous from `slice` and the hooks are empty.
+// A TREE MASK over the last keys of the sequence is the enclosing kernel's as well: FFPA_M16_TREE_ON = the launch carries one (it runs under the causal flag
+// with causal_offset = Nkv - tokens: every loop bound is the causal launch's), FFPA_M16_TREE_WORD(t, pin) = the 64-bit word of token t — bit j set = the token sees key
+// causal_offset + j; `pin` is a scalar zero the compiler cannot see through, added to the sequence index so that the word's address is computed where it is used.  Only the element test of the tiles that hold a key >= causal_offset differs (the two `tail || diag` branches below): the word is loaded inside
+// that branch and dies there.  The dense and paired kernels define "no tree" (false / 0ull): the branch folds to the text that stood here.
 #ifndef FFPA_M16_KV_SRC
 #define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) tile_src<BC>(slice, row_bytes, key0, a.Nkv, rb_valid)
 #define FFPA_M16_KV_BEGIN(t0_)
@@ -520,7 +524,10 @@
         bias_init(s0, k0 + BC);
         __builtin_amdgcn_sched_barrier(0);
         const bool tail = k0 + BC > a.Nkv;
-        const bool diag = a.causal && ((int64_t)k0 + BC - 1 > (int64_t)(a.causal_row_mod ? 0 : wq0) + a.causal_offset);
+        const bool tree = FFPA_M16_TREE_ON;  // (wave-uniform)
+        const bool diag = !tree && a.causal && ((int64_t)k0 + BC - 1 > (int64_t)(a.causal_row_mod ? 0 : wq0) + a.causal_offset);
+        // (a tree mask: every tile that holds a draft key or ends past the last key — draft key 0 itself is subject to the mask, so >= where the causal test has >)
+        const bool tree_tile = tree && (tail || (int64_t)k0 + BC - 1 >= (int64_t)a.causal_offset);
         // one group of the softmax's instructions per MFMA gap: g = 2 * fragment + (0: behind the first, 1: behind the second MFMA)
         auto softmax_gap = [&](auto gc) __attribute__((always_inline)) {
           constexpr int g = decltype(gc)::value;
@@ -557,7 +564,26 @@
                 }
               }
             }
-            if (tail || diag) {
+            if (tree_tile) {
+              // the row's token (rows past the last one repeat it: nothing of theirs is stored) and its mask word: computed and loaded here, dead at the end of
+              // the branch (the empty asm pins the chain to this place: hoisted in front of the KV loop, its loop-invariant parts would hold registers across the MFMA loops)
+              int trow = qrow_own, tcol = 4 * c, tmod = a.causal_row_mod, tpin = 0;
+              asm volatile("" : "+v"(trow), "+v"(tcol), "+s"(tmod), "+s"(tpin));
+              trow = trow < a.Nq ? trow : a.Nq - 1;
+              uint64_t word = FFPA_M16_TREE_WORD(tmod ? trow % tmod : trow, tpin);
+              // (a use on EVERY path of the branch: the compiler's wait for the load sits here — left pending on a path that skips its uses, it becomes a vmcnt(0)
+              // at the top of the PV loop of every KV step, which drains the LDS-DMA queue there: profiles/r12_tree_mask.md section 5)
+              asm volatile("" : "+v"(word));
+#pragma unroll
+              for (int kb = 0; kb < NKB; ++kb) {
+                const uint32_t vis = m16_tree_nibble(word, k0 + kb * 16 + tcol - a.causal_offset);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                  if (k0 + kb * 16 + 4 * c + r >= a.Nkv || ((vis >> r) & 1u) == 0u) x[kb][r] = -INFINITY;
+                __builtin_amdgcn_sched_barrier(0);  // (one key block at a time: interleaved, the blocks' temporaries add up at the kernel's register peak)
+              }
+            }
+            if ((tail && !tree) || diag) {
               const int crow = a.causal_row_mod ? qrow_own % a.causal_row_mod : qrow_own;
               const int64_t lim = a.causal ? (int64_t)crow + a.causal_offset : (int64_t)a.Nkv;
 #pragma unroll
@@ -971,8 +997,32 @@
       }
     }
     const bool tail = k0 + BC > a.Nkv;
-    const bool diag = a.causal && ((int64_t)k0 + BC - 1 > (int64_t)(a.causal_row_mod ? 0 : wq0) + a.causal_offset);
-    if (tail || diag) {
+    const bool tree = FFPA_M16_TREE_ON;  // (wave-uniform)
+    const bool diag = !tree && a.causal && ((int64_t)k0 + BC - 1 > (int64_t)(a.causal_row_mod ? 0 : wq0) + a.causal_offset);
+    // (a tree mask: every tile that holds a draft key or ends past the last key — draft key 0 itself is subject to the mask, so >= where the causal test has >)
+    if (tree && (tail || (int64_t)k0 + BC - 1 >= (int64_t)a.causal_offset)) {
+#pragma unroll
+      for (int rh = 0; rh < RHS; ++rh) {
+        // the row's token (rows past the last one repeat it: nothing of theirs is stored) and its mask word: computed and loaded here, dead at the end of the
+        // branch (the empty asm pins the chain to this place: hoisted in front of the KV loop, its loop-invariant parts would hold registers across the MFMA loops)
+        int trow = qrow_s[rh], tcol = 4 * c, tmod = a.causal_row_mod, tpin = 0;
+        asm volatile("" : "+v"(trow), "+v"(tcol), "+s"(tmod), "+s"(tpin));
+        trow = trow < a.Nq ? trow : a.Nq - 1;
+        uint64_t word = FFPA_M16_TREE_WORD(tmod ? trow % tmod : trow, tpin);
+        // (a use on EVERY path of the branch: the compiler's wait for the load sits here — left pending on a path that skips its uses, it becomes a vmcnt(0)
+        // at the top of the PV loop of every KV step, which drains the LDS-DMA queue there: profiles/r12_tree_mask.md section 5)
+        asm volatile("" : "+v"(word));
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) {
+          const uint32_t vis = m16_tree_nibble(word, k0 + kb * 16 + tcol - a.causal_offset);
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (k0 + kb * 16 + 4 * c + r >= a.Nkv || ((vis >> r) & 1u) == 0u) x[kb][rh][r] = -INFINITY;
+          __builtin_amdgcn_sched_barrier(0);  // (one key block at a time: interleaved, the blocks' temporaries add up at the kernel's register peak)
+        }
+      }
+    }
+    if ((tail && !tree) || diag) {
 #pragma unroll
       for (int rh = 0; rh < RHS; ++rh) {
         const int crow = a.causal_row_mod ? qrow_s[rh] % a.causal_row_mod : qrow_s[rh];

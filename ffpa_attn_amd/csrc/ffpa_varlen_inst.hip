@@ -17,6 +17,7 @@ template <typename T, int D, bool NT>
 static int launch_varlen(const FwdArgs& a, const VarlenArgs& va, hipStream_t stream) {
   constexpr int BC = m16_block_keys(D, false);
   constexpr int LDS = 2 * BC * D * 2 + m16_exchange_bytes(D, 0);
+  if (va.tree_tokens != 0) return launch_kernel<ffpa_fwd_m16_varlen_tree_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va);  // (under a tree mask: its own build)
   return launch_kernel<ffpa_fwd_m16_varlen_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va);
 }
 

@@ -175,6 +175,19 @@ class FfpaPagedKv(ctypes.Structure):
   ]
 
 
+class FfpaTreeMask(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_tree_mask`` (include/ffpa_attn.h): the mask words of the tree call."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("bits", ctypes.c_void_p),
+    ("batch_stride", ctypes.c_int64),
+    ("tokens", ctypes.c_int32),
+    ("reserved2", ctypes.c_int32),
+  ]
+
+
 class FfpaKvAppendParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_kv_append_params`` (include/ffpa_attn.h): the KV-cache append + rotary call."""
 
@@ -244,6 +257,7 @@ _lib_lock = threading.Lock()
 _P = ctypes.POINTER
 _INT, _SIZE, _VOID, _STR = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_char_p
 _VARLEN, _PAGED = [_P(FfpaVarlenFwdParams)], [_P(FfpaVarlenFwdParams), _P(FfpaPagedKv)]
+_TREE = _PAGED + [_P(FfpaTreeMask)]
 # Every function include/ffpa_attn.h declares: (symbol, argtypes, restype, since).  ``since``: the ABI version that added it (0: there from the start) — the
 # default library has them all; one loaded by path (developer A/B runs load a saved build of an older commit) may lack those with since > 0.
 _BINDINGS = (
@@ -261,6 +275,10 @@ _BINDINGS = (
   ("ffpa_attn_varlen_paged_fwd_plan", _PAGED + [_P(_INT)], _INT, 7),
   ("ffpa_attn_varlen_paged_fwd_kernel", _PAGED + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_paged_fwd_workspace_bytes", _PAGED, _SIZE, 7),
+  ("ffpa_attn_varlen_tree_fwd", _TREE + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_tree_fwd_plan", _TREE + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_tree_fwd_kernel", _TREE + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_tree_fwd_workspace_bytes", _TREE, _SIZE, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
   ("ffpa_attn_query", [_INT], _INT, 0),
@@ -350,10 +368,10 @@ def __getattr__(name: str):
 # ---- what every call of the library does, once: a stamped parameter struct, the status -> exception raise, the call on the current stream, the scratch hand-over,
 # the plan read-out.  Plain functions: ``forward`` / ``varlen_forward`` run once per decoded token.
 def _stamped(cls):
-  """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` rides next to a versioned struct), the ABI version — filled in."""
+  """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` ride next to a versioned struct), the ABI version — filled in."""
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
-  if cls is not FfpaPagedKv:
+  if cls not in (FfpaPagedKv, FfpaTreeMask):
     p.abi_version = ABI_VERSION
   return p
 
@@ -984,8 +1002,11 @@ def _paged_kv_of(block_table: torch.Tensor, k: torch.Tensor, v: torch.Tensor) ->
   return _paged_kv(block_table.data_ptr(), block_table.stride(0), block_table.size(1), k.size(1), k.size(0), k.stride(0), v.stride(0)), block_table
 
 
-def _varlen_fn(lib, kv: "FfpaPagedKv | None", suffix: str = ""):
-  """The packed call's export — or, with ``kv``, its paged twin's — of this suffix ("" the launch, "_plan", "_kernel", "_workspace_bytes")"""
+def _varlen_fn(lib, kv: "FfpaPagedKv | None", suffix: str = "", tree: bool = False):
+  """The packed call's export — or, with ``kv``, its paged twin's; with ``tree``, the tree call's (one export for both: its ``kv`` may be NULL) — of this suffix
+  ("" the launch, "_plan", "_kernel", "_workspace_bytes")"""
+  if tree:
+    return getattr(lib, "ffpa_attn_varlen_tree_fwd" + suffix)
   return getattr(lib, ("ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd") + suffix)
 
 
@@ -993,22 +1014,23 @@ def _varlen_fn(lib, kv: "FfpaPagedKv | None", suffix: str = ""):
 _VARLEN_SCRATCH: "dict[tuple, int]" = {}
 
 
-def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaPagedKv | None", args: tuple) -> int:
+def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaPagedKv | None", args: tuple, tree: bool = False) -> int:
   if p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC:
     return 0
   key = (id(lib), device_index, p.dtype, p.batch, p.heads_q, p.heads_kv, p.head_dim, p.max_seqlen_q, p.max_seqlen_kv, p.total_q, p.causal, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS"),
-         kv is not None)
+         kv is not None, tree)
   hit = _VARLEN_SCRATCH.get(key)
   if hit is None:
     if len(_VARLEN_SCRATCH) >= 512:
       _VARLEN_SCRATCH.clear()
-    hit = _VARLEN_SCRATCH[key] = int(_varlen_fn(lib, kv, "_workspace_bytes")(*args))
+    hit = _VARLEN_SCRATCH[key] = int(_varlen_fn(lib, kv, "_workspace_bytes", tree)(*args))
   return hit
 
 
 def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: "torch.Tensor | None", max_seqlen_q: int,
                    max_seqlen_k: int, causal: bool, softmax_scale: float, *, rescale_threshold: float = -1.0, return_lse: bool = True, flags: int = 0,
-                   plan_out: "dict | None" = None, seqused_k: "torch.Tensor | None" = None, num_splits: int = 0, block_table: "torch.Tensor | None" = None):
+                   plan_out: "dict | None" = None, seqused_k: "torch.Tensor | None" = None, num_splits: int = 0, block_table: "torch.Tensor | None" = None,
+                   tree_words: "torch.Tensor | None" = None):
   """One launch of the packed-sequence kernel: ``q [T_q, Hq, D]``, ``k`` / ``v [T_k, Hkv, D]``, int32 device ``cu_seqlens_*`` ``[B + 1]`` ->
   ``(o [T_q, Hq, D], lse [Hq, T_q] fp32 | None)``.  Nothing is read back to the host and nothing synchronises: the call captures into a HIP graph.
   Rows without a visible key: O = 0, LSE = -inf.
@@ -1025,9 +1047,14 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
   ``block_table`` (int32 device ``[B, pages_per_row]``): a PAGED KV cache — ``k`` / ``v`` are page pools ``[num_pages, page_size, Hkv, D]`` (``page_size`` a multiple
   of 64), key j of sequence i is row ``j % page_size`` of page ``block_table[i, j // page_size]``; ``seqused_k`` is required and gives the lengths (clamped to
   ``pages_per_row * page_size``), ``cu_seqlens_k`` is ignored (may be None).  One launch of the paged twin of the packed kernel (``ffpa_attn_varlen_paged_fwd``):
-  no gather, nothing read back to the host, graph-capturable; replays follow ``seqused_k`` / ``block_table`` written in place."""
+  no gather, nothing read back to the host, graph-capturable; replays follow ``seqused_k`` / ``block_table`` written in place.
+
+  ``tree_words`` (int64 device ``[B | 1, tokens]``, ``max_seqlen_q <= tokens <= 64``; ``tree_forward`` is this call with it): a TREE MASK over the last keys of
+  every sequence (``ffpa_attn_varlen_tree_fwd``) — token t of sequence i sees every key in front of its sequence's last ``ntok_i`` keys and, of those, key j iff
+  bit j of ``tree_words[i, t]`` is set; ``causal`` is ignored.  The same kernel and plan as the causal launch; a replay follows words written in place."""
   paged = block_table is not None
-  name = "ffpa_attn::_paged_fwd_hip" if paged else "ffpa_attn::_varlen_fwd_hip"
+  tree = tree_words is not None
+  name = "ffpa_attn::_tree_fwd_hip" if tree else "ffpa_attn::_paged_fwd_hip" if paged else "ffpa_attn::_varlen_fwd_hip"
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
@@ -1069,6 +1096,13 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
   if k.device != q.device or v.device != q.device:
     raise ValueError(f"{name}: q/k/v must be on one device, got {q.device}, {k.device}, {v.device}")
   Tq, Hq, D = q.shape
+  if tree:
+    if not isinstance(tree_words, torch.Tensor) or tree_words.dtype != torch.int64 or tree_words.dim() != 2 or tree_words.device != q.device:
+      raise ValueError(f"{name}: tree_words must be a 2-D int64 tensor [batch or 1, tokens] on q's device")
+    if tree_words.size(0) not in (1, cu_seqlens_q.numel() - 1) or not max(int(max_seqlen_q), 1) <= tree_words.size(1) <= 64:
+      raise ValueError(f"{name}: tree_words {tuple(tree_words.shape)} must be [batch={cu_seqlens_q.numel() - 1} or 1, tokens] with max_seqlen_q={max_seqlen_q} <= tokens <= 64")
+    if tree_words.stride(1) != 1:
+      tree_words = tree_words.contiguous()
   q, k, v, Dp = _pad_head_dim(q, k, v)  # (a paged call: copies the pools)
   if k.size(0) == 0:
     # no key row anywhere (an empty pool: ids clamp into this one zero page): every output row is the empty row (O = 0, LSE = -inf).  The C-ABI wants non-NULL
@@ -1096,15 +1130,33 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
   if paged:
     kv, block_table = _paged_kv_of(block_table, k, v)
     args = (ctypes.byref(p), ctypes.byref(kv))
+  if tree:
+    tm = _stamped(FfpaTreeMask)
+    tm.bits, tm.tokens = tree_words.data_ptr(), tree_words.size(1)
+    tm.batch_stride = tree_words.stride(0) if tree_words.size(0) > 1 else 0
+    args = (ctypes.byref(p), ctypes.byref(kv) if paged else None, ctypes.byref(tm))
   with torch.cuda.device(q.device):
     stream = torch.cuda.current_stream(q.device).cuda_stream
-    workspace = _hand_over_workspace(p, q.device, stream, _varlen_scratch(lib, p, q.device.index or 0, kv, args))  # (held in a local until the launch below has been enqueued)
+    workspace = _hand_over_workspace(p, q.device, stream, _varlen_scratch(lib, p, q.device.index or 0, kv, args, tree))  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
-      plan_out.update(_read_plan(lib, _varlen_fn(lib, kv, "_plan"), _varlen_fn(lib, kv, "_kernel"), _VARLEN_PLAN_KEYS, args))
-    rc = _varlen_fn(lib, kv)(*args, ctypes.c_void_p(stream))
+      plan_out.update(_read_plan(lib, _varlen_fn(lib, kv, "_plan", tree), _varlen_fn(lib, kv, "_kernel", tree), _VARLEN_PLAN_KEYS, args))
+    rc = _varlen_fn(lib, kv, "", tree)(*args, ctypes.c_void_p(stream))
   if rc != 0:
-    _raise_status(lib, rc, "ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd")
+    _raise_status(lib, rc, "ffpa_attn_varlen_tree_fwd" if tree else "ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd")
   return _unpad_head_dim(o, D), lse
+
+
+def tree_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: "torch.Tensor | None", max_seqlen_q: int,
+                 max_seqlen_k: int, softmax_scale: float, tree_words: torch.Tensor, *, rescale_threshold: float = -1.0, return_lse: bool = True, flags: int = 0,
+                 plan_out: "dict | None" = None, seqused_k: "torch.Tensor | None" = None, num_splits: int = 0, block_table: "torch.Tensor | None" = None):
+  """One launch of the packed-sequence kernel (``block_table``: of its paged twin) under a TREE MASK (``ffpa_attn_varlen_tree_fwd``; ``varlen_forward``'s
+  ``tree_words``): ``tree_words`` int64 ``[B | 1, tokens]`` as ``ffpa_attn_amd.pack_tree_mask`` makes them.  ``flags`` / ``plan_out`` as ``varlen_forward``
+  (``FLAG_NO_PACK_GQA``, ``FLAG_KV_STREAM``, the split count: tests force or inspect the launch)."""
+  if tree_words is None:
+    raise ValueError("ffpa_attn::_tree_fwd_hip: tree_words is required")
+  return varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, True, softmax_scale, rescale_threshold=rescale_threshold,
+                        return_lse=return_lse, flags=flags, plan_out=plan_out, seqused_k=seqused_k, num_splits=num_splits, block_table=block_table,
+                        tree_words=tree_words)
 
 
 def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: int, max_seqlen_k: int, head_dim: int, *,
@@ -1169,6 +1221,28 @@ def _paged_fwd_hip_torch_op(q, k, v, cu_seqlens_q, seqused_k, block_table, max_s
 
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_paged_fwd_hip")
 def _paged_fwd_hip_fake(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, softmax_scale, causal, rescale_threshold=-1.0, num_splits=0):
+  total_q, heads, head_dim = q.shape
+  return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
+
+
+# The tree-mask call (ffpa_attn_with_kvcache_tree): one op for both caches — ``block_table`` None = the contiguous cache as packed rows + ``cu_seqlens_k``
+torch.library.define(
+  f"{_OP_NAMESPACE}::_tree_fwd_hip",
+  "(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor? cu_seqlens_k, Tensor seqused_k, Tensor? block_table, Tensor tree_words, int max_seqlen_q, "
+  "int max_seqlen_k, float softmax_scale, float rescale_threshold=-1.0, int num_splits=0) -> (Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_tree_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _tree_fwd_hip_torch_op(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, tree_words, max_seqlen_q, max_seqlen_k, softmax_scale,
+                           rescale_threshold=-1.0, num_splits=0):
+  return tree_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, softmax_scale, tree_words, rescale_threshold=rescale_threshold,
+                      return_lse=True, seqused_k=seqused_k, num_splits=num_splits, block_table=block_table)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_tree_fwd_hip")
+def _tree_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, tree_words, max_seqlen_q, max_seqlen_k, softmax_scale,
+                       rescale_threshold=-1.0, num_splits=0):
   total_q, heads, head_dim = q.shape
   return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
 

@@ -231,6 +231,104 @@ def ffpa_attn_with_kvcache(
   return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
 
 
+# ---- tree-mask attention (the verification step of tree speculative decoding): ffpa_attn_with_kvcache_tree
+_TREE_MAX_TOKENS = 64  # one 64-bit word per (sequence, token)
+
+
+def pack_tree_mask(tree_mask: torch.Tensor) -> torch.Tensor:
+  """The mask words the tree launch reads: ``tree_mask`` bool ``[Sq, Sq]`` (one tree for the batch) or ``[B, Sq, Sq]``, ``1 <= Sq <= 64`` -> int64 ``[1 | B, Sq]``
+  with bit j of word ``[b, i]`` = ``tree_mask[b, i, j]`` (bit 63 is the int64's sign bit).  Torch ops on the mask's device, nothing read back to the host: a
+  caller that replays a captured graph writes new words into the tensor it handed to ``ffpa_attn_with_kvcache_tree`` in place."""
+  if not isinstance(tree_mask, torch.Tensor):
+    raise TypeError(f"pack_tree_mask: tree_mask must be a tensor, got {type(tree_mask).__name__}")
+  if tree_mask.dtype != torch.bool:
+    raise TypeError(f"pack_tree_mask: tree_mask must be a torch.bool tensor, got {tree_mask.dtype}")
+  if tree_mask.dim() not in (2, 3) or tree_mask.size(-1) != tree_mask.size(-2):
+    raise ValueError(f"pack_tree_mask: tree_mask must be [Sq, Sq] or [B, Sq, Sq], got {tuple(tree_mask.shape)}")
+  sq = tree_mask.size(-1)
+  if not 1 <= sq <= _TREE_MAX_TOKENS:
+    raise ValueError(f"pack_tree_mask: tree_mask holds Sq = {sq} tokens, outside [1, {_TREE_MAX_TOKENS}] (one 64-bit word per token)")
+  m = tree_mask if tree_mask.dim() == 3 else tree_mask[None]
+  bit = torch.ones((), dtype=torch.int64, device=m.device) << torch.arange(sq, dtype=torch.int64, device=m.device)  # (1 << 63 wraps to the sign bit)
+  return (m.to(torch.int64) * bit).sum(dim=-1)  # (disjoint bits: the wrapping sum is the OR)
+
+
+def _tree_words(tree_mask, B: int, Sq: int, device) -> torch.Tensor:
+  """``tree_mask`` of ffpa_attn_with_kvcache_tree checked against q's batch / tokens / device -> the int64 words ``[B | 1, Sq]``."""
+  name = "ffpa_attn_with_kvcache_tree"
+  if not isinstance(tree_mask, torch.Tensor):
+    raise TypeError(f"{name}: tree_mask must be a tensor, got {type(tree_mask).__name__}")
+  if tree_mask.dtype not in (torch.bool, torch.int64):
+    raise TypeError(f"{name}: tree_mask must be a torch.bool mask or int64 packed words (pack_tree_mask), got {tree_mask.dtype}")
+  if not 1 <= Sq <= _TREE_MAX_TOKENS:
+    raise ValueError(f"{name}: a tree_mask needs 1 <= Sq <= {_TREE_MAX_TOKENS} query tokens per sequence (one 64-bit word per token), got q with Sq = {Sq}")
+  if tree_mask.device != device:
+    raise ValueError(f"{name}: tree_mask must be on q's device, got {tree_mask.device} and {device}")
+  if tree_mask.dtype == torch.int64:
+    if tree_mask.dim() != 2 or tree_mask.size(0) not in (1, B) or tree_mask.size(1) != Sq:
+      raise ValueError(f"{name}: a packed tree_mask must be int64 [B={B} or 1, Sq={Sq}], got {tuple(tree_mask.shape)}")
+    return tree_mask
+  if tree_mask.dim() not in (2, 3) or tuple(tree_mask.shape[-2:]) != (Sq, Sq) or (tree_mask.dim() == 3 and tree_mask.size(0) != B):
+    raise ValueError(f"{name}: tree_mask must be bool [Sq={Sq}, Sq={Sq}] or [B={B}, Sq={Sq}, Sq={Sq}], got {tuple(tree_mask.shape)}")
+  return pack_tree_mask(tree_mask)
+
+
+def ffpa_attn_with_kvcache_tree(
+  q: torch.Tensor,
+  k_cache: torch.Tensor,
+  v_cache: torch.Tensor,
+  k: torch.Tensor | None = None,
+  v: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor | None" = None,
+  block_table: torch.Tensor | None = None,
+  *,
+  tree_mask: torch.Tensor,
+  softmax_scale: float | None = None,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+):
+  """``ffpa_attn_with_kvcache`` under a TREE MASK: the verification step of tree speculative decoding (EAGLE, Medusa, SpecInfer; FlashInfer's ``custom_mask`` for
+  that case).  The engine has appended — or appends here, with ``k`` / ``v`` — the ``Sq`` draft nodes of every sequence to its cache and calls attention once:
+  node i sees the whole prefix and, among the ``Sq`` draft keys, what ``tree_mask`` says (its ancestors and itself, in a tree).  ONE attention launch of the
+  same packed / paged kernel, the same plan as the causal call; no gather of the pages, no call per root-to-leaf path.
+
+  Shapes, dtypes, layouts, strides, paged or contiguous caches, GQA, ``num_splits`` and the returns are ``ffpa_attn_with_kvcache``'s.  ``tree_mask``: a
+  ``torch.bool`` tensor on q's device, ``[Sq, Sq]`` (one tree for the batch) or ``[B, Sq, Sq]``, ``1 <= Sq <= 64`` — or the int64 words ``[B | 1, Sq]``
+  ``pack_tree_mask`` makes of one (bit j of word ``[b, i]`` = ``tree_mask[b, i, j]``).  With ``L_b`` the keys attention runs over (``min(cache_seqlens[b] + Snew,
+  capacity)`` with ``k`` / ``v``, else ``cache_seqlens[b]`` clamped to the capacity), query token i of sequence b sees
+
+  * key ``p`` for every ``p < L_b - Sq`` (the prefix), and
+  * key ``L_b - Sq + j`` iff ``tree_mask[b, i, j]``; draft positions below 0 (``L_b < Sq``) do not exist.
+
+  The mask is arbitrary: a False diagonal and "sees a later node" are legal; ``tril(ones)`` is the causal call and all ones the non-causal one, to the bit.  A
+  row that sees no key returns O = 0, LSE = -inf.  ``k`` / ``v`` append exactly as in ``ffpa_attn_with_kvcache`` (key i at ``cache_seqlens[b] + i``: the same
+  launch).  There is no ``rotary_cos`` / ``rotary_sin`` here: a tree node's position is its DEPTH, not its index among the new keys, and the append kernel has
+  no per-token positions — rotate q and the draft keys before the call.  Nothing is read back to the host: the call captures into one HIP graph, and a replay
+  follows ``cache_seqlens``, ``block_table`` and the mask written in place — a bool mask is packed inside the graph; hand over packed words to write words.
+  Inference only: a tensor that requires grad raises ``NotImplementedError``."""
+  capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, None, None, cache_seqlens, None, None, block_table, softmax_scale, (-1, -1), 0.0, None,
+                                       num_splits)
+  if isinstance(tree_mask, torch.Tensor) and tree_mask.requires_grad and torch.is_grad_enabled():
+    raise NotImplementedError("ffpa_attn_with_kvcache is inference only: tree_mask requires grad and there is no backward")
+  B, Sq, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  words = _tree_words(tree_mask, B, Sq, q.device)
+  q, seqused = _append(q, k_cache, v_cache, k, v, None, None, cache_seqlens, seqused, block_table, capacity, True, False)
+  qp = q.reshape(B * Sq, Hq, D)
+  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
+  if block_table is not None:
+    kp, vp, cu_k = k_cache, v_cache, None
+  else:
+    # the contiguous cache as the packed call's seqused_k case (ffpa_attn_with_kvcache's view: sequence b's keys are rows b * capacity ...)
+    kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
+    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
+  o, lse = torch.ops.ffpa_attn._tree_fwd_hip(qp, kp, vp, cu_q, cu_k, seqused, block_table, words, Sq, capacity, scale, -1.0, num_splits)
+  out = o.view(B, Sq, Hq, D)
+  if not return_softmax_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
 # ---- cascade (shared-prefix) attention: ffpa_attn_with_kvcache_cascade
 # cascade=None takes the cascade where the K + V re-reads it saves — (B - 1) * P keys x Hkv x D x 2 (K and V) x 2 bytes, the copies of the prefix the plain
 # launch streams for sequences 1 .. B - 1 — reach _CASCADE_MIN_SAVED_BYTES.  Fitted to the interleaved A/B of tools/gpu_cascade_ab.py on MI355X

@@ -346,6 +346,41 @@ int ffpa_attn_varlen_paged_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_
 int ffpa_attn_varlen_paged_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, char* buf, size_t n);
 
 /*
+ * TREE MASK over the last keys of every sequence — the verification step of tree speculative decoding (EAGLE, Medusa, SpecInfer; FlashInfer's custom_mask for
+ * that case): the engine has appended the ntok_i draft nodes of sequence i to its keys and calls attention ONCE; node t must see the whole prefix and, among the
+ * draft keys, its own ancestors only.  The packed call (kv == NULL) or its paged twin (kv != NULL) with these changes:
+ *   the last ntok_i = cu_seqlens_q[i + 1] - cu_seqlens_q[i] keys of sequence i are its DRAFT keys.  Query token t of sequence i sees
+ *        key p                        for every p < Nkv_i - ntok_i (the prefix), and
+ *        key Nkv_i - ntok_i + j       iff bit j of bits[i * batch_stride + t] is set (0 <= j < ntok_i);
+ *        draft positions below key 0 (Nkv_i < ntok_i) do not exist.  The mask is arbitrary: a clear diagonal and "sees a later node" are legal.
+ *   p->causal is ignored (all ones below the diagonal IS the causal launch, all ones the non-causal one: the same bits as those launches).  A token whose
+ *        word hides every key it could see gives O = 0, LSE = -inf, the packed call's empty-row contract; one token per sequence keeps its mask (bit 0 clear =
+ *        "the prefix only").
+ *   (ffpa_varlen_fwd_params has no dropout: like the packed call, the tree call cannot be asked for it, so there is nothing to refuse.)
+ *   `tokens` words per sequence: max_seqlen_q <= tokens <= 64.  batch_stride = words between two sequences' rows (>= tokens), or 0 = one tree for the batch.
+ * Which tiles are walked — the tile range, the KV ranges of a split launch and their share-out, the workgroup order — is the causal launch's, whose last token
+ * sees the last key; only the element test of the KV tiles that hold a draft key reads the words.  The words are read on the device at launch time: a captured
+ * graph follows words written in place.
+ */
+typedef struct ffpa_tree_mask {
+  uint32_t struct_size;  /* sizeof(ffpa_tree_mask), checked */
+  uint32_t reserved;     /* 0 */
+  const uint64_t* bits;  /* device, 8-byte aligned: [batch or 1][tokens] words */
+  int64_t batch_stride;  /* words between two sequences (>= tokens); 0 = every sequence reads row 0 */
+  int32_t tokens;        /* words per sequence: 1 ... 64, >= max_seqlen_q */
+  int32_t reserved2;
+} ffpa_tree_mask;
+
+/* Launch the forward under a tree mask on `stream` of the CURRENT device (kv: the paged pool, NULL = the packed call's contiguous keys).  Asynchronous; every bad
+ * argument returns a status before any device work.  Returns an ffpa_status. */
+int ffpa_attn_varlen_tree_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, void* stream);
+
+/* As ffpa_attn_varlen_fwd_workspace_bytes / _plan / _kernel, for the tree call ("ffpa_fwd_m16_paged_tree_kernel<bf16, 512>": the packed / paged kernel's build that tests mask words; the plan is that call's own). */
+size_t ffpa_attn_varlen_tree_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree);
+int ffpa_attn_varlen_tree_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, int out[5]);
+int ffpa_attn_varlen_tree_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, char* buf, size_t n);
+
+/*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
  * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
  *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position
