@@ -1124,13 +1124,64 @@ int check_tree(const ffpa_varlen_fwd_params* p, const ffpa_tree_mask* tree) {
   return FFPA_OK;
 }
 
+// The window call's own argument (ffpa_window), checked behind the packed call's plan (and the paged pool) and before anything touches the device.
+int check_window(const ffpa_window* w) {
+  if (w == nullptr) return fail(FFPA_ERR_NULL_POINTER, "window is NULL");
+  if (w->struct_size != sizeof(ffpa_window)) return fail(FFPA_ERR_BAD_ABI, "ffpa_window ABI mismatch: size %u (want %zu)", w->struct_size, sizeof(ffpa_window));
+  if (w->reserved != 0) return fail(FFPA_ERR_BAD_ABI, "ffpa_window.reserved=%u must be 0", w->reserved);
+  if (w->left < -1 || w->right < -1) return fail(FFPA_ERR_BAD_SHAPE, "window (left=%d, right=%d): each must be >= -1 (-1 = unbounded)", w->left, w->right);
+  return FFPA_OK;
+}
+
+// What a window launch hands the kernel (VarlenArgs::window) and the params its plan is made from.
+struct WindowPlan {
+  int causal;  // the launch runs under the causal flag (right >= 0): `right` rides in the causal limit
+  int right;   // VarlenArgs::win_right
+  int span;    // VarlenArgs::win_span
+  ffpa_varlen_fwd_params priced;  // the caller's params with the causal flag above and max_seqlen_kv = the widest key span a row tile can see
+};
+
+// The window call's plan: the packed call's, PRICED AT WHAT THE WINDOW LEAVES.  A row tile of R token rows (all max_seqlen_q tokens under GQA row packing, else
+// the block rows) walks the keys from its first row's left bound to its last row's right bound — R + left + right of them, and never more than left +
+// max_seqlen_q (the last key is the right bound of the last token) — so the split count ("fill the chip, then balance") and the non-temporal fetch ("K / V bytes
+// with one reader, larger than the Infinity Cache") see that many keys, rounded up to a KV tile, and not the cache's capacity.  No left bound: the caller's
+// max_seqlen_kv.  `left` / `right` at or past the longest sequence are the unbounded side they amount to (they reach the kernel as small ints).
+int window_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, VarlenPlan* pl, WindowPlan* wp) {
+  const bool paged = kv != nullptr;
+  int rc = varlen_plan(p, pl, paged);  // (validates p; the tile rows and the GQA packing do not depend on max_seqlen_kv)
+  if (rc != FFPA_OK) return rc;
+  if (paged && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
+  if ((rc = check_window(w)) != FFPA_OK) return rc;
+  int64_t right = p->causal ? 0 : w->right;
+  if (right > p->max_seqlen_q) right = p->max_seqlen_q;  // (the last token's position + max_seqlen_q - 1 is already the last key)
+  int64_t left = w->left;
+  if (left >= p->max_seqlen_kv) left = -1;  // (no position reaches that far back: positions are below max_seqlen_kv)
+  wp->causal = right >= 0 ? 1 : 0;
+  wp->right = right >= 0 ? (int)right : 0;
+  wp->span = left >= 0 ? (int)(left + wp->right) : -1;
+  wp->priced = *p;
+  wp->priced.causal = wp->causal;
+  if (left >= 0) {
+    const int64_t rows = pl->pack || p->max_seqlen_q < pl->br ? p->max_seqlen_q : pl->br;
+    int64_t tail = right >= 0 ? rows + right : (int64_t)p->max_seqlen_q;
+    if (tail > p->max_seqlen_q) tail = p->max_seqlen_q;
+    const int64_t keys = (left + tail + pl->bc - 1) / pl->bc * pl->bc;
+    if (keys < p->max_seqlen_kv) wp->priced.max_seqlen_kv = (int)keys;
+  }
+  return varlen_plan(&wp->priced, pl, paged);
+}
+
 // The packed call and its paged twin (kv != NULL: k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read); `tree`: under a tree mask
-// (ffpa_attn_varlen_tree_fwd — the causal launch's plan and tile walk; the *_tree_kernel builds, whose element test reads the mask words)
-int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream, const ffpa_tree_mask* tree = nullptr, bool with_tree = false) {
+// (ffpa_attn_varlen_tree_fwd — the causal launch's plan and tile walk; the *_tree_kernel builds, whose element test reads the mask words); `win`: under a sliding
+// window (ffpa_attn_varlen_window_fwd — the window's own plan; the *_window_kernel builds)
+int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream, const ffpa_tree_mask* tree = nullptr, bool with_tree = false,
+                  const ffpa_window* win = nullptr, bool with_win = false) {
   const bool paged = kv != nullptr;
   VarlenPlan pl;
-  int rc = varlen_plan(p, &pl, paged);
+  WindowPlan wp;
+  int rc = with_win ? window_plan(p, kv, win, &pl, &wp) : varlen_plan(p, &pl, paged);
   if (rc != FFPA_OK) return rc;
+  if (with_win) p = &wp.priced;  // (the caller's params but for the causal flag and the length the plan saw; the kernel reads every sequence's own length)
   if (paged && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
   if (with_tree && (rc = check_tree(p, tree)) != FFPA_OK) return rc;
   if (!p->q || !p->k || !p->v || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
@@ -1213,6 +1264,13 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
     va.tree_stride = tree->batch_stride;
     va.tree_tokens = tree->tokens;
   }
+  if (with_win) {
+    // the causal flag as the window says (right >= 0), one packed token per sequence included: its limit is the last key either way, its LEFT bound stays
+    a.causal = wp.causal;
+    va.window = 1;
+    va.win_right = wp.right;
+    va.win_span = wp.span;
+  }
 
   va.compact_tiles = pl.compact;
   va.ws_head_rows = va.ws_split_rows = 0;
@@ -1276,9 +1334,9 @@ size_t workspace_bytes(const ffpa_varlen_fwd_params* params, bool paged) {
   return pl.ws_bytes;
 }
 
-int kernel_name(const ffpa_varlen_fwd_params* params, const VarlenPlan& pl, bool paged, char* buf, size_t n, bool tree = false) {
+int kernel_name(const ffpa_varlen_fwd_params* params, const VarlenPlan& pl, bool paged, char* buf, size_t n, bool tree = false, bool window = false) {
   if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
-  snprintf(buf, n, "ffpa_fwd_m16_%s%s_kernel<%s, %d%s>%s%s", paged ? "paged" : "varlen", tree ? "_tree" : "", params->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d,
+  snprintf(buf, n, "ffpa_fwd_m16_%s%s_kernel<%s, %d%s>%s%s", paged ? "paged" : "varlen", tree ? "_tree" : window ? "_window" : "", params->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d,
            pl.nt ? ", NT" : "", pl.pack ? " (GQA heads packed into rows)" : "", pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
   return FFPA_OK;
 }
@@ -1361,6 +1419,39 @@ int ffpa_attn_varlen_tree_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa
   const int rc = tree_plan(p, kv, tree, &pl);
   if (rc != FFPA_OK) return rc;
   return kernel_name(p, pl, kv != nullptr, buf, n, true);
+}
+
+// ---- the sliding-window call (include/ffpa_attn.h: ffpa_window): the packed call or its paged twin, planned at the window's length (window_plan)
+int ffpa_attn_varlen_window_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, void* stream) {
+  return varlen_launch(p, kv, stream, nullptr, false, w, true);
+}
+
+size_t ffpa_attn_varlen_window_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w) {
+  if (p == nullptr || p->struct_size != sizeof(ffpa_varlen_fwd_params) || w == nullptr || w->struct_size != sizeof(ffpa_window) ||
+      (kv != nullptr && kv->struct_size != sizeof(ffpa_paged_kv)))
+    return 0;
+  // size for the split count the heuristic would pick with unlimited scratch
+  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*p);
+  VarlenPlan pl;
+  WindowPlan wp;
+  if (window_plan(&q, kv, w, &pl, &wp) != FFPA_OK) return 0;
+  return pl.ws_bytes;
+}
+
+int ffpa_attn_varlen_window_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, int out[5]) {
+  VarlenPlan pl;
+  WindowPlan wp;
+  const int rc = window_plan(p, kv, w, &pl, &wp);
+  if (rc != FFPA_OK) return rc;
+  return plan_out(pl, out);
+}
+
+int ffpa_attn_varlen_window_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, char* buf, size_t n) {
+  VarlenPlan pl;
+  WindowPlan wp;
+  const int rc = window_plan(p, kv, w, &pl, &wp);
+  if (rc != FFPA_OK) return rc;
+  return kernel_name(&wp.priced, pl, kv != nullptr, buf, n, false, true);
 }
 
 // ---- the KV-cache append + rotary (include/ffpa_attn.h: ffpa_kv_append_params)

@@ -284,6 +284,13 @@ __device__ __forceinline__ uint32_t m16_tree_nibble(uint64_t word, int first) {
   return first >= 0 ? (uint32_t)(word >> (first & 63)) : (((uint32_t)word << (lead & 7)) | ((1u << (lead & 7)) - 1u));
 }
 
+// Sliding window (VarlenArgs::window): the first KV tile a row tile walks — the tile that holds the left bound `first_row + causal_offset - span` of its first
+// token row (`first_row`: 0 under GQA row packing); span < 0 = no left bound.
+__device__ __forceinline__ int m16_window_first_tile(int first_row, int causal_offset, int span, int bc) {
+  const int64_t lo = (int64_t)first_row + causal_offset - span;
+  return (span >= 0 && lo > 0) ? (int)(lo / bc) : 0;
+}
+
 // LDS images of the K / V tiles: row-major [BC][D], 16-byte slot s of row `key` stored at slot s ^ swizzle(key) (applied on the
 // DMA's per-lane source offset).  K fragments are fetched by ds_read_b128 whose 16-lane groups hold 16 different keys and two
 // neighbouring slots; V^T fragments by ds_read_b64_tr_b16 whose 32-lane halves hold 8 keys x 32 bytes.  Row strides that are whole
@@ -444,6 +451,14 @@ struct VarlenArgs {
   const uint64_t* tree_bits;
   int64_t tree_stride;
   int tree_tokens;
+  // SLIDING WINDOW (ffpa_attn_varlen_window_fwd: FlashAttention's window_size = (left, right), bottom-right aligned): window != 0 = the launch runs the
+  // *_window_kernel builds.  `right` lives in the causal limit: the launch runs under the causal flag with causal_offset = Nkv_i - ntok_i + win_right (right < 0:
+  // no causal flag, win_right = 0), so the upper edge is the causal launch's test as it stands.  win_span >= 0 adds the LEFT edge: token t sees key j only if
+  // j >= t + causal_offset - win_span (win_span = left + win_right; -1 = no left bound).  The row tile's walk starts at the KV tile that holds its first token's
+  // left bound (m16_window_first_tile) and the KV ranges of a split launch share out the tiles from there on.
+  int window;
+  int win_right;
+  int win_span;
 };
 // the tree hook of the tile text for the kernels that carry a VarlenArgs `va` and a sequence index `seq`: the word of a token (whether a kernel tests words at all is
 // a constant of its build: ffpa_fwd_m16_varlen_body.inc; the dense and paired kernels say "no tree")
@@ -454,7 +469,9 @@ struct VarlenArgs {
 template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_varlen_kernel(const FwdArgs a_in, const VarlenArgs va) {
 #define FFPA_M16_VARLEN_TREE false
+#define FFPA_M16_VARLEN_WINDOW false
 #include "ffpa_fwd_m16_varlen_body.inc"
+#undef FFPA_M16_VARLEN_WINDOW
 #undef FFPA_M16_VARLEN_TREE
 }
 
@@ -464,7 +481,20 @@ __global__ __launch_bounds__(256) void ffpa_fwd_m16_varlen_kernel(const FwdArgs 
 template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_varlen_tree_kernel(const FwdArgs a_in, const VarlenArgs va) {
 #define FFPA_M16_VARLEN_TREE true
+#define FFPA_M16_VARLEN_WINDOW false
 #include "ffpa_fwd_m16_varlen_body.inc"
+#undef FFPA_M16_VARLEN_WINDOW
+#undef FFPA_M16_VARLEN_TREE
+}
+
+// ... and under a SLIDING WINDOW (VarlenArgs::window; ffpa_attn_varlen_window_fwd): again a kernel of its own from the same text — the lower tile bound, the
+// left-edge element test and the ranges' share-out are constants of this build, the kernels above are what they were.
+template <typename T, int D, bool NT = false>
+__global__ __launch_bounds__(256) void ffpa_fwd_m16_varlen_window_kernel(const FwdArgs a_in, const VarlenArgs va) {
+#define FFPA_M16_VARLEN_TREE false
+#define FFPA_M16_VARLEN_WINDOW true
+#include "ffpa_fwd_m16_varlen_body.inc"
+#undef FFPA_M16_VARLEN_WINDOW
 #undef FFPA_M16_VARLEN_TREE
 }
 

@@ -1,5 +1,6 @@
 // ffpa_fwd_m16_paged_body.inc — the body of the paged-KV twin of the packed-sequence kernel (ffpa_paged_inst.hip), included once per kernel of that family:
-// ffpa_fwd_m16_paged_kernel (FFPA_M16_VARLEN_TREE false) and ffpa_fwd_m16_paged_tree_kernel (true: under a tree mask, VarlenArgs::tree_bits).  Text moved out of the
+// ffpa_fwd_m16_paged_kernel (FFPA_M16_VARLEN_TREE false) and ffpa_fwd_m16_paged_tree_kernel (true: under a tree mask, VarlenArgs::tree_bits); ffpa_fwd_m16_paged_window_kernel has FFPA_M16_VARLEN_WINDOW true (a sliding
+// window, VarlenArgs::window: the walk — and the page lookahead — start at the row tile's first windowed tile).  Text moved out of the
 // kernel, nothing changed.
   constexpr int MK = 0;  // no attn_bias, no mask ranges
   constexpr bool DROP = false;
@@ -68,7 +69,11 @@
 #define FFPA_M16_O_ROW_OFF(row) (va.pack ? (int64_t)((row) / ntok) * a.so[2] + (int64_t)((row) % ntok) * va.o_tok_stride : (int64_t)(row) * a.so[2])
 #define FFPA_M16_TREE_ON FFPA_M16_VARLEN_TREE
 #define FFPA_M16_TREE_WORD(tok, pin) FFPA_M16_VARLEN_TREE_WORD(tok, pin)
+#define FFPA_M16_WINDOW_ON FFPA_M16_VARLEN_WINDOW
+#define FFPA_M16_WINDOW_SPAN va.win_span
 #include "ffpa_fwd_m16_tile.inc"
+#undef FFPA_M16_WINDOW_SPAN
+#undef FFPA_M16_WINDOW_ON
 #undef FFPA_M16_TREE_WORD
 #undef FFPA_M16_TREE_ON
 #undef FFPA_M16_O_ROW_OFF

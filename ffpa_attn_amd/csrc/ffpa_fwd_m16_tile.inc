@@ -11,6 +11,15 @@
 // with causal_offset = Nkv - tokens: every loop bound is the causal launch's), FFPA_M16_TREE_WORD(t, pin) = the 64-bit word of token t — bit j set = the token sees key
 // causal_offset + j; `pin` is a scalar zero the compiler cannot see through, added to the sequence index so that the word's address is computed where it is used.  Only the element test of the tiles that hold a key >= causal_offset differs (the two `tail || diag` branches below): the word is loaded inside
 // that branch and dies there.  The dense and paired kernels define "no tree" (false / 0ull): the branch folds to the text that stood here.
+// A SLIDING WINDOW is the enclosing kernel's too: FFPA_M16_WINDOW_ON = a constant of its build, FFPA_M16_WINDOW_SPAN = the span (VarlenArgs::win_span): row `crow`
+// sees key j only if j >= crow + causal_offset - span (span < 0: no left bound; the right edge is the causal limit, into which the launch folded `right`).  Three
+// places read it: the tile range below (the walk starts at the tile of the first row's left bound), and the two `tail || diag` branches, which a tile that starts in
+// front of the left bound of the wave's LAST row takes as well.  Kernels that do not define the hooks have no window: everything folds to the text that stood here.
+#ifndef FFPA_M16_WINDOW_ON
+#define FFPA_M16_WINDOW_ON false
+#define FFPA_M16_WINDOW_SPAN (-1)
+#define FFPA_M16_WINDOW_DEFAULT_HOOKS
+#endif
 #ifndef FFPA_M16_KV_SRC
 #define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) tile_src<BC>(slice, row_bytes, key0, a.Nkv, rb_valid)
 #define FFPA_M16_KV_BEGIN(t0_)
@@ -171,9 +180,15 @@
     nt = nt < ntc ? nt : ntc;
   }
   int t0 = split * a.tiles_per_split;
+  if (FFPA_M16_WINDOW_ON) t0 += m16_window_first_tile(a.causal_row_mod ? 0 : q0, a.causal_offset, FFPA_M16_WINDOW_SPAN, BC);  // (a split launch's ranges start there too)
   {
     const int t1 = t0 + a.tiles_per_split;
     nt = nt < t1 ? nt : t1;
+  }
+  if (FFPA_M16_WINDOW_ON) {
+    // (wave-uniform by construction; pinned to scalar registers: they feed the tile descriptors of the LDS-DMA asm)
+    t0 = __builtin_amdgcn_readfirstlane(t0);
+    nt = __builtin_amdgcn_readfirstlane(nt);
   }
   // mask ranges (ffpa_fwd_params.kv_bounds): KV tiles no row of this row tile can see are skipped; keys [free_lo, free_hi) are
   // visible to EVERY row of this wave's 32-row block — tiles inside that range do not read the mask at all
@@ -528,6 +543,9 @@
         const bool diag = !tree && a.causal && ((int64_t)k0 + BC - 1 > (int64_t)(a.causal_row_mod ? 0 : wq0) + a.causal_offset);
         // (a tree mask: every tile that holds a draft key or ends past the last key — draft key 0 itself is subject to the mask, so >= where the causal test has >)
         const bool tree_tile = tree && (tail || (int64_t)k0 + BC - 1 >= (int64_t)a.causal_offset);
+        // (a sliding window: the tile starts in front of the left bound of the wave's last row — rows of a packed tile are (head, token): its last token's)
+        const bool ledge = FFPA_M16_WINDOW_ON && FFPA_M16_WINDOW_SPAN >= 0 &&
+                           (int64_t)k0 < (int64_t)(a.causal_row_mod ? a.causal_row_mod - 1 : wq0 + 31) + a.causal_offset - FFPA_M16_WINDOW_SPAN;
         // one group of the softmax's instructions per MFMA gap: g = 2 * fragment + (0: behind the first, 1: behind the second MFMA)
         auto softmax_gap = [&](auto gc) __attribute__((always_inline)) {
           constexpr int g = decltype(gc)::value;
@@ -583,15 +601,16 @@
                 __builtin_amdgcn_sched_barrier(0);  // (one key block at a time: interleaved, the blocks' temporaries add up at the kernel's register peak)
               }
             }
-            if ((tail && !tree) || diag) {
+            if ((tail && !tree) || diag || ledge) {
               const int crow = a.causal_row_mod ? qrow_own % a.causal_row_mod : qrow_own;
               const int64_t lim = a.causal ? (int64_t)crow + a.causal_offset : (int64_t)a.Nkv;
+              const int64_t wlo = FFPA_M16_WINDOW_ON && FFPA_M16_WINDOW_SPAN >= 0 ? (int64_t)crow + a.causal_offset - FFPA_M16_WINDOW_SPAN : 0;  // (keys are >= 0)
 #pragma unroll
               for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                   const int key = k0 + kb * 16 + 4 * c + r;
-                  if (key >= a.Nkv || key > lim) x[kb][r] = -INFINITY;
+                  if (key >= a.Nkv || key > lim || (FFPA_M16_WINDOW_ON && key < wlo)) x[kb][r] = -INFINITY;
                 }
             }
           } else if constexpr (g == 8) {  // row max, this lane's 8 keys (same order as the loop below)
@@ -1022,17 +1041,21 @@
         }
       }
     }
-    if ((tail && !tree) || diag) {
+    // (a sliding window: the tile starts in front of the left bound of the wave's last row — rows of a packed tile are (head, token): its last token's)
+    const bool ledge = FFPA_M16_WINDOW_ON && FFPA_M16_WINDOW_SPAN >= 0 &&
+                       (int64_t)k0 < (int64_t)(a.causal_row_mod ? a.causal_row_mod - 1 : wq0 + 31) + a.causal_offset - FFPA_M16_WINDOW_SPAN;
+    if ((tail && !tree) || diag || ledge) {
 #pragma unroll
       for (int rh = 0; rh < RHS; ++rh) {
         const int crow = a.causal_row_mod ? qrow_s[rh] % a.causal_row_mod : qrow_s[rh];
         const int64_t lim = a.causal ? (int64_t)crow + a.causal_offset : (int64_t)a.Nkv;
+        const int64_t wlo = FFPA_M16_WINDOW_ON && FFPA_M16_WINDOW_SPAN >= 0 ? (int64_t)crow + a.causal_offset - FFPA_M16_WINDOW_SPAN : 0;  // (keys are >= 0)
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = k0 + kb * 16 + 4 * c + r;
-            if (key >= a.Nkv || key > lim) x[kb][rh][r] = -INFINITY;
+            if (key >= a.Nkv || key > lim || (FFPA_M16_WINDOW_ON && key < wlo)) x[kb][rh][r] = -INFINITY;
           }
       }
     }
@@ -1347,6 +1370,11 @@
     }
 #endif
   }
+#ifdef FFPA_M16_WINDOW_DEFAULT_HOOKS
+#undef FFPA_M16_WINDOW_DEFAULT_HOOKS
+#undef FFPA_M16_WINDOW_SPAN
+#undef FFPA_M16_WINDOW_ON
+#endif
 #ifdef FFPA_M16_KV_DEFAULT_HOOKS
 #undef FFPA_M16_KV_DEFAULT_HOOKS
 #undef FFPA_M16_KV_STEP_END

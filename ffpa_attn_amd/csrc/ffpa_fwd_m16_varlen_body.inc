@@ -1,6 +1,7 @@
 // ffpa_fwd_m16_varlen_body.inc — the body of the packed-sequence kernel (ffpa_fwd_m16_kernel.h), included once per kernel of that family: ffpa_fwd_m16_varlen_kernel
 // (FFPA_M16_VARLEN_TREE false: the tree hooks of the tile text fold away, the kernel is what it was) and ffpa_fwd_m16_varlen_tree_kernel (true: the element test of
-// the tiles that hold a draft key reads VarlenArgs::tree_bits).  Text moved out of the kernel, nothing changed.
+// the tiles that hold a draft key reads VarlenArgs::tree_bits) and ffpa_fwd_m16_varlen_window_kernel (FFPA_M16_VARLEN_WINDOW true: the tile range, the element test and
+// the KV ranges' share-out take a sliding window, VarlenArgs::window).  Text moved out of the kernel, nothing changed.
   constexpr int MK = 0;  // no attn_bias, no mask ranges: what the reference's packed entry point accepts
   constexpr bool DROP = false;
 #define FFPA_M16_MFMA std::conditional_t<NT, Mfma16Nt<T>, Mfma16<T>>
@@ -18,7 +19,11 @@
 #define FFPA_M16_O_ROW_OFF(row) (va.pack ? (int64_t)((row) / ntok) * a.so[2] + (int64_t)((row) % ntok) * va.o_tok_stride : (int64_t)(row) * a.so[2])
 #define FFPA_M16_TREE_ON FFPA_M16_VARLEN_TREE
 #define FFPA_M16_TREE_WORD(tok, pin) FFPA_M16_VARLEN_TREE_WORD(tok, pin)
+#define FFPA_M16_WINDOW_ON FFPA_M16_VARLEN_WINDOW
+#define FFPA_M16_WINDOW_SPAN va.win_span
 #include "ffpa_fwd_m16_tile.inc"
+#undef FFPA_M16_WINDOW_SPAN
+#undef FFPA_M16_WINDOW_ON
 #undef FFPA_M16_TREE_WORD
 #undef FFPA_M16_TREE_ON
 #undef FFPA_M16_O_ROW_OFF

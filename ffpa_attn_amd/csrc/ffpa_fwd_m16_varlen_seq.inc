@@ -1,6 +1,7 @@
 // ffpa_fwd_m16_varlen_seq.inc — the sequence lookup of the packed-sequence kernels (ffpa_fwd_m16_varlen_kernel, ffpa_fwd_m16_kernel.h; its paged twin
 // ffpa_fwd_m16_paged_kernel, ffpa_paged_inst.hip): workgroup -> (KV range, sequence, row tile, head), the sequence's FwdArgs `a` and its KV split.  Text moved out
-// of the kernel, nothing changed; under FFPA_M16_PAGED the keys' length is seqused_k's (clamped to the block table's row) and K / V keep the pool's base.
+// of the kernel, nothing changed; FFPA_M16_VARLEN_WINDOW (a constant of the enclosing kernel's build) = a sliding window: `right` joins the causal offset and the KV
+// ranges share out the tiles from the window's first one on; under FFPA_M16_PAGED the keys' length is seqused_k's (clamped to the block table's row) and K / V keep the pool's base.
   int vid = blockIdx.x;
   if (!(a_in.flags & kFlagNoXcdRemap)) vid = xcd_logical_id(vid, gridDim.x, a_in.xcd_group);
   int split = 0;
@@ -99,6 +100,7 @@
     a.Nq = nq_seq;
     a.Nkv = nkv_seq > 0 ? nkv_seq : 0;
     a.causal_offset = a.Nkv - ntok_seq;  // (tail-aligned per sequence; a single packed token runs without the causal flag — it sees every key of its sequence)
+    if (FFPA_M16_VARLEN_WINDOW) a.causal_offset += va.win_right;  // (a sliding window's `right` rides in the causal limit: VarlenArgs::window)
     if (va.pack) a.causal_row_mod = ntok_seq;
     if (a_in.nsplit > 1 && (int64_t)q_lo + ntok_seq > va.ws_head_rows) return;  // (a caller whose total_q is smaller than its boundaries say: nothing is stored outside the scratch it sized)
     a.q = (const T*)a_in.q + (int64_t)q_lo * va.q_tok_stride;
@@ -117,6 +119,11 @@
       const int64_t last = (int64_t)last_row + a.causal_offset;
       const int ntc = last < 0 ? 0 : (int)(last / BC) + 1;
       tiles = tiles < ntc ? tiles : ntc;
+    }
+    if (FFPA_M16_VARLEN_WINDOW) {
+      // under a sliding window the row tile's walk starts at the tile of its first row's left bound (the tile text, restated): the ranges share out [t_lo, tiles)
+      tiles -= m16_window_first_tile(a.causal_row_mod ? 0 : qt * BR, a.causal_offset, va.win_span, BC);
+      tiles = tiles > 0 ? tiles : 0;
     }
     a.tiles_per_split = (tiles + a_in.nsplit - 1) / a_in.nsplit;  // (fewer tiles than ranges leaves ranges empty: dead partials, weight 0 in the merge)
   }

@@ -42,7 +42,9 @@ __device__ __forceinline__ TileSrc tile_src_at(const char* tile_base, uint32_t r
 template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_paged_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa) {
 #define FFPA_M16_VARLEN_TREE false
+#define FFPA_M16_VARLEN_WINDOW false
 #include "ffpa_fwd_m16_paged_body.inc"
+#undef FFPA_M16_VARLEN_WINDOW
 #undef FFPA_M16_VARLEN_TREE
 }
 
@@ -50,7 +52,20 @@ __global__ __launch_bounds__(256) void ffpa_fwd_m16_paged_kernel(const FwdArgs a
 template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_paged_tree_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa) {
 #define FFPA_M16_VARLEN_TREE true
+#define FFPA_M16_VARLEN_WINDOW false
 #include "ffpa_fwd_m16_paged_body.inc"
+#undef FFPA_M16_VARLEN_WINDOW
+#undef FFPA_M16_VARLEN_TREE
+}
+
+// ... and under a SLIDING WINDOW (ffpa_attn_varlen_window_fwd with a pool), as ffpa_fwd_m16_varlen_window_kernel: the page lookahead starts at the row tile's
+// first walked tile (FFPA_M16_KV_BEGIN takes any tile), so the pages in front of the window are never looked up
+template <typename T, int D, bool NT = false>
+__global__ __launch_bounds__(256) void ffpa_fwd_m16_paged_window_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa) {
+#define FFPA_M16_VARLEN_TREE false
+#define FFPA_M16_VARLEN_WINDOW true
+#include "ffpa_fwd_m16_paged_body.inc"
+#undef FFPA_M16_VARLEN_WINDOW
 #undef FFPA_M16_VARLEN_TREE
 }
 
@@ -59,6 +74,7 @@ static int launch_paged(const FwdArgs& a, const VarlenArgs& va, const PagedArgs&
   constexpr int BC = m16_block_keys(D, true);
   constexpr int LDS = 2 * BC * D * 2 + m16_exchange_bytes(D, 0);
   if (va.tree_tokens != 0) return launch_kernel<ffpa_fwd_m16_paged_tree_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa);  // (under a tree mask: its own build)
+  if (va.window != 0) return launch_kernel<ffpa_fwd_m16_paged_window_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa);  // (under a sliding window: its own build)
   return launch_kernel<ffpa_fwd_m16_paged_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa);
 }
 

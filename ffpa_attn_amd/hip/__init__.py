@@ -188,6 +188,17 @@ class FfpaTreeMask(ctypes.Structure):
   ]
 
 
+class FfpaWindow(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_window`` (include/ffpa_attn.h): the (left, right) of the sliding-window call."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("left", ctypes.c_int32),
+    ("right", ctypes.c_int32),
+  ]
+
+
 class FfpaKvAppendParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_kv_append_params`` (include/ffpa_attn.h): the KV-cache append + rotary call."""
 
@@ -258,8 +269,10 @@ _P = ctypes.POINTER
 _INT, _SIZE, _VOID, _STR = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_char_p
 _VARLEN, _PAGED = [_P(FfpaVarlenFwdParams)], [_P(FfpaVarlenFwdParams), _P(FfpaPagedKv)]
 _TREE = _PAGED + [_P(FfpaTreeMask)]
+_WINDOW = _PAGED + [_P(FfpaWindow)]
 # Every function include/ffpa_attn.h declares: (symbol, argtypes, restype, since).  ``since``: the ABI version that added it (0: there from the start) — the
-# default library has them all; one loaded by path (developer A/B runs load a saved build of an older commit) may lack those with since > 0.
+# default library has them all; one loaded by path or through FFPA_HIP_LIBRARY (developer A/B runs load a saved build of an older commit) may lack those with
+# since > 0: calling one of those is then an AttributeError.
 _BINDINGS = (
   ("ffpa_attn_fwd", [_P(FfpaFwdParams), _VOID], _INT, 0),
   ("ffpa_attn_fwd_workspace_bytes", [_P(FfpaFwdParams)], _SIZE, 0),
@@ -279,6 +292,10 @@ _BINDINGS = (
   ("ffpa_attn_varlen_tree_fwd_plan", _TREE + [_P(_INT)], _INT, 7),
   ("ffpa_attn_varlen_tree_fwd_kernel", _TREE + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_tree_fwd_workspace_bytes", _TREE, _SIZE, 7),
+  ("ffpa_attn_varlen_window_fwd", _WINDOW + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_window_fwd_plan", _WINDOW + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_window_fwd_kernel", _WINDOW + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_window_fwd_workspace_bytes", _WINDOW, _SIZE, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
   ("ffpa_attn_query", [_INT], _INT, 0),
@@ -306,8 +323,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "kernel): build it with `python -m ffpa_attn_amd.build` (needs hipcc, targets gfx950)."
       )
     lib = ctypes.CDLL(p)
+    named = path is not None or p != LIB_PATH  # (a library named by the caller or by FFPA_HIP_LIBRARY: a saved build of an older commit binds what it has)
     for symbol, argtypes, restype, since in _BINDINGS:
-      if path is not None and since > 0 and not hasattr(lib, symbol):
+      if named and since > 0 and not hasattr(lib, symbol):
         continue
       fn = getattr(lib, symbol)
       fn.argtypes, fn.restype = argtypes, restype
@@ -368,10 +386,10 @@ def __getattr__(name: str):
 # ---- what every call of the library does, once: a stamped parameter struct, the status -> exception raise, the call on the current stream, the scratch hand-over,
 # the plan read-out.  Plain functions: ``forward`` / ``varlen_forward`` run once per decoded token.
 def _stamped(cls):
-  """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` ride next to a versioned struct), the ABI version — filled in."""
+  """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` / ``ffpa_window`` ride next to a versioned struct), the ABI version — filled in."""
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
-  if cls not in (FfpaPagedKv, FfpaTreeMask):
+  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow):
     p.abi_version = ABI_VERSION
   return p
 
@@ -1002,11 +1020,11 @@ def _paged_kv_of(block_table: torch.Tensor, k: torch.Tensor, v: torch.Tensor) ->
   return _paged_kv(block_table.data_ptr(), block_table.stride(0), block_table.size(1), k.size(1), k.size(0), k.stride(0), v.stride(0)), block_table
 
 
-def _varlen_fn(lib, kv: "FfpaPagedKv | None", suffix: str = "", tree: bool = False):
-  """The packed call's export — or, with ``kv``, its paged twin's; with ``tree``, the tree call's (one export for both: its ``kv`` may be NULL) — of this suffix
-  ("" the launch, "_plan", "_kernel", "_workspace_bytes")"""
+def _varlen_fn(lib, kv: "FfpaPagedKv | None", suffix: str = "", tree: "bool | str" = False):
+  """The packed call's export — or, with ``kv``, its paged twin's; with ``tree``, the tree call's, with ``tree == "window"`` the window call's (one export for
+  both caches: their ``kv`` may be NULL) — of this suffix ("" the launch, "_plan", "_kernel", "_workspace_bytes")"""
   if tree:
-    return getattr(lib, "ffpa_attn_varlen_tree_fwd" + suffix)
+    return getattr(lib, ("ffpa_attn_varlen_window_fwd" if tree == "window" else "ffpa_attn_varlen_tree_fwd") + suffix)
   return getattr(lib, ("ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd") + suffix)
 
 
@@ -1014,11 +1032,12 @@ def _varlen_fn(lib, kv: "FfpaPagedKv | None", suffix: str = "", tree: bool = Fal
 _VARLEN_SCRATCH: "dict[tuple, int]" = {}
 
 
-def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaPagedKv | None", args: tuple, tree: bool = False) -> int:
+def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaPagedKv | None", args: tuple, tree: "bool | str" = False,
+                    window: "tuple | None" = None) -> int:
   if p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC:
     return 0
   key = (id(lib), device_index, p.dtype, p.batch, p.heads_q, p.heads_kv, p.head_dim, p.max_seqlen_q, p.max_seqlen_kv, p.total_q, p.causal, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS"),
-         kv is not None, tree)
+         kv is not None, tree, window)
   hit = _VARLEN_SCRATCH.get(key)
   if hit is None:
     if len(_VARLEN_SCRATCH) >= 512:
@@ -1030,7 +1049,7 @@ def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaP
 def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: "torch.Tensor | None", max_seqlen_q: int,
                    max_seqlen_k: int, causal: bool, softmax_scale: float, *, rescale_threshold: float = -1.0, return_lse: bool = True, flags: int = 0,
                    plan_out: "dict | None" = None, seqused_k: "torch.Tensor | None" = None, num_splits: int = 0, block_table: "torch.Tensor | None" = None,
-                   tree_words: "torch.Tensor | None" = None):
+                   tree_words: "torch.Tensor | None" = None, window: "tuple[int, int] | None" = None):
   """One launch of the packed-sequence kernel: ``q [T_q, Hq, D]``, ``k`` / ``v [T_k, Hkv, D]``, int32 device ``cu_seqlens_*`` ``[B + 1]`` ->
   ``(o [T_q, Hq, D], lse [Hq, T_q] fp32 | None)``.  Nothing is read back to the host and nothing synchronises: the call captures into a HIP graph.
   Rows without a visible key: O = 0, LSE = -inf.
@@ -1051,10 +1070,18 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
 
   ``tree_words`` (int64 device ``[B | 1, tokens]``, ``max_seqlen_q <= tokens <= 64``; ``tree_forward`` is this call with it): a TREE MASK over the last keys of
   every sequence (``ffpa_attn_varlen_tree_fwd``) — token t of sequence i sees every key in front of its sequence's last ``ntok_i`` keys and, of those, key j iff
-  bit j of ``tree_words[i, t]`` is set; ``causal`` is ignored.  The same kernel and plan as the causal launch; a replay follows words written in place."""
+  bit j of ``tree_words[i, t]`` is set; ``causal`` is ignored.  The same kernel and plan as the causal launch; a replay follows words written in place.
+
+  ``window`` (``(left, right)``, ints >= -1, -1 = unbounded; ``window_forward`` is this call with it): a SLIDING WINDOW (``ffpa_attn_varlen_window_fwd``) — token t
+  of sequence i, at position ``pos = t + L_i - ntok_i``, sees key j iff ``pos - left <= j <= pos + right``; ``causal`` means ``right = 0``.  The KV tiles in front
+  of a row tile's window are not read, and the plan prices the window's keys instead of ``max_seqlen_k``."""
   paged = block_table is not None
   tree = tree_words is not None
-  name = "ffpa_attn::_tree_fwd_hip" if tree else "ffpa_attn::_paged_fwd_hip" if paged else "ffpa_attn::_varlen_fwd_hip"
+  if window is not None:
+    if tree:
+      raise ValueError("ffpa_attn::_window_fwd_hip: a window and a tree mask do not combine")
+    tree = "window"  # (which export family the helpers below pick)
+  name = "ffpa_attn::_window_fwd_hip" if window is not None else "ffpa_attn::_tree_fwd_hip" if tree else "ffpa_attn::_paged_fwd_hip" if paged else "ffpa_attn::_varlen_fwd_hip"
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
@@ -1096,7 +1123,13 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
   if k.device != q.device or v.device != q.device:
     raise ValueError(f"{name}: q/k/v must be on one device, got {q.device}, {k.device}, {v.device}")
   Tq, Hq, D = q.shape
-  if tree:
+  if window is not None:
+    if not isinstance(window, (tuple, list)) or len(window) != 2 or not all(isinstance(x, int) and not isinstance(x, bool) for x in window):
+      raise TypeError(f"{name}: window must be a pair of ints (left, right), got {window!r}")
+    if min(window) < -1 or max(window) > 0x7FFFFFFF:
+      raise ValueError(f"{name}: window (left, right) = {tuple(window)}: each must be >= -1 (-1 = unbounded)")
+    window = (int(window[0]), int(window[1]))
+  elif tree:
     if not isinstance(tree_words, torch.Tensor) or tree_words.dtype != torch.int64 or tree_words.dim() != 2 or tree_words.device != q.device:
       raise ValueError(f"{name}: tree_words must be a 2-D int64 tensor [batch or 1, tokens] on q's device")
     if tree_words.size(0) not in (1, cu_seqlens_q.numel() - 1) or not max(int(max_seqlen_q), 1) <= tree_words.size(1) <= 64:
@@ -1130,19 +1163,23 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
   if paged:
     kv, block_table = _paged_kv_of(block_table, k, v)
     args = (ctypes.byref(p), ctypes.byref(kv))
-  if tree:
+  if window is not None:
+    wn = _stamped(FfpaWindow)
+    wn.left, wn.right = window
+    args = (ctypes.byref(p), ctypes.byref(kv) if paged else None, ctypes.byref(wn))
+  elif tree:
     tm = _stamped(FfpaTreeMask)
     tm.bits, tm.tokens = tree_words.data_ptr(), tree_words.size(1)
     tm.batch_stride = tree_words.stride(0) if tree_words.size(0) > 1 else 0
     args = (ctypes.byref(p), ctypes.byref(kv) if paged else None, ctypes.byref(tm))
   with torch.cuda.device(q.device):
     stream = torch.cuda.current_stream(q.device).cuda_stream
-    workspace = _hand_over_workspace(p, q.device, stream, _varlen_scratch(lib, p, q.device.index or 0, kv, args, tree))  # (held in a local until the launch below has been enqueued)
+    workspace = _hand_over_workspace(p, q.device, stream, _varlen_scratch(lib, p, q.device.index or 0, kv, args, tree, window))  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
       plan_out.update(_read_plan(lib, _varlen_fn(lib, kv, "_plan", tree), _varlen_fn(lib, kv, "_kernel", tree), _VARLEN_PLAN_KEYS, args))
     rc = _varlen_fn(lib, kv, "", tree)(*args, ctypes.c_void_p(stream))
   if rc != 0:
-    _raise_status(lib, rc, "ffpa_attn_varlen_tree_fwd" if tree else "ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd")
+    _raise_status(lib, rc, "ffpa_attn_varlen_window_fwd" if window is not None else "ffpa_attn_varlen_tree_fwd" if tree else "ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd")
   return _unpad_head_dim(o, D), lse
 
 
@@ -1159,13 +1196,26 @@ def tree_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q
                         tree_words=tree_words)
 
 
+def window_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: "torch.Tensor | None", max_seqlen_q: int,
+                   max_seqlen_k: int, causal: bool, softmax_scale: float, window: "tuple[int, int]", *, rescale_threshold: float = -1.0, return_lse: bool = True,
+                   flags: int = 0, plan_out: "dict | None" = None, seqused_k: "torch.Tensor | None" = None, num_splits: int = 0,
+                   block_table: "torch.Tensor | None" = None):
+  """One launch of the packed-sequence kernel (``block_table``: of its paged twin) under a SLIDING WINDOW (``ffpa_attn_varlen_window_fwd``; ``varlen_forward``'s
+  ``window``).  ``flags`` / ``plan_out`` as ``varlen_forward`` (tests force or inspect the launch)."""
+  if window is None:
+    raise ValueError("ffpa_attn::_window_fwd_hip: window is required")
+  return varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, rescale_threshold=rescale_threshold,
+                        return_lse=return_lse, flags=flags, plan_out=plan_out, seqused_k=seqused_k, num_splits=num_splits, block_table=block_table,
+                        window=window)
+
+
 def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: int, max_seqlen_k: int, head_dim: int, *,
                        dtype: torch.dtype = torch.bfloat16, causal: bool = False, flags: int = 0, total_q: int = 0, num_splits: int = 0,
-                       page_size: int = 0) -> dict:
+                       page_size: int = 0, window: "tuple[int, int] | None" = None) -> dict:
   """The packed-sequence launch for a shape class, without launching (placeholder pointers): row tiles per (sequence, head), tile, workgroups, KV ranges per
   sequence, kernel name.  ``total_q`` (rows of q) > 0: the plan of a call that hands the library its scratch (``varlen_forward`` does) — KV splits included;
   0: the plan without scratch (never split).  ``page_size`` > 0: the paged call's plan (``ffpa_attn_varlen_paged_fwd``, a table of one page per sequence row
-  covering max_seqlen_k)."""
+  covering max_seqlen_k).  ``window`` = (left, right): the sliding-window call's plan (``ffpa_attn_varlen_window_fwd``), priced at the window's keys."""
   lib = load_library()
   d8 = (int(head_dim) + 7) // 8 * 8
   strides = [(h * d8, d8) for h in (heads_q, heads_kv, heads_kv, heads_q)]
@@ -1180,7 +1230,12 @@ def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: in
     pages_per_row = max(1, -(-int(max_seqlen_k) // int(page_size)))
     kv = _paged_kv(16, pages_per_row, pages_per_row, int(page_size), int(batch) * pages_per_row, int(page_size) * heads_kv * d8, int(page_size) * heads_kv * d8)
     args = (ctypes.byref(p), ctypes.byref(kv))
-  out = _read_plan(lib, _varlen_fn(lib, kv, "_plan"), _varlen_fn(lib, kv, "_kernel"), _VARLEN_PLAN_KEYS, args, strict=True)
+  fam = False
+  if window is not None:
+    wn = _stamped(FfpaWindow)
+    wn.left, wn.right = int(window[0]), int(window[1])
+    args, fam = (ctypes.byref(p), ctypes.byref(kv) if kv is not None else None, ctypes.byref(wn)), "window"
+  out = _read_plan(lib, _varlen_fn(lib, kv, "_plan", fam), _varlen_fn(lib, kv, "_kernel", fam), _VARLEN_PLAN_KEYS, args, strict=True)
   if total_q <= 0:
     del out["splits"]
   return out
@@ -1243,6 +1298,28 @@ def _tree_fwd_hip_torch_op(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_tree_fwd_hip")
 def _tree_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, tree_words, max_seqlen_q, max_seqlen_k, softmax_scale,
                        rescale_threshold=-1.0, num_splits=0):
+  total_q, heads, head_dim = q.shape
+  return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
+
+
+# The sliding-window call (ffpa_attn_with_kvcache_window): one op for both caches, shaped like the tree call's — ``block_table`` None = the contiguous cache
+torch.library.define(
+  f"{_OP_NAMESPACE}::_window_fwd_hip",
+  "(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor? cu_seqlens_k, Tensor seqused_k, Tensor? block_table, int window_left, int window_right, "
+  "int max_seqlen_q, int max_seqlen_k, float softmax_scale, int causal, float rescale_threshold=-1.0, int num_splits=0) -> (Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_window_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _window_fwd_hip_torch_op(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, window_left, window_right, max_seqlen_q, max_seqlen_k, softmax_scale,
+                             causal, rescale_threshold=-1.0, num_splits=0):
+  return window_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, bool(causal), softmax_scale, (int(window_left), int(window_right)),
+                        rescale_threshold=rescale_threshold, return_lse=True, seqused_k=seqused_k, num_splits=num_splits, block_table=block_table)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_window_fwd_hip")
+def _window_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, window_left, window_right, max_seqlen_q, max_seqlen_k, softmax_scale,
+                         causal, rescale_threshold=-1.0, num_splits=0):
   total_q, heads, head_dim = q.shape
   return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
 

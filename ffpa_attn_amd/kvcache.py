@@ -11,7 +11,10 @@ same stream in front of the attention launch (``ffpa_attn::_kvcache_append_hip``
 position ``cache_seqlens[b] + i`` (K rotated), the rotated copy of q, and the lengths ``cache_seqlens + Snew`` the attention launch reads.  Still no host
 synchronisation: the two launches capture into one HIP graph.  ``cache_seqlens`` itself is not advanced (the caller does that, as with FlashAttention).
 
-Inference only: ``cache_batch_idx``, ``cache_leftpad``, local windows, softcap and ALiBi have no kernel-side implementation here and raise
+Local (sliding-window) attention has an entry of its own, ``ffpa_attn_with_kvcache_window`` (``window_size=(left, right)``, below): the KV tiles in front of
+the window are not read.  ``ffpa_attn_with_kvcache`` itself keeps refusing ``window_size``.
+
+Inference only: ``cache_batch_idx``, ``cache_leftpad``, softcap and ALiBi have no kernel-side implementation here and raise
 ``NotImplementedError`` naming the option — as do ``k`` without ``v`` (or ``v`` without ``k``) and rotary tables without ``k`` / ``v`` or one without the other;
 a tensor that requires grad raises (there is no backward).
 """
@@ -323,6 +326,79 @@ def ffpa_attn_with_kvcache_tree(
     kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
     cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
   o, lse = torch.ops.ffpa_attn._tree_fwd_hip(qp, kp, vp, cu_q, cu_k, seqused, block_table, words, Sq, capacity, scale, -1.0, num_splits)
+  out = o.view(B, Sq, Hq, D)
+  if not return_softmax_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+# ---- sliding-window (local) attention: ffpa_attn_with_kvcache_window
+def _window_pair(window_size) -> "tuple[int, int]":
+  """``window_size`` of ffpa_attn_with_kvcache_window -> (left, right): a pair of ints >= -1."""
+  name = "ffpa_attn_with_kvcache_window"
+  if not isinstance(window_size, (tuple, list)) or len(window_size) != 2:
+    raise TypeError(f"{name}: window_size must be a pair of ints (left, right), got {window_size!r}")
+  for x in window_size:
+    if isinstance(x, bool) or not isinstance(x, int):
+      raise TypeError(f"{name}: window_size must be a pair of ints (left, right), got {window_size!r}")
+  left, right = int(window_size[0]), int(window_size[1])
+  if left < -1 or right < -1:
+    raise ValueError(f"{name}: window_size = ({left}, {right}): each side must be >= -1 (-1 = unbounded)")
+  return min(left, 0x7FFFFFFF), min(right, 0x7FFFFFFF)
+
+
+def ffpa_attn_with_kvcache_window(
+  q: torch.Tensor,
+  k_cache: torch.Tensor,
+  v_cache: torch.Tensor,
+  k: torch.Tensor | None = None,
+  v: torch.Tensor | None = None,
+  rotary_cos: torch.Tensor | None = None,
+  rotary_sin: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor | None" = None,
+  block_table: torch.Tensor | None = None,
+  *,
+  window_size: tuple,
+  softmax_scale: float | None = None,
+  causal: bool = False,
+  rotary_interleaved: bool = True,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+):
+  """``ffpa_attn_with_kvcache`` under a SLIDING WINDOW — the local attention layers of Mistral, Gemma 2 / 3, Phi-3 and the long-context hybrids; FlashAttention's
+  ``window_size``.  ONE attention launch of the packed / paged kernel's window build: a row tile walks only the KV tiles between the left bound of its first token
+  and the right bound of its last one — the tiles, and the pages, in front of the window are never read, which on a decode step is the whole cost —, and the launch
+  plan (KV splits, the non-temporal fetch) is made for the window's keys, not the cache's capacity.
+
+  Shapes, dtypes, layouts, strides, paged or contiguous caches, GQA, the append of ``k`` / ``v`` with ``rotary_cos`` / ``rotary_sin``, ``num_splits`` and the returns
+  are ``ffpa_attn_with_kvcache``'s.  ``window_size = (left, right)``, ints >= -1 with -1 = unbounded on that side (``TypeError`` for anything but a pair of ints,
+  ``ValueError`` below -1).  With ``L_b`` the keys attention runs over (``min(cache_seqlens[b] + Snew, capacity)`` with ``k`` / ``v``, else ``cache_seqlens[b]``
+  clamped to the capacity) and ``pos_i = i + L_b - Sq`` the position of query token i (bottom-right aligned), token i sees key j iff
+
+  * ``0 <= j < L_b``,
+  * ``left < 0 or j >= pos_i - left``,
+  * ``right < 0 or j <= pos_i + right``.
+
+  ``causal=True`` means ``right = 0`` whatever ``right`` was given.  ``(-1, -1)`` is ``ffpa_attn_with_kvcache`` and ``(-1, 0)`` its causal call, to the bit (bf16).
+  A row that sees no key returns O = 0, LSE = -inf.  Nothing is read back to the host: the call captures into one HIP graph, and a replay follows
+  ``cache_seqlens`` / ``block_table`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``."""
+  if window_size is None:
+    raise TypeError("ffpa_attn_with_kvcache_window: window_size must be a pair of ints (left, right), got None")
+  left, right = _window_pair(window_size)
+  capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, None, None, block_table, softmax_scale, (-1, -1), 0.0,
+                                       None, num_splits)
+  q, seqused = _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal)
+  B, Sq, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  qp = q.reshape(B * Sq, Hq, D)
+  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device) if Sq > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
+  if block_table is not None:
+    kp, vp, cu_k = k_cache, v_cache, None
+  else:
+    # the contiguous cache as the packed call's seqused_k case (ffpa_attn_with_kvcache's view: sequence b's keys are rows b * capacity ...)
+    kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
+    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
+  o, lse = torch.ops.ffpa_attn._window_fwd_hip(qp, kp, vp, cu_q, cu_k, seqused, block_table, left, right, Sq, capacity, scale, 1 if causal else 0, -1.0, num_splits)
   out = o.view(B, Sq, Hq, D)
   if not return_softmax_lse:
     return out

@@ -381,6 +381,35 @@ int ffpa_attn_varlen_tree_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_p
 int ffpa_attn_varlen_tree_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, char* buf, size_t n);
 
 /*
+ * SLIDING WINDOW (local attention: Mistral, Gemma 2 / 3, Phi-3; FlashAttention's window_size = (left, right)) over the packed call (kv == NULL) or its paged
+ * twin (kv != NULL).  With L_i the keys of sequence i, ntok_i its query tokens and pos_t = t + L_i - ntok_i the position of token t (bottom-right aligned),
+ * token t sees key j iff
+ *        0 <= j < L_i,   left < 0 or j >= pos_t - left,   right < 0 or j <= pos_t + right          (-1 = unbounded on that side).
+ *   p->causal means right = 0, whatever `right` says (FlashAttention's rule).  (-1, -1) without the causal flag is the plain launch and (-1, 0) the causal one: the
+ *   same bits as those launches.  A token that sees no key gives O = 0, LSE = -inf, the packed call's empty-row contract.  One token per sequence — decode —
+ *   keeps its left bound.
+ * A row tile walks only the KV tiles between the left bound of its first token and the right bound of its last one — the tiles (and, paged, the pages) in front
+ * of the window are never read —, a split launch's KV ranges share out those tiles, and the launch plan (the split count, the non-temporal fetch) prices the
+ * widest key span a row tile can see, left + min(max_seqlen_q, tile rows + right) keys rounded up to a KV tile, instead of max_seqlen_kv: a 4k window over a
+ * 32k cache plans like a 4k cache.
+ */
+typedef struct ffpa_window {
+  uint32_t struct_size;  /* sizeof(ffpa_window), checked */
+  uint32_t reserved;     /* 0, checked */
+  int32_t left;          /* keys visible in front of a token's position; -1 = all of them */
+  int32_t right;         /* keys visible behind it; -1 = all of them (p->causal: taken as 0) */
+} ffpa_window;
+
+/* Launch the forward under a sliding window on `stream` of the CURRENT device (kv: the paged pool, NULL = the packed call's contiguous keys).  Asynchronous; every
+ * bad argument — a NULL w, a wrong struct_size, a non-zero reserved, left or right below -1 — returns a status before any device work.  Returns an ffpa_status. */
+int ffpa_attn_varlen_window_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, void* stream);
+
+/* As ffpa_attn_varlen_fwd_workspace_bytes / _plan / _kernel, for the window call ("ffpa_fwd_m16_paged_window_kernel<bf16, 512>"; the plan is the window's own). */
+size_t ffpa_attn_varlen_window_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w);
+int ffpa_attn_varlen_window_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, int out[5]);
+int ffpa_attn_varlen_window_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, char* buf, size_t n);
+
+/*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
  * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
  *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position
