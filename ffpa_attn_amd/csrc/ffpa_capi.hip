@@ -1171,11 +1171,24 @@ int window_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const 
   return varlen_plan(&wp->priced, pl, paged);
 }
 
+// The soft-capping call's own argument: a finite cap > 0 (0 = "off" is the Python entry's business: it forwards to the window call), checked before any device work.
+int check_softcap(float softcap) {
+  if (!isfinite(softcap) || !(softcap > 0.f)) return fail(FFPA_ERR_BAD_SHAPE, "softcap=%g must be finite and > 0", (double)softcap);
+  return FFPA_OK;
+}
+
+// The window the soft-capping call runs under: the caller's, or — NULL — (-1, -1), whose plan and tile walk are the plain launch's.
+const ffpa_window* softcap_window(const ffpa_window* w) {
+  static const ffpa_window kNone = {(uint32_t)sizeof(ffpa_window), 0u, -1, -1};
+  return w != nullptr ? w : &kNone;
+}
+
 // The packed call and its paged twin (kv != NULL: k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read); `tree`: under a tree mask
 // (ffpa_attn_varlen_tree_fwd — the causal launch's plan and tile walk; the *_tree_kernel builds, whose element test reads the mask words); `win`: under a sliding
-// window (ffpa_attn_varlen_window_fwd — the window's own plan; the *_window_kernel builds)
+// window (ffpa_attn_varlen_window_fwd — the window's own plan; the *_window_kernel builds); `softcap` > 0: a window launch with capped scores
+// (ffpa_attn_varlen_softcap_fwd — the same plan; the *_softcap_kernel builds)
 int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream, const ffpa_tree_mask* tree = nullptr, bool with_tree = false,
-                  const ffpa_window* win = nullptr, bool with_win = false) {
+                  const ffpa_window* win = nullptr, bool with_win = false, float softcap = 0.f) {
   const bool paged = kv != nullptr;
   VarlenPlan pl;
   WindowPlan wp;
@@ -1271,6 +1284,12 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
     va.win_right = wp.right;
     va.win_span = wp.span;
   }
+  if (softcap > 0.f) {
+    // score = cap * tanh(|scale| q.k / cap) (the sign of the scale went into Q, a zero scale zeroes Q: fold_scale): the kernel multiplies the raw score by
+    // softcap_in inside the tanh, and everything behind it — row max, exponent FMA, LSE — takes cap * log2(e) where it took scale * log2(e)
+    va.softcap_in = a.q_mode == 1 ? 1.f / softcap : fabsf(p->softmax_scale) / softcap;
+    a.scale_log2 = softcap * 1.4426950408889634f;
+  }
 
   va.compact_tiles = pl.compact;
   va.ws_head_rows = va.ws_split_rows = 0;
@@ -1334,9 +1353,9 @@ size_t workspace_bytes(const ffpa_varlen_fwd_params* params, bool paged) {
   return pl.ws_bytes;
 }
 
-int kernel_name(const ffpa_varlen_fwd_params* params, const VarlenPlan& pl, bool paged, char* buf, size_t n, bool tree = false, bool window = false) {
+int kernel_name(const ffpa_varlen_fwd_params* params, const VarlenPlan& pl, bool paged, char* buf, size_t n, bool tree = false, bool window = false, bool softcap = false) {
   if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
-  snprintf(buf, n, "ffpa_fwd_m16_%s%s_kernel<%s, %d%s>%s%s", paged ? "paged" : "varlen", tree ? "_tree" : window ? "_window" : "", params->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d,
+  snprintf(buf, n, "ffpa_fwd_m16_%s%s_kernel<%s, %d%s>%s%s", paged ? "paged" : "varlen", tree ? "_tree" : softcap ? "_softcap" : window ? "_window" : "", params->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d,
            pl.nt ? ", NT" : "", pl.pack ? " (GQA heads packed into rows)" : "", pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
   return FFPA_OK;
 }
@@ -1452,6 +1471,33 @@ int ffpa_attn_varlen_window_fwd_kernel(const ffpa_varlen_fwd_params* p, const ff
   const int rc = window_plan(p, kv, w, &pl, &wp);
   if (rc != FFPA_OK) return rc;
   return kernel_name(&wp.priced, pl, kv != nullptr, buf, n, false, true);
+}
+
+// ---- the soft-capping call (include/ffpa_attn.h): the window call — its checks, its plan; w == NULL = (-1, -1) — with capped scores
+int ffpa_attn_varlen_softcap_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap, void* stream) {
+  const int rc = check_softcap(softcap);
+  if (rc != FFPA_OK) return rc;
+  return varlen_launch(p, kv, stream, nullptr, false, softcap_window(w), true, softcap);
+}
+
+size_t ffpa_attn_varlen_softcap_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap) {
+  if (check_softcap(softcap) != FFPA_OK) return 0;
+  return ffpa_attn_varlen_window_fwd_workspace_bytes(p, kv, softcap_window(w));
+}
+
+int ffpa_attn_varlen_softcap_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap, int out[5]) {
+  const int rc = check_softcap(softcap);
+  if (rc != FFPA_OK) return rc;
+  return ffpa_attn_varlen_window_fwd_plan(p, kv, softcap_window(w), out);
+}
+
+int ffpa_attn_varlen_softcap_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap, char* buf, size_t n) {
+  VarlenPlan pl;
+  WindowPlan wp;
+  int rc = check_softcap(softcap);
+  if (rc != FFPA_OK) return rc;
+  if ((rc = window_plan(p, kv, softcap_window(w), &pl, &wp)) != FFPA_OK) return rc;
+  return kernel_name(&wp.priced, pl, kv != nullptr, buf, n, false, true, true);
 }
 
 // ---- the KV-cache append + rotary (include/ffpa_attn.h: ffpa_kv_append_params)

@@ -291,6 +291,18 @@ __device__ __forceinline__ int m16_window_first_tile(int first_row, int causal_o
   return (span >= 0 && lo > 0) ? (int)(lo / bc) : 0;
 }
 
+// Logit soft-capping (VarlenArgs::softcap_in): tanh(y), y = x * softcap_in, on the hardware transcendentals — one exp2 and one rcp per score:
+//        tanh(y) = 1 - 2 / (1 + e),   e = exp2(2 log2(e) y).
+// Exact at both saturations without a branch (e = inf: 1 - 2 * 0; e = 0: 1 - 2 * 1) and for y = 0 (e = 1); a NaN score stays NaN until the mask behind the cap
+// overwrites it.  ABSOLUTE error <= 2^-21 over all finite y (what matters: the launch multiplies by the cap): the exponent's rounding and v_exp_f32's 1 ulp reach
+// t through 2e / (1 + e)^2 <= 1/2, the sum's rounding and v_rcp_f32's 1 ulp through 2 / (1 + e) <= 2, plus the last rounding — tests/test_kvcache_softcap.py
+// holds the formula to that bound in float32.  m16_softcap_arg folds the constant into the launch's factor once per use site.
+__device__ __forceinline__ float m16_softcap_arg(float softcap_in) { return softcap_in * 2.8853900817779268f; }
+__device__ __forceinline__ float m16_softcap_tanh(float x, float arg) {
+  const float e = __builtin_amdgcn_exp2f(x * arg);
+  return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + e), 1.f);
+}
+
 // LDS images of the K / V tiles: row-major [BC][D], 16-byte slot s of row `key` stored at slot s ^ swizzle(key) (applied on the
 // DMA's per-lane source offset).  K fragments are fetched by ds_read_b128 whose 16-lane groups hold 16 different keys and two
 // neighbouring slots; V^T fragments by ds_read_b64_tr_b16 whose 32-lane halves hold 8 keys x 32 bytes.  Row strides that are whole
@@ -459,6 +471,10 @@ struct VarlenArgs {
   int window;
   int win_right;
   int win_span;
+  // LOGIT SOFT-CAPPING (ffpa_attn_varlen_softcap_fwd: FlashAttention's softcap; Gemma 2, Grok-1): softcap_in > 0 = the launch runs the *_softcap_kernel builds —
+  // the window builds with the cap hook on, window (-1, -1) when the caller has none — whose scores are cap * tanh(softmax_scale * q.k / cap): softcap_in =
+  // |softmax_scale| / cap multiplies the raw score inside the tanh (m16_softcap_tanh) and FwdArgs::scale_log2 = cap * log2(e) multiplies its result.  0 = no cap.
+  float softcap_in;
 };
 // the tree hook of the tile text for the kernels that carry a VarlenArgs `va` and a sequence index `seq`: the word of a token (whether a kernel tests words at all is
 // a constant of its build: ffpa_fwd_m16_varlen_body.inc; the dense and paired kernels say "no tree")
@@ -470,7 +486,9 @@ template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_varlen_kernel(const FwdArgs a_in, const VarlenArgs va) {
 #define FFPA_M16_VARLEN_TREE false
 #define FFPA_M16_VARLEN_WINDOW false
+#define FFPA_M16_VARLEN_SOFTCAP false
 #include "ffpa_fwd_m16_varlen_body.inc"
+#undef FFPA_M16_VARLEN_SOFTCAP
 #undef FFPA_M16_VARLEN_WINDOW
 #undef FFPA_M16_VARLEN_TREE
 }
@@ -482,7 +500,9 @@ template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_varlen_tree_kernel(const FwdArgs a_in, const VarlenArgs va) {
 #define FFPA_M16_VARLEN_TREE true
 #define FFPA_M16_VARLEN_WINDOW false
+#define FFPA_M16_VARLEN_SOFTCAP false
 #include "ffpa_fwd_m16_varlen_body.inc"
+#undef FFPA_M16_VARLEN_SOFTCAP
 #undef FFPA_M16_VARLEN_WINDOW
 #undef FFPA_M16_VARLEN_TREE
 }
@@ -493,7 +513,22 @@ template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_varlen_window_kernel(const FwdArgs a_in, const VarlenArgs va) {
 #define FFPA_M16_VARLEN_TREE false
 #define FFPA_M16_VARLEN_WINDOW true
+#define FFPA_M16_VARLEN_SOFTCAP false
 #include "ffpa_fwd_m16_varlen_body.inc"
+#undef FFPA_M16_VARLEN_SOFTCAP
+#undef FFPA_M16_VARLEN_WINDOW
+#undef FFPA_M16_VARLEN_TREE
+}
+
+// ... and with LOGIT SOFT-CAPPING (VarlenArgs::softcap_in; ffpa_attn_varlen_softcap_fwd): the window build with the cap hook on.  A window of (-1, -1) walks the
+// plain launch's tiles, so this one kernel serves capped layers with and without a window.
+template <typename T, int D, bool NT = false>
+__global__ __launch_bounds__(256) void ffpa_fwd_m16_varlen_softcap_kernel(const FwdArgs a_in, const VarlenArgs va) {
+#define FFPA_M16_VARLEN_TREE false
+#define FFPA_M16_VARLEN_WINDOW true
+#define FFPA_M16_VARLEN_SOFTCAP true
+#include "ffpa_fwd_m16_varlen_body.inc"
+#undef FFPA_M16_VARLEN_SOFTCAP
 #undef FFPA_M16_VARLEN_WINDOW
 #undef FFPA_M16_VARLEN_TREE
 }

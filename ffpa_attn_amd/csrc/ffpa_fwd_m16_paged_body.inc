@@ -1,6 +1,7 @@
 // ffpa_fwd_m16_paged_body.inc — the body of the paged-KV twin of the packed-sequence kernel (ffpa_paged_inst.hip), included once per kernel of that family:
 // ffpa_fwd_m16_paged_kernel (FFPA_M16_VARLEN_TREE false) and ffpa_fwd_m16_paged_tree_kernel (true: under a tree mask, VarlenArgs::tree_bits); ffpa_fwd_m16_paged_window_kernel has FFPA_M16_VARLEN_WINDOW true (a sliding
-// window, VarlenArgs::window: the walk — and the page lookahead — start at the row tile's first windowed tile).  Text moved out of the
+// window, VarlenArgs::window: the walk — and the page lookahead — start at the row tile's first windowed tile); ffpa_fwd_m16_paged_softcap_kernel is that build with
+// FFPA_M16_VARLEN_SOFTCAP true (capped scores, VarlenArgs::softcap_in).  Text moved out of the
 // kernel, nothing changed.
   constexpr int MK = 0;  // no attn_bias, no mask ranges
   constexpr bool DROP = false;
@@ -71,7 +72,11 @@
 #define FFPA_M16_TREE_WORD(tok, pin) FFPA_M16_VARLEN_TREE_WORD(tok, pin)
 #define FFPA_M16_WINDOW_ON FFPA_M16_VARLEN_WINDOW
 #define FFPA_M16_WINDOW_SPAN va.win_span
+#define FFPA_M16_SOFTCAP_ON FFPA_M16_VARLEN_SOFTCAP
+#define FFPA_M16_SOFTCAP_IN va.softcap_in
 #include "ffpa_fwd_m16_tile.inc"
+#undef FFPA_M16_SOFTCAP_IN
+#undef FFPA_M16_SOFTCAP_ON
 #undef FFPA_M16_WINDOW_SPAN
 #undef FFPA_M16_WINDOW_ON
 #undef FFPA_M16_TREE_WORD

@@ -20,6 +20,16 @@
 #define FFPA_M16_WINDOW_SPAN (-1)
 #define FFPA_M16_WINDOW_DEFAULT_HOOKS
 #endif
+// LOGIT SOFT-CAPPING is the enclosing kernel's as well: FFPA_M16_SOFTCAP_ON = a constant of its build, FFPA_M16_SOFTCAP_IN = softmax_scale / cap
+// (VarlenArgs::softcap_in).  Both softmax sites turn every raw score x into tanh(x * softcap_in) in place (m16_softcap_tanh), behind the QK^T sums — at D > 512
+// behind the sum of the two waves' partial S^T halves — and IN FRONT of every mask: a mask writes -inf over the capped score, it never feeds the tanh.  The
+// launch runs with scale_log2 = cap * log2(e), so the row max, the lazy rescale, the exponent FMA and the LSE below read capped scores without knowing.  The
+// un-pipelined split-D loop (D % 128 == 64) and D <= 512 share the second site.  Kernels that do not define the hooks have no cap: the text that stood here.
+#ifndef FFPA_M16_SOFTCAP_ON
+#define FFPA_M16_SOFTCAP_ON false
+#define FFPA_M16_SOFTCAP_IN 0.f
+#define FFPA_M16_SOFTCAP_DEFAULT_HOOKS
+#endif
 #ifndef FFPA_M16_KV_SRC
 #define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) tile_src<BC>(slice, row_bytes, key0, a.Nkv, rb_valid)
 #define FFPA_M16_KV_BEGIN(t0_)
@@ -554,6 +564,16 @@
 #pragma unroll
             for (int r = 0; r < 4; ++r) x[kb][r] = xc[kb][r] + tp[kb][r];
           } else if constexpr (g == 7) {
+            if (FFPA_M16_SOFTCAP_ON) {
+              // the cap, on the summed scores and in front of the masks below (one key block at a time: the chain's temporaries die before P^T comes alive)
+              const float cap_in = m16_softcap_arg(FFPA_M16_SOFTCAP_IN);
+#pragma unroll
+              for (int kb = 0; kb < NKB; ++kb) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) x[kb][r] = m16_softcap_tanh(x[kb][r], cap_in);
+                __builtin_amdgcn_sched_barrier(0);
+              }
+            }
             if constexpr (MK == 2) {
               // boolean mask bytes (non-zero = visible), straight from the caller's tensor, exactly as the loop below reads them; steps in the mask's
               // neutral interior (kv_bounds) read nothing.  (The loads are the compiler's: its wait in front of their first use also drains the DMA
@@ -985,6 +1005,18 @@
     }
     pre_k_group(std::integral_constant<int, 1>{});
 
+    if (FFPA_M16_SOFTCAP_ON) {
+      // the cap, on the summed scores and in front of the masks below (one key block at a time: the chain's temporaries die before P^T comes alive)
+      const float cap_in = m16_softcap_arg(FFPA_M16_SOFTCAP_IN);
+#pragma unroll
+      for (int kb = 0; kb < NKB; ++kb) {
+#pragma unroll
+        for (int rh = 0; rh < RHS; ++rh)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) x[kb][rh][r] = m16_softcap_tanh(x[kb][rh][r], cap_in);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
     if constexpr (MK == 2) {
       // boolean mask bytes (non-zero = visible), straight from the caller's tensor; the lane's 4 keys of a block are consecutive
       const bool mask_free = k0 >= free_lo && k0 + BC <= free_hi;  // wave-uniform: the step lies in the mask's neutral interior (kv_bounds)
@@ -1370,6 +1402,11 @@
     }
 #endif
   }
+#ifdef FFPA_M16_SOFTCAP_DEFAULT_HOOKS
+#undef FFPA_M16_SOFTCAP_DEFAULT_HOOKS
+#undef FFPA_M16_SOFTCAP_IN
+#undef FFPA_M16_SOFTCAP_ON
+#endif
 #ifdef FFPA_M16_WINDOW_DEFAULT_HOOKS
 #undef FFPA_M16_WINDOW_DEFAULT_HOOKS
 #undef FFPA_M16_WINDOW_SPAN

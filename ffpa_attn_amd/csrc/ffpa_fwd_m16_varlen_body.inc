@@ -1,7 +1,8 @@
 // ffpa_fwd_m16_varlen_body.inc — the body of the packed-sequence kernel (ffpa_fwd_m16_kernel.h), included once per kernel of that family: ffpa_fwd_m16_varlen_kernel
 // (FFPA_M16_VARLEN_TREE false: the tree hooks of the tile text fold away, the kernel is what it was) and ffpa_fwd_m16_varlen_tree_kernel (true: the element test of
 // the tiles that hold a draft key reads VarlenArgs::tree_bits) and ffpa_fwd_m16_varlen_window_kernel (FFPA_M16_VARLEN_WINDOW true: the tile range, the element test and
-// the KV ranges' share-out take a sliding window, VarlenArgs::window).  Text moved out of the kernel, nothing changed.
+// the KV ranges' share-out take a sliding window, VarlenArgs::window) and ffpa_fwd_m16_varlen_softcap_kernel (the window build with FFPA_M16_VARLEN_SOFTCAP true: both
+// softmax sites cap the scores, VarlenArgs::softcap_in).  Text moved out of the kernel, nothing changed.
   constexpr int MK = 0;  // no attn_bias, no mask ranges: what the reference's packed entry point accepts
   constexpr bool DROP = false;
 #define FFPA_M16_MFMA std::conditional_t<NT, Mfma16Nt<T>, Mfma16<T>>
@@ -21,7 +22,11 @@
 #define FFPA_M16_TREE_WORD(tok, pin) FFPA_M16_VARLEN_TREE_WORD(tok, pin)
 #define FFPA_M16_WINDOW_ON FFPA_M16_VARLEN_WINDOW
 #define FFPA_M16_WINDOW_SPAN va.win_span
+#define FFPA_M16_SOFTCAP_ON FFPA_M16_VARLEN_SOFTCAP
+#define FFPA_M16_SOFTCAP_IN va.softcap_in
 #include "ffpa_fwd_m16_tile.inc"
+#undef FFPA_M16_SOFTCAP_IN
+#undef FFPA_M16_SOFTCAP_ON
 #undef FFPA_M16_WINDOW_SPAN
 #undef FFPA_M16_WINDOW_ON
 #undef FFPA_M16_TREE_WORD

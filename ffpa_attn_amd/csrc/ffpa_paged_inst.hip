@@ -43,7 +43,9 @@ template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_paged_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa) {
 #define FFPA_M16_VARLEN_TREE false
 #define FFPA_M16_VARLEN_WINDOW false
+#define FFPA_M16_VARLEN_SOFTCAP false
 #include "ffpa_fwd_m16_paged_body.inc"
+#undef FFPA_M16_VARLEN_SOFTCAP
 #undef FFPA_M16_VARLEN_WINDOW
 #undef FFPA_M16_VARLEN_TREE
 }
@@ -53,7 +55,9 @@ template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_paged_tree_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa) {
 #define FFPA_M16_VARLEN_TREE true
 #define FFPA_M16_VARLEN_WINDOW false
+#define FFPA_M16_VARLEN_SOFTCAP false
 #include "ffpa_fwd_m16_paged_body.inc"
+#undef FFPA_M16_VARLEN_SOFTCAP
 #undef FFPA_M16_VARLEN_WINDOW
 #undef FFPA_M16_VARLEN_TREE
 }
@@ -64,7 +68,21 @@ template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_paged_window_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa) {
 #define FFPA_M16_VARLEN_TREE false
 #define FFPA_M16_VARLEN_WINDOW true
+#define FFPA_M16_VARLEN_SOFTCAP false
 #include "ffpa_fwd_m16_paged_body.inc"
+#undef FFPA_M16_VARLEN_SOFTCAP
+#undef FFPA_M16_VARLEN_WINDOW
+#undef FFPA_M16_VARLEN_TREE
+}
+
+// ... and with LOGIT SOFT-CAPPING (ffpa_attn_varlen_softcap_fwd with a pool), as ffpa_fwd_m16_varlen_softcap_kernel: the window build with the cap hook on
+template <typename T, int D, bool NT = false>
+__global__ __launch_bounds__(256) void ffpa_fwd_m16_paged_softcap_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa) {
+#define FFPA_M16_VARLEN_TREE false
+#define FFPA_M16_VARLEN_WINDOW true
+#define FFPA_M16_VARLEN_SOFTCAP true
+#include "ffpa_fwd_m16_paged_body.inc"
+#undef FFPA_M16_VARLEN_SOFTCAP
 #undef FFPA_M16_VARLEN_WINDOW
 #undef FFPA_M16_VARLEN_TREE
 }
@@ -74,6 +92,7 @@ static int launch_paged(const FwdArgs& a, const VarlenArgs& va, const PagedArgs&
   constexpr int BC = m16_block_keys(D, true);
   constexpr int LDS = 2 * BC * D * 2 + m16_exchange_bytes(D, 0);
   if (va.tree_tokens != 0) return launch_kernel<ffpa_fwd_m16_paged_tree_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa);  // (under a tree mask: its own build)
+  if (va.softcap_in > 0.f) return launch_kernel<ffpa_fwd_m16_paged_softcap_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa);  // (capped scores: the window build with the cap)
   if (va.window != 0) return launch_kernel<ffpa_fwd_m16_paged_window_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa);  // (under a sliding window: its own build)
   return launch_kernel<ffpa_fwd_m16_paged_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa);
 }

@@ -18,6 +18,7 @@ static int launch_varlen(const FwdArgs& a, const VarlenArgs& va, hipStream_t str
   constexpr int BC = m16_block_keys(D, false);
   constexpr int LDS = 2 * BC * D * 2 + m16_exchange_bytes(D, 0);
   if (va.tree_tokens != 0) return launch_kernel<ffpa_fwd_m16_varlen_tree_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va);  // (under a tree mask: its own build)
+  if (va.softcap_in > 0.f) return launch_kernel<ffpa_fwd_m16_varlen_softcap_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va);  // (capped scores: the window build with the cap)
   if (va.window != 0) return launch_kernel<ffpa_fwd_m16_varlen_window_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va);  // (under a sliding window: its own build)
   return launch_kernel<ffpa_fwd_m16_varlen_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va);
 }

@@ -270,6 +270,7 @@ _INT, _SIZE, _VOID, _STR = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctype
 _VARLEN, _PAGED = [_P(FfpaVarlenFwdParams)], [_P(FfpaVarlenFwdParams), _P(FfpaPagedKv)]
 _TREE = _PAGED + [_P(FfpaTreeMask)]
 _WINDOW = _PAGED + [_P(FfpaWindow)]
+_SOFTCAP = _WINDOW + [ctypes.c_float]
 # Every function include/ffpa_attn.h declares: (symbol, argtypes, restype, since).  ``since``: the ABI version that added it (0: there from the start) — the
 # default library has them all; one loaded by path or through FFPA_HIP_LIBRARY (developer A/B runs load a saved build of an older commit) may lack those with
 # since > 0: calling one of those is then an AttributeError.
@@ -296,6 +297,10 @@ _BINDINGS = (
   ("ffpa_attn_varlen_window_fwd_plan", _WINDOW + [_P(_INT)], _INT, 7),
   ("ffpa_attn_varlen_window_fwd_kernel", _WINDOW + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_window_fwd_workspace_bytes", _WINDOW, _SIZE, 7),
+  ("ffpa_attn_varlen_softcap_fwd", _SOFTCAP + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_softcap_fwd_plan", _SOFTCAP + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_softcap_fwd_kernel", _SOFTCAP + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_softcap_fwd_workspace_bytes", _SOFTCAP, _SIZE, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
   ("ffpa_attn_query", [_INT], _INT, 0),
@@ -1021,10 +1026,11 @@ def _paged_kv_of(block_table: torch.Tensor, k: torch.Tensor, v: torch.Tensor) ->
 
 
 def _varlen_fn(lib, kv: "FfpaPagedKv | None", suffix: str = "", tree: "bool | str" = False):
-  """The packed call's export — or, with ``kv``, its paged twin's; with ``tree``, the tree call's, with ``tree == "window"`` the window call's (one export for
-  both caches: their ``kv`` may be NULL) — of this suffix ("" the launch, "_plan", "_kernel", "_workspace_bytes")"""
+  """The packed call's export — or, with ``kv``, its paged twin's; with ``tree``, the tree call's, with ``tree == "window"`` the window call's and with
+  ``tree == "softcap"`` the soft-capping call's (one export for both caches: their ``kv`` may be NULL) — of this suffix ("" the launch, "_plan", "_kernel",
+  "_workspace_bytes")"""
   if tree:
-    return getattr(lib, ("ffpa_attn_varlen_window_fwd" if tree == "window" else "ffpa_attn_varlen_tree_fwd") + suffix)
+    return getattr(lib, {"window": "ffpa_attn_varlen_window_fwd", "softcap": "ffpa_attn_varlen_softcap_fwd"}.get(tree, "ffpa_attn_varlen_tree_fwd") + suffix)
   return getattr(lib, ("ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd") + suffix)
 
 
@@ -1049,7 +1055,7 @@ def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaP
 def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: "torch.Tensor | None", max_seqlen_q: int,
                    max_seqlen_k: int, causal: bool, softmax_scale: float, *, rescale_threshold: float = -1.0, return_lse: bool = True, flags: int = 0,
                    plan_out: "dict | None" = None, seqused_k: "torch.Tensor | None" = None, num_splits: int = 0, block_table: "torch.Tensor | None" = None,
-                   tree_words: "torch.Tensor | None" = None, window: "tuple[int, int] | None" = None):
+                   tree_words: "torch.Tensor | None" = None, window: "tuple[int, int] | None" = None, softcap: float = 0.0):
   """One launch of the packed-sequence kernel: ``q [T_q, Hq, D]``, ``k`` / ``v [T_k, Hkv, D]``, int32 device ``cu_seqlens_*`` ``[B + 1]`` ->
   ``(o [T_q, Hq, D], lse [Hq, T_q] fp32 | None)``.  Nothing is read back to the host and nothing synchronises: the call captures into a HIP graph.
   Rows without a visible key: O = 0, LSE = -inf.
@@ -1074,14 +1080,20 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
 
   ``window`` (``(left, right)``, ints >= -1, -1 = unbounded; ``window_forward`` is this call with it): a SLIDING WINDOW (``ffpa_attn_varlen_window_fwd``) — token t
   of sequence i, at position ``pos = t + L_i - ntok_i``, sees key j iff ``pos - left <= j <= pos + right``; ``causal`` means ``right = 0``.  The KV tiles in front
-  of a row tile's window are not read, and the plan prices the window's keys instead of ``max_seqlen_k``."""
+  of a row tile's window are not read, and the plan prices the window's keys instead of ``max_seqlen_k``.
+
+  ``softcap`` (a finite float > 0; ``softcap_forward`` is this call with it; 0 = none): LOGIT SOFT-CAPPING (``ffpa_attn_varlen_softcap_fwd``) — the scores are
+  ``softcap * tanh(softmax_scale * q.k / softcap)``, masked behind the cap; with or without ``window`` (None = ``(-1, -1)``), whose plan the launch runs."""
   paged = block_table is not None
   tree = tree_words is not None
+  capped = softcap != 0.0
+  if capped and window is None:
+    window = (-1, -1)
   if window is not None:
     if tree:
-      raise ValueError("ffpa_attn::_window_fwd_hip: a window and a tree mask do not combine")
-    tree = "window"  # (which export family the helpers below pick)
-  name = "ffpa_attn::_window_fwd_hip" if window is not None else "ffpa_attn::_tree_fwd_hip" if tree else "ffpa_attn::_paged_fwd_hip" if paged else "ffpa_attn::_varlen_fwd_hip"
+      raise ValueError(f"ffpa_attn::{'_softcap' if capped else '_window'}_fwd_hip: a window and a tree mask do not combine")
+    tree = "softcap" if capped else "window"  # (which export family the helpers below pick)
+  name = "ffpa_attn::_softcap_fwd_hip" if capped else "ffpa_attn::_window_fwd_hip" if window is not None else "ffpa_attn::_tree_fwd_hip" if tree else "ffpa_attn::_paged_fwd_hip" if paged else "ffpa_attn::_varlen_fwd_hip"
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
@@ -1129,6 +1141,12 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
     if min(window) < -1 or max(window) > 0x7FFFFFFF:
       raise ValueError(f"{name}: window (left, right) = {tuple(window)}: each must be >= -1 (-1 = unbounded)")
     window = (int(window[0]), int(window[1]))
+    if capped:
+      if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
+        raise TypeError(f"{name}: softcap must be a real number, got {softcap!r}")
+      softcap = float(softcap)
+      if not (softcap > 0.0 and softcap != float("inf")):
+        raise ValueError(f"{name}: softcap = {softcap} must be finite and > 0")
   elif tree:
     if not isinstance(tree_words, torch.Tensor) or tree_words.dtype != torch.int64 or tree_words.dim() != 2 or tree_words.device != q.device:
       raise ValueError(f"{name}: tree_words must be a 2-D int64 tensor [batch or 1, tokens] on q's device")
@@ -1167,6 +1185,8 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
     wn = _stamped(FfpaWindow)
     wn.left, wn.right = window
     args = (ctypes.byref(p), ctypes.byref(kv) if paged else None, ctypes.byref(wn))
+    if capped:
+      args += (ctypes.c_float(softcap),)
   elif tree:
     tm = _stamped(FfpaTreeMask)
     tm.bits, tm.tokens = tree_words.data_ptr(), tree_words.size(1)
@@ -1174,12 +1194,12 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
     args = (ctypes.byref(p), ctypes.byref(kv) if paged else None, ctypes.byref(tm))
   with torch.cuda.device(q.device):
     stream = torch.cuda.current_stream(q.device).cuda_stream
-    workspace = _hand_over_workspace(p, q.device, stream, _varlen_scratch(lib, p, q.device.index or 0, kv, args, tree, window))  # (held in a local until the launch below has been enqueued)
+    workspace = _hand_over_workspace(p, q.device, stream, _varlen_scratch(lib, p, q.device.index or 0, kv, args, tree, window))  # (the cap changes no plan: the key needs no softcap)  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
       plan_out.update(_read_plan(lib, _varlen_fn(lib, kv, "_plan", tree), _varlen_fn(lib, kv, "_kernel", tree), _VARLEN_PLAN_KEYS, args))
     rc = _varlen_fn(lib, kv, "", tree)(*args, ctypes.c_void_p(stream))
   if rc != 0:
-    _raise_status(lib, rc, "ffpa_attn_varlen_window_fwd" if window is not None else "ffpa_attn_varlen_tree_fwd" if tree else "ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd")
+    _raise_status(lib, rc, "ffpa_attn_varlen_softcap_fwd" if capped else "ffpa_attn_varlen_window_fwd" if window is not None else "ffpa_attn_varlen_tree_fwd" if tree else "ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd")
   return _unpad_head_dim(o, D), lse
 
 
@@ -1209,13 +1229,29 @@ def window_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
                         window=window)
 
 
+def softcap_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: "torch.Tensor | None", max_seqlen_q: int,
+                    max_seqlen_k: int, causal: bool, softmax_scale: float, softcap: float, window: "tuple[int, int]" = (-1, -1), *, rescale_threshold: float = -1.0,
+                    return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, seqused_k: "torch.Tensor | None" = None, num_splits: int = 0,
+                    block_table: "torch.Tensor | None" = None):
+  """One launch of the packed-sequence kernel (``block_table``: of its paged twin) with LOGIT SOFT-CAPPING, under ``window`` (``ffpa_attn_varlen_softcap_fwd``;
+  ``varlen_forward``'s ``softcap``).  ``flags`` / ``plan_out`` as ``varlen_forward`` (tests force or inspect the launch)."""
+  if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
+    raise TypeError(f"ffpa_attn::_softcap_fwd_hip: softcap must be a real number, got {softcap!r}")
+  if not (softcap > 0.0 and softcap != float("inf")):
+    raise ValueError(f"ffpa_attn::_softcap_fwd_hip: softcap = {softcap} must be finite and > 0")
+  return varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal, softmax_scale, rescale_threshold=rescale_threshold,
+                        return_lse=return_lse, flags=flags, plan_out=plan_out, seqused_k=seqused_k, num_splits=num_splits, block_table=block_table,
+                        window=window, softcap=float(softcap))
+
+
 def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: int, max_seqlen_k: int, head_dim: int, *,
                        dtype: torch.dtype = torch.bfloat16, causal: bool = False, flags: int = 0, total_q: int = 0, num_splits: int = 0,
-                       page_size: int = 0, window: "tuple[int, int] | None" = None) -> dict:
+                       page_size: int = 0, window: "tuple[int, int] | None" = None, softcap: float = 0.0) -> dict:
   """The packed-sequence launch for a shape class, without launching (placeholder pointers): row tiles per (sequence, head), tile, workgroups, KV ranges per
   sequence, kernel name.  ``total_q`` (rows of q) > 0: the plan of a call that hands the library its scratch (``varlen_forward`` does) — KV splits included;
   0: the plan without scratch (never split).  ``page_size`` > 0: the paged call's plan (``ffpa_attn_varlen_paged_fwd``, a table of one page per sequence row
-  covering max_seqlen_k).  ``window`` = (left, right): the sliding-window call's plan (``ffpa_attn_varlen_window_fwd``), priced at the window's keys."""
+  covering max_seqlen_k).  ``window`` = (left, right): the sliding-window call's plan (``ffpa_attn_varlen_window_fwd``), priced at the window's keys.
+  ``softcap`` > 0: the soft-capping call's (``ffpa_attn_varlen_softcap_fwd``: the window call's plan, ``window`` None = no window, and the capped kernel's name)."""
   lib = load_library()
   d8 = (int(head_dim) + 7) // 8 * 8
   strides = [(h * d8, d8) for h in (heads_q, heads_kv, heads_kv, heads_q)]
@@ -1231,10 +1267,14 @@ def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: in
     kv = _paged_kv(16, pages_per_row, pages_per_row, int(page_size), int(batch) * pages_per_row, int(page_size) * heads_kv * d8, int(page_size) * heads_kv * d8)
     args = (ctypes.byref(p), ctypes.byref(kv))
   fam = False
+  if softcap and window is None:
+    window = (-1, -1)
   if window is not None:
     wn = _stamped(FfpaWindow)
     wn.left, wn.right = int(window[0]), int(window[1])
     args, fam = (ctypes.byref(p), ctypes.byref(kv) if kv is not None else None, ctypes.byref(wn)), "window"
+    if softcap:
+      args, fam = args + (ctypes.c_float(softcap),), "softcap"
   out = _read_plan(lib, _varlen_fn(lib, kv, "_plan", fam), _varlen_fn(lib, kv, "_kernel", fam), _VARLEN_PLAN_KEYS, args, strict=True)
   if total_q <= 0:
     del out["splits"]
@@ -1320,6 +1360,30 @@ def _window_fwd_hip_torch_op(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, blo
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_window_fwd_hip")
 def _window_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, window_left, window_right, max_seqlen_q, max_seqlen_k, softmax_scale,
                          causal, rescale_threshold=-1.0, num_splits=0):
+  total_q, heads, head_dim = q.shape
+  return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
+
+
+# The soft-capping call (ffpa_attn_with_kvcache_softcap): the window call's op with the cap — ``block_table`` None = the contiguous cache, (-1, -1) = no window
+torch.library.define(
+  f"{_OP_NAMESPACE}::_softcap_fwd_hip",
+  "(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor? cu_seqlens_k, Tensor seqused_k, Tensor? block_table, float softcap, int window_left, "
+  "int window_right, int max_seqlen_q, int max_seqlen_k, float softmax_scale, int causal, float rescale_threshold=-1.0, int num_splits=0) -> "
+  "(Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_softcap_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _softcap_fwd_hip_torch_op(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, softcap, window_left, window_right, max_seqlen_q, max_seqlen_k,
+                              softmax_scale, causal, rescale_threshold=-1.0, num_splits=0):
+  return softcap_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, bool(causal), softmax_scale, float(softcap),
+                         (int(window_left), int(window_right)), rescale_threshold=rescale_threshold, return_lse=True, seqused_k=seqused_k, num_splits=num_splits,
+                         block_table=block_table)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_softcap_fwd_hip")
+def _softcap_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, softcap, window_left, window_right, max_seqlen_q, max_seqlen_k,
+                          softmax_scale, causal, rescale_threshold=-1.0, num_splits=0):
   total_q, heads, head_dim = q.shape
   return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
 

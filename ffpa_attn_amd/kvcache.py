@@ -14,7 +14,11 @@ synchronisation: the two launches capture into one HIP graph.  ``cache_seqlens``
 Local (sliding-window) attention has an entry of its own, ``ffpa_attn_with_kvcache_window`` (``window_size=(left, right)``, below): the KV tiles in front of
 the window are not read.  ``ffpa_attn_with_kvcache`` itself keeps refusing ``window_size``.
 
-Inference only: ``cache_batch_idx``, ``cache_leftpad``, softcap and ALiBi have no kernel-side implementation here and raise
+Logit soft-capping (Gemma 2, Grok-1: scores ``softcap * tanh(softmax_scale * q.k / softcap)``) has an entry of its own as well,
+``ffpa_attn_with_kvcache_softcap`` (``softcap=``, with or without ``window_size``, below): the cap is applied in the kernel, in front of the masks.  Every other
+entry point keeps refusing ``softcap``.
+
+Inference only: ``cache_batch_idx``, ``cache_leftpad`` and ALiBi have no kernel-side implementation here and raise
 ``NotImplementedError`` naming the option — as do ``k`` without ``v`` (or ``v`` without ``k``) and rotary tables without ``k`` / ``v`` or one without the other;
 a tensor that requires grad raises (there is no backward).
 """
@@ -399,6 +403,74 @@ def ffpa_attn_with_kvcache_window(
     kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
     cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
   o, lse = torch.ops.ffpa_attn._window_fwd_hip(qp, kp, vp, cu_q, cu_k, seqused, block_table, left, right, Sq, capacity, scale, 1 if causal else 0, -1.0, num_splits)
+  out = o.view(B, Sq, Hq, D)
+  if not return_softmax_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+# ---- logit soft-capping, with or without a sliding window: ffpa_attn_with_kvcache_softcap
+def ffpa_attn_with_kvcache_softcap(
+  q: torch.Tensor,
+  k_cache: torch.Tensor,
+  v_cache: torch.Tensor,
+  k: torch.Tensor | None = None,
+  v: torch.Tensor | None = None,
+  rotary_cos: torch.Tensor | None = None,
+  rotary_sin: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor | None" = None,
+  block_table: torch.Tensor | None = None,
+  *,
+  softcap: float,
+  window_size: tuple = (-1, -1),
+  softmax_scale: float | None = None,
+  causal: bool = False,
+  rotary_interleaved: bool = True,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+):
+  """``ffpa_attn_with_kvcache_window`` with LOGIT SOFT-CAPPING — FlashAttention's ``softcap``; Gemma 2 caps its attention logits at 50 in every layer (half of
+  them under a 4096-key window, half of them global), Grok-1 at 30.  With ``c = softcap > 0``
+
+      ``score(i, j) = c * tanh(softmax_scale * q_i . k_j / c)``;
+
+  the mask — the key length, the causal edge, the window's edges — is applied to the capped score (a hidden key has weight 0), and the softmax, O and the LSE
+  (natural log) are taken over the capped scores.  ONE attention launch of the packed / paged kernel's soft-capping build (the window build with the cap on: one
+  exp2 and one rcp per score, absolute tanh error <= 2^-21): ``window_size = (-1, -1)``, the default, walks the plain call's tiles, so the same kernel serves the
+  global and the local layers.
+
+  Shapes, dtypes, layouts, strides, paged or contiguous caches, GQA, the append of ``k`` / ``v`` with ``rotary_cos`` / ``rotary_sin``, ``window_size`` and its
+  errors, ``causal``, ``num_splits`` and the returns are ``ffpa_attn_with_kvcache_window``'s; a row that sees no key returns O = 0, LSE = -inf.  ``softcap`` must
+  be a real number (``TypeError`` otherwise, for a bool too), not negative, NaN or inf (``ValueError``); ``softcap == 0`` means "off" and forwards to
+  ``ffpa_attn_with_kvcache_window``: the same launch, the same bits.  Nothing is read back to the host: the call captures into one HIP graph, and a replay follows
+  ``cache_seqlens`` / ``block_table`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``."""
+  if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
+    raise TypeError(f"ffpa_attn_with_kvcache_softcap: softcap must be a real number, got {softcap!r}")
+  softcap = float(softcap)
+  if not 0.0 <= softcap < float("inf"):  # (NaN fails both comparisons)
+    raise ValueError(f"ffpa_attn_with_kvcache_softcap: softcap = {softcap} must be finite and >= 0 (0 = off)")
+  if window_size is None:
+    raise TypeError("ffpa_attn_with_kvcache_window: window_size must be a pair of ints (left, right), got None")
+  left, right = _window_pair(window_size)
+  if softcap == 0.0:
+    return ffpa_attn_with_kvcache_window(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, block_table, window_size=(left, right),
+                                         softmax_scale=softmax_scale, causal=causal, rotary_interleaved=rotary_interleaved, num_splits=num_splits,
+                                         return_softmax_lse=return_softmax_lse)
+  capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, None, None, block_table, softmax_scale, (-1, -1), 0.0,
+                                       None, num_splits)
+  q, seqused = _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal)
+  B, Sq, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  qp = q.reshape(B * Sq, Hq, D)
+  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device) if Sq > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
+  if block_table is not None:
+    kp, vp, cu_k = k_cache, v_cache, None
+  else:
+    # the contiguous cache as the packed call's seqused_k case (ffpa_attn_with_kvcache's view: sequence b's keys are rows b * capacity ...)
+    kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
+    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
+  o, lse = torch.ops.ffpa_attn._softcap_fwd_hip(qp, kp, vp, cu_q, cu_k, seqused, block_table, softcap, left, right, Sq, capacity, scale, 1 if causal else 0, -1.0,
+                                                num_splits)
   out = o.view(B, Sq, Hq, D)
   if not return_softmax_lse:
     return out

@@ -410,6 +410,24 @@ int ffpa_attn_varlen_window_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa
 int ffpa_attn_varlen_window_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, char* buf, size_t n);
 
 /*
+ * LOGIT SOFT-CAPPING (FlashAttention's softcap; Gemma 2 caps at 50, Grok-1 at 30) over the window call: with c = softcap,
+ *        score(t, j) = c * tanh(softmax_scale * q_t.k_j / c),
+ *   the mask — the key length, the causal edge, the window's edges — is applied to the CAPPED score (a hidden key has weight 0), and the softmax, O and the LSE
+ *   (natural log) are taken over the capped scores.  A token that sees no key gives O = 0, LSE = -inf.  w == NULL means no window, (-1, -1): one kernel family
+ *   (the *_softcap_kernel builds: the window builds with the cap on) serves capped layers with and without a window.  softcap must be finite and > 0: anything
+ *   else returns a status before any device work ("off" is the window call).  Every other check, the plan (row tiles, rows, keys per tile, workgroups, splits) and
+ *   the workspace are the window call's for the same (p, kv, w): the cap changes no tile count, and a split launch's partials are ordinary (O, LSE) states.
+ *   The tanh is one exp2 and one rcp per score, 1 - 2 / (1 + exp2(2 log2(e) y)): absolute error <= 2^-21, so a capped score is off by at most c * 2^-21.
+ */
+int ffpa_attn_varlen_softcap_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap, void* stream);
+
+/* As ffpa_attn_varlen_window_fwd_workspace_bytes / _plan / _kernel, for the soft-capping call ("ffpa_fwd_m16_paged_softcap_kernel<bf16, 512>"; a bad softcap:
+ * 0 bytes / a status). */
+size_t ffpa_attn_varlen_softcap_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap);
+int ffpa_attn_varlen_softcap_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap, int out[5]);
+int ffpa_attn_varlen_softcap_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap, char* buf, size_t n);
+
+/*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
  * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
  *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position
