@@ -69,6 +69,8 @@ def _units() -> list[Unit]:
   # inline asm — their assembly lands in directories the attention ISA rules do not read
   units.append(Unit("ffpa_kvcache_append.hip", "ffpa_kvcache_append.o", [], "temps_append", None, True, True))
   units.append(Unit("ffpa_merge_states.hip", "ffpa_merge_states.o", [], "temps_merge", None, True, True))
+  # the append for a ragged step (token rows packed by cu_seqlens_q, per-token rotary positions): shares ffpa_kvcache_append_rows.h with the [B, S] append
+  units.append(Unit("ffpa_kvcache_append_varlen.hip", "ffpa_kvcache_append_varlen.o", [], "temps_append_varlen", None, True, True))
   units.append(Unit("ffpa_capi.hip", "ffpa_capi.o", [], None, None, True, False))
   units.append(Unit("ffpa_capi.hip", "ffpa_capi_test.o", ["-DFFPA_INST_SAFE=1"], None, None, False, True))
   return units

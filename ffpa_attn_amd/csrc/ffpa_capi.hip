@@ -1580,6 +1580,87 @@ int ffpa_attn_kvcache_append(const ffpa_kv_append_params* p, const ffpa_paged_kv
   return FFPA_OK;
 }
 
+// ---- the same for a ragged step: token rows packed by cu_seqlens_q, optional per-token rotary positions (include/ffpa_attn.h: ffpa_kv_append_varlen_params)
+int ffpa_attn_kvcache_append_varlen(const ffpa_kv_append_varlen_params* p, const ffpa_paged_kv* kv, void* stream) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_kv_append_varlen_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_kv_append_varlen_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size,
+                sizeof(ffpa_kv_append_varlen_params), p->abi_version, FFPA_ATTN_ABI_VERSION);
+  if (p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
+  if (p->batch <= 0 || p->heads_q <= 0 || p->heads_kv <= 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "non-positive dimension: batch=%d Hq=%d Hkv=%d", p->batch, p->heads_q, p->heads_kv);
+  if (p->heads_q % p->heads_kv != 0) return fail(FFPA_ERR_BAD_SHAPE, "num_heads: Hq=%d is not a multiple of Hkv=%d", p->heads_q, p->heads_kv);
+  if (p->head_dim <= 0 || p->head_dim % 8 != 0 || p->head_dim > 1024)
+    return fail(FFPA_ERR_BAD_HEADDIM, "headdim not support! D=%d (supported: multiples of 8 in [8, 1024])", p->head_dim);
+  if (p->total_q < 0) return fail(FFPA_ERR_BAD_SHAPE, "total_q=%d must not be negative", p->total_q);
+  int rc;
+  int cap = p->capacity;
+  if (kv != nullptr) {
+    if ((rc = check_pool(kv)) != FFPA_OK) return rc;
+    cap = kv->pages_per_row * kv->page_size;
+  } else if (cap <= 0) {
+    return fail(FFPA_ERR_BAD_SHAPE, "capacity=%d of the contiguous cache must be positive", cap);
+  }
+  const int rd = p->rotary_dim;
+  if (rd < 0 || rd % 16 != 0 || rd > p->head_dim)
+    return fail(FFPA_ERR_BAD_SHAPE, "rotary_dim=%d must be a multiple of 16 in [0, head_dim=%d]", rd, p->head_dim);
+  if (rd > 0 && p->seqlen_ro < cap) return fail(FFPA_ERR_BAD_SHAPE, "seqlen_ro=%d rows of rotary_cos / rotary_sin is less than the capacity %d", p->seqlen_ro, cap);
+  const bool rows = p->total_q > 0, use_rot = rd > 0 && rows;
+  if (!p->k_cache || !p->v_cache || !p->seqused || !p->cache_seqlens || !p->cu_seqlens_q)
+    return fail(FFPA_ERR_NULL_POINTER, "k_cache / v_cache / seqused / cache_seqlens / cu_seqlens_q must be non-NULL");
+  if (rows && (!p->k || !p->v)) return fail(FFPA_ERR_NULL_POINTER, "k / v must be non-NULL when total_q > 0");
+  if (use_rot && (!p->rotary_cos || !p->rotary_sin))
+    return fail(FFPA_ERR_NULL_POINTER, "rotary_cos / rotary_sin must be non-NULL when rotary_dim > 0");
+  if (use_rot && (!p->q || !p->q_rot)) return fail(FFPA_ERR_NULL_POINTER, "q / q_rot must be non-NULL when rotary_dim > 0 and total_q > 0");
+  if (p->positions != nullptr && rd == 0) return fail(FFPA_ERR_BAD_SHAPE, "positions are rotary positions: they need rotary_dim > 0");
+  if (p->seqused == p->cache_seqlens) return fail(FFPA_ERR_BAD_SHAPE, "seqused must not be cache_seqlens (the kernel reads one while it writes the other)");
+  if ((reinterpret_cast<uintptr_t>(p->seqused) & 3u) || (reinterpret_cast<uintptr_t>(p->cache_seqlens) & 3u) ||
+      (reinterpret_cast<uintptr_t>(p->cu_seqlens_q) & 3u) || (reinterpret_cast<uintptr_t>(p->positions) & 3u))
+    return fail(FFPA_ERR_MISALIGNED, "seqused / cache_seqlens / cu_seqlens_q / positions must be 4-byte aligned");
+  if (!aligned16(p->k_cache) || !aligned16(p->v_cache) || (rows && (!aligned16(p->k) || !aligned16(p->v))) ||
+      (use_rot && (!aligned16(p->q) || !aligned16(p->q_rot) || !aligned16(p->rotary_cos) || !aligned16(p->rotary_sin))))
+    return fail(FFPA_ERR_MISALIGNED, "q / k / v / caches / q_rot / rotary_cos / rotary_sin base pointers must be 16-byte aligned");
+  if ((rc = check_strides("k_cache", p->k_cache_stride, 3)) || (rc = check_strides("v_cache", p->v_cache_stride, 3))) return rc;
+  if (rows && ((rc = check_strides("k", p->k_stride, 2)) || (rc = check_strides("v", p->v_stride, 2)))) return rc;
+  if (use_rot && ((rc = check_strides("q", p->q_stride, 2)) || (rc = check_strides("q_rot", p->q_rot_stride, 2)))) return rc;
+  if ((rc = check_device()) != FFPA_OK) return rc;
+
+  ffpa::KvAppendVarlenArgs va;
+  memset(&va, 0, sizeof(va));
+  ffpa::KvAppendArgs& a = va.a;
+  a.q = p->q, a.k = p->k, a.v = p->v;
+  a.kc = p->k_cache, a.vc = p->v_cache, a.q_rot = p->q_rot;
+  a.used = p->seqused, a.seqlens = p->cache_seqlens;
+  a.cos = p->rotary_cos, a.sin = p->rotary_sin;
+  va.cu_q = p->cu_seqlens_q, va.positions = p->positions;
+  for (int i = 0; i < 2; ++i) a.sq[i + 1] = p->q_stride[i], a.sk[i + 1] = p->k_stride[i], a.sv[i + 1] = p->v_stride[i], a.sqr[i + 1] = p->q_rot_stride[i];
+  a.skc[0] = p->k_cache_stride[1], a.skc[1] = p->k_cache_stride[2];
+  a.svc[0] = p->v_cache_stride[1], a.svc[1] = p->v_cache_stride[2];
+  if (kv != nullptr) {
+    a.table = kv->block_table, a.bt_stride = kv->bt_stride;
+    a.kc_page_stride = kv->k_page_stride, a.vc_page_stride = kv->v_page_stride;
+    a.page_size = kv->page_size, a.num_pages = kv->num_pages;
+  } else {
+    // one page per sequence: the slab of sequence b
+    a.kc_page_stride = p->k_cache_stride[0], a.vc_page_stride = p->v_cache_stride[0];
+    a.page_size = cap, a.num_pages = p->batch;
+  }
+  a.B = p->batch, a.Hq = p->heads_q, a.Hkv = p->heads_kv, a.D = p->head_dim;
+  a.cap = cap, a.seqlen_ro = p->seqlen_ro, a.rd = rd, a.causal = p->causal ? 1 : 0, a.T = p->total_q;
+  const bool interleaved = rd == 0 || p->rotary_interleaved != 0;
+  a.units = interleaved ? p->head_dim / 8 : rd / 16 + (p->head_dim - rd) / 8;
+  a.slots = 256 / a.units;
+  const int heads = rd > 0 ? std::max(p->heads_q, p->heads_kv) : p->heads_kv;
+  // workgroups per token row: the [B, S] append's rule (few token rows: spread a row's heads over up to one per lane until the grid covers the CUs)
+  const int per_wg = a.slots * ffpa::kAppendHeadsPerLane;
+  const int64_t grid_rows = std::max(1, p->total_q);
+  const int64_t fill = ((int64_t)device_cu_count() + grid_rows - 1) / grid_rows;
+  const int grid_y = std::max((heads + per_wg - 1) / per_wg, (int)std::min<int64_t>((heads + a.slots - 1) / a.slots, fill));
+  const int st = ffpa::launch_kv_append_varlen(p->dtype, interleaved, va, (unsigned)grid_y, static_cast<hipStream_t>(stream));
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "kv append (varlen) launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
+}
+
 // ---- the merge of two attention states (include/ffpa_attn.h: ffpa_merge_states_params)
 int ffpa_attn_merge_states(const ffpa_merge_states_params* p, void* stream) {
   if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");

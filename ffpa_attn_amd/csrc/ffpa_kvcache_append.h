@@ -44,4 +44,16 @@ constexpr int kAppendHeadsPerLane = 4;
 // grid = (B * T, y): y workgroups of `slots` x kAppendHeadsPerLane heads per token row.  Returns a hipError_t.
 int launch_kv_append(int dtype, bool interleaved, const KvAppendArgs& a, unsigned grid_y, hipStream_t stream);
 
+// The packed-token form (ffpa_attn_kvcache_append_varlen, ffpa_kvcache_append_varlen.hip): q / k / v are [total, H, D] token rows packed by cu_q, one grid row
+// per token.  `a` holds what both forms share — the pools, the table, the rotary tables, the head geometry — with a.sq / sk / sv / sqr = {unused, row, head},
+// a.B the sequences and a.T = total the token rows; a.Sq / a.Snew are not read (every token row is a query row and a new key).
+struct KvAppendVarlenArgs {
+  KvAppendArgs a;
+  const int* cu_q;       // [B + 1]: token row t belongs to the sequence b with cu_q[b] <= t < cu_q[b + 1]; rows from cu_q[B] on are padding
+  const int* positions;  // [total] rotary position of token row t (key AND query), or nullptr = the slot rule of the [B, S] form
+};
+
+// grid = (max(total, ceil(B / 256)), y): workgroup row t is token row t (if t < total); the first ceil(B / 256) rows of y == 0 also write used[].  Returns a hipError_t.
+int launch_kv_append_varlen(int dtype, bool interleaved, const KvAppendVarlenArgs& va, unsigned grid_y, hipStream_t stream);
+
 }  // namespace ffpa

@@ -236,6 +236,45 @@ class FfpaKvAppendParams(ctypes.Structure):
   ]
 
 
+class FfpaKvAppendVarlenParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_kv_append_varlen_params`` (include/ffpa_attn.h): the KV-cache append + rotary call of a ragged step."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("abi_version", ctypes.c_uint32),
+    ("q", ctypes.c_void_p),
+    ("k", ctypes.c_void_p),
+    ("v", ctypes.c_void_p),
+    ("k_cache", ctypes.c_void_p),
+    ("v_cache", ctypes.c_void_p),
+    ("q_rot", ctypes.c_void_p),
+    ("seqused", ctypes.c_void_p),
+    ("cache_seqlens", ctypes.c_void_p),
+    ("cu_seqlens_q", ctypes.c_void_p),
+    ("positions", ctypes.c_void_p),
+    ("rotary_cos", ctypes.c_void_p),
+    ("rotary_sin", ctypes.c_void_p),
+    ("batch", ctypes.c_int32),
+    ("heads_q", ctypes.c_int32),
+    ("heads_kv", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("total_q", ctypes.c_int32),
+    ("capacity", ctypes.c_int32),
+    ("seqlen_ro", ctypes.c_int32),
+    ("rotary_dim", ctypes.c_int32),
+    ("q_stride", ctypes.c_int64 * 2),
+    ("k_stride", ctypes.c_int64 * 2),
+    ("v_stride", ctypes.c_int64 * 2),
+    ("q_rot_stride", ctypes.c_int64 * 2),
+    ("k_cache_stride", ctypes.c_int64 * 3),
+    ("v_cache_stride", ctypes.c_int64 * 3),
+    ("rotary_interleaved", ctypes.c_int32),
+    ("causal", ctypes.c_int32),
+    ("dtype", ctypes.c_int32),
+    ("reserved", ctypes.c_int32),
+  ]
+
+
 class FfpaMergeStatesParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_merge_states_params`` (include/ffpa_attn.h): the merge of two attention states."""
 
@@ -302,6 +341,7 @@ _BINDINGS = (
   ("ffpa_attn_varlen_softcap_fwd_kernel", _SOFTCAP + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_softcap_fwd_workspace_bytes", _SOFTCAP, _SIZE, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
+  ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
   ("ffpa_attn_query", [_INT], _INT, 0),
   ("ffpa_attn_fwd_tile_config", [_INT, _P(_INT), _P(_INT), _P(_INT)], _INT, 0),
@@ -1465,6 +1505,88 @@ def _kvcache_append_hip_torch_op(q, k_cache, v_cache, k, v, cache_seqlens, block
 def _kvcache_append_hip_fake(q, k_cache, v_cache, k, v, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, causal):
   q_rot = q.new_empty(tuple(q.shape) if rotary_cos is not None else (0,))
   return q_rot, q.new_empty((q.size(0),), dtype=torch.int32)
+
+
+# The same for a ragged step (ffpa_attn_varlen_with_kvcache): token rows packed by cu_seqlens_q, optional per-token rotary positions
+def kvcache_append_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor,
+                          cache_seqlens: torch.Tensor, block_table: "torch.Tensor | None" = None, rotary_cos: "torch.Tensor | None" = None,
+                          rotary_sin: "torch.Tensor | None" = None, positions: "torch.Tensor | None" = None, rotary_interleaved: bool = True, causal: bool = False):
+  """One launch of ``ffpa_attn_kvcache_append_varlen``: ``k`` / ``v [T, Hkv, D]``, packed by the int32 device ``cu_seqlens_q [B + 1]`` like ``q [T, Hq, D]``, written
+  into the caches in place — key i of sequence b at ``cache_seqlens[b] + i`` (``k`` rotated when ``rotary_cos`` / ``rotary_sin`` are given: at that position, or at
+  ``positions[t]`` with the int32 ``positions [T]``) -> ``(q_rot, seqused)``: ``q`` rotated (an empty tensor without rotary) and the int32 ``[B]`` post-append lengths
+  ``min(max(cache_seqlens, 0) + Sq_b, capacity)``.  Contiguous caches ``[B, capacity, Hkv, D]``, or page pools with ``block_table``.  Token rows at or past
+  ``cu_seqlens_q[B]`` write nothing.  Asynchronous, nothing read back to the host."""
+  name = "ffpa_attn::_kvcache_append_varlen_hip"
+  if not q.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
+  lib = load_library()
+  T, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  B = cu_seqlens_q.numel() - 1
+  rot = rotary_cos is not None
+  q_rot = torch.empty((T, Hq, D) if rot else (0,), dtype=q.dtype, device=q.device)
+  seqused = torch.empty((B,), dtype=torch.int32, device=q.device)
+  if B <= 0:
+    return q_rot, seqused
+  for nm, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+    if not _layout_ok(t):
+      raise ValueError(f"{name}: {nm} is written in place and needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base")
+  k, v = _rows(k), _rows(v)
+  if rot:
+    q = _rows(q)
+  cache_seqlens, cu_seqlens_q = cache_seqlens.contiguous(), cu_seqlens_q.contiguous()
+  p = _stamped(FfpaKvAppendVarlenParams)
+  p.k_cache, p.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
+  p.seqused, p.cache_seqlens, p.cu_seqlens_q = seqused.data_ptr(), cache_seqlens.data_ptr(), cu_seqlens_q.data_ptr()
+  p.batch, p.heads_q, p.heads_kv, p.head_dim, p.total_q = B, Hq, Hkv, D, T
+  p.k_cache_stride[:] = list(k_cache.stride()[:3])
+  p.v_cache_stride[:] = list(v_cache.stride()[:3])
+  if T > 0:
+    p.k, p.v = k.data_ptr(), v.data_ptr()
+    p.k_stride[:] = list(k.stride()[:2])
+    p.v_stride[:] = list(v.stride()[:2])
+  if rot:
+    p.q, p.q_rot = q.data_ptr(), q_rot.data_ptr()
+    p.q_stride[:] = list(q.stride()[:2])
+    p.q_rot_stride[:] = list(q_rot.stride()[:2])
+    p.rotary_cos, p.rotary_sin = rotary_cos.data_ptr(), rotary_sin.data_ptr()
+    p.seqlen_ro = rotary_cos.size(0)
+    p.rotary_dim = 2 * rotary_cos.size(1)
+    p.rotary_interleaved = 1 if rotary_interleaved else 0
+    if positions is not None:
+      positions = positions.contiguous()
+      p.positions = positions.data_ptr()
+  p.causal = 1 if causal else 0
+  p.dtype = _DTYPE[q.dtype]
+  kv = None
+  if block_table is not None:
+    kv, block_table = _paged_kv_of(block_table, k_cache, v_cache)
+  else:
+    p.capacity = k_cache.size(1)
+  rc = _call_on_stream(lib.ffpa_attn_kvcache_append_varlen, q.device, ctypes.byref(p), ctypes.byref(kv) if kv is not None else None)
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_kvcache_append_varlen")
+  return q_rot, seqused
+
+
+torch.library.define(
+  f"{_OP_NAMESPACE}::_kvcache_append_varlen_hip",
+  "(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cache_seqlens, Tensor? block_table, Tensor? rotary_cos, "
+  "Tensor? rotary_sin, Tensor? positions, bool rotary_interleaved, bool causal) -> (Tensor q_rot, Tensor seqused)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_kvcache_append_varlen_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _kvcache_append_varlen_hip_torch_op(q, k_cache, v_cache, k, v, cu_seqlens_q, cache_seqlens, block_table, rotary_cos, rotary_sin, positions, rotary_interleaved,
+                                        causal):
+  return kvcache_append_varlen(q, k_cache, v_cache, k, v, cu_seqlens_q, cache_seqlens, block_table, rotary_cos, rotary_sin, positions, rotary_interleaved, causal)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_kvcache_append_varlen_hip")
+def _kvcache_append_varlen_hip_fake(q, k_cache, v_cache, k, v, cu_seqlens_q, cache_seqlens, block_table, rotary_cos, rotary_sin, positions, rotary_interleaved,
+                                    causal):
+  q_rot = q.new_empty(tuple(q.shape) if rotary_cos is not None else (0,))
+  return q_rot, q.new_empty((cu_seqlens_q.size(0) - 1,), dtype=torch.int32)
 
 
 # The merge of two attention states (ffpa_merge_attn_states; the last launch of ffpa_attn_with_kvcache_cascade)

@@ -351,6 +351,23 @@ def _window_pair(window_size) -> "tuple[int, int]":
   return min(left, 0x7FFFFFFF), min(right, 0x7FFFFFFF)
 
 
+def _window_arg(window_size) -> "tuple[int, int]":
+  """``window_size`` as the window, softcap and ragged calls take it: ``_window_pair``, with None refused by the same TypeError."""
+  if window_size is None:
+    raise TypeError("ffpa_attn_with_kvcache_window: window_size must be a pair of ints (left, right), got None")
+  return _window_pair(window_size)
+
+
+def _softcap_arg(softcap) -> float:
+  """``softcap`` as the softcap and ragged calls take it: a real number (not a bool), finite and >= 0 (0 = off)."""
+  if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
+    raise TypeError(f"ffpa_attn_with_kvcache_softcap: softcap must be a real number, got {softcap!r}")
+  softcap = float(softcap)
+  if not 0.0 <= softcap < float("inf"):  # (NaN fails both comparisons)
+    raise ValueError(f"ffpa_attn_with_kvcache_softcap: softcap = {softcap} must be finite and >= 0 (0 = off)")
+  return softcap
+
+
 def ffpa_attn_with_kvcache_window(
   q: torch.Tensor,
   k_cache: torch.Tensor,
@@ -386,9 +403,7 @@ def ffpa_attn_with_kvcache_window(
   ``causal=True`` means ``right = 0`` whatever ``right`` was given.  ``(-1, -1)`` is ``ffpa_attn_with_kvcache`` and ``(-1, 0)`` its causal call, to the bit (bf16).
   A row that sees no key returns O = 0, LSE = -inf.  Nothing is read back to the host: the call captures into one HIP graph, and a replay follows
   ``cache_seqlens`` / ``block_table`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``."""
-  if window_size is None:
-    raise TypeError("ffpa_attn_with_kvcache_window: window_size must be a pair of ints (left, right), got None")
-  left, right = _window_pair(window_size)
+  left, right = _window_arg(window_size)
   capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, None, None, block_table, softmax_scale, (-1, -1), 0.0,
                                        None, num_splits)
   q, seqused = _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal)
@@ -444,14 +459,8 @@ def ffpa_attn_with_kvcache_softcap(
   be a real number (``TypeError`` otherwise, for a bool too), not negative, NaN or inf (``ValueError``); ``softcap == 0`` means "off" and forwards to
   ``ffpa_attn_with_kvcache_window``: the same launch, the same bits.  Nothing is read back to the host: the call captures into one HIP graph, and a replay follows
   ``cache_seqlens`` / ``block_table`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``."""
-  if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
-    raise TypeError(f"ffpa_attn_with_kvcache_softcap: softcap must be a real number, got {softcap!r}")
-  softcap = float(softcap)
-  if not 0.0 <= softcap < float("inf"):  # (NaN fails both comparisons)
-    raise ValueError(f"ffpa_attn_with_kvcache_softcap: softcap = {softcap} must be finite and >= 0 (0 = off)")
-  if window_size is None:
-    raise TypeError("ffpa_attn_with_kvcache_window: window_size must be a pair of ints (left, right), got None")
-  left, right = _window_pair(window_size)
+  softcap = _softcap_arg(softcap)
+  left, right = _window_arg(window_size)
   if softcap == 0.0:
     return ffpa_attn_with_kvcache_window(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, block_table, window_size=(left, right),
                                          softmax_scale=softmax_scale, causal=causal, rotary_interleaved=rotary_interleaved, num_splits=num_splits,
@@ -475,6 +484,197 @@ def ffpa_attn_with_kvcache_softcap(
   if not return_softmax_lse:
     return out
   return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+# ---- ragged query batches (continuous batching, chunked prefill): ffpa_attn_varlen_with_kvcache
+def _validate_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k, v, rotary_cos, rotary_sin, positions, softmax_scale, num_splits):
+  """Every host-side check of ffpa_attn_varlen_with_kvcache but ``window_size`` / ``softcap`` (nothing read from the device, nothing launched)
+  -> (batch, capacity, softmax scale)."""
+  name = "ffpa_attn_varlen_with_kvcache"
+  append = k is not None and v is not None
+  rotary = rotary_cos is not None and rotary_sin is not None
+  bad = [n for n, t, ok in (("k", k, append), ("v", v, append), ("rotary_cos", rotary_cos, rotary and append), ("rotary_sin", rotary_sin, rotary and append),
+                            ("positions", positions, rotary and append)) if t is not None and not ok]
+  if bad:
+    raise NotImplementedError(f"{name} does not support: {', '.join(bad)} (k and v only together, rotary_cos and rotary_sin only together and with k / v, "
+                              "positions only with the rotary tables)")
+  for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("cu_seqlens_q", cu_seqlens_q), ("cache_seqlens", cache_seqlens)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {n} must be a tensor, got {type(t).__name__}")
+  for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("k", k), ("v", v)):
+    if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {n} requires grad and there is no backward")
+  if q.dtype not in _DTYPES or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q/k_cache/v_cache of one dtype, got {q.dtype}, {k_cache.dtype}, {v_cache.dtype}")
+  if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
+    raise ValueError(f"{name}: q must be packed [T, Hq, D] and k_cache / v_cache 4-D")
+  if k_cache.shape != v_cache.shape:
+    raise ValueError(f"{name}: k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} must share their shape")
+  T, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  if k_cache.size(3) != D:
+    raise ValueError(f"{name}: head dim of the cache ({k_cache.size(3)}) differs from q's ({D})")
+  if D % 8 != 0 or D > 1024 or D <= 0:
+    raise ValueError(f"{name}: head dim {D} is not a multiple of 8 in [8, 1024]")
+  if Hkv == 0 or Hq % Hkv != 0:
+    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of key/value num_heads ({Hkv})")
+  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
+  if cu_seqlens_q.dtype != torch.int32:
+    raise TypeError(f"{name}: cu_seqlens_q must be int32, got {cu_seqlens_q.dtype}")
+  if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.stride(0) != 1 or cu_seqlens_q.device != q.device:
+    raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor [batch + 1] of unit stride on q's device, got {tuple(cu_seqlens_q.shape)} on {cu_seqlens_q.device}")
+  B = cu_seqlens_q.numel() - 1
+  if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or (T > 0 and max_seqlen_q < 1):
+    raise ValueError(f"{name}: max_seqlen_q must be a host int >= 1 (>= 0 without a token) that bounds every sequence's tokens, got {max_seqlen_q!r}")
+  if cache_seqlens.dtype != torch.int32:
+    raise TypeError(f"{name}: cache_seqlens must be int32, got {cache_seqlens.dtype}")
+  if cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
+    raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [batch={B}] on q's device, got {tuple(cache_seqlens.shape)} on {cache_seqlens.device}")
+  if block_table is not None:
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B:
+      raise ValueError(f"{name}: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
+    if block_table.size(1) == 0:
+      raise ValueError(f"{name}: block_table needs at least one page per sequence")
+    page_size = k_cache.size(1)
+    if page_size <= 0 or page_size % 64 != 0:
+      raise ValueError(f"{name}: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
+    if block_table.device != q.device:
+      raise ValueError(f"{name}: block_table must be on q's device, got {block_table.device} and {q.device}")
+    capacity = block_table.size(1) * page_size
+  else:
+    if k_cache.size(0) != B:
+      raise ValueError(f"{name}: k_cache [B, capacity, Hkv, D] must have cu_seqlens_q's batch ({B}), got {k_cache.size(0)}")
+    capacity = k_cache.size(1)
+  if k_cache.device != q.device or v_cache.device != q.device:
+    raise ValueError(f"{name}: q / k_cache / v_cache must be on one device, got {q.device}, {k_cache.device}, {v_cache.device}")
+  scale = float(softmax_scale) if softmax_scale is not None else D ** -0.5
+  if not append:
+    return B, capacity, scale
+  for n, t in (("k", k), ("v", v)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {n} must be a tensor, got {type(t).__name__}")
+    if t.dtype != q.dtype:
+      raise TypeError(f"{name}: {n} must have the cache's dtype {q.dtype}, got {t.dtype}")
+    if t.device != q.device:
+      raise ValueError(f"{name}: {n} must be on q's device, got {t.device} and {q.device}")
+    if t.dim() != 3 or t.size(0) != T or t.size(1) != Hkv or t.size(2) != D:
+      raise ValueError(f"{name}: {n} must be [T={T}, Hkv={Hkv}, D={D}] (packed by cu_seqlens_q like q), got {tuple(t.shape)}")
+    if t.stride(-1) != 1:
+      raise ValueError(f"{name}: {n} must have a contiguous last dimension")
+  if not rotary:
+    return B, capacity, scale
+  for n, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {n} must be a tensor, got {type(t).__name__}")
+    if t.dtype != q.dtype:
+      raise TypeError(f"{name}: {n} must have q's dtype {q.dtype}, got {t.dtype}")
+    if t.device != q.device:
+      raise ValueError(f"{name}: {n} must be on q's device, got {t.device} and {q.device}")
+    if t.dim() != 2 or not t.is_contiguous():
+      raise ValueError(f"{name}: {n} must be a contiguous [seqlen_ro, rotary_dim / 2] tensor, got {tuple(t.shape)}")
+  if rotary_cos.shape != rotary_sin.shape:
+    raise ValueError(f"{name}: rotary_cos {tuple(rotary_cos.shape)} and rotary_sin {tuple(rotary_sin.shape)} must share their shape")
+  rotary_dim = 2 * rotary_cos.size(1)
+  if rotary_dim == 0 or rotary_dim % 16 != 0 or rotary_dim > D:
+    raise ValueError(f"{name}: rotary_dim ({rotary_dim}) must be a positive multiple of 16 and at most the head dim ({D})")
+  if rotary_cos.size(0) < capacity:
+    raise ValueError(f"{name}: rotary_cos / rotary_sin have {rotary_cos.size(0)} rows (seqlen_ro), fewer than the cache capacity {capacity}")
+  if positions is not None:
+    if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32:
+      raise TypeError(f"{name}: positions must be an int32 tensor, got {positions.dtype if isinstance(positions, torch.Tensor) else type(positions).__name__}")
+    if positions.dim() != 1 or positions.numel() != T or positions.stride(0) != 1 or positions.device != q.device:
+      raise ValueError(f"{name}: positions must be int32 [T={T}] of unit stride on q's device, got {tuple(positions.shape)} on {positions.device}")
+  return B, capacity, scale
+
+
+def ffpa_attn_varlen_with_kvcache(
+  q: torch.Tensor,
+  k_cache: torch.Tensor,
+  v_cache: torch.Tensor,
+  cu_seqlens_q: torch.Tensor,
+  max_seqlen_q: int,
+  cache_seqlens: torch.Tensor,
+  block_table: torch.Tensor | None = None,
+  k: torch.Tensor | None = None,
+  v: torch.Tensor | None = None,
+  rotary_cos: torch.Tensor | None = None,
+  rotary_sin: torch.Tensor | None = None,
+  positions: torch.Tensor | None = None,
+  *,
+  softmax_scale: float | None = None,
+  causal: bool = False,
+  window_size: tuple = (-1, -1),
+  softcap: float = 0.0,
+  rotary_interleaved: bool = True,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+):
+  """``ffpa_attn_with_kvcache`` for a RAGGED step — the batch of a continuous-batching engine with chunked prefill: a prompt chunk of hundreds of tokens, a few
+  speculative verifications of 3 - 5 and dozens of one-token decodes in ONE call; FlashAttention's ``flash_attn_varlen_func(..., seqused_k=, block_table=)`` plus
+  its cache append.  ``q [T, Hq, D]`` holds every sequence's query tokens packed by ``cu_seqlens_q`` (int32 ``[B + 1]``, on the device, unit stride: sequence b
+  owns rows ``cu_seqlens_q[b] ... cu_seqlens_q[b + 1]``, ``Sq_b`` of them; empty sequences are legal anywhere).  ``max_seqlen_q`` (a host int) is a CONTRACT, as
+  in ``ffpa_attn_varlen_func``: every ``Sq_b <= max_seqlen_q``; it is not checked (that would need a host read).  ``cache_seqlens`` (int32 ``[B]``, on the
+  device, required): the keys each sequence's cache holds BEFORE this call's append.  The caches, ``block_table``, dtypes, layouts and strides are
+  ``ffpa_attn_with_kvcache``'s — B comes from ``cu_seqlens_q``, a contiguous cache is ``[B, capacity, Hkv, D]``.
+
+  ``k`` / ``v [T, Hkv, D]`` (packed by the same ``cu_seqlens_q``: the step's new keys are its query tokens): ONE launch in front of the attention launch
+  (``ffpa_attn::_kvcache_append_varlen_hip``; every token row finds its sequence by a binary search of ``cu_seqlens_q`` on the device) writes key i of sequence b
+  in place at cache position ``max(cache_seqlens[b], 0) + i``, positions at or past the capacity dropped.  With ``rotary_cos`` / ``rotary_sin`` (they require
+  ``k`` / ``v``) the keys are stored rotated and a rotated copy of q attends — key i at position ``cache_seqlens[b] + i``, query token i at the same position
+  under ``causal``, at ``cache_seqlens[b]`` otherwise (``ffpa_attn_with_kvcache``'s rule).  ``positions`` (int32 ``[T]``, on q's device, unit stride; requires
+  the rotary tables; ``TypeError`` for another dtype, ``ValueError`` for another shape): key AND query token of row t rotate at ``positions[t]`` instead — the key
+  is still written at its slot.  This is the tree-draft case, where a node's position is its depth and not its slot.  Positions are clamped to
+  ``[0, seqlen_ro - 1]``.  On a uniform batch the append writes the bytes ``ffpa_attn_with_kvcache``'s does.
+
+  Attention for sequence b runs over ``L_b`` keys — ``min(max(cache_seqlens[b], 0) + Sq_b, capacity)`` with ``k`` / ``v``, else ``cache_seqlens[b]`` clamped to
+  ``[0, capacity]`` — with query token i at ``pos_i = i + L_b - Sq_b`` (bottom-right aligned per sequence).  ``causal``, ``window_size`` and ``softcap`` mean what
+  they mean in ``ffpa_attn_with_kvcache``, ``_window`` and ``_softcap`` (and raise what those raise): ``softcap > 0`` takes the soft-capping launch, otherwise a
+  window other than ``(-1, -1)`` the window launch, otherwise the paged launch — or the packed ``seqused_k`` launch for a contiguous cache.  The attention
+  kernels are those calls' kernels, which read ``cu_seqlens_q`` and the key lengths per sequence on the device.  GQA row packing stays a launch-wide decision
+  (``Hq / Hkv x max_seqlen_q`` fits a row tile): the decodes of a batch that also holds a long chunk run unpacked.  A row that sees no key returns O = 0,
+  LSE = -inf.  ``cache_seqlens`` is not advanced.  There is no tree mask here.
+
+  Returns ``out [T, Hq, D]`` — and, with ``return_softmax_lse``, the fp32 ``lse [Hq, T]`` (the layout of ``ffpa_attn_varlen_func``).  Rows at or past
+  ``cu_seqlens_q[B]`` (padding: T may exceed it) are unspecified, and nothing is appended for them.  ``T == 0`` returns empty tensors and launches nothing.
+  Nothing is read back to the host: the call captures into one HIP graph, and a replay follows ``q``, ``cu_seqlens_q`` (same T, same bound), ``cache_seqlens``,
+  ``block_table`` and ``positions`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``."""
+  from . import hip  # (registers the ffpa_attn ops)
+
+  softcap = _softcap_arg(softcap)
+  left, right = _window_arg(window_size)
+  B, capacity, scale = _validate_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k, v, rotary_cos, rotary_sin, positions,
+                                        softmax_scale, num_splits)
+  T, Hq, D = q.shape
+  Hkv = k_cache.size(2)
+  if T == 0:
+    out = q.new_empty((0, Hq, D))
+    return (out, torch.empty((Hq, 0), dtype=torch.float32, device=q.device)) if return_softmax_lse else out
+  seqused = cache_seqlens
+  if k is not None:
+    # the prepare launch: new keys into the cache (in place), rotated q, post-append lengths — read by the attention launch below on the same stream
+    q_rot, seqused = torch.ops.ffpa_attn._kvcache_append_varlen_hip(q, k_cache, v_cache, k, v, cu_seqlens_q, cache_seqlens, block_table, rotary_cos, rotary_sin,
+                                                                    positions, bool(rotary_interleaved), bool(causal))
+    if rotary_cos is not None:
+      q = q_rot
+  if block_table is not None:
+    kp, vp, cu_k = k_cache, v_cache, None
+  else:
+    # the contiguous cache as the packed call's seqused_k case (ffpa_attn_with_kvcache's view: sequence b's keys are rows b * capacity ...)
+    kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
+    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
+  c = 1 if causal else 0
+  if softcap > 0.0:
+    o, lse = torch.ops.ffpa_attn._softcap_fwd_hip(q, kp, vp, cu_seqlens_q, cu_k, seqused, block_table, softcap, left, right, max_seqlen_q, capacity, scale, c, -1.0,
+                                                  num_splits)
+  elif (left, right) != (-1, -1):
+    o, lse = torch.ops.ffpa_attn._window_fwd_hip(q, kp, vp, cu_seqlens_q, cu_k, seqused, block_table, left, right, max_seqlen_q, capacity, scale, c, -1.0, num_splits)
+  elif block_table is not None:
+    o, lse = torch.ops.ffpa_attn._paged_fwd_hip(q, kp, vp, cu_seqlens_q, seqused, block_table, max_seqlen_q, capacity, scale, c, -1.0, num_splits)
+  else:
+    o, lse = hip.varlen_forward(q, kp, vp, cu_seqlens_q, cu_k, max_seqlen_q, capacity, bool(causal), scale, return_lse=return_softmax_lse, seqused_k=seqused,
+                                num_splits=num_splits)
+  return (o, lse) if return_softmax_lse else o
 
 
 # ---- cascade (shared-prefix) attention: ffpa_attn_with_kvcache_cascade

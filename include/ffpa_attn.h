@@ -487,6 +487,65 @@ typedef struct ffpa_kv_append_params {
 int ffpa_attn_kvcache_append(const ffpa_kv_append_params* p, const ffpa_paged_kv* kv, void* stream);
 
 /*
+ * KV-CACHE APPEND + ROTARY FOR A RAGGED STEP (FlashAttention's flash_attn_varlen_func with seqused_k and block_table, plus its cache append) — the append above
+ * for the batch a continuous-batching engine steps with: a prompt chunk, a few speculative verifications and dozens of one-token decodes, packed as token rows.
+ * q [total_q, heads_q, D] and k, v [total_q, heads_kv, D] by q_stride / k_stride / v_stride = {row, head} are packed by cu_seqlens_q (device int32
+ * [batch + 1], ascending from 0): token row t belongs to the sequence b with cu_seqlens_q[b] <= t < cu_seqlens_q[b + 1], found on the device, as its token
+ * i = t - cu_seqlens_q[b].  Empty sequences are legal anywhere; rows from cu_seqlens_q[batch] on (total_q may exceed it) are padding: nothing is written for them.
+ * ONE kernel on `stream`:
+ *   * key i of sequence b is written at cache position pos = max(cache_seqlens[b], 0) + i — the cache addressing (contiguous or paged, ids clamped, positions at
+ *     or past the capacity dropped) is that of the append above; the block table is never read past its row.
+ *   * rotary_dim > 0: the first rotary_dim dims of the new keys are stored rotated and q is written rotated to q_rot ([total_q, heads_q, D] by q_rot_stride).
+ *     positions == NULL: key i at pos, query token i at pos when causal, at max(cache_seqlens[b], 0) otherwise (the rule above).  positions != NULL (device
+ *     int32 [total_q]): the key AND the query token of row t at positions[t] — the key is still written at its slot pos (a tree draft: the position is the
+ *     depth, not the slot).  Positions are clamped to [0, seqlen_ro - 1].  The pairing, the arithmetic and the rounding are those of the append above: on a
+ *     uniform batch the two calls write the same bytes.
+ *   * seqused[b] = min(max(cache_seqlens[b], 0) + (cu_seqlens_q[b + 1] - cu_seqlens_q[b]), capacity) for every b < batch, sequences without a token too.
+ */
+typedef struct ffpa_kv_append_varlen_params {
+  uint32_t struct_size; /* sizeof(ffpa_kv_append_varlen_params), checked */
+  uint32_t abi_version; /* FFPA_ATTN_ABI_VERSION                          */
+
+  const void* q;          /* [total_q, heads_q, D]; read only with rotary_dim > 0 */
+  const void* k;          /* [total_q, heads_kv, D] */
+  const void* v;
+  void* k_cache;          /* written in place */
+  void* v_cache;
+  void* q_rot;            /* out, [total_q, heads_q, D]: rotated q (rotary_dim > 0 only, else may be NULL) */
+  int32_t* seqused;       /* out, device [batch] */
+  const int32_t* cache_seqlens; /* device [batch], not modified */
+  const int32_t* cu_seqlens_q;  /* device [batch + 1] */
+  const int32_t* positions;     /* device [total_q] or NULL; read only with rotary_dim > 0 */
+  const void* rotary_cos; /* [seqlen_ro, rotary_dim / 2]; rotary_dim > 0 only */
+  const void* rotary_sin;
+
+  int32_t batch;
+  int32_t heads_q;
+  int32_t heads_kv;
+  int32_t head_dim;   /* a multiple of 8 in [8, 1024] */
+  int32_t total_q;    /* >= 0: token rows of q / k / v (the grid); 0 = only seqused is written */
+  int32_t capacity;   /* keys a sequence's contiguous cache holds; ignored when paged */
+  int32_t seqlen_ro;  /* rows of rotary_cos / rotary_sin (>= the capacity) */
+  int32_t rotary_dim; /* 0 = no rotary; else a multiple of 16 <= head_dim */
+
+  int64_t q_stride[2];       /* elements: row, head (head-dim stride 1) */
+  int64_t k_stride[2];
+  int64_t v_stride[2];
+  int64_t q_rot_stride[2];
+  int64_t k_cache_stride[3]; /* batch (ignored when paged), row, head */
+  int64_t v_cache_stride[3];
+
+  int32_t rotary_interleaved; /* 1: pairs (2j, 2j + 1); 0: pairs (j, j + rotary_dim / 2) */
+  int32_t causal;             /* query positions without `positions`: see above */
+  int32_t dtype;              /* enum ffpa_dtype: q, k, v, the caches, q_rot, cos / sin */
+  int32_t reserved;           /* 0 */
+} ffpa_kv_append_varlen_params;
+
+/* Launch the ragged append on `stream` of the CURRENT device (kv: the paged pool, NULL = contiguous cache [batch, capacity, heads_kv, D]).  Asynchronous: no
+ * allocation, no synchronisation; every bad argument returns a status before any device work.  Returns an ffpa_status. */
+int ffpa_attn_kvcache_append_varlen(const ffpa_kv_append_varlen_params* p, const ffpa_paged_kv* kv, void* stream);
+
+/*
  * MERGE OF TWO ATTENTION STATES (FlashInfer's / vLLM's merge_attn_states) — the last launch of a cascade (shared-prefix) attention step: two attentions of the
  * same queries over two disjoint key sets, each normalised on its own, combined into the attention over the union.  Per (token t, head h) row, in fp32:
  *     m = max(lse_a, lse_b),  w_x = exp(lse_x - m),  O = (w_a O_a + w_b O_b) / (w_a + w_b),  LSE = m + ln(w_a + w_b)
