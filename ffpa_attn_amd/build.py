@@ -36,6 +36,8 @@ HEAD_DIMS = [64 * i for i in range(1, 17)]
 SAFE_HEAD_DIMS = {64, 128, 320, 512, 640, 1024}
 # head dims the packed-sequence kernel is built for (FFPA_FOR_EACH_VARLEN_HEAD_DIM, csrc/ffpa_launch.h): the 16x16x32 build's
 VARLEN_HEAD_DIMS = [d for d in HEAD_DIMS if d >= 128]
+# (head dim, value width) pairs the MLA latent-cache kernel is built for (FFPA_FOR_EACH_MLA_BUILD, csrc/ffpa_mla.h)
+MLA_BUILDS = [(576, 512)]
 
 ARCH = "gfx950"
 CXXFLAGS = [
@@ -65,6 +67,9 @@ def _units() -> list[Unit]:
   # the packed-sequence kernel and its paged-KV twin: a TU of their own per head dim of the 16x16x32 build
   for kind in ("varlen", "paged"):
     units += [Unit(f"ffpa_{kind}_inst.hip", f"ffpa_{kind}_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d in VARLEN_HEAD_DIMS]
+  # the MLA latent-cache kernels (and their one-cache append): one TU per (head dim, value width) pair of MLA_BUILDS — adding a pair is one entry there and one
+  # line in FFPA_FOR_EACH_MLA_BUILD (csrc/ffpa_mla.h); the assembly lands next to the head dim's other kernels, where the ISA rules read it
+  units += [Unit("ffpa_mla_inst.hip", f"ffpa_mla_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
   # the KV-cache append + rotary launch (every dtype / rotary form) and the merge of two attention states (the cascade's last launch): one small TU each, no
   # inline asm — their assembly lands in directories the attention ISA rules do not read
   units.append(Unit("ffpa_kvcache_append.hip", "ffpa_kvcache_append.o", [], "temps_append", None, True, True))

@@ -21,6 +21,7 @@
 #include "ffpa_varlen_merge.h"   // (stage 2 of a KV-split packed-sequence launch)
 #include "ffpa_launch.h"
 #include "ffpa_paged.h"         // (the paged-KV twin of the packed-sequence kernel)
+#include "ffpa_mla.h"           // (the MLA latent-cache kernels and their append)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
 #include "ffpa_merge_states.h"    // (the merge of two attention states)
 
@@ -951,7 +952,8 @@ struct VarlenPlan {
 // Validation shared by the launch and the queries; fills the plan.  Head dims below the first 16x16x32 instantiation run on it (columns past the
 // caller's head dim read as zeros and are never stored, as in the dense call).  `paged`: the plan of the paged-KV kernel — 64-key tiles where the packed kernel
 // takes 128 (D = 256 / 320), everything else the same rule.
-int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = false) {
+// `mla`: the plan of the latent-cache call (ffpa_attn_varlen_mla_fwd) — the heads of a KV group are packed into rows HOWEVER MANY they are (see below).
+int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = false, bool mla = false) {
   if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
   if (p->struct_size != sizeof(ffpa_varlen_fwd_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
     return fail(FFPA_ERR_BAD_ABI, "ffpa_varlen_fwd_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size,
@@ -979,6 +981,15 @@ int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = f
   const int group = p->heads_q / p->heads_kv;
   out->pack = (group > 1 && (int64_t)group * p->max_seqlen_q <= out->br && !(p->flags & FFPA_FLAG_NO_PACK_GQA)) ? group : 0;
   out->nqt = out->pack ? 1 : (p->max_seqlen_q + out->br - 1) / out->br;
+  if (mla && group > 1 && !(p->flags & FFPA_FLAG_NO_PACK_GQA) && (int64_t)group * p->max_seqlen_q <= 0x7fffffffLL) {
+    // The latent-cache call packs a group WIDER THAN THE TILE as well: every query head of the model reads the one latent head (128 of them, 16 ... 64 per
+    // tensor-parallel rank), so a sequence's group x max_seqlen_q packed rows are cut into ceil(group x max_seqlen_q / block rows) CHUNKS — the row tiles of the
+    // packed rows, which the kernel's packed path walks like any row tile (row r = (head r / ntok, token r % ntok), whatever tile r falls into: a chunk boundary
+    // may fall inside a head's tokens).  The chunks of a (sequence, KV head) are neighbours in the launch order (KV head, sequence, row tile: the head-chunk order
+    // with chunks of one), so the second reader of a latent tile finds it in its XCD's L2: 128 heads x 1 token are two 64-row workgroups per sequence instead of 128.
+    out->pack = group;
+    out->nqt = (int)(((int64_t)group * p->max_seqlen_q + out->br - 1) / out->br);
+  }
   out->grid = (int64_t)p->batch * (out->pack ? p->heads_kv : p->heads_q) * out->nqt;
   // The COMPACT grid: a caller that says how many rows q has (total_q, ABI 6; >= cu_seqlens_q[batch]) lets a ragged prefill batch size its grid by the rows there are —
   // sum_i ceil(len_i / block rows) <= ceil(total_q / block rows) + batch slots per head — instead of batch x the longest sequence's row tiles, most of which would find
@@ -1000,8 +1011,9 @@ int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = f
   // packed decode batches: profiles/r06_varlen.txt.  FFPA_FLAG_KV_STREAM / _NO_KV_STREAM force either.
   {
     const bool one_reader = out->nqt == 1 && (out->pack > 0 || group == 1);
-    const int64_t kv_bound = 2LL * p->batch * p->heads_kv * (int64_t)p->max_seqlen_kv * p->head_dim * 2;
-    bool nt = one_reader && kv_bound / 2 >= (272LL << 20);
+    // (the latent-cache call: nqt counts the chunks of a packed group — a latent byte with two chunks has two readers —, and there is one stream, not K + V)
+    const int64_t kv_bound = (mla ? 1LL : 2LL) * p->batch * p->heads_kv * (int64_t)p->max_seqlen_kv * p->head_dim * 2;
+    bool nt = one_reader && kv_bound / (mla ? 1 : 2) >= (272LL << 20);
     if (p->flags & FFPA_FLAG_KV_STREAM) nt = true;
     if (p->flags & FFPA_FLAG_NO_KV_STREAM) nt = false;
     out->nt = nt ? 1 : 0;
@@ -1026,7 +1038,7 @@ int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = f
     int64_t want = 1;
     if ((p->flags & FFPA_FLAG_FORCE_SPLITS) && p->num_splits > 1) {
       want = p->num_splits < max_tiles ? p->num_splits : max_tiles;  // (sweeps and tests: exactly n, down to one tile per range)
-    } else if (out->nqt > 1) {
+    } else if (out->nqt > 1 && !(mla && out->pack)) {  // (the chunks of a packed latent group are a decode launch's workgroups: rule (a) / (b) on its grid)
       // (c): slots as in (a); the workgroups that find rows — the grid is sized by max_seqlen_q, a ragged batch's short sequences leave theirs at once — are at
       // least heads x ceil(total_q / block rows) (exact when the lengths are whole tiles; a range too many costs little, one too few a lot: 2 sequences of 1024 /
       // 256 rows, 8 heads: 2 ranges 361 us, 3 270, 4 277).  A causal launch that fills the slots only once and whose longest row tile walks >= 1.5 x the average
@@ -1183,30 +1195,76 @@ const ffpa_window* softcap_window(const ffpa_window* w) {
   return w != nullptr ? w : &kNone;
 }
 
+// The latent-cache call's own argument (ffpa_mla), checked behind the plan (and the pool) and before anything touches the device.
+typedef int (*mla_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, const ffpa::MlaArgs&, hipStream_t);
+struct MlaEntry {
+  int d, dv;
+  mla_fn launch;
+};
+const MlaEntry kMlaBuilds[] = {
+#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_paged_d##D},
+    FFPA_FOR_EACH_MLA_BUILD(FFPA_ROW)
+#undef FFPA_ROW
+};
+
+int check_mla(const ffpa_varlen_fwd_params* p, const ffpa_mla* m, const MlaEntry** build) {
+  if (m == nullptr) return fail(FFPA_ERR_NULL_POINTER, "mla is NULL");
+  if (m->struct_size != sizeof(ffpa_mla)) return fail(FFPA_ERR_BAD_ABI, "ffpa_mla ABI mismatch: size %u (want %zu)", m->struct_size, sizeof(ffpa_mla));
+  if (m->reserved != 0) return fail(FFPA_ERR_BAD_ABI, "ffpa_mla.reserved=%u must be 0", m->reserved);
+  if (p->head_dim % 64 != 0 || m->head_dim_v <= 0 || m->head_dim_v % 64 != 0 || m->head_dim_v > p->head_dim)
+    return fail(FFPA_ERR_BAD_SHAPE, "(head_dim, head_dim_v) = (%d, %d): both must be multiples of 64 with 0 < head_dim_v <= head_dim", p->head_dim, m->head_dim_v);
+  const MlaEntry* found = nullptr;
+  for (const MlaEntry& e : kMlaBuilds)
+    if (e.d == p->head_dim && e.dv == m->head_dim_v) found = &e;
+  if (found == nullptr) return fail(FFPA_ERR_BAD_HEADDIM, "(head_dim, head_dim_v) = (%d, %d) is not built (built: (576, 512))", p->head_dim, m->head_dim_v);
+  if (m->seqlen_new < 0) return fail(FFPA_ERR_BAD_SHAPE, "ffpa_mla.seqlen_new=%d must not be negative", m->seqlen_new);
+  if (m->seqlen_new > 0) {
+    if (m->kv_new == nullptr || m->cache_seqlens == nullptr) return fail(FFPA_ERR_NULL_POINTER, "kv_new / cache_seqlens must be non-NULL when seqlen_new > 0");
+    if (!aligned16(m->kv_new) || (reinterpret_cast<uintptr_t>(m->cache_seqlens) & 3u))
+      return fail(FFPA_ERR_MISALIGNED, "kv_new must be 16-byte aligned and cache_seqlens 4-byte aligned");
+    if (m->cache_seqlens == p->seqused_kv) return fail(FFPA_ERR_BAD_SHAPE, "seqused_kv receives the lengths behind the append: it must not be cache_seqlens");
+    const int rc = check_strides("kv_new", m->kv_new_stride, 3);
+    if (rc != FFPA_OK) return rc;
+    if ((int64_t)p->batch * m->seqlen_new > 0x7fffffffLL) return fail(FFPA_ERR_BAD_SHAPE, "grid of %lld new rows is too large", (long long)p->batch * m->seqlen_new);
+  }
+  if (build != nullptr) *build = found;
+  return FFPA_OK;
+}
+
+// The latent-cache call's plan: the paged call's with every group packed into rows (varlen_plan's `mla`), then the pool, then the call's own argument.
+int mla_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, VarlenPlan* pl, const MlaEntry** build = nullptr) {
+  int rc = varlen_plan(p, pl, true, true);
+  if (rc != FFPA_OK) return rc;
+  if ((rc = check_paged(p, kv)) != FFPA_OK) return rc;
+  return check_mla(p, m, build);
+}
+
 // The packed call and its paged twin (kv != NULL: k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read); `tree`: under a tree mask
 // (ffpa_attn_varlen_tree_fwd — the causal launch's plan and tile walk; the *_tree_kernel builds, whose element test reads the mask words); `win`: under a sliding
 // window (ffpa_attn_varlen_window_fwd — the window's own plan; the *_window_kernel builds); `softcap` > 0: a window launch with capped scores
 // (ffpa_attn_varlen_softcap_fwd — the same plan; the *_softcap_kernel builds)
 int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream, const ffpa_tree_mask* tree = nullptr, bool with_tree = false,
-                  const ffpa_window* win = nullptr, bool with_win = false, float softcap = 0.f) {
+                  const ffpa_window* win = nullptr, bool with_win = false, float softcap = 0.f, const ffpa_mla* mla = nullptr, bool with_mla = false) {
+  // (`mla`: the latent-cache call, ffpa_attn_varlen_mla_fwd — k is the latent pool and serves as v too, p->v is not read; its own plan and kernel; the append in front)
   const bool paged = kv != nullptr;
   VarlenPlan pl;
   WindowPlan wp;
-  int rc = with_win ? window_plan(p, kv, win, &pl, &wp) : varlen_plan(p, &pl, paged);
+  const MlaEntry* mb = nullptr;
+  int rc = with_mla ? mla_plan(p, kv, mla, &pl, &mb) : with_win ? window_plan(p, kv, win, &pl, &wp) : varlen_plan(p, &pl, paged);
   if (rc != FFPA_OK) return rc;
   if (with_win) p = &wp.priced;  // (the caller's params but for the causal flag and the length the plan saw; the kernel reads every sequence's own length)
   if (paged && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
   if (with_tree && (rc = check_tree(p, tree)) != FFPA_OK) return rc;
-  if (!p->q || !p->k || !p->v || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
+  if (!p->q || !p->k || (!with_mla && !p->v) || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
   if (!p->cu_seqlens_q || (!paged && !p->cu_seqlens_kv)) return fail(FFPA_ERR_NULL_POINTER, "cu_seqlens_q / cu_seqlens_kv must be non-NULL");
   if ((reinterpret_cast<uintptr_t>(p->cu_seqlens_q) & 3u) || (!paged && (reinterpret_cast<uintptr_t>(p->cu_seqlens_kv) & 3u)) || (reinterpret_cast<uintptr_t>(p->seqused_kv) & 3u))
     return fail(FFPA_ERR_MISALIGNED, "cu_seqlens_q / cu_seqlens_kv / seqused_kv must be 4-byte aligned");
-  if (!aligned16(p->q) || !aligned16(p->k) || !aligned16(p->v) || !aligned16(p->o))
+  if (!aligned16(p->q) || !aligned16(p->k) || (!with_mla && !aligned16(p->v)) || !aligned16(p->o))
     return fail(FFPA_ERR_MISALIGNED, "q/k/v/o base pointers must be 16-byte aligned");
-  if ((rc = check_strides("q", p->q_stride, 2)) || (rc = check_strides("k", p->k_stride, 2)) || (rc = check_strides("v", p->v_stride, 2)) ||
+  if ((rc = check_strides("q", p->q_stride, 2)) || (rc = check_strides("k", p->k_stride, 2)) || (!with_mla && (rc = check_strides("v", p->v_stride, 2))) ||
       (rc = check_strides("o", p->o_stride, 2)))
     return rc;
-  for (const int64_t* st : {p->k_stride, p->v_stride}) {
+  for (const int64_t* st : {p->k_stride, with_mla ? p->k_stride : p->v_stride}) {
     if (st[0] < p->head_dim || st[0] >= (1LL << 24))
       return fail(FFPA_ERR_BAD_STRIDE, "k/v row stride %lld: rows must not overlap and must be < 2^24 elements apart", (long long)st[0]);
   }
@@ -1220,13 +1278,13 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
   memset(&a, 0, sizeof(a));
   a.q = p->q;
   a.k = p->k;
-  a.v = p->v;
+  a.v = with_mla ? p->k : p->v;
   a.o = p->o;
   a.lse = p->lse;
   // element strides batch / head / row: a sequence's base is its row offset (the kernel adds it), so the batch stride is zero
   a.sq[1] = p->q_stride[1], a.sq[2] = p->q_stride[0];
   a.sk[1] = p->k_stride[1], a.sk[2] = p->k_stride[0];
-  a.sv[1] = p->v_stride[1], a.sv[2] = p->v_stride[0];
+  a.sv[1] = (with_mla ? p->k_stride : p->v_stride)[1], a.sv[2] = (with_mla ? p->k_stride : p->v_stride)[0];
   a.so[1] = p->o_stride[1], a.so[2] = p->o_stride[0];
   a.B = p->batch;
   a.Hq = p->heads_q;
@@ -1245,7 +1303,8 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
   a.nsplit = 1;
   a.tiles_per_split = 0x7fffffff / 2;  // (never the binding limit: the KV axis is not split)
   a.keep_scale = 1.f;
-  a.xcd_group = pick_xcd_group(p->flags, (int64_t)pl.nqt * (p->heads_q / p->heads_kv) >= 64, p->max_seqlen_kv, p->head_dim);
+  // (the row tiles of a packed latent group are a decode launch's workgroups, not the rounds of a prefill head: one XCD per head)
+  a.xcd_group = pick_xcd_group(p->flags, !with_mla && (int64_t)pl.nqt * (p->heads_q / p->heads_kv) >= 64, p->max_seqlen_kv, p->head_dim);
   a.l2_prefetch = pick_l2_prefetch(p->flags, pl.ve->d > 512);
 
   ffpa::VarlenArgs va;
@@ -1308,17 +1367,38 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
     pa.table = kv->block_table;
     pa.bt_stride = kv->bt_stride;
     pa.k_page_stride = kv->k_page_stride;
-    pa.v_page_stride = kv->v_page_stride;
+    pa.v_page_stride = with_mla ? kv->k_page_stride : kv->v_page_stride;
     pa.cap = kv->pages_per_row * kv->page_size;
     pa.page_size = kv->page_size;
     pa.tiles_per_page = kv->page_size / pl.bc;
     pa.num_pages = kv->num_pages;
-    st = kPagedDims[pl.ve - kVarlenDims](p->dtype, pl.nt, a, va, pa, static_cast<hipStream_t>(stream));
+    if (with_mla) {
+      st = 0;
+      if (mla->seqlen_new > 0) {
+        // the step's latent rows first, ONE store per element (there is one cache), and the lengths the attention launch behind it reads
+        ffpa::MlaAppendArgs ap;
+        memset(&ap, 0, sizeof(ap));
+        ap.kv_new = mla->kv_new, ap.cache = const_cast<void*>(p->k);
+        ap.seqlens = mla->cache_seqlens, ap.used = const_cast<int*>(p->seqused_kv), ap.table = kv->block_table;
+        for (int i = 0; i < 3; ++i) ap.s_new[i] = mla->kv_new_stride[i];
+        ap.s_row = p->k_stride[0], ap.s_head = p->k_stride[1], ap.s_page = kv->k_page_stride, ap.bt_stride = kv->bt_stride;
+        ap.B = p->batch, ap.Snew = mla->seqlen_new, ap.Hkv = p->heads_kv, ap.D = p->head_dim;
+        ap.cap = pa.cap, ap.page_size = kv->page_size, ap.num_pages = kv->num_pages;
+        st = ffpa::launch_mla_append(ap, static_cast<hipStream_t>(stream));
+      }
+      ffpa::MlaArgs ma;
+      ma.dv = mla->head_dim_v;
+      if (st == 0) st = mb->launch(p->dtype, pl.nt, a, va, pa, ma, static_cast<hipStream_t>(stream));
+    } else {
+      st = kPagedDims[pl.ve - kVarlenDims](p->dtype, pl.nt, a, va, pa, static_cast<hipStream_t>(stream));
+    }
   } else {
     st = pl.ve->launch(p->dtype, pl.nt, a, va, static_cast<hipStream_t>(stream));
   }
   if (st == 0 && pl.splits > 1) {
-    const dim3 grid((unsigned)((int64_t)p->heads_q * p->total_q), (unsigned)(p->head_dim + 255) / 256);
+    // (the latent-cache call: the partials keep all D columns, the merge stores the value columns — its column bound is d_valid)
+    if (with_mla) a.d_valid = mla->head_dim_v;
+    const dim3 grid((unsigned)((int64_t)p->heads_q * p->total_q), (unsigned)(a.d_valid + 255) / 256);
     st = ffpa::dispatch_dtype(p->dtype, [&](auto t) {
       using T = typename decltype(t)::type;
       hipLaunchKernelGGL(ffpa::ffpa_varlen_merge_kernel<T>, grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, va, pl.ve->d, p->batch, p->o_stride[1]);
@@ -1498,6 +1578,39 @@ int ffpa_attn_varlen_softcap_fwd_kernel(const ffpa_varlen_fwd_params* p, const f
   if (rc != FFPA_OK) return rc;
   if ((rc = window_plan(p, kv, softcap_window(w), &pl, &wp)) != FFPA_OK) return rc;
   return kernel_name(&wp.priced, pl, kv != nullptr, buf, n, false, true, true);
+}
+
+// ---- the MLA latent-cache call (include/ffpa_attn.h: ffpa_mla): the paged call on ONE pool, every group packed into rows, the append in front
+int ffpa_attn_varlen_mla_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, void* stream) {
+  return varlen_launch(p, kv, stream, nullptr, false, nullptr, false, 0.f, m, true);
+}
+
+size_t ffpa_attn_varlen_mla_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m) {
+  if (p == nullptr || p->struct_size != sizeof(ffpa_varlen_fwd_params) || kv == nullptr || kv->struct_size != sizeof(ffpa_paged_kv) || m == nullptr ||
+      m->struct_size != sizeof(ffpa_mla))
+    return 0;
+  // size for the split count the heuristic would pick with unlimited scratch
+  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*p);
+  VarlenPlan pl;
+  if (mla_plan(&q, kv, m, &pl) != FFPA_OK) return 0;
+  return pl.ws_bytes;
+}
+
+int ffpa_attn_varlen_mla_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int out[5]) {
+  VarlenPlan pl;
+  const int rc = mla_plan(p, kv, m, &pl);
+  if (rc != FFPA_OK) return rc;
+  return plan_out(pl, out);
+}
+
+int ffpa_attn_varlen_mla_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, char* buf, size_t n) {
+  VarlenPlan pl;
+  const int rc = mla_plan(p, kv, m, &pl);
+  if (rc != FFPA_OK) return rc;
+  if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
+  snprintf(buf, n, "ffpa_fwd_m16_mla_kernel<%s, %d, dv=%d%s>%s%s", p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", p->head_dim, m->head_dim_v, pl.nt ? ", NT" : "",
+           pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "", pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
+  return FFPA_OK;
 }
 
 // ---- the KV-cache append + rotary (include/ffpa_attn.h: ffpa_kv_append_params)

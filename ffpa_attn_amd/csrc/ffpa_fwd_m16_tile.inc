@@ -30,6 +30,31 @@
 #define FFPA_M16_SOFTCAP_IN 0.f
 #define FFPA_M16_SOFTCAP_DEFAULT_HOOKS
 #endif
+// An MLA LATENT CACHE is the enclosing kernel's as well (ffpa_mla_inst.hip): FFPA_M16_MLA_ON = a constant of its build, FFPA_M16_O_COLS = the value width (MlaArgs::dv).
+// The values of a KV head are the first FFPA_M16_O_COLS columns of the very rows that are its keys, so a latent tile is fetched ONCE and the two LDS images of the
+// tile, Kt and Vt — the same LDS bytes — ALTERNATE as its home: tile j lives in image j & 1 (the parity follows the TILE INDEX: a KV range that starts at an odd
+// tile starts in Vt, and prologue, loop and page lookahead all derive the image from the tile they name).  Only the un-pipelined split-D loop (D % 128 == 64)
+// carries the hook.  Per step j:
+//     QK^T(j) reads its K fragments from image j & 1            | DMA: the PPW pieces of tile j + 1 ride on its MFMAs (where the V(j) pieces ride in the other
+//                                                               |      builds) into image (j + 1) & 1, whose last readers — PV(j - 1) — passed barrier B of step j - 1
+//     barrier A1 (partial S^T visible)
+//     softmax(j)                                                | no DMA
+//     PV(j) reads its V^T fragments from THE SAME image j & 1   | no DMA; no barrier A2 — A2 only ever published V(j), and tile j was published by barrier B of
+//                                                               |      step j - 1; the partial-S exchange is ordered by A1 (written before, read behind it) and B
+//     barrier B: vmcnt <= (touch ? 1 : 0), then every wave is done reading image j & 1 and tile j + 1 has landed and is visible
+// The counted waits.  LDS-DMA pieces and the L2 touch retire in order.  Behind the prologue's dma_wait_all a wave has at most the touch of the step before in
+// flight at the top of a step; it issues the PPW pieces of tile j + 1 in QK^T(j), nothing in the softmax and PV phases, and the touch of tile j + 2 in front of
+// barrier B.  So at barrier B the queue holds [touch(j - 1)], piece 0 .. PPW - 1 of tile j + 1, [touch(j)] in this order: vmcnt(1) on the waves that touch — all
+// but the youngest, the touch itself — and vmcnt(0) on the others drains exactly the tile; there is no counted wait anywhere else in the step.  A tile past
+// the last one (j + 1 == nt) has an empty descriptor: its pieces move no bytes and retire like any other.
+// One source-side swizzle serves both read patterns: m16_v_swizzle — at D % 128 == 64 it is conflict-free for the ds_read_b128 K-fragment groups as well as for
+// the ds_read_b64_tr_b16 halves (tools/sim_lds_layout.py check_m16_shared; m16_k_swizzle would cost the transpose reads a 2-way conflict on every half).
+// Only O columns < FFPA_M16_O_COLS are stored (the split launch's fp32 partials keep all D columns: ffpa_varlen_merge_kernel bounds its stores by d_valid).
+#ifndef FFPA_M16_MLA_ON
+#define FFPA_M16_MLA_ON false
+#define FFPA_M16_O_COLS a.d_valid
+#define FFPA_M16_MLA_DEFAULT_HOOKS
+#endif
 #ifndef FFPA_M16_KV_SRC
 #define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) tile_src<BC>(slice, row_bytes, key0, a.Nkv, rb_valid)
 #define FFPA_M16_KV_BEGIN(t0_)
@@ -98,7 +123,7 @@
       const int gk = kKS ? ((i < kH ? wave * kH + i : 2 * PPW + wave * kH + (i - kH)) * 64 + lane) : g;
       const int kkey = gk / SPR;
       const int kslot = gk - kkey * SPR;
-      const int ks = kslot ^ m16_k_swizzle<D>(kkey);
+      const int ks = kslot ^ (FFPA_M16_MLA_ON ? m16_v_swizzle<D>(kkey) : m16_k_swizzle<D>(kkey));  // (MLA: the shared image takes the V map)
       krel[i] = (uint32_t)kkey * k_row_bytes + (uint32_t)(ks << 4);
       if (ks >= slots_valid) krel[i] = kDmaOob;
     }
@@ -106,13 +131,17 @@
     k_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(uintptr_t)Kt + (uint32_t)(wave * (kKS ? kH : PPW) * 1024)));
     v_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(uintptr_t)Vt + (uint32_t)(wave * PPW * 1024)));
   }
+  static_assert(!FFPA_M16_MLA_ON || (ND == 2 && !kPipe && !kRowDma && MK == 0 && !DROP && NH == 1), "the MLA hook lives in the un-pipelined split-D loop");
+  // MLA: where this wave's pieces of the latent tile at key0 land — the image of the tile's parity (k_lds: Kt's, v_lds: Vt's; the same piece offsets in both).
+  // (a macro, not a lambda: a lambda more in front of the others would renumber their symbols in every object built from this text)
+#define FFPA_M16_MLA_DST(key0_) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(((((key0_) / BC) & 1) != 0) ? v_lds : k_lds)))
   auto issue_k = [&](auto ic, int key0) {
     constexpr int i = decltype(ic)::value;
     const TileSrc ts = FFPA_M16_KV_SRC(0, Kg, k_row_bytes, key0);
     if constexpr (kRowDma) {
       lds_dma_row<(16 * (i >> 2) + (i & 3)) * RB, 0>(ts.rsrc, k_lds, kvo[i & 3], kro[i]);
     } else {
-      FFPA_M16_DMA16<(kKS && i >= kH ? 2 * PPW + (i - kH) : i) * 1024>(ts.rsrc, k_lds, krel[i], 0u);
+      FFPA_M16_DMA16<(kKS && i >= kH ? 2 * PPW + (i - kH) : i) * 1024>(ts.rsrc, FFPA_M16_MLA_ON ? FFPA_M16_MLA_DST(key0) : k_lds, krel[i], 0u);
     }
   };
   auto issue_v = [&](auto ic, int key0) {
@@ -131,7 +160,7 @@
   auto issue_k_on = [&](auto ic, int key0, auto kindc, f32x4& d, v8 fa, v8 fb) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
     const TileSrc ts = FFPA_M16_KV_SRC(0, Kg, k_row_bytes, key0);
-    M::template with_dma<decltype(kindc)::value, (kKS && i >= kH ? 2 * PPW + (i - kH) : i) * 1024>(d, fa, fb, ts.rsrc, k_lds, krel[kRowDma ? 0 : i], 0u);
+    M::template with_dma<decltype(kindc)::value, (kKS && i >= kH ? 2 * PPW + (i - kH) : i) * 1024>(d, fa, fb, ts.rsrc, FFPA_M16_MLA_ON ? FFPA_M16_MLA_DST(key0) : k_lds, krel[kRowDma ? 0 : i], 0u);
   };
   auto issue_v_on = [&](auto ic, int key0, auto kindc, f32x4& d, v8 fa, v8 fb) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
@@ -155,7 +184,7 @@
   // (built into the split-D tiles only: at D <= 512 a DMA piece has a whole step to land, the touches cost 1 ... 2 %, and the dropout +
   // bias builds there have no register to spare)
   constexpr bool kPf = ND == 2;
-  const bool pf_on = kPf && a.l2_prefetch != 0 && wave < FFPA_M16_PF_WAVES && ((FFPA_M16_PF_WHICH >> (wave & 1)) & 1);
+  const bool pf_on = kPf && a.l2_prefetch != 0 && wave < FFPA_M16_PF_WAVES && ((FFPA_M16_PF_WHICH >> (wave & 1)) & 1) && !(FFPA_M16_MLA_ON && (wave & 1));  // (MLA: there is no V stream to touch)
   const bool pf_k = (wave & 1) == 0;  // even waves touch K, odd waves V
   uint32_t pf_off = kDmaOob;
   uint32_t pf_junk = 0u;  // (the loads' destination: never read, but live through the loop so that nothing else is allocated to it)
@@ -266,7 +295,7 @@
 #pragma unroll
   for (int hf = 0; hf < NH; ++hf)
 #pragma unroll
-    for (int i = 0; i < KV; ++i) kaddr[hf][i] = Kt + (64 * hf + n16) * RB + (((dh * (DW / 8) + 4 * i + c) ^ m16_k_swizzle<D>(n16)) << 4);
+    for (int i = 0; i < KV; ++i) kaddr[hf][i] = Kt + (64 * hf + n16) * RB + (((dh * (DW / 8) + 4 * i + c) ^ (FFPA_M16_MLA_ON ? m16_v_swizzle<D>(n16) : m16_k_swizzle<D>(n16))) << 4);
   // V^T fragment of column block db = VV q + i, key step ks: lane L = lane % 16 of group c reads key 32 ks + 4 c + L / 4 (+ 16 for
   // the second read), 4 columns 16 db + 4 (L % 4) ..: vaddr[ks / 2][i] + VVB q + ((ks % 2) * 32 + {0, 16}) * RB
   FFPA_LDS const char* vaddr[NH][VV];
@@ -277,7 +306,7 @@
     for (int hf = 0; hf < NH; ++hf)
 #pragma unroll
       for (int i = 0; i < VV; ++i)
-        vaddr[hf][i] = Vt + (64 * hf + vkey) * RB + (((dh * (DW / 8) + 2 * i + ((n16 & 3) >> 1)) ^ sw) << 4) + 8 * (n16 & 1);
+        vaddr[hf][i] = (FFPA_M16_MLA_ON ? Kt : Vt) + (64 * hf + vkey) * RB + (((dh * (DW / 8) + 2 * i + ((n16 & 3) >> 1)) ^ sw) << 4) + 8 * (n16 & 1);  // (MLA: both address sets are image 0's; a step adds its image's offset)
   }
 
   // ---- additive bias (MK == 1): where the initial S^T accumulators of a KV step come from (see the header)
@@ -816,7 +845,8 @@
   for (int j = t0; j < nt; ++j) {
     const int k0 = j * BC;
     FFPA_M16_KV_STEP(k0)
-
+    // MLA: the image tile j lives in (wave-uniform; both products of the step read there)
+    const int mla_img = FFPA_M16_MLA_ON ? (j & 1) * TILE : 0;
 
     // ================= S^T = K.Q^T =================
     f32x4 sacc[NKB][2];
@@ -824,7 +854,7 @@
       v8 kf[N1];
       auto k_frag = [&](int n) -> v8 {
         const int s = n / NKB, kb = n % NKB;
-        return *(FFPA_LDS const v8*)(kaddr[kb / 4][s % KV] + (s / KV) * KVB + (kb % 4) * 16 * RB);
+        return *(FFPA_LDS const v8*)(kaddr[kb / 4][s % KV] + mla_img + (s / KV) * KVB + (kb % 4) * 16 * RB);
       };
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -926,7 +956,9 @@
         constexpr int s = n / NKB, kb = n % NKB;
         constexpr bool kPiece = n % kStep1 == 0 && n / kStep1 < PPW;
         // (a DMA piece sits BETWEEN the fragment's two MFMAs: + 0.4 ... 1.7 % against in front of / behind them; fused with the first one where the build allows)
-        if constexpr (kPiece && kFuse) {
+        if constexpr (kPiece && kFuse && FFPA_M16_MLA_ON) {  // (MLA: the pieces of latent tile j + 1, into the other image)
+          issue_k_on(std::integral_constant<int, n / kStep1>{}, k0 + BC, std::integral_constant<int, (s == 0 && !kBias) ? 0 : 1>{}, sacc[kb][0], kf[n], qf[s][0]);
+        } else if constexpr (kPiece && kFuse) {
           issue_v_on(std::integral_constant<int, n / kStep1>{}, k0, std::integral_constant<int, (s == 0 && !kBias) ? 0 : 1>{}, sacc[kb][0], kf[n], qf[s][0]);
         } else {
           if constexpr (s == 0 && !kBias) M::first(sacc[kb][0], kf[n], qf[s][0]);
@@ -950,7 +982,7 @@
 
     auto pre_k_group = [&](auto gc) __attribute__((always_inline)) {
       constexpr int g = decltype(gc)::value;
-      if constexpr (kPre >= 4) {
+      if constexpr (kPre >= 4 && !FFPA_M16_MLA_ON) {  // (MLA: tile j + 1 went out in the QK^T loop)
         __builtin_amdgcn_sched_barrier(0);
         static_for<kPre / 4>([&](auto ic) { issue_k(std::integral_constant<int, g * (kPre / 4) + decltype(ic)::value>{}, k0 + BC); });
         __builtin_amdgcn_sched_barrier(0);
@@ -1233,8 +1265,10 @@
       __builtin_amdgcn_sched_barrier(0);
       FFPA_TSTAMP(2);  // softmax + the K(j+1) pieces issued inside it
       // barrier A2: V(j) has landed on every wave (all but the kPre younger K pieces have retired)
-      dma_wait_except<kPre>();
-      __syncthreads();
+      if constexpr (!FFPA_M16_MLA_ON) {  // (MLA: PV(j) reads the image QK^T(j) read — published by barrier B of the step before; see the header)
+        dma_wait_except<kPre>();
+        __syncthreads();
+      }
       FFPA_TSTAMP(3);  // V(j) drain + wait at barrier A2
       if constexpr (kRowShare) {
         // both row halves' P^T fragments and rescale factors: half rh sits in the area of the row block's wave dh = rh, slots (0, rh) and (1, rh)
@@ -1262,7 +1296,7 @@
       v8 vf[N2];
       auto v_frag = [&](int n) -> v8 {
         const int db = n % NDB, ks = n / NDB;
-        FFPA_LDS const char* vp = vaddr[ks / 2][db % VV] + (db / VV) * VVB + (ks % 2) * 32 * RB;
+        FFPA_LDS const char* vp = vaddr[ks / 2][db % VV] + mla_img + (db / VV) * VVB + (ks % 2) * 32 * RB;
         const v4 lo = E::tr_read(vp);
         const v4 hi = E::tr_read(vp + 16 * RB);
         return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -1273,7 +1307,7 @@
         constexpr int n = decltype(ic)::value;
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (n + PF2 < N2) vf[n + PF2] = v_frag(n + PF2);
-        constexpr bool kPiece = n % kStep2 == 0 && n / kStep2 + kPre < PPW;  // the K(j+1) pieces that did not go out between the softmax stages
+        constexpr bool kPiece = n % kStep2 == 0 && n / kStep2 + kPre < PPW && !FFPA_M16_MLA_ON;  // the K(j+1) pieces that did not go out between the softmax stages (MLA: none)
         constexpr int kIdx = n / kStep2 + kPre;
         constexpr int db = n % NDB, ks = n / NDB;
         if constexpr (kPiece && kFuse) issue_k_on(std::integral_constant<int, kIdx>{}, k0 + BC, std::integral_constant<int, 2>{}, oacc[db][0], vf[n], pf[ks][0]);
@@ -1383,7 +1417,7 @@
         run[w] = sw[0];
         run[2 + w] = sw[1];
       }
-      if (ok && dh * DW + db * 16 + 4 * (c & ~1) < a.d_valid) *(u32x4*)(op + db * 16) = run;
+      if (ok && dh * DW + db * 16 + 4 * (c & ~1) < FFPA_M16_O_COLS) *(u32x4*)(op + db * 16) = run;
     }
 #ifdef FFPA_M16_TIMING
     if (a.lse != nullptr && lane == 0) {  // 16 floats per wave at LSE row q0 + 16 * wave: six phase totals, whole kernel, KV tiles, two more phases
@@ -1411,6 +1445,12 @@
 #undef FFPA_M16_WINDOW_DEFAULT_HOOKS
 #undef FFPA_M16_WINDOW_SPAN
 #undef FFPA_M16_WINDOW_ON
+#endif
+#undef FFPA_M16_MLA_DST
+#ifdef FFPA_M16_MLA_DEFAULT_HOOKS
+#undef FFPA_M16_MLA_DEFAULT_HOOKS
+#undef FFPA_M16_O_COLS
+#undef FFPA_M16_MLA_ON
 #endif
 #ifdef FFPA_M16_KV_DEFAULT_HOOKS
 #undef FFPA_M16_KV_DEFAULT_HOOKS

@@ -1,0 +1,41 @@
+// ffpa_mla.h — MLA latent-cache attention (ffpa_attn_varlen_mla_fwd, ffpa_capi.hip): what its kernels take beyond FwdArgs / VarlenArgs / PagedArgs and the launchers
+// of ffpa_mla_inst.hip.  A header of its own so that the dense, packed and paged objects see nothing of it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace ffpa {
+struct FwdArgs;
+struct VarlenArgs;
+struct PagedArgs;
+
+// The (head dim, value width) pairs ffpa_mla_inst.hip is built for: one line per pair here, one -DFFPA_INST_D=<D> unit in build.py.
+#define FFPA_FOR_EACH_MLA_BUILD(X) X(576, 512)
+
+// What the latent kernels need beyond the three shared structs (they keep their layout): the keys of a KV head are the latent rows' D columns, its values the
+// first `dv` of the same rows — only O columns < dv are stored.
+struct MlaArgs {
+  int dv;
+};
+
+// The latent append: row i of sequence b of kv_new goes to cache position max(seqlens[b], 0) + i (dropped at or past cap), ONE store per element, and
+// used[b] = min(max(seqlens[b], 0) + Snew, cap) is what the attention launch behind it reads as the sequence's length.
+struct MlaAppendArgs {
+  const void* kv_new;   // [B, Snew, Hkv, D] by s_new = {batch, row, head}
+  void* cache;          // the pool
+  const int* seqlens;   // [B] lengths before the step
+  int* used;            // [B] lengths after it
+  const int* table;     // [B][bt_stride] page ids (clamped to the pool)
+  int64_t s_new[3];
+  int64_t s_row, s_head, s_page;  // elements between two rows / heads / pages of the pool
+  int64_t bt_stride;
+  int B, Snew, Hkv, D, cap, page_size, num_pages;
+};
+
+#define FFPA_DECL(D, DV) int launch_mla_paged_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaArgs& ma, hipStream_t stream);
+FFPA_FOR_EACH_MLA_BUILD(FFPA_DECL)
+#undef FFPA_DECL
+int launch_mla_append(const MlaAppendArgs& a, hipStream_t stream);
+
+}  // namespace ffpa

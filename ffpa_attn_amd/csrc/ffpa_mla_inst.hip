@@ -1,0 +1,101 @@
+// ffpa_mla_inst.hip — MLA latent-cache attention (DeepSeek-V2 / V3 / R1, Kimi K2 in their "absorbed" decode form): every query head has D columns, all heads of a
+// group attend to ONE latent KV head, and the values are the first dv columns of the very rows that serve as keys.  One translation unit per (D, dv) pair of
+// FFPA_FOR_EACH_MLA_BUILD (ffpa_mla.h; compiled with -DFFPA_INST_D=<D>, bf16 + fp16 in the same TU); a TU of its own so that the dense, packed and paged objects
+// stay exactly what they were.  Entry point: ffpa_attn_varlen_mla_fwd (ffpa_capi.hip).
+//
+// The kernel is the paged twin of the packed-sequence kernel (ffpa_paged_inst.hip: the same sequence lookup, workgroup order, row packing, KV splits and page
+// lookahead) with the tile text's MLA hook on (FFPA_M16_MLA_ON, ffpa_fwd_m16_tile.inc): the two LDS images of the tile, Kt and Vt, alternate as the home of ONE
+// latent tile — tile j lives in image j & 1, QK^T(j) reads its K fragments there and PV(j) its V^T fragments from the same bytes.  There are no V pieces: a
+// latent row is fetched once.  A contiguous cache runs through the same kernel with one page per sequence (the Python entry's identity table).
+#include "ffpa_fwd_kernel.h"
+#include "ffpa_fwd_m16_kernel.h"
+#include "ffpa_launch_kernel.h"
+#include "ffpa_mla.h"
+#include "ffpa_paged.h"
+
+#ifndef FFPA_INST_D
+#error "compile with -DFFPA_INST_D=<head dim>"
+#endif
+
+namespace ffpa {
+
+// (ffpa_paged_inst.hip's: a tile whose first row is `tile_base` — rows past the sequence's last key read as zeros, a tile at or past the end moves no bytes)
+template <int BC>
+__device__ __forceinline__ TileSrc tile_src_at(const char* tile_base, uint32_t row_bytes, int key0, int nkv, uint32_t RB) {
+  const int kc = key0 < nkv ? key0 : nkv;
+  int rows = nkv - kc;
+  rows = rows < BC ? rows : BC;
+  const uint32_t span = (uint32_t)(rows < 1 ? rows : 1) * ((uint32_t)(rows - 1) * row_bytes + (uint32_t)RB);
+  TileSrc t;
+  t.base = tile_base;
+  t.rows = rows;
+  t.rsrc = make_rsrc(t.base, span);
+  return t;
+}
+
+template <typename T, int D, bool NT = false>
+__global__ __launch_bounds__(256) void ffpa_fwd_m16_mla_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa, const MlaArgs ma) {
+  static_assert(D > 512 && D % 128 == 64, "the MLA hook lives in the un-pipelined split-D loop of the tile text");
+#define FFPA_M16_VARLEN_TREE false
+#define FFPA_M16_VARLEN_WINDOW false
+#define FFPA_M16_VARLEN_SOFTCAP false
+#define FFPA_M16_MLA_ON true
+#define FFPA_M16_O_COLS ma.dv
+#include "ffpa_fwd_m16_paged_body.inc"
+#undef FFPA_M16_O_COLS
+#undef FFPA_M16_MLA_ON
+#undef FFPA_M16_VARLEN_SOFTCAP
+#undef FFPA_M16_VARLEN_WINDOW
+#undef FFPA_M16_VARLEN_TREE
+}
+
+template <typename T, int D, bool NT>
+static int launch_mla(const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaArgs& ma, hipStream_t stream) {
+  constexpr int BC = m16_block_keys(D, true);
+  constexpr int LDS = 2 * BC * D * 2 + m16_exchange_bytes(D, 0);  // (the two images of the paged kernel: the same LDS bytes)
+  return launch_kernel<ffpa_fwd_m16_mla_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa, ma);
+}
+
+int FFPA_CAT(launch_mla_paged_d, FFPA_INST_D)(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaArgs& ma, hipStream_t stream) {
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return nt ? launch_mla<T, FFPA_INST_D, true>(a, va, pa, ma, stream) : launch_mla<T, FFPA_INST_D, false>(a, va, pa, ma, stream);
+  });
+}
+
+#if FFPA_INST_D == 576  // (one copy of the append in the library: the first build's TU carries it)
+// THE LATENT APPEND (ffpa_attn_varlen_mla_fwd with kv_new): one workgroup per new token row; every 16-byte chunk of the row's Hkv heads is loaded and stored
+// once — the append of ffpa_kvcache_append.hip writes a K and a V cache, and here there is one cache.  16-bit elements of either dtype move as raw bytes.
+__global__ __launch_bounds__(256) void ffpa_mla_append_kernel(const MlaAppendArgs a) {
+  const int T = a.Snew > 0 ? a.Snew : 1;
+  const int b = blockIdx.x / T, i = blockIdx.x - b * T;
+  const int tid = threadIdx.x;
+  const int len = a.seqlens[b];
+  const int64_t base = len > 0 ? len : 0;  // (negative lengths act as 0, as in the attention kernels)
+  if (i == 0 && tid == 0) {
+    const int64_t n = base + a.Snew;
+    a.used[b] = (int)(n < a.cap ? n : a.cap);
+  }
+  const int64_t pos = base + i;
+  if (i >= a.Snew || pos >= a.cap) return;  // (a position at or past the capacity is dropped)
+  int page = a.table[(int64_t)b * a.bt_stride + pos / a.page_size];
+  page = page > 0 ? page : 0;
+  page = page < a.num_pages - 1 ? page : a.num_pages - 1;
+  const int row = (int)(pos % a.page_size);
+  const uint16_t* src = (const uint16_t*)a.kv_new + b * a.s_new[0] + i * a.s_new[1];
+  uint16_t* dst = (uint16_t*)a.cache + page * a.s_page + row * a.s_row;
+  const int cpr = a.D / 8;  // 16-byte chunks per head row
+  for (int e = tid; e < a.Hkv * cpr; e += 256) {
+    const int h = e / cpr, c = e - h * cpr;
+    *(u32x4*)(dst + h * a.s_head + c * 8) = *(const u32x4*)(src + h * a.s_new[2] + c * 8);
+  }
+}
+
+int launch_mla_append(const MlaAppendArgs& a, hipStream_t stream) {
+  const int T = a.Snew > 0 ? a.Snew : 1;
+  hipLaunchKernelGGL(ffpa_mla_append_kernel, dim3((unsigned)(a.B * T)), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+#endif
+
+}  // namespace ffpa

@@ -199,6 +199,20 @@ class FfpaWindow(ctypes.Structure):
   ]
 
 
+class FfpaMla(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_mla`` (include/ffpa_attn.h): the value width and the optional append of the MLA latent-cache call."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("head_dim_v", ctypes.c_int32),
+    ("seqlen_new", ctypes.c_int32),
+    ("kv_new", ctypes.c_void_p),
+    ("cache_seqlens", ctypes.c_void_p),
+    ("kv_new_stride", ctypes.c_int64 * 3),
+  ]
+
+
 class FfpaKvAppendParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_kv_append_params`` (include/ffpa_attn.h): the KV-cache append + rotary call."""
 
@@ -310,6 +324,7 @@ _VARLEN, _PAGED = [_P(FfpaVarlenFwdParams)], [_P(FfpaVarlenFwdParams), _P(FfpaPa
 _TREE = _PAGED + [_P(FfpaTreeMask)]
 _WINDOW = _PAGED + [_P(FfpaWindow)]
 _SOFTCAP = _WINDOW + [ctypes.c_float]
+_MLA = _PAGED + [_P(FfpaMla)]
 # Every function include/ffpa_attn.h declares: (symbol, argtypes, restype, since).  ``since``: the ABI version that added it (0: there from the start) — the
 # default library has them all; one loaded by path or through FFPA_HIP_LIBRARY (developer A/B runs load a saved build of an older commit) may lack those with
 # since > 0: calling one of those is then an AttributeError.
@@ -340,6 +355,10 @@ _BINDINGS = (
   ("ffpa_attn_varlen_softcap_fwd_plan", _SOFTCAP + [_P(_INT)], _INT, 7),
   ("ffpa_attn_varlen_softcap_fwd_kernel", _SOFTCAP + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_softcap_fwd_workspace_bytes", _SOFTCAP, _SIZE, 7),
+  ("ffpa_attn_varlen_mla_fwd", _MLA + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_fwd_plan", _MLA + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_fwd_kernel", _MLA + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_mla_fwd_workspace_bytes", _MLA, _SIZE, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
@@ -431,10 +450,10 @@ def __getattr__(name: str):
 # ---- what every call of the library does, once: a stamped parameter struct, the status -> exception raise, the call on the current stream, the scratch hand-over,
 # the plan read-out.  Plain functions: ``forward`` / ``varlen_forward`` run once per decoded token.
 def _stamped(cls):
-  """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` / ``ffpa_window`` ride next to a versioned struct), the ABI version — filled in."""
+  """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` / ``ffpa_window`` / ``ffpa_mla`` ride next to a versioned struct), the ABI version — filled in."""
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
-  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow):
+  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla):
     p.abi_version = ABI_VERSION
   return p
 
@@ -1426,6 +1445,124 @@ def _softcap_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_
                           softmax_scale, causal, rescale_threshold=-1.0, num_splits=0):
   total_q, heads, head_dim = q.shape
   return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
+
+
+# The MLA latent-cache call (ffpa_attn_with_kvcache_mla): ONE pool whose rows are the keys and, in their first ``head_dim_v`` columns, the values
+MLA_BUILDS = ((576, 512),)  # the (head dim, value width) pairs the library carries (csrc/ffpa_mla.h FFPA_FOR_EACH_MLA_BUILD)
+_MLA_SCRATCH: "dict[tuple, int]" = {}
+
+
+def mla_row_chunks(group: int, seqlen_q: int, block_rows: int = 64) -> "list[list[tuple[int, int]]]":
+  """The launch's row packing as a pure function: the ``group`` query heads of a KV head x the ``seqlen_q`` tokens of a sequence are the rows of its tiles,
+  head-major (row r = (head r // seqlen_q, token r % seqlen_q)), cut into ``ceil(group * seqlen_q / block_rows)`` chunks of at most ``block_rows`` rows — the row
+  tiles of one (sequence, KV head), neighbours in the launch order.  -> the (head in group, token) rows of every chunk.  ``group`` = 1 does not pack: rows are
+  tokens, and the chunks are its row tiles all the same."""
+  rows = [(r // seqlen_q, r % seqlen_q) for r in range(group * seqlen_q)]
+  return [rows[i:i + block_rows] for i in range(0, len(rows), block_rows)]
+
+
+def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seqlens_q: torch.Tensor, seqused_k: torch.Tensor, block_table: torch.Tensor,
+                max_seqlen_q: int, max_seqlen_k: int, causal: bool, softmax_scale: float, *, kv_new: "torch.Tensor | None" = None,
+                cache_seqlens: "torch.Tensor | None" = None, return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
+  """One call of ``ffpa_attn_varlen_mla_fwd``: ``q [T, Hq, D]`` packed by ``cu_seqlens_q``, the latent pool ``kv_cache [num_pages, page_size, Hkv, D]`` (written in
+  place by the append) with its int32 ``block_table [B, pages_per_seq]`` -> ``(o [T, Hq, head_dim_v], lse [Hq, T] fp32 | None)``.  The keys of KV head h are
+  ``kv_cache[..., h, :]``, its values ``kv_cache[..., h, :head_dim_v]``.  ``seqused_k`` int32 ``[B]``: the key lengths — or, with ``kv_new [B, Snew, Hkv, D]``, the
+  buffer that RECEIVES ``min(max(cache_seqlens, 0) + Snew, capacity)`` from the append launch in front of the attention launch (``cache_seqlens``: the lengths
+  before the step).  Nothing is read back to the host: the call captures into a HIP graph.  ``flags`` / ``plan_out`` / ``num_splits`` as ``varlen_forward``."""
+  name = "ffpa_attn::_mla_fwd_hip"
+  if not q.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
+  lib = load_library()
+  if q.dtype not in _DTYPE or kv_cache.dtype != q.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
+  if q.dim() != 3 or kv_cache.dim() != 4 or kv_cache.size(-1) != q.size(2):
+    raise ValueError(f"{name}: q must be packed [T, Hq, D] and kv_cache paged [num_pages, page_size, Hkv, D] of q's head dim")
+  Tq, Hq, D = q.shape
+  if (D, int(head_dim_v)) not in MLA_BUILDS:
+    raise NotImplementedError(f"{name}: (head_dim, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
+  if kv_cache.size(2) == 0 or Hq % kv_cache.size(2) != 0:
+    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of the latent num_heads ({kv_cache.size(2)})")
+  if kv_cache.size(1) <= 0 or kv_cache.size(1) % 64 != 0:
+    raise ValueError(f"{name}: page_size ({kv_cache.size(1)}) must be a positive multiple of 64")
+  if cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.device != q.device:
+    raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor of length batch + 1 on q's device")
+  batch = cu_seqlens_q.numel() - 1
+  for nm, t in (("seqused_k", seqused_k),) + ((("cache_seqlens", cache_seqlens),) if kv_new is not None else ()):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != batch or t.device != q.device:
+      raise ValueError(f"{name}: {nm} must be a 1-D int32 tensor of length batch on q's device")
+  if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != batch or block_table.size(1) == 0 or block_table.device != q.device:
+    raise ValueError(f"{name}: block_table must be a 2-D int32 tensor [batch, pages_per_seq] (pages_per_seq >= 1) on q's device")
+  if kv_cache.device != q.device or kv_cache.size(0) == 0:
+    raise ValueError(f"{name}: kv_cache must be a non-empty pool on q's device")
+  if not _layout_ok(kv_cache, -3):
+    raise ValueError(f"{name}: kv_cache needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base (it is read, and written, in place)")
+  q = _rows(q, 0)
+  cu_seqlens_q, seqused_k = cu_seqlens_q.contiguous(), seqused_k if seqused_k.is_contiguous() else seqused_k.contiguous()
+  o = torch.empty((Tq, Hq, int(head_dim_v)), dtype=q.dtype, device=q.device)
+  lse = torch.empty((Hq, Tq), dtype=torch.float32, device=q.device) if return_lse else None
+  if Tq == 0 or max_seqlen_q <= 0:
+    return o, lse
+  ks = kv_cache.stride()[-3:-1]
+  p = _varlen_params(q.dtype, batch, Hq, kv_cache.size(2), D, max_seqlen_q, max_seqlen_k, Tq, [q.stride()[-3:-1], ks, ks, o.stride()[-3:-1]], causal, softmax_scale,
+                     -1.0, int(flags) | _deterministic_flag(), num_splits)
+  p.q, p.k, p.v, p.o = q.data_ptr(), kv_cache.data_ptr(), kv_cache.data_ptr(), o.data_ptr()
+  p.lse = lse.data_ptr() if lse is not None else None
+  p.lse_stride_head = lse.stride(0) if lse is not None else 0
+  p.cu_seqlens_q = cu_seqlens_q.data_ptr()
+  p.seqused_kv = seqused_k.data_ptr()
+  kv, block_table = _paged_kv_of(block_table, kv_cache, kv_cache)
+  m = _stamped(FfpaMla)
+  m.head_dim_v = int(head_dim_v)
+  if kv_new is not None:
+    if kv_new.dtype != q.dtype or kv_new.device != q.device or kv_new.dim() != 4 or kv_new.size(0) != batch or tuple(kv_new.shape[2:]) != tuple(kv_cache.shape[2:]):
+      raise ValueError(f"{name}: kv_new must be [B={batch}, Snew, Hkv={kv_cache.size(2)}, D={D}] of q's dtype on q's device, got {tuple(kv_new.shape)}")
+    kv_new = _rows(kv_new)
+    cache_seqlens = cache_seqlens.contiguous()
+    if cache_seqlens.data_ptr() == seqused_k.data_ptr():
+      raise ValueError(f"{name}: seqused_k receives the post-append lengths and must not be cache_seqlens")
+    m.seqlen_new, m.kv_new, m.cache_seqlens = kv_new.size(1), kv_new.data_ptr(), cache_seqlens.data_ptr()
+    m.kv_new_stride[:] = list(kv_new.stride()[:3])
+  args = (ctypes.byref(p), ctypes.byref(kv), ctypes.byref(m))
+  with torch.cuda.device(q.device):
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    nbytes = 0
+    if not (p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC):
+      key = (id(lib), q.device.index or 0, p.dtype, batch, Hq, p.heads_kv, D, m.head_dim_v, p.max_seqlen_q, p.max_seqlen_kv, Tq, p.causal, p.flags, p.num_splits,
+             os.environ.get("FFPA_HIP_FAKE_CUS"))
+      nbytes = _MLA_SCRATCH.get(key)
+      if nbytes is None:
+        if len(_MLA_SCRATCH) >= 512:
+          _MLA_SCRATCH.clear()
+        nbytes = _MLA_SCRATCH[key] = int(lib.ffpa_attn_varlen_mla_fwd_workspace_bytes(*args))
+    workspace = _hand_over_workspace(p, q.device, stream, nbytes)  # (held in a local until the launch below has been enqueued)
+    if plan_out is not None:
+      plan_out.update(_read_plan(lib, lib.ffpa_attn_varlen_mla_fwd_plan, lib.ffpa_attn_varlen_mla_fwd_kernel, _VARLEN_PLAN_KEYS, args))
+    rc = lib.ffpa_attn_varlen_mla_fwd(*args, ctypes.c_void_p(stream))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_varlen_mla_fwd")
+  return o, lse
+
+
+# kv_cache is written in place by the append (kv_new): the schema says so
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_fwd_hip",
+  "(Tensor q, Tensor(a!) kv_cache, int head_dim_v, Tensor cu_seqlens_q, Tensor(b!) seqused_k, Tensor block_table, Tensor? kv_new, Tensor? cache_seqlens, "
+  "int max_seqlen_q, int max_seqlen_k, float softmax_scale, int causal, int num_splits=0) -> (Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_fwd_hip_torch_op(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k, softmax_scale, causal,
+                          num_splits=0):
+  return mla_forward(q, kv_cache, int(head_dim_v), cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, bool(causal), softmax_scale, kv_new=kv_new,
+                     cache_seqlens=cache_seqlens, return_lse=True, num_splits=num_splits)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_fwd_hip")
+def _mla_fwd_hip_fake(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k, softmax_scale, causal,
+                      num_splits=0):
+  total_q, heads, _ = q.shape
+  return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
 
 
 # The KV-cache append + rotary (ffpa_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)): the prepare launch in front of the attention launch

@@ -18,6 +18,10 @@ Logit soft-capping (Gemma 2, Grok-1: scores ``softcap * tanh(softmax_scale * q.k
 ``ffpa_attn_with_kvcache_softcap`` (``softcap=``, with or without ``window_size``, below): the cap is applied in the kernel, in front of the masks.  Every other
 entry point keeps refusing ``softcap``.
 
+An MLA latent cache — ONE cache whose rows are the keys and, in their first ``head_dim_v`` columns, the values (DeepSeek-V2 / V3 / R1, Kimi K2 in their
+"absorbed" decode form) — has an entry of its own too, ``ffpa_attn_with_kvcache_mla`` (below): every latent row is fetched once, and the heads of a latent head are
+packed into the rows of the tiles however many they are.
+
 Inference only: ``cache_batch_idx``, ``cache_leftpad`` and ALiBi have no kernel-side implementation here and raise
 ``NotImplementedError`` naming the option — as do ``k`` without ``v`` (or ``v`` without ``k``) and rotary tables without ``k`` / ``v`` or one without the other;
 a tensor that requires grad raises (there is no backward).
@@ -481,6 +485,156 @@ def ffpa_attn_with_kvcache_softcap(
   o, lse = torch.ops.ffpa_attn._softcap_fwd_hip(qp, kp, vp, cu_q, cu_k, seqused, block_table, softcap, left, right, Sq, capacity, scale, 1 if causal else 0, -1.0,
                                                 num_splits)
   out = o.view(B, Sq, Hq, D)
+  if not return_softmax_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+# ---- MLA latent-cache attention (DeepSeek-V2 / V3 / R1, Kimi K2 in their "absorbed" decode form): ffpa_attn_with_kvcache_mla
+_MLA_REQUIRED = object()
+_MLA_IDENTITY: "dict[tuple, torch.Tensor]" = {}
+
+
+def _mla_identity_table(B: int, device) -> torch.Tensor:
+  """The block table of a contiguous latent cache — one page per sequence, page b = slab b — made on the device once per (B, device)."""
+  key = (B, device.type, device.index)
+  t = _MLA_IDENTITY.get(key)
+  if t is None:
+    if len(_MLA_IDENTITY) >= 64:
+      _MLA_IDENTITY.clear()
+    t = _MLA_IDENTITY[key] = torch.arange(B, dtype=torch.int32, device=device).view(B, 1)
+  return t
+
+
+def ffpa_attn_with_kvcache_mla(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  *,
+  kv: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor",
+  block_table: torch.Tensor | None = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  causal: bool = False,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """Attention of ``q [B, Sq, Hq, D]`` over an MLA LATENT cache: ONE cache holds, per KV head h, rows whose ``D`` columns are the keys
+  (``kv_cache[..., h, :]``) and whose first ``head_dim_v`` columns are the values (``kv_cache[..., h, :head_dim_v]``) — multi-head latent attention in its
+  "absorbed" decode form, where every query head (D = 576: a 512-wide compressed latent + 64 rotary columns) attends to one latent head.  Returns
+  ``out [B, Sq, Hq, head_dim_v]`` and, with ``return_softmax_lse``, the fp32 ``lse [B, Hq, Sq]``; the numbers of
+  ``ffpa_attn_with_kvcache(q, kv_cache, kv_cache, ...)[..., :head_dim_v]``, from a kernel that fetches every latent row once (the K and the V^T fragments of a
+  tile are read from one LDS image), packs the ``Hq / Hkv`` heads of a latent head into the rows of its tiles however many they are (128 heads x 1 token = two
+  64-row workgroups per sequence), and stores no junk columns.
+
+  ``kv_cache``: the page pool ``[num_pages, page_size, Hkv, D]`` with an int32 ``block_table [B, pages_per_seq]`` (``page_size`` a multiple of 64), or a contiguous
+  ``[B, capacity, Hkv, D]`` without one.  The contiguous cache is served by the SAME paged kernel as a pool of one page per sequence, through an identity block
+  table made on the device once per (B, device): it needs ``capacity % 64 == 0`` (``ValueError`` otherwise) and has no kernel of its own.  ``Hq % Hkv == 0``
+  (``Hkv`` is 1 in the models named above; nothing assumes it).  ``cache_seqlens``: an int or an int32 ``[B]`` device tensor of keys per sequence.  ``causal`` is
+  ``ffpa_attn_with_kvcache``'s: the last ``Sq`` keys are the queries' own.  A row that sees no key returns O = 0, LSE = -inf.
+
+  ``softmax_scale`` is REQUIRED (``TypeError``): these models scale by ``1 / sqrt(qk_nope_head_dim + qk_rope_head_dim)`` = ``1 / sqrt(192)`` times their YaRN
+  factor, which is not ``1 / sqrt(D)`` — a default would be silently wrong.
+
+  Builds: ``(D, head_dim_v) = (576, 512)``, bf16 and fp16.  Both must be multiples of 64 with ``head_dim_v <= D`` (``ValueError``); any other pair raises
+  ``NotImplementedError`` naming it.
+
+  ``kv [B, Snew, Hkv, D]`` appends the step's latent rows in place at ``cache_seqlens[b] + i`` (dropped at or past the capacity; every element stored once:
+  there is one cache) and attends over ``min(cache_seqlens + Snew, capacity)`` keys, as ``ffpa_attn_with_kvcache`` does with ``k`` / ``v``; ``cache_seqlens`` is
+  not modified.  There are NO rotary parameters: these models rotate ``k_pe`` and ``q_pe`` before the concatenation, and their rotary columns sit at the END of
+  the row — rotate before the call.
+
+  Nothing is read back to the host: the call (append + attention + the split launch's merge) captures into one HIP graph, and a replay follows
+  ``cache_seqlens``, ``block_table`` and ``kv`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``.  NOT served here,
+  each raises ``NotImplementedError`` naming the keyword: ``window_size``, ``softcap``, ``tree_mask``, ``cu_seqlens_q`` (ragged batches), shared-prefix cascades,
+  ``rotary_cos`` / ``rotary_sin``, ALiBi, ``cache_batch_idx`` / ``cache_leftpad`` and FP8 latents (a dtype error)."""
+  name = "ffpa_attn_with_kvcache_mla"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no window, soft-cap, tree mask, cascade, ragged cu_seqlens_q, rotary "
+                              "tables, ALiBi, batch index or leftpad over the latent cache: rotate q_pe / k_pe before the call)")
+  if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
+    raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
+                    "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
+  if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
+    raise TypeError(f"{name}: softmax_scale must be a real number, got {softmax_scale!r}")
+  for nm, t in (("q", q), ("kv_cache", kv_cache)) + ((("kv", kv),) if kv is not None else ()):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  if q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
+  if q.dim() != 4 or kv_cache.dim() != 4:
+    raise ValueError(f"{name}: q must be [B, Sq, Hq, D] and kv_cache 4-D")
+  B, Sq, Hq, D = q.shape
+  Hkv = kv_cache.size(2)
+  if kv_cache.size(3) != D:
+    raise ValueError(f"{name}: head dim of the cache ({kv_cache.size(3)}) differs from q's ({D})")
+  if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int):
+    raise TypeError(f"{name}: head_dim_v must be an int, got {head_dim_v!r}")
+  if D % 64 != 0 or head_dim_v <= 0 or head_dim_v % 64 != 0 or head_dim_v > D:
+    raise ValueError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}): both must be multiples of 64 with 0 < head_dim_v <= D")
+  from .hip import MLA_BUILDS
+
+  if (D, head_dim_v) not in MLA_BUILDS:
+    raise NotImplementedError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
+  if Hkv == 0 or Hq % Hkv != 0:
+    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of the latent num_heads ({Hkv})")
+  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
+  if kv_cache.device != q.device:
+    raise ValueError(f"{name}: q / kv_cache must be on one device, got {q.device}, {kv_cache.device}")
+  if block_table is not None:
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B:
+      raise ValueError(f"{name}: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
+    if block_table.size(1) == 0:
+      raise ValueError(f"{name}: block_table needs at least one page per sequence")
+    page_size = kv_cache.size(1)
+    if page_size <= 0 or page_size % 64 != 0:
+      raise ValueError(f"{name}: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
+    if block_table.device != q.device:
+      raise ValueError(f"{name}: block_table must be on q's device, got {block_table.device} and {q.device}")
+    capacity = block_table.size(1) * page_size
+  else:
+    if kv_cache.size(0) != B:
+      raise ValueError(f"{name}: kv_cache [B, capacity, Hkv, D] must have q's batch ({B}), got {kv_cache.size(0)}")
+    capacity = kv_cache.size(1)
+    if capacity <= 0 or capacity % 64 != 0:
+      raise ValueError(f"{name}: a contiguous cache runs as a pool of one page per sequence: its capacity ({capacity}) must be a positive multiple of 64")
+  if isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
+    if cache_seqlens < 0:
+      raise ValueError(f"{name}: cache_seqlens must be non-negative, got {cache_seqlens}")
+    lens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
+  elif isinstance(cache_seqlens, torch.Tensor):
+    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
+      raise ValueError(f"{name}: cache_seqlens must be an int or an int32 tensor [batch={B}] on q's device")
+    lens = cache_seqlens
+  else:
+    raise TypeError(f"{name}: cache_seqlens must be an int or an int32 tensor, got {type(cache_seqlens).__name__}")
+  if kv is not None:
+    if kv.dtype != q.dtype:
+      raise TypeError(f"{name}: kv must have the cache's dtype {q.dtype}, got {kv.dtype}")
+    if kv.device != q.device:
+      raise ValueError(f"{name}: kv must be on q's device, got {kv.device} and {q.device}")
+    if kv.dim() != 4 or kv.size(0) != B or kv.size(2) != Hkv or kv.size(3) != D:
+      raise ValueError(f"{name}: kv must be [B={B}, Snew, Hkv={Hkv}, D={D}], got {tuple(kv.shape)}")
+    if kv.stride(-1) != 1:
+      raise ValueError(f"{name}: kv must have a contiguous last dimension")
+  from . import hip  # (registers the ffpa_attn ops)
+
+  out_shape = (B, Sq, Hq, head_dim_v)
+  if B == 0 or Sq == 0:
+    out = q.new_zeros(out_shape)
+    return (out, q.new_full((B, Hq, Sq), float("-inf"), dtype=torch.float32)) if return_softmax_lse else out
+  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
+  qp = q.reshape(B * Sq, Hq, D)
+  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
+  kv_new = kv if kv is not None and kv.size(1) > 0 else None
+  seqused = torch.empty((B,), dtype=torch.int32, device=q.device) if kv_new is not None else lens
+  o, lse = torch.ops.ffpa_attn._mla_fwd_hip(qp, kv_cache, head_dim_v, cu_q, seqused, table, kv_new, lens if kv_new is not None else None, Sq, capacity,
+                                            float(softmax_scale), 1 if causal else 0, num_splits)
+  out = o.view(*out_shape)
   if not return_softmax_lse:
     return out
   return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()

@@ -428,6 +428,45 @@ int ffpa_attn_varlen_softcap_fwd_plan(const ffpa_varlen_fwd_params* p, const ffp
 int ffpa_attn_varlen_softcap_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap, char* buf, size_t n);
 
 /*
+ * MLA LATENT CACHE (multi-head latent attention in its "absorbed" decode form: DeepSeek-V2 / V3 / R1, Kimi K2) over the paged call: ONE pool holds the latent
+ * rows, the keys of KV head h are a row's p->head_dim columns and its values the FIRST head_dim_v columns of the same row.  The paged call with these changes:
+ *   kv is REQUIRED (a contiguous cache is a pool of one page per sequence: page_size = its capacity, a multiple of 64, and an identity block table).
+ *   p->k is the latent pool (p->k_stride = {row, head} inside a page, kv->k_page_stride between pages); p->v, p->v_stride and kv->v_page_stride are NOT READ.
+ *   p->o is [total_q, heads_q, head_dim_v] by p->o_stride: only columns < head_dim_v are stored.  p->lse as in the paged call.
+ *   (p->head_dim, head_dim_v) must be a pair the library is built for — (576, 512) — and in general multiples of 64 with head_dim_v <= head_dim.
+ *   p->softmax_scale is the caller's: these models scale by 1 / sqrt(qk_nope + qk_rope) (x their YaRN factor), which is not 1 / sqrt(head_dim).
+ * A latent row is fetched once per workgroup (the kernel reads the K and the V^T fragments of a tile from one LDS image).  The heads_q / heads_kv query heads of
+ * a KV head x the sequence's tokens are the rows of its tiles, head-major, however many they are: ceil(group * max_seqlen_q / block rows) row tiles per
+ * (sequence, KV head), neighbours in the launch order — 128 heads on one latent head are two 64-row tiles per sequence (FFPA_FLAG_NO_PACK_GQA: one workgroup
+ * per query head).  The non-temporal fetch is taken only where a latent byte has one reader: one row tile.
+ * APPEND (seqlen_new > 0): row i of sequence b of kv_new ([batch, seqlen_new, heads_kv, head_dim] by kv_new_stride = {batch, row, head}) is first written — once —
+ * at cache position max(cache_seqlens[b], 0) + i (dropped at or past pages_per_row * page_size), by one more launch on `stream` in front of the attention
+ * launch, which also writes p->seqused_kv[b] = min(max(cache_seqlens[b], 0) + seqlen_new, capacity): p->seqused_kv is then an OUTPUT (and the lengths attention
+ * runs over) and must not be cache_seqlens.  No rotary: these models rotate k_pe / q_pe before the concatenation.
+ * Not served (use the other calls on a (kv, kv) pair): windows, soft-capping, tree masks, ragged positions, FP8 latents.
+ */
+typedef struct ffpa_mla {
+  uint32_t struct_size;          /* sizeof(ffpa_mla), checked */
+  uint32_t reserved;             /* 0, checked */
+  int32_t head_dim_v;            /* value width: the first head_dim_v columns of a latent row */
+  int32_t seqlen_new;            /* rows per sequence of kv_new; 0 = nothing is appended */
+  const void* kv_new;            /* device, 16-byte aligned; read when seqlen_new > 0 */
+  const int32_t* cache_seqlens;  /* device [batch]: the lengths before the step; read when seqlen_new > 0 */
+  int64_t kv_new_stride[3];      /* elements: batch, row, head */
+} ffpa_mla;
+
+/* Launch the latent-cache forward (and, in front of it, the append) on `stream` of the CURRENT device.  Asynchronous; every bad argument — a NULL kv or m, a wrong
+ * struct_size, a non-zero reserved, a value width that is no multiple of 64 in [64, head_dim], a pair that is not built — returns a status before any device
+ * work.  Returns an ffpa_status. */
+int ffpa_attn_varlen_mla_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, void* stream);
+
+/* As ffpa_attn_varlen_fwd_workspace_bytes / _plan / _kernel, for the latent-cache call ("ffpa_fwd_m16_mla_kernel<bf16, 576, dv=512>"; out[0] = row tiles per
+ * (sequence, KV head) when the heads are packed into rows). */
+size_t ffpa_attn_varlen_mla_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m);
+int ffpa_attn_varlen_mla_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int out[5]);
+int ffpa_attn_varlen_mla_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, char* buf, size_t n);
+
+/*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
  * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
  *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position

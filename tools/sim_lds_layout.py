@@ -211,12 +211,100 @@ def check_m16(D):
   return worst_k, worst_v
 
 
+def mla_sw(D, key):
+  """The source-side swizzle of the SHARED image of the MLA build (csrc/ffpa_fwd_m16_tile.inc under FFPA_M16_MLA_ON): the V map of the 16x16x32 build."""
+  return m16_v_sw(D, key)
+
+
+# What the shared image can be swizzled with: the two maps the K and V images of the 16x16x32 build use today, and no swizzle at all.
+MLA_CANDIDATES = {"k map": m16_k_sw, "v map": m16_v_sw, "none": lambda D, key: 0}
+
+
+def check_m16_shared(D=576, sw=None, quiet=False):
+  """The MLA build's ONE latent tile image (D % 128 == 64, D > 512: 32-key tiles, D split over two waves): both products read the image the DMA wrote once —
+    K fragment (lane l, step s, 16-key block kb) = L[16 kb + l % 16][dh DW + 32 s + 8 (l / 16) .. + 8]                       (ds_read_b128)
+    V^T fragment (lane l, column block db, element e) = L[16 (e / 4) + 4 (l / 16) + e % 4][dh DW + 16 db + l % 16]           (two ds_read_b64_tr_b16)
+  against ONE source-side swizzle ``sw(D, key)`` (default: ``mla_sw``).  Replays every ds_read_b128 16-lane group and every transpose-read 32-lane half under the
+  bank rule of ``check_m16`` -> (worst K conflict, worst V^T conflict, K conflict cycles, V^T conflict cycles): ways of the worst group (1 = conflict-free) and
+  the extra cycles summed over all groups of one tile (a group of m-way conflict costs m - 1)."""
+  sw = sw or mla_sw
+  assert D > 512 and D % 128 == 64, "the MLA hook lives in the un-pipelined split-D loop"
+  ND, BC = 2, 32
+  DW = D // ND
+  RB, SPR = D * 2, D // 8
+  PPW = BC * D * 2 // 4096
+  img = {}
+  for wave in range(4):
+    for i in range(PPW):
+      for lane in range(64):
+        g = (wave * PPW + i) * 64 + lane
+        key, slot = divmod(g, SPR)
+        src = (slot ^ sw(D, key)) << 4
+        dst = (wave * PPW + i) * 1024 + lane * 16
+        assert 0 <= src < RB and key < BC, (D, key, src)
+        for b in range(0, 16, 2):
+          assert dst + b not in img
+          img[dst + b] = (key, src + b)
+  assert len(img) == BC * RB // 2
+  KV, KVB, VV, VVB = 2, 128, 4, 128
+  worst_k = worst_v = 1
+  cyc_k = cyc_v = 0
+  for dh in range(ND):
+    c0 = dh * (DW // 8)
+    for kb in range(BC // 16):
+      for s in range(DW // 32):
+        addrs = []
+        for lane in range(64):
+          n, c = lane & 15, lane >> 4
+          a = n * RB + (((c0 + 4 * (s % KV) + c) ^ sw(D, n)) << 4) + (s // KV) * KVB + kb * 16 * RB
+          addrs.append(a)
+          for e in range(8):
+            assert img[a + 2 * e] == (16 * kb + n, (dh * DW + 32 * s + 8 * c + e) * 2), (D, lane, s, kb, e)
+        for grp in ([0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27], [4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31]):
+          for half in (0, 32):
+            banks = {}
+            for l in grp:
+              banks.setdefault((addrs[l + half] // 16) % 16, set()).add(addrs[l + half])
+            m = max(len(v) for v in banks.values())
+            worst_k, cyc_k = max(worst_k, m), cyc_k + m - 1
+    for db in range(DW // 16):
+      for second in (0, 1):
+        la = []
+        for lane in range(64):
+          n, c = lane & 15, lane >> 4
+          vkey = 4 * c + (n >> 2)
+          la.append(vkey * RB + (((c0 + 2 * (db % VV) + ((n & 3) >> 1)) ^ sw(D, vkey)) << 4) + 8 * (n & 1) + (db // VV) * VVB + 16 * second * RB)
+        for lane in range(64):
+          i, base_lane, c = lane & 15, lane & ~15, lane >> 4
+          for e in range(4):
+            got = img[la[base_lane + 4 * e + (i >> 2)] + 2 * (i & 3)]
+            want = (16 * second + 4 * c + e, (dh * DW + 16 * db + i) * 2)
+            assert got == want, (D, lane, db, second, e, got, want)
+        for half in (0, 32):
+          banks = {}
+          for l in range(32):
+            banks.setdefault((la[l + half] // 8) % 32, set()).add(la[l + half])
+          m = max(len(v) for v in banks.values())
+          worst_v, cyc_v = max(worst_v, m), cyc_v + m - 1
+  if not quiet:
+    print(f"D={D:5d} MLA shared image ND={ND} BC={BC}: K/V fragment maps OK; worst bank conflict: ds_read_b128 {worst_k}-way ({cyc_k} cycles), "
+          f"tr_b16 {worst_v}-way ({cyc_v} cycles)")
+  return worst_k, worst_v, cyc_k, cyc_v
+
+
 def variants(D):
   """(D, ND) pairs the library instantiates: the prefill tiles and the short-query (split over 2 / 4 waves) tiles."""
   return [(D, 1 if D <= 512 else 2), (D, 4 if D % 128 == 0 else 2)]
 
 
 if __name__ == "__main__":
+  if "--mla" in sys.argv[1:]:  # the shared image of the MLA build: every candidate map, then the one the kernel uses
+    for name, fn in MLA_CANDIDATES.items():
+      print(f"{name:6s}", end=" ")
+      check_m16_shared(576, fn)
+    print("kernel", end=" ")
+    check_m16_shared(576)
+    sys.exit(0)
   for D in ([int(x) for x in sys.argv[1:]] or [64, 128, 192, 256, 320, 384, 448, 512, 576, 640, 704, 768, 832, 896, 960, 1024]):
     for d, nd in dict.fromkeys(variants(D)):
       check(d, nd)
