@@ -1005,6 +1005,20 @@ int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = f
       out->grid = slots * p->heads_q;
     }
   }
+  // The same for the PACKED rows of a ragged latent-cache batch (one 40-token verification among five decodes at 128 heads: 480 workgroups of which 91 find rows;
+  // a 512-token chunk among 63 decodes: 65 536, about 1 150).  A sequence of len_b tokens has ceil(group x len_b / block rows) chunks — what the MLA build's scan
+  // counts (ffpa_fwd_m16_varlen_seq.inc) —, and sum_b ceil(group x len_b / BR) <= sum_b (group x len_b / BR + 1) <= ceil(group x total_q / BR) + batch: the
+  // slots per KV head.  The grid is slots x Hkv in the launch order it had (KV head, sequence, row tile): the chunks of a (sequence, latent head) stay neighbours.
+  // The three-quarter threshold is the rule above carried over — FITTED ON THE UNPACKED PREFILL KERNEL, not on this one (profiles/r18_mla_varlen.md: every batch
+  // the rule takes wins 2.5 ... 6.8 x against the full grid, one exactly on the threshold 2.9 x; the crossover was not located).  A uniform batch never meets it (slots >= batch x nqt there).  The split rule and the one-reader rule below run on this grid and nqt:
+  // the non-temporal fetch stays a launch-wide decision, so a decode batch that holds a chunk (nqt > 1) loses it.
+  if (mla && out->pack && out->nqt > 1 && p->total_q > 0 && !(p->flags & FFPA_FLAG_NO_COMPACT_GRID)) {
+    const int64_t slots = ((int64_t)group * p->total_q + out->br - 1) / out->br + p->batch;
+    if (slots * 4 <= (int64_t)p->batch * out->nqt && slots <= 0x7fffffffLL) {
+      out->compact = (int)slots;
+      out->grid = slots * p->heads_kv;
+    }
+  }
   // The non-temporal K / V fetch (the dense short-query launches' rule, ffpa_attn_fwd): every K / V byte is read by ONE workgroup — one row tile per (sequence,
   // head), and MHA or packed GQA rows — and the batch's K + V do not fit the 256 MiB Infinity Cache.  The launch side sees only max_seqlen_kv, not the lengths: it
   // prices a ragged batch at half of batch x max (>= 272 MiB of that).  LDS-DMA from HBM: 5.9 TB/s without the hint, 7.3 with it (profiles/r04_kv_stream.txt);
@@ -1608,8 +1622,57 @@ int ffpa_attn_varlen_mla_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_
   const int rc = mla_plan(p, kv, m, &pl);
   if (rc != FFPA_OK) return rc;
   if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
-  snprintf(buf, n, "ffpa_fwd_m16_mla_kernel<%s, %d, dv=%d%s>%s%s", p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", p->head_dim, m->head_dim_v, pl.nt ? ", NT" : "",
-           pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "", pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
+  snprintf(buf, n, "ffpa_fwd_m16_mla_kernel<%s, %d, dv=%d%s>%s%s%s", p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", p->head_dim, m->head_dim_v, pl.nt ? ", NT" : "",
+           pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "", pl.compact > 0 ? " (compact grid)" : "",
+           pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
+  return FFPA_OK;
+}
+
+int ffpa_attn_varlen_mla_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int* slots) {
+  VarlenPlan pl;
+  const int rc = mla_plan(p, kv, m, &pl);
+  if (rc != FFPA_OK) return rc;
+  if (slots == nullptr) return fail(FFPA_ERR_NULL_POINTER, "slots is NULL");
+  *slots = pl.compact;
+  return FFPA_OK;
+}
+
+// ---- the latent append of a ragged step (include/ffpa_attn.h: ffpa_mla_append_varlen_params): token rows packed by cu_seqlens_q into the ONE paged pool
+int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, void* stream) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_mla_append_varlen_params))
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_append_varlen_params ABI mismatch: size %u (want %zu)", p->struct_size, sizeof(ffpa_mla_append_varlen_params));
+  if (p->reserved != 0 || p->reserved2 != 0) return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_append_varlen_params.reserved=%u / reserved2=%d must be 0", p->reserved, p->reserved2);
+  if (p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
+  if (p->batch <= 0 || p->heads_kv <= 0) return fail(FFPA_ERR_BAD_SHAPE, "non-positive dimension: batch=%d Hkv=%d", p->batch, p->heads_kv);
+  if (p->head_dim <= 0 || p->head_dim % 8 != 0 || p->head_dim > 1024)
+    return fail(FFPA_ERR_BAD_HEADDIM, "headdim not support! D=%d (supported: multiples of 8 in [8, 1024])", p->head_dim);
+  if (p->total_q < 0) return fail(FFPA_ERR_BAD_SHAPE, "total_q=%d must not be negative", p->total_q);
+  if (kv == nullptr) return fail(FFPA_ERR_NULL_POINTER, "paged kv is NULL");
+  int rc;
+  if ((rc = check_pool(kv)) != FFPA_OK) return rc;  // (page_size % 64 among the rest)
+  if (!p->kv_cache || !p->cu_seqlens_q || !p->cache_seqlens || !p->seqused)
+    return fail(FFPA_ERR_NULL_POINTER, "kv_cache / cu_seqlens_q / cache_seqlens / seqused must be non-NULL");
+  if (p->total_q > 0 && !p->kv_new) return fail(FFPA_ERR_NULL_POINTER, "kv_new must be non-NULL when total_q > 0");
+  if (p->seqused == p->cache_seqlens) return fail(FFPA_ERR_BAD_SHAPE, "seqused must not be cache_seqlens (the kernel reads one while it writes the other)");
+  if ((reinterpret_cast<uintptr_t>(p->seqused) & 3u) || (reinterpret_cast<uintptr_t>(p->cache_seqlens) & 3u) || (reinterpret_cast<uintptr_t>(p->cu_seqlens_q) & 3u))
+    return fail(FFPA_ERR_MISALIGNED, "seqused / cache_seqlens / cu_seqlens_q must be 4-byte aligned");
+  if (!aligned16(p->kv_cache) || (p->total_q > 0 && !aligned16(p->kv_new))) return fail(FFPA_ERR_MISALIGNED, "kv_new / kv_cache base pointers must be 16-byte aligned");
+  if ((rc = check_strides("kv_cache", p->kv_cache_stride, 2)) || (p->total_q > 0 && (rc = check_strides("kv_new", p->kv_new_stride, 2)))) return rc;
+  if ((rc = check_device()) != FFPA_OK) return rc;
+
+  ffpa::MlaAppendVarlenArgs va;
+  memset(&va, 0, sizeof(va));
+  ffpa::MlaAppendArgs& a = va.a;
+  a.kv_new = p->kv_new, a.cache = p->kv_cache;
+  a.seqlens = p->cache_seqlens, a.used = p->seqused, a.table = kv->block_table;
+  a.s_new[1] = p->kv_new_stride[0], a.s_new[2] = p->kv_new_stride[1];
+  a.s_row = p->kv_cache_stride[0], a.s_head = p->kv_cache_stride[1], a.s_page = kv->k_page_stride, a.bt_stride = kv->bt_stride;
+  a.B = p->batch, a.Hkv = p->heads_kv, a.D = p->head_dim;
+  a.cap = kv->pages_per_row * kv->page_size, a.page_size = kv->page_size, a.num_pages = kv->num_pages;
+  va.cu_q = p->cu_seqlens_q, va.T = p->total_q;
+  const int st = ffpa::launch_mla_append_varlen(va, static_cast<hipStream_t>(stream));
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla append (varlen) launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
   return FFPA_OK;
 }
 

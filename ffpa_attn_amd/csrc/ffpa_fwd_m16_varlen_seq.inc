@@ -34,7 +34,14 @@
       int n = 0;
       if (i < a_in.B) {
         const int len = va.cu_q[i + 1] - va.cu_q[i];
+#ifdef FFPA_M16_MLA_ON
+        // (the latent-cache build, ffpa_mla_inst.hip: the row tiles of a packed launch are the chunks of the sequence's pack x len rows — the count the row test
+        // below and the causal reversal use; a preprocessor test, so that every other kernel's text is what it was)
+        const int rows = va.pack ? va.pack * len : len;
+        n = rows > 0 ? (rows + BR - 1) / BR : 0;
+#else
         n = len > 0 ? (len + BR - 1) / BR : 0;
+#endif
       }
       int incl = n;
 #pragma unroll

@@ -14,6 +14,7 @@
 //     lane l of workgroup row x (y == 0) writes used[256 x + l]; the grid has at least ceil(B / 256) rows.
 // The lane layout, the loads-before-stores order and the rotation are HeadRows' (ffpa_kvcache_append_rows.h): on a uniform batch the bytes written to the cache
 // and to q_rot are the [B, S] kernel's.
+#include "ffpa_cu_seqlens_find.h"
 #include "ffpa_kvcache_append.h"
 #include "ffpa_kvcache_append_rows.h"
 
@@ -28,19 +29,7 @@ __global__ __launch_bounds__(256) void ffpa_kv_append_varlen_kernel(const KvAppe
   // Everything the row reads through a wave-uniform index — the search of cu_q, its sequence's length, its page id, its position — is read BEFORE the kernel's
   // first store (used[], below): up to there the compiler can prove the arrays unchanged and reads them with scalar loads; a load behind the store is a vector
   // load plus a readfirstlane, and the search is a chain of dependent ones.
-  // the last b with cu_q[b] <= t: the first b in [0, B] whose cu_q[b + 1] > t (B: none — a padding row, as is every row t >= T of a grid sized for used[])
-  int b = a.B;
-  if (t < a.T) {
-    int hi = a.B;
-    b = 0;
-    while (b < hi) {
-      const int mid = (b + hi) >> 1;
-      if (va.cu_q[mid + 1] <= t)
-        b = mid + 1;
-      else
-        hi = mid;
-    }
-  }
+  const int b = cu_seqlens_find(va.cu_q, a.B, a.T, t);  // (a.B: a padding row)
   const bool real = b < a.B;
   const int i = real ? t - va.cu_q[b] : -1;  // (negative under a cu_q that does not ascend: the row is dropped, never a negative cache row)
   const int len = real ? a.seqlens[b] : 0;

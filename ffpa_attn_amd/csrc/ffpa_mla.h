@@ -33,9 +33,19 @@ struct MlaAppendArgs {
   int B, Snew, Hkv, D, cap, page_size, num_pages;
 };
 
+// The latent append of a RAGGED step (ffpa_attn_mla_append_varlen): kv_new is token rows [T, Hkv, D] packed by cu_q (a.s_new = {unused, row, head}; a.Snew is not
+// read), row t is token i = t - cu_q[b] of its sequence b and goes to cache position max(seqlens[b], 0) + i; used[b] = min(max(seqlens[b], 0) + (cu_q[b + 1] -
+// cu_q[b]), cap) for every b < B.
+struct MlaAppendVarlenArgs {
+  MlaAppendArgs a;
+  const int* cu_q;  // [B + 1]
+  int T;            // token rows of kv_new (>= cu_q[B]: the rest is padding)
+};
+
 #define FFPA_DECL(D, DV) int launch_mla_paged_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaArgs& ma, hipStream_t stream);
 FFPA_FOR_EACH_MLA_BUILD(FFPA_DECL)
 #undef FFPA_DECL
 int launch_mla_append(const MlaAppendArgs& a, hipStream_t stream);
+int launch_mla_append_varlen(const MlaAppendVarlenArgs& va, hipStream_t stream);
 
 }  // namespace ffpa

@@ -7,6 +7,7 @@
 // lookahead) with the tile text's MLA hook on (FFPA_M16_MLA_ON, ffpa_fwd_m16_tile.inc): the two LDS images of the tile, Kt and Vt, alternate as the home of ONE
 // latent tile — tile j lives in image j & 1, QK^T(j) reads its K fragments there and PV(j) its V^T fragments from the same bytes.  There are no V pieces: a
 // latent row is fetched once.  A contiguous cache runs through the same kernel with one page per sequence (the Python entry's identity table).
+#include "ffpa_cu_seqlens_find.h"
 #include "ffpa_fwd_kernel.h"
 #include "ffpa_fwd_m16_kernel.h"
 #include "ffpa_launch_kernel.h"
@@ -94,6 +95,51 @@ __global__ __launch_bounds__(256) void ffpa_mla_append_kernel(const MlaAppendArg
 int launch_mla_append(const MlaAppendArgs& a, hipStream_t stream) {
   const int T = a.Snew > 0 ? a.Snew : 1;
   hipLaunchKernelGGL(ffpa_mla_append_kernel, dim3((unsigned)(a.B * T)), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
+// THE LATENT APPEND OF A RAGGED STEP (ffpa_attn_mla_append_varlen): one workgroup per token row t of kv_new [T, Hkv, D] packed by cu_q.  The row finds its
+// sequence b by the two-cache ragged append's search (cu_seqlens_find) and is written once, as above, at cache position max(seqlens[b], 0) + (t - cu_q[b]);
+// rows from cu_q[B] on are padding and write nothing.  Everything read through a wave-uniform index — the search, the sequence's length, its page id — stands
+// in front of the kernel's first store (used[]): up to there the compiler reads the arrays with scalar loads.
+//   used[b] for EVERY b < B, sequences without a token too, so not by the token rows: lane l of workgroup x writes used[256 x + l]; the grid has at least
+//   ceil(B / 256) workgroups (T == 0 and T < B included).
+__global__ __launch_bounds__(256) void ffpa_mla_append_varlen_kernel(const MlaAppendVarlenArgs va) {
+  const MlaAppendArgs& a = va.a;
+  const int t = blockIdx.x, tid = threadIdx.x;
+  const int b = cu_seqlens_find(va.cu_q, a.B, va.T, t);  // (a.B: a padding row)
+  const bool real = b < a.B;
+  const int i = real ? t - va.cu_q[b] : -1;  // (negative under a cu_q that does not ascend: the row is dropped, never a negative cache row)
+  const int len = real ? a.seqlens[b] : 0;
+  const int64_t base = len > 0 ? len : 0;  // (negative lengths act as 0, as in the attention kernels)
+  const int64_t pos = base + i;
+  const bool kv_row = real && i >= 0 && pos < a.cap;  // (a position at or past the capacity is dropped; pos / page_size < pages_per_row: the table's row is not left)
+  int page = 0, row = 0;
+  if (kv_row) {
+    page = a.table[(int64_t)b * a.bt_stride + pos / a.page_size];
+    page = page > 0 ? page : 0;
+    page = page < a.num_pages - 1 ? page : a.num_pages - 1;
+    row = (int)(pos % a.page_size);
+  }
+  const int64_t s = (int64_t)t * 256 + tid;
+  if (s < a.B) {
+    const int slen = a.seqlens[s];
+    const int64_t n = (int64_t)(slen > 0 ? slen : 0) + (va.cu_q[s + 1] - va.cu_q[s]);
+    a.used[s] = (int)(n < a.cap ? n : a.cap);
+  }
+  if (!kv_row) return;
+  const uint16_t* src = (const uint16_t*)a.kv_new + t * a.s_new[1];
+  uint16_t* dst = (uint16_t*)a.cache + page * a.s_page + row * a.s_row;
+  const int cpr = a.D / 8;  // 16-byte chunks per head row
+  for (int e = tid; e < a.Hkv * cpr; e += 256) {
+    const int h = e / cpr, c = e - h * cpr;
+    *(u32x4*)(dst + h * a.s_head + c * 8) = *(const u32x4*)(src + h * a.s_new[2] + c * 8);
+  }
+}
+
+int launch_mla_append_varlen(const MlaAppendVarlenArgs& va, hipStream_t stream) {
+  const unsigned used_wgs = (unsigned)((va.a.B + 255) / 256);
+  hipLaunchKernelGGL(ffpa_mla_append_varlen_kernel, dim3((unsigned)va.T > used_wgs ? (unsigned)va.T : used_wgs), dim3(256), 0, stream, va);
   return (int)hipGetLastError();
 }
 #endif

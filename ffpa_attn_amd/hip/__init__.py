@@ -213,6 +213,28 @@ class FfpaMla(ctypes.Structure):
   ]
 
 
+class FfpaMlaAppendVarlenParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_mla_append_varlen_params`` (include/ffpa_attn.h): the latent append of a ragged step."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("kv_new", ctypes.c_void_p),
+    ("kv_cache", ctypes.c_void_p),
+    ("cu_seqlens_q", ctypes.c_void_p),
+    ("cache_seqlens", ctypes.c_void_p),
+    ("seqused", ctypes.c_void_p),
+    ("kv_new_stride", ctypes.c_int64 * 2),
+    ("kv_cache_stride", ctypes.c_int64 * 2),
+    ("batch", ctypes.c_int32),
+    ("total_q", ctypes.c_int32),
+    ("heads_kv", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("dtype", ctypes.c_int32),
+    ("reserved2", ctypes.c_int32),
+  ]
+
+
 class FfpaKvAppendParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_kv_append_params`` (include/ffpa_attn.h): the KV-cache append + rotary call."""
 
@@ -359,6 +381,8 @@ _BINDINGS = (
   ("ffpa_attn_varlen_mla_fwd_plan", _MLA + [_P(_INT)], _INT, 7),
   ("ffpa_attn_varlen_mla_fwd_kernel", _MLA + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_mla_fwd_workspace_bytes", _MLA, _SIZE, 7),
+  ("ffpa_attn_varlen_mla_fwd_compact_slots", _MLA + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_mla_append_varlen", [_P(FfpaMlaAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
@@ -453,7 +477,7 @@ def _stamped(cls):
   """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` / ``ffpa_window`` / ``ffpa_mla`` ride next to a versioned struct), the ABI version — filled in."""
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
-  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla):
+  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams):
     p.abi_version = ABI_VERSION
   return p
 
@@ -1461,6 +1485,23 @@ def mla_row_chunks(group: int, seqlen_q: int, block_rows: int = 64) -> "list[lis
   return [rows[i:i + block_rows] for i in range(0, len(rows), block_rows)]
 
 
+def mla_ragged_row_chunks(group: int, seqlens_q: "list[int]", block_rows: int = 64) -> "tuple[list[list[list[tuple[int, int]]]], int]":
+  """``mla_row_chunks`` for a RAGGED batch: sequence b brings ``seqlens_q[b]`` tokens, and its ``group * seqlens_q[b]`` packed rows are cut into its own
+  ``ceil(group * seqlens_q[b] / block_rows)`` chunks (none for an empty sequence) -> ``(the chunks of every sequence, slots)``.  ``slots`` =
+  ``ceil(group * sum(seqlens_q) / block_rows) + len(seqlens_q)``: the row-tile slots per KV head of the compact grid, an upper bound of the number of chunks
+  (every sequence rounds up by less than one tile).  The plan takes the compact grid when ``4 * slots <= len(seqlens_q) * ceil(group * max(seqlens_q) /
+  block_rows)`` — the full grid's row tiles per KV head — and the rows are packed over more than one tile (``group > 1``, ``group * max(seqlens_q) > block_rows``)."""
+  chunks = [mla_row_chunks(group, n, block_rows) if n > 0 else [] for n in seqlens_q]
+  return chunks, -(-group * sum(seqlens_q) // block_rows) + len(seqlens_q)
+
+
+def mla_compact_slots(group: int, seqlens_q: "list[int]", block_rows: int = 64) -> int:
+  """The plan's compact-grid decision for packed latent rows as a pure function (``mla_ragged_row_chunks``' rule) -> the slots per KV head, or 0 for the full grid."""
+  slots = mla_ragged_row_chunks(group, seqlens_q, block_rows)[1]
+  nqt = -(-group * max(seqlens_q) // block_rows)
+  return slots if group > 1 and nqt > 1 and sum(seqlens_q) > 0 and 4 * slots <= len(seqlens_q) * nqt else 0
+
+
 def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seqlens_q: torch.Tensor, seqused_k: torch.Tensor, block_table: torch.Tensor,
                 max_seqlen_q: int, max_seqlen_k: int, causal: bool, softmax_scale: float, *, kv_new: "torch.Tensor | None" = None,
                 cache_seqlens: "torch.Tensor | None" = None, return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
@@ -1537,6 +1578,9 @@ def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seq
     workspace = _hand_over_workspace(p, q.device, stream, nbytes)  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
       plan_out.update(_read_plan(lib, lib.ffpa_attn_varlen_mla_fwd_plan, lib.ffpa_attn_varlen_mla_fwd_kernel, _VARLEN_PLAN_KEYS, args))
+      slots = ctypes.c_int(0)
+      if hasattr(lib, "ffpa_attn_varlen_mla_fwd_compact_slots") and lib.ffpa_attn_varlen_mla_fwd_compact_slots(*args, ctypes.byref(slots)) == 0:
+        plan_out["compact_slots"] = slots.value  # (row-tile slots per KV head of the compact grid; 0: the full grid)
     rc = lib.ffpa_attn_varlen_mla_fwd(*args, ctypes.c_void_p(stream))
   if rc != 0:
     _raise_status(lib, rc, "ffpa_attn_varlen_mla_fwd")
@@ -1563,6 +1607,67 @@ def _mla_fwd_hip_fake(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_ta
                       num_splits=0):
   total_q, heads, _ = q.shape
   return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
+
+
+# The latent append of a ragged step (ffpa_attn_varlen_with_kvcache_mla(kv=)): token rows packed by cu_seqlens_q, in front of the attention launch
+def mla_append_varlen(kv_cache: torch.Tensor, kv_new: torch.Tensor, cu_seqlens_q: torch.Tensor, cache_seqlens: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+  """One launch of ``ffpa_attn_mla_append_varlen``: ``kv_new [T, Hkv, D]``, packed by the int32 device ``cu_seqlens_q [B + 1]``, written into the latent pool
+  ``kv_cache [num_pages, page_size, Hkv, D]`` in place through the int32 ``block_table [B, pages_per_seq]`` — token i of sequence b at cache position
+  ``max(cache_seqlens[b], 0) + i``, every element stored once, positions at or past the capacity dropped, rows at or past ``cu_seqlens_q[B]`` not written
+  -> ``seqused``: the int32 ``[B]`` post-append lengths ``min(max(cache_seqlens, 0) + Sq_b, capacity)``, sequences without a token included.  Asynchronous,
+  nothing read back to the host."""
+  name = "ffpa_attn::_mla_append_varlen_hip"
+  if not kv_cache.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{kv_cache.device.type}' (the HIP kernel needs a GPU tensor)")
+  lib = load_library()
+  if kv_cache.dtype not in _DTYPE or kv_new.dtype != kv_cache.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 kv_cache/kv_new of one dtype, got {kv_cache.dtype}, {kv_new.dtype}")
+  if kv_cache.dim() != 4 or kv_new.dim() != 3 or tuple(kv_new.shape[1:]) != tuple(kv_cache.shape[2:]):
+    raise ValueError(f"{name}: kv_new must be [T, Hkv={kv_cache.size(2)}, D={kv_cache.size(3)}] for the pool {tuple(kv_cache.shape)}, got {tuple(kv_new.shape)}")
+  if cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.device != kv_cache.device:
+    raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor of length batch + 1 on the cache's device")
+  B = cu_seqlens_q.numel() - 1
+  if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != kv_cache.device:
+    raise ValueError(f"{name}: cache_seqlens must be a 1-D int32 tensor of length batch on the cache's device")
+  if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B or block_table.size(1) == 0 or block_table.device != kv_cache.device:
+    raise ValueError(f"{name}: block_table must be a 2-D int32 tensor [batch, pages_per_seq] (pages_per_seq >= 1) on the cache's device")
+  if kv_new.device != kv_cache.device or kv_cache.size(0) == 0:
+    raise ValueError(f"{name}: kv_new and a non-empty kv_cache must be on one device")
+  if not _layout_ok(kv_cache, -3):
+    raise ValueError(f"{name}: kv_cache is written in place and needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base")
+  kv_new = _rows(kv_new)
+  cache_seqlens, cu_seqlens_q = cache_seqlens.contiguous(), cu_seqlens_q.contiguous()
+  seqused = torch.empty((B,), dtype=torch.int32, device=kv_cache.device)
+  p = _stamped(FfpaMlaAppendVarlenParams)
+  p.kv_cache = kv_cache.data_ptr()
+  p.cu_seqlens_q, p.cache_seqlens, p.seqused = cu_seqlens_q.data_ptr(), cache_seqlens.data_ptr(), seqused.data_ptr()
+  p.kv_cache_stride[:] = list(kv_cache.stride()[-3:-1])
+  p.batch, p.total_q, p.heads_kv, p.head_dim, p.dtype = B, kv_new.size(0), kv_cache.size(2), kv_cache.size(3), _DTYPE[kv_cache.dtype]
+  if kv_new.size(0) > 0:
+    p.kv_new = kv_new.data_ptr()
+    p.kv_new_stride[:] = list(kv_new.stride()[:2])
+  kv, block_table = _paged_kv_of(block_table, kv_cache, kv_cache)
+  rc = _call_on_stream(lib.ffpa_attn_mla_append_varlen, kv_cache.device, ctypes.byref(p), ctypes.byref(kv))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_mla_append_varlen")
+  return seqused
+
+
+# kv_cache is written in place: the schema says so
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_append_varlen_hip",
+  "(Tensor(a!) kv_cache, Tensor kv_new, Tensor cu_seqlens_q, Tensor cache_seqlens, Tensor block_table) -> Tensor seqused",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_append_varlen_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_append_varlen_hip_torch_op(kv_cache, kv_new, cu_seqlens_q, cache_seqlens, block_table):
+  return mla_append_varlen(kv_cache, kv_new, cu_seqlens_q, cache_seqlens, block_table)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_append_varlen_hip")
+def _mla_append_varlen_hip_fake(kv_cache, kv_new, cu_seqlens_q, cache_seqlens, block_table):
+  return kv_cache.new_empty((cu_seqlens_q.size(0) - 1,), dtype=torch.int32)
 
 
 # The KV-cache append + rotary (ffpa_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)): the prepare launch in front of the attention launch

@@ -547,12 +547,14 @@ def ffpa_attn_with_kvcache_mla(
 
   Nothing is read back to the host: the call (append + attention + the split launch's merge) captures into one HIP graph, and a replay follows
   ``cache_seqlens``, ``block_table`` and ``kv`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``.  NOT served here,
-  each raises ``NotImplementedError`` naming the keyword: ``window_size``, ``softcap``, ``tree_mask``, ``cu_seqlens_q`` (ragged batches), shared-prefix cascades,
-  ``rotary_cos`` / ``rotary_sin``, ALiBi, ``cache_batch_idx`` / ``cache_leftpad`` and FP8 latents (a dtype error)."""
+  each raises ``NotImplementedError`` naming the keyword: ``window_size``, ``softcap``, ``tree_mask``, ``cu_seqlens_q`` (ragged batches are
+  ``ffpa_attn_varlen_with_kvcache_mla``'s), shared-prefix cascades, ``rotary_cos`` / ``rotary_sin``, ALiBi, ``cache_batch_idx`` / ``cache_leftpad`` and FP8
+  latents (a dtype error)."""
   name = "ffpa_attn_with_kvcache_mla"
   if unsupported:
-    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no window, soft-cap, tree mask, cascade, ragged cu_seqlens_q, rotary "
-                              "tables, ALiBi, batch index or leftpad over the latent cache: rotate q_pe / k_pe before the call)")
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no window, soft-cap, tree mask, cascade, rotary tables, ALiBi, batch "
+                              "index or leftpad over the latent cache: rotate q_pe / k_pe before the call; a ragged batch — cu_seqlens_q — is "
+                              "ffpa_attn_varlen_with_kvcache_mla's)")
   if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
     raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
                     "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
@@ -828,6 +830,138 @@ def ffpa_attn_varlen_with_kvcache(
   else:
     o, lse = hip.varlen_forward(q, kp, vp, cu_seqlens_q, cu_k, max_seqlen_q, capacity, bool(causal), scale, return_lse=return_softmax_lse, seqused_k=seqused,
                                 num_splits=num_splits)
+  return (o, lse) if return_softmax_lse else o
+
+
+# ---- ragged query batches over the MLA latent cache: ffpa_attn_varlen_with_kvcache_mla
+def ffpa_attn_varlen_with_kvcache_mla(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  cu_seqlens_q: torch.Tensor,
+  max_seqlen_q: int,
+  cache_seqlens: torch.Tensor,
+  block_table: torch.Tensor | None = None,
+  *,
+  kv: torch.Tensor | None = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  causal: bool = False,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """``ffpa_attn_with_kvcache_mla`` for a RAGGED step — the batch of a continuous-batching engine that serves an MLA model: MTP / speculative verification leaves
+  1 - 4 tokens per sequence, a different count after every accept step, and a short extend chunk rides with dozens of one-token decodes.  ``q [T, Hq, D]`` holds
+  every sequence's query tokens packed by ``cu_seqlens_q`` (int32 ``[B + 1]``, on the device, unit stride: sequence b owns rows ``cu_seqlens_q[b] ...
+  cu_seqlens_q[b + 1]``, ``Sq_b`` of them; empty sequences are legal anywhere).  ``max_seqlen_q`` (a host int) is a CONTRACT, as in
+  ``ffpa_attn_varlen_with_kvcache``: every ``Sq_b <= max_seqlen_q``; it is not checked (that would need a host read).  ``cache_seqlens`` (int32 ``[B]``, on the
+  device, required): the latent rows each sequence's cache holds BEFORE this call's append.  ``kv_cache``, ``head_dim_v``, ``block_table``, the ``(D,
+  head_dim_v)`` build list, the required ``softmax_scale`` (``TypeError``) and the contiguous cache (``[B, capacity, Hkv, D]``, ``capacity % 64 == 0``, served as
+  one page per sequence through the identity table) are ``ffpa_attn_with_kvcache_mla``'s — B comes from ``cu_seqlens_q``.
+
+  ``kv [T, Hkv, D]`` (packed by the same ``cu_seqlens_q``: the step's new latent rows are its query tokens): ONE launch in front of the attention launch
+  (``ffpa_attn::_mla_append_varlen_hip``; every token row finds its sequence by a binary search of ``cu_seqlens_q`` on the device) writes row i of sequence b in
+  place at cache position ``max(cache_seqlens[b], 0) + i``, every element once, positions at or past the capacity dropped.  No rotary and no ``positions``:
+  rotate ``q_pe`` / ``k_pe`` before the call.
+
+  Attention for sequence b runs over ``L_b`` keys — ``min(max(cache_seqlens[b], 0) + Sq_b, capacity)`` with ``kv``, else ``cache_seqlens[b]`` clamped to
+  ``[0, capacity]`` — with query token i at ``pos_i = i + L_b - Sq_b`` (bottom-right aligned per sequence) under ``causal``.  The ``Hq / Hkv`` heads x ``Sq_b``
+  tokens of a sequence are the rows of ITS ``ceil(Hq / Hkv * Sq_b / 64)`` tiles; when at least three quarters of the grid that ``max_seqlen_q`` would size find no
+  row, the launch is sized by the rows there are (``ceil(Hq / Hkv * T / 64) + B`` slots per latent head).  Packing and the non-temporal fetch stay launch-wide
+  decisions.  A row that sees no key returns O = 0, LSE = -inf.  ``cache_seqlens`` is not advanced.
+
+  Returns ``out [T, Hq, head_dim_v]`` — and, with ``return_softmax_lse``, the fp32 ``lse [Hq, T]``.  Rows at or past ``cu_seqlens_q[B]`` (padding: T may exceed
+  it) are unspecified, and nothing is appended for them.  ``T == 0`` returns empty tensors and launches nothing.  Nothing is read back to the host: the step
+  (append + attention + the split launch's merge) captures into one HIP graph, and a replay follows ``q``, ``kv``, ``cu_seqlens_q`` (same T, same bound),
+  ``cache_seqlens`` and ``block_table`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``.  NOT served here, each
+  raises ``NotImplementedError`` naming the keyword: ``window_size``, ``softcap``, ``tree_mask``, shared-prefix cascades, ``rotary_cos`` / ``rotary_sin`` /
+  ``positions``, ALiBi, ``cache_batch_idx`` / ``cache_leftpad`` and FP8 latents (a dtype error)."""
+  name = "ffpa_attn_varlen_with_kvcache_mla"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no window, soft-cap, tree mask, cascade, rotary tables or positions, "
+                              "ALiBi, batch index or leftpad over the latent cache: rotate q_pe / k_pe before the call)")
+  if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
+    raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
+                    "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
+  if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
+    raise TypeError(f"{name}: softmax_scale must be a real number, got {softmax_scale!r}")
+  for nm, t in (("q", q), ("kv_cache", kv_cache), ("cu_seqlens_q", cu_seqlens_q), ("cache_seqlens", cache_seqlens)) + ((("kv", kv),) if kv is not None else ()):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+  for nm, t in (("q", q), ("kv_cache", kv_cache)) + ((("kv", kv),) if kv is not None else ()):
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  if q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
+  if q.dim() != 3 or kv_cache.dim() != 4:
+    raise ValueError(f"{name}: q must be packed [T, Hq, D] and kv_cache 4-D")
+  T, Hq, D = q.shape
+  Hkv = kv_cache.size(2)
+  if kv_cache.size(3) != D:
+    raise ValueError(f"{name}: head dim of the cache ({kv_cache.size(3)}) differs from q's ({D})")
+  if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int):
+    raise TypeError(f"{name}: head_dim_v must be an int, got {head_dim_v!r}")
+  if D % 64 != 0 or head_dim_v <= 0 or head_dim_v % 64 != 0 or head_dim_v > D:
+    raise ValueError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}): both must be multiples of 64 with 0 < head_dim_v <= D")
+  from .hip import MLA_BUILDS
+
+  if (D, head_dim_v) not in MLA_BUILDS:
+    raise NotImplementedError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
+  if Hkv == 0 or Hq % Hkv != 0:
+    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of the latent num_heads ({Hkv})")
+  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
+  if kv_cache.device != q.device:
+    raise ValueError(f"{name}: q / kv_cache must be on one device, got {q.device}, {kv_cache.device}")
+  if cu_seqlens_q.dtype != torch.int32:
+    raise TypeError(f"{name}: cu_seqlens_q must be int32, got {cu_seqlens_q.dtype}")
+  if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.stride(0) != 1 or cu_seqlens_q.device != q.device:
+    raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor [batch + 1] of unit stride on q's device, got {tuple(cu_seqlens_q.shape)} on {cu_seqlens_q.device}")
+  B = cu_seqlens_q.numel() - 1
+  if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or (T > 0 and max_seqlen_q < 1):
+    raise ValueError(f"{name}: max_seqlen_q must be a host int >= 1 (>= 0 without a token) that bounds every sequence's tokens, got {max_seqlen_q!r}")
+  if cache_seqlens.dtype != torch.int32:
+    raise TypeError(f"{name}: cache_seqlens must be int32, got {cache_seqlens.dtype}")
+  if cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
+    raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [batch={B}] on q's device, got {tuple(cache_seqlens.shape)} on {cache_seqlens.device}")
+  if block_table is not None:
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B:
+      raise ValueError(f"{name}: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
+    if block_table.size(1) == 0:
+      raise ValueError(f"{name}: block_table needs at least one page per sequence")
+    page_size = kv_cache.size(1)
+    if page_size <= 0 or page_size % 64 != 0:
+      raise ValueError(f"{name}: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
+    if block_table.device != q.device:
+      raise ValueError(f"{name}: block_table must be on q's device, got {block_table.device} and {q.device}")
+    capacity = block_table.size(1) * page_size
+  else:
+    if kv_cache.size(0) != B:
+      raise ValueError(f"{name}: kv_cache [B, capacity, Hkv, D] must have cu_seqlens_q's batch ({B}), got {kv_cache.size(0)}")
+    capacity = kv_cache.size(1)
+    if capacity <= 0 or capacity % 64 != 0:
+      raise ValueError(f"{name}: a contiguous cache runs as a pool of one page per sequence: its capacity ({capacity}) must be a positive multiple of 64")
+  if kv is not None:
+    if kv.dtype != q.dtype:
+      raise TypeError(f"{name}: kv must have the cache's dtype {q.dtype}, got {kv.dtype}")
+    if kv.device != q.device:
+      raise ValueError(f"{name}: kv must be on q's device, got {kv.device} and {q.device}")
+    if kv.dim() != 3 or kv.size(0) != T or kv.size(1) != Hkv or kv.size(2) != D:
+      raise ValueError(f"{name}: kv must be [T={T}, Hkv={Hkv}, D={D}] (packed by cu_seqlens_q like q), got {tuple(kv.shape)}")
+    if kv.stride(-1) != 1:
+      raise ValueError(f"{name}: kv must have a contiguous last dimension")
+  from . import hip  # (registers the ffpa_attn ops)
+
+  if T == 0:
+    out = q.new_empty((0, Hq, head_dim_v))
+    return (out, torch.empty((Hq, 0), dtype=torch.float32, device=q.device)) if return_softmax_lse else out
+  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
+  seqused = cache_seqlens
+  if kv is not None:
+    # the prepare launch: the step's latent rows into the cache (in place) and the post-append lengths — read by the attention launch below on the same stream
+    seqused = torch.ops.ffpa_attn._mla_append_varlen_hip(kv_cache, kv, cu_seqlens_q, cache_seqlens, table)
+  o, lse = torch.ops.ffpa_attn._mla_fwd_hip(q, kv_cache, head_dim_v, cu_seqlens_q, seqused, table, None, None, max_seqlen_q, capacity, float(softmax_scale),
+                                            1 if causal else 0, num_splits)
   return (o, lse) if return_softmax_lse else o
 
 

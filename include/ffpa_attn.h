@@ -443,7 +443,13 @@ int ffpa_attn_varlen_softcap_fwd_kernel(const ffpa_varlen_fwd_params* p, const f
  * at cache position max(cache_seqlens[b], 0) + i (dropped at or past pages_per_row * page_size), by one more launch on `stream` in front of the attention
  * launch, which also writes p->seqused_kv[b] = min(max(cache_seqlens[b], 0) + seqlen_new, capacity): p->seqused_kv is then an OUTPUT (and the lengths attention
  * runs over) and must not be cache_seqlens.  No rotary: these models rotate k_pe / q_pe before the concatenation.
- * Not served (use the other calls on a (kv, kv) pair): windows, soft-capping, tree masks, ragged positions, FP8 latents.
+ * RAGGED STEPS (sequences with different numbers of query tokens: MTP / speculative verification, an extend chunk among decodes): p->cu_seqlens_q says them, as
+ * in the packed call, and a sequence of len_b tokens has ceil(group * len_b / block rows) row tiles.  The step's append is ffpa_attn_mla_append_varlen (below) in
+ * front of this call with seqlen_new = 0 and p->seqused_kv = that call's `seqused`, on one stream.  When at least three quarters of the full grid of
+ * batch * ceil(group * max_seqlen_q / block rows) row tiles per KV head would find no row, the grid is sized by the rows there are:
+ * ceil(group * total_q / block rows) + batch slots per KV head (an upper bound of the sum of the sequences' tiles), each finding its (sequence, row tile) on the
+ * device; FFPA_FLAG_NO_COMPACT_GRID keeps the full grid (same order, same bits).  Packing and the non-temporal fetch stay launch-wide decisions.
+ * Not served (use the other calls on a (kv, kv) pair): windows, soft-capping, tree masks, FP8 latents.
  */
 typedef struct ffpa_mla {
   uint32_t struct_size;          /* sizeof(ffpa_mla), checked */
@@ -465,6 +471,47 @@ int ffpa_attn_varlen_mla_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_k
 size_t ffpa_attn_varlen_mla_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m);
 int ffpa_attn_varlen_mla_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int out[5]);
 int ffpa_attn_varlen_mla_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, char* buf, size_t n);
+
+/* *slots = row-tile slots per KV head of the compact grid the plan takes for this call (out[3] of the plan is then slots * heads_kv * KV ranges, and the kernel
+ * text carries "(compact grid)"); 0 = the full grid.  Returns an ffpa_status. */
+int ffpa_attn_varlen_mla_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int* slots);
+
+/*
+ * LATENT APPEND OF A RAGGED STEP — the launch in front of ffpa_attn_varlen_mla_fwd when the sequences of a step bring different numbers of new latent rows.
+ * kv_new [total_q, heads_kv, head_dim] by kv_new_stride = {row, head} is packed by cu_seqlens_q (device int32 [batch + 1], ascending from 0) exactly as the
+ * step's q: token row t belongs to the sequence b with cu_seqlens_q[b] <= t < cu_seqlens_q[b + 1], found on the device, as its token i = t - cu_seqlens_q[b].
+ * ONE kernel on `stream`:
+ *   * row t is written — once, as 16-byte chunks — at cache position pos = max(cache_seqlens[b], 0) + i of the latent pool kv_cache: row pos % page_size of page
+ *     kv->block_table[b * bt_stride + pos / page_size] (ids clamped to [0, num_pages); pages by kv->k_page_stride, rows and heads inside a page by
+ *     kv_cache_stride = {row, head}; kv->v_page_stride is not read).  A position at or past pages_per_row * page_size is dropped.  Rows from
+ *     cu_seqlens_q[batch] on (total_q may exceed it) are padding: nothing is written for them.
+ *   * seqused[b] = min(max(cache_seqlens[b], 0) + (cu_seqlens_q[b + 1] - cu_seqlens_q[b]), capacity) for every b < batch — sequences without a token too, and
+ *     with total_q < batch or total_q == 0 as well: the lengths the attention launch that follows reads (its seqused_kv).  cache_seqlens is not modified;
+ *     seqused must be another buffer.
+ * No rotary and no positions: MLA rotates k_pe / q_pe before the concatenation.  A contiguous cache is a pool of one page per sequence, as in the forward call.
+ */
+typedef struct ffpa_mla_append_varlen_params {
+  uint32_t struct_size;          /* sizeof(ffpa_mla_append_varlen_params), checked */
+  uint32_t reserved;             /* 0, checked */
+  const void* kv_new;            /* device [total_q, heads_kv, head_dim], 16-byte aligned; may be NULL when total_q == 0 */
+  void* kv_cache;                /* the latent pool, written in place; 16-byte aligned */
+  const int32_t* cu_seqlens_q;   /* device [batch + 1] */
+  const int32_t* cache_seqlens;  /* device [batch]: the lengths before the step, not modified */
+  int32_t* seqused;              /* out, device [batch] */
+  int64_t kv_new_stride[2];      /* elements: row, head (head-dim stride 1; multiples of 8) */
+  int64_t kv_cache_stride[2];    /* elements: row, head inside a page */
+  int32_t batch;
+  int32_t total_q;               /* >= 0: token rows of kv_new (the grid); 0 = only seqused is written */
+  int32_t heads_kv;
+  int32_t head_dim;              /* a multiple of 8 in [8, 1024] */
+  int32_t dtype;                 /* enum ffpa_dtype (16-bit elements move as raw bytes) */
+  int32_t reserved2;             /* 0, checked */
+} ffpa_mla_append_varlen_params;
+
+/* Launch the ragged latent append on `stream` of the CURRENT device.  Asynchronous: no allocation, no synchronisation; every bad argument — a NULL params, kv or
+ * pointer, a wrong struct_size, a non-zero reserved, a misaligned base, seqused == cache_seqlens, head_dim % 8, a page_size that is no multiple of 64 — returns a
+ * status before any device work.  Returns an ffpa_status. */
+int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, void* stream);
 
 /*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
