@@ -70,6 +70,8 @@ def _units() -> list[Unit]:
   # the MLA latent-cache kernels (and their one-cache append): one TU per (head dim, value width) pair of MLA_BUILDS — adding a pair is one entry there and one
   # line in FFPA_FOR_EACH_MLA_BUILD (csrc/ffpa_mla.h); the assembly lands next to the head dim's other kernels, where the ISA rules read it
   units += [Unit("ffpa_mla_inst.hip", f"ffpa_mla_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
+  # the sparse (top-k indexed) build of the latent kernel: the same text with the gather hook on, one TU per pair of MLA_BUILDS next to the dense one's
+  units += [Unit("ffpa_mla_sparse_inst.hip", f"ffpa_mla_sparse_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
   # the KV-cache append + rotary launch (every dtype / rotary form) and the merge of two attention states (the cascade's last launch): one small TU each, no
   # inline asm — their assembly lands in directories the attention ISA rules do not read
   units.append(Unit("ffpa_kvcache_append.hip", "ffpa_kvcache_append.o", [], "temps_append", None, True, True))

@@ -22,6 +22,7 @@
 #include "ffpa_launch.h"
 #include "ffpa_paged.h"         // (the paged-KV twin of the packed-sequence kernel)
 #include "ffpa_mla.h"           // (the MLA latent-cache kernels and their append)
+#include "ffpa_mla_sparse.h"    // (the sparse — top-k indexed — build of the latent kernel)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
 #include "ffpa_merge_states.h"    // (the merge of two attention states)
 
@@ -1253,21 +1254,87 @@ int mla_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffp
   return check_mla(p, m, build);
 }
 
+// The sparse latent call (ffpa_attn_varlen_mla_sparse_fwd): its own argument, checked before anything touches the device, and what the launch is made from.
+const MlaEntry kMlaSparseBuilds[] = {
+#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_sparse_d##D},
+    FFPA_FOR_EACH_MLA_BUILD(FFPA_ROW)
+#undef FFPA_ROW
+};
+
+struct SparsePlan {
+  ffpa_varlen_fwd_params priced;  // the caller's params as the latent launch reads them: T one-token sequences of topk keys, the pool's strides, the counts as lengths
+  ffpa_mla mla;                   // (head_dim_v; nothing is appended)
+  const ffpa_mla_sparse* s;
+  const MlaEntry* build;
+};
+
+// The reach of the kernel's addressing: every lane offset is 32 bits from the head's first row and bit 31 (kDmaOob) is the "no row" sentinel, so the rows of a
+// head span at most 2^31 bytes.
+constexpr int64_t kSparseSpanBytes = 1LL << 31;
+
+// The sparse call's plan: the latent call's for a batch of T one-token sequences of topk keys ("fill the chip, then balance", the one-reader rule of the NT build,
+// the row chunks of a group wider than the tile; a uniform batch never meets the compact grid).
+int mla_sparse_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, VarlenPlan* pl, SparsePlan* sp) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (s == nullptr) return fail(FFPA_ERR_NULL_POINTER, "mla_sparse is NULL");
+  if (s->struct_size != sizeof(ffpa_mla_sparse))
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_sparse ABI mismatch: size %u (want %zu)", s->struct_size, sizeof(ffpa_mla_sparse));
+  if (s->reserved != 0 || s->reserved2 != 0) return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_sparse.reserved=%u / reserved2=%d must be 0", s->reserved, s->reserved2);
+  if (p->struct_size != sizeof(ffpa_varlen_fwd_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_varlen_fwd_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size,
+                sizeof(ffpa_varlen_fwd_params), p->abi_version, FFPA_ATTN_ABI_VERSION);
+  if (p->max_seqlen_q != 1) return fail(FFPA_ERR_BAD_SHAPE, "max_seqlen_q=%d: the sparse call takes one query token per index row (max_seqlen_q = 1)", p->max_seqlen_q);
+  if (s->topk < 1 || s->num_rows < 1) return fail(FFPA_ERR_BAD_SHAPE, "topk=%d / num_rows=%d must be positive", s->topk, s->num_rows);
+  if (s->indices == nullptr) return fail(FFPA_ERR_NULL_POINTER, "indices must be non-NULL");
+  if ((reinterpret_cast<uintptr_t>(s->indices) & 3u) || (reinterpret_cast<uintptr_t>(s->topk_lens) & 3u))
+    return fail(FFPA_ERR_MISALIGNED, "indices / topk_lens must be 4-byte aligned");
+  if (s->indices_stride < s->topk) return fail(FFPA_ERR_BAD_STRIDE, "indices_stride=%lld is smaller than topk=%d", (long long)s->indices_stride, s->topk);
+  sp->s = s;
+  sp->priced = *p;
+  sp->priced.causal = 0;  // (the indexer has chosen visible keys)
+  sp->priced.max_seqlen_kv = s->topk;
+  sp->priced.k_stride[0] = s->kv_stride[0], sp->priced.k_stride[1] = s->kv_stride[1];
+  sp->priced.seqused_kv = s->topk_lens;
+  memset(&sp->mla, 0, sizeof(sp->mla));
+  sp->mla.struct_size = (uint32_t)sizeof(ffpa_mla);
+  sp->mla.head_dim_v = s->head_dim_v;
+  int rc = varlen_plan(&sp->priced, pl, true, true);
+  if (rc != FFPA_OK) return rc;
+  const MlaEntry* dense = nullptr;
+  if ((rc = check_mla(&sp->priced, &sp->mla, &dense)) != FFPA_OK) return rc;
+  sp->build = &kMlaSparseBuilds[dense - kMlaBuilds];
+  if ((rc = check_strides("kv", s->kv_stride, 2)) != FFPA_OK) return rc;
+  if (s->kv_stride[0] < p->head_dim || s->kv_stride[0] >= (1LL << 24))
+    return fail(FFPA_ERR_BAD_STRIDE, "kv row stride %lld: rows must not overlap and must be < 2^24 elements apart", (long long)s->kv_stride[0]);
+  const int64_t span = ((int64_t)s->num_rows - 1) * s->kv_stride[0] * 2 + (int64_t)p->head_dim * 2;
+  if (span > kSparseSpanBytes)
+    return fail(FFPA_ERR_BAD_SHAPE, "the pool's rows span %lld bytes per head: the sparse call reaches at most 2^31 = %lld ((num_rows - 1) * row stride * 2 + head_dim * 2)",
+                (long long)span, (long long)kSparseSpanBytes);
+  return FFPA_OK;
+}
+
 // The packed call and its paged twin (kv != NULL: k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read); `tree`: under a tree mask
 // (ffpa_attn_varlen_tree_fwd — the causal launch's plan and tile walk; the *_tree_kernel builds, whose element test reads the mask words); `win`: under a sliding
 // window (ffpa_attn_varlen_window_fwd — the window's own plan; the *_window_kernel builds); `softcap` > 0: a window launch with capped scores
 // (ffpa_attn_varlen_softcap_fwd — the same plan; the *_softcap_kernel builds)
 int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream, const ffpa_tree_mask* tree = nullptr, bool with_tree = false,
-                  const ffpa_window* win = nullptr, bool with_win = false, float softcap = 0.f, const ffpa_mla* mla = nullptr, bool with_mla = false) {
+                  const ffpa_window* win = nullptr, bool with_win = false, float softcap = 0.f, const ffpa_mla* mla = nullptr, bool with_mla = false,
+                  const ffpa_mla_sparse* sparse = nullptr, bool with_sparse = false) {
   // (`mla`: the latent-cache call, ffpa_attn_varlen_mla_fwd — k is the latent pool and serves as v too, p->v is not read; its own plan and kernel; the append in front)
-  const bool paged = kv != nullptr;
+  // (`sparse`: the sparse latent call, ffpa_attn_varlen_mla_sparse_fwd — a latent launch without a page pool: the index list stands where the block table stood)
+  const bool paged = kv != nullptr || with_sparse;
   VarlenPlan pl;
   WindowPlan wp;
+  SparsePlan sp;
   const MlaEntry* mb = nullptr;
-  int rc = with_mla ? mla_plan(p, kv, mla, &pl, &mb) : with_win ? window_plan(p, kv, win, &pl, &wp) : varlen_plan(p, &pl, paged);
+  int rc = with_sparse ? mla_sparse_plan(p, sparse, &pl, &sp)
+           : with_mla  ? mla_plan(p, kv, mla, &pl, &mb)
+           : with_win  ? window_plan(p, kv, win, &pl, &wp)
+                       : varlen_plan(p, &pl, paged);
   if (rc != FFPA_OK) return rc;
   if (with_win) p = &wp.priced;  // (the caller's params but for the causal flag and the length the plan saw; the kernel reads every sequence's own length)
-  if (paged && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
+  if (with_sparse) p = &sp.priced, mla = &sp.mla, mb = sp.build, with_mla = true;
+  if (paged && !with_sparse && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
   if (with_tree && (rc = check_tree(p, tree)) != FFPA_OK) return rc;
   if (!p->q || !p->k || (!with_mla && !p->v) || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
   if (!p->cu_seqlens_q || (!paged && !p->cu_seqlens_kv)) return fail(FFPA_ERR_NULL_POINTER, "cu_seqlens_q / cu_seqlens_kv must be non-NULL");
@@ -1378,14 +1445,24 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
   int st;
   if (paged) {
     ffpa::PagedArgs pa;
-    pa.table = kv->block_table;
-    pa.bt_stride = kv->bt_stride;
-    pa.k_page_stride = kv->k_page_stride;
-    pa.v_page_stride = with_mla ? kv->k_page_stride : kv->v_page_stride;
-    pa.cap = kv->pages_per_row * kv->page_size;
-    pa.page_size = kv->page_size;
-    pa.tiles_per_page = kv->page_size / pl.bc;
-    pa.num_pages = kv->num_pages;
+    if (with_sparse) {
+      // a token's "block table" is its index row, its "pages" are single rows of the pool (ffpa_mla_sparse.h)
+      memset(&pa, 0, sizeof(pa));
+      pa.table = sparse->indices;
+      pa.bt_stride = sparse->indices_stride;
+      pa.cap = sparse->topk;
+      pa.page_size = 1;
+      pa.num_pages = sparse->num_rows;
+    } else {
+      pa.table = kv->block_table;
+      pa.bt_stride = kv->bt_stride;
+      pa.k_page_stride = kv->k_page_stride;
+      pa.v_page_stride = with_mla ? kv->k_page_stride : kv->v_page_stride;
+      pa.cap = kv->pages_per_row * kv->page_size;
+      pa.page_size = kv->page_size;
+      pa.tiles_per_page = kv->page_size / pl.bc;
+      pa.num_pages = kv->num_pages;
+    }
     if (with_mla) {
       st = 0;
       if (mla->seqlen_new > 0) {
@@ -1634,6 +1711,40 @@ int ffpa_attn_varlen_mla_fwd_compact_slots(const ffpa_varlen_fwd_params* p, cons
   if (rc != FFPA_OK) return rc;
   if (slots == nullptr) return fail(FFPA_ERR_NULL_POINTER, "slots is NULL");
   *slots = pl.compact;
+  return FFPA_OK;
+}
+
+// ---- the sparse latent call (include/ffpa_attn.h: ffpa_mla_sparse): the latent launch over per-token index lists
+int ffpa_attn_varlen_mla_sparse_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream) {
+  return varlen_launch(p, nullptr, stream, nullptr, false, nullptr, false, 0.f, nullptr, false, s, true);
+}
+
+size_t ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
+  if (p == nullptr || p->struct_size != sizeof(ffpa_varlen_fwd_params) || s == nullptr || s->struct_size != sizeof(ffpa_mla_sparse)) return 0;
+  // size for the split count the heuristic would pick with unlimited scratch
+  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*p);
+  VarlenPlan pl;
+  SparsePlan sp;
+  if (mla_sparse_plan(&q, s, &pl, &sp) != FFPA_OK) return 0;
+  return pl.ws_bytes;
+}
+
+int ffpa_attn_varlen_mla_sparse_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]) {
+  VarlenPlan pl;
+  SparsePlan sp;
+  const int rc = mla_sparse_plan(p, s, &pl, &sp);
+  if (rc != FFPA_OK) return rc;
+  return plan_out(pl, out);
+}
+
+int ffpa_attn_varlen_mla_sparse_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n) {
+  VarlenPlan pl;
+  SparsePlan sp;
+  const int rc = mla_sparse_plan(p, s, &pl, &sp);
+  if (rc != FFPA_OK) return rc;
+  if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
+  snprintf(buf, n, "ffpa_fwd_m16_mla_sparse_kernel<%s, %d, dv=%d%s>%s%s", p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", p->head_dim, s->head_dim_v, pl.nt ? ", NT" : "",
+           pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "", pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
   return FFPA_OK;
 }
 

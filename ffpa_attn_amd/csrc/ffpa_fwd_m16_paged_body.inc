@@ -8,9 +8,76 @@
 #define FFPA_M16_MFMA std::conditional_t<NT, Mfma16Nt<T>, Mfma16<T>>
 #define FFPA_M16_DMA16 LdsDma16<NT>::template at
 #define FFPA_M16_PAGED 1
+#ifndef FFPA_M16_KV_GATHER  // (1: the keys of a tile are rows picked by an index list — ffpa_mla_sparse_inst.hip; see below)
+#define FFPA_M16_KV_GATHER 0
+#define FFPA_M16_PAGED_GATHER_DEFAULT
+#endif
 #include "ffpa_fwd_m16_head.inc"
 #include "ffpa_fwd_m16_varlen_seq.inc"
   static_assert(BC == m16_block_keys(D, true), "the paged build's tile: 64 keys (32 at D > 512)");
+#if FFPA_M16_KV_GATHER
+  // ---- GATHERED KEYS (ffpa_mla_sparse_inst.hip): "sequence" seq is ONE query token, its block table is its row of the index list (pa.table, pa.bt_stride; pa.cap
+  // = topk entries) and its page size is one row: key n of the token is pool row idx[n], clamped to [0, pa.num_pages).  There is no page-table state.  The pieces
+  // of wave w cover exactly the keys 8 w .. 8 w + 7 of a tile (PPW pieces x 64 slots = 8 rows of D / 8 slots), so the wave keeps EIGHT wave-uniform row ids per
+  // tile, read with scalar loads where the page ids are read in the other builds — the ids of tile j + 2 in front of barrier B of step j, waited for at the top of
+  // step j + 1, where they turn into the PPW per-lane source offsets of that tile (krel[], which the pieces riding on QK^T(j + 1) read) and die:
+  //     krel[i] = row id of the lane's key x row bytes + the lane's swizzled slot (g_sl[i], tile-invariant, the V map),
+  // a piece spans at most two rows with a compile-time boundary lane.  A key at or past the token's count (a.Nkv) gets bit 31 — kDmaOob — instead of a row offset:
+  // the descriptor spans the whole pool, at most 2^31 bytes (the launch side refuses larger ones), so such a lane is out of range, reads zeros and forms no address
+  // whatever its entry holds.  Entries are read at min(n, pa.cap - 1): no read leaves the token's row of the list.
+  constexpr int kGSpr = D / 8;  // 16-byte slots per row
+  static_assert(FFPA_M16_MLA_ON && PPW * 64 == 8 * kGSpr, "gathered keys: a wave's pieces of a tile are whole rows, eight of them");
+  using cint_ptr = __attribute__((address_space(4))) const int*;  // (constant address space: a uniform load is a scalar load)
+  const cint_ptr g_idx = (cint_ptr)(pa.table + (int64_t)seq * pa.bt_stride);
+  const uint32_t g_span = (uint32_t)(pa.num_pages - 1) * ((uint32_t)a.sk[2] * 2u) + (uint32_t)(D * 2);  // bytes of a head's rows in the pool (<= 2^31: the launch side)
+  int g_id[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the loaded row ids: this wave's keys of the tile whose offsets are formed next
+  int g_next = 0;                          // first key of the tile whose ids are loaded next
+  uint32_t g_sl[PPW];
+#pragma unroll
+  for (int i = 0; i < PPW; ++i) {
+    const int g = (wave * PPW + i) * 64 + lane;
+    const int key = g / kGSpr;
+    g_sl[i] = (uint32_t)(((g - key * kGSpr) ^ m16_v_swizzle<D>(key)) << 4);
+  }
+// (macros, not lambdas: they name krel[] and k_row_bytes of the tile text, and a lambda here would renumber the tile text's)
+#define FFPA_M16_GATHER_LOAD(key0_)                                        \
+  _Pragma("unroll") for (int gk_ = 0; gk_ < 8; ++gk_) {                    \
+    const int ge_ = (key0_) + 8 * wave + gk_;                              \
+    g_id[gk_] = g_idx[ge_ < pa.cap - 1 ? ge_ : pa.cap - 1];                \
+  }
+#define FFPA_M16_GATHER_FORM(key0_)                                                                        \
+  {                                                                                                        \
+    uint32_t g_ro_[8];                                                                                     \
+    int g_left_ = a.Nkv - ((key0_) + 8 * wave); /* valid keys among the wave's eight */                    \
+    _Pragma("unroll") for (int gk_ = 0; gk_ < 8; ++gk_) {                                                  \
+      int id_ = g_id[gk_];                                                                                 \
+      id_ = id_ > 0 ? id_ : 0;                                                                             \
+      id_ = id_ < pa.num_pages - 1 ? id_ : pa.num_pages - 1;                                               \
+      int oob_ = gk_ + 1 - g_left_; /* > 0: the key lies at or past the count */                           \
+      oob_ = oob_ > 0 ? oob_ : 0;                                                                          \
+      oob_ = oob_ < 1 ? oob_ : 1;                                                                          \
+      g_ro_[gk_] = ((uint32_t)id_ * k_row_bytes) | ((uint32_t)oob_ << 31);                                 \
+    }                                                                                                      \
+    _Pragma("unroll") for (int gi_ = 0; gi_ < PPW; ++gi_) {                                                \
+      const int lo_ = gi_ * 64 / kGSpr, hi_ = (gi_ * 64 + 63) / kGSpr;                                     \
+      krel[gi_] = g_sl[gi_] + (lane < hi_ * kGSpr - gi_ * 64 ? g_ro_[lo_] : g_ro_[hi_]);                   \
+    }                                                                                                      \
+  }
+#define FFPA_M16_KV_BEGIN(t0_)                               \
+  if (nt > (t0_)) {                                          \
+    FFPA_M16_GATHER_LOAD((t0_) * BC)                         \
+    FFPA_M16_GATHER_FORM((t0_) * BC)                         \
+    FFPA_M16_GATHER_LOAD((t0_) * BC + BC)                    \
+    g_next = (t0_) * BC + 2 * BC;                            \
+  }
+#define FFPA_M16_KV_STEP(k0_)                                \
+  __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0) */       \
+  FFPA_M16_GATHER_FORM((k0_) + BC)
+#define FFPA_M16_KV_STEP_END()                               \
+  FFPA_M16_GATHER_LOAD(g_next)                               \
+  g_next += BC;
+#define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) gather_src((slice), g_span)
+#else
   // ---- page-table state (all wave-uniform, scalar)
   using cint_ptr = __attribute__((address_space(4))) const int*;  // (constant address space: a uniform load is a scalar load)
   const cint_ptr tbl = (cint_ptr)(pa.table + (int64_t)seq * pa.bt_stride);
@@ -61,6 +128,7 @@
 #define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0)                                                                                    \
   tile_src_at<BC>((const char*)(slice) + pg_off((key0), (kind) == 0 ? k_ps : (kind) == 1 ? v_ps : pf_ps, (row_bytes)), (row_bytes), (key0), \
                   a.Nkv, rb_valid)
+#endif
 #define FFPA_M16_TILE_DONE return
 #define FFPA_M16_ROW_INV(l) ((l) > 0.f ? __builtin_amdgcn_rcpf(l) : 0.f)
 #define FFPA_M16_ROW_OUT(x, rh) (l_tot[rh] > 0.f ? (T)((x) * inv[rh]) : (T)0.f)
@@ -89,6 +157,14 @@
 #undef FFPA_M16_ROW_INV
 #undef FFPA_M16_TILE_DONE
 #undef FFPA_M16_KV_SRC
+#if FFPA_M16_KV_GATHER
+#undef FFPA_M16_GATHER_FORM
+#undef FFPA_M16_GATHER_LOAD
+#endif
+#ifdef FFPA_M16_PAGED_GATHER_DEFAULT
+#undef FFPA_M16_PAGED_GATHER_DEFAULT
+#undef FFPA_M16_KV_GATHER
+#endif
 #undef FFPA_M16_KV_STEP_END
 #undef FFPA_M16_KV_STEP
 #undef FFPA_M16_KV_BEGIN

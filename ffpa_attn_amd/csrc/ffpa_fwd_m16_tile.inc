@@ -55,6 +55,14 @@
 #define FFPA_M16_O_COLS a.d_valid
 #define FFPA_M16_MLA_DEFAULT_HOOKS
 #endif
+// GATHERED KEYS are the enclosing kernel's too (ffpa_mla_sparse_inst.hip): FFPA_M16_KV_GATHER = a constant of its build — the keys of a tile are rows picked by an
+// index list, one descriptor over the whole pool serves every tile and the hooks below rewrite krel[] per tile (row id x row bytes + the swizzled slot).  The tile
+// text itself reads the constant in ONE place: such a build has no contiguous tile two steps ahead, so its L2 touch is off (pf_on).  Kernels that do not define
+// it gather nothing: the text that stood here.
+#ifndef FFPA_M16_KV_GATHER
+#define FFPA_M16_KV_GATHER false
+#define FFPA_M16_KV_GATHER_DEFAULT_HOOKS
+#endif
 #ifndef FFPA_M16_KV_SRC
 #define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) tile_src<BC>(slice, row_bytes, key0, a.Nkv, rb_valid)
 #define FFPA_M16_KV_BEGIN(t0_)
@@ -184,7 +192,7 @@
   // (built into the split-D tiles only: at D <= 512 a DMA piece has a whole step to land, the touches cost 1 ... 2 %, and the dropout +
   // bias builds there have no register to spare)
   constexpr bool kPf = ND == 2;
-  const bool pf_on = kPf && a.l2_prefetch != 0 && wave < FFPA_M16_PF_WAVES && ((FFPA_M16_PF_WHICH >> (wave & 1)) & 1) && !(FFPA_M16_MLA_ON && (wave & 1));  // (MLA: there is no V stream to touch)
+  const bool pf_on = kPf && a.l2_prefetch != 0 && wave < FFPA_M16_PF_WAVES && ((FFPA_M16_PF_WHICH >> (wave & 1)) & 1) && !(FFPA_M16_MLA_ON && (wave & 1)) && !FFPA_M16_KV_GATHER;  // (MLA: there is no V stream to touch; gathered keys: no contiguous tile to touch)
   const bool pf_k = (wave & 1) == 0;  // even waves touch K, odd waves V
   uint32_t pf_off = kDmaOob;
   uint32_t pf_junk = 0u;  // (the loads' destination: never read, but live through the loop so that nothing else is allocated to it)
@@ -1458,4 +1466,8 @@
 #undef FFPA_M16_KV_STEP
 #undef FFPA_M16_KV_BEGIN
 #undef FFPA_M16_KV_SRC
+#endif
+#ifdef FFPA_M16_KV_GATHER_DEFAULT_HOOKS
+#undef FFPA_M16_KV_GATHER_DEFAULT_HOOKS
+#undef FFPA_M16_KV_GATHER
 #endif

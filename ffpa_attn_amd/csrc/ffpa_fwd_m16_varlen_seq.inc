@@ -97,7 +97,13 @@
 #else
     // (paged: the lengths are seqused_k's, clamped to what the sequence's row of the block table can hold; no contiguous key range)
     const int ntok_seq = va.cu_q[seq + 1] - q_lo;
+#if FFPA_M16_KV_GATHER
+    // (gathered keys, ffpa_mla_sparse_inst.hip: the token's count of valid entries; no counts = every entry of its row; a preprocessor test, so that every other
+    // kernel's text is what it was)
+    int nkv_seq = va.used_k != nullptr ? va.used_k[seq] : pa.cap;
+#else
     int nkv_seq = va.used_k[seq];
+#endif
     nkv_seq = nkv_seq < pa.cap ? nkv_seq : pa.cap;
 #endif
     ntok = ntok_seq > 0 ? ntok_seq : 1;

@@ -213,6 +213,23 @@ class FfpaMla(ctypes.Structure):
   ]
 
 
+class FfpaMlaSparse(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_mla_sparse`` (include/ffpa_attn.h): the index list, its counts and the latent pool's geometry of the sparse latent call."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("indices", ctypes.c_void_p),
+    ("indices_stride", ctypes.c_int64),
+    ("topk_lens", ctypes.c_void_p),
+    ("kv_stride", ctypes.c_int64 * 2),
+    ("topk", ctypes.c_int32),
+    ("num_rows", ctypes.c_int32),
+    ("head_dim_v", ctypes.c_int32),
+    ("reserved2", ctypes.c_int32),
+  ]
+
+
 class FfpaMlaAppendVarlenParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_mla_append_varlen_params`` (include/ffpa_attn.h): the latent append of a ragged step."""
 
@@ -347,6 +364,7 @@ _TREE = _PAGED + [_P(FfpaTreeMask)]
 _WINDOW = _PAGED + [_P(FfpaWindow)]
 _SOFTCAP = _WINDOW + [ctypes.c_float]
 _MLA = _PAGED + [_P(FfpaMla)]
+_MLA_SPARSE = [_P(FfpaVarlenFwdParams), _P(FfpaMlaSparse)]
 # Every function include/ffpa_attn.h declares: (symbol, argtypes, restype, since).  ``since``: the ABI version that added it (0: there from the start) — the
 # default library has them all; one loaded by path or through FFPA_HIP_LIBRARY (developer A/B runs load a saved build of an older commit) may lack those with
 # since > 0: calling one of those is then an AttributeError.
@@ -383,6 +401,10 @@ _BINDINGS = (
   ("ffpa_attn_varlen_mla_fwd_workspace_bytes", _MLA, _SIZE, 7),
   ("ffpa_attn_varlen_mla_fwd_compact_slots", _MLA + [_P(_INT)], _INT, 7),
   ("ffpa_attn_mla_append_varlen", [_P(FfpaMlaAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fwd", _MLA_SPARSE + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fwd_plan", _MLA_SPARSE + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fwd_kernel", _MLA_SPARSE + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes", _MLA_SPARSE, _SIZE, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
@@ -477,7 +499,7 @@ def _stamped(cls):
   """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` / ``ffpa_window`` / ``ffpa_mla`` ride next to a versioned struct), the ABI version — filled in."""
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
-  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams):
+  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse):
     p.abi_version = ABI_VERSION
   return p
 
@@ -1605,6 +1627,148 @@ def _mla_fwd_hip_torch_op(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, bloc
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_fwd_hip")
 def _mla_fwd_hip_fake(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k, softmax_scale, causal,
                       num_splits=0):
+  total_q, heads, _ = q.shape
+  return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
+
+
+# The sparse latent call (ffpa_attn_with_kvcache_mla_sparse): every query token attends to the latent rows its index list names
+MLA_SPARSE_SPAN_BYTES = 1 << 31  # what the kernel's 32-bit lane offsets reach: a head's rows of the pool span at most this many bytes (bit 31 = "no row")
+_MLA_SPARSE_IDENTITY: "dict[tuple, torch.Tensor]" = {}
+
+
+def mla_sparse_pool(kv_cache: torch.Tensor, name: str = "ffpa_attn::_mla_sparse_fwd_hip") -> "tuple[int, int, int]":
+  """``(num_rows, row stride, head stride)`` — elements — of a latent pool as the sparse call addresses it: the flat ``[num_rows, Hkv, D]``, or a page pool
+  ``[num_pages, page_size, Hkv, D]`` of any positive ``page_size`` whose pages are evenly spaced (slot r = row ``r % page_size`` of page ``r // page_size`` then
+  lies ``r`` row strides from the base).  ``ValueError``: pages that are not evenly spaced, and a pool whose rows span more than ``MLA_SPARSE_SPAN_BYTES`` —
+  from sizes and strides alone, so in front of any launch and without touching the pool's memory."""
+  if kv_cache.dim() == 4:
+    pages, page_size = kv_cache.size(0), kv_cache.size(1)
+    if page_size <= 0:
+      raise ValueError(f"{name}: page_size ({page_size}) must be positive")
+    if pages > 1 and page_size > 1 and kv_cache.stride(0) != page_size * kv_cache.stride(1):
+      raise ValueError(f"{name}: the pages of kv_cache must be evenly spaced — stride(0) == page_size * stride(1), got {kv_cache.stride(0)} and "
+                       f"{page_size} * {kv_cache.stride(1)}: slot r must lie r rows from the pool's base")
+    num_rows, row_stride, head_stride = pages * page_size, kv_cache.stride(1) if page_size > 1 else kv_cache.stride(0), kv_cache.stride(2)
+  elif kv_cache.dim() == 3:
+    num_rows, row_stride, head_stride = kv_cache.size(0), kv_cache.stride(0), kv_cache.stride(1)
+  else:
+    raise ValueError(f"{name}: kv_cache must be the flat pool [num_rows, Hkv, D] or a page pool [num_pages, page_size, Hkv, D], got {kv_cache.dim()}-D")
+  if num_rows > 0x7fffffff:
+    raise ValueError(f"{name}: a pool of {num_rows} rows is too large (slots are int32)")
+  span = (num_rows - 1) * row_stride * kv_cache.element_size() + kv_cache.size(-1) * kv_cache.element_size() if num_rows > 0 else 0
+  if span > MLA_SPARSE_SPAN_BYTES:
+    raise ValueError(f"{name}: the pool's rows span {span} bytes per latent head ((num_rows - 1) * row stride + one row = ({num_rows} - 1) * "
+                     f"{row_stride * kv_cache.element_size()} + {kv_cache.size(-1) * kv_cache.element_size()}); the sparse call's 32-bit offsets reach at most "
+                     f"2^31 = {MLA_SPARSE_SPAN_BYTES} bytes: hand it a view of the part of the pool the step's slots lie in")
+  return num_rows, row_stride, head_stride
+
+
+def _mla_sparse_cu_q(T: int, device) -> torch.Tensor:
+  """The boundaries of T one-token sequences, 0 ... T, made on the device once per (T, device)."""
+  key = (T, device.type, device.index)
+  t = _MLA_SPARSE_IDENTITY.get(key)
+  if t is None and torch.cuda.is_current_stream_capturing():
+    return torch.arange(T + 1, dtype=torch.int32, device=device)  # (memory of the graph's own pool: not kept for calls outside the graph)
+  if t is None:
+    if len(_MLA_SPARSE_IDENTITY) >= 64:
+      _MLA_SPARSE_IDENTITY.clear()
+    t = _MLA_SPARSE_IDENTITY[key] = torch.arange(T + 1, dtype=torch.int32, device=device)
+  return t
+
+
+def _mla_sparse_args(dtype, T: int, Hq: int, Hkv: int, D: int, head_dim_v: int, topk: int, num_rows: int, row_stride: int, head_stride: int, q_strides, o_strides,
+                     softmax_scale: float, flags: int, num_splits: int, indices_stride: "int | None" = None):
+  """``(ffpa_varlen_fwd_params, ffpa_mla_sparse)`` of the sparse call without their pointers: the shape class, the strides and the scalars."""
+  p = _varlen_params(dtype, T, Hq, Hkv, D, 1, topk, T, [q_strides, (row_stride, head_stride), (row_stride, head_stride), o_strides], False, softmax_scale, -1.0,
+                     flags, num_splits)
+  s = _stamped(FfpaMlaSparse)
+  s.indices_stride = topk if indices_stride is None else indices_stride
+  s.kv_stride[:] = [row_stride, head_stride]
+  s.topk, s.num_rows, s.head_dim_v = topk, num_rows, int(head_dim_v)
+  return p, s
+
+
+def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, indices: torch.Tensor, topk_lens: "torch.Tensor | None", softmax_scale: float, *,
+                       return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
+  """One call of ``ffpa_attn_varlen_mla_sparse_fwd``: ``q [T, Hq, D]`` (one row per query token), the latent pool ``kv_cache`` (``mla_sparse_pool``'s two forms),
+  the int32 device ``indices [T, topk]`` of pool slots and the optional int32 ``topk_lens [T]`` -> ``(o [T, Hq, head_dim_v], lse [Hq, T] fp32 | None)``.  Token t
+  attends to the rows ``indices[t, :clamp(topk_lens[t], 0, topk)]``; entries at and past the count are never turned into an address.  Nothing is read back to the
+  host: the call (and the split launch's merge) captures into a HIP graph.  ``flags`` / ``plan_out`` / ``num_splits`` as ``varlen_forward``."""
+  name = "ffpa_attn::_mla_sparse_fwd_hip"
+  if not q.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
+  lib = load_library()
+  if q.dtype not in _DTYPE or kv_cache.dtype != q.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
+  if q.dim() != 3 or kv_cache.dim() not in (3, 4) or kv_cache.size(-1) != q.size(2):
+    raise ValueError(f"{name}: q must be [T, Hq, D] and kv_cache [num_rows, Hkv, D] or [num_pages, page_size, Hkv, D] of q's head dim")
+  T, Hq, D = q.shape
+  Hkv = kv_cache.size(-2)
+  if (D, int(head_dim_v)) not in MLA_BUILDS:
+    raise NotImplementedError(f"{name}: (head_dim, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
+  if Hkv == 0 or Hq % Hkv != 0:
+    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of the latent num_heads ({Hkv})")
+  if indices.dtype != torch.int32 or indices.dim() != 2 or indices.size(0) != T or indices.size(1) < 1 or indices.device != q.device:
+    raise ValueError(f"{name}: indices must be a 2-D int32 tensor [T={T}, topk >= 1] on q's device")
+  if topk_lens is not None and (topk_lens.dtype != torch.int32 or topk_lens.dim() != 1 or topk_lens.numel() != T or topk_lens.device != q.device):
+    raise ValueError(f"{name}: topk_lens must be a 1-D int32 tensor of length T={T} on q's device")
+  if kv_cache.device != q.device or kv_cache.numel() == 0:
+    raise ValueError(f"{name}: kv_cache must be a non-empty pool on q's device")
+  if not _layout_ok(kv_cache, -3):
+    raise ValueError(f"{name}: kv_cache needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base (it is read in place)")
+  num_rows, row_stride, head_stride = mla_sparse_pool(kv_cache, name)
+  topk = indices.size(1)
+  q = _rows(q, 0)
+  if indices.stride(1) != 1 or indices.data_ptr() % 4 != 0 or (T > 1 and indices.stride(0) < topk):
+    indices = indices.contiguous()
+  if topk_lens is not None and not topk_lens.is_contiguous():
+    topk_lens = topk_lens.contiguous()
+  o = torch.empty((T, Hq, int(head_dim_v)), dtype=q.dtype, device=q.device)
+  lse = torch.empty((Hq, T), dtype=torch.float32, device=q.device) if return_lse else None
+  if T == 0:
+    return o, lse
+  p, s = _mla_sparse_args(q.dtype, T, Hq, Hkv, D, head_dim_v, topk, num_rows, row_stride, head_stride, q.stride()[-3:-1], o.stride()[-3:-1], softmax_scale,
+                          int(flags) | _deterministic_flag(), num_splits, indices.stride(0) if T > 1 else topk)
+  cu_q = _mla_sparse_cu_q(T, q.device)
+  p.q, p.k, p.v, p.o = q.data_ptr(), kv_cache.data_ptr(), kv_cache.data_ptr(), o.data_ptr()
+  p.lse = lse.data_ptr() if lse is not None else None
+  p.lse_stride_head = lse.stride(0) if lse is not None else 0
+  p.cu_seqlens_q = cu_q.data_ptr()
+  s.indices = indices.data_ptr()
+  s.topk_lens = topk_lens.data_ptr() if topk_lens is not None else None
+  args = (ctypes.byref(p), ctypes.byref(s))
+  with torch.cuda.device(q.device):
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    nbytes = 0
+    if not (p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC):
+      key = ("sparse", id(lib), q.device.index or 0, p.dtype, T, Hq, Hkv, D, s.head_dim_v, topk, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS"))
+      nbytes = _MLA_SCRATCH.get(key)
+      if nbytes is None:
+        if len(_MLA_SCRATCH) >= 512:
+          _MLA_SCRATCH.clear()
+        nbytes = _MLA_SCRATCH[key] = int(lib.ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(*args))
+    workspace = _hand_over_workspace(p, q.device, stream, nbytes)  # (held in a local until the launch below has been enqueued)
+    if plan_out is not None:
+      plan_out.update(_read_plan(lib, lib.ffpa_attn_varlen_mla_sparse_fwd_plan, lib.ffpa_attn_varlen_mla_sparse_fwd_kernel, _VARLEN_PLAN_KEYS, args))
+    rc = lib.ffpa_attn_varlen_mla_sparse_fwd(*args, ctypes.c_void_p(stream))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_varlen_mla_sparse_fwd")
+  return o, lse
+
+
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_sparse_fwd_hip",
+  "(Tensor q, Tensor kv_cache, int head_dim_v, Tensor indices, Tensor? topk_lens, float softmax_scale, int num_splits=0) -> (Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_sparse_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_sparse_fwd_hip_torch_op(q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits=0):
+  return mla_sparse_forward(q, kv_cache, int(head_dim_v), indices, topk_lens, softmax_scale, return_lse=True, num_splits=num_splits)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_fwd_hip")
+def _mla_sparse_fwd_hip_fake(q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits=0):
   total_q, heads, _ = q.shape
   return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
 

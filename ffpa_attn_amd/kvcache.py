@@ -20,7 +20,8 @@ entry point keeps refusing ``softcap``.
 
 An MLA latent cache — ONE cache whose rows are the keys and, in their first ``head_dim_v`` columns, the values (DeepSeek-V2 / V3 / R1, Kimi K2 in their
 "absorbed" decode form) — has an entry of its own too, ``ffpa_attn_with_kvcache_mla`` (below): every latent row is fetched once, and the heads of a latent head are
-packed into the rows of the tiles however many they are.
+packed into the rows of the tiles however many they are.  Sparse (top-k indexed) attention over that cache — every query token attends to the rows an
+indexer picked for it (DeepSeek-V3.2) — is ``ffpa_attn_with_kvcache_mla_sparse`` (below): the rows are read where they lie.
 
 Inference only: ``cache_batch_idx``, ``cache_leftpad`` and ALiBi have no kernel-side implementation here and raise
 ``NotImplementedError`` naming the option — as do ``k`` without ``v`` (or ``v`` without ``k``) and rotary tables without ``k`` / ``v`` or one without the other;
@@ -643,6 +644,133 @@ def ffpa_attn_with_kvcache_mla(
 
 
 # ---- ragged query batches (continuous batching, chunked prefill): ffpa_attn_varlen_with_kvcache
+# ----------------------------------------------------------------------------- sparse (top-k indexed) attention over the latent cache
+def compact_topk_indices(indices: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor]":
+  """``indices [..., topk]`` with ``-1`` (any negative entry) for "no key" anywhere in a row -> ``(indices with every row's entries >= 0 moved to the front in
+  their order, int32 counts [...])``: the form ``ffpa_attn_with_kvcache_mla_sparse`` takes (its kernel serves no holes inside a row).  A stable sort on
+  validity and a sum: plain torch, no host read — it captures into a graph.  What follows a row's valid entries are its invalid ones, as they were."""
+  if not isinstance(indices, torch.Tensor) or indices.dtype not in (torch.int32, torch.int64) or indices.dim() < 1:
+    raise ValueError("compact_topk_indices: indices must be an int32 / int64 tensor [..., topk]")
+  valid = indices >= 0
+  order = torch.sort((~valid).to(torch.int8), dim=-1, stable=True).indices
+  return torch.gather(indices, -1, order), valid.sum(dim=-1, dtype=torch.int32)
+
+
+def slots_from_block_table(positions: torch.Tensor, block_table: torch.Tensor, page_size: int) -> torch.Tensor:
+  """Logical key positions ``[T, topk]`` of sequences -> int32 slots of a page pool: position p of the sequence whose row of page ids is ``block_table[t]``
+  (``[T, pages_per_seq]``: one row per token — index the sequences' table by the tokens' sequence ids first) lives in slot
+  ``block_table[t, p // page_size] * page_size + p % page_size``.  ``positions < 0`` stay -1.  Plain torch, no host read."""
+  if positions.dim() != 2 or block_table.dim() != 2 or block_table.size(0) != positions.size(0):
+    raise ValueError("slots_from_block_table: positions must be [T, topk] and block_table [T, pages_per_seq]")
+  if isinstance(page_size, bool) or not isinstance(page_size, int) or page_size <= 0:
+    raise ValueError(f"slots_from_block_table: page_size must be a positive int, got {page_size!r}")
+  pos = positions.to(torch.int64)
+  live = pos >= 0
+  safe = torch.where(live, pos, torch.zeros_like(pos))
+  page = torch.gather(block_table.to(torch.int64), 1, (safe // page_size).clamp_(max=max(block_table.size(1) - 1, 0)))
+  return torch.where(live, page * page_size + safe % page_size, torch.full_like(pos, -1)).to(torch.int32)
+
+
+def ffpa_attn_with_kvcache_mla_sparse(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  indices: torch.Tensor,
+  *,
+  topk_lens: "torch.Tensor | None" = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """SPARSE attention over an MLA latent cache — DeepSeek-V3.2's "DeepSeek Sparse Attention" in its absorbed decode form (FlashMLA's sparse decode call): an
+  indexer has picked ``topk`` latent rows per query token, shared by all heads of the token, and ``q [T, Hq, D]`` — the step's query tokens, flat (a
+  ``[B, Sq, Hq, D]`` caller reshapes: every token brings its own keys) — attends to those rows only.  Returns ``out [T, Hq, head_dim_v]`` and, with
+  ``return_softmax_lse``, the fp32 ``lse [Hq, T]`` (the ragged latent call's layout).  The rows are read where they lie: the kernel is a build of
+  ``ffpa_attn_with_kvcache_mla``'s whose LDS-DMA pieces take their row from the index list — no gathered copy, no second launch.
+
+  ``kv_cache``: the flat latent pool ``[num_rows, Hkv, D]``, or a page pool ``[num_pages, page_size, Hkv, D]`` of ANY positive ``page_size`` whose pages are
+  evenly spaced (``stride(0) == page_size * stride(1)``, else ``ValueError``): slot r is row ``r % page_size`` of page ``r // page_size``.  Row and head strides
+  are free, the last dimension has unit stride; keys are a row's ``D`` columns, values its first ``head_dim_v``.  ``(D, head_dim_v)`` = (576, 512), bf16 / fp16,
+  ``Hq % Hkv == 0``.  The rows of a latent head may span at most 2^31 bytes — ``(num_rows - 1) * row stride + one row``, about 1.86 M dense 576-wide rows:
+  the kernel's offsets are 32-bit with one bit spent on "no row" — a larger pool raises ``ValueError`` before any launch (hand over a view of the part the
+  step's slots lie in).
+
+  ``indices``: int32 ``[T, topk]`` on the device (unit stride in the last dimension, ``topk >= 1``), entry ``[t, j]`` a slot of the pool; duplicates are legal
+  and count twice, as in a gather.  A 3-D ``[T, Hkv, topk]`` (per-head rows) raises ``NotImplementedError``.  ``topk_lens``: int32 ``[T]`` on the device, or
+  ``None`` = every row holds ``topk`` valid entries; token t attends to ``indices[t, :clamp(topk_lens[t], 0, topk)]``.  Entries at and past the count are NEVER
+  turned into an address, whatever they hold (engines pad with -1).  Entries in front of it must lie in ``[0, num_rows)``; one that does not is clamped into the
+  pool — memory-safe, the token's result unspecified.  -1 holes INSIDE a row are not served: ``compact_topk_indices`` moves a row's valid entries to the front
+  and counts them (plain torch, capturable); ``slots_from_block_table`` turns logical key positions into slots.  A token with count 0 returns O = 0 and
+  LSE = -inf; ``T == 0`` returns empty tensors and launches nothing.
+
+  ``softmax_scale`` is REQUIRED (``TypeError``), as in the two latent calls.  There is no ``causal`` (the indexer has chosen visible keys) and no ``kv=`` (the
+  step's rows are appended by the latent calls or by the engine).  Nothing is read back to the host: the call — with the merge of a split launch — captures
+  into one HIP graph, and a replay follows ``q``, ``indices``, ``topk_lens`` and the pool written in place.  Inference only: a tensor that requires grad raises
+  ``NotImplementedError``.  NOT served, each raises ``NotImplementedError`` naming the keyword: ``causal``, ``kv``, ``window_size``, ``softcap``, ``tree_mask``,
+  rotary tables, ALiBi, ``cache_batch_idx`` / ``cache_leftpad``; FP8 latents raise a dtype error."""
+  name = "ffpa_attn_with_kvcache_mla_sparse"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no causal flag — the indexer has chosen visible keys —, no kv= append, "
+                              "no window, soft-cap, tree mask, rotary tables, ALiBi, batch index or leftpad over the sparse latent call)")
+  if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
+    raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
+                    "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
+  if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
+    raise TypeError(f"{name}: softmax_scale must be a real number, got {softmax_scale!r}")
+  for nm, t in (("q", q), ("kv_cache", kv_cache), ("indices", indices)) + ((("topk_lens", topk_lens),) if topk_lens is not None else ()):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  if q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
+  if q.dim() != 3 or kv_cache.dim() not in (3, 4):
+    raise ValueError(f"{name}: q must be [T, Hq, D] (flatten a [B, Sq, Hq, D] step) and kv_cache [num_rows, Hkv, D] or [num_pages, page_size, Hkv, D]")
+  T, Hq, D = q.shape
+  Hkv = kv_cache.size(-2)
+  if kv_cache.size(-1) != D:
+    raise ValueError(f"{name}: head dim of the cache ({kv_cache.size(-1)}) differs from q's ({D})")
+  if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int):
+    raise TypeError(f"{name}: head_dim_v must be an int, got {head_dim_v!r}")
+  if D % 64 != 0 or head_dim_v <= 0 or head_dim_v % 64 != 0 or head_dim_v > D:
+    raise ValueError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}): both must be multiples of 64 with 0 < head_dim_v <= D")
+  from .hip import MLA_BUILDS, mla_sparse_pool
+
+  if (D, head_dim_v) not in MLA_BUILDS:
+    raise NotImplementedError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
+  if Hkv == 0 or Hq % Hkv != 0:
+    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of the latent num_heads ({Hkv})")
+  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
+  if kv_cache.device != q.device:
+    raise ValueError(f"{name}: q / kv_cache must be on one device, got {q.device}, {kv_cache.device}")
+  if kv_cache.stride(-1) != 1:
+    raise ValueError(f"{name}: kv_cache must have a contiguous last dimension")
+  if indices.dim() == 3:
+    raise NotImplementedError(f"{name}: per-head index rows ([T, Hkv, topk]) are not served: all latent heads of a token share one row [T, topk]")
+  if indices.dtype != torch.int32 or indices.dim() != 2 or indices.size(0) != T:
+    raise ValueError(f"{name}: indices must be an int32 tensor [T={T}, topk], got {indices.dtype} {tuple(indices.shape)}")
+  if indices.size(1) < 1:
+    raise ValueError(f"{name}: indices needs at least one entry per token (topk >= 1)")
+  if indices.stride(1) != 1:
+    raise ValueError(f"{name}: indices must have a contiguous last dimension")
+  if indices.device != q.device:
+    raise ValueError(f"{name}: indices must be on q's device, got {indices.device} and {q.device}")
+  if topk_lens is not None and (topk_lens.dtype != torch.int32 or topk_lens.dim() != 1 or topk_lens.numel() != T or topk_lens.device != q.device):
+    raise ValueError(f"{name}: topk_lens must be an int32 tensor [T={T}] on q's device")
+  if kv_cache.numel() == 0:
+    raise ValueError(f"{name}: kv_cache must be a non-empty pool")
+  mla_sparse_pool(kv_cache, name)  # (evenly spaced pages, the span the kernel's offsets reach: ValueError, from sizes and strides)
+  from . import hip  # noqa: F401  (registers the ffpa_attn ops)
+
+  if T == 0:
+    out = q.new_empty((0, Hq, head_dim_v))
+    return (out, q.new_empty((Hq, 0), dtype=torch.float32)) if return_softmax_lse else out
+  out, lse = torch.ops.ffpa_attn._mla_sparse_fwd_hip(q, kv_cache, head_dim_v, indices, topk_lens, float(softmax_scale), num_splits)
+  return (out, lse) if return_softmax_lse else out
+
+
 def _validate_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k, v, rotary_cos, rotary_sin, positions, softmax_scale, num_splits):
   """Every host-side check of ffpa_attn_varlen_with_kvcache but ``window_size`` / ``softcap`` (nothing read from the device, nothing launched)
   -> (batch, capacity, softmax scale)."""

@@ -514,6 +514,46 @@ typedef struct ffpa_mla_append_varlen_params {
 int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, void* stream);
 
 /*
+ * SPARSE (top-k indexed) attention over the MLA latent cache — DeepSeek-V3.2's "DeepSeek Sparse Attention" in its absorbed decode form, FlashMLA's sparse decode
+ * call: an indexer has picked, per query token, `topk` latent rows (shared by all heads of the token), and the token attends to those rows only.  The latent
+ * call with these changes (no ffpa_paged_kv, no ffpa_mla: this struct carries what they would):
+ *   p->q [batch, heads_q, head_dim] holds one query TOKEN per "sequence": batch = the number of tokens T, p->max_seqlen_q must be 1, p->total_q = T and
+ *        p->cu_seqlens_q the identity boundaries 0, 1, ..., T (device, [T + 1]).  p->max_seqlen_kv is not read (the plan prices topk keys per token).
+ *   p->k is the latent pool: slot r of latent head h starts at k + r * kv_stride[0] + h * kv_stride[1] elements, 0 <= r < num_rows (a page pool whose pages are
+ *        evenly spaced is this with r = page * page_size + row).  p->k_stride, p->v, p->v_stride, p->cu_seqlens_kv and p->seqused_kv are NOT READ.
+ *   Token t attends to slots indices[t * indices_stride + j], 0 <= j < n_t, n_t = clamp(topk_lens[t], 0, topk) (topk_lens == NULL: n_t = topk); duplicates count
+ *        twice.  Entries at and past n_t are never turned into an address, whatever they hold (engines pad with -1).  An entry in front of n_t outside
+ *        [0, num_rows) is clamped into the pool: memory-safe, the token's result unspecified.  -1 holes INSIDE a row are not served: compact the row first.
+ *   A token with n_t = 0 gives O = 0 and LSE = -inf.  p->o, p->lse, p->softmax_scale, the workspace fields and the flags as in the latent call.
+ *   (p->head_dim, head_dim_v) as in the latent call: (576, 512).
+ * The kernel is a build of the latent kernel that reads a tile's rows where they lie: each wave reads the ids of its eight keys of a tile with scalar loads and
+ * turns them into the source offsets of its LDS-DMA pieces — no gathered copy of the rows.  All offsets are 32-bit and bit 31 marks "no row", so the rows of a head
+ * must span at most 2^31 bytes: (num_rows - 1) * kv_stride[0] * 2 + head_dim * 2 <= 2^31 (about 1.86 M contiguous 576-wide rows), else FFPA_ERR_BAD_SHAPE.
+ * The plan is the latent call's for T one-token sequences of topk keys (row chunks of a group wider than the tile, KV ranges + merge, the non-temporal fetch).
+ */
+typedef struct ffpa_mla_sparse {
+  uint32_t struct_size;         /* sizeof(ffpa_mla_sparse), checked */
+  uint32_t reserved;            /* 0, checked */
+  const int32_t* indices;       /* device, 4-byte aligned: [batch][indices_stride] slots, the first topk of a row are the token's list */
+  int64_t indices_stride;       /* elements between two tokens' rows (>= topk) */
+  const int32_t* topk_lens;     /* optional, device [batch]: valid entries per row (clamped to [0, topk]); NULL = topk */
+  int64_t kv_stride[2];         /* elements: between two slots, between two latent heads (multiples of 8; slots must not overlap, < 2^24 apart) */
+  int32_t topk;                 /* entries per row, >= 1 */
+  int32_t num_rows;             /* slots in the pool, >= 1 (ids are clamped to it) */
+  int32_t head_dim_v;           /* value width: the first head_dim_v columns of a latent row */
+  int32_t reserved2;            /* 0, checked */
+} ffpa_mla_sparse;
+
+/* Launch the sparse latent forward on `stream` of the CURRENT device.  Asynchronous, nothing is read on the host; every bad argument returns a status before any
+ * device work.  Returns an ffpa_status. */
+int ffpa_attn_varlen_mla_sparse_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream);
+
+/* As ffpa_attn_varlen_mla_fwd_workspace_bytes / _plan / _kernel, for the sparse call ("ffpa_fwd_m16_mla_sparse_kernel<bf16, 576, dv=512>"). */
+size_t ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s);
+int ffpa_attn_varlen_mla_sparse_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]);
+int ffpa_attn_varlen_mla_sparse_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n);
+
+/*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
  * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
  *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position
