@@ -23,6 +23,7 @@
 #include "ffpa_paged.h"         // (the paged-KV twin of the packed-sequence kernel)
 #include "ffpa_mla.h"           // (the MLA latent-cache kernels and their append)
 #include "ffpa_mla_sparse.h"    // (the sparse — top-k indexed — build of the latent kernel)
+#include "ffpa_mla_tree.h"      // (the tree-mask build of the latent kernel)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
 #include "ffpa_merge_states.h"    // (the merge of two attention states)
 
@@ -1313,6 +1314,33 @@ int mla_sparse_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, V
   return FFPA_OK;
 }
 
+// The tree-mask latent call (ffpa_attn_varlen_mla_tree_fwd): the latent call's plan UNDER THE CAUSAL FLAG (whatever p->causal says: the tree launch walks the causal
+// launch's tiles), the latent call's checks, then the tree call's check of its mask; the launch takes the tree build of the pair the latent call would take.
+const MlaEntry kMlaTreeBuilds[] = {
+#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_tree_d##D},
+    FFPA_FOR_EACH_MLA_BUILD(FFPA_ROW)
+#undef FFPA_ROW
+};
+
+struct MlaTreePlan {
+  ffpa_varlen_fwd_params priced;  // the caller's params under the causal flag
+  const MlaEntry* build;
+};
+
+int mla_tree_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, VarlenPlan* pl, MlaTreePlan* tp) {
+  if (p != nullptr && p->struct_size == sizeof(ffpa_varlen_fwd_params)) {  // (anything else: varlen_plan refuses it by name)
+    tp->priced = *p;
+    tp->priced.causal = 1;
+    p = &tp->priced;
+  }
+  const MlaEntry* dense = nullptr;
+  int rc = mla_plan(p, kv, m, pl, &dense);
+  if (rc != FFPA_OK) return rc;
+  if ((rc = check_tree(p, tree)) != FFPA_OK) return rc;
+  tp->build = &kMlaTreeBuilds[dense - kMlaBuilds];
+  return FFPA_OK;
+}
+
 // The packed call and its paged twin (kv != NULL: k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read); `tree`: under a tree mask
 // (ffpa_attn_varlen_tree_fwd — the causal launch's plan and tile walk; the *_tree_kernel builds, whose element test reads the mask words); `win`: under a sliding
 // window (ffpa_attn_varlen_window_fwd — the window's own plan; the *_window_kernel builds); `softcap` > 0: a window launch with capped scores
@@ -1322,20 +1350,25 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
                   const ffpa_mla_sparse* sparse = nullptr, bool with_sparse = false) {
   // (`mla`: the latent-cache call, ffpa_attn_varlen_mla_fwd — k is the latent pool and serves as v too, p->v is not read; its own plan and kernel; the append in front)
   // (`sparse`: the sparse latent call, ffpa_attn_varlen_mla_sparse_fwd — a latent launch without a page pool: the index list stands where the block table stood)
+  // (`mla` and `tree` together: the tree-mask latent call, ffpa_attn_varlen_mla_tree_fwd — the latent launch under the causal flag, the tree build of its kernel)
   const bool paged = kv != nullptr || with_sparse;
   VarlenPlan pl;
   WindowPlan wp;
   SparsePlan sp;
+  MlaTreePlan tp;
   const MlaEntry* mb = nullptr;
+  const bool mla_tree = with_mla && with_tree;
   int rc = with_sparse ? mla_sparse_plan(p, sparse, &pl, &sp)
+           : mla_tree  ? mla_tree_plan(p, kv, mla, tree, &pl, &tp)
            : with_mla  ? mla_plan(p, kv, mla, &pl, &mb)
            : with_win  ? window_plan(p, kv, win, &pl, &wp)
                        : varlen_plan(p, &pl, paged);
   if (rc != FFPA_OK) return rc;
   if (with_win) p = &wp.priced;  // (the caller's params but for the causal flag and the length the plan saw; the kernel reads every sequence's own length)
   if (with_sparse) p = &sp.priced, mla = &sp.mla, mb = sp.build, with_mla = true;
+  if (mla_tree) p = &tp.priced, mb = tp.build;  // (its plan has checked the pool and the mask)
   if (paged && !with_sparse && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
-  if (with_tree && (rc = check_tree(p, tree)) != FFPA_OK) return rc;
+  if (with_tree && !mla_tree && (rc = check_tree(p, tree)) != FFPA_OK) return rc;
   if (!p->q || !p->k || (!with_mla && !p->v) || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
   if (!p->cu_seqlens_q || (!paged && !p->cu_seqlens_kv)) return fail(FFPA_ERR_NULL_POINTER, "cu_seqlens_q / cu_seqlens_kv must be non-NULL");
   if ((reinterpret_cast<uintptr_t>(p->cu_seqlens_q) & 3u) || (!paged && (reinterpret_cast<uintptr_t>(p->cu_seqlens_kv) & 3u)) || (reinterpret_cast<uintptr_t>(p->seqused_kv) & 3u))
@@ -1708,6 +1741,53 @@ int ffpa_attn_varlen_mla_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_
 int ffpa_attn_varlen_mla_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int* slots) {
   VarlenPlan pl;
   const int rc = mla_plan(p, kv, m, &pl);
+  if (rc != FFPA_OK) return rc;
+  if (slots == nullptr) return fail(FFPA_ERR_NULL_POINTER, "slots is NULL");
+  *slots = pl.compact;
+  return FFPA_OK;
+}
+
+// ---- the tree-mask latent call (include/ffpa_attn.h): the latent launch under the causal flag, the element test of the draft tiles reads the mask words
+int ffpa_attn_varlen_mla_tree_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, void* stream) {
+  return varlen_launch(p, kv, stream, tree, true, nullptr, false, 0.f, m, true);
+}
+
+size_t ffpa_attn_varlen_mla_tree_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree) {
+  if (p == nullptr || p->struct_size != sizeof(ffpa_varlen_fwd_params) || kv == nullptr || kv->struct_size != sizeof(ffpa_paged_kv) || m == nullptr ||
+      m->struct_size != sizeof(ffpa_mla) || tree == nullptr || tree->struct_size != sizeof(ffpa_tree_mask))
+    return 0;
+  // size for the split count the heuristic would pick with unlimited scratch
+  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*p);
+  VarlenPlan pl;
+  MlaTreePlan tp;
+  if (mla_tree_plan(&q, kv, m, tree, &pl, &tp) != FFPA_OK) return 0;
+  return pl.ws_bytes;
+}
+
+int ffpa_attn_varlen_mla_tree_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, int out[5]) {
+  VarlenPlan pl;
+  MlaTreePlan tp;
+  const int rc = mla_tree_plan(p, kv, m, tree, &pl, &tp);
+  if (rc != FFPA_OK) return rc;
+  return plan_out(pl, out);
+}
+
+int ffpa_attn_varlen_mla_tree_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, char* buf, size_t n) {
+  VarlenPlan pl;
+  MlaTreePlan tp;
+  const int rc = mla_tree_plan(p, kv, m, tree, &pl, &tp);
+  if (rc != FFPA_OK) return rc;
+  if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
+  snprintf(buf, n, "ffpa_fwd_m16_mla_tree_kernel<%s, %d, dv=%d%s>%s%s%s", p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", p->head_dim, m->head_dim_v, pl.nt ? ", NT" : "",
+           pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "", pl.compact > 0 ? " (compact grid)" : "",
+           pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
+  return FFPA_OK;
+}
+
+int ffpa_attn_varlen_mla_tree_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, int* slots) {
+  VarlenPlan pl;
+  MlaTreePlan tp;
+  const int rc = mla_tree_plan(p, kv, m, tree, &pl, &tp);
   if (rc != FFPA_OK) return rc;
   if (slots == nullptr) return fail(FFPA_ERR_NULL_POINTER, "slots is NULL");
   *slots = pl.compact;

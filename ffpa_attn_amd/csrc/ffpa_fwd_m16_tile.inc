@@ -850,6 +850,11 @@
   FFPA_LDS char* const xw_nd2 = Xb + wave * 4096 + lane * 16;                 // this wave's partial-S area: slot (kb, rh) at + (2 kb + rh) KiB
   FFPA_LDS const char* const xr_nd2 = Xb + (wave ^ 1) * 4096 + lane * 16;     // the other D-half's
   FFPA_LDS const char* const xb_nd2 = Xb + (qb * 2) * 4096 + lane * 16;       // the row block's two areas (wave dh = 0 first)
+#ifdef FFPA_M16_KV_LOOP_ENTRY
+  // (a statement of the enclosing kernel in front of this KV loop — ffpa_mla_tree_inst.hip, which says why; a preprocessor test: every kernel that does not define it
+  // has the text that stood here)
+  FFPA_M16_KV_LOOP_ENTRY
+#endif
   for (int j = t0; j < nt; ++j) {
     const int k0 = j * BC;
     FFPA_M16_KV_STEP(k0)
@@ -1372,6 +1377,11 @@
     dma_wait_all();      // zero-filled K pieces of the tile past the last one before the workgroup's LDS is)
     asm volatile("" : : "v"(pf_junk));
   }
+#ifdef FFPA_M16_KV_LOOP_EXIT
+  // (a statement of the enclosing kernel behind the KV loops, in front of the epilogue — ffpa_mla_tree_inst.hip, which says why; a preprocessor test: every kernel that
+  // does not define it has the text that stood here)
+  FFPA_M16_KV_LOOP_EXIT
+#endif
   // ================= epilogue (prefill.cuh:1018-1093) =================
   asm volatile("s_nop 15\n\ts_nop 3");  // last PV MFMA (inline asm) -> accumulator reads below: wait states the compiler cannot see
   float l_tot[2], inv[2];

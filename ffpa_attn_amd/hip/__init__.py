@@ -365,6 +365,7 @@ _WINDOW = _PAGED + [_P(FfpaWindow)]
 _SOFTCAP = _WINDOW + [ctypes.c_float]
 _MLA = _PAGED + [_P(FfpaMla)]
 _MLA_SPARSE = [_P(FfpaVarlenFwdParams), _P(FfpaMlaSparse)]
+_MLA_TREE = _MLA + [_P(FfpaTreeMask)]
 # Every function include/ffpa_attn.h declares: (symbol, argtypes, restype, since).  ``since``: the ABI version that added it (0: there from the start) — the
 # default library has them all; one loaded by path or through FFPA_HIP_LIBRARY (developer A/B runs load a saved build of an older commit) may lack those with
 # since > 0: calling one of those is then an AttributeError.
@@ -400,6 +401,11 @@ _BINDINGS = (
   ("ffpa_attn_varlen_mla_fwd_kernel", _MLA + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_mla_fwd_workspace_bytes", _MLA, _SIZE, 7),
   ("ffpa_attn_varlen_mla_fwd_compact_slots", _MLA + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_tree_fwd", _MLA_TREE + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_tree_fwd_plan", _MLA_TREE + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_tree_fwd_kernel", _MLA_TREE + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_mla_tree_fwd_workspace_bytes", _MLA_TREE, _SIZE, 7),
+  ("ffpa_attn_varlen_mla_tree_fwd_compact_slots", _MLA_TREE + [_P(_INT)], _INT, 7),
   ("ffpa_attn_mla_append_varlen", [_P(FfpaMlaAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_fwd", _MLA_SPARSE + [_VOID], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_fwd_plan", _MLA_SPARSE + [_P(_INT)], _INT, 7),
@@ -1526,13 +1532,20 @@ def mla_compact_slots(group: int, seqlens_q: "list[int]", block_rows: int = 64) 
 
 def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seqlens_q: torch.Tensor, seqused_k: torch.Tensor, block_table: torch.Tensor,
                 max_seqlen_q: int, max_seqlen_k: int, causal: bool, softmax_scale: float, *, kv_new: "torch.Tensor | None" = None,
-                cache_seqlens: "torch.Tensor | None" = None, return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
+                cache_seqlens: "torch.Tensor | None" = None, return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0,
+                tree_words: "torch.Tensor | None" = None):
   """One call of ``ffpa_attn_varlen_mla_fwd``: ``q [T, Hq, D]`` packed by ``cu_seqlens_q``, the latent pool ``kv_cache [num_pages, page_size, Hkv, D]`` (written in
   place by the append) with its int32 ``block_table [B, pages_per_seq]`` -> ``(o [T, Hq, head_dim_v], lse [Hq, T] fp32 | None)``.  The keys of KV head h are
   ``kv_cache[..., h, :]``, its values ``kv_cache[..., h, :head_dim_v]``.  ``seqused_k`` int32 ``[B]``: the key lengths — or, with ``kv_new [B, Snew, Hkv, D]``, the
   buffer that RECEIVES ``min(max(cache_seqlens, 0) + Snew, capacity)`` from the append launch in front of the attention launch (``cache_seqlens``: the lengths
-  before the step).  Nothing is read back to the host: the call captures into a HIP graph.  ``flags`` / ``plan_out`` / ``num_splits`` as ``varlen_forward``."""
-  name = "ffpa_attn::_mla_fwd_hip"
+  before the step).  Nothing is read back to the host: the call captures into a HIP graph.  ``flags`` / ``plan_out`` / ``num_splits`` as ``varlen_forward``.
+
+  ``tree_words`` (int64 device ``[B | 1, tokens]``, ``max_seqlen_q <= tokens <= 64``; ``mla_tree_forward`` is this call with it): a TREE MASK over the last rows
+  of every sequence (``ffpa_attn_varlen_mla_tree_fwd``, its own kernel) — token t of sequence i sees every row in front of its sequence's last ``ntok_i`` rows and,
+  of those, row j iff bit j of ``tree_words[i, t]`` is set; ``causal`` is ignored: the launch and its plan are the causal latent launch's."""
+  tree = tree_words is not None
+  name = "ffpa_attn::_mla_tree_fwd_hip" if tree else "ffpa_attn::_mla_fwd_hip"
+  export = "ffpa_attn_varlen_mla_tree_fwd" if tree else "ffpa_attn_varlen_mla_fwd"
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
@@ -1559,6 +1572,14 @@ def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seq
     raise ValueError(f"{name}: kv_cache must be a non-empty pool on q's device")
   if not _layout_ok(kv_cache, -3):
     raise ValueError(f"{name}: kv_cache needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base (it is read, and written, in place)")
+  if tree:
+    if not isinstance(tree_words, torch.Tensor) or tree_words.dtype != torch.int64 or tree_words.dim() != 2 or tree_words.device != q.device:
+      raise ValueError(f"{name}: tree_words must be a 2-D int64 tensor [batch or 1, tokens] on q's device")
+    if tree_words.size(0) not in (1, batch) or not max(int(max_seqlen_q), 1) <= tree_words.size(1) <= 64:
+      raise ValueError(f"{name}: tree_words {tuple(tree_words.shape)} must be [batch={batch} or 1, tokens] with max_seqlen_q={max_seqlen_q} <= tokens <= 64")
+    if tree_words.stride(1) != 1:
+      tree_words = tree_words.contiguous()
+    causal = True
   q = _rows(q, 0)
   cu_seqlens_q, seqused_k = cu_seqlens_q.contiguous(), seqused_k if seqused_k.is_contiguous() else seqused_k.contiguous()
   o = torch.empty((Tq, Hq, int(head_dim_v)), dtype=q.dtype, device=q.device)
@@ -1586,27 +1607,44 @@ def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seq
     m.seqlen_new, m.kv_new, m.cache_seqlens = kv_new.size(1), kv_new.data_ptr(), cache_seqlens.data_ptr()
     m.kv_new_stride[:] = list(kv_new.stride()[:3])
   args = (ctypes.byref(p), ctypes.byref(kv), ctypes.byref(m))
+  if tree:
+    tm = _stamped(FfpaTreeMask)
+    tm.bits, tm.tokens = tree_words.data_ptr(), tree_words.size(1)
+    tm.batch_stride = tree_words.stride(0) if tree_words.size(0) > 1 else 0
+    args += (ctypes.byref(tm),)
   with torch.cuda.device(q.device):
     stream = torch.cuda.current_stream(q.device).cuda_stream
     nbytes = 0
     if not (p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC):
       key = (id(lib), q.device.index or 0, p.dtype, batch, Hq, p.heads_kv, D, m.head_dim_v, p.max_seqlen_q, p.max_seqlen_kv, Tq, p.causal, p.flags, p.num_splits,
-             os.environ.get("FFPA_HIP_FAKE_CUS"))
+             os.environ.get("FFPA_HIP_FAKE_CUS"), tm.tokens if tree else 0)
       nbytes = _MLA_SCRATCH.get(key)
       if nbytes is None:
         if len(_MLA_SCRATCH) >= 512:
           _MLA_SCRATCH.clear()
-        nbytes = _MLA_SCRATCH[key] = int(lib.ffpa_attn_varlen_mla_fwd_workspace_bytes(*args))
+        nbytes = _MLA_SCRATCH[key] = int(getattr(lib, export + "_workspace_bytes")(*args))
     workspace = _hand_over_workspace(p, q.device, stream, nbytes)  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
-      plan_out.update(_read_plan(lib, lib.ffpa_attn_varlen_mla_fwd_plan, lib.ffpa_attn_varlen_mla_fwd_kernel, _VARLEN_PLAN_KEYS, args))
+      plan_out.update(_read_plan(lib, getattr(lib, export + "_plan"), getattr(lib, export + "_kernel"), _VARLEN_PLAN_KEYS, args))
       slots = ctypes.c_int(0)
-      if hasattr(lib, "ffpa_attn_varlen_mla_fwd_compact_slots") and lib.ffpa_attn_varlen_mla_fwd_compact_slots(*args, ctypes.byref(slots)) == 0:
+      if hasattr(lib, export + "_compact_slots") and getattr(lib, export + "_compact_slots")(*args, ctypes.byref(slots)) == 0:
         plan_out["compact_slots"] = slots.value  # (row-tile slots per KV head of the compact grid; 0: the full grid)
-    rc = lib.ffpa_attn_varlen_mla_fwd(*args, ctypes.c_void_p(stream))
+    rc = getattr(lib, export)(*args, ctypes.c_void_p(stream))
   if rc != 0:
-    _raise_status(lib, rc, "ffpa_attn_varlen_mla_fwd")
+    _raise_status(lib, rc, export)
   return o, lse
+
+
+def mla_tree_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seqlens_q: torch.Tensor, seqused_k: torch.Tensor, block_table: torch.Tensor,
+                     max_seqlen_q: int, max_seqlen_k: int, softmax_scale: float, tree_words: torch.Tensor, *, kv_new: "torch.Tensor | None" = None,
+                     cache_seqlens: "torch.Tensor | None" = None, return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
+  """One call of ``ffpa_attn_varlen_mla_tree_fwd`` — the latent call under a TREE MASK (``mla_forward``'s ``tree_words``): ``tree_words`` int64 ``[B | 1, tokens]`` as
+  ``ffpa_attn_amd.pack_tree_mask`` makes them.  ``kv_new`` / ``cache_seqlens`` / ``flags`` / ``plan_out`` / ``num_splits`` as ``mla_forward`` (tests force or inspect
+  the launch)."""
+  if tree_words is None:
+    raise ValueError("ffpa_attn::_mla_tree_fwd_hip: tree_words is required")
+  return mla_forward(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, True, softmax_scale, kv_new=kv_new,
+                     cache_seqlens=cache_seqlens, return_lse=return_lse, flags=flags, plan_out=plan_out, num_splits=num_splits, tree_words=tree_words)
 
 
 # kv_cache is written in place by the append (kv_new): the schema says so
@@ -1627,6 +1665,29 @@ def _mla_fwd_hip_torch_op(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, bloc
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_fwd_hip")
 def _mla_fwd_hip_fake(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k, softmax_scale, causal,
                       num_splits=0):
+  total_q, heads, _ = q.shape
+  return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
+
+
+# The tree-mask latent call (ffpa_attn_with_kvcache_mla_tree / ffpa_attn_varlen_with_kvcache_mla_tree): the latent call's op with the mask words — kv_cache is written
+# in place by the append (kv_new), as there; nothing else is marked written
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_tree_fwd_hip",
+  "(Tensor q, Tensor(a!) kv_cache, int head_dim_v, Tensor cu_seqlens_q, Tensor(b!) seqused_k, Tensor block_table, Tensor tree_words, Tensor? kv_new, "
+  "Tensor? cache_seqlens, int max_seqlen_q, int max_seqlen_k, float softmax_scale, int num_splits=0) -> (Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_tree_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_tree_fwd_hip_torch_op(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, tree_words, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k,
+                               softmax_scale, num_splits=0):
+  return mla_tree_forward(q, kv_cache, int(head_dim_v), cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, softmax_scale, tree_words, kv_new=kv_new,
+                          cache_seqlens=cache_seqlens, return_lse=True, num_splits=num_splits)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_tree_fwd_hip")
+def _mla_tree_fwd_hip_fake(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, tree_words, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k,
+                           softmax_scale, num_splits=0):
   total_q, heads, _ = q.shape
   return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
 

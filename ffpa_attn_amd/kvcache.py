@@ -265,9 +265,9 @@ def pack_tree_mask(tree_mask: torch.Tensor) -> torch.Tensor:
   return (m.to(torch.int64) * bit).sum(dim=-1)  # (disjoint bits: the wrapping sum is the OR)
 
 
-def _tree_words(tree_mask, B: int, Sq: int, device) -> torch.Tensor:
-  """``tree_mask`` of ffpa_attn_with_kvcache_tree checked against q's batch / tokens / device -> the int64 words ``[B | 1, Sq]``."""
-  name = "ffpa_attn_with_kvcache_tree"
+def _tree_words(tree_mask, B: int, Sq: int, device, name: str = "ffpa_attn_with_kvcache_tree", wide: bool = False) -> torch.Tensor:
+  """``tree_mask`` of ffpa_attn_with_kvcache_tree checked against q's batch / tokens / device -> the int64 words ``[B | 1, Sq]``.  ``wide`` (the latent tree
+  calls, under their ``name``): the mask may hold ``W`` tokens, ``Sq <= W <= 64`` -> ``[B | 1, W]``; a sequence of n tokens uses its top-left ``n x n``."""
   if not isinstance(tree_mask, torch.Tensor):
     raise TypeError(f"{name}: tree_mask must be a tensor, got {type(tree_mask).__name__}")
   if tree_mask.dtype not in (torch.bool, torch.int64):
@@ -276,6 +276,12 @@ def _tree_words(tree_mask, B: int, Sq: int, device) -> torch.Tensor:
     raise ValueError(f"{name}: a tree_mask needs 1 <= Sq <= {_TREE_MAX_TOKENS} query tokens per sequence (one 64-bit word per token), got q with Sq = {Sq}")
   if tree_mask.device != device:
     raise ValueError(f"{name}: tree_mask must be on q's device, got {tree_mask.device} and {device}")
+  if wide:
+    W = tree_mask.size(-1) if tree_mask.dim() >= 2 else -1
+    if tree_mask.dim() not in ((2,) if tree_mask.dtype == torch.int64 else (2, 3)) or not Sq <= W <= _TREE_MAX_TOKENS:
+      raise ValueError(f"{name}: tree_mask must be bool [W, W] or [B={B}, W, W], or int64 words [B={B} or 1, W], with {Sq} <= W <= {_TREE_MAX_TOKENS} (the query "
+                       f"tokens per sequence; one 64-bit word per token), got {tuple(tree_mask.shape)}")
+    Sq = W
   if tree_mask.dtype == torch.int64:
     if tree_mask.dim() != 2 or tree_mask.size(0) not in (1, B) or tree_mask.size(1) != Sq:
       raise ValueError(f"{name}: a packed tree_mask must be int64 [B={B} or 1, Sq={Sq}], got {tuple(tree_mask.shape)}")
@@ -507,55 +513,9 @@ def _mla_identity_table(B: int, device) -> torch.Tensor:
   return t
 
 
-def ffpa_attn_with_kvcache_mla(
-  q: torch.Tensor,
-  kv_cache: torch.Tensor,
-  head_dim_v: int,
-  *,
-  kv: torch.Tensor | None = None,
-  cache_seqlens: "int | torch.Tensor",
-  block_table: torch.Tensor | None = None,
-  softmax_scale: float = _MLA_REQUIRED,
-  causal: bool = False,
-  num_splits: int = 0,
-  return_softmax_lse: bool = False,
-  **unsupported,
-):
-  """Attention of ``q [B, Sq, Hq, D]`` over an MLA LATENT cache: ONE cache holds, per KV head h, rows whose ``D`` columns are the keys
-  (``kv_cache[..., h, :]``) and whose first ``head_dim_v`` columns are the values (``kv_cache[..., h, :head_dim_v]``) — multi-head latent attention in its
-  "absorbed" decode form, where every query head (D = 576: a 512-wide compressed latent + 64 rotary columns) attends to one latent head.  Returns
-  ``out [B, Sq, Hq, head_dim_v]`` and, with ``return_softmax_lse``, the fp32 ``lse [B, Hq, Sq]``; the numbers of
-  ``ffpa_attn_with_kvcache(q, kv_cache, kv_cache, ...)[..., :head_dim_v]``, from a kernel that fetches every latent row once (the K and the V^T fragments of a
-  tile are read from one LDS image), packs the ``Hq / Hkv`` heads of a latent head into the rows of its tiles however many they are (128 heads x 1 token = two
-  64-row workgroups per sequence), and stores no junk columns.
-
-  ``kv_cache``: the page pool ``[num_pages, page_size, Hkv, D]`` with an int32 ``block_table [B, pages_per_seq]`` (``page_size`` a multiple of 64), or a contiguous
-  ``[B, capacity, Hkv, D]`` without one.  The contiguous cache is served by the SAME paged kernel as a pool of one page per sequence, through an identity block
-  table made on the device once per (B, device): it needs ``capacity % 64 == 0`` (``ValueError`` otherwise) and has no kernel of its own.  ``Hq % Hkv == 0``
-  (``Hkv`` is 1 in the models named above; nothing assumes it).  ``cache_seqlens``: an int or an int32 ``[B]`` device tensor of keys per sequence.  ``causal`` is
-  ``ffpa_attn_with_kvcache``'s: the last ``Sq`` keys are the queries' own.  A row that sees no key returns O = 0, LSE = -inf.
-
-  ``softmax_scale`` is REQUIRED (``TypeError``): these models scale by ``1 / sqrt(qk_nope_head_dim + qk_rope_head_dim)`` = ``1 / sqrt(192)`` times their YaRN
-  factor, which is not ``1 / sqrt(D)`` — a default would be silently wrong.
-
-  Builds: ``(D, head_dim_v) = (576, 512)``, bf16 and fp16.  Both must be multiples of 64 with ``head_dim_v <= D`` (``ValueError``); any other pair raises
-  ``NotImplementedError`` naming it.
-
-  ``kv [B, Snew, Hkv, D]`` appends the step's latent rows in place at ``cache_seqlens[b] + i`` (dropped at or past the capacity; every element stored once:
-  there is one cache) and attends over ``min(cache_seqlens + Snew, capacity)`` keys, as ``ffpa_attn_with_kvcache`` does with ``k`` / ``v``; ``cache_seqlens`` is
-  not modified.  There are NO rotary parameters: these models rotate ``k_pe`` and ``q_pe`` before the concatenation, and their rotary columns sit at the END of
-  the row — rotate before the call.
-
-  Nothing is read back to the host: the call (append + attention + the split launch's merge) captures into one HIP graph, and a replay follows
-  ``cache_seqlens``, ``block_table`` and ``kv`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``.  NOT served here,
-  each raises ``NotImplementedError`` naming the keyword: ``window_size``, ``softcap``, ``tree_mask``, ``cu_seqlens_q`` (ragged batches are
-  ``ffpa_attn_varlen_with_kvcache_mla``'s), shared-prefix cascades, ``rotary_cos`` / ``rotary_sin``, ALiBi, ``cache_batch_idx`` / ``cache_leftpad`` and FP8
-  latents (a dtype error)."""
-  name = "ffpa_attn_with_kvcache_mla"
-  if unsupported:
-    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no window, soft-cap, tree mask, cascade, rotary tables, ALiBi, batch "
-                              "index or leftpad over the latent cache: rotate q_pe / k_pe before the call; a ragged batch — cu_seqlens_q — is "
-                              "ffpa_attn_varlen_with_kvcache_mla's)")
+def _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits):
+  """The argument checks of ``ffpa_attn_with_kvcache_mla`` — and of ``ffpa_attn_with_kvcache_mla_tree``, under its own ``name`` — in the order they are made
+  -> ``(capacity, cache_seqlens as an int32 [B] device tensor)``."""
   if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
     raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
                     "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
@@ -624,6 +584,136 @@ def ffpa_attn_with_kvcache_mla(
       raise ValueError(f"{name}: kv must be [B={B}, Snew, Hkv={Hkv}, D={D}], got {tuple(kv.shape)}")
     if kv.stride(-1) != 1:
       raise ValueError(f"{name}: kv must have a contiguous last dimension")
+  return capacity, lens
+
+
+def _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, kv, softmax_scale, num_splits):
+  """The argument checks of ``ffpa_attn_varlen_with_kvcache_mla`` — and of ``ffpa_attn_varlen_with_kvcache_mla_tree``, under its own ``name`` — in the order they are
+  made -> ``capacity``."""
+  if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
+    raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
+                    "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
+  if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
+    raise TypeError(f"{name}: softmax_scale must be a real number, got {softmax_scale!r}")
+  for nm, t in (("q", q), ("kv_cache", kv_cache), ("cu_seqlens_q", cu_seqlens_q), ("cache_seqlens", cache_seqlens)) + ((("kv", kv),) if kv is not None else ()):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+  for nm, t in (("q", q), ("kv_cache", kv_cache)) + ((("kv", kv),) if kv is not None else ()):
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  if q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
+  if q.dim() != 3 or kv_cache.dim() != 4:
+    raise ValueError(f"{name}: q must be packed [T, Hq, D] and kv_cache 4-D")
+  T, Hq, D = q.shape
+  Hkv = kv_cache.size(2)
+  if kv_cache.size(3) != D:
+    raise ValueError(f"{name}: head dim of the cache ({kv_cache.size(3)}) differs from q's ({D})")
+  if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int):
+    raise TypeError(f"{name}: head_dim_v must be an int, got {head_dim_v!r}")
+  if D % 64 != 0 or head_dim_v <= 0 or head_dim_v % 64 != 0 or head_dim_v > D:
+    raise ValueError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}): both must be multiples of 64 with 0 < head_dim_v <= D")
+  from .hip import MLA_BUILDS
+
+  if (D, head_dim_v) not in MLA_BUILDS:
+    raise NotImplementedError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
+  if Hkv == 0 or Hq % Hkv != 0:
+    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of the latent num_heads ({Hkv})")
+  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
+  if kv_cache.device != q.device:
+    raise ValueError(f"{name}: q / kv_cache must be on one device, got {q.device}, {kv_cache.device}")
+  if cu_seqlens_q.dtype != torch.int32:
+    raise TypeError(f"{name}: cu_seqlens_q must be int32, got {cu_seqlens_q.dtype}")
+  if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.stride(0) != 1 or cu_seqlens_q.device != q.device:
+    raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor [batch + 1] of unit stride on q's device, got {tuple(cu_seqlens_q.shape)} on {cu_seqlens_q.device}")
+  B = cu_seqlens_q.numel() - 1
+  if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or (T > 0 and max_seqlen_q < 1):
+    raise ValueError(f"{name}: max_seqlen_q must be a host int >= 1 (>= 0 without a token) that bounds every sequence's tokens, got {max_seqlen_q!r}")
+  if cache_seqlens.dtype != torch.int32:
+    raise TypeError(f"{name}: cache_seqlens must be int32, got {cache_seqlens.dtype}")
+  if cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
+    raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [batch={B}] on q's device, got {tuple(cache_seqlens.shape)} on {cache_seqlens.device}")
+  if block_table is not None:
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B:
+      raise ValueError(f"{name}: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
+    if block_table.size(1) == 0:
+      raise ValueError(f"{name}: block_table needs at least one page per sequence")
+    page_size = kv_cache.size(1)
+    if page_size <= 0 or page_size % 64 != 0:
+      raise ValueError(f"{name}: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
+    if block_table.device != q.device:
+      raise ValueError(f"{name}: block_table must be on q's device, got {block_table.device} and {q.device}")
+    capacity = block_table.size(1) * page_size
+  else:
+    if kv_cache.size(0) != B:
+      raise ValueError(f"{name}: kv_cache [B, capacity, Hkv, D] must have cu_seqlens_q's batch ({B}), got {kv_cache.size(0)}")
+    capacity = kv_cache.size(1)
+    if capacity <= 0 or capacity % 64 != 0:
+      raise ValueError(f"{name}: a contiguous cache runs as a pool of one page per sequence: its capacity ({capacity}) must be a positive multiple of 64")
+  if kv is not None:
+    if kv.dtype != q.dtype:
+      raise TypeError(f"{name}: kv must have the cache's dtype {q.dtype}, got {kv.dtype}")
+    if kv.device != q.device:
+      raise ValueError(f"{name}: kv must be on q's device, got {kv.device} and {q.device}")
+    if kv.dim() != 3 or kv.size(0) != T or kv.size(1) != Hkv or kv.size(2) != D:
+      raise ValueError(f"{name}: kv must be [T={T}, Hkv={Hkv}, D={D}] (packed by cu_seqlens_q like q), got {tuple(kv.shape)}")
+    if kv.stride(-1) != 1:
+      raise ValueError(f"{name}: kv must have a contiguous last dimension")
+  return capacity
+
+
+def ffpa_attn_with_kvcache_mla(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  *,
+  kv: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor",
+  block_table: torch.Tensor | None = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  causal: bool = False,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """Attention of ``q [B, Sq, Hq, D]`` over an MLA LATENT cache: ONE cache holds, per KV head h, rows whose ``D`` columns are the keys
+  (``kv_cache[..., h, :]``) and whose first ``head_dim_v`` columns are the values (``kv_cache[..., h, :head_dim_v]``) — multi-head latent attention in its
+  "absorbed" decode form, where every query head (D = 576: a 512-wide compressed latent + 64 rotary columns) attends to one latent head.  Returns
+  ``out [B, Sq, Hq, head_dim_v]`` and, with ``return_softmax_lse``, the fp32 ``lse [B, Hq, Sq]``; the numbers of
+  ``ffpa_attn_with_kvcache(q, kv_cache, kv_cache, ...)[..., :head_dim_v]``, from a kernel that fetches every latent row once (the K and the V^T fragments of a
+  tile are read from one LDS image), packs the ``Hq / Hkv`` heads of a latent head into the rows of its tiles however many they are (128 heads x 1 token = two
+  64-row workgroups per sequence), and stores no junk columns.
+
+  ``kv_cache``: the page pool ``[num_pages, page_size, Hkv, D]`` with an int32 ``block_table [B, pages_per_seq]`` (``page_size`` a multiple of 64), or a contiguous
+  ``[B, capacity, Hkv, D]`` without one.  The contiguous cache is served by the SAME paged kernel as a pool of one page per sequence, through an identity block
+  table made on the device once per (B, device): it needs ``capacity % 64 == 0`` (``ValueError`` otherwise) and has no kernel of its own.  ``Hq % Hkv == 0``
+  (``Hkv`` is 1 in the models named above; nothing assumes it).  ``cache_seqlens``: an int or an int32 ``[B]`` device tensor of keys per sequence.  ``causal`` is
+  ``ffpa_attn_with_kvcache``'s: the last ``Sq`` keys are the queries' own.  A row that sees no key returns O = 0, LSE = -inf.
+
+  ``softmax_scale`` is REQUIRED (``TypeError``): these models scale by ``1 / sqrt(qk_nope_head_dim + qk_rope_head_dim)`` = ``1 / sqrt(192)`` times their YaRN
+  factor, which is not ``1 / sqrt(D)`` — a default would be silently wrong.
+
+  Builds: ``(D, head_dim_v) = (576, 512)``, bf16 and fp16.  Both must be multiples of 64 with ``head_dim_v <= D`` (``ValueError``); any other pair raises
+  ``NotImplementedError`` naming it.
+
+  ``kv [B, Snew, Hkv, D]`` appends the step's latent rows in place at ``cache_seqlens[b] + i`` (dropped at or past the capacity; every element stored once:
+  there is one cache) and attends over ``min(cache_seqlens + Snew, capacity)`` keys, as ``ffpa_attn_with_kvcache`` does with ``k`` / ``v``; ``cache_seqlens`` is
+  not modified.  There are NO rotary parameters: these models rotate ``k_pe`` and ``q_pe`` before the concatenation, and their rotary columns sit at the END of
+  the row — rotate before the call.
+
+  Nothing is read back to the host: the call (append + attention + the split launch's merge) captures into one HIP graph, and a replay follows
+  ``cache_seqlens``, ``block_table`` and ``kv`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``.  NOT served here,
+  each raises ``NotImplementedError`` naming the keyword: ``window_size``, ``softcap``, ``tree_mask``, ``cu_seqlens_q`` (ragged batches are
+  ``ffpa_attn_varlen_with_kvcache_mla``'s), shared-prefix cascades, ``rotary_cos`` / ``rotary_sin``, ALiBi, ``cache_batch_idx`` / ``cache_leftpad`` and FP8
+  latents (a dtype error)."""
+  name = "ffpa_attn_with_kvcache_mla"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no window, soft-cap, tree mask, cascade, rotary tables, ALiBi, batch "
+                              "index or leftpad over the latent cache: rotate q_pe / k_pe before the call; a ragged batch — cu_seqlens_q — is "
+                              "ffpa_attn_varlen_with_kvcache_mla's)")
+  capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits)
+  B, Sq, Hq, D = q.shape
   from . import hip  # (registers the ffpa_attn ops)
 
   out_shape = (B, Sq, Hq, head_dim_v)
@@ -637,6 +727,77 @@ def ffpa_attn_with_kvcache_mla(
   seqused = torch.empty((B,), dtype=torch.int32, device=q.device) if kv_new is not None else lens
   o, lse = torch.ops.ffpa_attn._mla_fwd_hip(qp, kv_cache, head_dim_v, cu_q, seqused, table, kv_new, lens if kv_new is not None else None, Sq, capacity,
                                             float(softmax_scale), 1 if causal else 0, num_splits)
+  out = o.view(*out_shape)
+  if not return_softmax_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+# ---- tree-mask attention over the MLA latent cache (the verification step of tree speculative decoding for the MLA models): ffpa_attn_with_kvcache_mla_tree
+_MLA_TREE_UNSERVED = ("no causal flag — the mask says what a draft token sees —, no window, soft-cap, cascade, rotary tables, ALiBi, batch index or leftpad over "
+                      "the latent cache: rotate q_pe / k_pe before the call")
+
+
+def ffpa_attn_with_kvcache_mla_tree(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  *,
+  tree_mask: torch.Tensor,
+  kv: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor",
+  block_table: torch.Tensor | None = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """``ffpa_attn_with_kvcache_mla`` under a TREE MASK: the verification step of tree speculative decoding for the models whose cache is one latent pool (their MTP
+  head driven as an EAGLE draft model with a tree of more than one branch).  The engine has appended — or appends here, with ``kv`` — the ``Sq`` draft nodes of
+  every sequence to its latent cache and calls attention once: node i sees the whole prefix and, among the ``Sq`` draft rows, what ``tree_mask`` says.  ONE
+  attention launch of the latent kernel's tree build: every latent row is fetched once, the ``Hq / Hkv`` heads x ``Sq`` tokens are the rows of
+  ``ceil(Hq / Hkv * Sq / 64)`` tiles, and only the 32-key tiles that hold a draft row (at most three, and the tail) read the mask.  The launch and its plan are
+  the causal latent call's; no call per root-to-leaf path, no two-cache kernel on an aliased pool.
+
+  ``q [B, Sq, Hq, D]``, ``kv_cache``, ``head_dim_v``, ``kv``, ``cache_seqlens``, ``block_table``, the REQUIRED ``softmax_scale`` (``TypeError``), the ``(D,
+  head_dim_v) = (576, 512)`` build, the contiguous cache (``capacity % 64 == 0``, one page per sequence), ``num_splits`` and the returns (``out [B, Sq, Hq,
+  head_dim_v]``, fp32 ``lse [B, Hq, Sq]``) are ``ffpa_attn_with_kvcache_mla``'s.  ``tree_mask``: a ``torch.bool`` tensor on q's device, ``[W, W]`` (one tree for
+  the batch) or ``[B, W, W]`` — or the int64 words ``[B | 1, W]`` ``pack_tree_mask`` makes of one —, ``Sq <= W <= 64``: the top-left ``Sq x Sq`` is read.  With
+  ``L_b`` the rows attention runs over (``min(cache_seqlens[b] + Snew, capacity)`` with ``kv``, else ``cache_seqlens[b]`` clamped to the capacity), query token i
+  of sequence b sees
+
+  * row ``p`` for every ``p < L_b - Sq`` (the prefix), and
+  * row ``L_b - Sq + j`` iff ``tree_mask[b, i, j]``; draft positions below 0 (``L_b < Sq``) do not exist.
+
+  The mask is arbitrary: a False diagonal (one token per sequence included: ``[[False]]`` hides the token's own row) and "sees a later node" are legal;
+  ``tril(ones)`` is ``ffpa_attn_with_kvcache_mla(causal=True)`` and all ones ``causal=False``, to the bit.  A row that sees nothing returns O = 0, LSE = -inf.
+  Nothing is read back to the host: the call (append + attention + the split launch's merge) captures into one HIP graph, and a replay follows ``q``, ``kv``, the
+  mask words (hand over packed words to write words), ``cache_seqlens`` and ``block_table`` written in place.  Inference only: a tensor that requires grad raises
+  ``NotImplementedError``.  NOT served here, each raises ``NotImplementedError`` naming the keyword: ``causal`` (the mask says it), ``window_size``, ``softcap``,
+  ``cu_seqlens_q`` (ragged batches are ``ffpa_attn_varlen_with_kvcache_mla_tree``'s), shared-prefix cascades, ``rotary_cos`` / ``rotary_sin``, ALiBi,
+  ``cache_batch_idx`` / ``cache_leftpad``, masks over the prefix, more than 64 draft tokens and FP8 latents (a dtype error)."""
+  name = "ffpa_attn_with_kvcache_mla_tree"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} ({_MLA_TREE_UNSERVED}; a ragged batch — cu_seqlens_q — is "
+                              "ffpa_attn_varlen_with_kvcache_mla_tree's)")
+  capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits)
+  if isinstance(tree_mask, torch.Tensor) and tree_mask.requires_grad and torch.is_grad_enabled():
+    raise NotImplementedError(f"{name} is inference only: tree_mask requires grad and there is no backward")
+  B, Sq, Hq, D = q.shape
+  from . import hip  # (registers the ffpa_attn ops)
+
+  out_shape = (B, Sq, Hq, head_dim_v)
+  if B == 0 or Sq == 0:
+    out = q.new_zeros(out_shape)
+    return (out, q.new_full((B, Hq, Sq), float("-inf"), dtype=torch.float32)) if return_softmax_lse else out
+  words = _tree_words(tree_mask, B, Sq, q.device, name, wide=True)
+  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
+  qp = q.reshape(B * Sq, Hq, D)
+  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
+  kv_new = kv if kv is not None and kv.size(1) > 0 else None
+  seqused = torch.empty((B,), dtype=torch.int32, device=q.device) if kv_new is not None else lens
+  o, lse = torch.ops.ffpa_attn._mla_tree_fwd_hip(qp, kv_cache, head_dim_v, cu_q, seqused, table, words, kv_new, lens if kv_new is not None else None, Sq, capacity,
+                                                 float(softmax_scale), num_splits)
   out = o.view(*out_shape)
   if not return_softmax_lse:
     return out
@@ -1008,76 +1169,9 @@ def ffpa_attn_varlen_with_kvcache_mla(
   if unsupported:
     raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no window, soft-cap, tree mask, cascade, rotary tables or positions, "
                               "ALiBi, batch index or leftpad over the latent cache: rotate q_pe / k_pe before the call)")
-  if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
-    raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
-                    "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
-  if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
-    raise TypeError(f"{name}: softmax_scale must be a real number, got {softmax_scale!r}")
-  for nm, t in (("q", q), ("kv_cache", kv_cache), ("cu_seqlens_q", cu_seqlens_q), ("cache_seqlens", cache_seqlens)) + ((("kv", kv),) if kv is not None else ()):
-    if not isinstance(t, torch.Tensor):
-      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
-  for nm, t in (("q", q), ("kv_cache", kv_cache)) + ((("kv", kv),) if kv is not None else ()):
-    if t.requires_grad and torch.is_grad_enabled():
-      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
-  if q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
-    raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
-  if q.dim() != 3 or kv_cache.dim() != 4:
-    raise ValueError(f"{name}: q must be packed [T, Hq, D] and kv_cache 4-D")
+  capacity = _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, kv, softmax_scale, num_splits)
   T, Hq, D = q.shape
-  Hkv = kv_cache.size(2)
-  if kv_cache.size(3) != D:
-    raise ValueError(f"{name}: head dim of the cache ({kv_cache.size(3)}) differs from q's ({D})")
-  if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int):
-    raise TypeError(f"{name}: head_dim_v must be an int, got {head_dim_v!r}")
-  if D % 64 != 0 or head_dim_v <= 0 or head_dim_v % 64 != 0 or head_dim_v > D:
-    raise ValueError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}): both must be multiples of 64 with 0 < head_dim_v <= D")
-  from .hip import MLA_BUILDS
-
-  if (D, head_dim_v) not in MLA_BUILDS:
-    raise NotImplementedError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
-  if Hkv == 0 or Hq % Hkv != 0:
-    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of the latent num_heads ({Hkv})")
-  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
-    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
-  if kv_cache.device != q.device:
-    raise ValueError(f"{name}: q / kv_cache must be on one device, got {q.device}, {kv_cache.device}")
-  if cu_seqlens_q.dtype != torch.int32:
-    raise TypeError(f"{name}: cu_seqlens_q must be int32, got {cu_seqlens_q.dtype}")
-  if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.stride(0) != 1 or cu_seqlens_q.device != q.device:
-    raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor [batch + 1] of unit stride on q's device, got {tuple(cu_seqlens_q.shape)} on {cu_seqlens_q.device}")
   B = cu_seqlens_q.numel() - 1
-  if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or (T > 0 and max_seqlen_q < 1):
-    raise ValueError(f"{name}: max_seqlen_q must be a host int >= 1 (>= 0 without a token) that bounds every sequence's tokens, got {max_seqlen_q!r}")
-  if cache_seqlens.dtype != torch.int32:
-    raise TypeError(f"{name}: cache_seqlens must be int32, got {cache_seqlens.dtype}")
-  if cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
-    raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [batch={B}] on q's device, got {tuple(cache_seqlens.shape)} on {cache_seqlens.device}")
-  if block_table is not None:
-    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B:
-      raise ValueError(f"{name}: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
-    if block_table.size(1) == 0:
-      raise ValueError(f"{name}: block_table needs at least one page per sequence")
-    page_size = kv_cache.size(1)
-    if page_size <= 0 or page_size % 64 != 0:
-      raise ValueError(f"{name}: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
-    if block_table.device != q.device:
-      raise ValueError(f"{name}: block_table must be on q's device, got {block_table.device} and {q.device}")
-    capacity = block_table.size(1) * page_size
-  else:
-    if kv_cache.size(0) != B:
-      raise ValueError(f"{name}: kv_cache [B, capacity, Hkv, D] must have cu_seqlens_q's batch ({B}), got {kv_cache.size(0)}")
-    capacity = kv_cache.size(1)
-    if capacity <= 0 or capacity % 64 != 0:
-      raise ValueError(f"{name}: a contiguous cache runs as a pool of one page per sequence: its capacity ({capacity}) must be a positive multiple of 64")
-  if kv is not None:
-    if kv.dtype != q.dtype:
-      raise TypeError(f"{name}: kv must have the cache's dtype {q.dtype}, got {kv.dtype}")
-    if kv.device != q.device:
-      raise ValueError(f"{name}: kv must be on q's device, got {kv.device} and {q.device}")
-    if kv.dim() != 3 or kv.size(0) != T or kv.size(1) != Hkv or kv.size(2) != D:
-      raise ValueError(f"{name}: kv must be [T={T}, Hkv={Hkv}, D={D}] (packed by cu_seqlens_q like q), got {tuple(kv.shape)}")
-    if kv.stride(-1) != 1:
-      raise ValueError(f"{name}: kv must have a contiguous last dimension")
   from . import hip  # (registers the ffpa_attn ops)
 
   if T == 0:
@@ -1090,6 +1184,63 @@ def ffpa_attn_varlen_with_kvcache_mla(
     seqused = torch.ops.ffpa_attn._mla_append_varlen_hip(kv_cache, kv, cu_seqlens_q, cache_seqlens, table)
   o, lse = torch.ops.ffpa_attn._mla_fwd_hip(q, kv_cache, head_dim_v, cu_seqlens_q, seqused, table, None, None, max_seqlen_q, capacity, float(softmax_scale),
                                             1 if causal else 0, num_splits)
+  return (o, lse) if return_softmax_lse else o
+
+
+# ---- ragged query batches under a tree mask over the MLA latent cache: ffpa_attn_varlen_with_kvcache_mla_tree
+def ffpa_attn_varlen_with_kvcache_mla_tree(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  cu_seqlens_q: torch.Tensor,
+  max_seqlen_q: int,
+  cache_seqlens: torch.Tensor,
+  block_table: torch.Tensor | None = None,
+  *,
+  tree_mask: torch.Tensor,
+  kv: torch.Tensor | None = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """``ffpa_attn_with_kvcache_mla_tree`` for a RAGGED step: the sequences of a continuous-batching engine bring draft trees of different sizes (and plain decodes:
+  a tree of one node).  ``q [T, Hq, D]``, ``cu_seqlens_q``, the ``max_seqlen_q`` contract, ``cache_seqlens``, ``kv [T, Hkv, D]`` and its per-token append launch,
+  ``kv_cache``, ``head_dim_v``, ``block_table``, the REQUIRED ``softmax_scale``, the row chunks, the compact grid, ``num_splits`` and the returns (``out [T, Hq,
+  head_dim_v]``, fp32 ``lse [Hq, T]``; rows at or past ``cu_seqlens_q[B]`` unspecified) are ``ffpa_attn_varlen_with_kvcache_mla``'s — B comes from
+  ``cu_seqlens_q``.  ``tree_mask``: bool ``[W, W]`` or ``[B, W, W]``, or the int64 words ``[B | 1, W]`` of ``pack_tree_mask``, ``max_seqlen_q <= W <= 64``;
+  sequence b with ``n_b`` tokens uses the top-left ``n_b x n_b`` of its mask.  With ``L_b`` the rows attention runs over (``min(max(cache_seqlens[b], 0) + n_b,
+  capacity)`` with ``kv``, else ``cache_seqlens[b]`` clamped to ``[0, capacity]``), query token i of sequence b sees
+
+  * row ``p`` for every ``p < L_b - n_b`` (the prefix), and
+  * row ``L_b - n_b + j`` iff ``tree_mask[b, i, j]``; draft positions below 0 do not exist.
+
+  A row that sees nothing returns O = 0, LSE = -inf.  ``T == 0`` returns empty tensors and launches nothing.  Nothing is read back to the host: the step (append +
+  attention + the split launch's merge) captures into one HIP graph, and a replay follows ``q``, ``kv``, the mask words, ``cu_seqlens_q`` (same T, same bound),
+  ``cache_seqlens`` and ``block_table`` written in place.  Inference only.  NOT served here, each raises ``NotImplementedError`` naming the keyword: ``causal`` (the
+  mask says it), ``window_size``, ``softcap``, shared-prefix cascades, ``rotary_cos`` / ``rotary_sin`` / ``positions``, ALiBi, ``cache_batch_idx`` /
+  ``cache_leftpad``, masks over the prefix, more than 64 draft tokens per sequence and FP8 latents (a dtype error)."""
+  name = "ffpa_attn_varlen_with_kvcache_mla_tree"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} ({_MLA_TREE_UNSERVED}; no positions)")
+  capacity = _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, kv, softmax_scale, num_splits)
+  if isinstance(tree_mask, torch.Tensor) and tree_mask.requires_grad and torch.is_grad_enabled():
+    raise NotImplementedError(f"{name} is inference only: tree_mask requires grad and there is no backward")
+  T, Hq, D = q.shape
+  B = cu_seqlens_q.numel() - 1
+  from . import hip  # (registers the ffpa_attn ops)
+
+  if T == 0:
+    out = q.new_empty((0, Hq, head_dim_v))
+    return (out, torch.empty((Hq, 0), dtype=torch.float32, device=q.device)) if return_softmax_lse else out
+  words = _tree_words(tree_mask, B, max_seqlen_q, q.device, name, wide=True)
+  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
+  seqused = cache_seqlens
+  if kv is not None:
+    # the prepare launch: the step's latent rows into the cache (in place) and the post-append lengths — read by the attention launch below on the same stream
+    seqused = torch.ops.ffpa_attn._mla_append_varlen_hip(kv_cache, kv, cu_seqlens_q, cache_seqlens, table)
+  o, lse = torch.ops.ffpa_attn._mla_tree_fwd_hip(q, kv_cache, head_dim_v, cu_seqlens_q, seqused, table, words, None, None, max_seqlen_q, capacity,
+                                                 float(softmax_scale), num_splits)
   return (o, lse) if return_softmax_lse else o
 
 

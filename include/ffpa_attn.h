@@ -449,7 +449,7 @@ int ffpa_attn_varlen_softcap_fwd_kernel(const ffpa_varlen_fwd_params* p, const f
  * batch * ceil(group * max_seqlen_q / block rows) row tiles per KV head would find no row, the grid is sized by the rows there are:
  * ceil(group * total_q / block rows) + batch slots per KV head (an upper bound of the sum of the sequences' tiles), each finding its (sequence, row tile) on the
  * device; FFPA_FLAG_NO_COMPACT_GRID keeps the full grid (same order, same bits).  Packing and the non-temporal fetch stay launch-wide decisions.
- * Not served (use the other calls on a (kv, kv) pair): windows, soft-capping, tree masks, FP8 latents.
+ * Not served (use the other calls on a (kv, kv) pair): windows, soft-capping, FP8 latents; tree masks are ffpa_attn_varlen_mla_tree_fwd's (below).
  */
 typedef struct ffpa_mla {
   uint32_t struct_size;          /* sizeof(ffpa_mla), checked */
@@ -475,6 +475,30 @@ int ffpa_attn_varlen_mla_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_
 /* *slots = row-tile slots per KV head of the compact grid the plan takes for this call (out[3] of the plan is then slots * heads_kv * KV ranges, and the kernel
  * text carries "(compact grid)"); 0 = the full grid.  Returns an ffpa_status. */
 int ffpa_attn_varlen_mla_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int* slots);
+
+/*
+ * TREE MASK OVER THE LATENT CACHE — the verification step of tree speculative decoding for the models above (their MTP head driven as an EAGLE draft model with a
+ * tree of more than one branch): the latent call under an ffpa_tree_mask.  The ntok_i = cu_seqlens_q[i + 1] - cu_seqlens_q[i] draft nodes of sequence i are the
+ * LAST rows of its latent cache (L_i = p->seqused_kv[i] clamped to the capacity — with m->seqlen_new > 0, the length behind the append).  Query token t sees
+ *        row p                      for every p < L_i - ntok_i (the prefix), and
+ *        row L_i - ntok_i + j       iff bit j of tree->bits[i * batch_stride + t] is set (0 <= j < ntok_i); draft positions below row 0 do not exist.
+ *   ffpa_tree_mask keeps its meaning (one word per (sequence, token), batch_stride = 0: one tree for the batch, tokens in 1 ... 64 and >= max_seqlen_q, the token
+ *   index clamped on the device); p->causal is ignored: the launch, its plan, its KV ranges, the row chunks of a group wider than the tile and the compact grid are
+ *   ffpa_attn_varlen_mla_fwd's UNDER THE CAUSAL FLAG for the same (p, kv, m).  One token per sequence keeps its mask: a clear bit 0 hides the token's own row.
+ *   A token that sees no row gives O = 0, LSE = -inf.  All ones below the diagonal IS the causal latent launch and all ones the non-causal one, to the bit.
+ * The kernel is the latent kernel's text with the tree hook on (ffpa_fwd_m16_mla_tree_kernel): only the element test of the 32-key tiles that hold a draft row —
+ * at most three, plus the tail — reads the words.  The append is the latent call's (m->seqlen_new > 0), or ffpa_attn_mla_append_varlen in front for a ragged step.
+ * Every bad argument — those of ffpa_attn_varlen_mla_fwd, then a NULL tree, a wrong struct_size, NULL or misaligned bits, tokens outside [max_seqlen_q, 64], a
+ * batch_stride in (0, tokens) — returns a status before any device work.  Returns an ffpa_status.
+ */
+int ffpa_attn_varlen_mla_tree_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, void* stream);
+
+/* As ffpa_attn_varlen_mla_fwd_workspace_bytes / _plan / _kernel / _compact_slots, for the tree-mask latent call ("ffpa_fwd_m16_mla_tree_kernel<bf16, 576,
+ * dv=512>"; the plan is ffpa_attn_varlen_mla_fwd_plan's with p->causal = 1). */
+size_t ffpa_attn_varlen_mla_tree_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree);
+int ffpa_attn_varlen_mla_tree_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, int out[5]);
+int ffpa_attn_varlen_mla_tree_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, char* buf, size_t n);
+int ffpa_attn_varlen_mla_tree_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, int* slots);
 
 /*
  * LATENT APPEND OF A RAGGED STEP — the launch in front of ffpa_attn_varlen_mla_fwd when the sequences of a step bring different numbers of new latent rows.
