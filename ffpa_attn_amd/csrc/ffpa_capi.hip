@@ -54,25 +54,19 @@ const DimEntry kDims[] = {
 #undef FFPA_ROW
 };
 
-// the packed-sequence kernel: one launcher per head dim of the 16x16x32 build (ffpa_varlen_inst.hip)
+// the packed-sequence kernel and its paged-KV twin: one launcher each per head dim of the 16x16x32 build (ffpa_varlen_inst.hip, ffpa_paged_inst.hip)
 typedef int (*varlen_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, hipStream_t);
+typedef int (*paged_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, hipStream_t);
 struct VarlenEntry {
   int d;
   varlen_fn launch;
+  paged_fn paged;
 };
 const VarlenEntry kVarlenDims[] = {
-#define FFPA_ROW(D) {D, &ffpa::launch_varlen_d##D},
+#define FFPA_ROW(D) {D, &ffpa::launch_varlen_d##D, &ffpa::launch_paged_d##D},
     FFPA_FOR_EACH_VARLEN_HEAD_DIM(FFPA_ROW)
 #undef FFPA_ROW
 };
-// ... and its paged-KV twin (ffpa_paged_inst.hip), the same head dims: entry i serves kVarlenDims[i].d
-typedef int (*paged_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, hipStream_t);
-const paged_fn kPagedDims[] = {
-#define FFPA_ROW(D) &ffpa::launch_paged_d##D,
-    FFPA_FOR_EACH_VARLEN_HEAD_DIM(FFPA_ROW)
-#undef FFPA_ROW
-};
-static_assert(sizeof(kPagedDims) / sizeof(kPagedDims[0]) == sizeof(kVarlenDims) / sizeof(kVarlenDims[0]), "one paged launcher per packed head dim");
 
 // Head dims are instantiated in multiples of 64; any multiple of 8 up to 1024 runs on the next instantiation with the
 // columns past the caller's head dim read as zeros and never stored (the reference pads to its compiled multiples on
@@ -1161,44 +1155,6 @@ int check_window(const ffpa_window* w) {
   return FFPA_OK;
 }
 
-// What a window launch hands the kernel (VarlenArgs::window) and the params its plan is made from.
-struct WindowPlan {
-  int causal;  // the launch runs under the causal flag (right >= 0): `right` rides in the causal limit
-  int right;   // VarlenArgs::win_right
-  int span;    // VarlenArgs::win_span
-  ffpa_varlen_fwd_params priced;  // the caller's params with the causal flag above and max_seqlen_kv = the widest key span a row tile can see
-};
-
-// The window call's plan: the packed call's, PRICED AT WHAT THE WINDOW LEAVES.  A row tile of R token rows (all max_seqlen_q tokens under GQA row packing, else
-// the block rows) walks the keys from its first row's left bound to its last row's right bound — R + left + right of them, and never more than left +
-// max_seqlen_q (the last key is the right bound of the last token) — so the split count ("fill the chip, then balance") and the non-temporal fetch ("K / V bytes
-// with one reader, larger than the Infinity Cache") see that many keys, rounded up to a KV tile, and not the cache's capacity.  No left bound: the caller's
-// max_seqlen_kv.  `left` / `right` at or past the longest sequence are the unbounded side they amount to (they reach the kernel as small ints).
-int window_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, VarlenPlan* pl, WindowPlan* wp) {
-  const bool paged = kv != nullptr;
-  int rc = varlen_plan(p, pl, paged);  // (validates p; the tile rows and the GQA packing do not depend on max_seqlen_kv)
-  if (rc != FFPA_OK) return rc;
-  if (paged && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
-  if ((rc = check_window(w)) != FFPA_OK) return rc;
-  int64_t right = p->causal ? 0 : w->right;
-  if (right > p->max_seqlen_q) right = p->max_seqlen_q;  // (the last token's position + max_seqlen_q - 1 is already the last key)
-  int64_t left = w->left;
-  if (left >= p->max_seqlen_kv) left = -1;  // (no position reaches that far back: positions are below max_seqlen_kv)
-  wp->causal = right >= 0 ? 1 : 0;
-  wp->right = right >= 0 ? (int)right : 0;
-  wp->span = left >= 0 ? (int)(left + wp->right) : -1;
-  wp->priced = *p;
-  wp->priced.causal = wp->causal;
-  if (left >= 0) {
-    const int64_t rows = pl->pack || p->max_seqlen_q < pl->br ? p->max_seqlen_q : pl->br;
-    int64_t tail = right >= 0 ? rows + right : (int64_t)p->max_seqlen_q;
-    if (tail > p->max_seqlen_q) tail = p->max_seqlen_q;
-    const int64_t keys = (left + tail + pl->bc - 1) / pl->bc * pl->bc;
-    if (keys < p->max_seqlen_kv) wp->priced.max_seqlen_kv = (int)keys;
-  }
-  return varlen_plan(&wp->priced, pl, paged);
-}
-
 // The soft-capping call's own argument: a finite cap > 0 (0 = "off" is the Python entry's business: it forwards to the window call), checked before any device work.
 int check_softcap(float softcap) {
   if (!isfinite(softcap) || !(softcap > 0.f)) return fail(FFPA_ERR_BAD_SHAPE, "softcap=%g must be finite and > 0", (double)softcap);
@@ -1211,26 +1167,28 @@ const ffpa_window* softcap_window(const ffpa_window* w) {
   return w != nullptr ? w : &kNone;
 }
 
-// The latent-cache call's own argument (ffpa_mla), checked behind the plan (and the pool) and before anything touches the device.
+// The kernel builds of the latent-cache calls: one row per (head dim, value width) pair with its three launchers — the latent call's (ffpa_mla_inst.hip), the
+// sparse (top-k indexed) call's (ffpa_mla_sparse_inst.hip) and the tree-mask call's (ffpa_mla_tree_inst.hip).
 typedef int (*mla_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, const ffpa::MlaArgs&, hipStream_t);
-struct MlaEntry {
+struct MlaBuild {
   int d, dv;
-  mla_fn launch;
+  mla_fn latent, sparse, tree;
 };
-const MlaEntry kMlaBuilds[] = {
-#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_paged_d##D},
+const MlaBuild kMlaBuilds[] = {
+#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_paged_d##D, &ffpa::launch_mla_sparse_d##D, &ffpa::launch_mla_tree_d##D},
     FFPA_FOR_EACH_MLA_BUILD(FFPA_ROW)
 #undef FFPA_ROW
 };
 
-int check_mla(const ffpa_varlen_fwd_params* p, const ffpa_mla* m, const MlaEntry** build) {
+// The latent-cache call's own argument (ffpa_mla), checked behind the plan (and the pool) and before anything touches the device.
+int check_mla(const ffpa_varlen_fwd_params* p, const ffpa_mla* m, const MlaBuild** build) {
   if (m == nullptr) return fail(FFPA_ERR_NULL_POINTER, "mla is NULL");
   if (m->struct_size != sizeof(ffpa_mla)) return fail(FFPA_ERR_BAD_ABI, "ffpa_mla ABI mismatch: size %u (want %zu)", m->struct_size, sizeof(ffpa_mla));
   if (m->reserved != 0) return fail(FFPA_ERR_BAD_ABI, "ffpa_mla.reserved=%u must be 0", m->reserved);
   if (p->head_dim % 64 != 0 || m->head_dim_v <= 0 || m->head_dim_v % 64 != 0 || m->head_dim_v > p->head_dim)
     return fail(FFPA_ERR_BAD_SHAPE, "(head_dim, head_dim_v) = (%d, %d): both must be multiples of 64 with 0 < head_dim_v <= head_dim", p->head_dim, m->head_dim_v);
-  const MlaEntry* found = nullptr;
-  for (const MlaEntry& e : kMlaBuilds)
+  const MlaBuild* found = nullptr;
+  for (const MlaBuild& e : kMlaBuilds)
     if (e.d == p->head_dim && e.dv == m->head_dim_v) found = &e;
   if (found == nullptr) return fail(FFPA_ERR_BAD_HEADDIM, "(head_dim, head_dim_v) = (%d, %d) is not built (built: (576, 512))", p->head_dim, m->head_dim_v);
   if (m->seqlen_new < 0) return fail(FFPA_ERR_BAD_SHAPE, "ffpa_mla.seqlen_new=%d must not be negative", m->seqlen_new);
@@ -1243,39 +1201,13 @@ int check_mla(const ffpa_varlen_fwd_params* p, const ffpa_mla* m, const MlaEntry
     if (rc != FFPA_OK) return rc;
     if ((int64_t)p->batch * m->seqlen_new > 0x7fffffffLL) return fail(FFPA_ERR_BAD_SHAPE, "grid of %lld new rows is too large", (long long)p->batch * m->seqlen_new);
   }
-  if (build != nullptr) *build = found;
+  *build = found;
   return FFPA_OK;
 }
 
-// The latent-cache call's plan: the paged call's with every group packed into rows (varlen_plan's `mla`), then the pool, then the call's own argument.
-int mla_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, VarlenPlan* pl, const MlaEntry** build = nullptr) {
-  int rc = varlen_plan(p, pl, true, true);
-  if (rc != FFPA_OK) return rc;
-  if ((rc = check_paged(p, kv)) != FFPA_OK) return rc;
-  return check_mla(p, m, build);
-}
-
-// The sparse latent call (ffpa_attn_varlen_mla_sparse_fwd): its own argument, checked before anything touches the device, and what the launch is made from.
-const MlaEntry kMlaSparseBuilds[] = {
-#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_sparse_d##D},
-    FFPA_FOR_EACH_MLA_BUILD(FFPA_ROW)
-#undef FFPA_ROW
-};
-
-struct SparsePlan {
-  ffpa_varlen_fwd_params priced;  // the caller's params as the latent launch reads them: T one-token sequences of topk keys, the pool's strides, the counts as lengths
-  ffpa_mla mla;                   // (head_dim_v; nothing is appended)
-  const ffpa_mla_sparse* s;
-  const MlaEntry* build;
-};
-
-// The reach of the kernel's addressing: every lane offset is 32 bits from the head's first row and bit 31 (kDmaOob) is the "no row" sentinel, so the rows of a
-// head span at most 2^31 bytes.
-constexpr int64_t kSparseSpanBytes = 1LL << 31;
-
-// The sparse call's plan: the latent call's for a batch of T one-token sequences of topk keys ("fill the chip, then balance", the one-reader rule of the NT build,
-// the row chunks of a group wider than the tile; a uniform batch never meets the compact grid).
-int mla_sparse_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, VarlenPlan* pl, SparsePlan* sp) {
+// The sparse latent call's own argument (ffpa_mla_sparse), in two parts.  What it checks BEFORE the plan — both pointers, its struct, then the params' ABI (the plan
+// is made from a copy of them: price_sparse) and the index list ...
+int check_sparse(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
   if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
   if (s == nullptr) return fail(FFPA_ERR_NULL_POINTER, "mla_sparse is NULL");
   if (s->struct_size != sizeof(ffpa_mla_sparse))
@@ -1290,21 +1222,17 @@ int mla_sparse_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, V
   if ((reinterpret_cast<uintptr_t>(s->indices) & 3u) || (reinterpret_cast<uintptr_t>(s->topk_lens) & 3u))
     return fail(FFPA_ERR_MISALIGNED, "indices / topk_lens must be 4-byte aligned");
   if (s->indices_stride < s->topk) return fail(FFPA_ERR_BAD_STRIDE, "indices_stride=%lld is smaller than topk=%d", (long long)s->indices_stride, s->topk);
-  sp->s = s;
-  sp->priced = *p;
-  sp->priced.causal = 0;  // (the indexer has chosen visible keys)
-  sp->priced.max_seqlen_kv = s->topk;
-  sp->priced.k_stride[0] = s->kv_stride[0], sp->priced.k_stride[1] = s->kv_stride[1];
-  sp->priced.seqused_kv = s->topk_lens;
-  memset(&sp->mla, 0, sizeof(sp->mla));
-  sp->mla.struct_size = (uint32_t)sizeof(ffpa_mla);
-  sp->mla.head_dim_v = s->head_dim_v;
-  int rc = varlen_plan(&sp->priced, pl, true, true);
+  return FFPA_OK;
+}
+
+// The reach of the sparse kernel's addressing: every lane offset is 32 bits from the head's first row and bit 31 (kDmaOob) is the "no row" sentinel, so the rows of a
+// head span at most 2^31 bytes.
+constexpr int64_t kSparseSpanBytes = 1LL << 31;
+
+// ... and what it checks BEHIND the plan and the (head_dim, head_dim_v) pair: the latent pool's geometry.
+int check_sparse_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
+  const int rc = check_strides("kv", s->kv_stride, 2);
   if (rc != FFPA_OK) return rc;
-  const MlaEntry* dense = nullptr;
-  if ((rc = check_mla(&sp->priced, &sp->mla, &dense)) != FFPA_OK) return rc;
-  sp->build = &kMlaSparseBuilds[dense - kMlaBuilds];
-  if ((rc = check_strides("kv", s->kv_stride, 2)) != FFPA_OK) return rc;
   if (s->kv_stride[0] < p->head_dim || s->kv_stride[0] >= (1LL << 24))
     return fail(FFPA_ERR_BAD_STRIDE, "kv row stride %lld: rows must not overlap and must be < 2^24 elements apart", (long long)s->kv_stride[0]);
   const int64_t span = ((int64_t)s->num_rows - 1) * s->kv_stride[0] * 2 + (int64_t)p->head_dim * 2;
@@ -1314,71 +1242,210 @@ int mla_sparse_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, V
   return FFPA_OK;
 }
 
-// The tree-mask latent call (ffpa_attn_varlen_mla_tree_fwd): the latent call's plan UNDER THE CAUSAL FLAG (whatever p->causal says: the tree launch walks the causal
-// launch's tiles), the latent call's checks, then the tree call's check of its mask; the launch takes the tree build of the pair the latent call would take.
-const MlaEntry kMlaTreeBuilds[] = {
-#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_tree_d##D},
-    FFPA_FOR_EACH_MLA_BUILD(FFPA_ROW)
-#undef FFPA_ROW
+// ---- The host layer of the packed call and its relatives: a call is DESCRIBED (VarlenCall), PLANNED (plan_call -> CallPlan) and LAUNCHED from its plan
+// (varlen_launch); the plan / kernel / workspace / compact-slots queries are the first two steps and a read-out.
+//
+// What the caller passed, and WHICH call it is.  The tag says the family, never a NULL pointer: a family that needs a struct reports its absence (check_paged,
+// check_tree, check_window, check_mla, check_sparse), it does not turn into another call.
+enum class Family {
+  kPacked,   // ffpa_attn_varlen_fwd: cu_seqlens over contiguous K / V
+  kPaged,    // ffpa_attn_varlen_paged_fwd: kv (required) — k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read
+  kTree,     // ffpa_attn_varlen_tree_fwd: tree; kv optional (NULL: contiguous caches) — the causal launch's plan and tile walk, the *_tree_kernel builds
+  kWindow,   // ffpa_attn_varlen_window_fwd: win; kv optional — the window's own plan, the *_window_kernel builds
+  kSoftcap,  // ffpa_attn_varlen_softcap_fwd: softcap; win optional (NULL: (-1, -1)), kv optional — a window launch with capped scores, the *_softcap_kernel builds
+  kMla,      // ffpa_attn_varlen_mla_fwd: kv, mla — k is the latent pool and serves as v too (p->v is not read); its own plan and kernel, the append in front
+  kMlaTree,  // ffpa_attn_varlen_mla_tree_fwd: kv, mla, tree — the latent launch under the causal flag, the tree build of its kernel
+  kSparse,   // ffpa_attn_varlen_mla_sparse_fwd: sparse — a latent launch without a page pool: the index list stands where the block table stood
 };
+bool is_tree(Family f) { return f == Family::kTree || f == Family::kMlaTree; }
+bool is_window(Family f) { return f == Family::kWindow || f == Family::kSoftcap; }
 
-struct MlaTreePlan {
-  ffpa_varlen_fwd_params priced;  // the caller's params under the causal flag
-  const MlaEntry* build;
+struct VarlenCall {
+  Family family;
+  const ffpa_varlen_fwd_params* p;
+  const ffpa_paged_kv* kv;
+  const ffpa_tree_mask* tree;
+  const ffpa_window* win;
+  float softcap;
+  const ffpa_mla* mla;
+  const ffpa_mla_sparse* sparse;
 };
-
-int mla_tree_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, VarlenPlan* pl, MlaTreePlan* tp) {
-  if (p != nullptr && p->struct_size == sizeof(ffpa_varlen_fwd_params)) {  // (anything else: varlen_plan refuses it by name)
-    tp->priced = *p;
-    tp->priced.causal = 1;
-    p = &tp->priced;
-  }
-  const MlaEntry* dense = nullptr;
-  int rc = mla_plan(p, kv, m, pl, &dense);
-  if (rc != FFPA_OK) return rc;
-  if ((rc = check_tree(p, tree)) != FFPA_OK) return rc;
-  tp->build = &kMlaTreeBuilds[dense - kMlaBuilds];
-  return FFPA_OK;
+typedef const ffpa_varlen_fwd_params* ParamsPtr;
+VarlenCall make_call(Family family, ParamsPtr p, const ffpa_paged_kv* kv) {
+  VarlenCall c = {};
+  c.family = family, c.p = p, c.kv = kv;
+  return c;
+}
+VarlenCall packed_call(ParamsPtr p) { return make_call(Family::kPacked, p, nullptr); }
+VarlenCall paged_call(ParamsPtr p, const ffpa_paged_kv* kv) { return make_call(Family::kPaged, p, kv); }
+VarlenCall tree_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree) {
+  VarlenCall c = make_call(Family::kTree, p, kv);
+  c.tree = tree;
+  return c;
+}
+VarlenCall window_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_window* w) {
+  VarlenCall c = make_call(Family::kWindow, p, kv);
+  c.win = w;
+  return c;
+}
+VarlenCall softcap_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap) {
+  VarlenCall c = make_call(Family::kSoftcap, p, kv);
+  c.win = w, c.softcap = softcap;
+  return c;
+}
+VarlenCall mla_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m) {
+  VarlenCall c = make_call(Family::kMla, p, kv);
+  c.mla = m;
+  return c;
+}
+VarlenCall mla_tree_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree) {
+  VarlenCall c = make_call(Family::kMlaTree, p, kv);
+  c.mla = m, c.tree = tree;
+  return c;
+}
+VarlenCall sparse_call(ParamsPtr p, const ffpa_mla_sparse* s) {
+  VarlenCall c = make_call(Family::kSparse, p, nullptr);
+  c.sparse = s;
+  return c;
 }
 
-// The packed call and its paged twin (kv != NULL: k / v are page pools, the lengths are seqused_kv's, cu_seqlens_kv is not read); `tree`: under a tree mask
-// (ffpa_attn_varlen_tree_fwd — the causal launch's plan and tile walk; the *_tree_kernel builds, whose element test reads the mask words); `win`: under a sliding
-// window (ffpa_attn_varlen_window_fwd — the window's own plan; the *_window_kernel builds); `softcap` > 0: a window launch with capped scores
-// (ffpa_attn_varlen_softcap_fwd — the same plan; the *_softcap_kernel builds)
-int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream, const ffpa_tree_mask* tree = nullptr, bool with_tree = false,
-                  const ffpa_window* win = nullptr, bool with_win = false, float softcap = 0.f, const ffpa_mla* mla = nullptr, bool with_mla = false,
-                  const ffpa_mla_sparse* sparse = nullptr, bool with_sparse = false) {
-  // (`mla`: the latent-cache call, ffpa_attn_varlen_mla_fwd — k is the latent pool and serves as v too, p->v is not read; its own plan and kernel; the append in front)
-  // (`sparse`: the sparse latent call, ffpa_attn_varlen_mla_sparse_fwd — a latent launch without a page pool: the index list stands where the block table stood)
-  // (`mla` and `tree` together: the tree-mask latent call, ffpa_attn_varlen_mla_tree_fwd — the latent launch under the causal flag, the tree build of its kernel)
-  const bool paged = kv != nullptr || with_sparse;
+// What plan_call makes of a call: everything the launch and the queries read.  (It points into itself: made in place, never copied.)
+struct CallPlan {
   VarlenPlan pl;
-  WindowPlan wp;
-  SparsePlan sp;
-  MlaTreePlan tp;
-  const MlaEntry* mb = nullptr;
-  const bool mla_tree = with_mla && with_tree;
-  int rc = with_sparse ? mla_sparse_plan(p, sparse, &pl, &sp)
-           : mla_tree  ? mla_tree_plan(p, kv, mla, tree, &pl, &tp)
-           : with_mla  ? mla_plan(p, kv, mla, &pl, &mb)
-           : with_win  ? window_plan(p, kv, win, &pl, &wp)
-                       : varlen_plan(p, &pl, paged);
+  const ffpa_varlen_fwd_params* p;  // the params the launch runs under: the caller's, or `priced`
+  ffpa_varlen_fwd_params priced;    // the family's copy of the caller's params (price_window, price_sparse; the tree latent call: under the causal flag)
+  int win_causal, win_right, win_span;  // a window launch: it runs under the causal flag (right >= 0: `right` rides in the causal limit); VarlenArgs::win_right / win_span
+  const ffpa_mla* mla;              // a latent launch: the caller's ffpa_mla or — the sparse call — `own_mla`; NULL: a launch over a K and a V cache
+  ffpa_mla own_mla;
+  mla_fn launch_mla;                // ... and the build of the latent kernel it launches
+};
+
+// The window call's plan is the packed call's, PRICED AT WHAT THE WINDOW LEAVES.  A row tile of R token rows (all max_seqlen_q tokens under GQA row packing, else
+// the block rows) walks the keys from its first row's left bound to its last row's right bound — R + left + right of them, and never more than left +
+// max_seqlen_q (the last key is the right bound of the last token) — so the split count ("fill the chip, then balance") and the non-temporal fetch ("K / V bytes
+// with one reader, larger than the Infinity Cache") see that many keys, rounded up to a KV tile, and not the cache's capacity.  No left bound: the caller's
+// max_seqlen_kv.  `left` / `right` at or past the longest sequence are the unbounded side they amount to (they reach the kernel as small ints).
+// `pl`: the plan of the caller's own params (its tile rows and GQA packing do not depend on max_seqlen_kv).  The launch runs under the priced copy: the caller's params but
+// for the causal flag and the length the plan saw; the kernel reads every sequence's own length.
+void price_window(const ffpa_varlen_fwd_params* p, const ffpa_window* w, const VarlenPlan& pl, CallPlan* cp) {
+  int64_t right = p->causal ? 0 : w->right;
+  if (right > p->max_seqlen_q) right = p->max_seqlen_q;  // (the last token's position + max_seqlen_q - 1 is already the last key)
+  int64_t left = w->left;
+  if (left >= p->max_seqlen_kv) left = -1;  // (no position reaches that far back: positions are below max_seqlen_kv)
+  cp->win_causal = right >= 0 ? 1 : 0;
+  cp->win_right = right >= 0 ? (int)right : 0;
+  cp->win_span = left >= 0 ? (int)(left + cp->win_right) : -1;
+  cp->priced = *p;
+  cp->priced.causal = cp->win_causal;
+  if (left >= 0) {
+    const int64_t rows = pl.pack || p->max_seqlen_q < pl.br ? p->max_seqlen_q : pl.br;
+    int64_t tail = right >= 0 ? rows + right : (int64_t)p->max_seqlen_q;
+    if (tail > p->max_seqlen_q) tail = p->max_seqlen_q;
+    const int64_t keys = (left + tail + pl.bc - 1) / pl.bc * pl.bc;
+    if (keys < p->max_seqlen_kv) cp->priced.max_seqlen_kv = (int)keys;
+  }
+  cp->p = &cp->priced;
+}
+
+// The sparse call's plan is the latent call's for a batch of T one-token sequences of topk keys ("fill the chip, then balance", the one-reader rule of the NT build,
+// the row chunks of a group wider than the tile; a uniform batch never meets the compact grid): the caller's params as the latent launch reads them — the pool's
+// strides, the counts as lengths — and an ffpa_mla of its own (head_dim_v; nothing is appended).
+void price_sparse(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, CallPlan* cp) {
+  cp->priced = *p;
+  cp->priced.causal = 0;  // (the indexer has chosen visible keys)
+  cp->priced.max_seqlen_kv = s->topk;
+  cp->priced.k_stride[0] = s->kv_stride[0], cp->priced.k_stride[1] = s->kv_stride[1];
+  cp->priced.seqused_kv = s->topk_lens;
+  memset(&cp->own_mla, 0, sizeof(cp->own_mla));
+  cp->own_mla.struct_size = (uint32_t)sizeof(ffpa_mla);
+  cp->own_mla.head_dim_v = s->head_dim_v;
+  cp->p = &cp->priced;
+  cp->mla = &cp->own_mla;
+}
+
+// EVERY check of a call that precedes the device, family by family and in the family's order — this is the one place where that order is written down — and the
+// plan the launch and the queries read.  The words it is written in: varlen_plan (validates the params it is given and plans them; `paged`: 64-key tiles where the
+// packed kernel takes 128; `mla`: every group packed into rows), check_paged, check_tree, check_window, check_softcap, check_mla, check_sparse / check_sparse_pool.
+int plan_call(const VarlenCall& c, CallPlan* cp) {
+  const ffpa_varlen_fwd_params* p = c.p;
+  VarlenPlan* pl = &cp->pl;
+  const MlaBuild* build = nullptr;
+  const bool paged = c.kv != nullptr;
+  int rc;
+  cp->p = p;
+  cp->win_causal = cp->win_right = cp->win_span = 0;
+  cp->mla = nullptr;
+  cp->launch_mla = nullptr;
+  switch (c.family) {
+    case Family::kPacked:
+      return varlen_plan(p, pl);
+    case Family::kPaged:
+      if ((rc = varlen_plan(p, pl, true)) != FFPA_OK) return rc;
+      return check_paged(p, c.kv);
+    case Family::kTree:
+      if ((rc = varlen_plan(p, pl, paged)) != FFPA_OK) return rc;
+      if (paged && (rc = check_paged(p, c.kv)) != FFPA_OK) return rc;
+      return check_tree(p, c.tree);
+    case Family::kSoftcap:  // the window call behind the cap's own check; no window = (-1, -1)
+    case Family::kWindow: {
+      if (c.family == Family::kSoftcap && (rc = check_softcap(c.softcap)) != FFPA_OK) return rc;
+      const ffpa_window* w = c.family == Family::kSoftcap ? softcap_window(c.win) : c.win;
+      if ((rc = varlen_plan(p, pl, paged)) != FFPA_OK) return rc;  // (errors are those of the caller's params; price_window reads this plan's tile)
+      if (paged && (rc = check_paged(p, c.kv)) != FFPA_OK) return rc;
+      if ((rc = check_window(w)) != FFPA_OK) return rc;
+      price_window(p, w, *pl, cp);
+      return varlen_plan(cp->p, pl, paged);
+    }
+    case Family::kMlaTree:  // the latent call UNDER THE CAUSAL FLAG, whatever p->causal says (the tree launch walks the causal launch's tiles), then the mask
+      if (p != nullptr && p->struct_size == sizeof(ffpa_varlen_fwd_params)) {  // (anything else: varlen_plan refuses it by name)
+        cp->priced = *p;
+        cp->priced.causal = 1;
+        cp->p = p = &cp->priced;
+      }
+      [[fallthrough]];
+    case Family::kMla:
+      if ((rc = varlen_plan(p, pl, true, true)) != FFPA_OK) return rc;
+      if ((rc = check_paged(p, c.kv)) != FFPA_OK) return rc;
+      if ((rc = check_mla(p, c.mla, &build)) != FFPA_OK) return rc;
+      if (c.family == Family::kMlaTree && (rc = check_tree(p, c.tree)) != FFPA_OK) return rc;
+      cp->mla = c.mla;
+      cp->launch_mla = c.family == Family::kMlaTree ? build->tree : build->latent;
+      return FFPA_OK;
+    case Family::kSparse:
+      if ((rc = check_sparse(p, c.sparse)) != FFPA_OK) return rc;
+      price_sparse(p, c.sparse, cp);
+      if ((rc = varlen_plan(cp->p, pl, true, true)) != FFPA_OK) return rc;
+      if ((rc = check_mla(cp->p, cp->mla, &build)) != FFPA_OK) return rc;
+      if ((rc = check_sparse_pool(p, c.sparse)) != FFPA_OK) return rc;
+      cp->launch_mla = build->sparse;
+      return FFPA_OK;
+  }
+  return fail(FFPA_ERR_UNSUPPORTED, "unknown call family %d", (int)c.family);
+}
+
+// Plan the call, then launch the plan: the checks every family shares (in front of the device), the argument blocks, the append in front of a latent launch, the
+// kernel, the merge behind a split one.
+int varlen_launch(const VarlenCall& c, void* stream) {
+  CallPlan cp;
+  int rc = plan_call(c, &cp);
   if (rc != FFPA_OK) return rc;
-  if (with_win) p = &wp.priced;  // (the caller's params but for the causal flag and the length the plan saw; the kernel reads every sequence's own length)
-  if (with_sparse) p = &sp.priced, mla = &sp.mla, mb = sp.build, with_mla = true;
-  if (mla_tree) p = &tp.priced, mb = tp.build;  // (its plan has checked the pool and the mask)
-  if (paged && !with_sparse && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
-  if (with_tree && !mla_tree && (rc = check_tree(p, tree)) != FFPA_OK) return rc;
-  if (!p->q || !p->k || (!with_mla && !p->v) || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
+  const ffpa_varlen_fwd_params* p = cp.p;
+  const VarlenPlan& pl = cp.pl;
+  const ffpa_paged_kv* kv = c.kv;
+  const ffpa_mla* mla = cp.mla;
+  const ffpa_mla_sparse* sparse = c.family == Family::kSparse ? c.sparse : nullptr;
+  const bool latent = mla != nullptr;                   // k is the one cache: it serves as v too, p->v is not read
+  const bool paged = kv != nullptr || sparse != nullptr;  // the keys are found through a table: cu_seqlens_kv is not read
+  if (!p->q || !p->k || (!latent && !p->v) || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
   if (!p->cu_seqlens_q || (!paged && !p->cu_seqlens_kv)) return fail(FFPA_ERR_NULL_POINTER, "cu_seqlens_q / cu_seqlens_kv must be non-NULL");
   if ((reinterpret_cast<uintptr_t>(p->cu_seqlens_q) & 3u) || (!paged && (reinterpret_cast<uintptr_t>(p->cu_seqlens_kv) & 3u)) || (reinterpret_cast<uintptr_t>(p->seqused_kv) & 3u))
     return fail(FFPA_ERR_MISALIGNED, "cu_seqlens_q / cu_seqlens_kv / seqused_kv must be 4-byte aligned");
-  if (!aligned16(p->q) || !aligned16(p->k) || (!with_mla && !aligned16(p->v)) || !aligned16(p->o))
+  if (!aligned16(p->q) || !aligned16(p->k) || (!latent && !aligned16(p->v)) || !aligned16(p->o))
     return fail(FFPA_ERR_MISALIGNED, "q/k/v/o base pointers must be 16-byte aligned");
-  if ((rc = check_strides("q", p->q_stride, 2)) || (rc = check_strides("k", p->k_stride, 2)) || (!with_mla && (rc = check_strides("v", p->v_stride, 2))) ||
+  if ((rc = check_strides("q", p->q_stride, 2)) || (rc = check_strides("k", p->k_stride, 2)) || (!latent && (rc = check_strides("v", p->v_stride, 2))) ||
       (rc = check_strides("o", p->o_stride, 2)))
     return rc;
-  for (const int64_t* st : {p->k_stride, with_mla ? p->k_stride : p->v_stride}) {
+  for (const int64_t* st : {p->k_stride, latent ? p->k_stride : p->v_stride}) {
     if (st[0] < p->head_dim || st[0] >= (1LL << 24))
       return fail(FFPA_ERR_BAD_STRIDE, "k/v row stride %lld: rows must not overlap and must be < 2^24 elements apart", (long long)st[0]);
   }
@@ -1392,13 +1459,13 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
   memset(&a, 0, sizeof(a));
   a.q = p->q;
   a.k = p->k;
-  a.v = with_mla ? p->k : p->v;
+  a.v = latent ? p->k : p->v;
   a.o = p->o;
   a.lse = p->lse;
   // element strides batch / head / row: a sequence's base is its row offset (the kernel adds it), so the batch stride is zero
   a.sq[1] = p->q_stride[1], a.sq[2] = p->q_stride[0];
   a.sk[1] = p->k_stride[1], a.sk[2] = p->k_stride[0];
-  a.sv[1] = (with_mla ? p->k_stride : p->v_stride)[1], a.sv[2] = (with_mla ? p->k_stride : p->v_stride)[0];
+  a.sv[1] = (latent ? p->k_stride : p->v_stride)[1], a.sv[2] = (latent ? p->k_stride : p->v_stride)[0];
   a.so[1] = p->o_stride[1], a.so[2] = p->o_stride[0];
   a.B = p->batch;
   a.Hq = p->heads_q;
@@ -1418,7 +1485,7 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
   a.tiles_per_split = 0x7fffffff / 2;  // (never the binding limit: the KV axis is not split)
   a.keep_scale = 1.f;
   // (the row tiles of a packed latent group are a decode launch's workgroups, not the rounds of a prefill head: one XCD per head)
-  a.xcd_group = pick_xcd_group(p->flags, !with_mla && (int64_t)pl.nqt * (p->heads_q / p->heads_kv) >= 64, p->max_seqlen_kv, p->head_dim);
+  a.xcd_group = pick_xcd_group(p->flags, !latent && (int64_t)pl.nqt * (p->heads_q / p->heads_kv) >= 64, p->max_seqlen_kv, p->head_dim);
   a.l2_prefetch = pick_l2_prefetch(p->flags, pl.ve->d > 512);
 
   ffpa::VarlenArgs va;
@@ -1442,26 +1509,26 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
     if (p->max_seqlen_q == 1) a.causal = 0;  // (a single token sees every key of its sequence; more tokens: the kernel sets causal_row_mod per sequence)
     va.head_chunk = 1;  // (the rows of a tile ARE the group: KV heads share nothing)
   }
-  if (with_tree) {
+  if (is_tree(c.family)) {
     // the causal launch's walk with causal_offset = Nkv_i - ntok_i (the kernel, per sequence): the last token's limit is the last key, so every tile is walked and
     // the KV ranges share out all of them; one token per sequence keeps the flag here — its word may hide its own key
     a.causal = 1;
-    va.tree_bits = tree->bits;
-    va.tree_stride = tree->batch_stride;
-    va.tree_tokens = tree->tokens;
+    va.tree_bits = c.tree->bits;
+    va.tree_stride = c.tree->batch_stride;
+    va.tree_tokens = c.tree->tokens;
   }
-  if (with_win) {
+  if (is_window(c.family)) {
     // the causal flag as the window says (right >= 0), one packed token per sequence included: its limit is the last key either way, its LEFT bound stays
-    a.causal = wp.causal;
+    a.causal = cp.win_causal;
     va.window = 1;
-    va.win_right = wp.right;
-    va.win_span = wp.span;
+    va.win_right = cp.win_right;
+    va.win_span = cp.win_span;
   }
-  if (softcap > 0.f) {
+  if (c.family == Family::kSoftcap) {
     // score = cap * tanh(|scale| q.k / cap) (the sign of the scale went into Q, a zero scale zeroes Q: fold_scale): the kernel multiplies the raw score by
     // softcap_in inside the tanh, and everything behind it — row max, exponent FMA, LSE — takes cap * log2(e) where it took scale * log2(e)
-    va.softcap_in = a.q_mode == 1 ? 1.f / softcap : fabsf(p->softmax_scale) / softcap;
-    a.scale_log2 = softcap * 1.4426950408889634f;
+    va.softcap_in = a.q_mode == 1 ? 1.f / c.softcap : fabsf(p->softmax_scale) / c.softcap;
+    a.scale_log2 = c.softcap * 1.4426950408889634f;
   }
 
   va.compact_tiles = pl.compact;
@@ -1478,7 +1545,7 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
   int st;
   if (paged) {
     ffpa::PagedArgs pa;
-    if (with_sparse) {
+    if (sparse != nullptr) {
       // a token's "block table" is its index row, its "pages" are single rows of the pool (ffpa_mla_sparse.h)
       memset(&pa, 0, sizeof(pa));
       pa.table = sparse->indices;
@@ -1490,13 +1557,13 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
       pa.table = kv->block_table;
       pa.bt_stride = kv->bt_stride;
       pa.k_page_stride = kv->k_page_stride;
-      pa.v_page_stride = with_mla ? kv->k_page_stride : kv->v_page_stride;
+      pa.v_page_stride = latent ? kv->k_page_stride : kv->v_page_stride;
       pa.cap = kv->pages_per_row * kv->page_size;
       pa.page_size = kv->page_size;
       pa.tiles_per_page = kv->page_size / pl.bc;
       pa.num_pages = kv->num_pages;
     }
-    if (with_mla) {
+    if (latent) {
       st = 0;
       if (mla->seqlen_new > 0) {
         // the step's latent rows first, ONE store per element (there is one cache), and the lengths the attention launch behind it reads
@@ -1512,16 +1579,16 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
       }
       ffpa::MlaArgs ma;
       ma.dv = mla->head_dim_v;
-      if (st == 0) st = mb->launch(p->dtype, pl.nt, a, va, pa, ma, static_cast<hipStream_t>(stream));
+      if (st == 0) st = cp.launch_mla(p->dtype, pl.nt, a, va, pa, ma, static_cast<hipStream_t>(stream));
     } else {
-      st = kPagedDims[pl.ve - kVarlenDims](p->dtype, pl.nt, a, va, pa, static_cast<hipStream_t>(stream));
+      st = pl.ve->paged(p->dtype, pl.nt, a, va, pa, static_cast<hipStream_t>(stream));
     }
   } else {
     st = pl.ve->launch(p->dtype, pl.nt, a, va, static_cast<hipStream_t>(stream));
   }
   if (st == 0 && pl.splits > 1) {
     // (the latent-cache call: the partials keep all D columns, the merge stores the value columns — its column bound is d_valid)
-    if (with_mla) a.d_valid = mla->head_dim_v;
+    if (latent) a.d_valid = mla->head_dim_v;
     const dim3 grid((unsigned)((int64_t)p->heads_q * p->total_q), (unsigned)(a.d_valid + 255) / 256);
     st = ffpa::dispatch_dtype(p->dtype, [&](auto t) {
       using T = typename decltype(t)::type;
@@ -1532,301 +1599,160 @@ int varlen_launch(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void
   return launch_status(st, -1, 0);
 }
 
-}  // namespace
-
-int ffpa_attn_varlen_fwd(const ffpa_varlen_fwd_params* p, void* stream) { return varlen_launch(p, nullptr, stream); }
-
-namespace {
-
-int plan_out(const VarlenPlan& pl, int out[5]) {
+// ---- The queries of a call, one helper per kind: plan the call, check the output argument, read the plan out.
+int call_plan(const VarlenCall& c, int out[5]) {
+  CallPlan cp;
+  const int rc = plan_call(c, &cp);
+  if (rc != FFPA_OK) return rc;
   if (out == nullptr) return fail(FFPA_ERR_NULL_POINTER, "out is NULL");
-  out[0] = pl.nqt;
-  out[1] = pl.br;
-  out[2] = pl.bc;
-  out[3] = (int)pl.grid;
-  out[4] = pl.splits;
+  out[0] = cp.pl.nqt;
+  out[1] = cp.pl.br;
+  out[2] = cp.pl.bc;
+  out[3] = (int)cp.pl.grid;
+  out[4] = cp.pl.splits;
   return FFPA_OK;
 }
 
-size_t workspace_bytes(const ffpa_varlen_fwd_params* params, bool paged) {
-  if (params == nullptr || params->struct_size != sizeof(ffpa_varlen_fwd_params)) return 0;
-  // size for the split count the heuristic would pick with unlimited scratch
-  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*params);
-  VarlenPlan pl;
-  if (varlen_plan(&q, &pl, paged) != FFPA_OK) return 0;
-  return pl.ws_bytes;
+// The scratch of the split count the heuristic would pick with unlimited scratch; 0 for arguments the call's plan refuses (the launch refuses them too, with the
+// plan's status and message, whether or not it was handed scratch).
+size_t call_workspace_bytes(VarlenCall c) {
+  if (c.p == nullptr || c.p->struct_size != sizeof(ffpa_varlen_fwd_params)) return 0;
+  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*c.p);
+  c.p = &q;
+  CallPlan cp;
+  return plan_call(c, &cp) == FFPA_OK ? cp.pl.ws_bytes : 0;
 }
 
-int kernel_name(const ffpa_varlen_fwd_params* params, const VarlenPlan& pl, bool paged, char* buf, size_t n, bool tree = false, bool window = false, bool softcap = false) {
+int call_kernel(const VarlenCall& c, char* buf, size_t n) {
+  CallPlan cp;
+  const int rc = plan_call(c, &cp);
+  if (rc != FFPA_OK) return rc;
   if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
-  snprintf(buf, n, "ffpa_fwd_m16_%s%s_kernel<%s, %d%s>%s%s", paged ? "paged" : "varlen", tree ? "_tree" : softcap ? "_softcap" : window ? "_window" : "", params->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d,
-           pl.nt ? ", NT" : "", pl.pack ? " (GQA heads packed into rows)" : "", pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
+  const VarlenPlan& pl = cp.pl;
+  const char* nt = pl.nt ? ", NT" : "";
+  const char* merge = pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "";
+  if (cp.mla != nullptr) {
+    // (a latent call's name is formatted from the caller's params; the sparse call — a uniform batch — has never named the compact grid)
+    const char* kind = c.family == Family::kSparse ? "_sparse" : c.family == Family::kMlaTree ? "_tree" : "";
+    snprintf(buf, n, "ffpa_fwd_m16_mla%s_kernel<%s, %d, dv=%d%s>%s%s%s", kind, c.p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", c.p->head_dim, cp.mla->head_dim_v, nt,
+             pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "",
+             pl.compact > 0 && c.family != Family::kSparse ? " (compact grid)" : "", merge);
+  } else {
+    // (a window / soft-cap call's name is formatted from the priced params)
+    const char* kind = is_tree(c.family) ? "_tree" : c.family == Family::kSoftcap ? "_softcap" : c.family == Family::kWindow ? "_window" : "";
+    snprintf(buf, n, "ffpa_fwd_m16_%s%s_kernel<%s, %d%s>%s%s", c.kv != nullptr ? "paged" : "varlen", kind, cp.p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d, nt,
+             pl.pack ? " (GQA heads packed into rows)" : "", merge);
+  }
+  return FFPA_OK;
+}
+
+int call_compact_slots(const VarlenCall& c, int* slots) {
+  CallPlan cp;
+  const int rc = plan_call(c, &cp);
+  if (rc != FFPA_OK) return rc;
+  if (slots == nullptr) return fail(FFPA_ERR_NULL_POINTER, "slots is NULL");
+  *slots = cp.pl.compact;
   return FFPA_OK;
 }
 
 }  // namespace
 
-int ffpa_attn_varlen_fwd_plan(const ffpa_varlen_fwd_params* params, int out[5]) {
-  VarlenPlan pl;
-  const int rc = varlen_plan(params, &pl);
-  if (rc != FFPA_OK) return rc;
-  return plan_out(pl, out);
-}
-
-size_t ffpa_attn_varlen_fwd_workspace_bytes(const ffpa_varlen_fwd_params* params) { return workspace_bytes(params, false); }
-
-int ffpa_attn_varlen_fwd_kernel(const ffpa_varlen_fwd_params* params, char* buf, size_t n) {
-  VarlenPlan pl;
-  const int rc = varlen_plan(params, &pl);
-  if (rc != FFPA_OK) return rc;
-  return kernel_name(params, pl, false, buf, n);
-}
+// ---- packed sequences
+int ffpa_attn_varlen_fwd(const ffpa_varlen_fwd_params* p, void* stream) { return varlen_launch(packed_call(p), stream); }
+int ffpa_attn_varlen_fwd_plan(const ffpa_varlen_fwd_params* p, int out[5]) { return call_plan(packed_call(p), out); }
+int ffpa_attn_varlen_fwd_kernel(const ffpa_varlen_fwd_params* p, char* buf, size_t n) { return call_kernel(packed_call(p), buf, n); }
+size_t ffpa_attn_varlen_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p) { return call_workspace_bytes(packed_call(p)); }
 
 // ---- the paged-KV twin (include/ffpa_attn.h: ffpa_paged_kv)
 int ffpa_attn_varlen_paged_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, void* stream) {
-  if (kv == nullptr) return fail(FFPA_ERR_NULL_POINTER, "paged kv is NULL");
-  return varlen_launch(p, kv, stream);
+  if (kv == nullptr) return fail(FFPA_ERR_NULL_POINTER, "paged kv is NULL");  // (this export alone names a missing pool before anything about the params)
+  return varlen_launch(paged_call(p, kv), stream);
 }
-
-size_t ffpa_attn_varlen_paged_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv) {
-  if (kv == nullptr || kv->struct_size != sizeof(ffpa_paged_kv)) return 0;
-  return workspace_bytes(p, true);
-}
-
-int ffpa_attn_varlen_paged_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, int out[5]) {
-  VarlenPlan pl;
-  int rc = varlen_plan(p, &pl, true);
-  if (rc != FFPA_OK) return rc;
-  if ((rc = check_paged(p, kv)) != FFPA_OK) return rc;
-  return plan_out(pl, out);
-}
-
-int ffpa_attn_varlen_paged_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, char* buf, size_t n) {
-  VarlenPlan pl;
-  int rc = varlen_plan(p, &pl, true);
-  if (rc != FFPA_OK) return rc;
-  if ((rc = check_paged(p, kv)) != FFPA_OK) return rc;
-  return kernel_name(p, pl, true, buf, n);
-}
+int ffpa_attn_varlen_paged_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, int out[5]) { return call_plan(paged_call(p, kv), out); }
+int ffpa_attn_varlen_paged_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, char* buf, size_t n) { return call_kernel(paged_call(p, kv), buf, n); }
+size_t ffpa_attn_varlen_paged_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv) { return call_workspace_bytes(paged_call(p, kv)); }
 
 // ---- the tree-mask call (include/ffpa_attn.h: ffpa_tree_mask): the packed call or its paged twin, the causal launch's plan
 int ffpa_attn_varlen_tree_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, void* stream) {
-  return varlen_launch(p, kv, stream, tree, true);
+  return varlen_launch(tree_call(p, kv, tree), stream);
 }
-
-namespace {
-
-int tree_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, VarlenPlan* pl) {
-  int rc = varlen_plan(p, pl, kv != nullptr);
-  if (rc != FFPA_OK) return rc;
-  if (kv != nullptr && (rc = check_paged(p, kv)) != FFPA_OK) return rc;
-  return check_tree(p, tree);
-}
-
-}  // namespace
-
-size_t ffpa_attn_varlen_tree_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree) {
-  if (tree == nullptr || tree->struct_size != sizeof(ffpa_tree_mask) || (kv != nullptr && kv->struct_size != sizeof(ffpa_paged_kv))) return 0;
-  return workspace_bytes(p, kv != nullptr);
-}
-
 int ffpa_attn_varlen_tree_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, int out[5]) {
-  VarlenPlan pl;
-  const int rc = tree_plan(p, kv, tree, &pl);
-  if (rc != FFPA_OK) return rc;
-  return plan_out(pl, out);
+  return call_plan(tree_call(p, kv, tree), out);
 }
-
 int ffpa_attn_varlen_tree_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree, char* buf, size_t n) {
-  VarlenPlan pl;
-  const int rc = tree_plan(p, kv, tree, &pl);
-  if (rc != FFPA_OK) return rc;
-  return kernel_name(p, pl, kv != nullptr, buf, n, true);
+  return call_kernel(tree_call(p, kv, tree), buf, n);
+}
+size_t ffpa_attn_varlen_tree_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_tree_mask* tree) {
+  return call_workspace_bytes(tree_call(p, kv, tree));
 }
 
-// ---- the sliding-window call (include/ffpa_attn.h: ffpa_window): the packed call or its paged twin, planned at the window's length (window_plan)
+// ---- the sliding-window call (include/ffpa_attn.h: ffpa_window): the packed call or its paged twin, planned at the window's length (price_window)
 int ffpa_attn_varlen_window_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, void* stream) {
-  return varlen_launch(p, kv, stream, nullptr, false, w, true);
+  return varlen_launch(window_call(p, kv, w), stream);
 }
-
-size_t ffpa_attn_varlen_window_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w) {
-  if (p == nullptr || p->struct_size != sizeof(ffpa_varlen_fwd_params) || w == nullptr || w->struct_size != sizeof(ffpa_window) ||
-      (kv != nullptr && kv->struct_size != sizeof(ffpa_paged_kv)))
-    return 0;
-  // size for the split count the heuristic would pick with unlimited scratch
-  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*p);
-  VarlenPlan pl;
-  WindowPlan wp;
-  if (window_plan(&q, kv, w, &pl, &wp) != FFPA_OK) return 0;
-  return pl.ws_bytes;
-}
-
 int ffpa_attn_varlen_window_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, int out[5]) {
-  VarlenPlan pl;
-  WindowPlan wp;
-  const int rc = window_plan(p, kv, w, &pl, &wp);
-  if (rc != FFPA_OK) return rc;
-  return plan_out(pl, out);
+  return call_plan(window_call(p, kv, w), out);
 }
-
 int ffpa_attn_varlen_window_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, char* buf, size_t n) {
-  VarlenPlan pl;
-  WindowPlan wp;
-  const int rc = window_plan(p, kv, w, &pl, &wp);
-  if (rc != FFPA_OK) return rc;
-  return kernel_name(&wp.priced, pl, kv != nullptr, buf, n, false, true);
+  return call_kernel(window_call(p, kv, w), buf, n);
+}
+size_t ffpa_attn_varlen_window_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w) {
+  return call_workspace_bytes(window_call(p, kv, w));
 }
 
 // ---- the soft-capping call (include/ffpa_attn.h): the window call — its checks, its plan; w == NULL = (-1, -1) — with capped scores
 int ffpa_attn_varlen_softcap_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap, void* stream) {
-  const int rc = check_softcap(softcap);
-  if (rc != FFPA_OK) return rc;
-  return varlen_launch(p, kv, stream, nullptr, false, softcap_window(w), true, softcap);
+  return varlen_launch(softcap_call(p, kv, w, softcap), stream);
 }
-
-size_t ffpa_attn_varlen_softcap_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap) {
-  if (check_softcap(softcap) != FFPA_OK) return 0;
-  return ffpa_attn_varlen_window_fwd_workspace_bytes(p, kv, softcap_window(w));
-}
-
 int ffpa_attn_varlen_softcap_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap, int out[5]) {
-  const int rc = check_softcap(softcap);
-  if (rc != FFPA_OK) return rc;
-  return ffpa_attn_varlen_window_fwd_plan(p, kv, softcap_window(w), out);
+  return call_plan(softcap_call(p, kv, w, softcap), out);
 }
-
 int ffpa_attn_varlen_softcap_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap, char* buf, size_t n) {
-  VarlenPlan pl;
-  WindowPlan wp;
-  int rc = check_softcap(softcap);
-  if (rc != FFPA_OK) return rc;
-  if ((rc = window_plan(p, kv, softcap_window(w), &pl, &wp)) != FFPA_OK) return rc;
-  return kernel_name(&wp.priced, pl, kv != nullptr, buf, n, false, true, true);
+  return call_kernel(softcap_call(p, kv, w, softcap), buf, n);
+}
+size_t ffpa_attn_varlen_softcap_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_window* w, float softcap) {
+  return call_workspace_bytes(softcap_call(p, kv, w, softcap));
 }
 
 // ---- the MLA latent-cache call (include/ffpa_attn.h: ffpa_mla): the paged call on ONE pool, every group packed into rows, the append in front
 int ffpa_attn_varlen_mla_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, void* stream) {
-  return varlen_launch(p, kv, stream, nullptr, false, nullptr, false, 0.f, m, true);
+  return varlen_launch(mla_call(p, kv, m), stream);
 }
-
-size_t ffpa_attn_varlen_mla_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m) {
-  if (p == nullptr || p->struct_size != sizeof(ffpa_varlen_fwd_params) || kv == nullptr || kv->struct_size != sizeof(ffpa_paged_kv) || m == nullptr ||
-      m->struct_size != sizeof(ffpa_mla))
-    return 0;
-  // size for the split count the heuristic would pick with unlimited scratch
-  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*p);
-  VarlenPlan pl;
-  if (mla_plan(&q, kv, m, &pl) != FFPA_OK) return 0;
-  return pl.ws_bytes;
-}
-
-int ffpa_attn_varlen_mla_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int out[5]) {
-  VarlenPlan pl;
-  const int rc = mla_plan(p, kv, m, &pl);
-  if (rc != FFPA_OK) return rc;
-  return plan_out(pl, out);
-}
-
+int ffpa_attn_varlen_mla_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int out[5]) { return call_plan(mla_call(p, kv, m), out); }
 int ffpa_attn_varlen_mla_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, char* buf, size_t n) {
-  VarlenPlan pl;
-  const int rc = mla_plan(p, kv, m, &pl);
-  if (rc != FFPA_OK) return rc;
-  if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
-  snprintf(buf, n, "ffpa_fwd_m16_mla_kernel<%s, %d, dv=%d%s>%s%s%s", p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", p->head_dim, m->head_dim_v, pl.nt ? ", NT" : "",
-           pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "", pl.compact > 0 ? " (compact grid)" : "",
-           pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
-  return FFPA_OK;
+  return call_kernel(mla_call(p, kv, m), buf, n);
 }
-
+size_t ffpa_attn_varlen_mla_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m) {
+  return call_workspace_bytes(mla_call(p, kv, m));
+}
 int ffpa_attn_varlen_mla_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int* slots) {
-  VarlenPlan pl;
-  const int rc = mla_plan(p, kv, m, &pl);
-  if (rc != FFPA_OK) return rc;
-  if (slots == nullptr) return fail(FFPA_ERR_NULL_POINTER, "slots is NULL");
-  *slots = pl.compact;
-  return FFPA_OK;
+  return call_compact_slots(mla_call(p, kv, m), slots);
 }
 
 // ---- the tree-mask latent call (include/ffpa_attn.h): the latent launch under the causal flag, the element test of the draft tiles reads the mask words
 int ffpa_attn_varlen_mla_tree_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, void* stream) {
-  return varlen_launch(p, kv, stream, tree, true, nullptr, false, 0.f, m, true);
+  return varlen_launch(mla_tree_call(p, kv, m, tree), stream);
 }
-
-size_t ffpa_attn_varlen_mla_tree_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree) {
-  if (p == nullptr || p->struct_size != sizeof(ffpa_varlen_fwd_params) || kv == nullptr || kv->struct_size != sizeof(ffpa_paged_kv) || m == nullptr ||
-      m->struct_size != sizeof(ffpa_mla) || tree == nullptr || tree->struct_size != sizeof(ffpa_tree_mask))
-    return 0;
-  // size for the split count the heuristic would pick with unlimited scratch
-  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*p);
-  VarlenPlan pl;
-  MlaTreePlan tp;
-  if (mla_tree_plan(&q, kv, m, tree, &pl, &tp) != FFPA_OK) return 0;
-  return pl.ws_bytes;
-}
-
 int ffpa_attn_varlen_mla_tree_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, int out[5]) {
-  VarlenPlan pl;
-  MlaTreePlan tp;
-  const int rc = mla_tree_plan(p, kv, m, tree, &pl, &tp);
-  if (rc != FFPA_OK) return rc;
-  return plan_out(pl, out);
+  return call_plan(mla_tree_call(p, kv, m, tree), out);
 }
-
 int ffpa_attn_varlen_mla_tree_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, char* buf, size_t n) {
-  VarlenPlan pl;
-  MlaTreePlan tp;
-  const int rc = mla_tree_plan(p, kv, m, tree, &pl, &tp);
-  if (rc != FFPA_OK) return rc;
-  if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
-  snprintf(buf, n, "ffpa_fwd_m16_mla_tree_kernel<%s, %d, dv=%d%s>%s%s%s", p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", p->head_dim, m->head_dim_v, pl.nt ? ", NT" : "",
-           pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "", pl.compact > 0 ? " (compact grid)" : "",
-           pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
-  return FFPA_OK;
+  return call_kernel(mla_tree_call(p, kv, m, tree), buf, n);
 }
-
+size_t ffpa_attn_varlen_mla_tree_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree) {
+  return call_workspace_bytes(mla_tree_call(p, kv, m, tree));
+}
 int ffpa_attn_varlen_mla_tree_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, int* slots) {
-  VarlenPlan pl;
-  MlaTreePlan tp;
-  const int rc = mla_tree_plan(p, kv, m, tree, &pl, &tp);
-  if (rc != FFPA_OK) return rc;
-  if (slots == nullptr) return fail(FFPA_ERR_NULL_POINTER, "slots is NULL");
-  *slots = pl.compact;
-  return FFPA_OK;
+  return call_compact_slots(mla_tree_call(p, kv, m, tree), slots);
 }
 
 // ---- the sparse latent call (include/ffpa_attn.h: ffpa_mla_sparse): the latent launch over per-token index lists
-int ffpa_attn_varlen_mla_sparse_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream) {
-  return varlen_launch(p, nullptr, stream, nullptr, false, nullptr, false, 0.f, nullptr, false, s, true);
-}
-
-size_t ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
-  if (p == nullptr || p->struct_size != sizeof(ffpa_varlen_fwd_params) || s == nullptr || s->struct_size != sizeof(ffpa_mla_sparse)) return 0;
-  // size for the split count the heuristic would pick with unlimited scratch
-  const ffpa_varlen_fwd_params q = with_unlimited_scratch(*p);
-  VarlenPlan pl;
-  SparsePlan sp;
-  if (mla_sparse_plan(&q, s, &pl, &sp) != FFPA_OK) return 0;
-  return pl.ws_bytes;
-}
-
-int ffpa_attn_varlen_mla_sparse_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]) {
-  VarlenPlan pl;
-  SparsePlan sp;
-  const int rc = mla_sparse_plan(p, s, &pl, &sp);
-  if (rc != FFPA_OK) return rc;
-  return plan_out(pl, out);
-}
-
+int ffpa_attn_varlen_mla_sparse_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream) { return varlen_launch(sparse_call(p, s), stream); }
+int ffpa_attn_varlen_mla_sparse_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]) { return call_plan(sparse_call(p, s), out); }
 int ffpa_attn_varlen_mla_sparse_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n) {
-  VarlenPlan pl;
-  SparsePlan sp;
-  const int rc = mla_sparse_plan(p, s, &pl, &sp);
-  if (rc != FFPA_OK) return rc;
-  if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL");
-  snprintf(buf, n, "ffpa_fwd_m16_mla_sparse_kernel<%s, %d, dv=%d%s>%s%s", p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", p->head_dim, s->head_dim_v, pl.nt ? ", NT" : "",
-           pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "", pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "");
-  return FFPA_OK;
+  return call_kernel(sparse_call(p, s), buf, n);
 }
+size_t ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) { return call_workspace_bytes(sparse_call(p, s)); }
 
 // ---- the latent append of a ragged step (include/ffpa_attn.h: ffpa_mla_append_varlen_params): token rows packed by cu_seqlens_q into the ONE paged pool
 int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, void* stream) {

@@ -813,19 +813,28 @@ def _hand_over_workspace(p, device: torch.device, stream: int, nbytes: int) -> "
 _PLAN_SCRATCH: "dict[tuple, tuple[int, int]]" = {}
 
 
+def _cached_scratch(table: dict, key: tuple, ask):
+  """``table[key]``, or — the first call of a shape class — what ``ask()`` gets from the library; a table of 512 classes starts over."""
+  hit = table.get(key)
+  if hit is None:
+    if len(table) >= 512:
+      table.clear()
+    hit = table[key] = ask()
+  return hit
+
+
 def _plan_scratch(lib, p: "FfpaFwdParams", num_splits: int, want_tickets: bool, device_index: int) -> tuple[int, int]:
   if num_splits == 1:
     return 0, 0
   key = (id(lib), device_index, p.dtype, p.batch, p.heads_q, p.heads_kv, p.seqlen_q, p.seqlen_kv, p.head_dim, p.causal, p.bias_dtype if p.bias else 0,
          bool(p.bias) and p.bias_stride[2] == 0, p.kv_bounds is not None, p.dropout_p > 0.0, p.flags, num_splits, p.causal_row_mod, p.causal_offset, want_tickets, os.environ.get("FFPA_HIP_FAKE_CUS"))
-  hit = _PLAN_SCRATCH.get(key)
-  if hit is None:
+
+  def ask():
     ws = int(lib.ffpa_attn_fwd_workspace_bytes(ctypes.byref(p)))
     nt = int(lib.ffpa_attn_fwd_split_tickets(ctypes.byref(p))) if (ws and want_tickets and hasattr(lib, "ffpa_attn_fwd_split_tickets")) else 0
-    if len(_PLAN_SCRATCH) >= 512:
-      _PLAN_SCRATCH.clear()
-    hit = _PLAN_SCRATCH[key] = (ws, nt)
-  return hit
+    return ws, nt
+
+  return _cached_scratch(_PLAN_SCRATCH, key, ask)
 
 
 def forward(
@@ -1136,31 +1145,26 @@ def _paged_kv_of(block_table: torch.Tensor, k: torch.Tensor, v: torch.Tensor) ->
   return _paged_kv(block_table.data_ptr(), block_table.stride(0), block_table.size(1), k.size(1), k.size(0), k.stride(0), v.stride(0)), block_table
 
 
-def _varlen_fn(lib, kv: "FfpaPagedKv | None", suffix: str = "", tree: "bool | str" = False):
-  """The packed call's export — or, with ``kv``, its paged twin's; with ``tree``, the tree call's, with ``tree == "window"`` the window call's and with
-  ``tree == "softcap"`` the soft-capping call's (one export for both caches: their ``kv`` may be NULL) — of this suffix ("" the launch, "_plan", "_kernel",
-  "_workspace_bytes")"""
-  if tree:
-    return getattr(lib, {"window": "ffpa_attn_varlen_window_fwd", "softcap": "ffpa_attn_varlen_softcap_fwd"}.get(tree, "ffpa_attn_varlen_tree_fwd") + suffix)
-  return getattr(lib, ("ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd") + suffix)
+# The call families over a K and a V cache and their launch exports (the tree, window and soft-capping calls serve both caches: their ``kv`` may be NULL)
+_VARLEN_EXPORTS = {"packed": "ffpa_attn_varlen_fwd", "paged": "ffpa_attn_varlen_paged_fwd", "tree": "ffpa_attn_varlen_tree_fwd",
+                   "window": "ffpa_attn_varlen_window_fwd", "softcap": "ffpa_attn_varlen_softcap_fwd"}
+
+
+def _varlen_fn(lib, family: str, suffix: str = ""):
+  """The export of a family of ``_VARLEN_EXPORTS`` with this suffix ("" the launch, "_plan", "_kernel", "_workspace_bytes")"""
+  return getattr(lib, _VARLEN_EXPORTS[family] + suffix)
 
 
 # Scratch of a KV-split packed launch: a function of the shape class (ffpa_capi.hip varlen_plan), asked once per class
 _VARLEN_SCRATCH: "dict[tuple, int]" = {}
 
 
-def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, kv: "FfpaPagedKv | None", args: tuple, tree: "bool | str" = False,
-                    window: "tuple | None" = None) -> int:
+def _varlen_scratch(lib, p: "FfpaVarlenFwdParams", device_index: int, family: str, paged: bool, args: tuple, window: "tuple | None" = None) -> int:
   if p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC:
     return 0
   key = (id(lib), device_index, p.dtype, p.batch, p.heads_q, p.heads_kv, p.head_dim, p.max_seqlen_q, p.max_seqlen_kv, p.total_q, p.causal, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS"),
-         kv is not None, tree, window)
-  hit = _VARLEN_SCRATCH.get(key)
-  if hit is None:
-    if len(_VARLEN_SCRATCH) >= 512:
-      _VARLEN_SCRATCH.clear()
-    hit = _VARLEN_SCRATCH[key] = int(_varlen_fn(lib, kv, "_workspace_bytes", tree)(*args))
-  return hit
+         paged, {"tree": True, "window": "window", "softcap": "softcap"}.get(family, False), window)  # (the key's values are the ones it has always held)
+  return _cached_scratch(_VARLEN_SCRATCH, key, lambda: int(_varlen_fn(lib, family, "_workspace_bytes")(*args)))
 
 
 def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: "torch.Tensor | None", max_seqlen_q: int,
@@ -1203,8 +1207,8 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
   if window is not None:
     if tree:
       raise ValueError(f"ffpa_attn::{'_softcap' if capped else '_window'}_fwd_hip: a window and a tree mask do not combine")
-    tree = "softcap" if capped else "window"  # (which export family the helpers below pick)
-  name = "ffpa_attn::_softcap_fwd_hip" if capped else "ffpa_attn::_window_fwd_hip" if window is not None else "ffpa_attn::_tree_fwd_hip" if tree else "ffpa_attn::_paged_fwd_hip" if paged else "ffpa_attn::_varlen_fwd_hip"
+  family = "softcap" if capped else "window" if window is not None else "tree" if tree else "paged" if paged else "packed"  # (a key of _VARLEN_EXPORTS)
+  name = f"ffpa_attn::_{'varlen' if family == 'packed' else family}_fwd_hip"
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
@@ -1305,12 +1309,12 @@ def varlen_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens
     args = (ctypes.byref(p), ctypes.byref(kv) if paged else None, ctypes.byref(tm))
   with torch.cuda.device(q.device):
     stream = torch.cuda.current_stream(q.device).cuda_stream
-    workspace = _hand_over_workspace(p, q.device, stream, _varlen_scratch(lib, p, q.device.index or 0, kv, args, tree, window))  # (the cap changes no plan: the key needs no softcap)  # (held in a local until the launch below has been enqueued)
+    workspace = _hand_over_workspace(p, q.device, stream, _varlen_scratch(lib, p, q.device.index or 0, family, paged, args, window))  # (the cap changes no plan: the key needs no softcap)  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
-      plan_out.update(_read_plan(lib, _varlen_fn(lib, kv, "_plan", tree), _varlen_fn(lib, kv, "_kernel", tree), _VARLEN_PLAN_KEYS, args))
-    rc = _varlen_fn(lib, kv, "", tree)(*args, ctypes.c_void_p(stream))
+      plan_out.update(_read_plan(lib, _varlen_fn(lib, family, "_plan"), _varlen_fn(lib, family, "_kernel"), _VARLEN_PLAN_KEYS, args))
+    rc = _varlen_fn(lib, family)(*args, ctypes.c_void_p(stream))
   if rc != 0:
-    _raise_status(lib, rc, "ffpa_attn_varlen_softcap_fwd" if capped else "ffpa_attn_varlen_window_fwd" if window is not None else "ffpa_attn_varlen_tree_fwd" if tree else "ffpa_attn_varlen_fwd" if kv is None else "ffpa_attn_varlen_paged_fwd")
+    _raise_status(lib, rc, _VARLEN_EXPORTS[family])
   return _unpad_head_dim(o, D), lse
 
 
@@ -1370,14 +1374,14 @@ def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: in
   p.q = p.k = p.v = p.o = p.cu_seqlens_q = p.cu_seqlens_kv = 16
   if total_q > 0:
     p.workspace, p.workspace_bytes = 16, 0xFFFFFFFFFFFFFFFF
-  kv = None
+  kv, fam = None, "packed"
   args = (ctypes.byref(p),)
   if page_size:
+    fam = "paged"
     p.seqused_kv = 16
     pages_per_row = max(1, -(-int(max_seqlen_k) // int(page_size)))
     kv = _paged_kv(16, pages_per_row, pages_per_row, int(page_size), int(batch) * pages_per_row, int(page_size) * heads_kv * d8, int(page_size) * heads_kv * d8)
     args = (ctypes.byref(p), ctypes.byref(kv))
-  fam = False
   if softcap and window is None:
     window = (-1, -1)
   if window is not None:
@@ -1386,7 +1390,7 @@ def varlen_launch_plan(batch: int, heads_q: int, heads_kv: int, max_seqlen_q: in
     args, fam = (ctypes.byref(p), ctypes.byref(kv) if kv is not None else None, ctypes.byref(wn)), "window"
     if softcap:
       args, fam = args + (ctypes.c_float(softcap),), "softcap"
-  out = _read_plan(lib, _varlen_fn(lib, kv, "_plan", fam), _varlen_fn(lib, kv, "_kernel", fam), _VARLEN_PLAN_KEYS, args, strict=True)
+  out = _read_plan(lib, _varlen_fn(lib, fam, "_plan"), _varlen_fn(lib, fam, "_kernel"), _VARLEN_PLAN_KEYS, args, strict=True)
   if total_q <= 0:
     del out["splits"]
   return out
@@ -1618,11 +1622,7 @@ def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seq
     if not (p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC):
       key = (id(lib), q.device.index or 0, p.dtype, batch, Hq, p.heads_kv, D, m.head_dim_v, p.max_seqlen_q, p.max_seqlen_kv, Tq, p.causal, p.flags, p.num_splits,
              os.environ.get("FFPA_HIP_FAKE_CUS"), tm.tokens if tree else 0)
-      nbytes = _MLA_SCRATCH.get(key)
-      if nbytes is None:
-        if len(_MLA_SCRATCH) >= 512:
-          _MLA_SCRATCH.clear()
-        nbytes = _MLA_SCRATCH[key] = int(getattr(lib, export + "_workspace_bytes")(*args))
+      nbytes = _cached_scratch(_MLA_SCRATCH, key, lambda: int(getattr(lib, export + "_workspace_bytes")(*args)))
     workspace = _hand_over_workspace(p, q.device, stream, nbytes)  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
       plan_out.update(_read_plan(lib, getattr(lib, export + "_plan"), getattr(lib, export + "_kernel"), _VARLEN_PLAN_KEYS, args))
@@ -1803,11 +1803,7 @@ def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int,
     nbytes = 0
     if not (p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC):
       key = ("sparse", id(lib), q.device.index or 0, p.dtype, T, Hq, Hkv, D, s.head_dim_v, topk, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS"))
-      nbytes = _MLA_SCRATCH.get(key)
-      if nbytes is None:
-        if len(_MLA_SCRATCH) >= 512:
-          _MLA_SCRATCH.clear()
-        nbytes = _MLA_SCRATCH[key] = int(lib.ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(*args))
+      nbytes = _cached_scratch(_MLA_SCRATCH, key, lambda: int(lib.ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(*args)))
     workspace = _hand_over_workspace(p, q.device, stream, nbytes)  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
       plan_out.update(_read_plan(lib, lib.ffpa_attn_varlen_mla_sparse_fwd_plan, lib.ffpa_attn_varlen_mla_sparse_fwd_kernel, _VARLEN_PLAN_KEYS, args))
