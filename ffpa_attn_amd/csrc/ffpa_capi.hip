@@ -22,6 +22,7 @@
 #include "ffpa_launch.h"
 #include "ffpa_paged.h"         // (the paged-KV twin of the packed-sequence kernel)
 #include "ffpa_mla.h"           // (the MLA latent-cache kernels and their append)
+#include "ffpa_mla_fp8.h"       // (the FP8 build of the latent kernel and its quantising appends)
 #include "ffpa_mla_sparse.h"    // (the sparse — top-k indexed — build of the latent kernel)
 #include "ffpa_mla_tree.h"      // (the tree-mask build of the latent kernel)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
@@ -949,7 +950,8 @@ struct VarlenPlan {
 // caller's head dim read as zeros and are never stored, as in the dense call).  `paged`: the plan of the paged-KV kernel — 64-key tiles where the packed kernel
 // takes 128 (D = 256 / 320), everything else the same rule.
 // `mla`: the plan of the latent-cache call (ffpa_attn_varlen_mla_fwd) — the heads of a KV group are packed into rows HOWEVER MANY they are (see below).
-int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = false, bool mla = false) {
+// `kv_bytes`: bytes per cache element as the non-temporal rule prices them (1: the FP8 latent call).
+int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = false, bool mla = false, int kv_bytes = 2) {
   if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
   if (p->struct_size != sizeof(ffpa_varlen_fwd_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
     return fail(FFPA_ERR_BAD_ABI, "ffpa_varlen_fwd_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size,
@@ -1022,7 +1024,7 @@ int varlen_plan(const ffpa_varlen_fwd_params* p, VarlenPlan* out, bool paged = f
   {
     const bool one_reader = out->nqt == 1 && (out->pack > 0 || group == 1);
     // (the latent-cache call: nqt counts the chunks of a packed group — a latent byte with two chunks has two readers —, and there is one stream, not K + V)
-    const int64_t kv_bound = (mla ? 1LL : 2LL) * p->batch * p->heads_kv * (int64_t)p->max_seqlen_kv * p->head_dim * 2;
+    const int64_t kv_bound = (mla ? 1LL : 2LL) * p->batch * p->heads_kv * (int64_t)p->max_seqlen_kv * p->head_dim * kv_bytes;
     bool nt = one_reader && kv_bound / (mla ? 1 : 2) >= (272LL << 20);
     if (p->flags & FFPA_FLAG_KV_STREAM) nt = true;
     if (p->flags & FFPA_FLAG_NO_KV_STREAM) nt = false;
@@ -1168,14 +1170,16 @@ const ffpa_window* softcap_window(const ffpa_window* w) {
 }
 
 // The kernel builds of the latent-cache calls: one row per (head dim, value width) pair with its three launchers — the latent call's (ffpa_mla_inst.hip), the
-// sparse (top-k indexed) call's (ffpa_mla_sparse_inst.hip) and the tree-mask call's (ffpa_mla_tree_inst.hip).
+// sparse (top-k indexed) call's (ffpa_mla_sparse_inst.hip) and the tree-mask call's (ffpa_mla_tree_inst.hip) — and the FP8 latent call's (ffpa_mla_fp8_inst.hip).
 typedef int (*mla_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, const ffpa::MlaArgs&, hipStream_t);
+typedef int (*mla_fp8_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, const ffpa::MlaFp8Args&, hipStream_t);
 struct MlaBuild {
   int d, dv;
   mla_fn latent, sparse, tree;
+  mla_fp8_fn fp8;
 };
 const MlaBuild kMlaBuilds[] = {
-#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_paged_d##D, &ffpa::launch_mla_sparse_d##D, &ffpa::launch_mla_tree_d##D},
+#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_paged_d##D, &ffpa::launch_mla_sparse_d##D, &ffpa::launch_mla_tree_d##D, &ffpa::launch_mla_fp8_paged_d##D},
     FFPA_FOR_EACH_MLA_BUILD(FFPA_ROW)
 #undef FFPA_ROW
 };
@@ -1202,6 +1206,24 @@ int check_mla(const ffpa_varlen_fwd_params* p, const ffpa_mla* m, const MlaBuild
     if ((int64_t)p->batch * m->seqlen_new > 0x7fffffffLL) return fail(FFPA_ERR_BAD_SHAPE, "grid of %lld new rows is too large", (long long)p->batch * m->seqlen_new);
   }
   *build = found;
+  return FFPA_OK;
+}
+
+// The FP8 latent call's own argument (ffpa_mla_fp8): its struct, checked in front of everything else of the call ...
+int check_mla_fp8(const ffpa_mla_fp8* f8) {
+  if (f8 == nullptr) return fail(FFPA_ERR_NULL_POINTER, "mla_fp8 is NULL");
+  if (f8->struct_size != sizeof(ffpa_mla_fp8)) return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_fp8 ABI mismatch: size %u (want %zu)", f8->struct_size, sizeof(ffpa_mla_fp8));
+  if (f8->reserved != 0 || f8->reserved2 != 0.f)
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_fp8.reserved=%u / reserved2=%g must be 0", f8->reserved, (double)f8->reserved2);
+  if (!isfinite(f8->kv_scale) || !(f8->kv_scale > 0.f)) return fail(FFPA_ERR_BAD_SHAPE, "ffpa_mla_fp8.kv_scale=%g must be finite and > 0", (double)f8->kv_scale);
+  return FFPA_OK;
+}
+
+// ... and the geometry of a pool of one byte per element: the kernel's text doubles every cache stride (it was written for 16-bit elements) and its register loads
+// and the append's stores are 8 bytes wide, so rows, heads and pages lie multiples of 16 elements apart.
+int check_fp8_strides(int64_t row, int64_t head, int64_t page) {
+  if (row % 16 != 0 || head % 16 != 0 || page % 16 != 0)
+    return fail(FFPA_ERR_BAD_STRIDE, "FP8 pool strides (row %lld, head %lld, page %lld) must be multiples of 16 elements", (long long)row, (long long)head, (long long)page);
   return FFPA_OK;
 }
 
@@ -1255,6 +1277,7 @@ enum class Family {
   kSoftcap,  // ffpa_attn_varlen_softcap_fwd: softcap; win optional (NULL: (-1, -1)), kv optional — a window launch with capped scores, the *_softcap_kernel builds
   kMla,      // ffpa_attn_varlen_mla_fwd: kv, mla — k is the latent pool and serves as v too (p->v is not read); its own plan and kernel, the append in front
   kMlaTree,  // ffpa_attn_varlen_mla_tree_fwd: kv, mla, tree — the latent launch under the causal flag, the tree build of its kernel
+  kMlaFp8,   // ffpa_attn_varlen_mla_fp8_fwd: kv, mla, fp8 — the latent call over a pool of e4m3 codes: its plan on the FP8 bytes, the FP8 build of its kernel
   kSparse,   // ffpa_attn_varlen_mla_sparse_fwd: sparse — a latent launch without a page pool: the index list stands where the block table stood
 };
 bool is_tree(Family f) { return f == Family::kTree || f == Family::kMlaTree; }
@@ -1269,6 +1292,7 @@ struct VarlenCall {
   float softcap;
   const ffpa_mla* mla;
   const ffpa_mla_sparse* sparse;
+  const ffpa_mla_fp8* fp8;
 };
 typedef const ffpa_varlen_fwd_params* ParamsPtr;
 VarlenCall make_call(Family family, ParamsPtr p, const ffpa_paged_kv* kv) {
@@ -1303,6 +1327,11 @@ VarlenCall mla_tree_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m
   c.mla = m, c.tree = tree;
   return c;
 }
+VarlenCall mla_fp8_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8) {
+  VarlenCall c = make_call(Family::kMlaFp8, p, kv);
+  c.mla = m, c.fp8 = f8;
+  return c;
+}
 VarlenCall sparse_call(ParamsPtr p, const ffpa_mla_sparse* s) {
   VarlenCall c = make_call(Family::kSparse, p, nullptr);
   c.sparse = s;
@@ -1318,6 +1347,8 @@ struct CallPlan {
   const ffpa_mla* mla;              // a latent launch: the caller's ffpa_mla or — the sparse call — `own_mla`; NULL: a launch over a K and a V cache
   ffpa_mla own_mla;
   mla_fn launch_mla;                // ... and the build of the latent kernel it launches
+  const ffpa_mla_fp8* fp8;          // the FP8 latent launch: its scale ...
+  mla_fp8_fn launch_mla_fp8;        // ... and its build (launch_mla is NULL then)
 };
 
 // The window call's plan is the packed call's, PRICED AT WHAT THE WINDOW LEAVES.  A row tile of R token rows (all max_seqlen_q tokens under GQA row packing, else
@@ -1376,6 +1407,8 @@ int plan_call(const VarlenCall& c, CallPlan* cp) {
   cp->win_causal = cp->win_right = cp->win_span = 0;
   cp->mla = nullptr;
   cp->launch_mla = nullptr;
+  cp->fp8 = nullptr;
+  cp->launch_mla_fp8 = nullptr;
   switch (c.family) {
     case Family::kPacked:
       return varlen_plan(p, pl);
@@ -1410,6 +1443,16 @@ int plan_call(const VarlenCall& c, CallPlan* cp) {
       if (c.family == Family::kMlaTree && (rc = check_tree(p, c.tree)) != FFPA_OK) return rc;
       cp->mla = c.mla;
       cp->launch_mla = c.family == Family::kMlaTree ? build->tree : build->latent;
+      return FFPA_OK;
+    case Family::kMlaFp8:  // its own struct first, then the latent call's checks with the cache priced at one byte per element, then the pool's geometry
+      if ((rc = check_mla_fp8(c.fp8)) != FFPA_OK) return rc;
+      if ((rc = varlen_plan(p, pl, true, true, 1)) != FFPA_OK) return rc;
+      if ((rc = check_paged(p, c.kv)) != FFPA_OK) return rc;
+      if ((rc = check_mla(p, c.mla, &build)) != FFPA_OK) return rc;
+      if ((rc = check_fp8_strides(p->k_stride[0], p->k_stride[1], c.kv->k_page_stride)) != FFPA_OK) return rc;
+      cp->mla = c.mla;
+      cp->fp8 = c.fp8;
+      cp->launch_mla_fp8 = build->fp8;
       return FFPA_OK;
     case Family::kSparse:
       if ((rc = check_sparse(p, c.sparse)) != FFPA_OK) return rc;
@@ -1451,6 +1494,9 @@ int varlen_launch(const VarlenCall& c, void* stream) {
   }
   if (p->lse != nullptr && p->lse_stride_head < 0) return fail(FFPA_ERR_BAD_STRIDE, "lse_stride_head is negative");
   if (!isfinite(p->softmax_scale)) return fail(FFPA_ERR_BAD_SHAPE, "softmax_scale is not finite");
+  // (the FP8 latent launch: the scores are (softmax_scale x kv_scale) q.K8 — the factor rides in the scale, no element is touched)
+  const float score_scale = cp.fp8 != nullptr ? p->softmax_scale * cp.fp8->kv_scale : p->softmax_scale;
+  if (!isfinite(score_scale)) return fail(FFPA_ERR_BAD_SHAPE, "softmax_scale x kv_scale is not finite");
   if (p->total_q < 0) return fail(FFPA_ERR_BAD_SHAPE, "total_q=%d is negative", p->total_q);
   if (p->workspace != nullptr && !aligned16(p->workspace)) return fail(FFPA_ERR_MISALIGNED, "workspace must be 16-byte aligned");
   if ((rc = check_device()) != FFPA_OK) return rc;
@@ -1478,7 +1524,7 @@ int varlen_launch(const VarlenCall& c, void* stream) {
   a.total_wg = (int)pl.grid;
   a.causal = p->causal ? 1 : 0;
   a.inv_scale = 1.f;
-  fold_scale(a, p->softmax_scale);
+  fold_scale(a, score_scale);
   a.thr = p->rescale_threshold < 0.f ? 8.0f : p->rescale_threshold;
   a.flags = p->flags & (FFPA_FLAG_NO_XCD_REMAP);
   a.nsplit = 1;
@@ -1563,7 +1609,30 @@ int varlen_launch(const VarlenCall& c, void* stream) {
       pa.tiles_per_page = kv->page_size / pl.bc;
       pa.num_pages = kv->num_pages;
     }
-    if (latent) {
+    if (cp.fp8 != nullptr) {
+      // the FP8 latent launch: the quantising append in front (the pool's strides in its elements: bytes), then the kernel — whose text doubles every cache
+      // stride — with the strides in units of two bytes (check_fp8_strides: exact)
+      st = 0;
+      if (mla->seqlen_new > 0) {
+        ffpa::MlaFp8AppendArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        ffpa::MlaAppendArgs& ap = fa.a;
+        ap.kv_new = mla->kv_new, ap.cache = const_cast<void*>(p->k);
+        ap.seqlens = mla->cache_seqlens, ap.used = const_cast<int*>(p->seqused_kv), ap.table = kv->block_table;
+        for (int i = 0; i < 3; ++i) ap.s_new[i] = mla->kv_new_stride[i];
+        ap.s_row = p->k_stride[0], ap.s_head = p->k_stride[1], ap.s_page = kv->k_page_stride, ap.bt_stride = kv->bt_stride;
+        ap.B = p->batch, ap.Snew = mla->seqlen_new, ap.Hkv = p->heads_kv, ap.D = p->head_dim;
+        ap.cap = pa.cap, ap.page_size = kv->page_size, ap.num_pages = kv->num_pages;
+        fa.inv = 1.f / cp.fp8->kv_scale;
+        st = ffpa::launch_mla_fp8_append(p->dtype, fa, static_cast<hipStream_t>(stream));
+      }
+      a.sk[1] /= 2, a.sk[2] /= 2, a.sv[1] /= 2, a.sv[2] /= 2;
+      pa.k_page_stride /= 2, pa.v_page_stride /= 2;
+      ffpa::MlaFp8Args ma;
+      ma.dv = mla->head_dim_v;
+      ma.kv_scale = cp.fp8->kv_scale;
+      if (st == 0) st = cp.launch_mla_fp8(p->dtype, pl.nt, a, va, pa, ma, static_cast<hipStream_t>(stream));
+    } else if (latent) {
       st = 0;
       if (mla->seqlen_new > 0) {
         // the step's latent rows first, ONE store per element (there is one cache), and the lengths the attention launch behind it reads
@@ -1633,7 +1702,7 @@ int call_kernel(const VarlenCall& c, char* buf, size_t n) {
   const char* merge = pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "";
   if (cp.mla != nullptr) {
     // (a latent call's name is formatted from the caller's params; the sparse call — a uniform batch — has never named the compact grid)
-    const char* kind = c.family == Family::kSparse ? "_sparse" : c.family == Family::kMlaTree ? "_tree" : "";
+    const char* kind = c.family == Family::kSparse ? "_sparse" : c.family == Family::kMlaTree ? "_tree" : c.family == Family::kMlaFp8 ? "_fp8" : "";
     snprintf(buf, n, "ffpa_fwd_m16_mla%s_kernel<%s, %d, dv=%d%s>%s%s%s", kind, c.p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", c.p->head_dim, cp.mla->head_dim_v, nt,
              pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "",
              pl.compact > 0 && c.family != Family::kSparse ? " (compact grid)" : "", merge);
@@ -1746,6 +1815,23 @@ int ffpa_attn_varlen_mla_tree_fwd_compact_slots(const ffpa_varlen_fwd_params* p,
   return call_compact_slots(mla_tree_call(p, kv, m, tree), slots);
 }
 
+// ---- the FP8 latent call (include/ffpa_attn.h: ffpa_mla_fp8): the latent call over a pool of e4m3 codes with one per-tensor scale
+int ffpa_attn_varlen_mla_fp8_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, void* stream) {
+  return varlen_launch(mla_fp8_call(p, kv, m, f8), stream);
+}
+int ffpa_attn_varlen_mla_fp8_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, int out[5]) {
+  return call_plan(mla_fp8_call(p, kv, m, f8), out);
+}
+int ffpa_attn_varlen_mla_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, char* buf, size_t n) {
+  return call_kernel(mla_fp8_call(p, kv, m, f8), buf, n);
+}
+size_t ffpa_attn_varlen_mla_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8) {
+  return call_workspace_bytes(mla_fp8_call(p, kv, m, f8));
+}
+int ffpa_attn_varlen_mla_fp8_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, int* slots) {
+  return call_compact_slots(mla_fp8_call(p, kv, m, f8), slots);
+}
+
 // ---- the sparse latent call (include/ffpa_attn.h: ffpa_mla_sparse): the latent launch over per-token index lists
 int ffpa_attn_varlen_mla_sparse_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream) { return varlen_launch(sparse_call(p, s), stream); }
 int ffpa_attn_varlen_mla_sparse_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]) { return call_plan(sparse_call(p, s), out); }
@@ -1755,7 +1841,8 @@ int ffpa_attn_varlen_mla_sparse_fwd_kernel(const ffpa_varlen_fwd_params* p, cons
 size_t ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) { return call_workspace_bytes(sparse_call(p, s)); }
 
 // ---- the latent append of a ragged step (include/ffpa_attn.h: ffpa_mla_append_varlen_params): token rows packed by cu_seqlens_q into the ONE paged pool
-int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, void* stream) {
+// (one body for the 16-bit pool and — f8 non-NULL, checked by the caller — the FP8 pool, whose rows are quantised on their way in)
+static int mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, const ffpa_mla_fp8* f8, void* stream) {
   if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
   if (p->struct_size != sizeof(ffpa_mla_append_varlen_params))
     return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_append_varlen_params ABI mismatch: size %u (want %zu)", p->struct_size, sizeof(ffpa_mla_append_varlen_params));
@@ -1776,10 +1863,12 @@ int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ff
     return fail(FFPA_ERR_MISALIGNED, "seqused / cache_seqlens / cu_seqlens_q must be 4-byte aligned");
   if (!aligned16(p->kv_cache) || (p->total_q > 0 && !aligned16(p->kv_new))) return fail(FFPA_ERR_MISALIGNED, "kv_new / kv_cache base pointers must be 16-byte aligned");
   if ((rc = check_strides("kv_cache", p->kv_cache_stride, 2)) || (p->total_q > 0 && (rc = check_strides("kv_new", p->kv_new_stride, 2)))) return rc;
+  if (f8 != nullptr && (rc = check_fp8_strides(p->kv_cache_stride[0], p->kv_cache_stride[1], kv->k_page_stride)) != FFPA_OK) return rc;
   if ((rc = check_device()) != FFPA_OK) return rc;
 
-  ffpa::MlaAppendVarlenArgs va;
-  memset(&va, 0, sizeof(va));
+  ffpa::MlaFp8AppendVarlenArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  ffpa::MlaAppendVarlenArgs& va = fa.va;
   ffpa::MlaAppendArgs& a = va.a;
   a.kv_new = p->kv_new, a.cache = p->kv_cache;
   a.seqlens = p->cache_seqlens, a.used = p->seqused, a.table = kv->block_table;
@@ -1788,9 +1877,16 @@ int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ff
   a.B = p->batch, a.Hkv = p->heads_kv, a.D = p->head_dim;
   a.cap = kv->pages_per_row * kv->page_size, a.page_size = kv->page_size, a.num_pages = kv->num_pages;
   va.cu_q = p->cu_seqlens_q, va.T = p->total_q;
-  const int st = ffpa::launch_mla_append_varlen(va, static_cast<hipStream_t>(stream));
+  if (f8 != nullptr) fa.inv = 1.f / f8->kv_scale;
+  const int st = f8 != nullptr ? ffpa::launch_mla_fp8_append_varlen(p->dtype, fa, static_cast<hipStream_t>(stream))
+                               : ffpa::launch_mla_append_varlen(va, static_cast<hipStream_t>(stream));
   if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla append (varlen) launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
   return FFPA_OK;
+}
+int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, void* stream) { return mla_append_varlen(p, kv, nullptr, stream); }
+int ffpa_attn_mla_fp8_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, const ffpa_mla_fp8* f8, void* stream) {
+  const int rc = check_mla_fp8(f8);
+  return rc != FFPA_OK ? rc : mla_append_varlen(p, kv, f8, stream);
 }
 
 // ---- the KV-cache append + rotary (include/ffpa_attn.h: ffpa_kv_append_params)

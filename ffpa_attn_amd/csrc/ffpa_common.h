@@ -381,6 +381,32 @@ __device__ __forceinline__ u32x4 make_rsrc(const void* base, uint32_t bytes) {
   return r;
 }
 
+// One 8-byte buffer load per lane INTO REGISTERS (the FP8 latent build, ffpa_mla_fp8_inst.hip: an e4m3 tile is staged in VGPRs, widened and written to LDS where
+// the LDS-DMA pieces of the 16-bit builds land).  The compiler's own load: it counts vmcnt for it and waits in front of the first use; the descriptor's range
+// check returns zeros for an out-of-range lane (kDmaOob, rows past the last key), as the LDS-DMA writes zeros.  NT: the non-temporal hint (aux bit 1).
+__device__ u32x2 ffpa_raw_buffer_load_b64(u32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2i32");
+template <bool NT>
+__device__ __forceinline__ u32x2 buffer_load_8(u32x4 rsrc, uint32_t voff) {
+  return ffpa_raw_buffer_load_b64(rsrc, (int)voff, 0, NT ? 2 : 0);
+}
+
+// Eight OCP e4m3 codes (two dwords, element 0 in the low byte) -> eight elements of T (bf16 / fp16) as one 16-byte LDS slot.  EXACT: every finite e4m3 value —
+// the subnormals down to 2^-9 and the largest, 448, included — is representable in both 16-bit formats, so neither conversion step rounds; the NaN codes stay NaN.
+template <typename T>
+__device__ __forceinline__ u32x4 fp8x8_widen(u32x2 w) {
+  typename Elem<T>::v8 r;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[h], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[h], true);
+    r[4 * h + 0] = (T)lo[0];
+    r[4 * h + 1] = (T)lo[1];
+    r[4 * h + 2] = (T)hi[0];
+    r[4 * h + 3] = (T)hi[1];
+  }
+  return __builtin_bit_cast(u32x4, r);
+}
+
 // Source of one KV tile: a descriptor whose base is the tile's first row, so that every DMA offset is
 // tile-relative and 32-bit no matter how large the (batch, head) slice is (a token-major [B,N,H,D] cache
 // passes 4 GiB at 128k tokens); only BC rows must span < 4 GiB.  num_records covers exactly the `rows` valid

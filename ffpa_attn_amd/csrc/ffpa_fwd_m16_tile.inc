@@ -63,6 +63,28 @@
 #define FFPA_M16_KV_GATHER false
 #define FFPA_M16_KV_GATHER_DEFAULT_HOOKS
 #endif
+// AN FP8 (OCP e4m3) LATENT CACHE is the enclosing kernel's as well (ffpa_mla_fp8_inst.hip, on top of the MLA hook): FFPA_M16_KV_FP8 = a constant of its build,
+// FFPA_M16_KV_SCALE = the per-tensor dequantisation factor (K = scale x K8), FFPA_M16_KV_FP8_LOAD(rsrc, voff) = its 8-byte register load (buffer_load_8 with the
+// build's non-temporal choice).  The pool holds ONE byte per element, and every e4m3 value is exactly a T: the build's
+// one job is to put the exact 16-bit image of a tile where the LDS-DMA pieces of the 16-bit build put it — everything behind the image is that build's text.
+//   * no LDS-DMA: piece i of a wave is one 8-byte buffer load per lane (buffer_load_8) into the register pair kv8[i], issued where the DMA piece was (on the QK^T
+//     MFMAs of step j for tile j + 1, the prologue for tile t0).  The lane's source offset is the 16-bit build's with 8-byte slots (ks << 3, row bytes = the pool's
+//     row stride in bytes: the launch side hands FwdArgs::sk / PagedArgs::k_page_stride in units of TWO bytes, so `* 2u` below yields bytes), the out-of-range
+//     sentinel and the tile descriptor are the same (rb_valid = the row's FP8 bytes): slots >= slots_valid and rows past the last key are zeros;
+//   * behind PV(j) — in front of barrier B, where the 16-bit build drains its DMA queue — FFPA_M16_KV_FP8_COMMIT widens the nine pairs (fp8x8_widen: exact) and
+//     writes each with one ds_write_b128 at image((j + 1) & 1) + piece * 1024 + lane * 16: the byte the DMA piece targets.  The destination is free for the 16-bit
+//     build's reason (its last readers, PV(j - 1), passed barrier B of step j - 1); barrier B (its lgkmcnt(0) in front) publishes the writes;
+//   * the loads are the compiler's (it counts vmcnt and waits in front of the first conversion); there is no LDS-DMA and no hidden load in this build — the L2 touch
+//     is OFF (pf_on) —, so at barrier B the vector-memory queue is EMPTY: the nine loads of tile j + 1 were consumed by the commit, dma_wait_except<0> finds nothing;
+//   * the scores are (softmax_scale x kv_scale) q.K8 — the launch side folds the factor into FwdArgs::scale_log2 — and O = kv_scale x sum p K8[:, :dv]: the factor
+//     enters ONCE, in the 1 / l of the two epilogues (direct store, fp32 partials of a split launch).
+// Kernels that do not define the hook read 16-bit caches: the text that stood here.
+#ifndef FFPA_M16_KV_FP8
+#define FFPA_M16_KV_FP8 false
+#define FFPA_M16_KV_SCALE 1.f
+#define FFPA_M16_KV_FP8_LOAD(rsrc_, voff_) u32x2{0u, 0u}
+#define FFPA_M16_KV_FP8_DEFAULT_HOOKS
+#endif
 #ifndef FFPA_M16_KV_SRC
 #define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) tile_src<BC>(slice, row_bytes, key0, a.Nkv, rb_valid)
 #define FFPA_M16_KV_BEGIN(t0_)
@@ -94,7 +116,7 @@
   //     everything but the swizzled lane offset is scalar;
   //   * other head dims: piece p = wave * PPW + i covers slots [64 p, 64 p + 64) of the row-major image; the per-lane source
   //     offsets are tile-invariant and live in PPW + PPW registers.
-  const uint32_t rb_valid = (uint32_t)a.d_valid * 2u;
+  const uint32_t rb_valid = (uint32_t)a.d_valid * (FFPA_M16_KV_FP8 ? 1u : 2u);  // (FP8 pool: one byte per element)
   const int slots_valid = a.d_valid >> 3;
   uint32_t kvo[kRowDma ? 4 : 1], vvo[kRowDma ? 4 : 1];
   uint32_t kro[kRowDma ? KPW : 1], vro[kRowDma ? KPW : 1];
@@ -132,7 +154,7 @@
       const int kkey = gk / SPR;
       const int kslot = gk - kkey * SPR;
       const int ks = kslot ^ (FFPA_M16_MLA_ON ? m16_v_swizzle<D>(kkey) : m16_k_swizzle<D>(kkey));  // (MLA: the shared image takes the V map)
-      krel[i] = (uint32_t)kkey * k_row_bytes + (uint32_t)(ks << 4);
+      krel[i] = (uint32_t)kkey * k_row_bytes + (uint32_t)(ks << (FFPA_M16_KV_FP8 ? 3 : 4));  // (FP8 pool: a slot's 8 elements are 8 bytes of the source)
       if (ks >= slots_valid) krel[i] = kDmaOob;
     }
     // this wave's pieces land at base + i KiB: one scalar base per tile image, the piece index is an immediate of the DMA asm
@@ -143,11 +165,22 @@
   // MLA: where this wave's pieces of the latent tile at key0 land — the image of the tile's parity (k_lds: Kt's, v_lds: Vt's; the same piece offsets in both).
   // (a macro, not a lambda: a lambda more in front of the others would renumber their symbols in every object built from this text)
 #define FFPA_M16_MLA_DST(key0_) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(((((key0_) / BC) & 1) != 0) ? v_lds : k_lds)))
+  static_assert(!FFPA_M16_KV_FP8 || FFPA_M16_MLA_ON, "the FP8 hook lives on top of the MLA hook");
+  // FP8: this wave's pieces of the latent tile at key0, staged in registers by issue_k / issue_k_on, and their commit to the image of the tile's parity — lane l's
+  // slot of piece i at + i KiB + 16 l, the LDS-DMA's lane-linear rule.  (a macro, not a lambda: see FFPA_M16_MLA_DST)
+  u32x2 kv8[FFPA_M16_KV_FP8 ? PPW : 1];
+#define FFPA_M16_KV_FP8_COMMIT(key0_)                                                                                        \
+  {                                                                                                                          \
+    FFPA_LDS char* const dst8_ = ((((key0_) / BC) & 1) != 0 ? Vt : Kt) + wave * (PPW * 1024) + lane * 16;                    \
+    _Pragma("unroll") for (int i8_ = 0; i8_ < PPW; ++i8_) *(FFPA_LDS u32x4*)(dst8_ + i8_ * 1024) = fp8x8_widen<T>(kv8[i8_]); \
+  }
   auto issue_k = [&](auto ic, int key0) {
     constexpr int i = decltype(ic)::value;
     const TileSrc ts = FFPA_M16_KV_SRC(0, Kg, k_row_bytes, key0);
     if constexpr (kRowDma) {
       lds_dma_row<(16 * (i >> 2) + (i & 3)) * RB, 0>(ts.rsrc, k_lds, kvo[i & 3], kro[i]);
+    } else if constexpr (FFPA_M16_KV_FP8) {
+      kv8[i] = FFPA_M16_KV_FP8_LOAD(ts.rsrc, krel[i]);
     } else {
       FFPA_M16_DMA16<(kKS && i >= kH ? 2 * PPW + (i - kH) : i) * 1024>(ts.rsrc, FFPA_M16_MLA_ON ? FFPA_M16_MLA_DST(key0) : k_lds, krel[i], 0u);
     }
@@ -168,6 +201,12 @@
   auto issue_k_on = [&](auto ic, int key0, auto kindc, f32x4& d, v8 fa, v8 fb) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
     const TileSrc ts = FFPA_M16_KV_SRC(0, Kg, k_row_bytes, key0);
+    if constexpr (FFPA_M16_KV_FP8) {  // (the MFMA, then the piece's register load behind it)
+      if constexpr (decltype(kindc)::value == 0) M::first(d, fa, fb);
+      else if constexpr (decltype(kindc)::value == 1) M::acc(d, fa, fb);
+      else M::acc_a(d, fa, fb);
+      kv8[kRowDma ? 0 : i] = FFPA_M16_KV_FP8_LOAD(ts.rsrc, krel[kRowDma ? 0 : i]);
+    } else
     M::template with_dma<decltype(kindc)::value, (kKS && i >= kH ? 2 * PPW + (i - kH) : i) * 1024>(d, fa, fb, ts.rsrc, FFPA_M16_MLA_ON ? FFPA_M16_MLA_DST(key0) : k_lds, krel[kRowDma ? 0 : i], 0u);
   };
   auto issue_v_on = [&](auto ic, int key0, auto kindc, f32x4& d, v8 fa, v8 fb) __attribute__((always_inline)) {
@@ -192,7 +231,7 @@
   // (built into the split-D tiles only: at D <= 512 a DMA piece has a whole step to land, the touches cost 1 ... 2 %, and the dropout +
   // bias builds there have no register to spare)
   constexpr bool kPf = ND == 2;
-  const bool pf_on = kPf && a.l2_prefetch != 0 && wave < FFPA_M16_PF_WAVES && ((FFPA_M16_PF_WHICH >> (wave & 1)) & 1) && !(FFPA_M16_MLA_ON && (wave & 1)) && !FFPA_M16_KV_GATHER;  // (MLA: there is no V stream to touch; gathered keys: no contiguous tile to touch)
+  const bool pf_on = kPf && a.l2_prefetch != 0 && wave < FFPA_M16_PF_WAVES && ((FFPA_M16_PF_WHICH >> (wave & 1)) & 1) && !(FFPA_M16_MLA_ON && (wave & 1)) && !FFPA_M16_KV_GATHER && !FFPA_M16_KV_FP8;  // (MLA: there is no V stream to touch; gathered keys: no contiguous tile to touch; FP8: no hidden load next to the compiler's)
   const bool pf_k = (wave & 1) == 0;  // even waves touch K, odd waves V
   uint32_t pf_off = kDmaOob;
   uint32_t pf_junk = 0u;  // (the loads' destination: never read, but live through the loop so that nothing else is allocated to it)
@@ -406,6 +445,7 @@
   FFPA_M16_KV_BEGIN(t0)
   if (nt > t0) {
     static_for<PPW>([&](auto ic) { issue_k(ic, t0 * BC); });
+    if constexpr (FFPA_M16_KV_FP8) FFPA_M16_KV_FP8_COMMIT(t0 * BC)
     if constexpr (MK == 1) {
       const u32x4 brs = bias_rsrc();
       static_for<kBtMax>([&](auto ic) {
@@ -1351,6 +1391,7 @@
     FFPA_TSTAMP(4);  // PV loop
     // barrier B: every wave is done reading V(j); K(j+1) has landed and is visible
     FFPA_M16_KV_STEP_END()
+    if constexpr (FFPA_M16_KV_FP8) FFPA_M16_KV_FP8_COMMIT(k0 + BC)  // (tile j + 1: staged during QK^T(j), widened and written behind PV(j); barrier B publishes it)
     if (pf_on) {  // (wave-uniform)
       issue_prefetch(k0 + FFPA_M16_PF_DIST * BC);
       dma_wait_except<1>();
@@ -1390,6 +1431,10 @@
   row4_reduce2<false>(l_tot[0], l_tot[1]);
 #pragma unroll
   for (int rh = 0; rh < 2; ++rh) inv[rh] = FFPA_M16_ROW_INV(l_tot[rh]);  // fully masked row: 0 * inf = NaN, as SDPA (the packed-sequence kernel: 0, its contract)
+  if constexpr (FFPA_M16_KV_FP8) {  // O = kv_scale x sum p K8[:, :dv]: the factor enters here, once, for both epilogues
+#pragma unroll
+    for (int rh = 0; rh < 2; ++rh) inv[rh] *= FFPA_M16_KV_SCALE;
+  }
   if (a.nsplit > 1) {
     // split-KV partial: normalised fp32 O and its LSE (merged by ffpa_fwd_merge_kernel)
 #pragma unroll
@@ -1465,6 +1510,13 @@
 #undef FFPA_M16_WINDOW_ON
 #endif
 #undef FFPA_M16_MLA_DST
+#undef FFPA_M16_KV_FP8_COMMIT
+#ifdef FFPA_M16_KV_FP8_DEFAULT_HOOKS
+#undef FFPA_M16_KV_FP8_DEFAULT_HOOKS
+#undef FFPA_M16_KV_FP8_LOAD
+#undef FFPA_M16_KV_SCALE
+#undef FFPA_M16_KV_FP8
+#endif
 #ifdef FFPA_M16_MLA_DEFAULT_HOOKS
 #undef FFPA_M16_MLA_DEFAULT_HOOKS
 #undef FFPA_M16_O_COLS

@@ -1,0 +1,187 @@
+// ffpa_mla_fp8_inst.hip — MLA latent-cache attention over an FP8 cache: the latent pool holds OCP e4m3 codes with ONE per-tensor scale (K = kv_scale x K8), the
+// form in which the serving engines keep the latent cache of DeepSeek-V2 / V3 / R1 and Kimi K2 (kv_cache_dtype = "fp8").  One translation unit per (D, dv) pair of
+// FFPA_FOR_EACH_MLA_BUILD (compiled with -DFFPA_INST_D=<D>, q / O in bf16 + fp16 in the same TU); a TU of its own so that every other object stays what it was.
+// Entry point: ffpa_attn_varlen_mla_fp8_fwd (ffpa_capi.hip).
+//
+// The kernel is the latent kernel's text (ffpa_mla_inst.hip: ffpa_fwd_m16_paged_body.inc + ffpa_fwd_m16_tile.inc under FFPA_M16_MLA_ON) with one more hook of the
+// tile text on, FFPA_M16_KV_FP8 (described there).  There is no FP8 arithmetic: every e4m3 value is exactly a bf16 and exactly an fp16, so the kernel stages a tile's
+// bytes in registers, widens them and writes the EXACT 16-bit image of the tile to LDS where the LDS-DMA pieces of the 16-bit build land; the MFMAs, the shared
+// image under the V swizzle, the two alternating images, the two-barrier step, row chunks, KV ranges + merge and the compact grid are that build's.  The scale
+// never touches an element: the scores are (softmax_scale x kv_scale) q.K8, and O is multiplied by kv_scale once in the epilogues' 1 / l.  With a power-of-two
+// kv_scale the call returns the bits of the 16-bit latent call on the dequantised pool.
+#include "ffpa_cu_seqlens_find.h"
+#include "ffpa_fwd_kernel.h"
+#include "ffpa_fwd_m16_kernel.h"
+#include "ffpa_launch_kernel.h"
+#include "ffpa_mla_fp8.h"
+#include "ffpa_paged.h"
+
+#ifndef FFPA_INST_D
+#error "compile with -DFFPA_INST_D=<head dim>"
+#endif
+
+namespace ffpa {
+
+// (ffpa_paged_inst.hip's: a tile whose first row is `tile_base` — rows past the sequence's last key read as zeros, a tile at or past the end moves no bytes)
+template <int BC>
+__device__ __forceinline__ TileSrc tile_src_at(const char* tile_base, uint32_t row_bytes, int key0, int nkv, uint32_t RB) {
+  const int kc = key0 < nkv ? key0 : nkv;
+  int rows = nkv - kc;
+  rows = rows < BC ? rows : BC;
+  const uint32_t span = (uint32_t)(rows < 1 ? rows : 1) * ((uint32_t)(rows - 1) * row_bytes + (uint32_t)RB);
+  TileSrc t;
+  t.base = tile_base;
+  t.rows = rows;
+  t.rsrc = make_rsrc(t.base, span);
+  return t;
+}
+
+template <typename T, int D, bool NT = false>
+__global__ __launch_bounds__(256) void ffpa_fwd_m16_mla_fp8_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa, const MlaFp8Args ma) {
+  static_assert(D > 512 && D % 128 == 64, "the MLA hook lives in the un-pipelined split-D loop of the tile text");
+#define FFPA_M16_VARLEN_TREE false
+#define FFPA_M16_VARLEN_WINDOW false
+#define FFPA_M16_VARLEN_SOFTCAP false
+#define FFPA_M16_MLA_ON true
+#define FFPA_M16_O_COLS ma.dv
+#define FFPA_M16_KV_FP8 true
+#define FFPA_M16_KV_SCALE ma.kv_scale
+#define FFPA_M16_KV_FP8_LOAD(rsrc_, voff_) buffer_load_8<NT>((rsrc_), (voff_))
+#include "ffpa_fwd_m16_paged_body.inc"
+#undef FFPA_M16_KV_FP8_LOAD
+#undef FFPA_M16_KV_SCALE
+#undef FFPA_M16_KV_FP8
+#undef FFPA_M16_O_COLS
+#undef FFPA_M16_MLA_ON
+#undef FFPA_M16_VARLEN_SOFTCAP
+#undef FFPA_M16_VARLEN_WINDOW
+#undef FFPA_M16_VARLEN_TREE
+}
+
+template <typename T, int D, bool NT>
+static int launch_mla_fp8(const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaFp8Args& ma, hipStream_t stream) {
+  constexpr int BC = m16_block_keys(D, true);
+  constexpr int LDS = 2 * BC * D * 2 + m16_exchange_bytes(D, 0);  // (the two 16-bit images of the latent kernel: the same LDS bytes)
+  return launch_kernel<ffpa_fwd_m16_mla_fp8_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa, ma);
+}
+
+int FFPA_CAT(launch_mla_fp8_paged_d, FFPA_INST_D)(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaFp8Args& ma,
+                                                  hipStream_t stream) {
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return nt ? launch_mla_fp8<T, FFPA_INST_D, true>(a, va, pa, ma, stream) : launch_mla_fp8<T, FFPA_INST_D, false>(a, va, pa, ma, stream);
+  });
+}
+
+#if FFPA_INST_D == 576  // (one copy of the appends in the library: the first build's TU carries them)
+// THE QUANTISATION of the appends, to the bit: rne_e4m3(clamp(float32(x) * inv, -448, +448)).  +-inf saturates; NaN stays NaN — a max / min (or med3) clamp returns
+// its non-NaN operand, so the NaN is selected back explicitly.  The conversion instruction rounds to nearest even and keeps subnormals (down to 2^-9; +-2^-10 is a
+// tie and goes to +-0); behind the clamp it never meets a value out of range.  Eight elements of T -> eight codes, element 0 in the low byte.
+template <typename T>
+__device__ __forceinline__ u32x2 quantize8_e4m3(u32x4 raw, float inv) {
+  const typename Elem<T>::v8 x = __builtin_bit_cast(typename Elem<T>::v8, raw);
+  float v[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float s = (float)x[e] * inv;
+    const float c = fminf(fmaxf(s, -448.f), 448.f);
+    v[e] = s != s ? s : c;
+  }
+  u32x2 w;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    int p = 0;
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * h + 0], v[4 * h + 1], p, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * h + 2], v[4 * h + 3], p, true);
+    w[h] = (uint32_t)p;
+  }
+  return w;
+}
+
+// One new row's Hkv heads, 8 elements per thread and step: ONE 16-byte load of T, ONE 8-byte vector store of codes.  (Strides of the pool are in its elements: bytes.)
+template <typename T>
+__device__ __forceinline__ void fp8_append_row(const MlaAppendArgs& a, const T* src, uint8_t* dst, float inv, int tid) {
+  const int cpr = a.D / 8;  // 8-element chunks per head row
+  for (int e = tid; e < a.Hkv * cpr; e += 256) {
+    const int h = e / cpr, c = e - h * cpr;
+    *(u32x2*)(dst + h * a.s_head + c * 8) = quantize8_e4m3<T>(*(const u32x4*)(src + h * a.s_new[2] + c * 8), inv);
+  }
+}
+
+// THE QUANTISING LATENT APPEND (ffpa_attn_varlen_mla_fp8_fwd with kv_new): ffpa_mla_append_kernel's rules — one workgroup per new token row, positions at or
+// past the capacity dropped, page ids clamped to the pool, used[b] written for every sequence — with the row stored as e4m3 codes.
+template <typename T>
+__global__ __launch_bounds__(256) void ffpa_mla_fp8_append_kernel(const MlaFp8AppendArgs fa) {
+  const MlaAppendArgs& a = fa.a;
+  const int S = a.Snew > 0 ? a.Snew : 1;
+  const int b = blockIdx.x / S, i = blockIdx.x - b * S;
+  const int tid = threadIdx.x;
+  const int len = a.seqlens[b];
+  const int64_t base = len > 0 ? len : 0;  // (negative lengths act as 0, as in the attention kernels)
+  const int64_t pos = base + i;
+  const bool kv_row = i < a.Snew && pos < a.cap;  // (a position at or past the capacity is dropped)
+  int page = 0, row = 0;
+  if (kv_row) {
+    page = mla_append_page(a, b, pos);
+    row = (int)(pos % a.page_size);
+  }
+  if (i == 0 && tid == 0) {
+    const int64_t n = base + a.Snew;
+    a.used[b] = (int)(n < a.cap ? n : a.cap);
+  }
+  if (!kv_row) return;
+  fp8_append_row<T>(a, (const T*)a.kv_new + b * a.s_new[0] + i * a.s_new[1], (uint8_t*)a.cache + page * a.s_page + row * a.s_row, fa.inv, tid);
+}
+
+int launch_mla_fp8_append(int dtype, const MlaFp8AppendArgs& fa, hipStream_t stream) {
+  const int S = fa.a.Snew > 0 ? fa.a.Snew : 1;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(ffpa_mla_fp8_append_kernel<T>, dim3((unsigned)(fa.a.B * S)), dim3(256), 0, stream, fa);
+    return (int)hipGetLastError();
+  });
+}
+
+// THE QUANTISING LATENT APPEND OF A RAGGED STEP (ffpa_attn_mla_fp8_append_varlen): ffpa_mla_append_varlen_kernel's rules — one workgroup per token row t of kv_new
+// [T, Hkv, D] packed by cu_q, the row's sequence by cu_seqlens_find, rows from cu_q[B] on write nothing, lane l of workgroup x writes used[256 x + l] (the grid has
+// at least ceil(B / 256) workgroups) — and every read through a wave-uniform index (the search, the sequence's length, its page id) stands in front of the
+// kernel's first store (used[]).
+template <typename T>
+__global__ __launch_bounds__(256) void ffpa_mla_fp8_append_varlen_kernel(const MlaFp8AppendVarlenArgs fa) {
+  const MlaAppendVarlenArgs& va = fa.va;
+  const MlaAppendArgs& a = va.a;
+  const int t = blockIdx.x, tid = threadIdx.x;
+  const int b = cu_seqlens_find(va.cu_q, a.B, va.T, t);  // (a.B: a padding row)
+  const bool real = b < a.B;
+  const int i = real ? t - va.cu_q[b] : -1;  // (negative under a cu_q that does not ascend: the row is dropped, never a negative cache row)
+  const int len = real ? a.seqlens[b] : 0;
+  const int64_t base = len > 0 ? len : 0;
+  const int64_t pos = base + i;
+  const bool kv_row = real && i >= 0 && pos < a.cap;  // (pos / page_size < pages_per_row: the table's row is not left)
+  int page = 0, row = 0;
+  if (kv_row) {
+    page = mla_append_page(a, b, pos);
+    row = (int)(pos % a.page_size);
+  }
+  const int64_t s = (int64_t)t * 256 + tid;
+  if (s < a.B) {
+    const int slen = a.seqlens[s];
+    const int64_t n = (int64_t)(slen > 0 ? slen : 0) + (va.cu_q[s + 1] - va.cu_q[s]);
+    a.used[s] = (int)(n < a.cap ? n : a.cap);
+  }
+  if (!kv_row) return;
+  fp8_append_row<T>(a, (const T*)a.kv_new + t * a.s_new[1], (uint8_t*)a.cache + page * a.s_page + row * a.s_row, fa.inv, tid);
+}
+
+int launch_mla_fp8_append_varlen(int dtype, const MlaFp8AppendVarlenArgs& fa, hipStream_t stream) {
+  const unsigned used_wgs = (unsigned)((fa.va.a.B + 255) / 256);
+  const unsigned grid = (unsigned)fa.va.T > used_wgs ? (unsigned)fa.va.T : used_wgs;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(ffpa_mla_fp8_append_varlen_kernel<T>, dim3(grid), dim3(256), 0, stream, fa);
+    return (int)hipGetLastError();
+  });
+}
+#endif
+
+}  // namespace ffpa

@@ -21,6 +21,7 @@ compiled, ``cuda/__init__.py:94-99``).
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import threading
 
@@ -213,6 +214,17 @@ class FfpaMla(ctypes.Structure):
   ]
 
 
+class FfpaMlaFp8(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_mla_fp8`` (include/ffpa_attn.h): the per-tensor scale of the FP8 latent-cache call."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("kv_scale", ctypes.c_float),
+    ("reserved2", ctypes.c_float),
+  ]
+
+
 class FfpaMlaSparse(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_mla_sparse`` (include/ffpa_attn.h): the index list, its counts and the latent pool's geometry of the sparse latent call."""
 
@@ -366,6 +378,7 @@ _SOFTCAP = _WINDOW + [ctypes.c_float]
 _MLA = _PAGED + [_P(FfpaMla)]
 _MLA_SPARSE = [_P(FfpaVarlenFwdParams), _P(FfpaMlaSparse)]
 _MLA_TREE = _MLA + [_P(FfpaTreeMask)]
+_MLA_FP8 = _MLA + [_P(FfpaMlaFp8)]
 # Every function include/ffpa_attn.h declares: (symbol, argtypes, restype, since).  ``since``: the ABI version that added it (0: there from the start) — the
 # default library has them all; one loaded by path or through FFPA_HIP_LIBRARY (developer A/B runs load a saved build of an older commit) may lack those with
 # since > 0: calling one of those is then an AttributeError.
@@ -407,6 +420,12 @@ _BINDINGS = (
   ("ffpa_attn_varlen_mla_tree_fwd_workspace_bytes", _MLA_TREE, _SIZE, 7),
   ("ffpa_attn_varlen_mla_tree_fwd_compact_slots", _MLA_TREE + [_P(_INT)], _INT, 7),
   ("ffpa_attn_mla_append_varlen", [_P(FfpaMlaAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_fp8_fwd", _MLA_FP8 + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_fp8_fwd_plan", _MLA_FP8 + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_fp8_fwd_kernel", _MLA_FP8 + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_mla_fp8_fwd_workspace_bytes", _MLA_FP8, _SIZE, 7),
+  ("ffpa_attn_varlen_mla_fp8_fwd_compact_slots", _MLA_FP8 + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_mla_fp8_append_varlen", [_P(FfpaMlaAppendVarlenParams), _P(FfpaPagedKv), _P(FfpaMlaFp8), _VOID], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_fwd", _MLA_SPARSE + [_VOID], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_fwd_plan", _MLA_SPARSE + [_P(_INT)], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_fwd_kernel", _MLA_SPARSE + [_STR, _SIZE], _INT, 7),
@@ -505,7 +524,7 @@ def _stamped(cls):
   """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` / ``ffpa_window`` / ``ffpa_mla`` ride next to a versioned struct), the ABI version — filled in."""
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
-  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse):
+  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse, FfpaMlaFp8):
     p.abi_version = ABI_VERSION
   return p
 
@@ -1537,7 +1556,7 @@ def mla_compact_slots(group: int, seqlens_q: "list[int]", block_rows: int = 64) 
 def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seqlens_q: torch.Tensor, seqused_k: torch.Tensor, block_table: torch.Tensor,
                 max_seqlen_q: int, max_seqlen_k: int, causal: bool, softmax_scale: float, *, kv_new: "torch.Tensor | None" = None,
                 cache_seqlens: "torch.Tensor | None" = None, return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0,
-                tree_words: "torch.Tensor | None" = None):
+                tree_words: "torch.Tensor | None" = None, kv_scale: "float | None" = None):
   """One call of ``ffpa_attn_varlen_mla_fwd``: ``q [T, Hq, D]`` packed by ``cu_seqlens_q``, the latent pool ``kv_cache [num_pages, page_size, Hkv, D]`` (written in
   place by the append) with its int32 ``block_table [B, pages_per_seq]`` -> ``(o [T, Hq, head_dim_v], lse [Hq, T] fp32 | None)``.  The keys of KV head h are
   ``kv_cache[..., h, :]``, its values ``kv_cache[..., h, :head_dim_v]``.  ``seqused_k`` int32 ``[B]``: the key lengths — or, with ``kv_new [B, Snew, Hkv, D]``, the
@@ -1546,14 +1565,25 @@ def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seq
 
   ``tree_words`` (int64 device ``[B | 1, tokens]``, ``max_seqlen_q <= tokens <= 64``; ``mla_tree_forward`` is this call with it): a TREE MASK over the last rows
   of every sequence (``ffpa_attn_varlen_mla_tree_fwd``, its own kernel) — token t of sequence i sees every row in front of its sequence's last ``ntok_i`` rows and,
-  of those, row j iff bit j of ``tree_words[i, t]`` is set; ``causal`` is ignored: the launch and its plan are the causal latent launch's."""
+  of those, row j iff bit j of ``tree_words[i, t]`` is set; ``causal`` is ignored: the launch and its plan are the causal latent launch's.
+
+  ``kv_scale`` (a host float, finite and > 0; ``mla_fp8_forward`` is this call with it): the pool is ``torch.float8_e4m3fn`` — OCP e4m3 codes, K = kv_scale x K8 —
+  and the call is ``ffpa_attn_varlen_mla_fp8_fwd``, its own kernel; q, ``kv_new`` (quantised by the append, ``quantize_latent_rows``' definition) and o stay
+  bf16 / fp16.  Not with ``tree_words``."""
   tree = tree_words is not None
-  name = "ffpa_attn::_mla_tree_fwd_hip" if tree else "ffpa_attn::_mla_fwd_hip"
-  export = "ffpa_attn_varlen_mla_tree_fwd" if tree else "ffpa_attn_varlen_mla_fwd"
+  fp8 = kv_scale is not None
+  name = "ffpa_attn::_mla_tree_fwd_hip" if tree else "ffpa_attn::_mla_fp8_fwd_hip" if fp8 else "ffpa_attn::_mla_fwd_hip"
+  export = "ffpa_attn_varlen_mla_tree_fwd" if tree else "ffpa_attn_varlen_mla_fp8_fwd" if fp8 else "ffpa_attn_varlen_mla_fwd"
+  if fp8 and tree:
+    raise NotImplementedError(f"{name}: FP8 latent pools are not served under a tree mask")
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
-  if q.dtype not in _DTYPE or kv_cache.dtype != q.dtype:
+  if fp8:
+    if q.dtype not in _DTYPE or kv_cache.dtype != torch.float8_e4m3fn:
+      raise TypeError(f"{name} only supports fp16/bf16 q over a torch.float8_e4m3fn kv_cache (OCP e4m3, the chip's FP8 format), got {q.dtype}, {kv_cache.dtype}")
+    kv_scale = check_kv_scale(kv_scale, name)
+  elif q.dtype not in _DTYPE or kv_cache.dtype != q.dtype:
     raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
   if q.dim() != 3 or kv_cache.dim() != 4 or kv_cache.size(-1) != q.size(2):
     raise ValueError(f"{name}: q must be packed [T, Hq, D] and kv_cache paged [num_pages, page_size, Hkv, D] of q's head dim")
@@ -1574,8 +1604,9 @@ def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seq
     raise ValueError(f"{name}: block_table must be a 2-D int32 tensor [batch, pages_per_seq] (pages_per_seq >= 1) on q's device")
   if kv_cache.device != q.device or kv_cache.size(0) == 0:
     raise ValueError(f"{name}: kv_cache must be a non-empty pool on q's device")
-  if not _layout_ok(kv_cache, -3):
-    raise ValueError(f"{name}: kv_cache needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base (it is read, and written, in place)")
+  if not _layout_ok(kv_cache, -3) or (fp8 and any(st % 16 for st in kv_cache.stride()[:-1])):
+    raise ValueError(f"{name}: kv_cache needs head-dim stride 1, strides that are multiples of {16 if fp8 else 8} elements and a 16-byte aligned base (it is read, and "
+                     "written, in place)")
   if tree:
     if not isinstance(tree_words, torch.Tensor) or tree_words.dtype != torch.int64 or tree_words.dim() != 2 or tree_words.device != q.device:
       raise ValueError(f"{name}: tree_words must be a 2-D int64 tensor [batch or 1, tokens] on q's device")
@@ -1611,6 +1642,10 @@ def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seq
     m.seqlen_new, m.kv_new, m.cache_seqlens = kv_new.size(1), kv_new.data_ptr(), cache_seqlens.data_ptr()
     m.kv_new_stride[:] = list(kv_new.stride()[:3])
   args = (ctypes.byref(p), ctypes.byref(kv), ctypes.byref(m))
+  if fp8:
+    f8 = _stamped(FfpaMlaFp8)
+    f8.kv_scale = kv_scale
+    args += (ctypes.byref(f8),)
   if tree:
     tm = _stamped(FfpaTreeMask)
     tm.bits, tm.tokens = tree_words.data_ptr(), tree_words.size(1)
@@ -1621,7 +1656,7 @@ def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seq
     nbytes = 0
     if not (p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC):
       key = (id(lib), q.device.index or 0, p.dtype, batch, Hq, p.heads_kv, D, m.head_dim_v, p.max_seqlen_q, p.max_seqlen_kv, Tq, p.causal, p.flags, p.num_splits,
-             os.environ.get("FFPA_HIP_FAKE_CUS"), tm.tokens if tree else 0)
+             os.environ.get("FFPA_HIP_FAKE_CUS"), tm.tokens if tree else 0, fp8)
       nbytes = _cached_scratch(_MLA_SCRATCH, key, lambda: int(getattr(lib, export + "_workspace_bytes")(*args)))
     workspace = _hand_over_workspace(p, q.device, stream, nbytes)  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
@@ -1647,6 +1682,29 @@ def mla_tree_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, c
                      cache_seqlens=cache_seqlens, return_lse=return_lse, flags=flags, plan_out=plan_out, num_splits=num_splits, tree_words=tree_words)
 
 
+def check_kv_scale(kv_scale, name: str) -> float:
+  """``kv_scale`` of the FP8 latent calls -> a float: a host real number, finite and positive (a tensor would need a read-back: ``TypeError``)."""
+  if isinstance(kv_scale, torch.Tensor):
+    raise TypeError(f"{name}: kv_scale must be a host float, not a tensor (a device scalar would need a read-back to the host)")
+  if isinstance(kv_scale, bool) or not isinstance(kv_scale, (int, float)):
+    raise TypeError(f"{name}: kv_scale must be a real number, got {kv_scale!r}")
+  kv_scale = float(kv_scale)
+  if not math.isfinite(kv_scale) or not kv_scale > 0.0 or not math.isfinite(1.0 / kv_scale):
+    raise ValueError(f"{name}: kv_scale must be finite and > 0 (K = kv_scale * K8), got {kv_scale!r}")
+  return kv_scale
+
+
+def mla_fp8_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seqlens_q: torch.Tensor, seqused_k: torch.Tensor, block_table: torch.Tensor,
+                    max_seqlen_q: int, max_seqlen_k: int, causal: bool, softmax_scale: float, kv_scale: float, *, kv_new: "torch.Tensor | None" = None,
+                    cache_seqlens: "torch.Tensor | None" = None, return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
+  """One call of ``ffpa_attn_varlen_mla_fp8_fwd`` — the latent call over a ``torch.float8_e4m3fn`` pool with the per-tensor ``kv_scale`` (``mla_forward``'s
+  ``kv_scale``).  ``kv_new`` / ``cache_seqlens`` / ``flags`` / ``plan_out`` / ``num_splits`` as ``mla_forward`` (tests force or inspect the launch)."""
+  if kv_scale is None:
+    raise ValueError("ffpa_attn::_mla_fp8_fwd_hip: kv_scale is required")
+  return mla_forward(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, causal, softmax_scale, kv_new=kv_new,
+                     cache_seqlens=cache_seqlens, return_lse=return_lse, flags=flags, plan_out=plan_out, num_splits=num_splits, kv_scale=kv_scale)
+
+
 # kv_cache is written in place by the append (kv_new): the schema says so
 torch.library.define(
   f"{_OP_NAMESPACE}::_mla_fwd_hip",
@@ -1665,6 +1723,29 @@ def _mla_fwd_hip_torch_op(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, bloc
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_fwd_hip")
 def _mla_fwd_hip_fake(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k, softmax_scale, causal,
                       num_splits=0):
+  total_q, heads, _ = q.shape
+  return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
+
+
+# The FP8 latent call (ffpa_attn_with_kvcache_mla_fp8 / ffpa_attn_varlen_with_kvcache_mla_fp8): the latent call's op with the per-tensor scale — kv_cache (float8_e4m3fn)
+# is written in place by the quantising append (kv_new), as there
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_fp8_fwd_hip",
+  "(Tensor q, Tensor(a!) kv_cache, int head_dim_v, float kv_scale, Tensor cu_seqlens_q, Tensor(b!) seqused_k, Tensor block_table, Tensor? kv_new, "
+  "Tensor? cache_seqlens, int max_seqlen_q, int max_seqlen_k, float softmax_scale, int causal, int num_splits=0) -> (Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_fp8_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_fp8_fwd_hip_torch_op(q, kv_cache, head_dim_v, kv_scale, cu_seqlens_q, seqused_k, block_table, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k,
+                              softmax_scale, causal, num_splits=0):
+  return mla_fp8_forward(q, kv_cache, int(head_dim_v), cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, bool(causal), softmax_scale, kv_scale,
+                         kv_new=kv_new, cache_seqlens=cache_seqlens, return_lse=True, num_splits=num_splits)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_fp8_fwd_hip")
+def _mla_fp8_fwd_hip_fake(q, kv_cache, head_dim_v, kv_scale, cu_seqlens_q, seqused_k, block_table, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k,
+                          softmax_scale, causal, num_splits=0):
   total_q, heads, _ = q.shape
   return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
 
@@ -1831,17 +1912,24 @@ def _mla_sparse_fwd_hip_fake(q, kv_cache, head_dim_v, indices, topk_lens, softma
 
 
 # The latent append of a ragged step (ffpa_attn_varlen_with_kvcache_mla(kv=)): token rows packed by cu_seqlens_q, in front of the attention launch
-def mla_append_varlen(kv_cache: torch.Tensor, kv_new: torch.Tensor, cu_seqlens_q: torch.Tensor, cache_seqlens: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+def mla_append_varlen(kv_cache: torch.Tensor, kv_new: torch.Tensor, cu_seqlens_q: torch.Tensor, cache_seqlens: torch.Tensor, block_table: torch.Tensor,
+                      kv_scale: "float | None" = None) -> torch.Tensor:
   """One launch of ``ffpa_attn_mla_append_varlen``: ``kv_new [T, Hkv, D]``, packed by the int32 device ``cu_seqlens_q [B + 1]``, written into the latent pool
   ``kv_cache [num_pages, page_size, Hkv, D]`` in place through the int32 ``block_table [B, pages_per_seq]`` — token i of sequence b at cache position
   ``max(cache_seqlens[b], 0) + i``, every element stored once, positions at or past the capacity dropped, rows at or past ``cu_seqlens_q[B]`` not written
   -> ``seqused``: the int32 ``[B]`` post-append lengths ``min(max(cache_seqlens, 0) + Sq_b, capacity)``, sequences without a token included.  Asynchronous,
-  nothing read back to the host."""
-  name = "ffpa_attn::_mla_append_varlen_hip"
+  nothing read back to the host.  ``kv_scale`` (a host float): the pool is ``torch.float8_e4m3fn`` and the launch is ``ffpa_attn_mla_fp8_append_varlen`` — the
+  bf16 / fp16 rows of ``kv_new`` are stored as ``quantize_latent_rows(kv_new, kv_scale)``."""
+  fp8 = kv_scale is not None
+  name = "ffpa_attn::_mla_fp8_append_varlen_hip" if fp8 else "ffpa_attn::_mla_append_varlen_hip"
   if not kv_cache.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{kv_cache.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
-  if kv_cache.dtype not in _DTYPE or kv_new.dtype != kv_cache.dtype:
+  if fp8:
+    if kv_new.dtype not in _DTYPE or kv_cache.dtype != torch.float8_e4m3fn:
+      raise TypeError(f"{name} only supports fp16/bf16 kv_new into a torch.float8_e4m3fn kv_cache (OCP e4m3), got {kv_new.dtype}, {kv_cache.dtype}")
+    kv_scale = check_kv_scale(kv_scale, name)
+  elif kv_cache.dtype not in _DTYPE or kv_new.dtype != kv_cache.dtype:
     raise TypeError(f"{name} only supports fp16/bf16 kv_cache/kv_new of one dtype, got {kv_cache.dtype}, {kv_new.dtype}")
   if kv_cache.dim() != 4 or kv_new.dim() != 3 or tuple(kv_new.shape[1:]) != tuple(kv_cache.shape[2:]):
     raise ValueError(f"{name}: kv_new must be [T, Hkv={kv_cache.size(2)}, D={kv_cache.size(3)}] for the pool {tuple(kv_cache.shape)}, got {tuple(kv_new.shape)}")
@@ -1854,8 +1942,8 @@ def mla_append_varlen(kv_cache: torch.Tensor, kv_new: torch.Tensor, cu_seqlens_q
     raise ValueError(f"{name}: block_table must be a 2-D int32 tensor [batch, pages_per_seq] (pages_per_seq >= 1) on the cache's device")
   if kv_new.device != kv_cache.device or kv_cache.size(0) == 0:
     raise ValueError(f"{name}: kv_new and a non-empty kv_cache must be on one device")
-  if not _layout_ok(kv_cache, -3):
-    raise ValueError(f"{name}: kv_cache is written in place and needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base")
+  if not _layout_ok(kv_cache, -3) or (fp8 and any(st % 16 for st in kv_cache.stride()[:-1])):
+    raise ValueError(f"{name}: kv_cache is written in place and needs head-dim stride 1, strides that are multiples of {16 if fp8 else 8} elements and a 16-byte aligned base")
   kv_new = _rows(kv_new)
   cache_seqlens, cu_seqlens_q = cache_seqlens.contiguous(), cu_seqlens_q.contiguous()
   seqused = torch.empty((B,), dtype=torch.int32, device=kv_cache.device)
@@ -1863,14 +1951,19 @@ def mla_append_varlen(kv_cache: torch.Tensor, kv_new: torch.Tensor, cu_seqlens_q
   p.kv_cache = kv_cache.data_ptr()
   p.cu_seqlens_q, p.cache_seqlens, p.seqused = cu_seqlens_q.data_ptr(), cache_seqlens.data_ptr(), seqused.data_ptr()
   p.kv_cache_stride[:] = list(kv_cache.stride()[-3:-1])
-  p.batch, p.total_q, p.heads_kv, p.head_dim, p.dtype = B, kv_new.size(0), kv_cache.size(2), kv_cache.size(3), _DTYPE[kv_cache.dtype]
+  p.batch, p.total_q, p.heads_kv, p.head_dim, p.dtype = B, kv_new.size(0), kv_cache.size(2), kv_cache.size(3), _DTYPE[kv_new.dtype]
   if kv_new.size(0) > 0:
     p.kv_new = kv_new.data_ptr()
     p.kv_new_stride[:] = list(kv_new.stride()[:2])
   kv, block_table = _paged_kv_of(block_table, kv_cache, kv_cache)
-  rc = _call_on_stream(lib.ffpa_attn_mla_append_varlen, kv_cache.device, ctypes.byref(p), ctypes.byref(kv))
+  if fp8:
+    f8 = _stamped(FfpaMlaFp8)
+    f8.kv_scale = kv_scale
+    rc = _call_on_stream(lib.ffpa_attn_mla_fp8_append_varlen, kv_cache.device, ctypes.byref(p), ctypes.byref(kv), ctypes.byref(f8))
+  else:
+    rc = _call_on_stream(lib.ffpa_attn_mla_append_varlen, kv_cache.device, ctypes.byref(p), ctypes.byref(kv))
   if rc != 0:
-    _raise_status(lib, rc, "ffpa_attn_mla_append_varlen")
+    _raise_status(lib, rc, "ffpa_attn_mla_fp8_append_varlen" if fp8 else "ffpa_attn_mla_append_varlen")
   return seqused
 
 
@@ -1888,6 +1981,23 @@ def _mla_append_varlen_hip_torch_op(kv_cache, kv_new, cu_seqlens_q, cache_seqlen
 
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_append_varlen_hip")
 def _mla_append_varlen_hip_fake(kv_cache, kv_new, cu_seqlens_q, cache_seqlens, block_table):
+  return kv_cache.new_empty((cu_seqlens_q.size(0) - 1,), dtype=torch.int32)
+
+
+# ... and into an FP8 pool (ffpa_attn_varlen_with_kvcache_mla_fp8(kv=)): kv_cache (float8_e4m3fn) is written in place with the quantised rows
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_fp8_append_varlen_hip",
+  "(Tensor(a!) kv_cache, Tensor kv_new, float kv_scale, Tensor cu_seqlens_q, Tensor cache_seqlens, Tensor block_table) -> Tensor seqused",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_fp8_append_varlen_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_fp8_append_varlen_hip_torch_op(kv_cache, kv_new, kv_scale, cu_seqlens_q, cache_seqlens, block_table):
+  return mla_append_varlen(kv_cache, kv_new, cu_seqlens_q, cache_seqlens, block_table, kv_scale=kv_scale)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_fp8_append_varlen_hip")
+def _mla_fp8_append_varlen_hip_fake(kv_cache, kv_new, kv_scale, cu_seqlens_q, cache_seqlens, block_table):
   return kv_cache.new_empty((cu_seqlens_q.size(0) - 1,), dtype=torch.int32)
 
 

@@ -513,9 +513,16 @@ def _mla_identity_table(B: int, device) -> torch.Tensor:
   return t
 
 
-def _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits):
+def _mla_fp8_dtypes(name, q, kv_cache) -> None:
+  """The dtype rule of the FP8 latent calls: q in bf16 / fp16 over a ``torch.float8_e4m3fn`` cache."""
+  if q.dtype not in _DTYPES or kv_cache.dtype != torch.float8_e4m3fn:
+    raise TypeError(f"{name} only supports fp16/bf16 q over a torch.float8_e4m3fn kv_cache — OCP e4m3 is the chip's FP8 format; float8_e4m3fnuz and the e5m2 "
+                    f"formats are not served —, got {q.dtype}, {kv_cache.dtype}")
+
+
+def _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, fp8=False):
   """The argument checks of ``ffpa_attn_with_kvcache_mla`` — and of ``ffpa_attn_with_kvcache_mla_tree``, under its own ``name`` — in the order they are made
-  -> ``(capacity, cache_seqlens as an int32 [B] device tensor)``."""
+  -> ``(capacity, cache_seqlens as an int32 [B] device tensor)``.  ``fp8``: the cache is ``torch.float8_e4m3fn`` (``ffpa_attn_with_kvcache_mla_fp8``)."""
   if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
     raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
                     "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
@@ -526,7 +533,9 @@ def _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, so
       raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
     if t.requires_grad and torch.is_grad_enabled():
       raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
-  if q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
+  if fp8:
+    _mla_fp8_dtypes(name, q, kv_cache)
+  elif q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
     raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
   if q.dim() != 4 or kv_cache.dim() != 4:
     raise ValueError(f"{name}: q must be [B, Sq, Hq, D] and kv_cache 4-D")
@@ -577,7 +586,7 @@ def _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, so
     raise TypeError(f"{name}: cache_seqlens must be an int or an int32 tensor, got {type(cache_seqlens).__name__}")
   if kv is not None:
     if kv.dtype != q.dtype:
-      raise TypeError(f"{name}: kv must have the cache's dtype {q.dtype}, got {kv.dtype}")
+      raise TypeError(f"{name}: kv must have {'q' if fp8 else 'the cache'}'s dtype {q.dtype}, got {kv.dtype}")
     if kv.device != q.device:
       raise ValueError(f"{name}: kv must be on q's device, got {kv.device} and {q.device}")
     if kv.dim() != 4 or kv.size(0) != B or kv.size(2) != Hkv or kv.size(3) != D:
@@ -587,9 +596,9 @@ def _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, so
   return capacity, lens
 
 
-def _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, kv, softmax_scale, num_splits):
+def _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, kv, softmax_scale, num_splits, fp8=False):
   """The argument checks of ``ffpa_attn_varlen_with_kvcache_mla`` — and of ``ffpa_attn_varlen_with_kvcache_mla_tree``, under its own ``name`` — in the order they are
-  made -> ``capacity``."""
+  made -> ``capacity``.  ``fp8``: the cache is ``torch.float8_e4m3fn`` (``ffpa_attn_varlen_with_kvcache_mla_fp8``)."""
   if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
     raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
                     "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
@@ -601,7 +610,9 @@ def _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q,
   for nm, t in (("q", q), ("kv_cache", kv_cache)) + ((("kv", kv),) if kv is not None else ()):
     if t.requires_grad and torch.is_grad_enabled():
       raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
-  if q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
+  if fp8:
+    _mla_fp8_dtypes(name, q, kv_cache)
+  elif q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
     raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
   if q.dim() != 3 or kv_cache.dim() != 4:
     raise ValueError(f"{name}: q must be packed [T, Hq, D] and kv_cache 4-D")
@@ -653,7 +664,7 @@ def _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q,
       raise ValueError(f"{name}: a contiguous cache runs as a pool of one page per sequence: its capacity ({capacity}) must be a positive multiple of 64")
   if kv is not None:
     if kv.dtype != q.dtype:
-      raise TypeError(f"{name}: kv must have the cache's dtype {q.dtype}, got {kv.dtype}")
+      raise TypeError(f"{name}: kv must have {'q' if fp8 else 'the cache'}'s dtype {q.dtype}, got {kv.dtype}")
     if kv.device != q.device:
       raise ValueError(f"{name}: kv must be on q's device, got {kv.device} and {q.device}")
     if kv.dim() != 3 or kv.size(0) != T or kv.size(1) != Hkv or kv.size(2) != D:
@@ -705,8 +716,8 @@ def ffpa_attn_with_kvcache_mla(
   Nothing is read back to the host: the call (append + attention + the split launch's merge) captures into one HIP graph, and a replay follows
   ``cache_seqlens``, ``block_table`` and ``kv`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``.  NOT served here,
   each raises ``NotImplementedError`` naming the keyword: ``window_size``, ``softcap``, ``tree_mask``, ``cu_seqlens_q`` (ragged batches are
-  ``ffpa_attn_varlen_with_kvcache_mla``'s), shared-prefix cascades, ``rotary_cos`` / ``rotary_sin``, ALiBi, ``cache_batch_idx`` / ``cache_leftpad`` and FP8
-  latents (a dtype error)."""
+  ``ffpa_attn_varlen_with_kvcache_mla``'s), shared-prefix cascades, ``rotary_cos`` / ``rotary_sin``, ALiBi, ``cache_batch_idx`` / ``cache_leftpad``.  FP8
+  latents are a dtype error HERE: a ``torch.float8_e4m3fn`` cache is ``ffpa_attn_with_kvcache_mla_fp8``'s."""
   name = "ffpa_attn_with_kvcache_mla"
   if unsupported:
     raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no window, soft-cap, tree mask, cascade, rotary tables, ALiBi, batch "
@@ -731,6 +742,133 @@ def ffpa_attn_with_kvcache_mla(
   if not return_softmax_lse:
     return out
   return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+# ---- FP8 latent caches (OCP e4m3 codes, one per-tensor scale): ffpa_attn_with_kvcache_mla_fp8 / ffpa_attn_varlen_with_kvcache_mla_fp8
+_E4M3_MAX = 448.0
+
+
+def quantize_latent_rows(kv: torch.Tensor, kv_scale: float) -> torch.Tensor:
+  """Latent rows ``kv`` (bf16 / fp16 / fp32, any shape) -> ``torch.float8_e4m3fn`` codes under the per-tensor dequantisation factor ``kv_scale`` (K = kv_scale x
+  K8), by the definition the appends of the FP8 latent calls implement TO THE BIT::
+
+      code = rne_e4m3(clamp(float32(x) * float32(1 / kv_scale), -448, +448))
+
+  +-inf therefore saturates to +-448 and NaN stays NaN (torch's bare ``.to(torch.float8_e4m3fn)`` turns every overflow into NaN: the clamp is part of the
+  definition).  Round to nearest even, subnormals kept (the smallest is 2^-9; +-2^-10 is a tie and goes to +-0).  Plain torch on any device: what a caller fills
+  an FP8 pool with, and the reference the tests hold the append kernels to."""
+  from .hip import check_kv_scale
+
+  if not isinstance(kv, torch.Tensor) or not kv.is_floating_point():
+    raise TypeError(f"quantize_latent_rows: kv must be a floating-point tensor, got {type(kv).__name__}")
+  kv_scale = check_kv_scale(kv_scale, "quantize_latent_rows")
+  inv = torch.tensor(1.0 / kv_scale, dtype=torch.float32, device=kv.device)
+  v = kv.to(torch.float32) * inv
+  v = torch.where(torch.isnan(v), v, v.clamp(-_E4M3_MAX, _E4M3_MAX))
+  return v.to(torch.float8_e4m3fn)
+
+
+_MLA_FP8_UNSERVED = ("no window, soft-cap, tree mask, cascade, rotary tables, ALiBi, batch index or leftpad over the latent cache: rotate q_pe / k_pe before the "
+                     "call; FP8 pools are not served by the sparse and the tree call")
+
+
+def ffpa_attn_with_kvcache_mla_fp8(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  *,
+  kv_scale: float = 1.0,
+  kv: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor",
+  block_table: torch.Tensor | None = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  causal: bool = False,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """``ffpa_attn_with_kvcache_mla`` over an FP8 latent cache — the serving engines' ``kv_cache_dtype="fp8"`` for the MLA models: ``kv_cache`` is
+  ``torch.float8_e4m3fn`` (OCP e4m3, the chip's FP8 format; ``float8_e4m3fnuz`` and the e5m2 formats raise ``TypeError``), the whole 576-wide row under ONE
+  per-tensor scale, ``K = kv_scale * K8`` (the engines' ``k_scale``).  ``kv_scale`` is a host float, finite and positive (``ValueError``; a tensor raises
+  ``TypeError``: a device scalar would need a read-back).  ``q``, ``kv`` and the output are bf16 or fp16.
+
+  There is no FP8 arithmetic and no dequantised copy: every e4m3 value is exactly representable in bf16 and in fp16, so the kernel widens a tile on its way into
+  LDS and runs the 16-bit latent kernel's MFMAs on it, and the scale never touches an element — the scores are ``(softmax_scale * kv_scale) * q.K8`` and
+  ``O = kv_scale * sum p K8[:, :head_dim_v]``.  With a power-of-two ``kv_scale`` the call returns the bits of ``ffpa_attn_with_kvcache_mla(q,
+  kv_cache.to(q.dtype), ..., softmax_scale=softmax_scale * kv_scale) * kv_scale``.
+
+  ``kv [B, Snew, Hkv, D]`` (q's dtype) is QUANTISED by the append, one store per element, exactly as ``quantize_latent_rows(kv, kv_scale)`` — clamped to +-448,
+  NaN kept.  Everything else is the latent call's: the page pool ``[num_pages, page_size, Hkv, D]`` with a ``block_table`` or a contiguous ``[B, capacity, Hkv,
+  D]`` (strides multiples of 16 elements), the required ``softmax_scale``, the ``(576, 512)`` build, ``cache_seqlens``, ``causal``, ``num_splits``, one HIP graph for
+  append + attention + merge, inference only, unsupported keywords refused by name.  Not served: per-token / per-block scales, FP8 ``q``, FP8 pools in the sparse
+  and the tree call."""
+  name = "ffpa_attn_with_kvcache_mla_fp8"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} ({_MLA_FP8_UNSERVED}; a ragged batch — cu_seqlens_q — is "
+                              "ffpa_attn_varlen_with_kvcache_mla_fp8's)")
+  from . import hip  # (registers the ffpa_attn ops)
+
+  kv_scale = hip.check_kv_scale(kv_scale, name)
+  capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, fp8=True)
+  B, Sq, Hq, D = q.shape
+  out_shape = (B, Sq, Hq, head_dim_v)
+  if B == 0 or Sq == 0:
+    out = q.new_zeros(out_shape)
+    return (out, q.new_full((B, Hq, Sq), float("-inf"), dtype=torch.float32)) if return_softmax_lse else out
+  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
+  qp = q.reshape(B * Sq, Hq, D)
+  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
+  kv_new = kv if kv is not None and kv.size(1) > 0 else None
+  seqused = torch.empty((B,), dtype=torch.int32, device=q.device) if kv_new is not None else lens
+  o, lse = torch.ops.ffpa_attn._mla_fp8_fwd_hip(qp, kv_cache, head_dim_v, kv_scale, cu_q, seqused, table, kv_new, lens if kv_new is not None else None, Sq, capacity,
+                                                float(softmax_scale), 1 if causal else 0, num_splits)
+  out = o.view(*out_shape)
+  if not return_softmax_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+def ffpa_attn_varlen_with_kvcache_mla_fp8(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  cu_seqlens_q: torch.Tensor,
+  max_seqlen_q: int,
+  cache_seqlens: torch.Tensor,
+  block_table: torch.Tensor | None = None,
+  *,
+  kv_scale: float = 1.0,
+  kv: torch.Tensor | None = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  causal: bool = False,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """``ffpa_attn_varlen_with_kvcache_mla`` over an FP8 latent cache: the ragged step (``q [T, Hq, D]`` packed by ``cu_seqlens_q``) of
+  ``ffpa_attn_with_kvcache_mla_fp8`` — ``kv_cache`` is ``torch.float8_e4m3fn`` under the per-tensor ``kv_scale`` (a host float), ``q``, ``kv [T, Hkv, D]`` and the
+  output are bf16 or fp16, and ``kv`` is quantised by the ragged append as ``quantize_latent_rows(kv, kv_scale)``.  Shapes, the ``max_seqlen_q`` contract, the
+  compact grid, the returned ``out [T, Hq, head_dim_v]`` / ``lse [Hq, T]`` and the one-graph step are ``ffpa_attn_varlen_with_kvcache_mla``'s; every sequence's rows
+  are the bits of the uniform FP8 call on that sequence alone."""
+  name = "ffpa_attn_varlen_with_kvcache_mla_fp8"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} ({_MLA_FP8_UNSERVED})")
+  from . import hip  # (registers the ffpa_attn ops)
+
+  kv_scale = hip.check_kv_scale(kv_scale, name)
+  capacity = _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, kv, softmax_scale, num_splits, fp8=True)
+  T, Hq, D = q.shape
+  B = cu_seqlens_q.numel() - 1
+  if T == 0:
+    out = q.new_empty((0, Hq, head_dim_v))
+    return (out, torch.empty((Hq, 0), dtype=torch.float32, device=q.device)) if return_softmax_lse else out
+  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
+  seqused = cache_seqlens
+  if kv is not None:
+    seqused = torch.ops.ffpa_attn._mla_fp8_append_varlen_hip(kv_cache, kv, kv_scale, cu_seqlens_q, cache_seqlens, table)
+  o, lse = torch.ops.ffpa_attn._mla_fp8_fwd_hip(q, kv_cache, head_dim_v, kv_scale, cu_seqlens_q, seqused, table, None, None, max_seqlen_q, capacity,
+                                                float(softmax_scale), 1 if causal else 0, num_splits)
+  return (o, lse) if return_softmax_lse else o
 
 
 # ---- tree-mask attention over the MLA latent cache (the verification step of tree speculative decoding for the MLA models): ffpa_attn_with_kvcache_mla_tree
@@ -1164,7 +1302,8 @@ def ffpa_attn_varlen_with_kvcache_mla(
   (append + attention + the split launch's merge) captures into one HIP graph, and a replay follows ``q``, ``kv``, ``cu_seqlens_q`` (same T, same bound),
   ``cache_seqlens`` and ``block_table`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``.  NOT served here, each
   raises ``NotImplementedError`` naming the keyword: ``window_size``, ``softcap``, ``tree_mask``, shared-prefix cascades, ``rotary_cos`` / ``rotary_sin`` /
-  ``positions``, ALiBi, ``cache_batch_idx`` / ``cache_leftpad`` and FP8 latents (a dtype error)."""
+  ``positions``, ALiBi, ``cache_batch_idx`` / ``cache_leftpad``.  FP8 latents are a dtype error HERE: a ``torch.float8_e4m3fn`` cache is
+  ``ffpa_attn_varlen_with_kvcache_mla_fp8``'s."""
   name = "ffpa_attn_varlen_with_kvcache_mla"
   if unsupported:
     raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no window, soft-cap, tree mask, cascade, rotary tables or positions, "

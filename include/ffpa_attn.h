@@ -449,7 +449,8 @@ int ffpa_attn_varlen_softcap_fwd_kernel(const ffpa_varlen_fwd_params* p, const f
  * batch * ceil(group * max_seqlen_q / block rows) row tiles per KV head would find no row, the grid is sized by the rows there are:
  * ceil(group * total_q / block rows) + batch slots per KV head (an upper bound of the sum of the sequences' tiles), each finding its (sequence, row tile) on the
  * device; FFPA_FLAG_NO_COMPACT_GRID keeps the full grid (same order, same bits).  Packing and the non-temporal fetch stay launch-wide decisions.
- * Not served (use the other calls on a (kv, kv) pair): windows, soft-capping, FP8 latents; tree masks are ffpa_attn_varlen_mla_tree_fwd's (below).
+ * Not served (use the other calls on a (kv, kv) pair): windows, soft-capping; tree masks are ffpa_attn_varlen_mla_tree_fwd's and FP8 latents (a pool of e4m3
+ * codes under one scale) ffpa_attn_varlen_mla_fp8_fwd's (both below): this call reads 16-bit pools only.
  */
 typedef struct ffpa_mla {
   uint32_t struct_size;          /* sizeof(ffpa_mla), checked */
@@ -536,6 +537,39 @@ typedef struct ffpa_mla_append_varlen_params {
  * pointer, a wrong struct_size, a non-zero reserved, a misaligned base, seqused == cache_seqlens, head_dim % 8, a page_size that is no multiple of 64 — returns a
  * status before any device work.  Returns an ffpa_status. */
 int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, void* stream);
+
+/*
+ * FP8 LATENT CACHE — ffpa_attn_varlen_mla_fwd over a pool that holds OCP e4m3 codes (1 byte per element, "float8_e4m3fn"; NOT the fnuz format, NOT e5m2) with ONE
+ * per-tensor scale: K = kv_scale * K8, the serving engines' kv_cache_dtype = "fp8" for the latent cache of the MLA models.  ffpa_attn_varlen_mla_fwd with these
+ * changes:
+ *   * p->k is the FP8 pool.  p->dtype stays the dtype of q, o and kv_new (bf16 / fp16).  p->k_stride, kv->k_page_stride and the append's strides are in ELEMENTS OF
+ *     THE POOL (bytes); rows, heads and pages must be multiples of 16 elements apart (FFPA_ERR_BAD_STRIDE) and the base 16-byte aligned.
+ *   * there is no FP8 arithmetic.  Every e4m3 value is exactly a bf16 and exactly an fp16: the kernel widens a tile on its way into LDS and runs the 16-bit latent
+ *     kernel's MFMAs on it; the scale never touches an element — the scores are (softmax_scale * kv_scale) * q.K8 and O = kv_scale * sum p K8[:, :head_dim_v].
+ *     With a power-of-two kv_scale the call returns the bits of ffpa_attn_varlen_mla_fwd on the dequantised pool.
+ *   * m->kv_new (p->dtype) is QUANTISED by the append in front of the attention launch, one store per element:
+ *         code = rne_e4m3(clamp(float32(x) * float32(1 / kv_scale), -448, +448)),   NaN stays NaN, +-inf saturates to +-448.
+ *   * the plan is the latent call's with the cache priced at one byte per element (the non-temporal rule sees half the bytes).
+ * The kernel name reads ffpa_fwd_m16_mla_fp8_kernel<bf16, 576, dv=512>...  Not served: FP8 pools in the sparse and the tree call, per-token / per-block scales.
+ */
+typedef struct ffpa_mla_fp8 {
+  uint32_t struct_size; /* sizeof(ffpa_mla_fp8), checked */
+  uint32_t reserved;    /* 0, checked */
+  float kv_scale;       /* finite and > 0 (FFPA_ERR_BAD_SHAPE): the dequantisation factor, K = kv_scale * K8 */
+  float reserved2;      /* 0, checked */
+} ffpa_mla_fp8;
+
+/* Launch on `stream` of the CURRENT device, as ffpa_attn_varlen_mla_fwd.  Every bad argument — those of ffpa_attn_varlen_mla_fwd, a NULL f8, a wrong struct_size, a
+ * non-zero reserved field, a kv_scale that is not finite or not positive, a stride that is no multiple of 16 — returns a status before any device work. */
+int ffpa_attn_varlen_mla_fp8_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, void* stream);
+size_t ffpa_attn_varlen_mla_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8);
+int ffpa_attn_varlen_mla_fp8_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, int out[5]);
+int ffpa_attn_varlen_mla_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, char* buf, size_t n);
+int ffpa_attn_varlen_mla_fp8_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, int* slots);
+
+/* The ragged latent append (ffpa_attn_mla_append_varlen) into an FP8 pool: p->dtype is kv_new's (bf16 / fp16), p->kv_cache the FP8 pool, kv_cache_stride and
+ * kv->k_page_stride in elements of the pool (multiples of 16); every row is quantised as above, every rule of ffpa_attn_mla_append_varlen holds. */
+int ffpa_attn_mla_fp8_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, const ffpa_mla_fp8* f8, void* stream);
 
 /*
  * SPARSE (top-k indexed) attention over the MLA latent cache — DeepSeek-V3.2's "DeepSeek Sparse Attention" in its absorbed decode form, FlashMLA's sparse decode

@@ -292,6 +292,49 @@ def check_m16_shared(D=576, sw=None, quiet=False):
   return worst_k, worst_v, cyc_k, cyc_v
 
 
+def check_mla_fp8_writes(D=576, sw=None, quiet=False):
+  """The FP8 build of the MLA kernel (csrc/ffpa_fwd_m16_tile.inc under FFPA_M16_KV_FP8) has no LDS-DMA: lane l of piece p = wave PPW + i loads the EIGHT e4m3
+  bytes at  key x row bytes + ((slot ^ sw(key)) << 3)  of the FP8 tile (g = 64 p + l, key = g / SPR, slot = g % SPR), widens them to eight 16-bit elements and
+  writes them with ONE ds_write_b128 at  p x 1024 + 16 l.  Checks that
+    * the image those writes leave is, byte for byte, the image the LDS-DMA pieces of the 16-bit build leave (``check_m16_shared``'s: element e of the 16-byte
+      slot at dst comes from column 8 (slot ^ sw) + e of row key) — so every fragment read that function verifies holds for this build too;
+    * the writes are conflict-free under the bank rule of ds_write_b128 (MI355X_MICROARCH.md section LDS): 8 groups of 8 contiguous lanes, bank = (a / 4) % 32,
+      4 dwords per lane
+  -> (worst conflict of a group in ways: 1 = free, extra cycles summed over the tile's groups)."""
+  sw = sw or mla_sw
+  assert D > 512 and D % 128 == 64, "the MLA hook lives in the un-pipelined split-D loop"
+  BC = 32
+  RB8, RB16, SPR = D, D * 2, D // 8
+  PPW = BC * D * 2 // 4096
+  dma, fp8 = {}, {}
+  worst, cycles = 1, 0
+  for wave in range(4):
+    for i in range(PPW):
+      dsts = []
+      for lane in range(64):
+        g = (wave * PPW + i) * 64 + lane
+        key, slot = divmod(g, SPR)
+        dst = (wave * PPW + i) * 1024 + lane * 16
+        src16 = (slot ^ sw(D, key)) << 4  # the 16-bit build's source offset inside the row, bytes
+        src8 = (slot ^ sw(D, key)) << 3   # the FP8 build's
+        assert key < BC and 0 <= src8 and src8 + 8 <= RB8 and src16 + 16 <= RB16, (D, key, src8)
+        for e in range(8):
+          dma[dst + 2 * e] = (key, (src16 + 2 * e) // 2)  # (row, column) of the element at this LDS byte
+          fp8[dst + 2 * e] = (key, src8 + e)               # byte e of the pair widens to element e of the slot
+        dsts.append(dst)
+      for grp in range(8):
+        banks = {}
+        for lane in range(8 * grp, 8 * grp + 8):
+          for dw in range(4):
+            banks.setdefault(((dsts[lane] + 4 * dw) // 4) % 32, set()).add(dsts[lane] + 4 * dw)
+        m = max(len(v) for v in banks.values())
+        worst, cycles = max(worst, m), cycles + m - 1
+  assert len(dma) == BC * D and fp8 == dma, "the widened writes must leave the image of the LDS-DMA pieces"
+  if not quiet:
+    print(f"D={D:5d} MLA FP8 build BC={BC}: the ds_write_b128 image equals the LDS-DMA image; worst write conflict {worst}-way ({cycles} cycles)")
+  return worst, cycles
+
+
 def variants(D):
   """(D, ND) pairs the library instantiates: the prefill tiles and the short-query (split over 2 / 4 waves) tiles."""
   return [(D, 1 if D <= 512 else 2), (D, 4 if D % 128 == 0 else 2)]
@@ -304,6 +347,7 @@ if __name__ == "__main__":
       check_m16_shared(576, fn)
     print("kernel", end=" ")
     check_m16_shared(576)
+    check_mla_fp8_writes(576)
     sys.exit(0)
   for D in ([int(x) for x in sys.argv[1:]] or [64, 128, 192, 256, 320, 384, 448, 512, 576, 640, 704, 768, 832, 896, 960, 1024]):
     for d, nd in dict.fromkeys(variants(D)):
