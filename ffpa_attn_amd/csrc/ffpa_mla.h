@@ -42,6 +42,39 @@ struct MlaAppendVarlenArgs {
   int T;            // token rows of kv_new (>= cu_q[B]: the rest is padding)
 };
 
+// THE PLACEMENT RULE of the latent appends — the four kernels of ffpa_mla_inst.hip and ffpa_mla_fp8_inst.hip, which differ in how a workgroup finds its (b, i) and in
+// how it writes the row.  Everything here is read through wave-uniform indices: a scalar load as long as it stands in front of the kernel's first store, so every
+// kernel calls mla_append_place BEFORE it stores used[].
+//   The id of the page that holds cache position `pos` of sequence b, clamped to the pool.
+__device__ __forceinline__ int mla_append_page(const MlaAppendArgs& a, int b, int64_t pos) {
+  int page = a.table[(int64_t)b * a.bt_stride + pos / a.page_size];
+  page = page > 0 ? page : 0;
+  return page < a.num_pages - 1 ? page : a.num_pages - 1;
+}
+
+//   Where new row i of sequence b goes: cache position max(len, 0) + i (a negative length acts as 0, as in the attention kernels); `keep` is false — and the table
+//   is not read — for a position at or past the capacity and for a row the step does not have (`valid` false; i may be negative then, never a negative cache row).
+//   pos < cap means pos / page_size < pages_per_row: the table's row is not left.
+struct MlaAppendPlace {
+  bool keep;
+  int page, row;
+};
+__device__ __forceinline__ MlaAppendPlace mla_append_place(const MlaAppendArgs& a, int b, int i, int len, bool valid) {
+  const int64_t pos = (int64_t)(len > 0 ? len : 0) + i;
+  MlaAppendPlace at = {valid && pos < a.cap, 0, 0};
+  if (at.keep) {
+    at.page = mla_append_page(a, b, pos);
+    at.row = (int)(pos % a.page_size);
+  }
+  return at;
+}
+
+//   used[b] of a sequence of length `len` that brings n new rows (n = 0 included: every sequence gets one).
+__device__ __forceinline__ int mla_append_used(const MlaAppendArgs& a, int len, int n) {
+  const int64_t u = (int64_t)(len > 0 ? len : 0) + n;
+  return (int)(u < a.cap ? u : a.cap);
+}
+
 #define FFPA_DECL(D, DV) int launch_mla_paged_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaArgs& ma, hipStream_t stream);
 FFPA_FOR_EACH_MLA_BUILD(FFPA_DECL)
 #undef FFPA_DECL

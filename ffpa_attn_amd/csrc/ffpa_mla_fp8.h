@@ -26,14 +26,6 @@ struct MlaFp8AppendVarlenArgs {
   float inv;
 };
 
-// The page lookup of the latent appends (ffpa_mla_append_kernel's, restated for the quantising ones): the id of the page that holds cache position `pos` of
-// sequence b, clamped to the pool.  Read through wave-uniform indices: a scalar load as long as it stands in front of the kernel's first store.
-__device__ __forceinline__ int mla_append_page(const MlaAppendArgs& a, int b, int64_t pos) {
-  int page = a.table[(int64_t)b * a.bt_stride + pos / a.page_size];
-  page = page > 0 ? page : 0;
-  return page < a.num_pages - 1 ? page : a.num_pages - 1;
-}
-
 #define FFPA_DECL(D, DV) \
   int launch_mla_fp8_paged_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaFp8Args& ma, hipStream_t stream);
 FFPA_FOR_EACH_MLA_BUILD(FFPA_DECL)

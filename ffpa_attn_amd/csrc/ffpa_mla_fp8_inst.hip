@@ -22,20 +22,6 @@
 
 namespace ffpa {
 
-// (ffpa_paged_inst.hip's: a tile whose first row is `tile_base` — rows past the sequence's last key read as zeros, a tile at or past the end moves no bytes)
-template <int BC>
-__device__ __forceinline__ TileSrc tile_src_at(const char* tile_base, uint32_t row_bytes, int key0, int nkv, uint32_t RB) {
-  const int kc = key0 < nkv ? key0 : nkv;
-  int rows = nkv - kc;
-  rows = rows < BC ? rows : BC;
-  const uint32_t span = (uint32_t)(rows < 1 ? rows : 1) * ((uint32_t)(rows - 1) * row_bytes + (uint32_t)RB);
-  TileSrc t;
-  t.base = tile_base;
-  t.rows = rows;
-  t.rsrc = make_rsrc(t.base, span);
-  return t;
-}
-
 template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_mla_fp8_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa, const MlaFp8Args ma) {
   static_assert(D > 512 && D % 128 == 64, "the MLA hook lives in the un-pipelined split-D loop of the tile text");
@@ -108,8 +94,8 @@ __device__ __forceinline__ void fp8_append_row(const MlaAppendArgs& a, const T* 
   }
 }
 
-// THE QUANTISING LATENT APPEND (ffpa_attn_varlen_mla_fp8_fwd with kv_new): ffpa_mla_append_kernel's rules — one workgroup per new token row, positions at or
-// past the capacity dropped, page ids clamped to the pool, used[b] written for every sequence — with the row stored as e4m3 codes.
+// THE QUANTISING LATENT APPEND (ffpa_attn_varlen_mla_fp8_fwd with kv_new): ffpa_mla_append_kernel — one workgroup per new token row, placed by the rule of
+// ffpa_mla.h, used[b] written for every sequence — with the row stored as e4m3 codes.
 template <typename T>
 __global__ __launch_bounds__(256) void ffpa_mla_fp8_append_kernel(const MlaFp8AppendArgs fa) {
   const MlaAppendArgs& a = fa.a;
@@ -117,20 +103,10 @@ __global__ __launch_bounds__(256) void ffpa_mla_fp8_append_kernel(const MlaFp8Ap
   const int b = blockIdx.x / S, i = blockIdx.x - b * S;
   const int tid = threadIdx.x;
   const int len = a.seqlens[b];
-  const int64_t base = len > 0 ? len : 0;  // (negative lengths act as 0, as in the attention kernels)
-  const int64_t pos = base + i;
-  const bool kv_row = i < a.Snew && pos < a.cap;  // (a position at or past the capacity is dropped)
-  int page = 0, row = 0;
-  if (kv_row) {
-    page = mla_append_page(a, b, pos);
-    row = (int)(pos % a.page_size);
-  }
-  if (i == 0 && tid == 0) {
-    const int64_t n = base + a.Snew;
-    a.used[b] = (int)(n < a.cap ? n : a.cap);
-  }
-  if (!kv_row) return;
-  fp8_append_row<T>(a, (const T*)a.kv_new + b * a.s_new[0] + i * a.s_new[1], (uint8_t*)a.cache + page * a.s_page + row * a.s_row, fa.inv, tid);
+  const MlaAppendPlace at = mla_append_place(a, b, i, len, i < a.Snew);
+  if (i == 0 && tid == 0) a.used[b] = mla_append_used(a, len, a.Snew);
+  if (!at.keep) return;
+  fp8_append_row<T>(a, (const T*)a.kv_new + b * a.s_new[0] + i * a.s_new[1], (uint8_t*)a.cache + at.page * a.s_page + at.row * a.s_row, fa.inv, tid);
 }
 
 int launch_mla_fp8_append(int dtype, const MlaFp8AppendArgs& fa, hipStream_t stream) {
@@ -142,10 +118,9 @@ int launch_mla_fp8_append(int dtype, const MlaFp8AppendArgs& fa, hipStream_t str
   });
 }
 
-// THE QUANTISING LATENT APPEND OF A RAGGED STEP (ffpa_attn_mla_fp8_append_varlen): ffpa_mla_append_varlen_kernel's rules — one workgroup per token row t of kv_new
+// THE QUANTISING LATENT APPEND OF A RAGGED STEP (ffpa_attn_mla_fp8_append_varlen): ffpa_mla_append_varlen_kernel — one workgroup per token row t of kv_new
 // [T, Hkv, D] packed by cu_q, the row's sequence by cu_seqlens_find, rows from cu_q[B] on write nothing, lane l of workgroup x writes used[256 x + l] (the grid has
-// at least ceil(B / 256) workgroups) — and every read through a wave-uniform index (the search, the sequence's length, its page id) stands in front of the
-// kernel's first store (used[]).
+// at least ceil(B / 256) workgroups), every read through a wave-uniform index in front of the first store — with the row stored as e4m3 codes.
 template <typename T>
 __global__ __launch_bounds__(256) void ffpa_mla_fp8_append_varlen_kernel(const MlaFp8AppendVarlenArgs fa) {
   const MlaAppendVarlenArgs& va = fa.va;
@@ -153,24 +128,12 @@ __global__ __launch_bounds__(256) void ffpa_mla_fp8_append_varlen_kernel(const M
   const int t = blockIdx.x, tid = threadIdx.x;
   const int b = cu_seqlens_find(va.cu_q, a.B, va.T, t);  // (a.B: a padding row)
   const bool real = b < a.B;
-  const int i = real ? t - va.cu_q[b] : -1;  // (negative under a cu_q that does not ascend: the row is dropped, never a negative cache row)
-  const int len = real ? a.seqlens[b] : 0;
-  const int64_t base = len > 0 ? len : 0;
-  const int64_t pos = base + i;
-  const bool kv_row = real && i >= 0 && pos < a.cap;  // (pos / page_size < pages_per_row: the table's row is not left)
-  int page = 0, row = 0;
-  if (kv_row) {
-    page = mla_append_page(a, b, pos);
-    row = (int)(pos % a.page_size);
-  }
+  const int i = real ? t - va.cu_q[b] : -1;  // (negative under a cu_q that does not ascend: the row is dropped)
+  const MlaAppendPlace at = mla_append_place(a, b, i, real ? a.seqlens[b] : 0, real && i >= 0);
   const int64_t s = (int64_t)t * 256 + tid;
-  if (s < a.B) {
-    const int slen = a.seqlens[s];
-    const int64_t n = (int64_t)(slen > 0 ? slen : 0) + (va.cu_q[s + 1] - va.cu_q[s]);
-    a.used[s] = (int)(n < a.cap ? n : a.cap);
-  }
-  if (!kv_row) return;
-  fp8_append_row<T>(a, (const T*)a.kv_new + t * a.s_new[1], (uint8_t*)a.cache + page * a.s_page + row * a.s_row, fa.inv, tid);
+  if (s < a.B) a.used[s] = mla_append_used(a, a.seqlens[s], va.cu_q[s + 1] - va.cu_q[s]);
+  if (!at.keep) return;
+  fp8_append_row<T>(a, (const T*)a.kv_new + t * a.s_new[1], (uint8_t*)a.cache + at.page * a.s_page + at.row * a.s_row, fa.inv, tid);
 }
 
 int launch_mla_fp8_append_varlen(int dtype, const MlaFp8AppendVarlenArgs& fa, hipStream_t stream) {

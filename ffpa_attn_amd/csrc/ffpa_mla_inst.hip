@@ -20,20 +20,6 @@
 
 namespace ffpa {
 
-// (ffpa_paged_inst.hip's: a tile whose first row is `tile_base` — rows past the sequence's last key read as zeros, a tile at or past the end moves no bytes)
-template <int BC>
-__device__ __forceinline__ TileSrc tile_src_at(const char* tile_base, uint32_t row_bytes, int key0, int nkv, uint32_t RB) {
-  const int kc = key0 < nkv ? key0 : nkv;
-  int rows = nkv - kc;
-  rows = rows < BC ? rows : BC;
-  const uint32_t span = (uint32_t)(rows < 1 ? rows : 1) * ((uint32_t)(rows - 1) * row_bytes + (uint32_t)RB);
-  TileSrc t;
-  t.base = tile_base;
-  t.rows = rows;
-  t.rsrc = make_rsrc(t.base, span);
-  return t;
-}
-
 template <typename T, int D, bool NT = false>
 __global__ __launch_bounds__(256) void ffpa_fwd_m16_mla_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa, const MlaArgs ma) {
   static_assert(D > 512 && D % 128 == 64, "the MLA hook lives in the un-pipelined split-D loop of the tile text");
@@ -65,31 +51,26 @@ int FFPA_CAT(launch_mla_paged_d, FFPA_INST_D)(int dtype, int nt, const FwdArgs& 
 }
 
 #if FFPA_INST_D == 576  // (one copy of the append in the library: the first build's TU carries it)
-// THE LATENT APPEND (ffpa_attn_varlen_mla_fwd with kv_new): one workgroup per new token row; every 16-byte chunk of the row's Hkv heads is loaded and stored
-// once — the append of ffpa_kvcache_append.hip writes a K and a V cache, and here there is one cache.  16-bit elements of either dtype move as raw bytes.
-__global__ __launch_bounds__(256) void ffpa_mla_append_kernel(const MlaAppendArgs a) {
-  const int T = a.Snew > 0 ? a.Snew : 1;
-  const int b = blockIdx.x / T, i = blockIdx.x - b * T;
-  const int tid = threadIdx.x;
-  const int len = a.seqlens[b];
-  const int64_t base = len > 0 ? len : 0;  // (negative lengths act as 0, as in the attention kernels)
-  if (i == 0 && tid == 0) {
-    const int64_t n = base + a.Snew;
-    a.used[b] = (int)(n < a.cap ? n : a.cap);
-  }
-  const int64_t pos = base + i;
-  if (i >= a.Snew || pos >= a.cap) return;  // (a position at or past the capacity is dropped)
-  int page = a.table[(int64_t)b * a.bt_stride + pos / a.page_size];
-  page = page > 0 ? page : 0;
-  page = page < a.num_pages - 1 ? page : a.num_pages - 1;
-  const int row = (int)(pos % a.page_size);
-  const uint16_t* src = (const uint16_t*)a.kv_new + b * a.s_new[0] + i * a.s_new[1];
-  uint16_t* dst = (uint16_t*)a.cache + page * a.s_page + row * a.s_row;
+// One new row's Hkv heads as raw bytes — 16-bit elements of either dtype —, every 16-byte chunk loaded and stored once.
+__device__ __forceinline__ void mla_append_row(const MlaAppendArgs& a, const uint16_t* src, uint16_t* dst, int tid) {
   const int cpr = a.D / 8;  // 16-byte chunks per head row
   for (int e = tid; e < a.Hkv * cpr; e += 256) {
     const int h = e / cpr, c = e - h * cpr;
     *(u32x4*)(dst + h * a.s_head + c * 8) = *(const u32x4*)(src + h * a.s_new[2] + c * 8);
   }
+}
+
+// THE LATENT APPEND (ffpa_attn_varlen_mla_fwd with kv_new): one workgroup per new token row, placed by the rule of ffpa_mla.h and stored once — the append of
+// ffpa_kvcache_append.hip writes a K and a V cache, and here there is one cache.  used[b] by the workgroup of the sequence's first row (one at Snew == 0 too).
+__global__ __launch_bounds__(256) void ffpa_mla_append_kernel(const MlaAppendArgs a) {
+  const int T = a.Snew > 0 ? a.Snew : 1;
+  const int b = blockIdx.x / T, i = blockIdx.x - b * T;
+  const int tid = threadIdx.x;
+  const int len = a.seqlens[b];
+  const MlaAppendPlace at = mla_append_place(a, b, i, len, i < a.Snew);
+  if (i == 0 && tid == 0) a.used[b] = mla_append_used(a, len, a.Snew);
+  if (!at.keep) return;
+  mla_append_row(a, (const uint16_t*)a.kv_new + b * a.s_new[0] + i * a.s_new[1], (uint16_t*)a.cache + at.page * a.s_page + at.row * a.s_row, tid);
 }
 
 int launch_mla_append(const MlaAppendArgs& a, hipStream_t stream) {
@@ -99,9 +80,8 @@ int launch_mla_append(const MlaAppendArgs& a, hipStream_t stream) {
 }
 
 // THE LATENT APPEND OF A RAGGED STEP (ffpa_attn_mla_append_varlen): one workgroup per token row t of kv_new [T, Hkv, D] packed by cu_q.  The row finds its
-// sequence b by the two-cache ragged append's search (cu_seqlens_find) and is written once, as above, at cache position max(seqlens[b], 0) + (t - cu_q[b]);
-// rows from cu_q[B] on are padding and write nothing.  Everything read through a wave-uniform index — the search, the sequence's length, its page id — stands
-// in front of the kernel's first store (used[]): up to there the compiler reads the arrays with scalar loads.
+// sequence b by the two-cache ragged append's search (cu_seqlens_find) and is placed as above, as token t - cu_q[b]; rows from cu_q[B] on are padding and write
+// nothing.  Everything read through a wave-uniform index — the search, the sequence's length, its page id — stands in front of the kernel's first store (used[]).
 //   used[b] for EVERY b < B, sequences without a token too, so not by the token rows: lane l of workgroup x writes used[256 x + l]; the grid has at least
 //   ceil(B / 256) workgroups (T == 0 and T < B included).
 __global__ __launch_bounds__(256) void ffpa_mla_append_varlen_kernel(const MlaAppendVarlenArgs va) {
@@ -109,32 +89,12 @@ __global__ __launch_bounds__(256) void ffpa_mla_append_varlen_kernel(const MlaAp
   const int t = blockIdx.x, tid = threadIdx.x;
   const int b = cu_seqlens_find(va.cu_q, a.B, va.T, t);  // (a.B: a padding row)
   const bool real = b < a.B;
-  const int i = real ? t - va.cu_q[b] : -1;  // (negative under a cu_q that does not ascend: the row is dropped, never a negative cache row)
-  const int len = real ? a.seqlens[b] : 0;
-  const int64_t base = len > 0 ? len : 0;  // (negative lengths act as 0, as in the attention kernels)
-  const int64_t pos = base + i;
-  const bool kv_row = real && i >= 0 && pos < a.cap;  // (a position at or past the capacity is dropped; pos / page_size < pages_per_row: the table's row is not left)
-  int page = 0, row = 0;
-  if (kv_row) {
-    page = a.table[(int64_t)b * a.bt_stride + pos / a.page_size];
-    page = page > 0 ? page : 0;
-    page = page < a.num_pages - 1 ? page : a.num_pages - 1;
-    row = (int)(pos % a.page_size);
-  }
+  const int i = real ? t - va.cu_q[b] : -1;  // (negative under a cu_q that does not ascend: the row is dropped)
+  const MlaAppendPlace at = mla_append_place(a, b, i, real ? a.seqlens[b] : 0, real && i >= 0);
   const int64_t s = (int64_t)t * 256 + tid;
-  if (s < a.B) {
-    const int slen = a.seqlens[s];
-    const int64_t n = (int64_t)(slen > 0 ? slen : 0) + (va.cu_q[s + 1] - va.cu_q[s]);
-    a.used[s] = (int)(n < a.cap ? n : a.cap);
-  }
-  if (!kv_row) return;
-  const uint16_t* src = (const uint16_t*)a.kv_new + t * a.s_new[1];
-  uint16_t* dst = (uint16_t*)a.cache + page * a.s_page + row * a.s_row;
-  const int cpr = a.D / 8;  // 16-byte chunks per head row
-  for (int e = tid; e < a.Hkv * cpr; e += 256) {
-    const int h = e / cpr, c = e - h * cpr;
-    *(u32x4*)(dst + h * a.s_head + c * 8) = *(const u32x4*)(src + h * a.s_new[2] + c * 8);
-  }
+  if (s < a.B) a.used[s] = mla_append_used(a, a.seqlens[s], va.cu_q[s + 1] - va.cu_q[s]);
+  if (!at.keep) return;
+  mla_append_row(a, (const uint16_t*)a.kv_new + t * a.s_new[1], (uint16_t*)a.cache + at.page * a.s_page + at.row * a.s_row, tid);
 }
 
 int launch_mla_append_varlen(const MlaAppendVarlenArgs& va, hipStream_t stream) {

@@ -24,20 +24,6 @@
 
 namespace ffpa {
 
-// (ffpa_mla_inst.hip's: a tile whose first row is `tile_base` — rows past the sequence's last key read as zeros, a tile at or past the end moves no bytes)
-template <int BC>
-__device__ __forceinline__ TileSrc tile_src_at(const char* tile_base, uint32_t row_bytes, int key0, int nkv, uint32_t RB) {
-  const int kc = key0 < nkv ? key0 : nkv;
-  int rows = nkv - kc;
-  rows = rows < BC ? rows : BC;
-  const uint32_t span = (uint32_t)(rows < 1 ? rows : 1) * ((uint32_t)(rows - 1) * row_bytes + (uint32_t)RB);
-  TileSrc t;
-  t.base = tile_base;
-  t.rows = rows;
-  t.rsrc = make_rsrc(t.base, span);
-  return t;
-}
-
 // The kernel's argument block as the kernel below declares it (by value, in this order: the offsets are the code object's .args offsets 0 / 376 / 496 / 544), read
 // through the constant address space: uniform loads are scalar loads.
 struct MlaTreeKernArgsBlock {

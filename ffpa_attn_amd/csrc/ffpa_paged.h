@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "ffpa_common.h"
 #include "ffpa_launch.h"
 
 namespace ffpa {
@@ -23,6 +24,21 @@ struct PagedArgs {
   int tiles_per_page;      // page_size / block keys
   int num_pages;           // pages in the pool: ids are clamped to [0, num_pages)
 };
+
+// tile_src (ffpa_common.h) for a tile whose first row is `tile_base` (its page's row): the same row count and span — rows past the sequence's last key read as
+// zeros, a tile at or past the end moves no bytes.  What FFPA_M16_KV_SRC of ffpa_fwd_m16_paged_body.inc calls: the paged kernel and the latent kernels built on it.
+template <int BC>
+__device__ __forceinline__ TileSrc tile_src_at(const char* tile_base, uint32_t row_bytes, int key0, int nkv, uint32_t RB) {
+  const int kc = key0 < nkv ? key0 : nkv;
+  int rows = nkv - kc;
+  rows = rows < BC ? rows : BC;
+  const uint32_t span = (uint32_t)(rows < 1 ? rows : 1) * ((uint32_t)(rows - 1) * row_bytes + (uint32_t)RB);
+  TileSrc t;
+  t.base = tile_base;
+  t.rows = rows;
+  t.rsrc = make_rsrc(t.base, span);
+  return t;
+}
 
 #define FFPA_DECL(D) int launch_paged_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, hipStream_t stream);
 FFPA_FOR_EACH_VARLEN_HEAD_DIM(FFPA_DECL)

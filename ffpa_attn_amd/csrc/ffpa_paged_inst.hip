@@ -12,21 +12,6 @@
 
 namespace ffpa {
 
-// tile_src (ffpa_common.h) for a tile whose first row is `tile_base` (its page's row): the same row count and span — rows past the sequence's last key read as
-// zeros, a tile at or past the end moves no bytes
-template <int BC>
-__device__ __forceinline__ TileSrc tile_src_at(const char* tile_base, uint32_t row_bytes, int key0, int nkv, uint32_t RB) {
-  const int kc = key0 < nkv ? key0 : nkv;
-  int rows = nkv - kc;
-  rows = rows < BC ? rows : BC;
-  const uint32_t span = (uint32_t)(rows < 1 ? rows : 1) * ((uint32_t)(rows - 1) * row_bytes + (uint32_t)RB);
-  TileSrc t;
-  t.base = tile_base;
-  t.rows = rows;
-  t.rsrc = make_rsrc(t.base, span);
-  return t;
-}
-
 // PAGED KV CACHE (vLLM / SGLang / FlashAttention's flash_attn_with_kvcache(block_table=...)): K and V live in a pool of pages of page_size keys; sequence i's keys
 // are its row of the block table, in key order.  The same kernel as ffpa_fwd_m16_varlen_kernel — the same sequence lookup (ffpa_fwd_m16_varlen_seq.inc), workgroup
 // order, GQA row packing, KV splits, compact grid and NT build, the same tile text — but for where a K / V tile comes from: its descriptor's base is the tile's

@@ -1721,8 +1721,8 @@ def _mla_fwd_hip_torch_op(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, bloc
 
 
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_fwd_hip")
-def _mla_fwd_hip_fake(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k, softmax_scale, causal,
-                      num_splits=0):
+def _mla_out_fake(q, kv_cache, head_dim_v, *args, **kwargs):
+  """What the four latent attention ops return (this one, its FP8, tree and sparse twins: their argument lists differ behind ``head_dim_v``)."""
   total_q, heads, _ = q.shape
   return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
 
@@ -1743,11 +1743,7 @@ def _mla_fp8_fwd_hip_torch_op(q, kv_cache, head_dim_v, kv_scale, cu_seqlens_q, s
                          kv_new=kv_new, cache_seqlens=cache_seqlens, return_lse=True, num_splits=num_splits)
 
 
-@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_fp8_fwd_hip")
-def _mla_fp8_fwd_hip_fake(q, kv_cache, head_dim_v, kv_scale, cu_seqlens_q, seqused_k, block_table, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k,
-                          softmax_scale, causal, num_splits=0):
-  total_q, heads, _ = q.shape
-  return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
+torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_fp8_fwd_hip", _mla_out_fake)
 
 
 # The tree-mask latent call (ffpa_attn_with_kvcache_mla_tree / ffpa_attn_varlen_with_kvcache_mla_tree): the latent call's op with the mask words — kv_cache is written
@@ -1766,11 +1762,7 @@ def _mla_tree_fwd_hip_torch_op(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k,
                           cache_seqlens=cache_seqlens, return_lse=True, num_splits=num_splits)
 
 
-@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_tree_fwd_hip")
-def _mla_tree_fwd_hip_fake(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, tree_words, kv_new, cache_seqlens, max_seqlen_q, max_seqlen_k,
-                           softmax_scale, num_splits=0):
-  total_q, heads, _ = q.shape
-  return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
+torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_tree_fwd_hip", _mla_out_fake)
 
 
 # The sparse latent call (ffpa_attn_with_kvcache_mla_sparse): every query token attends to the latent rows its index list names
@@ -1905,10 +1897,7 @@ def _mla_sparse_fwd_hip_torch_op(q, kv_cache, head_dim_v, indices, topk_lens, so
   return mla_sparse_forward(q, kv_cache, int(head_dim_v), indices, topk_lens, softmax_scale, return_lse=True, num_splits=num_splits)
 
 
-@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_fwd_hip")
-def _mla_sparse_fwd_hip_fake(q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits=0):
-  total_q, heads, _ = q.shape
-  return q.new_empty((total_q, heads, head_dim_v)), q.new_empty((heads, total_q), dtype=torch.float32)
+torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_fwd_hip", _mla_out_fake)
 
 
 # The latent append of a ragged step (ffpa_attn_varlen_with_kvcache_mla(kv=)): token rows packed by cu_seqlens_q, in front of the attention launch
@@ -1979,9 +1968,14 @@ def _mla_append_varlen_hip_torch_op(kv_cache, kv_new, cu_seqlens_q, cache_seqlen
   return mla_append_varlen(kv_cache, kv_new, cu_seqlens_q, cache_seqlens, block_table)
 
 
+def _mla_append_varlen_fake(kv_cache, cu_seqlens_q):
+  """``seqused`` of the two ragged latent appends (this one and its FP8 twin)."""
+  return kv_cache.new_empty((cu_seqlens_q.size(0) - 1,), dtype=torch.int32)
+
+
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_append_varlen_hip")
 def _mla_append_varlen_hip_fake(kv_cache, kv_new, cu_seqlens_q, cache_seqlens, block_table):
-  return kv_cache.new_empty((cu_seqlens_q.size(0) - 1,), dtype=torch.int32)
+  return _mla_append_varlen_fake(kv_cache, cu_seqlens_q)
 
 
 # ... and into an FP8 pool (ffpa_attn_varlen_with_kvcache_mla_fp8(kv=)): kv_cache (float8_e4m3fn) is written in place with the quantised rows
@@ -1998,7 +1992,7 @@ def _mla_fp8_append_varlen_hip_torch_op(kv_cache, kv_new, kv_scale, cu_seqlens_q
 
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_fp8_append_varlen_hip")
 def _mla_fp8_append_varlen_hip_fake(kv_cache, kv_new, kv_scale, cu_seqlens_q, cache_seqlens, block_table):
-  return kv_cache.new_empty((cu_seqlens_q.size(0) - 1,), dtype=torch.int32)
+  return _mla_append_varlen_fake(kv_cache, cu_seqlens_q)
 
 
 # The KV-cache append + rotary (ffpa_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)): the prepare launch in front of the attention launch

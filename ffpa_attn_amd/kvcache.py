@@ -513,36 +513,44 @@ def _mla_identity_table(B: int, device) -> torch.Tensor:
   return t
 
 
-def _mla_fp8_dtypes(name, q, kv_cache) -> None:
-  """The dtype rule of the FP8 latent calls: q in bf16 / fp16 over a ``torch.float8_e4m3fn`` cache."""
-  if q.dtype not in _DTYPES or kv_cache.dtype != torch.float8_e4m3fn:
-    raise TypeError(f"{name} only supports fp16/bf16 q over a torch.float8_e4m3fn kv_cache — OCP e4m3 is the chip's FP8 format; float8_e4m3fnuz and the e5m2 "
-                    f"formats are not served —, got {q.dtype}, {kv_cache.dtype}")
-
-
-def _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, fp8=False):
-  """The argument checks of ``ffpa_attn_with_kvcache_mla`` — and of ``ffpa_attn_with_kvcache_mla_tree``, under its own ``name`` — in the order they are made
-  -> ``(capacity, cache_seqlens as an int32 [B] device tensor)``.  ``fp8``: the cache is ``torch.float8_e4m3fn`` (``ffpa_attn_with_kvcache_mla_fp8``)."""
+def _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, fp8=False, ragged=None):
+  """The argument checks of the six latent calls under their own ``name``, every rule written once, in the order the uniform calls (``ragged`` None) and the
+  ragged calls (``ragged = (cu_seqlens_q, max_seqlen_q)``) make them -> ``(capacity, cache_seqlens as an int32 [B] device tensor)``.  The two orders differ, and
+  tests/golden/mla_front_calls.json holds both: the uniform calls test tensor and grad per tensor and ``cache_seqlens`` behind the pool; the ragged ones test
+  every tensor, then every grad, and ``cache_seqlens`` in front of the pool.  ``fp8``: the cache is ``torch.float8_e4m3fn`` (the ``_fp8`` calls)."""
   if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
     raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
                     "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
   if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
     raise TypeError(f"{name}: softmax_scale must be a real number, got {softmax_scale!r}")
-  for nm, t in (("q", q), ("kv_cache", kv_cache)) + ((("kv", kv),) if kv is not None else ()):
-    if not isinstance(t, torch.Tensor):
-      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
-    if t.requires_grad and torch.is_grad_enabled():
-      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  named = (("q", q), ("kv_cache", kv_cache), ("kv", kv)) if kv is not None else (("q", q), ("kv_cache", kv_cache))
+  if ragged is None:  # (tensor and grad, tensor by tensor)
+    for nm, t in named:
+      if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+      if t.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  else:  # (every tensor, then every grad)
+    cu_seqlens_q, max_seqlen_q = ragged
+    for nm, t in (("q", q), ("kv_cache", kv_cache), ("cu_seqlens_q", cu_seqlens_q), ("cache_seqlens", cache_seqlens)) + named[2:]:
+      if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+    for nm, t in named:
+      if t.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
   if fp8:
-    _mla_fp8_dtypes(name, q, kv_cache)
+    if q.dtype not in _DTYPES or kv_cache.dtype != torch.float8_e4m3fn:
+      raise TypeError(f"{name} only supports fp16/bf16 q over a torch.float8_e4m3fn kv_cache — OCP e4m3 is the chip's FP8 format; float8_e4m3fnuz and the e5m2 "
+                      f"formats are not served —, got {q.dtype}, {kv_cache.dtype}")
   elif q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
     raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
-  if q.dim() != 4 or kv_cache.dim() != 4:
-    raise ValueError(f"{name}: q must be [B, Sq, Hq, D] and kv_cache 4-D")
-  B, Sq, Hq, D = q.shape
-  Hkv = kv_cache.size(2)
-  if kv_cache.size(3) != D:
-    raise ValueError(f"{name}: head dim of the cache ({kv_cache.size(3)}) differs from q's ({D})")
+  if q.dim() != (4 if ragged is None else 3) or kv_cache.dim() != 4:
+    raise ValueError(f"{name}: q must be {'[B, Sq, Hq, D]' if ragged is None else 'packed [T, Hq, D]'} and kv_cache 4-D")
+  shape, pool = q.shape, kv_cache.shape  # (read once: every .size() is a call into torch)
+  rows, Hq, D = shape[0], shape[-2], shape[-1]  # (rows: B of a uniform call, T of a ragged one)
+  Hkv = pool[2]
+  if pool[3] != D:
+    raise ValueError(f"{name}: head dim of the cache ({pool[3]}) differs from q's ({D})")
   if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int):
     raise TypeError(f"{name}: head_dim_v must be an int, got {head_dim_v!r}")
   if D % 64 != 0 or head_dim_v <= 0 or head_dim_v % 64 != 0 or head_dim_v > D:
@@ -557,121 +565,119 @@ def _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, so
     raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
   if kv_cache.device != q.device:
     raise ValueError(f"{name}: q / kv_cache must be on one device, got {q.device}, {kv_cache.device}")
+  if ragged is None:
+    B = rows
+  else:
+    if cu_seqlens_q.dtype != torch.int32:
+      raise TypeError(f"{name}: cu_seqlens_q must be int32, got {cu_seqlens_q.dtype}")
+    if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.stride(0) != 1 or cu_seqlens_q.device != q.device:
+      raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor [batch + 1] of unit stride on q's device, got {tuple(cu_seqlens_q.shape)} on {cu_seqlens_q.device}")
+    B = cu_seqlens_q.numel() - 1
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or (rows > 0 and max_seqlen_q < 1):
+      raise ValueError(f"{name}: max_seqlen_q must be a host int >= 1 (>= 0 without a token) that bounds every sequence's tokens, got {max_seqlen_q!r}")
+    if cache_seqlens.dtype != torch.int32:
+      raise TypeError(f"{name}: cache_seqlens must be int32, got {cache_seqlens.dtype}")
+    if cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
+      raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [batch={B}] on q's device, got {tuple(cache_seqlens.shape)} on {cache_seqlens.device}")
   if block_table is not None:
     if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B:
       raise ValueError(f"{name}: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
     if block_table.size(1) == 0:
       raise ValueError(f"{name}: block_table needs at least one page per sequence")
-    page_size = kv_cache.size(1)
+    page_size = pool[1]
     if page_size <= 0 or page_size % 64 != 0:
       raise ValueError(f"{name}: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
     if block_table.device != q.device:
       raise ValueError(f"{name}: block_table must be on q's device, got {block_table.device} and {q.device}")
     capacity = block_table.size(1) * page_size
   else:
-    if kv_cache.size(0) != B:
-      raise ValueError(f"{name}: kv_cache [B, capacity, Hkv, D] must have q's batch ({B}), got {kv_cache.size(0)}")
-    capacity = kv_cache.size(1)
+    if pool[0] != B:
+      raise ValueError(f"{name}: kv_cache [B, capacity, Hkv, D] must have {'q' if ragged is None else 'cu_seqlens_q'}'s batch ({B}), got {pool[0]}")
+    capacity = pool[1]
     if capacity <= 0 or capacity % 64 != 0:
       raise ValueError(f"{name}: a contiguous cache runs as a pool of one page per sequence: its capacity ({capacity}) must be a positive multiple of 64")
-  if isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
-    if cache_seqlens < 0:
-      raise ValueError(f"{name}: cache_seqlens must be non-negative, got {cache_seqlens}")
-    lens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
-  elif isinstance(cache_seqlens, torch.Tensor):
-    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
+  if ragged is None:  # (an int, or the tensor the ragged calls have tested above)
+    if isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
+      if cache_seqlens < 0:
+        raise ValueError(f"{name}: cache_seqlens must be non-negative, got {cache_seqlens}")
+      cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
+    elif not isinstance(cache_seqlens, torch.Tensor):
+      raise TypeError(f"{name}: cache_seqlens must be an int or an int32 tensor, got {type(cache_seqlens).__name__}")
+    elif cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
       raise ValueError(f"{name}: cache_seqlens must be an int or an int32 tensor [batch={B}] on q's device")
-    lens = cache_seqlens
-  else:
-    raise TypeError(f"{name}: cache_seqlens must be an int or an int32 tensor, got {type(cache_seqlens).__name__}")
   if kv is not None:
     if kv.dtype != q.dtype:
       raise TypeError(f"{name}: kv must have {'q' if fp8 else 'the cache'}'s dtype {q.dtype}, got {kv.dtype}")
     if kv.device != q.device:
       raise ValueError(f"{name}: kv must be on q's device, got {kv.device} and {q.device}")
-    if kv.dim() != 4 or kv.size(0) != B or kv.size(2) != Hkv or kv.size(3) != D:
-      raise ValueError(f"{name}: kv must be [B={B}, Snew, Hkv={Hkv}, D={D}], got {tuple(kv.shape)}")
+    new = kv.shape
+    if len(new) != len(shape) or new[0] != rows or new[-2] != Hkv or new[-1] != D:
+      form = f"[B={B}, Snew, Hkv={Hkv}, D={D}]" if ragged is None else f"[T={rows}, Hkv={Hkv}, D={D}] (packed by cu_seqlens_q like q)"
+      raise ValueError(f"{name}: kv must be {form}, got {tuple(new)}")
     if kv.stride(-1) != 1:
       raise ValueError(f"{name}: kv must have a contiguous last dimension")
-  return capacity, lens
+  return capacity, cache_seqlens
 
 
-def _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, kv, softmax_scale, num_splits, fp8=False):
-  """The argument checks of ``ffpa_attn_varlen_with_kvcache_mla`` — and of ``ffpa_attn_varlen_with_kvcache_mla_tree``, under its own ``name`` — in the order they are
-  made -> ``capacity``.  ``fp8``: the cache is ``torch.float8_e4m3fn`` (``ffpa_attn_varlen_with_kvcache_mla_fp8``)."""
-  if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
-    raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
-                    "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
-  if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
-    raise TypeError(f"{name}: softmax_scale must be a real number, got {softmax_scale!r}")
-  for nm, t in (("q", q), ("kv_cache", kv_cache), ("cu_seqlens_q", cu_seqlens_q), ("cache_seqlens", cache_seqlens)) + ((("kv", kv),) if kv is not None else ()):
-    if not isinstance(t, torch.Tensor):
-      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
-  for nm, t in (("q", q), ("kv_cache", kv_cache)) + ((("kv", kv),) if kv is not None else ()):
-    if t.requires_grad and torch.is_grad_enabled():
-      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
-  if fp8:
-    _mla_fp8_dtypes(name, q, kv_cache)
-  elif q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
-    raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
-  if q.dim() != 3 or kv_cache.dim() != 4:
-    raise ValueError(f"{name}: q must be packed [T, Hq, D] and kv_cache 4-D")
+# The step behind _mla_check, once per kind.  ``op`` names the attention op: "mla" is ffpa_attn::_mla_fwd_hip; "fp8" its FP8 twin, with ``extra`` the kv_scale; "tree"
+# its tree-mask twin, with ``extra`` the caller's tree_mask — checked here, behind the empty returns that never look at it — and no causal flag.  The ops are
+# registered: _mla_check has imported .hip.
+def _mla_step(name, op, extra, q, kv_cache, head_dim_v, kv, lens, block_table, capacity, softmax_scale, causal, num_splits, return_softmax_lse):
+  """The uniform step: append (``kv``) + attention in ONE call of the attention op, q as a packed batch of B sequences of Sq tokens."""
+  B, Sq, Hq, D = q.shape
+  if B == 0 or Sq == 0:
+    out = q.new_zeros((B, Sq, Hq, head_dim_v))
+    return (out, q.new_full((B, Hq, Sq), float("-inf"), dtype=torch.float32)) if return_softmax_lse else out
+  if op == "tree":
+    extra = _tree_words(extra, B, Sq, q.device, name, wide=True)  # (from here on `extra` is the packed words the tree op takes, no longer the caller's mask)
+  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
+  qp = q.reshape(B * Sq, Hq, D)
+  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
+  kv_new = kv if kv is not None and kv.size(1) > 0 else None
+  seqused = torch.empty((B,), dtype=torch.int32, device=q.device) if kv_new is not None else lens
+  before = lens if kv_new is not None else None
+  if op == "tree":
+    o, lse = torch.ops.ffpa_attn._mla_tree_fwd_hip(qp, kv_cache, head_dim_v, cu_q, seqused, table, extra, kv_new, before, Sq, capacity, float(softmax_scale), num_splits)
+  elif op == "fp8":
+    o, lse = torch.ops.ffpa_attn._mla_fp8_fwd_hip(qp, kv_cache, head_dim_v, extra, cu_q, seqused, table, kv_new, before, Sq, capacity, float(softmax_scale),
+                                                  1 if causal else 0, num_splits)
+  else:
+    o, lse = torch.ops.ffpa_attn._mla_fwd_hip(qp, kv_cache, head_dim_v, cu_q, seqused, table, kv_new, before, Sq, capacity, float(softmax_scale), 1 if causal else 0,
+                                              num_splits)
+  out = o.view(B, Sq, Hq, head_dim_v)
+  if not return_softmax_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+def _mla_step_varlen(name, op, extra, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, kv, lens, block_table, capacity, softmax_scale, causal, num_splits,
+                     return_softmax_lse):
+  """The ragged step: the per-token append launch (``kv``), then the attention launch over the lengths it returns."""
   T, Hq, D = q.shape
-  Hkv = kv_cache.size(2)
-  if kv_cache.size(3) != D:
-    raise ValueError(f"{name}: head dim of the cache ({kv_cache.size(3)}) differs from q's ({D})")
-  if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int):
-    raise TypeError(f"{name}: head_dim_v must be an int, got {head_dim_v!r}")
-  if D % 64 != 0 or head_dim_v <= 0 or head_dim_v % 64 != 0 or head_dim_v > D:
-    raise ValueError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}): both must be multiples of 64 with 0 < head_dim_v <= D")
-  from .hip import MLA_BUILDS
-
-  if (D, head_dim_v) not in MLA_BUILDS:
-    raise NotImplementedError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
-  if Hkv == 0 or Hq % Hkv != 0:
-    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of the latent num_heads ({Hkv})")
-  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
-    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
-  if kv_cache.device != q.device:
-    raise ValueError(f"{name}: q / kv_cache must be on one device, got {q.device}, {kv_cache.device}")
-  if cu_seqlens_q.dtype != torch.int32:
-    raise TypeError(f"{name}: cu_seqlens_q must be int32, got {cu_seqlens_q.dtype}")
-  if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.stride(0) != 1 or cu_seqlens_q.device != q.device:
-    raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor [batch + 1] of unit stride on q's device, got {tuple(cu_seqlens_q.shape)} on {cu_seqlens_q.device}")
   B = cu_seqlens_q.numel() - 1
-  if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or (T > 0 and max_seqlen_q < 1):
-    raise ValueError(f"{name}: max_seqlen_q must be a host int >= 1 (>= 0 without a token) that bounds every sequence's tokens, got {max_seqlen_q!r}")
-  if cache_seqlens.dtype != torch.int32:
-    raise TypeError(f"{name}: cache_seqlens must be int32, got {cache_seqlens.dtype}")
-  if cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
-    raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [batch={B}] on q's device, got {tuple(cache_seqlens.shape)} on {cache_seqlens.device}")
-  if block_table is not None:
-    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B:
-      raise ValueError(f"{name}: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
-    if block_table.size(1) == 0:
-      raise ValueError(f"{name}: block_table needs at least one page per sequence")
-    page_size = kv_cache.size(1)
-    if page_size <= 0 or page_size % 64 != 0:
-      raise ValueError(f"{name}: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
-    if block_table.device != q.device:
-      raise ValueError(f"{name}: block_table must be on q's device, got {block_table.device} and {q.device}")
-    capacity = block_table.size(1) * page_size
-  else:
-    if kv_cache.size(0) != B:
-      raise ValueError(f"{name}: kv_cache [B, capacity, Hkv, D] must have cu_seqlens_q's batch ({B}), got {kv_cache.size(0)}")
-    capacity = kv_cache.size(1)
-    if capacity <= 0 or capacity % 64 != 0:
-      raise ValueError(f"{name}: a contiguous cache runs as a pool of one page per sequence: its capacity ({capacity}) must be a positive multiple of 64")
+  if T == 0:
+    out = q.new_empty((0, Hq, head_dim_v))
+    return (out, torch.empty((Hq, 0), dtype=torch.float32, device=q.device)) if return_softmax_lse else out
+  if op == "tree":
+    extra = _tree_words(extra, B, max_seqlen_q, q.device, name, wide=True)  # (from here on `extra` is the packed words the tree op takes, no longer the caller's mask)
+  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
+  seqused = lens
   if kv is not None:
-    if kv.dtype != q.dtype:
-      raise TypeError(f"{name}: kv must have {'q' if fp8 else 'the cache'}'s dtype {q.dtype}, got {kv.dtype}")
-    if kv.device != q.device:
-      raise ValueError(f"{name}: kv must be on q's device, got {kv.device} and {q.device}")
-    if kv.dim() != 3 or kv.size(0) != T or kv.size(1) != Hkv or kv.size(2) != D:
-      raise ValueError(f"{name}: kv must be [T={T}, Hkv={Hkv}, D={D}] (packed by cu_seqlens_q like q), got {tuple(kv.shape)}")
-    if kv.stride(-1) != 1:
-      raise ValueError(f"{name}: kv must have a contiguous last dimension")
-  return capacity
+    # the prepare launch: the step's latent rows into the cache (in place) and the post-append lengths — read by the attention launch below on the same stream
+    if op == "fp8":
+      seqused = torch.ops.ffpa_attn._mla_fp8_append_varlen_hip(kv_cache, kv, extra, cu_seqlens_q, lens, table)
+    else:
+      seqused = torch.ops.ffpa_attn._mla_append_varlen_hip(kv_cache, kv, cu_seqlens_q, lens, table)
+  if op == "tree":
+    o, lse = torch.ops.ffpa_attn._mla_tree_fwd_hip(q, kv_cache, head_dim_v, cu_seqlens_q, seqused, table, extra, None, None, max_seqlen_q, capacity,
+                                                   float(softmax_scale), num_splits)
+  elif op == "fp8":
+    o, lse = torch.ops.ffpa_attn._mla_fp8_fwd_hip(q, kv_cache, head_dim_v, extra, cu_seqlens_q, seqused, table, None, None, max_seqlen_q, capacity,
+                                                  float(softmax_scale), 1 if causal else 0, num_splits)
+  else:
+    o, lse = torch.ops.ffpa_attn._mla_fwd_hip(q, kv_cache, head_dim_v, cu_seqlens_q, seqused, table, None, None, max_seqlen_q, capacity, float(softmax_scale),
+                                              1 if causal else 0, num_splits)
+  return (o, lse) if return_softmax_lse else o
 
 
 def ffpa_attn_with_kvcache_mla(
@@ -724,24 +730,7 @@ def ffpa_attn_with_kvcache_mla(
                               "index or leftpad over the latent cache: rotate q_pe / k_pe before the call; a ragged batch — cu_seqlens_q — is "
                               "ffpa_attn_varlen_with_kvcache_mla's)")
   capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits)
-  B, Sq, Hq, D = q.shape
-  from . import hip  # (registers the ffpa_attn ops)
-
-  out_shape = (B, Sq, Hq, head_dim_v)
-  if B == 0 or Sq == 0:
-    out = q.new_zeros(out_shape)
-    return (out, q.new_full((B, Hq, Sq), float("-inf"), dtype=torch.float32)) if return_softmax_lse else out
-  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
-  qp = q.reshape(B * Sq, Hq, D)
-  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
-  kv_new = kv if kv is not None and kv.size(1) > 0 else None
-  seqused = torch.empty((B,), dtype=torch.int32, device=q.device) if kv_new is not None else lens
-  o, lse = torch.ops.ffpa_attn._mla_fwd_hip(qp, kv_cache, head_dim_v, cu_q, seqused, table, kv_new, lens if kv_new is not None else None, Sq, capacity,
-                                            float(softmax_scale), 1 if causal else 0, num_splits)
-  out = o.view(*out_shape)
-  if not return_softmax_lse:
-    return out
-  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+  return _mla_step(name, "mla", None, q, kv_cache, head_dim_v, kv, lens, block_table, capacity, softmax_scale, causal, num_splits, return_softmax_lse)
 
 
 # ---- FP8 latent caches (OCP e4m3 codes, one per-tensor scale): ffpa_attn_with_kvcache_mla_fp8 / ffpa_attn_varlen_with_kvcache_mla_fp8
@@ -810,22 +799,7 @@ def ffpa_attn_with_kvcache_mla_fp8(
 
   kv_scale = hip.check_kv_scale(kv_scale, name)
   capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, fp8=True)
-  B, Sq, Hq, D = q.shape
-  out_shape = (B, Sq, Hq, head_dim_v)
-  if B == 0 or Sq == 0:
-    out = q.new_zeros(out_shape)
-    return (out, q.new_full((B, Hq, Sq), float("-inf"), dtype=torch.float32)) if return_softmax_lse else out
-  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
-  qp = q.reshape(B * Sq, Hq, D)
-  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
-  kv_new = kv if kv is not None and kv.size(1) > 0 else None
-  seqused = torch.empty((B,), dtype=torch.int32, device=q.device) if kv_new is not None else lens
-  o, lse = torch.ops.ffpa_attn._mla_fp8_fwd_hip(qp, kv_cache, head_dim_v, kv_scale, cu_q, seqused, table, kv_new, lens if kv_new is not None else None, Sq, capacity,
-                                                float(softmax_scale), 1 if causal else 0, num_splits)
-  out = o.view(*out_shape)
-  if not return_softmax_lse:
-    return out
-  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+  return _mla_step(name, "fp8", kv_scale, q, kv_cache, head_dim_v, kv, lens, block_table, capacity, softmax_scale, causal, num_splits, return_softmax_lse)
 
 
 def ffpa_attn_varlen_with_kvcache_mla_fp8(
@@ -856,19 +830,9 @@ def ffpa_attn_varlen_with_kvcache_mla_fp8(
   from . import hip  # (registers the ffpa_attn ops)
 
   kv_scale = hip.check_kv_scale(kv_scale, name)
-  capacity = _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, kv, softmax_scale, num_splits, fp8=True)
-  T, Hq, D = q.shape
-  B = cu_seqlens_q.numel() - 1
-  if T == 0:
-    out = q.new_empty((0, Hq, head_dim_v))
-    return (out, torch.empty((Hq, 0), dtype=torch.float32, device=q.device)) if return_softmax_lse else out
-  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
-  seqused = cache_seqlens
-  if kv is not None:
-    seqused = torch.ops.ffpa_attn._mla_fp8_append_varlen_hip(kv_cache, kv, kv_scale, cu_seqlens_q, cache_seqlens, table)
-  o, lse = torch.ops.ffpa_attn._mla_fp8_fwd_hip(q, kv_cache, head_dim_v, kv_scale, cu_seqlens_q, seqused, table, None, None, max_seqlen_q, capacity,
-                                                float(softmax_scale), 1 if causal else 0, num_splits)
-  return (o, lse) if return_softmax_lse else o
+  capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, fp8=True, ragged=(cu_seqlens_q, max_seqlen_q))
+  return _mla_step_varlen(name, "fp8", kv_scale, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, kv, lens, block_table, capacity, softmax_scale, causal, num_splits,
+                          return_softmax_lse)
 
 
 # ---- tree-mask attention over the MLA latent cache (the verification step of tree speculative decoding for the MLA models): ffpa_attn_with_kvcache_mla_tree
@@ -921,25 +885,7 @@ def ffpa_attn_with_kvcache_mla_tree(
   capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits)
   if isinstance(tree_mask, torch.Tensor) and tree_mask.requires_grad and torch.is_grad_enabled():
     raise NotImplementedError(f"{name} is inference only: tree_mask requires grad and there is no backward")
-  B, Sq, Hq, D = q.shape
-  from . import hip  # (registers the ffpa_attn ops)
-
-  out_shape = (B, Sq, Hq, head_dim_v)
-  if B == 0 or Sq == 0:
-    out = q.new_zeros(out_shape)
-    return (out, q.new_full((B, Hq, Sq), float("-inf"), dtype=torch.float32)) if return_softmax_lse else out
-  words = _tree_words(tree_mask, B, Sq, q.device, name, wide=True)
-  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
-  qp = q.reshape(B * Sq, Hq, D)
-  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
-  kv_new = kv if kv is not None and kv.size(1) > 0 else None
-  seqused = torch.empty((B,), dtype=torch.int32, device=q.device) if kv_new is not None else lens
-  o, lse = torch.ops.ffpa_attn._mla_tree_fwd_hip(qp, kv_cache, head_dim_v, cu_q, seqused, table, words, kv_new, lens if kv_new is not None else None, Sq, capacity,
-                                                 float(softmax_scale), num_splits)
-  out = o.view(*out_shape)
-  if not return_softmax_lse:
-    return out
-  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+  return _mla_step(name, "tree", tree_mask, q, kv_cache, head_dim_v, kv, lens, block_table, capacity, softmax_scale, False, num_splits, return_softmax_lse)
 
 
 # ---- ragged query batches (continuous batching, chunked prefill): ffpa_attn_varlen_with_kvcache
@@ -1308,22 +1254,9 @@ def ffpa_attn_varlen_with_kvcache_mla(
   if unsupported:
     raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no window, soft-cap, tree mask, cascade, rotary tables or positions, "
                               "ALiBi, batch index or leftpad over the latent cache: rotate q_pe / k_pe before the call)")
-  capacity = _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, kv, softmax_scale, num_splits)
-  T, Hq, D = q.shape
-  B = cu_seqlens_q.numel() - 1
-  from . import hip  # (registers the ffpa_attn ops)
-
-  if T == 0:
-    out = q.new_empty((0, Hq, head_dim_v))
-    return (out, torch.empty((Hq, 0), dtype=torch.float32, device=q.device)) if return_softmax_lse else out
-  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
-  seqused = cache_seqlens
-  if kv is not None:
-    # the prepare launch: the step's latent rows into the cache (in place) and the post-append lengths — read by the attention launch below on the same stream
-    seqused = torch.ops.ffpa_attn._mla_append_varlen_hip(kv_cache, kv, cu_seqlens_q, cache_seqlens, table)
-  o, lse = torch.ops.ffpa_attn._mla_fwd_hip(q, kv_cache, head_dim_v, cu_seqlens_q, seqused, table, None, None, max_seqlen_q, capacity, float(softmax_scale),
-                                            1 if causal else 0, num_splits)
-  return (o, lse) if return_softmax_lse else o
+  capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, ragged=(cu_seqlens_q, max_seqlen_q))
+  return _mla_step_varlen(name, "mla", None, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, kv, lens, block_table, capacity, softmax_scale, causal, num_splits,
+                          return_softmax_lse)
 
 
 # ---- ragged query batches under a tree mask over the MLA latent cache: ffpa_attn_varlen_with_kvcache_mla_tree
@@ -1362,25 +1295,11 @@ def ffpa_attn_varlen_with_kvcache_mla_tree(
   name = "ffpa_attn_varlen_with_kvcache_mla_tree"
   if unsupported:
     raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} ({_MLA_TREE_UNSERVED}; no positions)")
-  capacity = _mla_check_varlen(name, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, kv, softmax_scale, num_splits)
+  capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, ragged=(cu_seqlens_q, max_seqlen_q))
   if isinstance(tree_mask, torch.Tensor) and tree_mask.requires_grad and torch.is_grad_enabled():
     raise NotImplementedError(f"{name} is inference only: tree_mask requires grad and there is no backward")
-  T, Hq, D = q.shape
-  B = cu_seqlens_q.numel() - 1
-  from . import hip  # (registers the ffpa_attn ops)
-
-  if T == 0:
-    out = q.new_empty((0, Hq, head_dim_v))
-    return (out, torch.empty((Hq, 0), dtype=torch.float32, device=q.device)) if return_softmax_lse else out
-  words = _tree_words(tree_mask, B, max_seqlen_q, q.device, name, wide=True)
-  table = block_table if block_table is not None else _mla_identity_table(B, q.device)
-  seqused = cache_seqlens
-  if kv is not None:
-    # the prepare launch: the step's latent rows into the cache (in place) and the post-append lengths — read by the attention launch below on the same stream
-    seqused = torch.ops.ffpa_attn._mla_append_varlen_hip(kv_cache, kv, cu_seqlens_q, cache_seqlens, table)
-  o, lse = torch.ops.ffpa_attn._mla_tree_fwd_hip(q, kv_cache, head_dim_v, cu_seqlens_q, seqused, table, words, None, None, max_seqlen_q, capacity,
-                                                 float(softmax_scale), num_splits)
-  return (o, lse) if return_softmax_lse else o
+  return _mla_step_varlen(name, "tree", tree_mask, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, kv, lens, block_table, capacity, softmax_scale, False, num_splits,
+                          return_softmax_lse)
 
 
 # ---- cascade (shared-prefix) attention: ffpa_attn_with_kvcache_cascade

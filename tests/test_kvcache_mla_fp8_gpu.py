@@ -332,6 +332,49 @@ def test_the_ragged_append_stores_quantize_latent_rows_and_nothing_else(hip, dty
   assert _same_out(out[:T], again[0][:T]) and _same_out(lse[:, :T], again[1][:, :T])
 
 
+# the placement rule of both quantising appends at its edges, in ONE call (tests/test_kvcache_mla_varlen_gpu.py holds the 16-bit appends to the same steps)
+EDGE_STEPS = [((-1, 0, 126), (3, 0, 3)), ((-1, 0, 62, 126), (3, 0, 3, 3))]  # (lengths before the step, token rows of the ragged step; a uniform step brings 3 each)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("hkv", [1, 2])
+@pytest.mark.parametrize("lens, counts", EDGE_STEPS)
+@pytest.mark.parametrize("kernel", ["uniform", "ragged"])
+def test_both_quantising_appends_place_rows_by_one_rule_at_its_edges(hip, kernel, lens, counts, hkv, dtype):
+  """One call of ``ffpa_mla_fp8_append_kernel`` (3 new rows per sequence) and of ``ffpa_mla_fp8_append_varlen_kernel`` (3, 0, 3 rows) at lengths -1 (acts as 0),
+  0 and 126 of 128 (the third row is past the capacity) — and, with a fourth sequence, 62 (the rows cross into the next page): the pool's codes are those of
+  ``quantize_latent_rows`` written with torch (no NaN among the new rows: the bytes compare as they are), ``used[]`` is written for every sequence, the one
+  without a token included, and ``cache_seqlens`` is left alone."""
+  from ffpa_attn_amd import quantize_latent_rows
+
+  B, kv_scale = len(lens), 0.37
+  counts = (3,) * B if kernel == "uniform" else counts
+  g = torch.Generator(device="cuda").manual_seed(13 * hkv + B)
+  pool = torch.randint(0, 256, (2 * B + 2, PAGE, hkv, D), device="cuda", generator=g, dtype=torch.uint8)
+  ids = torch.randperm(2 * B + 2, device="cuda", generator=g)[:2 * B].to(torch.int32).view(B, 2)
+  rows = torch.randn((sum(counts), hkv, D), device="cuda", generator=g).to(R.TORCH_DTYPE[dtype])
+  codes = quantize_latent_rows(rows, kv_scale).view(torch.uint8)
+  want, used_want, r = pool.clone(), [], 0
+  for b, (n, c) in enumerate(zip(lens, counts)):
+    base = max(n, 0)
+    used_want.append(min(base + c, 2 * PAGE))
+    for pos in range(base, min(base + c, 2 * PAGE)):
+      want[int(ids[b, pos // PAGE]), pos % PAGE] = codes[r + pos - base]
+    r += c
+  lens_t = torch.tensor(lens, dtype=torch.int32, device="cuda")
+  cu = torch.tensor(np.concatenate(([0], np.cumsum(counts))), dtype=torch.int32, device="cuda")
+  got = pool.clone()
+  if kernel == "uniform":
+    q = torch.randn((3 * B, 16, D), device="cuda", generator=g).to(rows.dtype)
+    used = torch.full((B,), -7, dtype=torch.int32, device="cuda")
+    torch.ops.ffpa_attn._mla_fp8_fwd_hip(q, got.view(F8), DV, kv_scale, cu, used, ids, rows.view(B, 3, hkv, D), lens_t, 3, 2 * PAGE, SCALE, 1, 0)
+  else:
+    used = torch.ops.ffpa_attn._mla_fp8_append_varlen_hip(got.view(F8), rows, kv_scale, cu, lens_t, ids)
+  assert used.tolist() == used_want
+  assert torch.equal(got, want), "the pool's codes differ from the torch-written ones"
+  assert lens_t.tolist() == list(lens)
+
+
 # ----------------------------------------------------------------------------- 5. the ragged call
 RAGGED = [([1, 1, 1, 40], [300, 33, 0, 97]), ([1, 1, 1, 40, 1, 1], [300, 33, 0, 97, 64, 65])]
 

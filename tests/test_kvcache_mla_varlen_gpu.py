@@ -321,6 +321,56 @@ def test_used_lengths_padding_rows_capacity_and_negative_lengths(hip):
     row += n
 
 
+# ----------------------------------------------------------------------------- the placement rule of both 16-bit appends at its edges, in ONE call
+EDGE_STEPS = [((-1, 0, 126), (3, 0, 3)), ((-1, 0, 62, 126), (3, 0, 3, 3))]  # (lengths before the step, token rows of the ragged step; a uniform step brings 3 each)
+
+
+def _edge_pool(B, hkv, dtype, seed):
+  """A pool of 2 B + 2 pages of 64 rows of random values and a table of 2 shuffled pages per sequence (capacity 128)."""
+  g = torch.Generator(device="cuda").manual_seed(seed)
+  pool = torch.randn((2 * B + 2, PAGE, hkv, D), device="cuda", generator=g).to(dtype)
+  table = torch.randperm(2 * B + 2, device="cuda", generator=g)[:2 * B].to(torch.int32).view(B, 2)
+  return pool, table, g
+
+
+def _placed(pool, table, lens, counts, rows):
+  """The torch statement of the latent appends' rule: row i of sequence b goes to position max(lens[b], 0) + i of its pages, dropped at or past the capacity
+  -> (the pool after the step, used = min(max(lens, 0) + counts, capacity))."""
+  want, ids, cap, used, r = pool.clone(), table.tolist(), table.size(1) * PAGE, [], 0
+  for b, (n, c) in enumerate(zip(lens, counts)):
+    base = max(n, 0)
+    used.append(min(base + c, cap))
+    for pos in range(base, min(base + c, cap)):
+      want[ids[b][pos // PAGE], pos % PAGE] = rows[r + pos - base]
+    r += c
+  return want, used
+
+
+@pytest.mark.parametrize("hkv", [1, 2])
+@pytest.mark.parametrize("lens, counts", EDGE_STEPS)
+@pytest.mark.parametrize("kernel", ["uniform", "ragged"])
+def test_both_appends_place_rows_by_one_rule_at_its_edges(hip, kernel, lens, counts, hkv):
+  """One call of ``ffpa_mla_append_kernel`` (3 new rows per sequence) and of ``ffpa_mla_append_varlen_kernel`` (3, 0, 3 rows) at lengths -1 (acts as 0), 0 and
+  126 of 128 (the third row is past the capacity) — and, with a fourth sequence, 62 (the rows cross into the next page): the raw pool is the torch-written one,
+  ``used[]`` is written for every sequence, the one without a token included, and ``cache_seqlens`` is left alone."""
+  B = len(lens)
+  counts = (3,) * B if kernel == "uniform" else counts
+  pool, table, g = _edge_pool(B, hkv, torch.bfloat16, 11 * hkv + B)
+  rows = torch.randn((sum(counts), hkv, D), device="cuda", generator=g).to(torch.bfloat16)
+  want, want_used = _placed(pool, table, lens, counts, rows)
+  lens_t = torch.tensor(lens, dtype=torch.int32, device="cuda")
+  got = pool.clone()
+  if kernel == "uniform":
+    q = torch.randn((3 * B, 16, D), device="cuda", generator=g).to(torch.bfloat16)
+    used = torch.full((B,), -7, dtype=torch.int32, device="cuda")
+    torch.ops.ffpa_attn._mla_fwd_hip(q, got, DV, _cu(counts), used, table, rows.view(B, 3, hkv, D), lens_t, 3, 2 * PAGE, SCALE, 1, 0)
+  else:
+    used = torch.ops.ffpa_attn._mla_append_varlen_hip(got, rows, _cu(counts), lens_t, table)
+  assert used.tolist() == want_used
+  assert torch.equal(got.view(torch.int16), want.view(torch.int16)), "the raw pool differs from the torch-written one"
+  assert lens_t.tolist() == list(lens)
+
+
 # ----------------------------------------------------------------------------- the contiguous cache
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 def test_a_contiguous_cache_runs_as_one_page_per_sequence(hip, dtype):
