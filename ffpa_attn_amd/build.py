@@ -76,6 +76,9 @@ def _units() -> list[Unit]:
   units += [Unit("ffpa_mla_tree_inst.hip", f"ffpa_mla_tree_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
   # the FP8 (OCP e4m3) build of the latent kernel and its quantising appends: the same text with the FP8 hook on, one TU per pair of MLA_BUILDS
   units += [Unit("ffpa_mla_fp8_inst.hip", f"ffpa_mla_fp8_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
+  # the FP8 builds of the sparse and of the tree-mask latent kernel: the same text with the gather resp. the tree hook on next to the FP8 hook, one TU each per pair
+  units += [Unit("ffpa_mla_sparse_fp8_inst.hip", f"ffpa_mla_sparse_fp8_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
+  units += [Unit("ffpa_mla_tree_fp8_inst.hip", f"ffpa_mla_tree_fp8_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
   # the KV-cache append + rotary launch (every dtype / rotary form) and the merge of two attention states (the cascade's last launch): one small TU each, no
   # inline asm — their assembly lands in directories the attention ISA rules do not read
   units.append(Unit("ffpa_kvcache_append.hip", "ffpa_kvcache_append.o", [], "temps_append", None, True, True))

@@ -23,6 +23,8 @@
 #include "ffpa_paged.h"         // (the paged-KV twin of the packed-sequence kernel)
 #include "ffpa_mla.h"           // (the MLA latent-cache kernels and their append)
 #include "ffpa_mla_fp8.h"       // (the FP8 build of the latent kernel and its quantising appends)
+#include "ffpa_mla_sparse_fp8.h"  // (the FP8 build of the sparse latent kernel)
+#include "ffpa_mla_tree_fp8.h"    // (the FP8 build of the tree-mask latent kernel)
 #include "ffpa_mla_sparse.h"    // (the sparse — top-k indexed — build of the latent kernel)
 #include "ffpa_mla_tree.h"      // (the tree-mask build of the latent kernel)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
@@ -1170,16 +1172,18 @@ const ffpa_window* softcap_window(const ffpa_window* w) {
 }
 
 // The kernel builds of the latent-cache calls: one row per (head dim, value width) pair with its three launchers — the latent call's (ffpa_mla_inst.hip), the
-// sparse (top-k indexed) call's (ffpa_mla_sparse_inst.hip) and the tree-mask call's (ffpa_mla_tree_inst.hip) — and the FP8 latent call's (ffpa_mla_fp8_inst.hip).
+// sparse (top-k indexed) call's (ffpa_mla_sparse_inst.hip) and the tree-mask call's (ffpa_mla_tree_inst.hip) — and the FP8 latent call's (ffpa_mla_fp8_inst.hip), the
+// FP8 sparse call's (ffpa_mla_sparse_fp8_inst.hip) and the FP8 tree-mask call's (ffpa_mla_tree_fp8_inst.hip).
 typedef int (*mla_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, const ffpa::MlaArgs&, hipStream_t);
 typedef int (*mla_fp8_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, const ffpa::MlaFp8Args&, hipStream_t);
 struct MlaBuild {
   int d, dv;
   mla_fn latent, sparse, tree;
-  mla_fp8_fn fp8;
+  mla_fp8_fn fp8, sparse_fp8, tree_fp8;
 };
 const MlaBuild kMlaBuilds[] = {
-#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_paged_d##D, &ffpa::launch_mla_sparse_d##D, &ffpa::launch_mla_tree_d##D, &ffpa::launch_mla_fp8_paged_d##D},
+#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_paged_d##D, &ffpa::launch_mla_sparse_d##D, &ffpa::launch_mla_tree_d##D, &ffpa::launch_mla_fp8_paged_d##D, \
+                         &ffpa::launch_mla_sparse_fp8_d##D, &ffpa::launch_mla_tree_fp8_d##D},
     FFPA_FOR_EACH_MLA_BUILD(FFPA_ROW)
 #undef FFPA_ROW
 };
@@ -1251,16 +1255,17 @@ int check_sparse(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
 // head span at most 2^31 bytes.
 constexpr int64_t kSparseSpanBytes = 1LL << 31;
 
-// ... and what it checks BEHIND the plan and the (head_dim, head_dim_v) pair: the latent pool's geometry.
-int check_sparse_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
+// ... and what it checks BEHIND the plan and the (head_dim, head_dim_v) pair: the latent pool's geometry.  `esz`: bytes per pool element (2; 1: the FP8 sparse
+// call, whose span is counted in ITS bytes — the same 2^31 reach holds twice as many rows).
+int check_sparse_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int esz = 2) {
   const int rc = check_strides("kv", s->kv_stride, 2);
   if (rc != FFPA_OK) return rc;
   if (s->kv_stride[0] < p->head_dim || s->kv_stride[0] >= (1LL << 24))
     return fail(FFPA_ERR_BAD_STRIDE, "kv row stride %lld: rows must not overlap and must be < 2^24 elements apart", (long long)s->kv_stride[0]);
-  const int64_t span = ((int64_t)s->num_rows - 1) * s->kv_stride[0] * 2 + (int64_t)p->head_dim * 2;
+  const int64_t span = ((int64_t)s->num_rows - 1) * s->kv_stride[0] * esz + (int64_t)p->head_dim * esz;
   if (span > kSparseSpanBytes)
-    return fail(FFPA_ERR_BAD_SHAPE, "the pool's rows span %lld bytes per head: the sparse call reaches at most 2^31 = %lld ((num_rows - 1) * row stride * 2 + head_dim * 2)",
-                (long long)span, (long long)kSparseSpanBytes);
+    return fail(FFPA_ERR_BAD_SHAPE, "the pool's rows span %lld bytes per head: the sparse call reaches at most 2^31 = %lld ((num_rows - 1) * row stride * %d + head_dim * %d)",
+                (long long)span, (long long)kSparseSpanBytes, esz, esz);
   return FFPA_OK;
 }
 
@@ -1279,8 +1284,11 @@ enum class Family {
   kMlaTree,  // ffpa_attn_varlen_mla_tree_fwd: kv, mla, tree — the latent launch under the causal flag, the tree build of its kernel
   kMlaFp8,   // ffpa_attn_varlen_mla_fp8_fwd: kv, mla, fp8 — the latent call over a pool of e4m3 codes: its plan on the FP8 bytes, the FP8 build of its kernel
   kSparse,   // ffpa_attn_varlen_mla_sparse_fwd: sparse — a latent launch without a page pool: the index list stands where the block table stood
+  kMlaTreeFp8,  // ffpa_attn_varlen_mla_tree_fp8_fwd: kv, mla, tree, fp8 — kMlaTree over a pool of e4m3 codes: kMlaFp8's plan and append, the tree + FP8 build
+  kSparseFp8,   // ffpa_attn_varlen_mla_sparse_fp8_fwd: sparse, fp8 — kSparse over a pool of e4m3 codes: its plan on the FP8 bytes, the gather + FP8 build
 };
-bool is_tree(Family f) { return f == Family::kTree || f == Family::kMlaTree; }
+bool is_tree(Family f) { return f == Family::kTree || f == Family::kMlaTree || f == Family::kMlaTreeFp8; }
+bool is_sparse(Family f) { return f == Family::kSparse || f == Family::kSparseFp8; }
 bool is_window(Family f) { return f == Family::kWindow || f == Family::kSoftcap; }
 
 struct VarlenCall {
@@ -1335,6 +1343,16 @@ VarlenCall mla_fp8_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m,
 VarlenCall sparse_call(ParamsPtr p, const ffpa_mla_sparse* s) {
   VarlenCall c = make_call(Family::kSparse, p, nullptr);
   c.sparse = s;
+  return c;
+}
+VarlenCall mla_tree_fp8_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, const ffpa_mla_fp8* f8) {
+  VarlenCall c = make_call(Family::kMlaTreeFp8, p, kv);
+  c.mla = m, c.tree = tree, c.fp8 = f8;
+  return c;
+}
+VarlenCall sparse_fp8_call(ParamsPtr p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8) {
+  VarlenCall c = make_call(Family::kSparseFp8, p, nullptr);
+  c.sparse = s, c.fp8 = f8;
   return c;
 }
 
@@ -1462,6 +1480,33 @@ int plan_call(const VarlenCall& c, CallPlan* cp) {
       if ((rc = check_sparse_pool(p, c.sparse)) != FFPA_OK) return rc;
       cp->launch_mla = build->sparse;
       return FFPA_OK;
+    case Family::kMlaTreeFp8:  // kMlaFp8's order under kMlaTree's causal flag, the mask where kMlaTree checks it: behind the latent struct, in front of the pool's geometry
+      if ((rc = check_mla_fp8(c.fp8)) != FFPA_OK) return rc;
+      if (p != nullptr && p->struct_size == sizeof(ffpa_varlen_fwd_params)) {  // (anything else: varlen_plan refuses it by name)
+        cp->priced = *p;
+        cp->priced.causal = 1;
+        cp->p = p = &cp->priced;
+      }
+      if ((rc = varlen_plan(p, pl, true, true, 1)) != FFPA_OK) return rc;
+      if ((rc = check_paged(p, c.kv)) != FFPA_OK) return rc;
+      if ((rc = check_mla(p, c.mla, &build)) != FFPA_OK) return rc;
+      if ((rc = check_tree(p, c.tree)) != FFPA_OK) return rc;
+      if ((rc = check_fp8_strides(p->k_stride[0], p->k_stride[1], c.kv->k_page_stride)) != FFPA_OK) return rc;
+      cp->mla = c.mla;
+      cp->fp8 = c.fp8;
+      cp->launch_mla_fp8 = build->tree_fp8;
+      return FFPA_OK;
+    case Family::kSparseFp8:  // kSparse's order with the FP8 struct in front and the stride rule behind; the plan and the span count one byte per element
+      if ((rc = check_mla_fp8(c.fp8)) != FFPA_OK) return rc;
+      if ((rc = check_sparse(p, c.sparse)) != FFPA_OK) return rc;
+      price_sparse(p, c.sparse, cp);
+      if ((rc = varlen_plan(cp->p, pl, true, true, 1)) != FFPA_OK) return rc;
+      if ((rc = check_mla(cp->p, cp->mla, &build)) != FFPA_OK) return rc;
+      if ((rc = check_sparse_pool(p, c.sparse, 1)) != FFPA_OK) return rc;
+      if ((rc = check_fp8_strides(c.sparse->kv_stride[0], c.sparse->kv_stride[1], 0)) != FFPA_OK) return rc;
+      cp->fp8 = c.fp8;
+      cp->launch_mla_fp8 = build->sparse_fp8;
+      return FFPA_OK;
   }
   return fail(FFPA_ERR_UNSUPPORTED, "unknown call family %d", (int)c.family);
 }
@@ -1476,7 +1521,7 @@ int varlen_launch(const VarlenCall& c, void* stream) {
   const VarlenPlan& pl = cp.pl;
   const ffpa_paged_kv* kv = c.kv;
   const ffpa_mla* mla = cp.mla;
-  const ffpa_mla_sparse* sparse = c.family == Family::kSparse ? c.sparse : nullptr;
+  const ffpa_mla_sparse* sparse = is_sparse(c.family) ? c.sparse : nullptr;
   const bool latent = mla != nullptr;                   // k is the one cache: it serves as v too, p->v is not read
   const bool paged = kv != nullptr || sparse != nullptr;  // the keys are found through a table: cu_seqlens_kv is not read
   if (!p->q || !p->k || (!latent && !p->v) || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
@@ -1702,10 +1747,15 @@ int call_kernel(const VarlenCall& c, char* buf, size_t n) {
   const char* merge = pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "";
   if (cp.mla != nullptr) {
     // (a latent call's name is formatted from the caller's params; the sparse call — a uniform batch — has never named the compact grid)
-    const char* kind = c.family == Family::kSparse ? "_sparse" : c.family == Family::kMlaTree ? "_tree" : c.family == Family::kMlaFp8 ? "_fp8" : "";
+    const char* kind = c.family == Family::kSparse       ? "_sparse"
+                       : c.family == Family::kMlaTree    ? "_tree"
+                       : c.family == Family::kMlaFp8     ? "_fp8"
+                       : c.family == Family::kSparseFp8  ? "_sparse_fp8"
+                       : c.family == Family::kMlaTreeFp8 ? "_tree_fp8"
+                                                         : "";
     snprintf(buf, n, "ffpa_fwd_m16_mla%s_kernel<%s, %d, dv=%d%s>%s%s%s", kind, c.p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", c.p->head_dim, cp.mla->head_dim_v, nt,
              pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "",
-             pl.compact > 0 && c.family != Family::kSparse ? " (compact grid)" : "", merge);
+             pl.compact > 0 && !is_sparse(c.family) ? " (compact grid)" : "", merge);
   } else {
     // (a window / soft-cap call's name is formatted from the priced params)
     const char* kind = is_tree(c.family) ? "_tree" : c.family == Family::kSoftcap ? "_softcap" : c.family == Family::kWindow ? "_window" : "";
@@ -1830,6 +1880,42 @@ size_t ffpa_attn_varlen_mla_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params
 }
 int ffpa_attn_varlen_mla_fp8_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, int* slots) {
   return call_compact_slots(mla_fp8_call(p, kv, m, f8), slots);
+}
+
+// ---- the FP8 tree-mask latent call: the tree-mask latent call over a pool of e4m3 codes (the FP8 latent call's plan, append and scale)
+int ffpa_attn_varlen_mla_tree_fp8_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, const ffpa_mla_fp8* f8,
+                                      void* stream) {
+  return varlen_launch(mla_tree_fp8_call(p, kv, m, tree, f8), stream);
+}
+int ffpa_attn_varlen_mla_tree_fp8_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, const ffpa_mla_fp8* f8,
+                                           int out[5]) {
+  return call_plan(mla_tree_fp8_call(p, kv, m, tree, f8), out);
+}
+int ffpa_attn_varlen_mla_tree_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree,
+                                             const ffpa_mla_fp8* f8, char* buf, size_t n) {
+  return call_kernel(mla_tree_fp8_call(p, kv, m, tree, f8), buf, n);
+}
+size_t ffpa_attn_varlen_mla_tree_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree,
+                                                         const ffpa_mla_fp8* f8) {
+  return call_workspace_bytes(mla_tree_fp8_call(p, kv, m, tree, f8));
+}
+int ffpa_attn_varlen_mla_tree_fp8_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree,
+                                                    const ffpa_mla_fp8* f8, int* slots) {
+  return call_compact_slots(mla_tree_fp8_call(p, kv, m, tree, f8), slots);
+}
+
+// ---- the FP8 sparse latent call: the sparse latent call over a pool of e4m3 codes
+int ffpa_attn_varlen_mla_sparse_fp8_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, void* stream) {
+  return varlen_launch(sparse_fp8_call(p, s, f8), stream);
+}
+int ffpa_attn_varlen_mla_sparse_fp8_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, int out[5]) {
+  return call_plan(sparse_fp8_call(p, s, f8), out);
+}
+int ffpa_attn_varlen_mla_sparse_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, char* buf, size_t n) {
+  return call_kernel(sparse_fp8_call(p, s, f8), buf, n);
+}
+size_t ffpa_attn_varlen_mla_sparse_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8) {
+  return call_workspace_bytes(sparse_fp8_call(p, s, f8));
 }
 
 // ---- the sparse latent call (include/ffpa_attn.h: ffpa_mla_sparse): the latent launch over per-token index lists

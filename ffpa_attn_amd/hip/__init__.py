@@ -379,6 +379,8 @@ _MLA = _PAGED + [_P(FfpaMla)]
 _MLA_SPARSE = [_P(FfpaVarlenFwdParams), _P(FfpaMlaSparse)]
 _MLA_TREE = _MLA + [_P(FfpaTreeMask)]
 _MLA_FP8 = _MLA + [_P(FfpaMlaFp8)]
+_MLA_TREE_FP8 = _MLA_TREE + [_P(FfpaMlaFp8)]
+_MLA_SPARSE_FP8 = _MLA_SPARSE + [_P(FfpaMlaFp8)]
 # Every function include/ffpa_attn.h declares: (symbol, argtypes, restype, since).  ``since``: the ABI version that added it (0: there from the start) — the
 # default library has them all; one loaded by path or through FFPA_HIP_LIBRARY (developer A/B runs load a saved build of an older commit) may lack those with
 # since > 0: calling one of those is then an AttributeError.
@@ -430,6 +432,15 @@ _BINDINGS = (
   ("ffpa_attn_varlen_mla_sparse_fwd_plan", _MLA_SPARSE + [_P(_INT)], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_fwd_kernel", _MLA_SPARSE + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes", _MLA_SPARSE, _SIZE, 7),
+  ("ffpa_attn_varlen_mla_tree_fp8_fwd", _MLA_TREE_FP8 + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_tree_fp8_fwd_plan", _MLA_TREE_FP8 + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_tree_fp8_fwd_kernel", _MLA_TREE_FP8 + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_mla_tree_fp8_fwd_workspace_bytes", _MLA_TREE_FP8, _SIZE, 7),
+  ("ffpa_attn_varlen_mla_tree_fp8_fwd_compact_slots", _MLA_TREE_FP8 + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fp8_fwd", _MLA_SPARSE_FP8 + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fp8_fwd_plan", _MLA_SPARSE_FP8 + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fp8_fwd_kernel", _MLA_SPARSE_FP8 + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fp8_fwd_workspace_bytes", _MLA_SPARSE_FP8, _SIZE, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
@@ -1569,13 +1580,12 @@ def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seq
 
   ``kv_scale`` (a host float, finite and > 0; ``mla_fp8_forward`` is this call with it): the pool is ``torch.float8_e4m3fn`` — OCP e4m3 codes, K = kv_scale x K8 —
   and the call is ``ffpa_attn_varlen_mla_fp8_fwd``, its own kernel; q, ``kv_new`` (quantised by the append, ``quantize_latent_rows``' definition) and o stay
-  bf16 / fp16.  Not with ``tree_words``."""
+  bf16 / fp16.  With ``tree_words`` as well (``mla_tree_fp8_forward``): ``ffpa_attn_varlen_mla_tree_fp8_fwd``, the tree mask over the FP8 pool."""
   tree = tree_words is not None
   fp8 = kv_scale is not None
-  name = "ffpa_attn::_mla_tree_fwd_hip" if tree else "ffpa_attn::_mla_fp8_fwd_hip" if fp8 else "ffpa_attn::_mla_fwd_hip"
-  export = "ffpa_attn_varlen_mla_tree_fwd" if tree else "ffpa_attn_varlen_mla_fp8_fwd" if fp8 else "ffpa_attn_varlen_mla_fwd"
-  if fp8 and tree:
-    raise NotImplementedError(f"{name}: FP8 latent pools are not served under a tree mask")
+  kind = ("_tree" if tree else "") + ("_fp8" if fp8 else "")
+  name = f"ffpa_attn::_mla{kind}_fwd_hip"
+  export = f"ffpa_attn_varlen_mla{kind}_fwd"
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
@@ -1642,15 +1652,15 @@ def mla_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seq
     m.seqlen_new, m.kv_new, m.cache_seqlens = kv_new.size(1), kv_new.data_ptr(), cache_seqlens.data_ptr()
     m.kv_new_stride[:] = list(kv_new.stride()[:3])
   args = (ctypes.byref(p), ctypes.byref(kv), ctypes.byref(m))
-  if fp8:
-    f8 = _stamped(FfpaMlaFp8)
-    f8.kv_scale = kv_scale
-    args += (ctypes.byref(f8),)
   if tree:
     tm = _stamped(FfpaTreeMask)
     tm.bits, tm.tokens = tree_words.data_ptr(), tree_words.size(1)
     tm.batch_stride = tree_words.stride(0) if tree_words.size(0) > 1 else 0
     args += (ctypes.byref(tm),)
+  if fp8:  # (behind the mask: the order of the C calls' arguments)
+    f8 = _stamped(FfpaMlaFp8)
+    f8.kv_scale = kv_scale
+    args += (ctypes.byref(f8),)
   with torch.cuda.device(q.device):
     stream = torch.cuda.current_stream(q.device).cuda_stream
     nbytes = 0
@@ -1703,6 +1713,19 @@ def mla_fp8_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu
     raise ValueError("ffpa_attn::_mla_fp8_fwd_hip: kv_scale is required")
   return mla_forward(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, causal, softmax_scale, kv_new=kv_new,
                      cache_seqlens=cache_seqlens, return_lse=return_lse, flags=flags, plan_out=plan_out, num_splits=num_splits, kv_scale=kv_scale)
+
+
+def mla_tree_fp8_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, cu_seqlens_q: torch.Tensor, seqused_k: torch.Tensor, block_table: torch.Tensor,
+                         max_seqlen_q: int, max_seqlen_k: int, softmax_scale: float, tree_words: torch.Tensor, kv_scale: float, *,
+                         kv_new: "torch.Tensor | None" = None, cache_seqlens: "torch.Tensor | None" = None, return_lse: bool = True, flags: int = 0,
+                         plan_out: "dict | None" = None, num_splits: int = 0):
+  """One call of ``ffpa_attn_varlen_mla_tree_fp8_fwd`` — the latent call under a TREE MASK over a ``torch.float8_e4m3fn`` pool (``mla_forward``'s ``tree_words`` and
+  ``kv_scale`` together).  ``kv_new`` (quantised by the append) / ``cache_seqlens`` / ``flags`` / ``plan_out`` / ``num_splits`` as ``mla_forward``."""
+  if tree_words is None or kv_scale is None:
+    raise ValueError("ffpa_attn::_mla_tree_fp8_fwd_hip: tree_words and kv_scale are required")
+  return mla_forward(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, True, softmax_scale, kv_new=kv_new,
+                     cache_seqlens=cache_seqlens, return_lse=return_lse, flags=flags, plan_out=plan_out, num_splits=num_splits, tree_words=tree_words,
+                     kv_scale=kv_scale)
 
 
 # kv_cache is written in place by the append (kv_new): the schema says so
@@ -1765,6 +1788,25 @@ def _mla_tree_fwd_hip_torch_op(q, kv_cache, head_dim_v, cu_seqlens_q, seqused_k,
 torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_tree_fwd_hip", _mla_out_fake)
 
 
+# The tree-mask latent call over an FP8 pool (ffpa_attn_with_kvcache_mla_tree_fp8 / ffpa_attn_varlen_with_kvcache_mla_tree_fp8): the tree op with the per-tensor scale —
+# kv_cache (float8_e4m3fn) is written in place by the quantising append (kv_new)
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_tree_fp8_fwd_hip",
+  "(Tensor q, Tensor(a!) kv_cache, int head_dim_v, float kv_scale, Tensor cu_seqlens_q, Tensor(b!) seqused_k, Tensor block_table, Tensor tree_words, "
+  "Tensor? kv_new, Tensor? cache_seqlens, int max_seqlen_q, int max_seqlen_k, float softmax_scale, int num_splits=0) -> (Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_tree_fp8_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_tree_fp8_fwd_hip_torch_op(q, kv_cache, head_dim_v, kv_scale, cu_seqlens_q, seqused_k, block_table, tree_words, kv_new, cache_seqlens, max_seqlen_q,
+                                   max_seqlen_k, softmax_scale, num_splits=0):
+  return mla_tree_fp8_forward(q, kv_cache, int(head_dim_v), cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, softmax_scale, tree_words, kv_scale,
+                              kv_new=kv_new, cache_seqlens=cache_seqlens, return_lse=True, num_splits=num_splits)
+
+
+torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_tree_fp8_fwd_hip", _mla_out_fake)
+
+
 # The sparse latent call (ffpa_attn_with_kvcache_mla_sparse): every query token attends to the latent rows its index list names
 MLA_SPARSE_SPAN_BYTES = 1 << 31  # what the kernel's 32-bit lane offsets reach: a head's rows of the pool span at most this many bytes (bit 31 = "no row")
 _MLA_SPARSE_IDENTITY: "dict[tuple, torch.Tensor]" = {}
@@ -1789,6 +1831,9 @@ def mla_sparse_pool(kv_cache: torch.Tensor, name: str = "ffpa_attn::_mla_sparse_
     raise ValueError(f"{name}: kv_cache must be the flat pool [num_rows, Hkv, D] or a page pool [num_pages, page_size, Hkv, D], got {kv_cache.dim()}-D")
   if num_rows > 0x7fffffff:
     raise ValueError(f"{name}: a pool of {num_rows} rows is too large (slots are int32)")
+  if kv_cache.element_size() == 1 and (row_stride % 16 != 0 or head_stride % 16 != 0):
+    # (an FP8 pool: its loads are 8 bytes wide and the kernel's text doubles every stride; the span below counts its bytes — twice the rows of a 16-bit pool)
+    raise ValueError(f"{name}: the row and head strides of an FP8 pool ({row_stride}, {head_stride}) must be multiples of 16 elements")
   span = (num_rows - 1) * row_stride * kv_cache.element_size() + kv_cache.size(-1) * kv_cache.element_size() if num_rows > 0 else 0
   if span > MLA_SPARSE_SPAN_BYTES:
     raise ValueError(f"{name}: the pool's rows span {span} bytes per latent head ((num_rows - 1) * row stride + one row = ({num_rows} - 1) * "
@@ -1823,16 +1868,25 @@ def _mla_sparse_args(dtype, T: int, Hq: int, Hkv: int, D: int, head_dim_v: int, 
 
 
 def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, indices: torch.Tensor, topk_lens: "torch.Tensor | None", softmax_scale: float, *,
-                       return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
+                       return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0, kv_scale: "float | None" = None):
   """One call of ``ffpa_attn_varlen_mla_sparse_fwd``: ``q [T, Hq, D]`` (one row per query token), the latent pool ``kv_cache`` (``mla_sparse_pool``'s two forms),
   the int32 device ``indices [T, topk]`` of pool slots and the optional int32 ``topk_lens [T]`` -> ``(o [T, Hq, head_dim_v], lse [Hq, T] fp32 | None)``.  Token t
   attends to the rows ``indices[t, :clamp(topk_lens[t], 0, topk)]``; entries at and past the count are never turned into an address.  Nothing is read back to the
-  host: the call (and the split launch's merge) captures into a HIP graph.  ``flags`` / ``plan_out`` / ``num_splits`` as ``varlen_forward``."""
-  name = "ffpa_attn::_mla_sparse_fwd_hip"
+  host: the call (and the split launch's merge) captures into a HIP graph.  ``flags`` / ``plan_out`` / ``num_splits`` as ``varlen_forward``.
+
+  ``kv_scale`` (a host float, finite and > 0; ``mla_sparse_fp8_forward`` is this call with it): the pool is ``torch.float8_e4m3fn`` — OCP e4m3 codes, K = kv_scale x
+  K8, row and head strides multiples of 16 — and the call is ``ffpa_attn_varlen_mla_sparse_fp8_fwd``, its own kernel; q and o stay bf16 / fp16."""
+  fp8 = kv_scale is not None
+  name = "ffpa_attn::_mla_sparse_fp8_fwd_hip" if fp8 else "ffpa_attn::_mla_sparse_fwd_hip"
+  export = "ffpa_attn_varlen_mla_sparse_fp8_fwd" if fp8 else "ffpa_attn_varlen_mla_sparse_fwd"
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
-  if q.dtype not in _DTYPE or kv_cache.dtype != q.dtype:
+  if fp8:
+    if q.dtype not in _DTYPE or kv_cache.dtype != torch.float8_e4m3fn:
+      raise TypeError(f"{name} only supports fp16/bf16 q over a torch.float8_e4m3fn kv_cache (OCP e4m3, the chip's FP8 format), got {q.dtype}, {kv_cache.dtype}")
+    kv_scale = check_kv_scale(kv_scale, name)
+  elif q.dtype not in _DTYPE or kv_cache.dtype != q.dtype:
     raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
   if q.dim() != 3 or kv_cache.dim() not in (3, 4) or kv_cache.size(-1) != q.size(2):
     raise ValueError(f"{name}: q must be [T, Hq, D] and kv_cache [num_rows, Hkv, D] or [num_pages, page_size, Hkv, D] of q's head dim")
@@ -1849,7 +1903,8 @@ def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int,
   if kv_cache.device != q.device or kv_cache.numel() == 0:
     raise ValueError(f"{name}: kv_cache must be a non-empty pool on q's device")
   if not _layout_ok(kv_cache, -3):
-    raise ValueError(f"{name}: kv_cache needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base (it is read in place)")
+    raise ValueError(f"{name}: kv_cache needs head-dim stride 1, strides that are multiples of {16 if fp8 else 8} elements and a 16-byte aligned base (it is read "
+                     "in place)")
   num_rows, row_stride, head_stride = mla_sparse_pool(kv_cache, name)
   topk = indices.size(1)
   q = _rows(q, 0)
@@ -1871,19 +1926,34 @@ def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int,
   s.indices = indices.data_ptr()
   s.topk_lens = topk_lens.data_ptr() if topk_lens is not None else None
   args = (ctypes.byref(p), ctypes.byref(s))
+  if fp8:
+    f8 = _stamped(FfpaMlaFp8)
+    f8.kv_scale = kv_scale
+    args += (ctypes.byref(f8),)
   with torch.cuda.device(q.device):
     stream = torch.cuda.current_stream(q.device).cuda_stream
     nbytes = 0
     if not (p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC):
-      key = ("sparse", id(lib), q.device.index or 0, p.dtype, T, Hq, Hkv, D, s.head_dim_v, topk, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS"))
-      nbytes = _cached_scratch(_MLA_SCRATCH, key, lambda: int(lib.ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(*args)))
+      key = ("sparse", id(lib), q.device.index or 0, p.dtype, T, Hq, Hkv, D, s.head_dim_v, topk, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS")) + (
+        ("fp8",) if fp8 else ())
+      nbytes = _cached_scratch(_MLA_SCRATCH, key, lambda: int(getattr(lib, export + "_workspace_bytes")(*args)))
     workspace = _hand_over_workspace(p, q.device, stream, nbytes)  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
-      plan_out.update(_read_plan(lib, lib.ffpa_attn_varlen_mla_sparse_fwd_plan, lib.ffpa_attn_varlen_mla_sparse_fwd_kernel, _VARLEN_PLAN_KEYS, args))
-    rc = lib.ffpa_attn_varlen_mla_sparse_fwd(*args, ctypes.c_void_p(stream))
+      plan_out.update(_read_plan(lib, getattr(lib, export + "_plan"), getattr(lib, export + "_kernel"), _VARLEN_PLAN_KEYS, args))
+    rc = getattr(lib, export)(*args, ctypes.c_void_p(stream))
   if rc != 0:
-    _raise_status(lib, rc, "ffpa_attn_varlen_mla_sparse_fwd")
+    _raise_status(lib, rc, export)
   return o, lse
+
+
+def mla_sparse_fp8_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, indices: torch.Tensor, topk_lens: "torch.Tensor | None", softmax_scale: float,
+                           kv_scale: float, *, return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
+  """One call of ``ffpa_attn_varlen_mla_sparse_fp8_fwd`` — the sparse latent call over a ``torch.float8_e4m3fn`` pool with the per-tensor ``kv_scale``
+  (``mla_sparse_forward``'s ``kv_scale``).  ``flags`` / ``plan_out`` / ``num_splits`` as there (tests force or inspect the launch)."""
+  if kv_scale is None:
+    raise ValueError("ffpa_attn::_mla_sparse_fp8_fwd_hip: kv_scale is required")
+  return mla_sparse_forward(q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, return_lse=return_lse, flags=flags, plan_out=plan_out, num_splits=num_splits,
+                            kv_scale=kv_scale)
 
 
 torch.library.define(
@@ -1898,6 +1968,22 @@ def _mla_sparse_fwd_hip_torch_op(q, kv_cache, head_dim_v, indices, topk_lens, so
 
 
 torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_fwd_hip", _mla_out_fake)
+
+
+# The sparse latent call over an FP8 pool (ffpa_attn_with_kvcache_mla_sparse_fp8): the sparse op with the per-tensor scale
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_sparse_fp8_fwd_hip",
+  "(Tensor q, Tensor kv_cache, int head_dim_v, float kv_scale, Tensor indices, Tensor? topk_lens, float softmax_scale, int num_splits=0) -> "
+  "(Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_sparse_fp8_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_sparse_fp8_fwd_hip_torch_op(q, kv_cache, head_dim_v, kv_scale, indices, topk_lens, softmax_scale, num_splits=0):
+  return mla_sparse_fp8_forward(q, kv_cache, int(head_dim_v), indices, topk_lens, softmax_scale, kv_scale, return_lse=True, num_splits=num_splits)
+
+
+torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_fp8_fwd_hip", _mla_out_fake)
 
 
 # The latent append of a ragged step (ffpa_attn_varlen_with_kvcache_mla(kv=)): token rows packed by cu_seqlens_q, in front of the attention launch

@@ -21,7 +21,10 @@ entry point keeps refusing ``softcap``.
 An MLA latent cache — ONE cache whose rows are the keys and, in their first ``head_dim_v`` columns, the values (DeepSeek-V2 / V3 / R1, Kimi K2 in their
 "absorbed" decode form) — has an entry of its own too, ``ffpa_attn_with_kvcache_mla`` (below): every latent row is fetched once, and the heads of a latent head are
 packed into the rows of the tiles however many they are.  Sparse (top-k indexed) attention over that cache — every query token attends to the rows an
-indexer picked for it (DeepSeek-V3.2) — is ``ffpa_attn_with_kvcache_mla_sparse`` (below): the rows are read where they lie.
+indexer picked for it (DeepSeek-V3.2) — is ``ffpa_attn_with_kvcache_mla_sparse`` (below): the rows are read where they lie.  An FP8 latent cache
+(``torch.float8_e4m3fn`` codes under one per-tensor scale) is served by the ``_fp8`` twins of the latent calls:
+``ffpa_attn_with_kvcache_mla_fp8``, ``ffpa_attn_varlen_with_kvcache_mla_fp8``, ``ffpa_attn_with_kvcache_mla_sparse_fp8``,
+``ffpa_attn_with_kvcache_mla_tree_fp8`` and ``ffpa_attn_varlen_with_kvcache_mla_tree_fp8``.
 
 Inference only: ``cache_batch_idx``, ``cache_leftpad`` and ALiBi have no kernel-side implementation here and raise
 ``NotImplementedError`` naming the option — as do ``k`` without ``v`` (or ``v`` without ``k``) and rotary tables without ``k`` / ``v`` or one without the other;
@@ -621,7 +624,8 @@ def _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, so
 
 # The step behind _mla_check, once per kind.  ``op`` names the attention op: "mla" is ffpa_attn::_mla_fwd_hip; "fp8" its FP8 twin, with ``extra`` the kv_scale; "tree"
 # its tree-mask twin, with ``extra`` the caller's tree_mask — checked here, behind the empty returns that never look at it — and no causal flag.  The ops are
-# registered: _mla_check has imported .hip.
+# registered: _mla_check has imported .hip.  "tree_fp8" is the tree twin over an FP8 pool: ``extra`` is ``(tree_mask, kv_scale)``, the mask checked where "tree"
+# checks it, the rows of ``kv`` quantised by the appends "fp8" uses.
 def _mla_step(name, op, extra, q, kv_cache, head_dim_v, kv, lens, block_table, capacity, softmax_scale, causal, num_splits, return_softmax_lse):
   """The uniform step: append (``kv``) + attention in ONE call of the attention op, q as a packed batch of B sequences of Sq tokens."""
   B, Sq, Hq, D = q.shape
@@ -630,6 +634,8 @@ def _mla_step(name, op, extra, q, kv_cache, head_dim_v, kv, lens, block_table, c
     return (out, q.new_full((B, Hq, Sq), float("-inf"), dtype=torch.float32)) if return_softmax_lse else out
   if op == "tree":
     extra = _tree_words(extra, B, Sq, q.device, name, wide=True)  # (from here on `extra` is the packed words the tree op takes, no longer the caller's mask)
+  elif op == "tree_fp8":
+    extra = (_tree_words(extra[0], B, Sq, q.device, name, wide=True), extra[1])
   table = block_table if block_table is not None else _mla_identity_table(B, q.device)
   qp = q.reshape(B * Sq, Hq, D)
   cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
@@ -638,6 +644,9 @@ def _mla_step(name, op, extra, q, kv_cache, head_dim_v, kv, lens, block_table, c
   before = lens if kv_new is not None else None
   if op == "tree":
     o, lse = torch.ops.ffpa_attn._mla_tree_fwd_hip(qp, kv_cache, head_dim_v, cu_q, seqused, table, extra, kv_new, before, Sq, capacity, float(softmax_scale), num_splits)
+  elif op == "tree_fp8":
+    o, lse = torch.ops.ffpa_attn._mla_tree_fp8_fwd_hip(qp, kv_cache, head_dim_v, extra[1], cu_q, seqused, table, extra[0], kv_new, before, Sq, capacity,
+                                                       float(softmax_scale), num_splits)
   elif op == "fp8":
     o, lse = torch.ops.ffpa_attn._mla_fp8_fwd_hip(qp, kv_cache, head_dim_v, extra, cu_q, seqused, table, kv_new, before, Sq, capacity, float(softmax_scale),
                                                   1 if causal else 0, num_splits)
@@ -660,17 +669,22 @@ def _mla_step_varlen(name, op, extra, q, kv_cache, head_dim_v, cu_seqlens_q, max
     return (out, torch.empty((Hq, 0), dtype=torch.float32, device=q.device)) if return_softmax_lse else out
   if op == "tree":
     extra = _tree_words(extra, B, max_seqlen_q, q.device, name, wide=True)  # (from here on `extra` is the packed words the tree op takes, no longer the caller's mask)
+  elif op == "tree_fp8":
+    extra = (_tree_words(extra[0], B, max_seqlen_q, q.device, name, wide=True), extra[1])
   table = block_table if block_table is not None else _mla_identity_table(B, q.device)
   seqused = lens
   if kv is not None:
     # the prepare launch: the step's latent rows into the cache (in place) and the post-append lengths — read by the attention launch below on the same stream
-    if op == "fp8":
-      seqused = torch.ops.ffpa_attn._mla_fp8_append_varlen_hip(kv_cache, kv, extra, cu_seqlens_q, lens, table)
+    if op in ("fp8", "tree_fp8"):
+      seqused = torch.ops.ffpa_attn._mla_fp8_append_varlen_hip(kv_cache, kv, extra if op == "fp8" else extra[1], cu_seqlens_q, lens, table)
     else:
       seqused = torch.ops.ffpa_attn._mla_append_varlen_hip(kv_cache, kv, cu_seqlens_q, lens, table)
   if op == "tree":
     o, lse = torch.ops.ffpa_attn._mla_tree_fwd_hip(q, kv_cache, head_dim_v, cu_seqlens_q, seqused, table, extra, None, None, max_seqlen_q, capacity,
                                                    float(softmax_scale), num_splits)
+  elif op == "tree_fp8":
+    o, lse = torch.ops.ffpa_attn._mla_tree_fp8_fwd_hip(q, kv_cache, head_dim_v, extra[1], cu_seqlens_q, seqused, table, extra[0], None, None, max_seqlen_q, capacity,
+                                                       float(softmax_scale), num_splits)
   elif op == "fp8":
     o, lse = torch.ops.ffpa_attn._mla_fp8_fwd_hip(q, kv_cache, head_dim_v, extra, cu_seqlens_q, seqused, table, None, None, max_seqlen_q, capacity,
                                                   float(softmax_scale), 1 if causal else 0, num_splits)
@@ -757,6 +771,9 @@ def quantize_latent_rows(kv: torch.Tensor, kv_scale: float) -> torch.Tensor:
   return v.to(torch.float8_e4m3fn)
 
 
+# (tests/golden/mla_front_calls.json pins this text and the docstrings of the six calls it replays, byte for byte — the last clause here and the "FP8 pools in the
+# sparse and the tree call" / "FP8 latents (a dtype error)" of those docstrings included, which ffpa_attn_with_kvcache_mla_sparse_fp8 and the two *_mla_tree_fp8 calls
+# below have made stale: they stay as recorded until a change regenerates the golden.)
 _MLA_FP8_UNSERVED = ("no window, soft-cap, tree mask, cascade, rotary tables, ALiBi, batch index or leftpad over the latent cache: rotate q_pe / k_pe before the "
                      "call; FP8 pools are not served by the sparse and the tree call")
 
@@ -888,6 +905,46 @@ def ffpa_attn_with_kvcache_mla_tree(
   return _mla_step(name, "tree", tree_mask, q, kv_cache, head_dim_v, kv, lens, block_table, capacity, softmax_scale, False, num_splits, return_softmax_lse)
 
 
+def ffpa_attn_with_kvcache_mla_tree_fp8(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  *,
+  kv_scale: float = 1.0,
+  tree_mask: torch.Tensor,
+  kv: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor",
+  block_table: torch.Tensor | None = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """``ffpa_attn_with_kvcache_mla_tree`` over an FP8 latent cache — the verification step of tree speculative decoding (MTP / EAGLE drafting) for an engine that
+  keeps the latent cache as ``kv_cache_dtype="fp8"``: ``kv_cache`` is ``torch.float8_e4m3fn`` (OCP e4m3; ``float8_e4m3fnuz`` and the e5m2 formats raise
+  ``TypeError``) under ONE per-tensor scale, ``K = kv_scale * K8``; ``kv_scale`` is a host float, finite and positive (``ValueError``; a tensor raises
+  ``TypeError``).  ``q``, ``kv`` and the output are bf16 or fp16.  ``kv [B, Snew, Hkv, D]`` is QUANTISED by the FP8 latent call's append, exactly as
+  ``quantize_latent_rows(kv, kv_scale)``.
+
+  ``tree_mask``, what a draft token sees, the shapes, ``cache_seqlens``, ``block_table``, the contiguous cache, the required ``softmax_scale``, ``num_splits``, the
+  returns and the one-graph step are ``ffpa_attn_with_kvcache_mla_tree``'s; the pool (strides multiples of 16 elements), the exact widening and the place of the
+  scale are ``ffpa_attn_with_kvcache_mla_fp8``'s.  ``tril(ones)`` is ``ffpa_attn_with_kvcache_mla_fp8(causal=True)`` and all ones ``causal=False``, to the bit; with
+  a power-of-two ``kv_scale`` the call returns the bits of ``ffpa_attn_with_kvcache_mla_tree(q, kv_cache.to(q.dtype), ..., softmax_scale=softmax_scale *
+  kv_scale) * kv_scale``.  Not served: per-token / per-block scales, FP8 ``q``, a ``kv_scale`` on the device; every keyword the 16-bit call refuses."""
+  name = "ffpa_attn_with_kvcache_mla_tree_fp8"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} ({_MLA_TREE_UNSERVED}; a ragged batch — cu_seqlens_q — is "
+                              "ffpa_attn_varlen_with_kvcache_mla_tree_fp8's)")
+  from . import hip  # (registers the ffpa_attn ops)
+
+  kv_scale = hip.check_kv_scale(kv_scale, name)
+  capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, fp8=True)
+  if isinstance(tree_mask, torch.Tensor) and tree_mask.requires_grad and torch.is_grad_enabled():
+    raise NotImplementedError(f"{name} is inference only: tree_mask requires grad and there is no backward")
+  return _mla_step(name, "tree_fp8", (tree_mask, kv_scale), q, kv_cache, head_dim_v, kv, lens, block_table, capacity, softmax_scale, False, num_splits,
+                   return_softmax_lse)
+
+
 # ---- ragged query batches (continuous batching, chunked prefill): ffpa_attn_varlen_with_kvcache
 # ----------------------------------------------------------------------------- sparse (top-k indexed) attention over the latent cache
 def compact_topk_indices(indices: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor]":
@@ -914,6 +971,66 @@ def slots_from_block_table(positions: torch.Tensor, block_table: torch.Tensor, p
   safe = torch.where(live, pos, torch.zeros_like(pos))
   page = torch.gather(block_table.to(torch.int64), 1, (safe // page_size).clamp_(max=max(block_table.size(1) - 1, 0)))
   return torch.where(live, page * page_size + safe % page_size, torch.full_like(pos, -1)).to(torch.int32)
+
+
+def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=False):
+  """The argument checks of the two sparse latent calls under their own ``name``, every rule written once and in the order ``ffpa_attn_with_kvcache_mla_sparse`` has
+  always made them -> ``(T, Hq)``.  ``fp8``: the pool is ``torch.float8_e4m3fn`` (``ffpa_attn_with_kvcache_mla_sparse_fp8``) — the dtype rule is the FP8 latent
+  calls', and ``mla_sparse_pool`` holds the pool to the FP8 stride rule and counts its span in its own bytes."""
+  if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
+    raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
+                    "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
+  if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
+    raise TypeError(f"{name}: softmax_scale must be a real number, got {softmax_scale!r}")
+  for nm, t in (("q", q), ("kv_cache", kv_cache), ("indices", indices)) + ((("topk_lens", topk_lens),) if topk_lens is not None else ()):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  if fp8:
+    if q.dtype not in _DTYPES or kv_cache.dtype != torch.float8_e4m3fn:
+      raise TypeError(f"{name} only supports fp16/bf16 q over a torch.float8_e4m3fn kv_cache — OCP e4m3 is the chip's FP8 format; float8_e4m3fnuz and the e5m2 "
+                      f"formats are not served —, got {q.dtype}, {kv_cache.dtype}")
+  elif q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
+  if q.dim() != 3 or kv_cache.dim() not in (3, 4):
+    raise ValueError(f"{name}: q must be [T, Hq, D] (flatten a [B, Sq, Hq, D] step) and kv_cache [num_rows, Hkv, D] or [num_pages, page_size, Hkv, D]")
+  T, Hq, D = q.shape
+  Hkv = kv_cache.size(-2)
+  if kv_cache.size(-1) != D:
+    raise ValueError(f"{name}: head dim of the cache ({kv_cache.size(-1)}) differs from q's ({D})")
+  if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int):
+    raise TypeError(f"{name}: head_dim_v must be an int, got {head_dim_v!r}")
+  if D % 64 != 0 or head_dim_v <= 0 or head_dim_v % 64 != 0 or head_dim_v > D:
+    raise ValueError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}): both must be multiples of 64 with 0 < head_dim_v <= D")
+  from .hip import MLA_BUILDS, mla_sparse_pool
+
+  if (D, head_dim_v) not in MLA_BUILDS:
+    raise NotImplementedError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
+  if Hkv == 0 or Hq % Hkv != 0:
+    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of the latent num_heads ({Hkv})")
+  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
+  if kv_cache.device != q.device:
+    raise ValueError(f"{name}: q / kv_cache must be on one device, got {q.device}, {kv_cache.device}")
+  if kv_cache.stride(-1) != 1:
+    raise ValueError(f"{name}: kv_cache must have a contiguous last dimension")
+  if indices.dim() == 3:
+    raise NotImplementedError(f"{name}: per-head index rows ([T, Hkv, topk]) are not served: all latent heads of a token share one row [T, topk]")
+  if indices.dtype != torch.int32 or indices.dim() != 2 or indices.size(0) != T:
+    raise ValueError(f"{name}: indices must be an int32 tensor [T={T}, topk], got {indices.dtype} {tuple(indices.shape)}")
+  if indices.size(1) < 1:
+    raise ValueError(f"{name}: indices needs at least one entry per token (topk >= 1)")
+  if indices.stride(1) != 1:
+    raise ValueError(f"{name}: indices must have a contiguous last dimension")
+  if indices.device != q.device:
+    raise ValueError(f"{name}: indices must be on q's device, got {indices.device} and {q.device}")
+  if topk_lens is not None and (topk_lens.dtype != torch.int32 or topk_lens.dim() != 1 or topk_lens.numel() != T or topk_lens.device != q.device):
+    raise ValueError(f"{name}: topk_lens must be an int32 tensor [T={T}] on q's device")
+  if kv_cache.numel() == 0:
+    raise ValueError(f"{name}: kv_cache must be a non-empty pool")
+  mla_sparse_pool(kv_cache, name)  # (evenly spaced pages, the span the kernel's offsets reach, an FP8 pool's strides: ValueError, from sizes and strides)
+  return T, Hq
 
 
 def ffpa_attn_with_kvcache_mla_sparse(
@@ -953,66 +1070,61 @@ def ffpa_attn_with_kvcache_mla_sparse(
   step's rows are appended by the latent calls or by the engine).  Nothing is read back to the host: the call — with the merge of a split launch — captures
   into one HIP graph, and a replay follows ``q``, ``indices``, ``topk_lens`` and the pool written in place.  Inference only: a tensor that requires grad raises
   ``NotImplementedError``.  NOT served, each raises ``NotImplementedError`` naming the keyword: ``causal``, ``kv``, ``window_size``, ``softcap``, ``tree_mask``,
-  rotary tables, ALiBi, ``cache_batch_idx`` / ``cache_leftpad``; FP8 latents raise a dtype error."""
+  rotary tables, ALiBi, ``cache_batch_idx`` / ``cache_leftpad``.  FP8 latents are a dtype error HERE: a ``torch.float8_e4m3fn`` pool is
+  ``ffpa_attn_with_kvcache_mla_sparse_fp8``'s."""
   name = "ffpa_attn_with_kvcache_mla_sparse"
   if unsupported:
     raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no causal flag — the indexer has chosen visible keys —, no kv= append, "
                               "no window, soft-cap, tree mask, rotary tables, ALiBi, batch index or leftpad over the sparse latent call)")
-  if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
-    raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
-                    "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
-  if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
-    raise TypeError(f"{name}: softmax_scale must be a real number, got {softmax_scale!r}")
-  for nm, t in (("q", q), ("kv_cache", kv_cache), ("indices", indices)) + ((("topk_lens", topk_lens),) if topk_lens is not None else ()):
-    if not isinstance(t, torch.Tensor):
-      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
-    if t.requires_grad and torch.is_grad_enabled():
-      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
-  if q.dtype not in _DTYPES or kv_cache.dtype != q.dtype:
-    raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
-  if q.dim() != 3 or kv_cache.dim() not in (3, 4):
-    raise ValueError(f"{name}: q must be [T, Hq, D] (flatten a [B, Sq, Hq, D] step) and kv_cache [num_rows, Hkv, D] or [num_pages, page_size, Hkv, D]")
-  T, Hq, D = q.shape
-  Hkv = kv_cache.size(-2)
-  if kv_cache.size(-1) != D:
-    raise ValueError(f"{name}: head dim of the cache ({kv_cache.size(-1)}) differs from q's ({D})")
-  if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int):
-    raise TypeError(f"{name}: head_dim_v must be an int, got {head_dim_v!r}")
-  if D % 64 != 0 or head_dim_v <= 0 or head_dim_v % 64 != 0 or head_dim_v > D:
-    raise ValueError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}): both must be multiples of 64 with 0 < head_dim_v <= D")
-  from .hip import MLA_BUILDS, mla_sparse_pool
-
-  if (D, head_dim_v) not in MLA_BUILDS:
-    raise NotImplementedError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
-  if Hkv == 0 or Hq % Hkv != 0:
-    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of the latent num_heads ({Hkv})")
-  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
-    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
-  if kv_cache.device != q.device:
-    raise ValueError(f"{name}: q / kv_cache must be on one device, got {q.device}, {kv_cache.device}")
-  if kv_cache.stride(-1) != 1:
-    raise ValueError(f"{name}: kv_cache must have a contiguous last dimension")
-  if indices.dim() == 3:
-    raise NotImplementedError(f"{name}: per-head index rows ([T, Hkv, topk]) are not served: all latent heads of a token share one row [T, topk]")
-  if indices.dtype != torch.int32 or indices.dim() != 2 or indices.size(0) != T:
-    raise ValueError(f"{name}: indices must be an int32 tensor [T={T}, topk], got {indices.dtype} {tuple(indices.shape)}")
-  if indices.size(1) < 1:
-    raise ValueError(f"{name}: indices needs at least one entry per token (topk >= 1)")
-  if indices.stride(1) != 1:
-    raise ValueError(f"{name}: indices must have a contiguous last dimension")
-  if indices.device != q.device:
-    raise ValueError(f"{name}: indices must be on q's device, got {indices.device} and {q.device}")
-  if topk_lens is not None and (topk_lens.dtype != torch.int32 or topk_lens.dim() != 1 or topk_lens.numel() != T or topk_lens.device != q.device):
-    raise ValueError(f"{name}: topk_lens must be an int32 tensor [T={T}] on q's device")
-  if kv_cache.numel() == 0:
-    raise ValueError(f"{name}: kv_cache must be a non-empty pool")
-  mla_sparse_pool(kv_cache, name)  # (evenly spaced pages, the span the kernel's offsets reach: ValueError, from sizes and strides)
+  T, Hq = _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits)
   from . import hip  # noqa: F401  (registers the ffpa_attn ops)
 
   if T == 0:
     out = q.new_empty((0, Hq, head_dim_v))
     return (out, q.new_empty((Hq, 0), dtype=torch.float32)) if return_softmax_lse else out
   out, lse = torch.ops.ffpa_attn._mla_sparse_fwd_hip(q, kv_cache, head_dim_v, indices, topk_lens, float(softmax_scale), num_splits)
+  return (out, lse) if return_softmax_lse else out
+
+
+def ffpa_attn_with_kvcache_mla_sparse_fp8(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  indices: torch.Tensor,
+  *,
+  kv_scale: float = 1.0,
+  topk_lens: "torch.Tensor | None" = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """``ffpa_attn_with_kvcache_mla_sparse`` over an FP8 latent pool — DeepSeek-V3.2's top-k attention as an engine with ``kv_cache_dtype="fp8"`` issues it:
+  ``kv_cache`` is ``torch.float8_e4m3fn`` (OCP e4m3; ``float8_e4m3fnuz`` and the e5m2 formats raise ``TypeError``), the whole 576-wide row under ONE per-tensor
+  scale, ``K = kv_scale * K8``.  ``kv_scale`` is a host float, finite and positive (``ValueError``; a tensor raises ``TypeError``).  ``q`` and the output are bf16
+  or fp16.  The rows are read where they lie, as codes: the kernel is the sparse kernel's build whose pieces are 8-byte register loads at the gathered offsets,
+  widened exactly on their way into LDS — no dequantised scratch pool, no gathered copy.  The scale never touches an element: the scores are ``(softmax_scale *
+  kv_scale) * q.K8`` and ``O = kv_scale * sum p K8[:, :head_dim_v]``; with a power-of-two ``kv_scale`` the call returns the bits of
+  ``ffpa_attn_with_kvcache_mla_sparse(q, kv_cache.to(q.dtype), ..., softmax_scale=softmax_scale * kv_scale) * kv_scale``.
+
+  The pool's two forms, ``indices`` / ``topk_lens`` and their safety rules (entries at and past the count are never turned into an address, entries in front of it
+  are clamped into the pool), the required ``softmax_scale``, the ``(576, 512)`` build, ``num_splits``, the returns (``out [T, Hq, head_dim_v]``, fp32 ``lse [Hq,
+  T]``) and the one-graph call are ``ffpa_attn_with_kvcache_mla_sparse``'s.  Two rules are the FP8 pool's own (``ValueError`` before any launch): the row and
+  head strides must be multiples of 16 elements, and the rows of a latent head may span at most 2^31 BYTES — for a pool of one byte per element that is twice as
+  many rows, about 3.7 M dense 576-wide rows.  No ``kv=``: the step's rows are appended by the FP8 latent calls or by the engine
+  (``quantize_latent_rows``).  Not served: per-token / per-block scales (the 656-byte row layout), FP8 ``q``, a ``kv_scale`` on the device."""
+  name = "ffpa_attn_with_kvcache_mla_sparse_fp8"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no causal flag — the indexer has chosen visible keys —, no kv= append, "
+                              "no window, soft-cap, tree mask, rotary tables, ALiBi, batch index or leftpad over the sparse latent call)")
+  from . import hip  # (registers the ffpa_attn ops)
+
+  kv_scale = hip.check_kv_scale(kv_scale, name)
+  T, Hq = _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=True)
+  if T == 0:
+    out = q.new_empty((0, Hq, head_dim_v))
+    return (out, q.new_empty((Hq, 0), dtype=torch.float32)) if return_softmax_lse else out
+  out, lse = torch.ops.ffpa_attn._mla_sparse_fp8_fwd_hip(q, kv_cache, head_dim_v, kv_scale, indices, topk_lens, float(softmax_scale), num_splits)
   return (out, lse) if return_softmax_lse else out
 
 
@@ -1300,6 +1412,40 @@ def ffpa_attn_varlen_with_kvcache_mla_tree(
     raise NotImplementedError(f"{name} is inference only: tree_mask requires grad and there is no backward")
   return _mla_step_varlen(name, "tree", tree_mask, q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, kv, lens, block_table, capacity, softmax_scale, False, num_splits,
                           return_softmax_lse)
+
+
+def ffpa_attn_varlen_with_kvcache_mla_tree_fp8(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  cu_seqlens_q: torch.Tensor,
+  max_seqlen_q: int,
+  cache_seqlens: torch.Tensor,
+  block_table: torch.Tensor | None = None,
+  *,
+  kv_scale: float = 1.0,
+  tree_mask: torch.Tensor,
+  kv: torch.Tensor | None = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """``ffpa_attn_varlen_with_kvcache_mla_tree`` over an FP8 latent cache: the ragged step (``q [T, Hq, D]`` packed by ``cu_seqlens_q``, draft trees of different
+  sizes) of ``ffpa_attn_with_kvcache_mla_tree_fp8`` — ``kv_cache`` is ``torch.float8_e4m3fn`` under the per-tensor ``kv_scale`` (a host float), ``q``, ``kv [T, Hkv,
+  D]`` and the output are bf16 or fp16, and ``kv`` is quantised by the ragged FP8 append as ``quantize_latent_rows(kv, kv_scale)``.  Everything else is
+  ``ffpa_attn_varlen_with_kvcache_mla_tree``'s; every sequence's rows are the bits of the uniform FP8 tree call on that sequence alone."""
+  name = "ffpa_attn_varlen_with_kvcache_mla_tree_fp8"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} ({_MLA_TREE_UNSERVED}; no positions)")
+  from . import hip  # (registers the ffpa_attn ops)
+
+  kv_scale = hip.check_kv_scale(kv_scale, name)
+  capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, fp8=True, ragged=(cu_seqlens_q, max_seqlen_q))
+  if isinstance(tree_mask, torch.Tensor) and tree_mask.requires_grad and torch.is_grad_enabled():
+    raise NotImplementedError(f"{name} is inference only: tree_mask requires grad and there is no backward")
+  return _mla_step_varlen(name, "tree_fp8", (tree_mask, kv_scale), q, kv_cache, head_dim_v, cu_seqlens_q, max_seqlen_q, kv, lens, block_table, capacity, softmax_scale,
+                          False, num_splits, return_softmax_lse)
 
 
 # ---- cascade (shared-prefix) attention: ffpa_attn_with_kvcache_cascade

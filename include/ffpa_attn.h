@@ -550,7 +550,9 @@ int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ff
  *   * m->kv_new (p->dtype) is QUANTISED by the append in front of the attention launch, one store per element:
  *         code = rne_e4m3(clamp(float32(x) * float32(1 / kv_scale), -448, +448)),   NaN stays NaN, +-inf saturates to +-448.
  *   * the plan is the latent call's with the cache priced at one byte per element (the non-temporal rule sees half the bytes).
- * The kernel name reads ffpa_fwd_m16_mla_fp8_kernel<bf16, 576, dv=512>...  Not served: FP8 pools in the sparse and the tree call, per-token / per-block scales.
+ * The kernel name reads ffpa_fwd_m16_mla_fp8_kernel<bf16, 576, dv=512>...  FP8 pools in the tree-mask and the sparse call: ffpa_attn_varlen_mla_tree_fp8_fwd and
+ * ffpa_attn_varlen_mla_sparse_fp8_fwd (below).  Not served: per-token / per-block scales (the 656-byte row layout of DeepSeek-V3.2), an FP8 q, a kv_scale that
+ * lives on the device, FP8 in the two-cache (non-MLA) calls.
  */
 typedef struct ffpa_mla_fp8 {
   uint32_t struct_size; /* sizeof(ffpa_mla_fp8), checked */
@@ -610,6 +612,38 @@ int ffpa_attn_varlen_mla_sparse_fwd(const ffpa_varlen_fwd_params* p, const ffpa_
 size_t ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s);
 int ffpa_attn_varlen_mla_sparse_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]);
 int ffpa_attn_varlen_mla_sparse_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n);
+
+/*
+ * FP8 POOLS IN THE TREE-MASK AND THE SPARSE LATENT CALL — an engine that keeps the latent cache as e4m3 codes keeps it so for every attention call of a step.
+ *
+ * ffpa_attn_varlen_mla_tree_fp8_fwd is ffpa_attn_varlen_mla_tree_fwd over the pool of ffpa_attn_varlen_mla_fp8_fwd: every rule of the tree-mask latent call (the
+ * causal flag is not read, the mask words, tokens <= 64) and every rule of the FP8 latent call (p->k holds e4m3 codes, strides in elements of the pool and
+ * multiples of 16, K = kv_scale * K8, m->kv_new quantised by the same append in front of the launch, the plan priced at one byte per element).  Checks in the
+ * order: f8, the params and the plan, kv, m, tree, the FP8 stride rule.  The kernel name reads ffpa_fwd_m16_mla_tree_fp8_kernel<bf16, 576, dv=512>...
+ *
+ * ffpa_attn_varlen_mla_sparse_fp8_fwd is ffpa_attn_varlen_mla_sparse_fwd over such a pool: p->k holds e4m3 codes, s->kv_stride is in elements of the pool (bytes)
+ * and both strides must be multiples of 16 (FFPA_ERR_BAD_STRIDE); nothing is appended.  The reach of the addressing is the same 2^31 BYTES per latent head, which
+ * a pool of one byte per element fills with twice as many rows: (num_rows - 1) * kv_stride[0] + head_dim <= 2^31 (about 3.7 M contiguous 576-wide rows), else
+ * FFPA_ERR_BAD_SHAPE.  Entries at and past a token's count are never turned into an address, entries in front of it are clamped into the pool, as in the 16-bit
+ * call.  Checks in the order: f8, s and the params, the plan, the (head_dim, head_dim_v) pair, the pool's geometry, the FP8 stride rule.  The kernel name reads
+ * ffpa_fwd_m16_mla_sparse_fp8_kernel<bf16, 576, dv=512>...
+ *
+ * Both: with a power-of-two kv_scale the call returns the bits of its 16-bit twin on the dequantised pool under softmax_scale * kv_scale, O scaled by kv_scale.
+ */
+int ffpa_attn_varlen_mla_tree_fp8_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, const ffpa_mla_fp8* f8,
+                                      void* stream);
+size_t ffpa_attn_varlen_mla_tree_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree,
+                                                         const ffpa_mla_fp8* f8);
+int ffpa_attn_varlen_mla_tree_fp8_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, const ffpa_mla_fp8* f8,
+                                           int out[5]);
+int ffpa_attn_varlen_mla_tree_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree,
+                                             const ffpa_mla_fp8* f8, char* buf, size_t n);
+int ffpa_attn_varlen_mla_tree_fp8_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree,
+                                                    const ffpa_mla_fp8* f8, int* slots);
+int ffpa_attn_varlen_mla_sparse_fp8_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, void* stream);
+size_t ffpa_attn_varlen_mla_sparse_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8);
+int ffpa_attn_varlen_mla_sparse_fp8_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, int out[5]);
+int ffpa_attn_varlen_mla_sparse_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, char* buf, size_t n);
 
 /*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention

@@ -335,6 +335,89 @@ def check_mla_fp8_writes(D=576, sw=None, quiet=False):
   return worst, cycles
 
 
+def mla_gather_image(D, ids, count, num_rows, row_stride, esz, key0=0, sw=None):
+  """The LDS image of ONE gathered tile of the sparse MLA builds, as csrc/ffpa_fwd_m16_paged_body.inc forms it under FFPA_M16_KV_GATHER (FFPA_M16_GATHER_LOAD /
+  FFPA_M16_GATHER_FORM, restated): wave w keeps the ids of keys key0 + 8 w .. + 7 (entries read at min(n, topk - 1)), clamps them into [0, num_rows), gives keys at
+  and past ``count`` bit 31 instead of a row offset, and lane l of its piece i reads  row offset + ((slot ^ sw(key)) << (3 | 4))  through ONE descriptor of
+  ``span`` bytes — a piece spans at most two rows with a compile-time boundary lane.  ``esz``: bytes per pool element (2: the LDS-DMA build, 16 bytes per lane; 1:
+  the FP8 build, 8 bytes per lane widened to 16).  ``row_stride`` in elements.  -> {LDS byte offset of an element: (pool row, column) or None (a zero)}, and
+  asserts that every offset without the sentinel lies wholly inside the span and every offset with it outside."""
+  sw = sw or mla_sw
+  BC, SPR = 32, D // 8
+  PPW = BC * D * 2 // 4096
+  assert PPW * 64 == 8 * SPR
+  row_bytes = row_stride * esz
+  span = (num_rows - 1) * row_bytes + D * esz
+  assert span <= 1 << 31
+  topk = len(ids)
+  img = {}
+  for wave in range(4):
+    g_ro = []
+    left = count - (key0 + 8 * wave)
+    for gk in range(8):
+      n = key0 + 8 * wave + gk
+      rid = ids[min(n, topk - 1)]
+      rid = min(max(rid, 0), num_rows - 1)
+      oob = min(max(gk + 1 - left, 0), 1)
+      g_ro.append(((rid * row_bytes) & 0xffffffff) | (oob << 31))
+    for i in range(PPW):
+      lo, hi = i * 64 // SPR, (i * 64 + 63) // SPR
+      for lane in range(64):
+        g = (wave * PPW + i) * 64 + lane
+        key, slot = divmod(g, SPR)
+        g_sl = (slot ^ sw(D, key)) << (3 if esz == 1 else 4)
+        off = (g_sl + (g_ro[lo] if lane < hi * SPR - i * 64 else g_ro[hi])) & 0xffffffff
+        assert key - 8 * wave == (lo if lane < hi * SPR - i * 64 else hi), "the boundary lane splits the piece where its rows change"
+        dst = (wave * PPW + i) * 1024 + lane * 16
+        live = off + 8 * esz <= span  # (the descriptor's range check of a raw buffer: the whole access inside num_records)
+        assert live == (off < (1 << 31)), (wave, i, lane, off, span)
+        for e in range(8):
+          img[dst + 2 * e] = (off // row_bytes, (off % row_bytes) // esz + e) if live else None
+  assert len(img) == BC * D
+  return img
+
+
+def check_mla_fp8_gather_writes(D=576, cases=None, quiet=False):
+  """The FP8 build of the SPARSE MLA kernel (csrc/ffpa_mla_sparse_fp8_inst.hip: FFPA_M16_KV_GATHER and FFPA_M16_KV_FP8 together): for a gathered tile with
+  arbitrary row ids — in and out of the pool, duplicates, garbage at and past the count — the image its widened ds_write_b128s leave equals, element for element,
+  the image the LDS-DMA pieces of the 16-bit sparse build leave for the same ids over the same rows (``mla_gather_image`` with 1 and 2 bytes per element; the row
+  stride in elements is the same, so the FP8 pool's row bytes are half).  The writes themselves are ``check_mla_fp8_writes``': lane l of piece p at p x 1024 + 16
+  l, conflict-free.  ``cases``: (ids, count, num_rows, row_stride, key0) tuples; default: a seeded set.  -> the number of cases checked."""
+  import random
+
+  if cases is None:
+    rng = random.Random(24)
+    cases = []
+    for num_rows, row_stride in ((1024, D), (1024, 592), (7, 1152), (1, D), (3_700_000, D)):
+      for count in (0, 1, 7, 8, 9, 31, 32, 33, 64, 97):
+        topk = max(count, 1) + rng.choice((0, 3, 40))
+        ids = [rng.randrange(num_rows) for _ in range(count)] + [rng.choice((-1, -(1 << 31), (1 << 31) - 1, num_rows, num_rows + 5)) for _ in range(topk - count)]
+        if count > 2:
+          ids[1] = -3  # (in front of the count and outside the pool: clamped, not followed)
+          ids[2] = num_rows + 11
+        for key0 in range(0, max(count, 1) + 32, 32):
+          cases.append((ids, count, num_rows, row_stride, key0))
+  for ids, count, num_rows, row_stride, key0 in cases:
+    if (num_rows - 1) * row_stride * 2 + D * 2 <= 1 << 31:
+      a = mla_gather_image(D, ids, count, num_rows, row_stride, 2, key0)
+    else:  # (a pool only the FP8 build reaches: the 16-bit image of the rows it names, without that build's span)
+      a = None
+    b = mla_gather_image(D, ids, count, num_rows, row_stride, 1, key0)
+    if a is not None:
+      assert a == b, ("the FP8 gather must leave the 16-bit gather's image", count, num_rows, row_stride, key0)
+    for dst, src in b.items():  # (either way: keys at and past the count are zeros, every other element is a column of a row of the pool)
+      key = dst // (D * 2)
+      if key0 + key >= count:
+        assert src is None
+      else:
+        assert src is not None and 0 <= src[0] < num_rows and 0 <= src[1] < D
+  worst, _ = check_mla_fp8_writes(D, quiet=True)
+  assert worst == 1
+  if not quiet:
+    print(f"D={D:5d} MLA sparse FP8 build: {len(cases)} gathered tiles leave the 16-bit gather's image; ds_write_b128 pattern unchanged (conflict-free)")
+  return len(cases)
+
+
 def variants(D):
   """(D, ND) pairs the library instantiates: the prefill tiles and the short-query (split over 2 / 4 waves) tiles."""
   return [(D, 1 if D <= 512 else 2), (D, 4 if D % 128 == 0 else 2)]
@@ -348,6 +431,7 @@ if __name__ == "__main__":
     print("kernel", end=" ")
     check_m16_shared(576)
     check_mla_fp8_writes(576)
+    check_mla_fp8_gather_writes(576)
     sys.exit(0)
   for D in ([int(x) for x in sys.argv[1:]] or [64, 128, 192, 256, 320, 384, 448, 512, 576, 640, 704, 768, 832, 896, 960, 1024]):
     for d, nd in dict.fromkeys(variants(D)):
