@@ -79,6 +79,10 @@ def _units() -> list[Unit]:
   # the FP8 builds of the sparse and of the tree-mask latent kernel: the same text with the gather resp. the tree hook on next to the FP8 hook, one TU each per pair
   units += [Unit("ffpa_mla_sparse_fp8_inst.hip", f"ffpa_mla_sparse_fp8_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
   units += [Unit("ffpa_mla_tree_fp8_inst.hip", f"ffpa_mla_tree_fp8_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
+  # the sparse latent kernel over the 656-byte FP8 rows of DeepSeek-V3.2 (the gather, the FP8 and the row-format hook on; bf16 only), one TU per pair, and the small
+  # kernel that writes such rows by slot (no inline asm: its assembly lands where the attention ISA rules do not read)
+  units += [Unit("ffpa_mla_sparse_ds_inst.hip", f"ffpa_mla_sparse_ds_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
+  units.append(Unit("ffpa_mla_ds_store.hip", "ffpa_mla_ds_store.o", [], "temps_mla_store", None, True, True))
   # the KV-cache append + rotary launch (every dtype / rotary form) and the merge of two attention states (the cascade's last launch): one small TU each, no
   # inline asm — their assembly lands in directories the attention ISA rules do not read
   units.append(Unit("ffpa_kvcache_append.hip", "ffpa_kvcache_append.o", [], "temps_append", None, True, True))

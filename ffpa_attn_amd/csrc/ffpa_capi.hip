@@ -24,6 +24,7 @@
 #include "ffpa_mla.h"           // (the MLA latent-cache kernels and their append)
 #include "ffpa_mla_fp8.h"       // (the FP8 build of the latent kernel and its quantising appends)
 #include "ffpa_mla_sparse_fp8.h"  // (the FP8 build of the sparse latent kernel)
+#include "ffpa_mla_sparse_ds.h"   // (the sparse latent kernel over the 656-byte FP8 rows of DeepSeek-V3.2, and the store that writes them)
 #include "ffpa_mla_tree_fp8.h"    // (the FP8 build of the tree-mask latent kernel)
 #include "ffpa_mla_sparse.h"    // (the sparse — top-k indexed — build of the latent kernel)
 #include "ffpa_mla_tree.h"      // (the tree-mask build of the latent kernel)
@@ -1173,17 +1174,19 @@ const ffpa_window* softcap_window(const ffpa_window* w) {
 
 // The kernel builds of the latent-cache calls: one row per (head dim, value width) pair with its three launchers — the latent call's (ffpa_mla_inst.hip), the
 // sparse (top-k indexed) call's (ffpa_mla_sparse_inst.hip) and the tree-mask call's (ffpa_mla_tree_inst.hip) — and the FP8 latent call's (ffpa_mla_fp8_inst.hip), the
-// FP8 sparse call's (ffpa_mla_sparse_fp8_inst.hip) and the FP8 tree-mask call's (ffpa_mla_tree_fp8_inst.hip).
+// FP8 sparse call's (ffpa_mla_sparse_fp8_inst.hip) and the FP8 tree-mask call's (ffpa_mla_tree_fp8_inst.hip); last the sparse call's over 656-byte FP8 rows
+// (ffpa_mla_sparse_ds_inst.hip), which takes the latent call's argument structs.
 typedef int (*mla_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, const ffpa::MlaArgs&, hipStream_t);
 typedef int (*mla_fp8_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, const ffpa::MlaFp8Args&, hipStream_t);
 struct MlaBuild {
   int d, dv;
   mla_fn latent, sparse, tree;
   mla_fp8_fn fp8, sparse_fp8, tree_fp8;
+  mla_fn sparse_ds;
 };
 const MlaBuild kMlaBuilds[] = {
 #define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_paged_d##D, &ffpa::launch_mla_sparse_d##D, &ffpa::launch_mla_tree_d##D, &ffpa::launch_mla_fp8_paged_d##D, \
-                         &ffpa::launch_mla_sparse_fp8_d##D, &ffpa::launch_mla_tree_fp8_d##D},
+                         &ffpa::launch_mla_sparse_fp8_d##D, &ffpa::launch_mla_tree_fp8_d##D, &ffpa::launch_mla_sparse_ds_d##D},
     FFPA_FOR_EACH_MLA_BUILD(FFPA_ROW)
 #undef FFPA_ROW
 };
@@ -1269,6 +1272,25 @@ int check_sparse_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s,
   return FFPA_OK;
 }
 
+// The geometry of a pool of 656-byte FP8 rows (ffpa_attn_varlen_mla_sparse_ds_fwd), behind the plan and the (head_dim, head_dim_v) pair, in this order: q's dtype
+// (the rotary bytes of a row are bf16 and reach the kernel's image as they are), the one row format there is, the strides — in BYTES; the kernel's text doubles
+// every stride and its loads are 16 bytes wide —, the base, the reach of the 32-bit offsets.
+int check_sparse_ds_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
+  if (p->dtype != FFPA_DTYPE_BF16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d: the 656-byte rows carry bf16 rotary columns, q must be bf16(0)", p->dtype);
+  if (p->head_dim != ffpa::kDsNope + 64 || s->head_dim_v != ffpa::kDsNope)
+    return fail(FFPA_ERR_BAD_HEADDIM, "(head_dim, head_dim_v) = (%d, %d): a 656-byte row holds (576, 512)", p->head_dim, s->head_dim_v);
+  if (s->kv_stride[0] < 0 || s->kv_stride[1] < 0 || s->kv_stride[0] % 16 != 0 || s->kv_stride[1] % 16 != 0 || s->kv_stride[0] < ffpa::kDsRowBytes ||
+      s->kv_stride[0] >= (1LL << 24))
+    return fail(FFPA_ERR_BAD_STRIDE, "kv strides (slot %lld, head %lld) must be multiples of 16 bytes, slots at least %d and less than 2^24 bytes apart",
+                (long long)s->kv_stride[0], (long long)s->kv_stride[1], ffpa::kDsRowBytes);
+  if (!aligned16(p->k)) return fail(FFPA_ERR_MISALIGNED, "the pool's base must be 16-byte aligned");
+  const int64_t span = ((int64_t)s->num_rows - 1) * s->kv_stride[0] + ffpa::kDsRowBytes;
+  if (span > kSparseSpanBytes)
+    return fail(FFPA_ERR_BAD_SHAPE, "the pool's rows span %lld bytes per head: the sparse call reaches at most 2^31 = %lld ((num_rows - 1) * slot stride + %d)",
+                (long long)span, (long long)kSparseSpanBytes, ffpa::kDsRowBytes);
+  return FFPA_OK;
+}
+
 // ---- The host layer of the packed call and its relatives: a call is DESCRIBED (VarlenCall), PLANNED (plan_call -> CallPlan) and LAUNCHED from its plan
 // (varlen_launch); the plan / kernel / workspace / compact-slots queries are the first two steps and a read-out.
 //
@@ -1286,9 +1308,10 @@ enum class Family {
   kSparse,   // ffpa_attn_varlen_mla_sparse_fwd: sparse — a latent launch without a page pool: the index list stands where the block table stood
   kMlaTreeFp8,  // ffpa_attn_varlen_mla_tree_fp8_fwd: kv, mla, tree, fp8 — kMlaTree over a pool of e4m3 codes: kMlaFp8's plan and append, the tree + FP8 build
   kSparseFp8,   // ffpa_attn_varlen_mla_sparse_fp8_fwd: sparse, fp8 — kSparse over a pool of e4m3 codes: its plan on the FP8 bytes, the gather + FP8 build
+  kSparseDs,    // ffpa_attn_varlen_mla_sparse_ds_fwd: sparse — kSparse over a byte pool of 656-byte FP8 rows: kSparseFp8's plan, the gather + FP8 + row-format build
 };
 bool is_tree(Family f) { return f == Family::kTree || f == Family::kMlaTree || f == Family::kMlaTreeFp8; }
-bool is_sparse(Family f) { return f == Family::kSparse || f == Family::kSparseFp8; }
+bool is_sparse(Family f) { return f == Family::kSparse || f == Family::kSparseFp8 || f == Family::kSparseDs; }
 bool is_window(Family f) { return f == Family::kWindow || f == Family::kSoftcap; }
 
 struct VarlenCall {
@@ -1356,6 +1379,12 @@ VarlenCall sparse_fp8_call(ParamsPtr p, const ffpa_mla_sparse* s, const ffpa_mla
   return c;
 }
 
+VarlenCall sparse_ds_call(ParamsPtr p, const ffpa_mla_sparse* s) {
+  VarlenCall c = make_call(Family::kSparseDs, p, nullptr);
+  c.sparse = s;
+  return c;
+}
+
 // What plan_call makes of a call: everything the launch and the queries read.  (It points into itself: made in place, never copied.)
 struct CallPlan {
   VarlenPlan pl;
@@ -1367,6 +1396,7 @@ struct CallPlan {
   mla_fn launch_mla;                // ... and the build of the latent kernel it launches
   const ffpa_mla_fp8* fp8;          // the FP8 latent launch: its scale ...
   mla_fp8_fn launch_mla_fp8;        // ... and its build (launch_mla is NULL then)
+  bool byte_pool;                   // a latent launch without ffpa_mla_fp8 over a pool counted in bytes (656-byte rows): the kernel takes its strides in units of two
 };
 
 // The window call's plan is the packed call's, PRICED AT WHAT THE WINDOW LEAVES.  A row tile of R token rows (all max_seqlen_q tokens under GQA row packing, else
@@ -1427,6 +1457,7 @@ int plan_call(const VarlenCall& c, CallPlan* cp) {
   cp->launch_mla = nullptr;
   cp->fp8 = nullptr;
   cp->launch_mla_fp8 = nullptr;
+  cp->byte_pool = false;
   switch (c.family) {
     case Family::kPacked:
       return varlen_plan(p, pl);
@@ -1506,6 +1537,15 @@ int plan_call(const VarlenCall& c, CallPlan* cp) {
       if ((rc = check_fp8_strides(c.sparse->kv_stride[0], c.sparse->kv_stride[1], 0)) != FFPA_OK) return rc;
       cp->fp8 = c.fp8;
       cp->launch_mla_fp8 = build->sparse_fp8;
+      return FFPA_OK;
+    case Family::kSparseDs:  // kSparseFp8's order without the FP8 struct — the scales lie in the rows —, its plan, then the row format's own rules
+      if ((rc = check_sparse(p, c.sparse)) != FFPA_OK) return rc;
+      price_sparse(p, c.sparse, cp);
+      if ((rc = varlen_plan(cp->p, pl, true, true, 1)) != FFPA_OK) return rc;
+      if ((rc = check_mla(cp->p, cp->mla, &build)) != FFPA_OK) return rc;
+      if ((rc = check_sparse_ds_pool(p, c.sparse)) != FFPA_OK) return rc;
+      cp->launch_mla = build->sparse_ds;
+      cp->byte_pool = true;
       return FFPA_OK;
   }
   return fail(FFPA_ERR_UNSUPPORTED, "unknown call family %d", (int)c.family);
@@ -1679,6 +1719,7 @@ int varlen_launch(const VarlenCall& c, void* stream) {
       if (st == 0) st = cp.launch_mla_fp8(p->dtype, pl.nt, a, va, pa, ma, static_cast<hipStream_t>(stream));
     } else if (latent) {
       st = 0;
+      if (cp.byte_pool) a.sk[1] /= 2, a.sk[2] /= 2, a.sv[1] /= 2, a.sv[2] /= 2;  // (strides in bytes, multiples of 16: the kernel's text doubles them)
       if (mla->seqlen_new > 0) {
         // the step's latent rows first, ONE store per element (there is one cache), and the lengths the attention launch behind it reads
         ffpa::MlaAppendArgs ap;
@@ -1751,6 +1792,7 @@ int call_kernel(const VarlenCall& c, char* buf, size_t n) {
                        : c.family == Family::kMlaTree    ? "_tree"
                        : c.family == Family::kMlaFp8     ? "_fp8"
                        : c.family == Family::kSparseFp8  ? "_sparse_fp8"
+                       : c.family == Family::kSparseDs   ? "_sparse_ds"
                        : c.family == Family::kMlaTreeFp8 ? "_tree_fp8"
                                                          : "";
     snprintf(buf, n, "ffpa_fwd_m16_mla%s_kernel<%s, %d, dv=%d%s>%s%s%s", kind, c.p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", c.p->head_dim, cp.mla->head_dim_v, nt,
@@ -1916,6 +1958,44 @@ int ffpa_attn_varlen_mla_sparse_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, 
 }
 size_t ffpa_attn_varlen_mla_sparse_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8) {
   return call_workspace_bytes(sparse_fp8_call(p, s, f8));
+}
+
+// ---- the sparse latent call over the 656-byte FP8 rows of DeepSeek-V3.2, and the store that writes such rows by slot
+int ffpa_attn_varlen_mla_sparse_ds_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream) { return varlen_launch(sparse_ds_call(p, s), stream); }
+int ffpa_attn_varlen_mla_sparse_ds_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]) { return call_plan(sparse_ds_call(p, s), out); }
+int ffpa_attn_varlen_mla_sparse_ds_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n) {
+  return call_kernel(sparse_ds_call(p, s), buf, n);
+}
+size_t ffpa_attn_varlen_mla_sparse_ds_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
+  return call_workspace_bytes(sparse_ds_call(p, s));
+}
+int ffpa_attn_mla_ds_store(const ffpa_mla_ds_store_params* p, void* stream) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_mla_ds_store_params))
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_ds_store_params ABI mismatch: size %u (want %zu)", p->struct_size, sizeof(ffpa_mla_ds_store_params));
+  if (p->reserved != 0 || p->reserved2 != 0) return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_ds_store_params.reserved=%u / reserved2=%d must be 0", p->reserved, p->reserved2);
+  if (p->dtype != FFPA_DTYPE_BF16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d: the 656-byte rows carry bf16 rotary columns, kv_new must be bf16(0)", p->dtype);
+  if (p->head_dim != ffpa::kDsNope + 64) return fail(FFPA_ERR_BAD_HEADDIM, "head_dim=%d: a 656-byte row holds 576 columns", p->head_dim);
+  if (p->tokens < 0 || p->heads_kv <= 0 || p->num_rows <= 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "tokens=%d must not be negative, heads_kv=%d / num_rows=%d must be positive", p->tokens, p->heads_kv, p->num_rows);
+  if ((int64_t)p->tokens * p->heads_kv > 0x7fffffffLL) return fail(FFPA_ERR_BAD_SHAPE, "grid of %lld rows is too large", (long long)p->tokens * p->heads_kv);
+  if (!p->kv_cache || (p->tokens > 0 && (!p->kv_new || !p->slots))) return fail(FFPA_ERR_NULL_POINTER, "kv_cache / kv_new / slots must be non-NULL");
+  if (!aligned16(p->kv_cache) || (p->tokens > 0 && !aligned16(p->kv_new)) || (reinterpret_cast<uintptr_t>(p->slots) & 3u))
+    return fail(FFPA_ERR_MISALIGNED, "kv_new / kv_cache must be 16-byte aligned and slots 4-byte aligned");
+  int rc;
+  if (p->tokens > 0 && (rc = check_strides("kv_new", p->kv_new_stride, 2))) return rc;
+  if (p->kv_cache_stride[0] < ffpa::kDsRowBytes || p->kv_cache_stride[1] < 0 || p->kv_cache_stride[0] % 16 != 0 || p->kv_cache_stride[1] % 16 != 0)
+    return fail(FFPA_ERR_BAD_STRIDE, "kv_cache strides (slot %lld, head %lld) must be multiples of 16 bytes, slots at least %d bytes apart",
+                (long long)p->kv_cache_stride[0], (long long)p->kv_cache_stride[1], ffpa::kDsRowBytes);
+  if ((rc = check_device()) != FFPA_OK) return rc;
+  ffpa::MlaDsStoreArgs a;
+  memset(&a, 0, sizeof(a));
+  a.kv_new = p->kv_new, a.slots = p->slots, a.pool = p->kv_cache;
+  for (int i = 0; i < 2; ++i) a.s_new[i] = p->kv_new_stride[i], a.s_pool[i] = p->kv_cache_stride[i];
+  a.T = p->tokens, a.Hkv = p->heads_kv, a.num_rows = p->num_rows;
+  const int st = ffpa::launch_mla_ds_store(a, static_cast<hipStream_t>(stream));
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla ds store launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
 }
 
 // ---- the sparse latent call (include/ffpa_attn.h: ffpa_mla_sparse): the latent launch over per-token index lists

@@ -28,24 +28,41 @@
   // Over an FP8 pool (FFPA_M16_KV_FP8 of the tile text, set by ffpa_mla_sparse_fp8_inst.hip: one byte per element, the pieces are 8-byte register loads) the same
   // rule holds in the pool's bytes: a slot's 8 elements are 8 bytes of the source (g_sl: << 3), a row's D bytes end the span, and the row term is the BYTE row
   // stride — strides arrive in units of two bytes and k_row_bytes doubles them.  The sentinel is the same bit of the same 32-bit offset of the same descriptor.
+  // Over the 656-byte FP8 rows of DeepSeek-V3.2 (FFPA_M16_KV_DS of the tile text, set by ffpa_mla_sparse_ds_inst.hip together with the three macros read here) a
+  // row is no array of equal slots: slot s of the image lies at FFPA_M16_KV_DS_SLOT_OFF(s) bytes of the row — eight codes, or sixteen rotary bytes —, a row's
+  // FFPA_M16_KV_DS_ROW_BYTES end the span, and g_sd[i] keeps what leads from the lane's slot of piece i to the scale of its 128 columns
+  // (FFPA_M16_KV_DS_SCALE_DELTA; the scale load adds it to krel[i], sentinel and all).  The row term and the sentinel are the FP8 pool's.
 #ifdef FFPA_M16_KV_FP8
 #define FFPA_M16_GATHER_ESZ (FFPA_M16_KV_FP8 ? 1 : 2)
 #else
 #define FFPA_M16_GATHER_ESZ 2
 #endif
+#ifdef FFPA_M16_KV_DS
+#define FFPA_M16_GATHER_ROW_BYTES FFPA_M16_KV_DS_ROW_BYTES
+#define FFPA_M16_GATHER_SLOT_OFF(s_) FFPA_M16_KV_DS_SLOT_OFF(s_)
+#else
+#define FFPA_M16_GATHER_ROW_BYTES (D * FFPA_M16_GATHER_ESZ)
+#define FFPA_M16_GATHER_SLOT_OFF(s_) ((s_) << (FFPA_M16_GATHER_ESZ == 1 ? 3 : 4))
+#endif
   constexpr int kGSpr = D / 8;  // 16-byte slots per row (of the LDS image; 8 x FFPA_M16_GATHER_ESZ bytes of the source)
   static_assert(FFPA_M16_MLA_ON && PPW * 64 == 8 * kGSpr, "gathered keys: a wave's pieces of a tile are whole rows, eight of them");
   using cint_ptr = __attribute__((address_space(4))) const int*;  // (constant address space: a uniform load is a scalar load)
   const cint_ptr g_idx = (cint_ptr)(pa.table + (int64_t)seq * pa.bt_stride);
-  const uint32_t g_span = (uint32_t)(pa.num_pages - 1) * ((uint32_t)a.sk[2] * 2u) + (uint32_t)(D * FFPA_M16_GATHER_ESZ);  // bytes of a head's rows in the pool (<= 2^31: the launch side)
+  const uint32_t g_span = (uint32_t)(pa.num_pages - 1) * ((uint32_t)a.sk[2] * 2u) + (uint32_t)FFPA_M16_GATHER_ROW_BYTES;  // bytes of a head's rows in the pool (<= 2^31: the launch side)
   int g_id[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the loaded row ids: this wave's keys of the tile whose offsets are formed next
   int g_next = 0;                          // first key of the tile whose ids are loaded next
   uint32_t g_sl[PPW];
+#ifdef FFPA_M16_KV_DS
+  uint32_t g_sd[PPW];
+#endif
 #pragma unroll
   for (int i = 0; i < PPW; ++i) {
     const int g = (wave * PPW + i) * 64 + lane;
     const int key = g / kGSpr;
-    g_sl[i] = (uint32_t)(((g - key * kGSpr) ^ m16_v_swizzle<D>(key)) << (FFPA_M16_GATHER_ESZ == 1 ? 3 : 4));
+    g_sl[i] = (uint32_t)FFPA_M16_GATHER_SLOT_OFF((g - key * kGSpr) ^ m16_v_swizzle<D>(key));
+#ifdef FFPA_M16_KV_DS
+    g_sd[i] = FFPA_M16_KV_DS_SCALE_DELTA((g - key * kGSpr) ^ m16_v_swizzle<D>(key));
+#endif
   }
 // (macros, not lambdas: they name krel[] and k_row_bytes of the tile text, and a lambda here would renumber the tile text's)
 #define FFPA_M16_GATHER_LOAD(key0_)                                        \
@@ -168,6 +185,8 @@
 #if FFPA_M16_KV_GATHER
 #undef FFPA_M16_GATHER_FORM
 #undef FFPA_M16_GATHER_LOAD
+#undef FFPA_M16_GATHER_SLOT_OFF
+#undef FFPA_M16_GATHER_ROW_BYTES
 #undef FFPA_M16_GATHER_ESZ
 #endif
 #ifdef FFPA_M16_PAGED_GATHER_DEFAULT

@@ -85,6 +85,20 @@
 #define FFPA_M16_KV_FP8_LOAD(rsrc_, voff_) u32x2{0u, 0u}
 #define FFPA_M16_KV_FP8_DEFAULT_HOOKS
 #endif
+// THE 656-BYTE FP8 ROWS OF DEEPSEEK-V3.2 (ffpa_mla_sparse_ds_inst.hip, on top of the FP8 and the gather hook): FFPA_M16_KV_DS = a constant of its build — a row is
+// 512 e4m3 codes, four float32 scales (one per 128 columns) and 64 bf16 rotary columns.  The FP8 build's schedule with another piece: where that build issues one
+// 8-byte load per lane, this one issues FFPA_M16_KV_DS_LOAD(rsrc, voff) — sixteen bytes at the lane's source slot, krel[] as the gather forms it — into kvd[i] and
+// FFPA_M16_KV_DS_LOAD_SCALE(rsrc, voff, i) — the dword of the slot's scale, the same offset + a lane constant — into kvs[i]; the commit writes a lane of the rotary
+// slots (image slot (64 i + lane) mod 72 >= 64: the swizzle permutes inside 8-slot groups, so the source slot is rotary exactly then) as loaded and every other lane
+// as FFPA_M16_KV_DS_WIDEN(kvd[i], kvs[i]): code x scale, rounded once.  A lane without a row loads zeros twice and writes 0 x 0.  FFPA_M16_KV_SCALE is 1.
+// Kernels that do not define the hook stage no such rows: the text that stood here.
+#ifndef FFPA_M16_KV_DS
+#define FFPA_M16_KV_DS false
+#define FFPA_M16_KV_DS_LOAD(rsrc_, voff_) u32x4{0u, 0u, 0u, 0u}
+#define FFPA_M16_KV_DS_LOAD_SCALE(rsrc_, voff_, i_) 0.f
+#define FFPA_M16_KV_DS_WIDEN(raw_, scale_) (raw_)
+#define FFPA_M16_KV_DS_DEFAULT_HOOKS
+#endif
 #ifndef FFPA_M16_KV_SRC
 #define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) tile_src<BC>(slice, row_bytes, key0, a.Nkv, rb_valid)
 #define FFPA_M16_KV_BEGIN(t0_)
@@ -169,16 +183,30 @@
   // FP8: this wave's pieces of the latent tile at key0, staged in registers by issue_k / issue_k_on, and their commit to the image of the tile's parity — lane l's
   // slot of piece i at + i KiB + 16 l, the LDS-DMA's lane-linear rule.  (a macro, not a lambda: see FFPA_M16_MLA_DST)
   u32x2 kv8[FFPA_M16_KV_FP8 ? PPW : 1];
+  static_assert(!FFPA_M16_KV_DS || (FFPA_M16_KV_FP8 && FFPA_M16_KV_GATHER), "the 656-byte row hook lives on top of the FP8 and the gather hook");
+  u32x4 kvd[FFPA_M16_KV_DS ? PPW : 1];  // (656-byte rows: the sixteen bytes at the lane's slot and the slot's scale)
+  float kvs[FFPA_M16_KV_DS ? PPW : 1];
 #define FFPA_M16_KV_FP8_COMMIT(key0_)                                                                                        \
   {                                                                                                                          \
     FFPA_LDS char* const dst8_ = ((((key0_) / BC) & 1) != 0 ? Vt : Kt) + wave * (PPW * 1024) + lane * 16;                    \
+    if constexpr (FFPA_M16_KV_DS) {                                                                                          \
+      _Pragma("unroll") for (int i8_ = 0; i8_ < PPW; ++i8_) {                                                                \
+        const bool rope8_ = (uint32_t)(lane + (64 * i8_) % (D / 8) - 64) < 8u; /* image slot (64 i + lane) mod 72 >= 64 */   \
+        const u32x4 w8_ = FFPA_M16_KV_DS_WIDEN(kvd[i8_], kvs[i8_]);                                                          \
+        *(FFPA_LDS u32x4*)(dst8_ + i8_ * 1024) = rope8_ ? kvd[i8_] : w8_;                                                    \
+      }                                                                                                                      \
+    } else {                                                                                                                 \
     _Pragma("unroll") for (int i8_ = 0; i8_ < PPW; ++i8_) *(FFPA_LDS u32x4*)(dst8_ + i8_ * 1024) = fp8x8_widen<T>(kv8[i8_]); \
+    }                                                                                                                        \
   }
   auto issue_k = [&](auto ic, int key0) {
     constexpr int i = decltype(ic)::value;
     const TileSrc ts = FFPA_M16_KV_SRC(0, Kg, k_row_bytes, key0);
     if constexpr (kRowDma) {
       lds_dma_row<(16 * (i >> 2) + (i & 3)) * RB, 0>(ts.rsrc, k_lds, kvo[i & 3], kro[i]);
+    } else if constexpr (FFPA_M16_KV_DS) {
+      kvd[i] = FFPA_M16_KV_DS_LOAD(ts.rsrc, krel[i]);
+      kvs[i] = FFPA_M16_KV_DS_LOAD_SCALE(ts.rsrc, krel[i], i);
     } else if constexpr (FFPA_M16_KV_FP8) {
       kv8[i] = FFPA_M16_KV_FP8_LOAD(ts.rsrc, krel[i]);
     } else {
@@ -205,6 +233,10 @@
       if constexpr (decltype(kindc)::value == 0) M::first(d, fa, fb);
       else if constexpr (decltype(kindc)::value == 1) M::acc(d, fa, fb);
       else M::acc_a(d, fa, fb);
+      if constexpr (FFPA_M16_KV_DS) {
+        kvd[kRowDma ? 0 : i] = FFPA_M16_KV_DS_LOAD(ts.rsrc, krel[kRowDma ? 0 : i]);
+        kvs[kRowDma ? 0 : i] = FFPA_M16_KV_DS_LOAD_SCALE(ts.rsrc, krel[kRowDma ? 0 : i], kRowDma ? 0 : i);
+      } else
       kv8[kRowDma ? 0 : i] = FFPA_M16_KV_FP8_LOAD(ts.rsrc, krel[kRowDma ? 0 : i]);
     } else
     M::template with_dma<decltype(kindc)::value, (kKS && i >= kH ? 2 * PPW + (i - kH) : i) * 1024>(d, fa, fb, ts.rsrc, FFPA_M16_MLA_ON ? FFPA_M16_MLA_DST(key0) : k_lds, krel[kRowDma ? 0 : i], 0u);
@@ -1511,6 +1543,13 @@
 #endif
 #undef FFPA_M16_MLA_DST
 #undef FFPA_M16_KV_FP8_COMMIT
+#ifdef FFPA_M16_KV_DS_DEFAULT_HOOKS
+#undef FFPA_M16_KV_DS_DEFAULT_HOOKS
+#undef FFPA_M16_KV_DS_WIDEN
+#undef FFPA_M16_KV_DS_LOAD_SCALE
+#undef FFPA_M16_KV_DS_LOAD
+#undef FFPA_M16_KV_DS
+#endif
 #ifdef FFPA_M16_KV_FP8_DEFAULT_HOOKS
 #undef FFPA_M16_KV_FP8_DEFAULT_HOOKS
 #undef FFPA_M16_KV_FP8_LOAD

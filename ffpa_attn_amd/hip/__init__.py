@@ -242,6 +242,26 @@ class FfpaMlaSparse(ctypes.Structure):
   ]
 
 
+class FfpaMlaDsStoreParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_mla_ds_store_params`` (include/ffpa_attn.h): the store of new latent rows into a pool of 656-byte FP8 rows, by slot."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("kv_new", ctypes.c_void_p),
+    ("slots", ctypes.c_void_p),
+    ("kv_cache", ctypes.c_void_p),
+    ("kv_new_stride", ctypes.c_int64 * 2),
+    ("kv_cache_stride", ctypes.c_int64 * 2),
+    ("tokens", ctypes.c_int32),
+    ("heads_kv", ctypes.c_int32),
+    ("num_rows", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("dtype", ctypes.c_int32),
+    ("reserved2", ctypes.c_int32),
+  ]
+
+
 class FfpaMlaAppendVarlenParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_mla_append_varlen_params`` (include/ffpa_attn.h): the latent append of a ragged step."""
 
@@ -441,6 +461,11 @@ _BINDINGS = (
   ("ffpa_attn_varlen_mla_sparse_fp8_fwd_plan", _MLA_SPARSE_FP8 + [_P(_INT)], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_fp8_fwd_kernel", _MLA_SPARSE_FP8 + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_fp8_fwd_workspace_bytes", _MLA_SPARSE_FP8, _SIZE, 7),
+  ("ffpa_attn_varlen_mla_sparse_ds_fwd", _MLA_SPARSE + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_ds_fwd_plan", _MLA_SPARSE + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_ds_fwd_kernel", _MLA_SPARSE + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_ds_fwd_workspace_bytes", _MLA_SPARSE, _SIZE, 7),
+  ("ffpa_attn_mla_ds_store", [_P(FfpaMlaDsStoreParams), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
@@ -535,7 +560,7 @@ def _stamped(cls):
   """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` / ``ffpa_window`` / ``ffpa_mla`` ride next to a versioned struct), the ABI version — filled in."""
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
-  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse, FfpaMlaFp8):
+  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse, FfpaMlaFp8, FfpaMlaDsStoreParams):
     p.abi_version = ABI_VERSION
   return p
 
@@ -1817,6 +1842,20 @@ def mla_sparse_pool(kv_cache: torch.Tensor, name: str = "ffpa_attn::_mla_sparse_
   ``[num_pages, page_size, Hkv, D]`` of any positive ``page_size`` whose pages are evenly spaced (slot r = row ``r % page_size`` of page ``r // page_size`` then
   lies ``r`` row strides from the base).  ``ValueError``: pages that are not evenly spaced, and a pool whose rows span more than ``MLA_SPARSE_SPAN_BYTES`` —
   from sizes and strides alone, so in front of any launch and without touching the pool's memory."""
+  num_rows, row_stride, head_stride = _mla_sparse_slots(kv_cache, name)
+  if kv_cache.element_size() == 1 and (row_stride % 16 != 0 or head_stride % 16 != 0):
+    # (an FP8 pool: its loads are 8 bytes wide and the kernel's text doubles every stride; the span below counts its bytes — twice the rows of a 16-bit pool)
+    raise ValueError(f"{name}: the row and head strides of an FP8 pool ({row_stride}, {head_stride}) must be multiples of 16 elements")
+  span = (num_rows - 1) * row_stride * kv_cache.element_size() + kv_cache.size(-1) * kv_cache.element_size() if num_rows > 0 else 0
+  if span > MLA_SPARSE_SPAN_BYTES:
+    raise ValueError(f"{name}: the pool's rows span {span} bytes per latent head ((num_rows - 1) * row stride + one row = ({num_rows} - 1) * "
+                     f"{row_stride * kv_cache.element_size()} + {kv_cache.size(-1) * kv_cache.element_size()}); the sparse call's 32-bit offsets reach at most "
+                     f"2^31 = {MLA_SPARSE_SPAN_BYTES} bytes: hand it a view of the part of the pool the step's slots lie in")
+  return num_rows, row_stride, head_stride
+
+
+def _mla_sparse_slots(kv_cache: torch.Tensor, name: str) -> "tuple[int, int, int]":
+  """``mla_sparse_pool``'s first half, shared with ``mla_sparse_ds_pool``: the two pool forms -> ``(num_rows, row stride, head stride)`` in elements."""
   if kv_cache.dim() == 4:
     pages, page_size = kv_cache.size(0), kv_cache.size(1)
     if page_size <= 0:
@@ -1831,14 +1870,24 @@ def mla_sparse_pool(kv_cache: torch.Tensor, name: str = "ffpa_attn::_mla_sparse_
     raise ValueError(f"{name}: kv_cache must be the flat pool [num_rows, Hkv, D] or a page pool [num_pages, page_size, Hkv, D], got {kv_cache.dim()}-D")
   if num_rows > 0x7fffffff:
     raise ValueError(f"{name}: a pool of {num_rows} rows is too large (slots are int32)")
-  if kv_cache.element_size() == 1 and (row_stride % 16 != 0 or head_stride % 16 != 0):
-    # (an FP8 pool: its loads are 8 bytes wide and the kernel's text doubles every stride; the span below counts its bytes — twice the rows of a 16-bit pool)
-    raise ValueError(f"{name}: the row and head strides of an FP8 pool ({row_stride}, {head_stride}) must be multiples of 16 elements")
-  span = (num_rows - 1) * row_stride * kv_cache.element_size() + kv_cache.size(-1) * kv_cache.element_size() if num_rows > 0 else 0
+  return num_rows, row_stride, head_stride
+
+
+MLA_DS_ROW_BYTES = 656  # a latent row of DeepSeek-V3.2's FP8 cache: 512 e4m3 codes, four float32 scales (one per 128 columns), 64 bf16 rotary columns
+
+
+def mla_sparse_ds_pool(kv_cache: torch.Tensor, name: str = "ffpa_attn::_mla_sparse_ds_fwd_hip") -> "tuple[int, int, int]":
+  """``mla_sparse_pool`` for a ``torch.uint8`` pool of 656-byte rows -> ``(num_rows, slot stride, head stride)`` in BYTES.  ``ValueError``: pages that are not
+  evenly spaced, a stride that is no multiple of 16 or a slot stride below 656, a pool whose rows span more than ``MLA_SPARSE_SPAN_BYTES``."""
+  num_rows, row_stride, head_stride = _mla_sparse_slots(kv_cache, name)
+  if row_stride % 16 != 0 or head_stride % 16 != 0 or (num_rows > 1 and row_stride < MLA_DS_ROW_BYTES):
+    raise ValueError(f"{name}: the slot and head strides of the pool ({row_stride}, {head_stride}) must be multiples of 16 bytes, slots at least "
+                     f"{MLA_DS_ROW_BYTES} bytes apart")
+  span = (num_rows - 1) * row_stride + MLA_DS_ROW_BYTES if num_rows > 0 else 0
   if span > MLA_SPARSE_SPAN_BYTES:
-    raise ValueError(f"{name}: the pool's rows span {span} bytes per latent head ((num_rows - 1) * row stride + one row = ({num_rows} - 1) * "
-                     f"{row_stride * kv_cache.element_size()} + {kv_cache.size(-1) * kv_cache.element_size()}); the sparse call's 32-bit offsets reach at most "
-                     f"2^31 = {MLA_SPARSE_SPAN_BYTES} bytes: hand it a view of the part of the pool the step's slots lie in")
+    raise ValueError(f"{name}: the pool's rows span {span} bytes per latent head ((num_rows - 1) * slot stride + one row = ({num_rows} - 1) * {row_stride} + "
+                     f"{MLA_DS_ROW_BYTES}); the sparse call's 32-bit offsets reach at most 2^31 = {MLA_SPARSE_SPAN_BYTES} bytes: hand it a view of the part of "
+                     "the pool the step's slots lie in")
   return num_rows, row_stride, head_stride
 
 
@@ -1868,28 +1917,36 @@ def _mla_sparse_args(dtype, T: int, Hq: int, Hkv: int, D: int, head_dim_v: int, 
 
 
 def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, indices: torch.Tensor, topk_lens: "torch.Tensor | None", softmax_scale: float, *,
-                       return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0, kv_scale: "float | None" = None):
+                       return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0, kv_scale: "float | None" = None,
+                       ds: bool = False):
   """One call of ``ffpa_attn_varlen_mla_sparse_fwd``: ``q [T, Hq, D]`` (one row per query token), the latent pool ``kv_cache`` (``mla_sparse_pool``'s two forms),
   the int32 device ``indices [T, topk]`` of pool slots and the optional int32 ``topk_lens [T]`` -> ``(o [T, Hq, head_dim_v], lse [Hq, T] fp32 | None)``.  Token t
   attends to the rows ``indices[t, :clamp(topk_lens[t], 0, topk)]``; entries at and past the count are never turned into an address.  Nothing is read back to the
   host: the call (and the split launch's merge) captures into a HIP graph.  ``flags`` / ``plan_out`` / ``num_splits`` as ``varlen_forward``.
 
   ``kv_scale`` (a host float, finite and > 0; ``mla_sparse_fp8_forward`` is this call with it): the pool is ``torch.float8_e4m3fn`` — OCP e4m3 codes, K = kv_scale x
-  K8, row and head strides multiples of 16 — and the call is ``ffpa_attn_varlen_mla_sparse_fp8_fwd``, its own kernel; q and o stay bf16 / fp16."""
+  K8, row and head strides multiples of 16 — and the call is ``ffpa_attn_varlen_mla_sparse_fp8_fwd``, its own kernel; q and o stay bf16 / fp16.
+
+  ``ds`` (``mla_sparse_ds_forward`` is this call with it): the pool is ``torch.uint8`` rows of ``MLA_DS_ROW_BYTES`` (``mla_sparse_ds_pool``'s two forms, strides in
+  bytes), q and o are bf16, and the call is ``ffpa_attn_varlen_mla_sparse_ds_fwd``."""
   fp8 = kv_scale is not None
-  name = "ffpa_attn::_mla_sparse_fp8_fwd_hip" if fp8 else "ffpa_attn::_mla_sparse_fwd_hip"
-  export = "ffpa_attn_varlen_mla_sparse_fp8_fwd" if fp8 else "ffpa_attn_varlen_mla_sparse_fwd"
+  name = "ffpa_attn::_mla_sparse_ds_fwd_hip" if ds else "ffpa_attn::_mla_sparse_fp8_fwd_hip" if fp8 else "ffpa_attn::_mla_sparse_fwd_hip"
+  export = "ffpa_attn_varlen_mla_sparse_ds_fwd" if ds else "ffpa_attn_varlen_mla_sparse_fp8_fwd" if fp8 else "ffpa_attn_varlen_mla_sparse_fwd"
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
-  if fp8:
+  if ds:
+    if q.dtype != torch.bfloat16 or kv_cache.dtype != torch.uint8:
+      raise TypeError(f"{name} only supports bf16 q over a torch.uint8 kv_cache of {MLA_DS_ROW_BYTES}-byte rows, got {q.dtype}, {kv_cache.dtype}")
+  elif fp8:
     if q.dtype not in _DTYPE or kv_cache.dtype != torch.float8_e4m3fn:
       raise TypeError(f"{name} only supports fp16/bf16 q over a torch.float8_e4m3fn kv_cache (OCP e4m3, the chip's FP8 format), got {q.dtype}, {kv_cache.dtype}")
     kv_scale = check_kv_scale(kv_scale, name)
   elif q.dtype not in _DTYPE or kv_cache.dtype != q.dtype:
     raise TypeError(f"{name} only supports fp16/bf16 q/kv_cache of one dtype, got {q.dtype}, {kv_cache.dtype}")
-  if q.dim() != 3 or kv_cache.dim() not in (3, 4) or kv_cache.size(-1) != q.size(2):
-    raise ValueError(f"{name}: q must be [T, Hq, D] and kv_cache [num_rows, Hkv, D] or [num_pages, page_size, Hkv, D] of q's head dim")
+  if q.dim() != 3 or kv_cache.dim() not in (3, 4) or kv_cache.size(-1) != (MLA_DS_ROW_BYTES if ds else q.size(2)):
+    raise ValueError(f"{name}: q must be [T, Hq, D] and kv_cache [num_rows, Hkv, D] or [num_pages, page_size, Hkv, D] of " +
+                     (f"{MLA_DS_ROW_BYTES}-byte rows" if ds else "q's head dim"))
   T, Hq, D = q.shape
   Hkv = kv_cache.size(-2)
   if (D, int(head_dim_v)) not in MLA_BUILDS:
@@ -1903,9 +1960,9 @@ def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int,
   if kv_cache.device != q.device or kv_cache.numel() == 0:
     raise ValueError(f"{name}: kv_cache must be a non-empty pool on q's device")
   if not _layout_ok(kv_cache, -3):
-    raise ValueError(f"{name}: kv_cache needs head-dim stride 1, strides that are multiples of {16 if fp8 else 8} elements and a 16-byte aligned base (it is read "
-                     "in place)")
-  num_rows, row_stride, head_stride = mla_sparse_pool(kv_cache, name)
+    raise ValueError(f"{name}: kv_cache needs head-dim stride 1, strides that are multiples of {16 if fp8 or ds else 8} elements and a 16-byte aligned base (it is "
+                     "read in place)")
+  num_rows, row_stride, head_stride = (mla_sparse_ds_pool if ds else mla_sparse_pool)(kv_cache, name)
   topk = indices.size(1)
   q = _rows(q, 0)
   if indices.stride(1) != 1 or indices.data_ptr() % 4 != 0 or (T > 1 and indices.stride(0) < topk):
@@ -1935,7 +1992,7 @@ def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int,
     nbytes = 0
     if not (p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC):
       key = ("sparse", id(lib), q.device.index or 0, p.dtype, T, Hq, Hkv, D, s.head_dim_v, topk, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS")) + (
-        ("fp8",) if fp8 else ())
+        ("ds",) if ds else ("fp8",) if fp8 else ())
       nbytes = _cached_scratch(_MLA_SCRATCH, key, lambda: int(getattr(lib, export + "_workspace_bytes")(*args)))
     workspace = _hand_over_workspace(p, q.device, stream, nbytes)  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
@@ -1984,6 +2041,81 @@ def _mla_sparse_fp8_fwd_hip_torch_op(q, kv_cache, head_dim_v, kv_scale, indices,
 
 
 torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_fp8_fwd_hip", _mla_out_fake)
+
+
+# The sparse latent call over DeepSeek-V3.2's 656-byte FP8 rows (ffpa_attn_with_kvcache_mla_sparse_ds): the sparse op over a uint8 pool — and the store that writes
+# such rows by slot (store_latent_rows_ds), which mutates the pool
+def mla_sparse_ds_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, indices: torch.Tensor, topk_lens: "torch.Tensor | None", softmax_scale: float, *,
+                          return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0):
+  """One call of ``ffpa_attn_varlen_mla_sparse_ds_fwd`` — the sparse latent call over a ``torch.uint8`` pool of 656-byte rows (``mla_sparse_forward``'s ``ds``).
+  ``flags`` / ``plan_out`` / ``num_splits`` as there (tests force or inspect the launch)."""
+  return mla_sparse_forward(q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, return_lse=return_lse, flags=flags, plan_out=plan_out, num_splits=num_splits,
+                            ds=True)
+
+
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_sparse_ds_fwd_hip",
+  "(Tensor q, Tensor kv_cache, int head_dim_v, Tensor indices, Tensor? topk_lens, float softmax_scale, int num_splits=0) -> (Tensor o, Tensor softmax_lse)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_sparse_ds_fwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_sparse_ds_fwd_hip_torch_op(q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits=0):
+  return mla_sparse_ds_forward(q, kv_cache, int(head_dim_v), indices, topk_lens, softmax_scale, return_lse=True, num_splits=num_splits)
+
+
+torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_ds_fwd_hip", _mla_out_fake)
+
+
+def mla_ds_store(kv_cache: torch.Tensor, kv_new: torch.Tensor, slots: torch.Tensor) -> None:
+  """One launch of ``ffpa_attn_mla_ds_store``: row t of the bf16 ``kv_new [T, Hkv, 576]`` is packed (``pack_latent_rows_ds``, to the byte) into slot ``slots[t]``
+  of the ``torch.uint8`` pool ``kv_cache`` (``mla_sparse_ds_pool``'s two forms), in place.  ``slots``: int32 ``[T]`` on the device; a slot < 0 or >= the pool's
+  rows writes nothing.  Asynchronous, nothing read back to the host."""
+  name = "ffpa_attn::_mla_ds_store_hip"
+  if not kv_cache.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{kv_cache.device.type}' (the HIP kernel needs a GPU tensor)")
+  lib = load_library()
+  if kv_new.dtype != torch.bfloat16 or kv_cache.dtype != torch.uint8:
+    raise TypeError(f"{name} only supports bf16 kv over a torch.uint8 kv_cache of {MLA_DS_ROW_BYTES}-byte rows, got {kv_new.dtype}, {kv_cache.dtype}")
+  if kv_new.dim() != 3 or kv_cache.dim() not in (3, 4) or kv_cache.size(-1) != MLA_DS_ROW_BYTES or kv_new.size(1) != kv_cache.size(-2):
+    raise ValueError(f"{name}: kv must be [T, Hkv, D] and kv_cache [num_rows, Hkv, {MLA_DS_ROW_BYTES}] or [num_pages, page_size, Hkv, {MLA_DS_ROW_BYTES}] of the "
+                     "same Hkv")
+  T, Hkv, D = kv_new.shape
+  if (D, 512) not in MLA_BUILDS:
+    raise NotImplementedError(f"{name}: rows of {D} columns are not built (built: 576 = 512 quantised + 64 rotary)")
+  if slots.dtype != torch.int32 or slots.dim() != 1 or slots.numel() != T or slots.device != kv_cache.device or kv_new.device != kv_cache.device:
+    raise ValueError(f"{name}: slots must be an int32 tensor [T={T}] and kv, slots and kv_cache on one device")
+  if not _layout_ok(kv_cache, -3) or kv_cache.numel() == 0:
+    raise ValueError(f"{name}: kv_cache needs a non-empty pool with unit stride in the last dimension, strides that are multiples of 16 bytes and a 16-byte "
+                     "aligned base (it is written in place)")
+  num_rows, row_stride, head_stride = mla_sparse_ds_pool(kv_cache, name)
+  if T == 0:
+    return
+  kv_new = _rows(kv_new, 0)
+  if not slots.is_contiguous():
+    slots = slots.contiguous()
+  p = _stamped(FfpaMlaDsStoreParams)
+  p.kv_new, p.slots, p.kv_cache = kv_new.data_ptr(), slots.data_ptr(), kv_cache.data_ptr()
+  p.kv_new_stride[:] = list(kv_new.stride()[:2])
+  p.kv_cache_stride[:] = [row_stride, head_stride]
+  p.tokens, p.heads_kv, p.num_rows, p.head_dim, p.dtype = T, Hkv, num_rows, D, _DTYPE[kv_new.dtype]
+  with torch.cuda.device(kv_cache.device):
+    rc = lib.ffpa_attn_mla_ds_store(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream(kv_cache.device).cuda_stream))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_mla_ds_store")
+
+
+torch.library.define(f"{_OP_NAMESPACE}::_mla_ds_store_hip", "(Tensor(a!) kv_cache, Tensor kv_new, Tensor slots) -> ()")
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_ds_store_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_ds_store_hip_torch_op(kv_cache, kv_new, slots):
+  mla_ds_store(kv_cache, kv_new, slots)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_ds_store_hip")
+def _mla_ds_store_fake(kv_cache, kv_new, slots):
+  return None
 
 
 # The latent append of a ragged step (ffpa_attn_varlen_with_kvcache_mla(kv=)): token rows packed by cu_seqlens_q, in front of the attention launch

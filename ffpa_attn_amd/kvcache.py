@@ -24,7 +24,9 @@ packed into the rows of the tiles however many they are.  Sparse (top-k indexed)
 indexer picked for it (DeepSeek-V3.2) — is ``ffpa_attn_with_kvcache_mla_sparse`` (below): the rows are read where they lie.  An FP8 latent cache
 (``torch.float8_e4m3fn`` codes under one per-tensor scale) is served by the ``_fp8`` twins of the latent calls:
 ``ffpa_attn_with_kvcache_mla_fp8``, ``ffpa_attn_varlen_with_kvcache_mla_fp8``, ``ffpa_attn_with_kvcache_mla_sparse_fp8``,
-``ffpa_attn_with_kvcache_mla_tree_fp8`` and ``ffpa_attn_varlen_with_kvcache_mla_tree_fp8``.
+``ffpa_attn_with_kvcache_mla_tree_fp8`` and ``ffpa_attn_varlen_with_kvcache_mla_tree_fp8``.  The 656-byte FP8 rows in which DeepSeek-V3.2's cache is kept (e4m3
+codes, four float32 scales per row, bf16 rotary columns) are served by the sparse call's ``ffpa_attn_with_kvcache_mla_sparse_ds``, written by
+``store_latent_rows_ds`` and defined by ``pack_latent_rows_ds`` / ``unpack_latent_rows_ds``.
 
 Inference only: ``cache_batch_idx``, ``cache_leftpad`` and ALiBi have no kernel-side implementation here and raise
 ``NotImplementedError`` naming the option — as do ``k`` without ``v`` (or ``v`` without ``k``) and rotary tables without ``k`` / ``v`` or one without the other;
@@ -973,10 +975,11 @@ def slots_from_block_table(positions: torch.Tensor, block_table: torch.Tensor, p
   return torch.where(live, page * page_size + safe % page_size, torch.full_like(pos, -1)).to(torch.int32)
 
 
-def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=False):
-  """The argument checks of the two sparse latent calls under their own ``name``, every rule written once and in the order ``ffpa_attn_with_kvcache_mla_sparse`` has
+def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=False, ds=False):
+  """The argument checks of the sparse latent calls under their own ``name``, every rule written once and in the order ``ffpa_attn_with_kvcache_mla_sparse`` has
   always made them -> ``(T, Hq)``.  ``fp8``: the pool is ``torch.float8_e4m3fn`` (``ffpa_attn_with_kvcache_mla_sparse_fp8``) — the dtype rule is the FP8 latent
-  calls', and ``mla_sparse_pool`` holds the pool to the FP8 stride rule and counts its span in its own bytes."""
+  calls', and ``mla_sparse_pool`` holds the pool to the FP8 stride rule and counts its span in its own bytes.  ``ds``: the pool is ``torch.uint8`` rows of 656
+  bytes (``ffpa_attn_with_kvcache_mla_sparse_ds``) under a bf16 ``q`` — its last dimension is the row's bytes, and ``mla_sparse_ds_pool`` holds its geometry."""
   if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
     raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
                     "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
@@ -987,7 +990,11 @@ def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax
       raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
     if t.requires_grad and torch.is_grad_enabled():
       raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
-  if fp8:
+  if ds:
+    if q.dtype != torch.bfloat16 or kv_cache.dtype != torch.uint8:
+      raise TypeError(f"{name} only supports bf16 q over a torch.uint8 kv_cache of {_DS_ROW_BYTES}-byte rows — the rotary columns of a row are bf16 and are read "
+                      f"as they are; fp16 q is not served —, got {q.dtype}, {kv_cache.dtype}")
+  elif fp8:
     if q.dtype not in _DTYPES or kv_cache.dtype != torch.float8_e4m3fn:
       raise TypeError(f"{name} only supports fp16/bf16 q over a torch.float8_e4m3fn kv_cache — OCP e4m3 is the chip's FP8 format; float8_e4m3fnuz and the e5m2 "
                       f"formats are not served —, got {q.dtype}, {kv_cache.dtype}")
@@ -997,13 +1004,15 @@ def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax
     raise ValueError(f"{name}: q must be [T, Hq, D] (flatten a [B, Sq, Hq, D] step) and kv_cache [num_rows, Hkv, D] or [num_pages, page_size, Hkv, D]")
   T, Hq, D = q.shape
   Hkv = kv_cache.size(-2)
-  if kv_cache.size(-1) != D:
+  if ds and kv_cache.size(-1) != _DS_ROW_BYTES:
+    raise ValueError(f"{name}: the last dimension of the cache ({kv_cache.size(-1)}) must be the {_DS_ROW_BYTES} bytes of a row")
+  if not ds and kv_cache.size(-1) != D:
     raise ValueError(f"{name}: head dim of the cache ({kv_cache.size(-1)}) differs from q's ({D})")
   if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int):
     raise TypeError(f"{name}: head_dim_v must be an int, got {head_dim_v!r}")
   if D % 64 != 0 or head_dim_v <= 0 or head_dim_v % 64 != 0 or head_dim_v > D:
     raise ValueError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}): both must be multiples of 64 with 0 < head_dim_v <= D")
-  from .hip import MLA_BUILDS, mla_sparse_pool
+  from .hip import MLA_BUILDS, mla_sparse_ds_pool, mla_sparse_pool
 
   if (D, head_dim_v) not in MLA_BUILDS:
     raise NotImplementedError(f"{name}: (D, head_dim_v) = ({D}, {head_dim_v}) is not built (built: {', '.join(map(str, MLA_BUILDS))})")
@@ -1029,7 +1038,7 @@ def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax
     raise ValueError(f"{name}: topk_lens must be an int32 tensor [T={T}] on q's device")
   if kv_cache.numel() == 0:
     raise ValueError(f"{name}: kv_cache must be a non-empty pool")
-  mla_sparse_pool(kv_cache, name)  # (evenly spaced pages, the span the kernel's offsets reach, an FP8 pool's strides: ValueError, from sizes and strides)
+  (mla_sparse_ds_pool if ds else mla_sparse_pool)(kv_cache, name)  # (evenly spaced pages, the span the kernel's offsets reach, a byte pool's strides: ValueError)
   return T, Hq
 
 
@@ -1112,7 +1121,8 @@ def ffpa_attn_with_kvcache_mla_sparse_fp8(
   T]``) and the one-graph call are ``ffpa_attn_with_kvcache_mla_sparse``'s.  Two rules are the FP8 pool's own (``ValueError`` before any launch): the row and
   head strides must be multiples of 16 elements, and the rows of a latent head may span at most 2^31 BYTES — for a pool of one byte per element that is twice as
   many rows, about 3.7 M dense 576-wide rows.  No ``kv=``: the step's rows are appended by the FP8 latent calls or by the engine
-  (``quantize_latent_rows``).  Not served: per-token / per-block scales (the 656-byte row layout), FP8 ``q``, a ``kv_scale`` on the device."""
+  (``quantize_latent_rows``).  Per-block scales inside the row — the 656-byte row layout of DeepSeek-V3.2 — are ``ffpa_attn_with_kvcache_mla_sparse_ds``'s.
+  Not served: FP8 ``q``, a ``kv_scale`` on the device."""
   name = "ffpa_attn_with_kvcache_mla_sparse_fp8"
   if unsupported:
     raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no causal flag — the indexer has chosen visible keys —, no kv= append, "
@@ -1125,6 +1135,117 @@ def ffpa_attn_with_kvcache_mla_sparse_fp8(
     out = q.new_empty((0, Hq, head_dim_v))
     return (out, q.new_empty((Hq, 0), dtype=torch.float32)) if return_softmax_lse else out
   out, lse = torch.ops.ffpa_attn._mla_sparse_fp8_fwd_hip(q, kv_cache, head_dim_v, kv_scale, indices, topk_lens, float(softmax_scale), num_splits)
+  return (out, lse) if return_softmax_lse else out
+
+
+# ---- the 656-byte FP8 latent rows of DeepSeek-V3.2 (vLLM's "fp8_ds_mla", the FP8 KV layout of FlashMLA's sparse decode): the format, the store, the sparse call
+_DS_NOPE, _DS_TILE, _DS_ROPE, _DS_ROW_BYTES = 512, 128, 64, 656
+_DS_SCALE_FLOOR = 2.0 ** -100
+
+
+def pack_latent_rows_ds(kv: torch.Tensor) -> torch.Tensor:
+  """Latent rows ``kv [..., 576]`` (bf16 / fp16 / fp32) -> ``torch.uint8 [..., 656]``, the row format in which the engines keep DeepSeek-V3.2's latent cache::
+
+      bytes   0 ... 511   the 512 latent ("NoPE") columns as OCP e4m3 codes
+      bytes 512 ... 527   four little-endian float32 scales, one per 128 columns
+      bytes 528 ... 655   the 64 rotary columns as bf16, not quantised
+
+  For each 128-column tile ``x`` of the first 512 columns: ``a = amax(|float32(x)|)`` with non-finite elements counted as 0, ``s = max(a / 448, 2^-100)`` in
+  float32, ``code = rne_e4m3(clamp(float32(x) / s, -448, +448))`` — IEEE divisions; NaN stays NaN (the code keeps x's sign) and +-inf saturates, the clamp and
+  NaN rule of ``quantize_latent_rows``.  Plain torch on any device: THE DEFINITION ``store_latent_rows_ds``'s kernel implements to the byte."""
+  if not isinstance(kv, torch.Tensor) or kv.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+    raise TypeError(f"pack_latent_rows_ds: kv must be a bf16 / fp16 / fp32 tensor, got {kv.dtype if isinstance(kv, torch.Tensor) else type(kv).__name__}")
+  if kv.dim() < 1 or kv.size(-1) != _DS_NOPE + _DS_ROPE:
+    raise ValueError(f"pack_latent_rows_ds: kv must be [..., {_DS_NOPE + _DS_ROPE}], got {tuple(kv.shape)}")
+  x = kv[..., :_DS_NOPE].to(torch.float32).unflatten(-1, (_DS_NOPE // _DS_TILE, _DS_TILE))
+  a = torch.where(torch.isfinite(x), x.abs(), torch.zeros_like(x)).amax(dim=-1, keepdim=True)
+  s = (a / torch.full_like(a, _E4M3_MAX)).clamp_min(_DS_SCALE_FLOOR)  # (tensor / tensor: by a Python scalar torch multiplies by 1 / 448 on the GPU — not this division)
+  v = x / s
+  codes = torch.where(torch.isnan(x), x, v.clamp(-_E4M3_MAX, _E4M3_MAX)).to(torch.float8_e4m3fn).flatten(-2)  # (x's own NaN: the sign of NaN / s is the platform's)
+  rope = kv[..., _DS_NOPE:].to(torch.bfloat16).contiguous()
+  return torch.cat([codes.view(torch.uint8), s.squeeze(-1).contiguous().view(torch.uint8), rope.view(torch.uint8)], dim=-1)
+
+
+def unpack_latent_rows_ds(rows: torch.Tensor) -> torch.Tensor:
+  """``torch.uint8 [..., 656]`` rows of ``pack_latent_rows_ds``'s format -> bf16 ``[..., 576]``: latent column ``c`` is ``bf16_rne(float32(code[c]) *
+  scale[c // 128])`` — ONE float32 multiply, then ONE round-to-nearest-even to bf16 —, the rotary bytes are reinterpreted, not converted.  THE DEFINITION of what
+  ``ffpa_attn_with_kvcache_mla_sparse_ds`` computes on.  A scale outside ``[2^-100, 2^100]`` or not finite, in a pool somebody else packed, gives unspecified
+  values for its 128 columns and nothing else: no address depends on a scale.  The last dimension must have unit stride; rows may be strided."""
+  if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8:
+    raise TypeError(f"unpack_latent_rows_ds: rows must be a torch.uint8 tensor, got {rows.dtype if isinstance(rows, torch.Tensor) else type(rows).__name__}")
+  if rows.dim() < 1 or rows.size(-1) != _DS_ROW_BYTES:
+    raise ValueError(f"unpack_latent_rows_ds: rows must be [..., {_DS_ROW_BYTES}], got {tuple(rows.shape)}")
+  codes = rows[..., :_DS_NOPE].contiguous().view(torch.float8_e4m3fn).to(torch.float32).unflatten(-1, (_DS_NOPE // _DS_TILE, _DS_TILE))
+  s = rows[..., _DS_NOPE:_DS_NOPE + 16].contiguous().view(torch.float32).unsqueeze(-1)
+  rope = rows[..., _DS_NOPE + 16:].contiguous().view(torch.bfloat16)
+  return torch.cat([(codes * s).to(torch.bfloat16).flatten(-2), rope], dim=-1)
+
+
+def store_latent_rows_ds(kv_cache: torch.Tensor, kv: torch.Tensor, slots: torch.Tensor) -> None:
+  """Write the step's new latent rows into a pool of 656-byte rows BY SLOT, as the engines write this cache (``slot_mapping``): row ``t`` of the bf16 ``kv [T, Hkv,
+  576]`` goes, packed as ``pack_latent_rows_ds(kv[t])`` to the byte, to slot ``slots[t]`` of ``kv_cache`` — ``torch.uint8``, ``[num_rows, Hkv, 656]`` or a page
+  pool ``[num_pages, page_size, Hkv, 656]`` with evenly spaced pages, written in place.  ``slots``: int32 ``[T]`` on the device; a slot ``< 0`` (the engines'
+  padding) or ``>= num_rows`` writes nothing, and two tokens with one slot are the caller's error (one of them wins).  ONE kernel, nothing read back to the host:
+  it captures into a HIP graph in front of ``ffpa_attn_with_kvcache_mla_sparse_ds``.  ``kv`` may be strided in its token and head dimensions."""
+  name = "store_latent_rows_ds"
+  for nm, t in (("kv_cache", kv_cache), ("kv", kv), ("slots", slots)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+  if kv.dtype != torch.bfloat16 or kv_cache.dtype != torch.uint8:
+    raise TypeError(f"{name} only supports bf16 kv over a torch.uint8 kv_cache of {_DS_ROW_BYTES}-byte rows, got {kv.dtype}, {kv_cache.dtype}")
+  if kv.dim() != 3 or kv.size(-1) != _DS_NOPE + _DS_ROPE or kv_cache.dim() not in (3, 4) or kv_cache.size(-1) != _DS_ROW_BYTES or kv_cache.size(-2) != kv.size(1):
+    raise ValueError(f"{name}: kv must be [T, Hkv, {_DS_NOPE + _DS_ROPE}] and kv_cache [num_rows, Hkv, {_DS_ROW_BYTES}] or [num_pages, page_size, Hkv, "
+                     f"{_DS_ROW_BYTES}] of the same Hkv, got {tuple(kv.shape)} and {tuple(kv_cache.shape)}")
+  if slots.dtype != torch.int32 or slots.dim() != 1 or slots.numel() != kv.size(0):
+    raise ValueError(f"{name}: slots must be an int32 tensor [T={kv.size(0)}], got {slots.dtype} {tuple(slots.shape)}")
+  if kv.device != kv_cache.device or slots.device != kv_cache.device:
+    raise ValueError(f"{name}: kv_cache / kv / slots must be on one device, got {kv_cache.device}, {kv.device}, {slots.device}")
+  if kv_cache.stride(-1) != 1 or kv_cache.numel() == 0:
+    raise ValueError(f"{name}: kv_cache must be a non-empty pool with a contiguous last dimension")
+  from . import hip
+
+  hip.mla_sparse_ds_pool(kv_cache, name)
+  torch.ops.ffpa_attn._mla_ds_store_hip(kv_cache, kv, slots)
+
+
+def ffpa_attn_with_kvcache_mla_sparse_ds(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  indices: torch.Tensor,
+  *,
+  topk_lens: "torch.Tensor | None" = None,
+  softmax_scale: float = _MLA_REQUIRED,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  **unsupported,
+):
+  """``ffpa_attn_with_kvcache_mla_sparse`` over the 656-byte FP8 latent rows of DeepSeek-V3.2 — the format in which the engines that serve that model keep its
+  cache (vLLM's ``fp8_ds_mla``, the FP8 KV layout of FlashMLA's sparse decode; ``pack_latent_rows_ds`` says it byte by byte): ``kv_cache`` is ``torch.uint8``,
+  ``[num_rows, Hkv, 656]`` or a page pool ``[num_pages, page_size, Hkv, 656]`` with evenly spaced pages; any other dtype (``TypeError``) or last dimension
+  (``ValueError``) is refused.  ``q`` and the output are bf16 (fp16 ``q``: ``TypeError`` — the rotary columns of a row are bf16 and are read as they are).  The rows
+  are read where they lie: the kernel is the sparse FP8 kernel's build whose pieces are a 16-byte and a 4-byte register load at the gathered offsets, dequantised
+  — code x the scale of its 128 columns, rounded once to bf16 — on their way into LDS; no unpacked scratch pool, no gathered copy.  Nothing is folded into the
+  softmax scale: the call returns THE BITS of ``ffpa_attn_with_kvcache_mla_sparse(q, unpack_latent_rows_ds(kv_cache), ...)``.
+
+  ``indices`` / ``topk_lens`` and their safety rules (entries at and past the count are never turned into an address — by the scale's load as little as by the
+  codes' —, entries in front of it are clamped into the pool), the required ``softmax_scale``, the ``(576, 512)`` build, ``num_splits``, the returns (``out [T, Hq,
+  head_dim_v]``, fp32 ``lse [Hq, T]``) and the one-graph call are ``ffpa_attn_with_kvcache_mla_sparse``'s.  The pool's own rules (``ValueError`` before any
+  launch): slot and head strides are multiples of 16 bytes, slots at least 656 bytes apart (a padded slot stride is fine), the base 16-byte aligned, and the rows
+  of a latent head span at most 2^31 bytes — about 3.27 M contiguous rows.  No ``kv=``: the step's rows are written by slot, ``store_latent_rows_ds``.  Not
+  served: fp16 ``q``, ue8m0 / power-of-two scale variants of the row, this layout in the dense latent call and the tree call, ``-1`` holes inside an index row
+  (``compact_topk_indices``)."""
+  name = "ffpa_attn_with_kvcache_mla_sparse_ds"
+  if unsupported:
+    raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no causal flag — the indexer has chosen visible keys —, no kv= append, "
+                              "no window, soft-cap, tree mask, rotary tables, ALiBi, batch index or leftpad over the sparse latent call)")
+  T, Hq = _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, ds=True)
+  from . import hip  # noqa: F401  (registers the ffpa_attn ops)
+
+  if T == 0:
+    out = q.new_empty((0, Hq, head_dim_v))
+    return (out, q.new_empty((Hq, 0), dtype=torch.float32)) if return_softmax_lse else out
+  out, lse = torch.ops.ffpa_attn._mla_sparse_ds_fwd_hip(q, kv_cache, head_dim_v, indices, topk_lens, float(softmax_scale), num_splits)
   return (out, lse) if return_softmax_lse else out
 
 

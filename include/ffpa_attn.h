@@ -551,8 +551,9 @@ int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ff
  *         code = rne_e4m3(clamp(float32(x) * float32(1 / kv_scale), -448, +448)),   NaN stays NaN, +-inf saturates to +-448.
  *   * the plan is the latent call's with the cache priced at one byte per element (the non-temporal rule sees half the bytes).
  * The kernel name reads ffpa_fwd_m16_mla_fp8_kernel<bf16, 576, dv=512>...  FP8 pools in the tree-mask and the sparse call: ffpa_attn_varlen_mla_tree_fp8_fwd and
- * ffpa_attn_varlen_mla_sparse_fp8_fwd (below).  Not served: per-token / per-block scales (the 656-byte row layout of DeepSeek-V3.2), an FP8 q, a kv_scale that
- * lives on the device, FP8 in the two-cache (non-MLA) calls.
+ * ffpa_attn_varlen_mla_sparse_fp8_fwd (below).  Per-block scales inside the row — the 656-byte row layout of DeepSeek-V3.2 — are served by the sparse call alone:
+ * ffpa_attn_varlen_mla_sparse_ds_fwd (below).  Not served: that layout in this call and in the tree-mask call, an FP8 q, a kv_scale that lives on the device, FP8
+ * in the two-cache (non-MLA) calls.
  */
 typedef struct ffpa_mla_fp8 {
   uint32_t struct_size; /* sizeof(ffpa_mla_fp8), checked */
@@ -644,6 +645,59 @@ int ffpa_attn_varlen_mla_sparse_fp8_fwd(const ffpa_varlen_fwd_params* p, const f
 size_t ffpa_attn_varlen_mla_sparse_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8);
 int ffpa_attn_varlen_mla_sparse_fp8_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, int out[5]);
 int ffpa_attn_varlen_mla_sparse_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, char* buf, size_t n);
+
+/*
+ * THE 656-BYTE FP8 LATENT ROWS OF DEEPSEEK-V3.2 IN THE SPARSE CALL — the row format in which the engines that serve that model keep its latent cache (vLLM's
+ * "fp8_ds_mla", the FP8 KV layout of FlashMLA's sparse decode).  One row of one latent head:
+ *     bytes   0 ... 511   the 512 latent ("NoPE") columns as OCP e4m3 codes
+ *     bytes 512 ... 527   four little-endian float32 scales, one per 128 columns
+ *     bytes 528 ... 655   the 64 rotary columns as bf16, not quantised
+ * and what the kernel computes on is, to the bit, column c < 512 = bf16_rne(float32(code[c]) * scale[c / 128]) — one float32 multiply, one rounding — next to the
+ * rotary columns as they are.  A scale outside [2^-100, 2^100] or not finite gives unspecified values for its 128 columns and nothing else: no address depends on
+ * a scale.
+ *
+ * ffpa_attn_varlen_mla_sparse_ds_fwd is ffpa_attn_varlen_mla_sparse_fwd over such a pool: p->k is the BYTE pool, s->kv_stride is in bytes; there is no ffpa_mla_fp8
+ * (the scales lie in the rows) and nothing is folded into the softmax scale: the call returns the bits of ffpa_attn_varlen_mla_sparse_fwd on the unpacked pool.
+ * The checks are those of ffpa_attn_varlen_mla_sparse_fp8_fwd — s and the params, the plan, the (head_dim, head_dim_v) pair — then, in this order: p->dtype must
+ * be bf16 (FFPA_ERR_BAD_DTYPE: the rotary bytes reach the kernel's image as they are), (head_dim, head_dim_v) = (576, 512) (FFPA_ERR_BAD_HEADDIM), both strides
+ * multiples of 16 with slots at least 656 bytes apart (FFPA_ERR_BAD_STRIDE), a 16-byte aligned pool base (FFPA_ERR_MISALIGNED), and the reach of the addressing:
+ * (num_rows - 1) * kv_stride[0] + 656 <= 2^31 (about 3.27 M contiguous rows), else FFPA_ERR_BAD_SHAPE.  Entries at and past a token's count are never turned
+ * into an address — on the scale's load as little as on the codes' —, entries in front of it are clamped into the pool.  The plan is the sparse FP8 call's.  The
+ * kernel name reads ffpa_fwd_m16_mla_sparse_ds_kernel<bf16, 576, dv=512>...
+ * Not served: an fp16 q, ue8m0 / power-of-two scale variants of the row, this layout in the dense latent call and the tree-mask call, -1 holes inside an index row.
+ */
+int ffpa_attn_varlen_mla_sparse_ds_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream);
+size_t ffpa_attn_varlen_mla_sparse_ds_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s);
+int ffpa_attn_varlen_mla_sparse_ds_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]);
+int ffpa_attn_varlen_mla_sparse_ds_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n);
+
+/*
+ * THE STORE OF SUCH ROWS, BY SLOT — engines write this cache through a slot mapping, not through sequence lengths.  ONE kernel on `stream`: row t of kv_new
+ * [tokens, heads_kv, 576] (bf16, by kv_new_stride = {token, head} in elements) is packed into slot slots[t] of the pool (kv_cache_stride = {slot, head} in
+ * bytes).  For each of the four 128-column tiles x of the first 512 columns:
+ *     a = amax(|float32(x)|) with non-finite elements counted as 0;   s = max(a / 448, 2^-100) in float32;
+ *     code = rne_e4m3(clamp(float32(x) / s, -448, +448)),   NaN stays NaN (x's sign), +-inf saturates;   both divisions correctly rounded,
+ * then the four s and the rotary columns' bytes as they are.  A slot < 0 (the engines' padding) or >= num_rows writes nothing; two tokens with one slot are the
+ * caller's error (one of them wins).  Nothing is read back: the launch captures into a graph.
+ */
+typedef struct ffpa_mla_ds_store_params {
+  uint32_t struct_size;       /* sizeof(ffpa_mla_ds_store_params), checked */
+  uint32_t reserved;          /* 0, checked */
+  const void* kv_new;         /* device [tokens, heads_kv, 576] bf16, 16-byte aligned; may be NULL when tokens == 0 */
+  const int32_t* slots;       /* device [tokens] */
+  void* kv_cache;             /* the byte pool, written in place; 16-byte aligned */
+  int64_t kv_new_stride[2];   /* elements: token, head (multiples of 8) */
+  int64_t kv_cache_stride[2]; /* bytes: slot, head (multiples of 16; slots >= 656 apart) */
+  int32_t tokens;             /* >= 0 */
+  int32_t heads_kv;
+  int32_t num_rows;           /* slots in the pool */
+  int32_t head_dim;           /* 576 */
+  int32_t dtype;              /* FFPA_DTYPE_BF16 */
+  int32_t reserved2;          /* 0, checked */
+} ffpa_mla_ds_store_params;
+
+/* Launch the store on `stream` of the CURRENT device.  Asynchronous; every bad argument returns a status before any device work.  Returns an ffpa_status. */
+int ffpa_attn_mla_ds_store(const ffpa_mla_ds_store_params* p, void* stream);
 
 /*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
