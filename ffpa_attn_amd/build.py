@@ -89,6 +89,9 @@ def _units() -> list[Unit]:
   units.append(Unit("ffpa_merge_states.hip", "ffpa_merge_states.o", [], "temps_merge", None, True, True))
   # the append for a ragged step (token rows packed by cu_seqlens_q, per-token rotary positions): shares ffpa_kvcache_append_rows.h with the [B, S] append
   units.append(Unit("ffpa_kvcache_append_varlen.hip", "ffpa_kvcache_append_varlen.o", [], "temps_append_varlen", None, True, True))
+  # the plan launch of a shared-prefix (cascade) step over the MLA latent cache: group boundaries, effective prefix lengths and the two passes' tables in one
+  # small kernel (no inline asm)
+  units.append(Unit("ffpa_mla_cascade_plan.hip", "ffpa_mla_cascade_plan.o", [], "temps_mla_cascade_plan", None, True, True))
   units.append(Unit("ffpa_capi.hip", "ffpa_capi.o", [], None, None, True, False))
   units.append(Unit("ffpa_capi.hip", "ffpa_capi_test.o", ["-DFFPA_INST_SAFE=1"], None, None, False, True))
   return units

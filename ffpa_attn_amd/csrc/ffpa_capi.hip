@@ -30,6 +30,7 @@
 #include "ffpa_mla_tree.h"      // (the tree-mask build of the latent kernel)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
 #include "ffpa_merge_states.h"    // (the merge of two attention states)
+#include "ffpa_mla_cascade_plan.h"  // (the plan launch of a shared-prefix step over the MLA latent cache)
 
 namespace {
 
@@ -2263,6 +2264,72 @@ int ffpa_attn_merge_states(const ffpa_merge_states_params* p, void* stream) {
   const int64_t blocks = std::min<int64_t>((chunks + threads - 1) / threads, 8 * cus);
   const int st = ffpa::launch_merge_states(p->dtype, a, (unsigned)blocks, threads, static_cast<hipStream_t>(stream));
   if (st != 0) return fail(FFPA_ERR_LAUNCH, "merge states launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
+}
+
+// ---- the plan launch of a shared-prefix step over the MLA latent cache (include/ffpa_attn.h: ffpa_mla_cascade_plan_params)
+int ffpa_attn_mla_cascade_plan(const ffpa_mla_cascade_plan_params* p, void* stream) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_mla_cascade_plan_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_cascade_plan_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size,
+                sizeof(ffpa_mla_cascade_plan_params), p->abi_version, FFPA_ATTN_ABI_VERSION);
+  if (!p->lens || !p->block_table) return fail(FFPA_ERR_NULL_POINTER, "lens / block_table must be non-NULL");
+  if (!p->cu_q_prefix || !p->prefix_lens || !p->prefix_table || !p->suffix_table || !p->suffix_lens)
+    return fail(FFPA_ERR_NULL_POINTER, "cu_q_prefix / prefix_lens / prefix_table / suffix_table / suffix_lens must be non-NULL");
+  if (p->batch < 1 || p->pages_per_seq < 1) return fail(FFPA_ERR_BAD_SHAPE, "batch=%d / pages_per_seq=%d must be at least 1", p->batch, p->pages_per_seq);
+  if (p->groups < 1) return fail(FFPA_ERR_BAD_SHAPE, "groups=%d must be at least 1", p->groups);
+  if (p->cu_group_seqs == nullptr && p->groups != 1) return fail(FFPA_ERR_BAD_SHAPE, "groups=%d without cu_group_seqs (NULL means one group)", p->groups);
+  if (p->seqlen_q < 1 || (int64_t)p->batch * p->seqlen_q > INT32_MAX)
+    return fail(FFPA_ERR_BAD_SHAPE, "seqlen_q=%d must be at least 1 with batch * seqlen_q < 2^31", p->seqlen_q);
+  if (p->page_size <= 0 || p->page_size % 64 != 0) return fail(FFPA_ERR_BAD_SHAPE, "page_size=%d must be a positive multiple of 64", p->page_size);
+  if (p->causal != 0 && p->causal != 1) return fail(FFPA_ERR_BAD_SHAPE, "causal=%d must be 0 or 1", p->causal);
+  if (p->capacity <= 0 || (int64_t)p->capacity > (int64_t)p->pages_per_seq * p->page_size)
+    return fail(FFPA_ERR_BAD_SHAPE, "capacity=%d must lie in (0, pages_per_seq * page_size = %lld]", p->capacity, (long long)p->pages_per_seq * p->page_size);
+  if (p->shared_prefix_len == nullptr && p->shared_prefix_len_host < 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "shared_prefix_len_host=%d must not be negative", p->shared_prefix_len_host);
+  if (p->batch > 1 && p->bt_stride < p->pages_per_seq)
+    return fail(FFPA_ERR_BAD_STRIDE, "block_table row stride %lld is less than pages_per_seq=%d", (long long)p->bt_stride, p->pages_per_seq);
+  // every array as a byte range: all 4-byte aligned, no output on an input or on another output (two workgroups would race, or a read would see a store)
+  struct Range {
+    const char* name;
+    uintptr_t lo, hi;
+    bool out;
+  };
+  const auto range = [](const char* name, const void* ptr, int64_t n, bool out) {
+    return Range{name, reinterpret_cast<uintptr_t>(ptr), reinterpret_cast<uintptr_t>(ptr) + (uintptr_t)n * 4u, out};
+  };
+  const int64_t B = p->batch, G = p->groups, W = p->pages_per_seq;
+  const Range rs[] = {
+      range("cu_group_seqs", p->cu_group_seqs, p->cu_group_seqs ? G + 1 : 0, false),
+      range("shared_prefix_len", p->shared_prefix_len, p->shared_prefix_len ? G : 0, false),
+      range("lens", p->lens, B, false),
+      range("block_table", p->block_table, (B - 1) * p->bt_stride + W, false),
+      range("cu_q_prefix", p->cu_q_prefix, G + 1, true),
+      range("prefix_lens", p->prefix_lens, G, true),
+      range("prefix_table", p->prefix_table, G * W, true),
+      range("suffix_table", p->suffix_table, B * W, true),
+      range("suffix_lens", p->suffix_lens, B, true),
+  };
+  const int n = (int)(sizeof(rs) / sizeof(rs[0]));
+  for (int i = 0; i < n; ++i)
+    if (rs[i].lo & 3u) return fail(FFPA_ERR_MISALIGNED, "%s must be 4-byte aligned", rs[i].name);
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j)
+      if ((rs[i].out || rs[j].out) && rs[i].lo < rs[j].hi && rs[j].lo < rs[i].hi)
+        return fail(FFPA_ERR_BAD_SHAPE, "%s overlaps %s: the outputs must overlap neither the inputs nor one another", rs[j].name, rs[i].name);
+  int rc;
+  if ((rc = check_device()) != FFPA_OK) return rc;
+
+  ffpa::MlaCascadePlanArgs a;
+  memset(&a, 0, sizeof(a));
+  a.cu_group = p->cu_group_seqs, a.prefix = p->shared_prefix_len, a.lens = p->lens, a.table = p->block_table;
+  a.cu_q_prefix = p->cu_q_prefix, a.prefix_lens = p->prefix_lens, a.prefix_table = p->prefix_table;
+  a.suffix_table = p->suffix_table, a.suffix_lens = p->suffix_lens;
+  a.bt_stride = p->bt_stride;
+  a.B = p->batch, a.G = p->groups, a.W = p->pages_per_seq, a.page = p->page_size, a.Sq = p->seqlen_q, a.causal = p->causal;
+  a.capacity = p->capacity, a.prefix_host = p->shared_prefix_len_host;
+  const int st = ffpa::launch_mla_cascade_plan(a, static_cast<hipStream_t>(stream));
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla cascade plan launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
   return FFPA_OK;
 }
 

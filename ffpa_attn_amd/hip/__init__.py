@@ -385,6 +385,33 @@ class FfpaMergeStatesParams(ctypes.Structure):
   ]
 
 
+class FfpaMlaCascadePlanParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_mla_cascade_plan_params`` (include/ffpa_attn.h): the plan launch of a shared-prefix step over the MLA latent cache."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("abi_version", ctypes.c_uint32),
+    ("cu_group_seqs", ctypes.c_void_p),
+    ("shared_prefix_len", ctypes.c_void_p),
+    ("lens", ctypes.c_void_p),
+    ("block_table", ctypes.c_void_p),
+    ("cu_q_prefix", ctypes.c_void_p),
+    ("prefix_lens", ctypes.c_void_p),
+    ("prefix_table", ctypes.c_void_p),
+    ("suffix_table", ctypes.c_void_p),
+    ("suffix_lens", ctypes.c_void_p),
+    ("bt_stride", ctypes.c_int64),
+    ("batch", ctypes.c_int32),
+    ("groups", ctypes.c_int32),
+    ("pages_per_seq", ctypes.c_int32),
+    ("page_size", ctypes.c_int32),
+    ("seqlen_q", ctypes.c_int32),
+    ("causal", ctypes.c_int32),
+    ("capacity", ctypes.c_int32),
+    ("shared_prefix_len_host", ctypes.c_int32),
+  ]
+
+
 _lib = None
 _debug_lib = None
 _lib_lock = threading.Lock()
@@ -469,6 +496,7 @@ _BINDINGS = (
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
+  ("ffpa_attn_mla_cascade_plan", [_P(FfpaMlaCascadePlanParams), _VOID], _INT, 7),
   ("ffpa_attn_query", [_INT], _INT, 0),
   ("ffpa_attn_fwd_tile_config", [_INT, _P(_INT), _P(_INT), _P(_INT)], _INT, 0),
   ("ffpa_attn_last_error", [], _STR, 0),
@@ -2444,3 +2472,93 @@ def _merge_states_hip_fake(o_a, lse_a, o_b, lse_b):
   check_merge_states(o_a, lse_a, o_b, lse_b, "ffpa_attn::_merge_states_hip")
   T, H, D = o_a.shape
   return o_a.new_empty((T, H, D)), o_a.new_empty((H, T), dtype=torch.float32)
+
+
+# The plan launch of a shared-prefix step over the MLA latent cache (ffpa_attn_with_kvcache_mla_cascade: between the append and the two attention launches)
+def check_mla_cascade_plan(lens: torch.Tensor, block_table: torch.Tensor, cu_group_seqs: "torch.Tensor | None", shared_prefix_len: "torch.Tensor | None",
+                           shared_prefix_len_host: int, page_size: int, seqlen_q: int, capacity: int, name: str = "ffpa_attn::_mla_cascade_plan_hip") -> "tuple[int, int, int]":
+  """Host-side checks of a plan launch (types, shapes, dtypes, devices: nothing read from the device) -> ``(B, G, W)``."""
+  for nm, t in (("lens", lens), ("block_table", block_table)):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+      raise TypeError(f"{name}: {nm} must be an int32 tensor")
+  if lens.dim() != 1 or lens.numel() < 1:
+    raise ValueError(f"{name}: lens must be a 1-D int32 tensor [batch >= 1], got {tuple(lens.shape)}")
+  B = lens.numel()
+  if block_table.dim() != 2 or block_table.size(0) != B or block_table.size(1) == 0 or block_table.device != lens.device:
+    raise ValueError(f"{name}: block_table must be a 2-D int32 tensor [batch={B}, pages_per_seq >= 1] on the device of lens")
+  G = 1
+  if cu_group_seqs is not None:
+    if cu_group_seqs.dtype != torch.int32:
+      raise TypeError(f"{name}: cu_group_seqs must be int32, got {cu_group_seqs.dtype}")
+    if cu_group_seqs.dim() != 1 or cu_group_seqs.numel() < 2 or cu_group_seqs.device != lens.device:
+      raise ValueError(f"{name}: cu_group_seqs must be a 1-D int32 tensor [groups + 1] on the device of lens, got {tuple(cu_group_seqs.shape)} on {cu_group_seqs.device}")
+    G = cu_group_seqs.numel() - 1
+  if shared_prefix_len is not None:
+    if shared_prefix_len.dtype != torch.int32:
+      raise TypeError(f"{name}: a tensor shared_prefix_len must be int32, got {shared_prefix_len.dtype}")
+    if tuple(shared_prefix_len.shape) != (G,) or shared_prefix_len.device != lens.device:
+      raise ValueError(f"{name}: a tensor shared_prefix_len must be [groups={G}] on the device of lens, got {tuple(shared_prefix_len.shape)} on {shared_prefix_len.device}")
+  elif shared_prefix_len_host < 0:
+    raise ValueError(f"{name}: shared_prefix_len must be non-negative, got {shared_prefix_len_host}")
+  W = block_table.size(1)
+  if page_size <= 0 or page_size % 64 != 0:
+    raise ValueError(f"{name}: page_size ({page_size}) must be a positive multiple of 64")
+  if seqlen_q < 1 or not 0 < capacity <= W * page_size:
+    raise ValueError(f"{name}: seqlen_q ({seqlen_q}) must be at least 1 and capacity ({capacity}) in (0, pages_per_seq * page_size = {W * page_size}]")
+  return B, G, W
+
+
+def _mla_cascade_plan_outputs(lens: torch.Tensor, B: int, G: int, W: int):
+  new = lambda *shape: lens.new_empty(shape, dtype=torch.int32)
+  return new(G + 1), new(G), new(G, W), new(B, W), new(B)
+
+
+def mla_cascade_plan(lens: torch.Tensor, block_table: torch.Tensor, cu_group_seqs: "torch.Tensor | None", shared_prefix_len: "torch.Tensor | None",
+                     shared_prefix_len_host: int, page_size: int, seqlen_q: int, causal: bool, capacity: int):
+  """One launch of ``ffpa_attn_mla_cascade_plan`` -> ``(cu_q_prefix [G + 1], prefix_lens [G], prefix_table [G, W], suffix_table [B, W], suffix_lens [B])``, all
+  int32 on the device of ``lens`` (the keys every sequence holds after the step's append, not clamped): the effective prefix of every group of
+  ``cu_group_seqs`` (None: one group) — the stated one (``shared_prefix_len [G]`` on the device, or the host int) cut back to what every sequence of the group
+  holds (and, under ``causal``, to what its first query token may see) and rounded down to whole pages —, the packed queries' boundaries by group, the block-table
+  row of every group's first sequence, every sequence's row shifted left by its group's prefix pages, and the suffix lengths.  Asynchronous, nothing read back to
+  the host."""
+  name = "ffpa_attn::_mla_cascade_plan_hip"
+  B, G, W = check_mla_cascade_plan(lens, block_table, cu_group_seqs, shared_prefix_len, shared_prefix_len_host, page_size, seqlen_q, capacity, name)
+  if not lens.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{lens.device.type}' (the HIP kernel needs a GPU tensor)")
+  lib = load_library()
+  lens = lens.contiguous()
+  if block_table.stride(1) != 1 or block_table.data_ptr() % 4 != 0:
+    block_table = block_table.contiguous()
+  cu_group_seqs = cu_group_seqs.contiguous() if cu_group_seqs is not None else None
+  shared_prefix_len = shared_prefix_len.contiguous() if shared_prefix_len is not None else None
+  outs = _mla_cascade_plan_outputs(lens, B, G, W)
+  p = _stamped(FfpaMlaCascadePlanParams)
+  p.cu_group_seqs = cu_group_seqs.data_ptr() if cu_group_seqs is not None else None
+  p.shared_prefix_len = shared_prefix_len.data_ptr() if shared_prefix_len is not None else None
+  p.lens, p.block_table = lens.data_ptr(), block_table.data_ptr()
+  p.cu_q_prefix, p.prefix_lens, p.prefix_table, p.suffix_table, p.suffix_lens = (t.data_ptr() for t in outs)
+  p.bt_stride = block_table.stride(0) if B > 1 else W
+  p.batch, p.groups, p.pages_per_seq, p.page_size, p.seqlen_q, p.causal, p.capacity = B, G, W, page_size, seqlen_q, 1 if causal else 0, capacity
+  p.shared_prefix_len_host = shared_prefix_len_host if shared_prefix_len is None else 0
+  rc = _call_on_stream(lib.ffpa_attn_mla_cascade_plan, lens.device, ctypes.byref(p))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_mla_cascade_plan")
+  return outs
+
+
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_cascade_plan_hip",
+  "(Tensor lens, Tensor block_table, Tensor? cu_group_seqs, Tensor? shared_prefix_len, int shared_prefix_len_host, int page_size, int seqlen_q, int causal, "
+  "int capacity) -> (Tensor cu_q_prefix, Tensor prefix_lens, Tensor prefix_table, Tensor suffix_table, Tensor suffix_lens)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_cascade_plan_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_cascade_plan_hip_torch_op(lens, block_table, cu_group_seqs, shared_prefix_len, shared_prefix_len_host, page_size, seqlen_q, causal, capacity):
+  return mla_cascade_plan(lens, block_table, cu_group_seqs, shared_prefix_len, shared_prefix_len_host, page_size, seqlen_q, bool(causal), capacity)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_cascade_plan_hip")
+def _mla_cascade_plan_hip_fake(lens, block_table, cu_group_seqs, shared_prefix_len, shared_prefix_len_host, page_size, seqlen_q, causal, capacity):
+  B, G, W = check_mla_cascade_plan(lens, block_table, cu_group_seqs, shared_prefix_len, shared_prefix_len_host, page_size, seqlen_q, capacity)
+  return _mla_cascade_plan_outputs(lens, B, G, W)

@@ -27,6 +27,8 @@ indexer picked for it (DeepSeek-V3.2) — is ``ffpa_attn_with_kvcache_mla_sparse
 ``ffpa_attn_with_kvcache_mla_tree_fp8`` and ``ffpa_attn_varlen_with_kvcache_mla_tree_fp8``.  The 656-byte FP8 rows in which DeepSeek-V3.2's cache is kept (e4m3
 codes, four float32 scales per row, bf16 rotary columns) are served by the sparse call's ``ffpa_attn_with_kvcache_mla_sparse_ds``, written by
 ``store_latent_rows_ds`` and defined by ``pack_latent_rows_ds`` / ``unpack_latent_rows_ds``.
+A batch whose sequences share their first latent rows — groups of consecutive sequences, prefix lengths and group boundaries on the device — is
+``ffpa_attn_with_kvcache_mla_cascade`` (and its ``_fp8`` twin, at the end of this file): one plan launch, a prefix pass per group, a suffix pass and the merge.
 
 Inference only: ``cache_batch_idx``, ``cache_leftpad`` and ALiBi have no kernel-side implementation here and raise
 ``NotImplementedError`` naming the option — as do ``k`` without ``v`` (or ``v`` without ``k``) and rotary tables without ``k`` / ``v`` or one without the other;
@@ -1717,3 +1719,188 @@ def _cascade(q, k_cache, v_cache, seqused, block_table, capacity, P, scale, caus
     cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=dev)
     o_s, lse_s = hip.varlen_forward(qp, kp, vp, cu_q, cu_k, Sq, capacity - P, bool(causal), scale, seqused_k=used_suf, num_splits=num_splits)
   return _merge(o_p, lse_p, o_s, lse_s)
+
+
+# ---- shared-prefix (cascade) attention over the MLA latent cache: ffpa_attn_with_kvcache_mla_cascade / ffpa_attn_with_kvcache_mla_cascade_fp8
+# cascade=None, measured on MI355X (profiles/r26_mla_cascade.md, tools/gpu_mla_cascade_ab.py; "fit" rows: page 64, Hq 16 / 128 on one latent head, B 16 / 64 as one
+# group and B 64 as 8 groups of 8, P 2k / 8k / 32k, suffixes 128 / 2k, 1 token and 4 tokens causal).  The latent step is bound by its tiles, not by its bytes: what
+# the cascade buys is tiles FILLED — at Hq 16, one token, a 64-row tile of the plain call holds 16 live rows, and the prefix pass packs four sequences into it.  So
+# the only class that won is Hq 16 x 1 token: at B x P = 2^21 sequence-keys (B 64, P 32k: 4 shapes) and at 2^20 (B 64 x 16k, B 128 x 8k) it won replayed from a
+# graph AND launched eagerly (1.96 ... 2.53 x), in groups of 64, 8 and 4 sequences alike (4 x 16 rows fill a tile); at 2^19 (B 64 x 8k, B 16 x 32k) it won
+# replayed (1.32 ... 1.46 x) and LOST eagerly (0.60 ... 0.95 x: five launches from Python cost ~ 135 us, the plain step 110 ... 130 us), below that it lost both.
+# With 4 tokens (64 rows: the tiles are full) it lost everywhere at Hq 16 (0.56 ... 0.93 x), and at Hq 128 it lost (0.57 ... 0.96 x) except at P 32k in ONE group
+# (1.02 ... 1.22 x, both ways) — too narrow a win to build a class on: it stays plain.  The rule takes the measured winners; the "check" rows of the same profile
+# confirm it off the grid (B 32 ... 256, P 8k ... 64k, 16 ... 96 sequences per group, pages of 128, one FP8 row: 2.16 ... 2.67 x, both ways).  Everything else was
+# either measured as a loss or NOT MEASURED and stays plain under None: more than one latent head, other head counts, Sq > 1 at Hq < 16, groups of fewer than 4
+# sequences; cascade=True forces the cascade there.
+_MLA_CASCADE_HEADS_Q = 16             # r26_mla_cascade: query heads on the one latent head, one token: 16 live rows of a tile's 64
+_MLA_CASCADE_MIN_SEQ_KEYS = 1 << 20    # r26_mla_cascade: batch x shared_prefix_len; 2^19 lost eagerly, 2^20 won both
+_MLA_CASCADE_MIN_GROUP_SEQS = 4        # r26_mla_cascade: sequences per group (batch / num_groups), the smallest measured
+
+
+def mla_cascade_rule(batch: int, seqlen_q: int, heads_q: int, heads_kv: int, shared_prefix_len: int, num_groups: int = 1) -> bool:
+  """The host-side rule of ``ffpa_attn_with_kvcache_mla_cascade(cascade=None)`` for a host-int ``shared_prefix_len``: True where the cascade (plan + prefix pass +
+  suffix pass + merge) was measured faster than the plain latent launch on MI355X, replayed from a graph AND launched eagerly (profiles/r26_mla_cascade.md): one
+  latent head under 16 query heads, one token, ``batch * shared_prefix_len >= 2^20`` sequence-keys and on average 4 or more sequences per group.  Everything else
+  — measured as a loss, or not measured — is plain."""
+  if num_groups < 1 or batch <= num_groups or shared_prefix_len <= 0 or seqlen_q < 1 or heads_kv <= 0 or heads_q < heads_kv:
+    return False
+  if heads_kv != 1 or heads_q != _MLA_CASCADE_HEADS_Q or seqlen_q != 1:
+    return False
+  if batch < _MLA_CASCADE_MIN_GROUP_SEQS * num_groups:
+    return False
+  return batch * shared_prefix_len >= _MLA_CASCADE_MIN_SEQ_KEYS
+
+
+def _mla_cascade(name, fp8, kv_scale, q, kv_cache, head_dim_v, shared_prefix_len, cu_group_seqs, max_group_seqs, kv, cache_seqlens, block_table, softmax_scale, causal,
+                 num_splits, return_softmax_lse, cascade):
+  """Both cascade calls behind their names: the checks, the route (plain / cascade) and the cascade's five steps."""
+  if cascade is not None and not isinstance(cascade, bool):
+    raise TypeError(f"{name}: cascade must be True, False or None, got {cascade!r}")
+  on_device = isinstance(shared_prefix_len, torch.Tensor)
+  if not on_device:
+    if isinstance(shared_prefix_len, bool) or not isinstance(shared_prefix_len, int):
+      raise TypeError(f"{name}: shared_prefix_len must be an int or an int32 device tensor [groups], got {type(shared_prefix_len).__name__}")
+    if shared_prefix_len < 0:
+      raise ValueError(f"{name}: shared_prefix_len must be non-negative, got {shared_prefix_len}")
+  capacity, lens = _mla_check(name, q, kv_cache, head_dim_v, kv, cache_seqlens, block_table, softmax_scale, num_splits, fp8=fp8)
+  if block_table is None:
+    raise ValueError(f"{name}: block_table is required — a contiguous latent cache has no shared pages (every sequence owns its slab); the plain call serves it")
+  B, Sq, Hq, _ = q.shape
+  G = 1
+  if cu_group_seqs is not None:
+    if not isinstance(cu_group_seqs, torch.Tensor) or cu_group_seqs.dtype != torch.int32:
+      raise TypeError(f"{name}: cu_group_seqs must be an int32 tensor [groups + 1], got {getattr(cu_group_seqs, 'dtype', type(cu_group_seqs).__name__)}")
+    if cu_group_seqs.dim() != 1 or cu_group_seqs.numel() < 2 or cu_group_seqs.device != q.device:
+      raise ValueError(f"{name}: cu_group_seqs must be a 1-D int32 tensor [groups + 1] on q's device, got {tuple(cu_group_seqs.shape)} on {cu_group_seqs.device}")
+    G = cu_group_seqs.numel() - 1
+  if on_device:
+    if shared_prefix_len.dtype != torch.int32:
+      raise TypeError(f"{name}: a tensor shared_prefix_len must be int32, got {shared_prefix_len.dtype}")
+    if tuple(shared_prefix_len.shape) != (G,) or shared_prefix_len.device != q.device:
+      raise ValueError(f"{name}: a tensor shared_prefix_len must be [groups={G}] on q's device, got {tuple(shared_prefix_len.shape)} on {shared_prefix_len.device}")
+  if max_group_seqs is None:
+    max_group_seqs = B
+  elif isinstance(max_group_seqs, bool) or not isinstance(max_group_seqs, int) or max_group_seqs < 0 or (B > 0 and max_group_seqs < 1):
+    raise ValueError(f"{name}: max_group_seqs must be a host int >= 1 that bounds the sequences of every group, got {max_group_seqs!r}")
+  op = "fp8" if fp8 else "mla"
+  use = cascade
+  if use is None:
+    use = True if on_device else mla_cascade_rule(B, Sq, Hq, kv_cache.size(2), shared_prefix_len, G)
+  if not use or B == 0 or Sq == 0:
+    return _mla_step(name, op, kv_scale, q, kv_cache, head_dim_v, kv, lens, block_table, capacity, softmax_scale, causal, num_splits, return_softmax_lse)
+  # 1. the step's latent rows into the pool, on the full table: the ragged append with Snew rows per sequence returns the post-append lengths
+  if kv is not None and kv.size(1) > 0:
+    Snew = kv.size(1)
+    cu_new = torch.arange(0, (B + 1) * Snew, Snew, dtype=torch.int32, device=q.device)
+    rows = kv.reshape(B * Snew, kv.size(2), kv.size(3))
+    if fp8:
+      lens = torch.ops.ffpa_attn._mla_fp8_append_varlen_hip(kv_cache, rows, kv_scale, cu_new, lens, block_table)
+    else:
+      lens = torch.ops.ffpa_attn._mla_append_varlen_hip(kv_cache, rows, cu_new, lens, block_table)
+  # 2. the plan: effective prefixes, the groups' query boundaries, the prefix rows and the shifted suffix rows, in one launch
+  cu_pre, len_pre, table_pre, table_suf, len_suf = torch.ops.ffpa_attn._mla_cascade_plan_hip(
+    lens, block_table, cu_group_seqs, shared_prefix_len if on_device else None, 0 if on_device else shared_prefix_len, kv_cache.size(1), Sq, 1 if causal else 0, capacity)
+  qp = q.reshape(B * Sq, Hq, q.size(3))
+  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
+  scale = float(softmax_scale)
+  # 3. the prefix pass (every group one packed sequence, not causal) and 4. the suffix pass (the caller's causal: bottom-right aligned, so exact)
+  if fp8:
+    o_p, lse_p = torch.ops.ffpa_attn._mla_fp8_fwd_hip(qp, kv_cache, head_dim_v, kv_scale, cu_pre, len_pre, table_pre, None, None, max_group_seqs * Sq, capacity, scale, 0,
+                                                      num_splits)
+    o_s, lse_s = torch.ops.ffpa_attn._mla_fp8_fwd_hip(qp, kv_cache, head_dim_v, kv_scale, cu_q, len_suf, table_suf, None, None, Sq, capacity, scale,
+                                                      1 if causal else 0, num_splits)
+  else:
+    o_p, lse_p = torch.ops.ffpa_attn._mla_fwd_hip(qp, kv_cache, head_dim_v, cu_pre, len_pre, table_pre, None, None, max_group_seqs * Sq, capacity, scale, 0, num_splits)
+    o_s, lse_s = torch.ops.ffpa_attn._mla_fwd_hip(qp, kv_cache, head_dim_v, cu_q, len_suf, table_suf, None, None, Sq, capacity, scale, 1 if causal else 0, num_splits)
+  # 5. the merge of the two states
+  o, lse = _merge(o_p, lse_p, o_s, lse_s)
+  out = o.view(B, Sq, Hq, head_dim_v)
+  if not return_softmax_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+
+
+def ffpa_attn_with_kvcache_mla_cascade(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  *,
+  shared_prefix_len: "int | torch.Tensor",
+  cu_group_seqs: torch.Tensor | None = None,
+  max_group_seqs: int | None = None,
+  kv: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor",
+  block_table: torch.Tensor,
+  softmax_scale: float,
+  causal: bool = False,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  cascade: "bool | None" = None,
+):
+  """``ffpa_attn_with_kvcache_mla`` for a batch whose sequences share their first keys — a shared system prompt under prefix caching, parallel sampling and
+  best-of-n, RL rollouts that draw many samples per prompt — as CASCADE attention over the latent cache: the shared latent rows are read once per GROUP of
+  sequences instead of once per sequence, and the prefix pass fills its 64-row tiles with the rows of several sequences at once (at ``Hq = 16``, one token, a
+  tile of the plain call holds 16 live rows).  Shapes, return values, the required ``softmax_scale``, the ``(576, 512)`` build, ``cache_seqlens``, ``causal``,
+  ``num_splits``, the ``kv=`` append, inference only and every argument check are ``ffpa_attn_with_kvcache_mla``'s.  ``block_table`` is REQUIRED: a contiguous
+  latent cache has no shared pages (``ValueError``).
+
+  GROUPS.  ``cu_group_seqs`` (int32 ``[G + 1]``, on the device; non-decreasing from 0 to B; not checked) cuts the batch into G groups of consecutive sequences;
+  None is one group of all B; an empty group is allowed.  The shared keys of group g are read through the ``block_table`` row of its FIRST sequence only.
+  ``max_group_seqs`` (a host int, default B: always safe) bounds the sequences of any one group; it sizes the prefix pass (``max_seqlen_q = max_group_seqs *
+  Sq``) and is a contract like ``max_seqlen_q`` of the ragged calls — not checked; the latent launch's compact grid takes over when most of the full grid would be
+  idle.
+
+  PREFIX LENGTHS.  ``shared_prefix_len``: a non-negative host int (one length for every group) or an int32 device tensor ``[G]``.  Nothing of it is read back to
+  the host; the effective prefix is made on the device::
+
+      P_g = page_size * floor(clamp(min(shared_prefix_len[g], min over b in g of (clamp(len_b, 0, capacity) - (Sq - 1 if causal else 0))), 0, capacity) / page_size)
+
+  with ``len_b`` the length after the append; an empty group has ``P_g = 0``.  A length that is no page multiple is rounded down, one that exceeds what some
+  sequence of the group holds (or what its first causal token may see) is cut back: the call is exact for ANY lengths.  THE ONE UNCHECKED CONTRACT: pages
+  ``[0, P_g / page_size)`` really are the same keys for every sequence of group g.  An append into shared pages is the caller's race.
+
+  STEPS of the cascade, nothing read back to the host, so the whole call captures into one HIP graph and a replay follows ``cache_seqlens``, ``block_table``,
+  ``cu_group_seqs`` and a tensor ``shared_prefix_len`` written in place: (1) with ``kv``, the ragged latent append on the full table; (2) ONE plan launch
+  (``ffpa_attn::_mla_cascade_plan_hip``): the effective prefixes, the queries' boundaries by group, the prefix rows and every row shifted left by its group's
+  prefix pages; (3) the PREFIX pass: the latent kernel on the packed q as G sequences against ``P_g`` keys, not causal; (4) the SUFFIX pass: the latent kernel on
+  the shifted table with lengths ``len_b - P_g`` under the caller's ``causal`` (bottom-right aligned: exact); (5) the merge of the two (O, LSE) states
+  (``ffpa_merge_attn_states``).  The cascade differs from the plain launch by rounding only; with ``P_g = 0`` it returns the plain call's bits.
+
+  ``cascade``: False = exactly ``ffpa_attn_with_kvcache_mla`` (the same launch, the same bits, the same append); True = the cascade; None = ``mla_cascade_rule``
+  when ``shared_prefix_len`` is a host int — and the CASCADE when it is a device tensor: that cannot be priced without a host read, and the caller who built
+  device-side groups has asked for it.  ``B * Sq == 0`` returns the plain call's empty results.  NOT served: ragged ``q``, the tree-mask and sparse calls,
+  contiguous caches."""
+  return _mla_cascade("ffpa_attn_with_kvcache_mla_cascade", False, None, q, kv_cache, head_dim_v, shared_prefix_len, cu_group_seqs, max_group_seqs, kv, cache_seqlens,
+                      block_table, softmax_scale, causal, num_splits, return_softmax_lse, cascade)
+
+
+def ffpa_attn_with_kvcache_mla_cascade_fp8(
+  q: torch.Tensor,
+  kv_cache: torch.Tensor,
+  head_dim_v: int,
+  *,
+  shared_prefix_len: "int | torch.Tensor",
+  kv_scale: float = 1.0,
+  cu_group_seqs: torch.Tensor | None = None,
+  max_group_seqs: int | None = None,
+  kv: torch.Tensor | None = None,
+  cache_seqlens: "int | torch.Tensor",
+  block_table: torch.Tensor,
+  softmax_scale: float,
+  causal: bool = False,
+  num_splits: int = 0,
+  return_softmax_lse: bool = False,
+  cascade: "bool | None" = None,
+):
+  """``ffpa_attn_with_kvcache_mla_cascade`` over an FP8 latent cache: ``kv_cache`` is ``torch.float8_e4m3fn`` under the per-tensor ``kv_scale`` (a host float,
+  finite and positive), ``q``, ``kv`` and the output are bf16 or fp16, ``kv`` is quantised by the append as ``quantize_latent_rows(kv, kv_scale)`` — everything
+  ``ffpa_attn_with_kvcache_mla_fp8`` says of the pool.  Groups, prefix lengths, the steps, ``cascade`` and the contract are the 16-bit cascade's; both passes run
+  the FP8 latent kernel, so with a power-of-two ``kv_scale`` the call returns the bits of ``ffpa_attn_with_kvcache_mla_cascade(q, kv_cache.to(q.dtype), ...,
+  softmax_scale=softmax_scale * kv_scale) * kv_scale``.  ``cascade=False`` is exactly ``ffpa_attn_with_kvcache_mla_fp8``."""
+  name = "ffpa_attn_with_kvcache_mla_cascade_fp8"
+  from . import hip  # (registers the ffpa_attn ops)
+
+  kv_scale = hip.check_kv_scale(kv_scale, name)
+  return _mla_cascade(name, True, kv_scale, q, kv_cache, head_dim_v, shared_prefix_len, cu_group_seqs, max_group_seqs, kv, cache_seqlens, block_table, softmax_scale,
+                      causal, num_splits, return_softmax_lse, cascade)

@@ -856,6 +856,51 @@ typedef struct ffpa_merge_states_params {
  * work.  Returns an ffpa_status. */
 int ffpa_attn_merge_states(const ffpa_merge_states_params* p, void* stream);
 
+/*
+ * PLAN OF A SHARED-PREFIX (CASCADE) STEP OVER THE MLA LATENT CACHE — the one launch between the append and the two attention launches of
+ * ffpa_attn_with_kvcache_mla_cascade.  The batch of `batch` sequences (seqlen_q query tokens each) is cut into `groups` groups of consecutive sequences by
+ * cu_group_seqs [groups + 1] (non-decreasing, from 0 to batch; an empty group is allowed; NULL: groups must be 1 and the group holds every sequence).  The
+ * sequences of a group share their first keys: pages [0, P_g / page_size) of their block-table rows are the same pages, read through the row of the group's
+ * FIRST sequence.  With len'_b = clamp(lens[b], 0, capacity) the launch makes, on the device,
+ *     P_g = page_size * floor(clamp(min(stated_g, min over b in g of (len'_b - (seqlen_q - 1 if causal else 0))), 0, capacity) / page_size)    (empty group: 0)
+ * (stated_g = shared_prefix_len[g], or shared_prefix_len_host for every group when that pointer is NULL) and stores
+ *     cu_q_prefix [groups + 1]  = cu_group_seqs * seqlen_q        — the packed queries as `groups` sequences, for the prefix pass
+ *     prefix_lens [groups]      = P_g
+ *     prefix_table [groups, pages_per_seq] : row g = block_table[first sequence of g] (an empty group: some in-range row)
+ *     suffix_table [batch, pages_per_seq]  : [b, j] = block_table[b, min(j + P_g / page_size, pages_per_seq - 1)]
+ *     suffix_lens [batch]       = len'_b - P_g
+ * Everything is int32 and 4-byte aligned; the outputs are dense and must overlap neither the inputs nor one another (FFPA_ERR_BAD_SHAPE).  No atomics, no
+ * workspace.  A cu_group_seqs that breaks its contract gives unspecified values, never an access outside the arrays.
+ */
+typedef struct ffpa_mla_cascade_plan_params {
+  uint32_t struct_size; /* sizeof(ffpa_mla_cascade_plan_params), checked */
+  uint32_t abi_version; /* FFPA_ATTN_ABI_VERSION                          */
+
+  const int32_t* cu_group_seqs;     /* [groups + 1], or NULL (groups == 1) */
+  const int32_t* shared_prefix_len; /* [groups] on the device, or NULL: shared_prefix_len_host */
+  const int32_t* lens;              /* [batch]: the keys every sequence holds (after the step's append), not clamped */
+  const int32_t* block_table;       /* [batch, pages_per_seq] by bt_stride, column stride 1 */
+  int32_t* cu_q_prefix;             /* out [groups + 1] */
+  int32_t* prefix_lens;             /* out [groups] */
+  int32_t* prefix_table;            /* out [groups, pages_per_seq] */
+  int32_t* suffix_table;            /* out [batch, pages_per_seq] */
+  int32_t* suffix_lens;             /* out [batch] */
+
+  int64_t bt_stride;                /* elements between rows of block_table, >= pages_per_seq when batch > 1 */
+  int32_t batch;                    /* >= 1 */
+  int32_t groups;                   /* >= 1 */
+  int32_t pages_per_seq;            /* >= 1 */
+  int32_t page_size;                /* a positive multiple of 64 */
+  int32_t seqlen_q;                 /* >= 1, batch * seqlen_q < 2^31 */
+  int32_t causal;                   /* 0 / 1 */
+  int32_t capacity;                 /* keys a sequence can hold: in (0, pages_per_seq * page_size] */
+  int32_t shared_prefix_len_host;   /* >= 0; read when shared_prefix_len == NULL */
+} ffpa_mla_cascade_plan_params;
+
+/* Launch the plan on `stream` of the CURRENT device.  Asynchronous: no allocation, no synchronisation; every bad argument returns a status before any device
+ * work.  Returns an ffpa_status. */
+int ffpa_attn_mla_cascade_plan(const ffpa_mla_cascade_plan_params* p, void* stream);
+
 /* Capability / build queries.  Replaces the module attributes
  * CUDA_FWD_AVAILABLE, F16_ACC_AVAILABLE, ... (csrc/cuffpa/ffpa_api.cc:283-305). */
 enum ffpa_query {
