@@ -487,3 +487,146 @@ def test_the_uniform_call_under_torch_compile_fullgraph(hip):
   assert torch.equal(s_compiled, want)
   ref, vstat = _ref(t, True, 0.37, lens=used, pool=_pool_of(t, want))
   R.check((compiled[0].double() / 2).to(torch.float16), compiled[1], ref, v=vstat, dtype="fp16", name="torch.compile")
+
+
+# ----------------------------------------------------------------------------- 8. FP8 pools past 2^32 bytes
+# tests/test_kvcache_mla_contract_gpu.py section f, for the builds that count the pool in BYTES through strides in two-byte units (k_ps = k_page_stride * 2u): the
+# FP8 latent call with and without kv=, the tree call and the cascade.  The pools are ~ 4.3 GB of the NaN code; float64 and the 16-bit twin work on the USED pages
+# alone, gathered into a small pool under a remapped table (the twin's pool would be 8.6 GB, a float64 copy 34 GB).
+HIGH_LENS = [700, 1500, 1027]
+
+
+def _high_pool(page):
+  """``[num_pages, page, 1, 576]`` uint8, every byte the NaN code, whose used pages — the highest ids, shuffled — all START past byte 2^32; sequence b holds
+  ``HIGH_LENS[b]`` rows of codes.  -> the storage, the table, the table of the cascade (every sequence reads its first page through sequence 0's id)."""
+  from ffpa_attn_amd import quantize_latent_rows
+
+  B, pps = len(HIGH_LENS), -(-(max(HIGH_LENS) + 2) // page) + 1
+  n_pages = -(-(2 ** 32) // (page * D)) + B * pps
+  storage = torch.full((n_pages, page, 1, D), 0xFF, dtype=torch.uint8, device="cuda")
+  ids = (n_pages - 1 - torch.randperm(B * pps, generator=torch.Generator().manual_seed(page))).to(torch.int32).view(B, pps)
+  assert int(ids.min()) * storage.stride(0) >= 2 ** 32, "the used pages must start past byte 2^32"
+  g = torch.Generator(device="cuda").manual_seed(page)
+  for b, n in enumerate(HIGH_LENS):
+    j = torch.arange(n)
+    storage[ids[b].long()[j // page].cuda(), (j % page).cuda()] = quantize_latent_rows(torch.randn((n, 1, D), device="cuda", generator=g), 1.0).view(torch.uint8)
+  shared = ids.clone()
+  shared[:, 0] = ids[0, 0]
+  return storage, ids, shared
+
+
+def _gathered(storage, ids):
+  """The pages ``ids`` names, gathered into a small pool, and ``ids`` remapped to it."""
+  flat = ids.flatten().long()
+  return storage[flat.cuda()].contiguous(), torch.arange(flat.numel(), dtype=torch.int32, device="cuda").view(ids.shape)
+
+
+def _float64_on(small, table, q, lens, kv_scale, causal=True, mask=None):
+  import tree_ref
+
+  deq = small.view(F8).double() * kv_scale
+  if mask is not None:
+    o, lse, pmax, p2sum = tree_ref.attend_tree(q, deq, deq, lens, table, mask, SCALE)
+  else:
+    o, lse, pmax, p2sum = R.attend(q, deq, deq, lens, table, causal, SCALE)
+  return (o[..., :DV].contiguous(), lse, pmax, p2sum), R.visible_values(deq[..., :DV], lens, table)
+
+
+@pytest.mark.parametrize("page", [64, 256])
+def test_fp8_pool_pages_past_2_32_bytes(hip, page):
+  """The FP8 latent call (non-temporal and plain, unsplit and three forced ranges), the tree call and the cascade against float64 at kv_scale 0.37; the 16-bit
+  call's bits at 0.25 on the dequantised used pages; then ``kv=``: the used pages hold ``quantize_latent_rows`` of the new rows, every other byte its 0xFF."""
+  import tree_ref
+  from ffpa_attn_amd import (ffpa_attn_with_kvcache_mla, ffpa_attn_with_kvcache_mla_cascade_fp8, ffpa_attn_with_kvcache_mla_tree_fp8, quantize_latent_rows)
+
+  storage, ids, shared = _high_pool(page)
+  low, B, sq, lens = int(ids.min()), len(HIGH_LENS), 2, HIGH_LENS
+  g = torch.Generator(device="cuda").manual_seed(11)
+  q = torch.randn((B, sq, 16, D), device="cuda", generator=g).bfloat16()
+  t = dict(q=q, pool=storage.view(F8), table=ids.cuda(), lens=torch.tensor(lens, dtype=torch.int32, device="cuda"), dtype="bf16")
+  small, remap = _gathered(storage, ids)
+  ref, vstat = _float64_on(small, remap, q, lens, 0.37)
+  for flag in (hip.FLAG_KV_STREAM, hip.FLAG_NO_KV_STREAM):
+    for ns in (1, 3):
+      out, lse, plan = _fp8(hip, t, True, kv_scale=0.37, num_splits=ns, flags=flag | (hip.FLAG_FORCE_SPLITS if ns > 1 else 0))
+      assert plan["splits"] == ns and ((", NT>" in plan["kernel"]) == (flag == hip.FLAG_KV_STREAM)), plan
+      print(f"[mla fp8 > 2^32 bytes] page {page} {R.check(out, lse, ref, v=vstat, dtype='bf16', name=f'page {page} past 2^32 bytes {plan}'):.3f} {plan}")
+  # the 16-bit call's bits at a power-of-two scale, on the used pages dequantised
+  flags = hip.FLAG_FORCE_SPLITS | hip.FLAG_NO_KV_STREAM
+  out, lse, plan = _fp8(hip, t, True, kv_scale=0.25, num_splits=3, flags=flags)
+  with _launches(hip, flags) as plans:
+    want, want_lse = ffpa_attn_with_kvcache_mla(q, small.view(F8).to(torch.bfloat16), DV, cache_seqlens=t["lens"], block_table=remap, softmax_scale=SCALE * 0.25,
+                                                causal=True, num_splits=3, return_softmax_lse=True)
+  assert plans[0]["splits"] == plan["splits"] == 3 and plans[0]["kernel"] == plan["kernel"].replace("_mla_fp8_kernel", "_mla_kernel"), (plan, plans)
+  assert _same_bits(lse, want_lse) and _same_bits(out, want * 0.25)
+  # the tree call
+  mask = tree_ref.tree_mask_from_parents([-1, 0]).cuda()
+  with _launches(hip) as plans:
+    out, lse = ffpa_attn_with_kvcache_mla_tree_fp8(q, t["pool"], DV, kv_scale=0.37, tree_mask=mask, cache_seqlens=t["lens"], block_table=t["table"], softmax_scale=SCALE,
+                                                   return_softmax_lse=True)
+  assert len(plans) == 1 and plans[0]["kernel"].startswith("ffpa_fwd_m16_mla_tree_fp8_kernel<bf16"), plans
+  tref, tstat = _float64_on(small, remap, q, lens, 0.37, mask=mask)
+  print(f"[mla tree fp8 > 2^32 bytes] page {page} {R.check(out, lse, tref, v=tstat, dtype='bf16', name=f'tree, page {page} past 2^32 bytes'):.3f}")
+  # the cascade: every sequence reads its first page through sequence 0's row — the prefix pass and the shifted table rows of the suffix pass
+  with _launches(hip) as plans:
+    out, lse = ffpa_attn_with_kvcache_mla_cascade_fp8(q, t["pool"], DV, shared_prefix_len=page, kv_scale=0.37, cache_seqlens=t["lens"], block_table=shared.cuda(),
+                                                      softmax_scale=SCALE, causal=True, return_softmax_lse=True, cascade=True)
+  assert len(plans) == 2 and all(p["kernel"].startswith("ffpa_fwd_m16_mla_fp8_kernel<bf16") for p in plans), plans
+  csmall, cremap = _gathered(storage, shared)
+  cref, cstat = _float64_on(csmall, cremap, q, lens, 0.37)
+  print(f"[mla cascade fp8 > 2^32 bytes] page {page} {R.check(out, lse, cref, v=cstat, dtype='bf16', name=f'cascade, page {page} past 2^32 bytes'):.3f}")
+  # kv=: two rows per sequence
+  kv = torch.randn((B, sq, 1, D), device="cuda", generator=g).bfloat16()
+  want = storage.clone()
+  codes = quantize_latent_rows(kv, 0.37).view(torch.uint8)
+  for b, n in enumerate(lens):
+    for i in range(sq):
+      want[int(ids[b, (n + i) // page]), (n + i) % page] = codes[b, i]
+  out, lse, plan = _fp8(hip, t, True, kv_scale=0.37, kv=kv)
+  assert torch.equal(storage, want) and (storage[:low] == 0xFF).all() and int((want != 0xFF).any(dim=-1).sum()) == sum(lens) + B * sq
+  used = [n + sq for n in lens]
+  small, remap = _gathered(want, ids)
+  ref, vstat = _float64_on(small, remap, q, used, 0.37)
+  print(f"[mla fp8 append > 2^32 bytes] page {page} {R.check(out, lse, ref, v=vstat, dtype='bf16', name=f'append, page {page} past 2^32 bytes {plan}'):.3f}")
+  del storage, want, t
+  torch.cuda.empty_cache()
+
+
+def test_fp8_contiguous_cache_whose_last_slabs_start_past_2_32_bytes(hip):
+  """A contiguous FP8 cache [913, 8192, 1, 576] (4.3 GB) in which only the last two slabs hold keys: the FP8 call and the tree call, then ``kv=`` — every sequence
+  appends, so the NaN slabs receive rows 0 and 1 and nothing else."""
+  import tree_ref
+  from ffpa_attn_amd import ffpa_attn_with_kvcache_mla_tree_fp8, quantize_latent_rows
+
+  B, cap, sq = 913, 8192, 2
+  g = torch.Generator(device="cuda").manual_seed(12)
+  storage = torch.full((B, cap, 1, D), 0xFF, dtype=torch.uint8, device="cuda")
+  lens = [0] * (B - 2) + [1500, 700]
+  assert (B - 2) * storage.stride(0) >= 2 ** 32, "the last two slabs must start past byte 2^32"
+  for b in (B - 2, B - 1):
+    storage[b, :lens[b]] = quantize_latent_rows(torch.randn((lens[b], 1, D), device="cuda", generator=g), 1.0).view(torch.uint8)
+  q = torch.randn((B, sq, 16, D), device="cuda", generator=g).bfloat16()
+  t = dict(q=q, pool=storage.view(F8), table=None, lens=torch.tensor(lens, dtype=torch.int32, device="cuda"), dtype="bf16")
+  ref, vstat = _float64_on(storage[B - 2:], None, q[B - 2:], lens[B - 2:], 0.37)
+  for ns, flag in ((1, hip.FLAG_KV_STREAM), (3, hip.FLAG_NO_KV_STREAM | hip.FLAG_FORCE_SPLITS)):
+    out, lse, plan = _fp8(hip, t, True, kv_scale=0.37, num_splits=ns, flags=flag)
+    assert plan["splits"] == ns and (out[:B - 2] == 0).all() and torch.isneginf(lse[:B - 2]).all(), plan
+    print(f"[mla fp8 contiguous > 2^32 bytes] {R.check(out[B - 2:], lse[B - 2:], ref, v=vstat, dtype='bf16', name=f'contiguous past 2^32 bytes {plan}'):.3f} {plan}")
+  mask = tree_ref.tree_mask_from_parents([-1, 0]).cuda()
+  out, lse = ffpa_attn_with_kvcache_mla_tree_fp8(q, t["pool"], DV, kv_scale=0.37, tree_mask=mask, cache_seqlens=t["lens"], softmax_scale=SCALE, return_softmax_lse=True)
+  tref, tstat = _float64_on(storage[B - 2:], None, q[B - 2:], lens[B - 2:], 0.37, mask=mask)
+  assert (out[:B - 2] == 0).all() and torch.isneginf(lse[:B - 2]).all()
+  print(f"[mla tree fp8 contiguous > 2^32 bytes] {R.check(out[B - 2:], lse[B - 2:], tref, v=tstat, dtype='bf16', name='tree, contiguous past 2^32 bytes'):.3f}")
+  kv = torch.randn((B, sq, 1, D), device="cuda", generator=g).bfloat16()
+  want = storage.clone()
+  codes = quantize_latent_rows(kv, 0.37).view(torch.uint8)
+  for b in range(B):
+    want[b, lens[b]:lens[b] + sq] = codes[b]
+  out, lse, plan = _fp8(hip, t, True, kv_scale=0.37, kv=kv)
+  assert torch.equal(storage, want) and (storage[:B - 2, sq:] == 0xFF).all() and not (storage[:B - 2, :sq] == 0xFF).all(dim=-1).any()
+  head, hstat = _float64_on(want[:B - 2, :64], None, q[:B - 2], [sq] * (B - 2), 0.37)  # (the first rows of the slabs that held nothing: the two new rows)
+  tail, tstat = _float64_on(want[B - 2:], None, q[B - 2:], [n + sq for n in lens[B - 2:]], 0.37)
+  print(f"[mla fp8 append contiguous > 2^32 bytes] {R.check(out[:B - 2], lse[:B - 2], head, v=hstat, dtype='bf16', name='append into the empty slabs'):.3f} "
+        f"{R.check(out[B - 2:], lse[B - 2:], tail, v=tstat, dtype='bf16', name='append into the last two slabs'):.3f}")
+  del storage, want, t
+  torch.cuda.empty_cache()
