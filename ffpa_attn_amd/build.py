@@ -38,6 +38,8 @@ SAFE_HEAD_DIMS = {64, 128, 320, 512, 640, 1024}
 VARLEN_HEAD_DIMS = [d for d in HEAD_DIMS if d >= 128]
 # (head dim, value width) pairs the MLA latent-cache kernel is built for (FFPA_FOR_EACH_MLA_BUILD, csrc/ffpa_mla.h)
 MLA_BUILDS = [(576, 512)]
+# the variants of that kernel, by the stem of their row in FFPA_FOR_EACH_MLA_VARIANT (csrc/ffpa_mla.h), in its order: the link order
+MLA_VARIANTS = ["mla", "mla_sparse", "mla_tree", "mla_fp8", "mla_sparse_fp8", "mla_tree_fp8", "mla_sparse_ds"]
 
 ARCH = "gfx950"
 CXXFLAGS = [
@@ -67,21 +69,11 @@ def _units() -> list[Unit]:
   # the packed-sequence kernel and its paged-KV twin: a TU of their own per head dim of the 16x16x32 build
   for kind in ("varlen", "paged"):
     units += [Unit(f"ffpa_{kind}_inst.hip", f"ffpa_{kind}_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d in VARLEN_HEAD_DIMS]
-  # the MLA latent-cache kernels (and their one-cache append): one TU per (head dim, value width) pair of MLA_BUILDS — adding a pair is one entry there and one
-  # line in FFPA_FOR_EACH_MLA_BUILD (csrc/ffpa_mla.h); the assembly lands next to the head dim's other kernels, where the ISA rules read it
-  units += [Unit("ffpa_mla_inst.hip", f"ffpa_mla_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
-  # the sparse (top-k indexed) build of the latent kernel: the same text with the gather hook on, one TU per pair of MLA_BUILDS next to the dense one's
-  units += [Unit("ffpa_mla_sparse_inst.hip", f"ffpa_mla_sparse_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
-  # the tree-mask build of the latent kernel: the same text with the tree hook on as well, one TU per pair of MLA_BUILDS next to the dense and the sparse one's
-  units += [Unit("ffpa_mla_tree_inst.hip", f"ffpa_mla_tree_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
-  # the FP8 (OCP e4m3) build of the latent kernel and its quantising appends: the same text with the FP8 hook on, one TU per pair of MLA_BUILDS
-  units += [Unit("ffpa_mla_fp8_inst.hip", f"ffpa_mla_fp8_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
-  # the FP8 builds of the sparse and of the tree-mask latent kernel: the same text with the gather resp. the tree hook on next to the FP8 hook, one TU each per pair
-  units += [Unit("ffpa_mla_sparse_fp8_inst.hip", f"ffpa_mla_sparse_fp8_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
-  units += [Unit("ffpa_mla_tree_fp8_inst.hip", f"ffpa_mla_tree_fp8_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
-  # the sparse latent kernel over the 656-byte FP8 rows of DeepSeek-V3.2 (the gather, the FP8 and the row-format hook on; bf16 only), one TU per pair, and the small
-  # kernel that writes such rows by slot (no inline asm: its assembly lands where the attention ISA rules do not read)
-  units += [Unit("ffpa_mla_sparse_ds_inst.hip", f"ffpa_mla_sparse_ds_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
+  # the MLA latent-cache kernels: one TU per variant (MLA_VARIANTS; ffpa_mla_inst.hip and ffpa_mla_fp8_inst.hip carry the appends too) and (head dim, value width)
+  # pair of MLA_BUILDS; the assembly lands next to the head dim's other kernels, where the ISA rules read it.  Behind them the small kernel that writes 656-byte
+  # rows by slot (no inline asm: its assembly lands where the attention ISA rules do not read)
+  for stem in MLA_VARIANTS:
+    units += [Unit(f"ffpa_{stem}_inst.hip", f"ffpa_{stem}_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
   units.append(Unit("ffpa_mla_ds_store.hip", "ffpa_mla_ds_store.o", [], "temps_mla_store", None, True, True))
   # the KV-cache append + rotary launch (every dtype / rotary form) and the merge of two attention states (the cascade's last launch): one small TU each, no
   # inline asm — their assembly lands in directories the attention ISA rules do not read

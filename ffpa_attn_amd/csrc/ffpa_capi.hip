@@ -21,13 +21,9 @@
 #include "ffpa_varlen_merge.h"   // (stage 2 of a KV-split packed-sequence launch)
 #include "ffpa_launch.h"
 #include "ffpa_paged.h"         // (the paged-KV twin of the packed-sequence kernel)
-#include "ffpa_mla.h"           // (the MLA latent-cache kernels and their append)
-#include "ffpa_mla_fp8.h"       // (the FP8 build of the latent kernel and its quantising appends)
-#include "ffpa_mla_sparse_fp8.h"  // (the FP8 build of the sparse latent kernel)
-#include "ffpa_mla_sparse_ds.h"   // (the sparse latent kernel over the 656-byte FP8 rows of DeepSeek-V3.2, and the store that writes them)
-#include "ffpa_mla_tree_fp8.h"    // (the FP8 build of the tree-mask latent kernel)
-#include "ffpa_mla_sparse.h"    // (the sparse — top-k indexed — build of the latent kernel)
-#include "ffpa_mla_tree.h"      // (the tree-mask build of the latent kernel)
+#include "ffpa_mla.h"           // (the MLA latent-cache kernels — the list of their variants, every variant's launcher — and the 16-bit appends)
+#include "ffpa_mla_fp8.h"       // (the e4m3 variants' fourth argument struct and the quantising appends)
+#include "ffpa_mla_sparse_ds.h"   // (the 656-byte FP8 rows of DeepSeek-V3.2: the row format, and the store that writes them)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
 #include "ffpa_merge_states.h"    // (the merge of two attention states)
 #include "ffpa_mla_cascade_plan.h"  // (the plan launch of a shared-prefix step over the MLA latent cache)
@@ -1173,23 +1169,19 @@ const ffpa_window* softcap_window(const ffpa_window* w) {
   return w != nullptr ? w : &kNone;
 }
 
-// The kernel builds of the latent-cache calls: one row per (head dim, value width) pair with its three launchers — the latent call's (ffpa_mla_inst.hip), the
-// sparse (top-k indexed) call's (ffpa_mla_sparse_inst.hip) and the tree-mask call's (ffpa_mla_tree_inst.hip) — and the FP8 latent call's (ffpa_mla_fp8_inst.hip), the
-// FP8 sparse call's (ffpa_mla_sparse_fp8_inst.hip) and the FP8 tree-mask call's (ffpa_mla_tree_fp8_inst.hip); last the sparse call's over 656-byte FP8 rows
-// (ffpa_mla_sparse_ds_inst.hip), which takes the latent call's argument structs.
-typedef int (*mla_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, const ffpa::MlaArgs&, hipStream_t);
-typedef int (*mla_fp8_fn)(int, int, const ffpa::FwdArgs&, const ffpa::VarlenArgs&, const ffpa::PagedArgs&, const ffpa::MlaFp8Args&, hipStream_t);
+// The kernel builds of the latent-cache calls: one row per (head dim, value width) pair with the launcher of every variant of FFPA_FOR_EACH_MLA_VARIANT
+// (ffpa_mla.h), indexed by MlaVariantId.
+using ffpa::MlaVariant;
 struct MlaBuild {
   int d, dv;
-  mla_fn latent, sparse, tree;
-  mla_fp8_fn fp8, sparse_fp8, tree_fp8;
-  mla_fn sparse_ds;
+  ffpa::mla_launch_fn launch[ffpa::kMlaVariantCount];
 };
 const MlaBuild kMlaBuilds[] = {
-#define FFPA_ROW(D, DV) {D, DV, &ffpa::launch_mla_paged_d##D, &ffpa::launch_mla_sparse_d##D, &ffpa::launch_mla_tree_d##D, &ffpa::launch_mla_fp8_paged_d##D, \
-                         &ffpa::launch_mla_sparse_fp8_d##D, &ffpa::launch_mla_tree_fp8_d##D, &ffpa::launch_mla_sparse_ds_d##D},
+#define FFPA_FN(stem, tree, gather, pool, refresh, D) &ffpa::launch_##stem##_d##D,
+#define FFPA_ROW(D, DV) {D, DV, {FFPA_FOR_EACH_MLA_VARIANT(FFPA_FN, D)}},
     FFPA_FOR_EACH_MLA_BUILD(FFPA_ROW)
 #undef FFPA_ROW
+#undef FFPA_FN
 };
 
 // The latent-cache call's own argument (ffpa_mla), checked behind the plan (and the pool) and before anything touches the device.
@@ -1303,16 +1295,10 @@ enum class Family {
   kTree,     // ffpa_attn_varlen_tree_fwd: tree; kv optional (NULL: contiguous caches) — the causal launch's plan and tile walk, the *_tree_kernel builds
   kWindow,   // ffpa_attn_varlen_window_fwd: win; kv optional — the window's own plan, the *_window_kernel builds
   kSoftcap,  // ffpa_attn_varlen_softcap_fwd: softcap; win optional (NULL: (-1, -1)), kv optional — a window launch with capped scores, the *_softcap_kernel builds
-  kMla,      // ffpa_attn_varlen_mla_fwd: kv, mla — k is the latent pool and serves as v too (p->v is not read); its own plan and kernel, the append in front
-  kMlaTree,  // ffpa_attn_varlen_mla_tree_fwd: kv, mla, tree — the latent launch under the causal flag, the tree build of its kernel
-  kMlaFp8,   // ffpa_attn_varlen_mla_fp8_fwd: kv, mla, fp8 — the latent call over a pool of e4m3 codes: its plan on the FP8 bytes, the FP8 build of its kernel
-  kSparse,   // ffpa_attn_varlen_mla_sparse_fwd: sparse — a latent launch without a page pool: the index list stands where the block table stood
-  kMlaTreeFp8,  // ffpa_attn_varlen_mla_tree_fp8_fwd: kv, mla, tree, fp8 — kMlaTree over a pool of e4m3 codes: kMlaFp8's plan and append, the tree + FP8 build
-  kSparseFp8,   // ffpa_attn_varlen_mla_sparse_fp8_fwd: sparse, fp8 — kSparse over a pool of e4m3 codes: its plan on the FP8 bytes, the gather + FP8 build
-  kSparseDs,    // ffpa_attn_varlen_mla_sparse_ds_fwd: sparse — kSparse over a byte pool of 656-byte FP8 rows: kSparseFp8's plan, the gather + FP8 + row-format build
+  kLatent,   // the seven ffpa_attn_varlen_mla*_fwd calls: ONE pool — k is the latent pool and serves as v too (p->v is not read) —, every group packed into rows.
+             // WHICH of them is VarlenCall::variant, a row of ffpa_mla.h's list: its traits say which structs the call takes (tree: tree; gather: sparse, else kv +
+             // mla — with the append in front —; an e4m3 pool: fp8) and plan_latent reads nothing else of it
 };
-bool is_tree(Family f) { return f == Family::kTree || f == Family::kMlaTree || f == Family::kMlaTreeFp8; }
-bool is_sparse(Family f) { return f == Family::kSparse || f == Family::kSparseFp8 || f == Family::kSparseDs; }
 bool is_window(Family f) { return f == Family::kWindow || f == Family::kSoftcap; }
 
 struct VarlenCall {
@@ -1325,7 +1311,10 @@ struct VarlenCall {
   const ffpa_mla* mla;
   const ffpa_mla_sparse* sparse;
   const ffpa_mla_fp8* fp8;
+  const MlaVariant* variant;  // kLatent: the call's row of ffpa::kMlaVariants
 };
+bool is_tree(const VarlenCall& c) { return c.family == Family::kTree || (c.variant != nullptr && c.variant->tree); }
+bool is_sparse(const VarlenCall& c) { return c.variant != nullptr && c.variant->gather; }
 typedef const ffpa_varlen_fwd_params* ParamsPtr;
 VarlenCall make_call(Family family, ParamsPtr p, const ffpa_paged_kv* kv) {
   VarlenCall c = {};
@@ -1349,40 +1338,19 @@ VarlenCall softcap_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_window*
   c.win = w, c.softcap = softcap;
   return c;
 }
-VarlenCall mla_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m) {
-  VarlenCall c = make_call(Family::kMla, p, kv);
-  c.mla = m;
-  return c;
-}
-VarlenCall mla_tree_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree) {
-  VarlenCall c = make_call(Family::kMlaTree, p, kv);
-  c.mla = m, c.tree = tree;
-  return c;
-}
-VarlenCall mla_fp8_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8) {
-  VarlenCall c = make_call(Family::kMlaFp8, p, kv);
-  c.mla = m, c.fp8 = f8;
-  return c;
-}
-VarlenCall sparse_call(ParamsPtr p, const ffpa_mla_sparse* s) {
-  VarlenCall c = make_call(Family::kSparse, p, nullptr);
-  c.sparse = s;
-  return c;
-}
-VarlenCall mla_tree_fp8_call(ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, const ffpa_mla_fp8* f8) {
-  VarlenCall c = make_call(Family::kMlaTreeFp8, p, kv);
+// A latent call, by how its variant finds the keys — through a page table (kv, mla; tree and fp8 where the variant takes them) or through the gather's list
+// (sparse; fp8 likewise).  The structs a variant does not take stay NULL.
+VarlenCall latent_call(ffpa::MlaVariantId id, ParamsPtr p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree = nullptr,
+                       const ffpa_mla_fp8* f8 = nullptr) {
+  VarlenCall c = make_call(Family::kLatent, p, kv);
   c.mla = m, c.tree = tree, c.fp8 = f8;
+  c.variant = &ffpa::kMlaVariants[id];
   return c;
 }
-VarlenCall sparse_fp8_call(ParamsPtr p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8) {
-  VarlenCall c = make_call(Family::kSparseFp8, p, nullptr);
+VarlenCall gather_call(ffpa::MlaVariantId id, ParamsPtr p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8 = nullptr) {
+  VarlenCall c = make_call(Family::kLatent, p, nullptr);
   c.sparse = s, c.fp8 = f8;
-  return c;
-}
-
-VarlenCall sparse_ds_call(ParamsPtr p, const ffpa_mla_sparse* s) {
-  VarlenCall c = make_call(Family::kSparseDs, p, nullptr);
-  c.sparse = s;
+  c.variant = &ffpa::kMlaVariants[id];
   return c;
 }
 
@@ -1394,10 +1362,9 @@ struct CallPlan {
   int win_causal, win_right, win_span;  // a window launch: it runs under the causal flag (right >= 0: `right` rides in the causal limit); VarlenArgs::win_right / win_span
   const ffpa_mla* mla;              // a latent launch: the caller's ffpa_mla or — the sparse call — `own_mla`; NULL: a launch over a K and a V cache
   ffpa_mla own_mla;
-  mla_fn launch_mla;                // ... and the build of the latent kernel it launches
-  const ffpa_mla_fp8* fp8;          // the FP8 latent launch: its scale ...
-  mla_fp8_fn launch_mla_fp8;        // ... and its build (launch_mla is NULL then)
-  bool byte_pool;                   // a latent launch without ffpa_mla_fp8 over a pool counted in bytes (656-byte rows): the kernel takes its strides in units of two
+  ffpa::mla_launch_fn launch_mla;   // ... and the build of the variant's kernel it launches
+  const ffpa_mla_fp8* fp8;          // a latent launch over an e4m3 pool: its scale
+  bool byte_pool;                   // a latent launch over a pool counted in bytes (e4m3 codes, 656-byte rows): the kernel takes its strides in units of two
 };
 
 // The window call's plan is the packed call's, PRICED AT WHAT THE WINDOW LEAVES.  A row tile of R token rows (all max_seqlen_q tokens under GQA row packing, else
@@ -1443,13 +1410,57 @@ void price_sparse(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, Cal
   cp->mla = &cp->own_mla;
 }
 
+// The seven latent calls are ONE order of checks, each step taken where the variant's traits ask for it (tests/golden/capi_varlen_calls.json pins the order, form
+// by form).  Tree and gather both price a copy of the params: no variant has both.
+#define FFPA_ROW(stem, tree, gather, ...) static_assert(!(tree && gather), "plan_latent prices ONE copy of the params");
+FFPA_FOR_EACH_MLA_VARIANT(FFPA_ROW, )
+#undef FFPA_ROW
+int plan_latent(const VarlenCall& c, CallPlan* cp) {
+  const MlaVariant& v = *c.variant;
+  const bool e4m3 = v.pool == FFPA_MLA_POOL_E4M3, ds = v.pool == FFPA_MLA_POOL_DS;
+  const int esz = v.pool == FFPA_MLA_POOL_16BIT ? 2 : 1;  // bytes per element of the pool: what the plan prices a key at, what the gather's span counts
+  const ffpa_varlen_fwd_params* p = c.p;
+  const MlaBuild* build = nullptr;
+  int rc;
+  // 1. an e4m3 pool: its own struct, in front of everything else of the call
+  if (e4m3 && (rc = check_mla_fp8(c.fp8)) != FFPA_OK) return rc;
+  // 2. the gather: its struct and the index list, then the params as the latent launch reads them — and an ffpa_mla of the call's own
+  if (v.gather) {
+    if ((rc = check_sparse(p, c.sparse)) != FFPA_OK) return rc;
+    price_sparse(p, c.sparse, cp);
+  }
+  // 3. the tree: the latent call UNDER THE CAUSAL FLAG, whatever p->causal says (the tree launch walks the causal launch's tiles)
+  if (v.tree && p != nullptr && p->struct_size == sizeof(ffpa_varlen_fwd_params)) {  // (anything else: varlen_plan refuses it by name)
+    cp->priced = *p;
+    cp->priced.causal = 1;
+    cp->p = &cp->priced;
+  }
+  p = cp->p;
+  const ffpa_mla* mla = v.gather ? cp->mla : c.mla;
+  // 4. - 7. the plan, with a key priced at the pool's bytes; the page pool; the latent struct and the (head dim, value width) pair; the mask
+  if ((rc = varlen_plan(p, &cp->pl, true, true, esz)) != FFPA_OK) return rc;
+  if (!v.gather && (rc = check_paged(p, c.kv)) != FFPA_OK) return rc;
+  if ((rc = check_mla(p, mla, &build)) != FFPA_OK) return rc;
+  if (v.tree && (rc = check_tree(p, c.tree)) != FFPA_OK) return rc;
+  // 8. the gathered pool's geometry, 9. the stride rule of a pool of one-byte elements
+  if (v.gather && (rc = ds ? check_sparse_ds_pool(p, c.sparse) : check_sparse_pool(p, c.sparse, esz)) != FFPA_OK) return rc;
+  if (e4m3 && (rc = v.gather ? check_fp8_strides(c.sparse->kv_stride[0], c.sparse->kv_stride[1], 0)
+                             : check_fp8_strides(p->k_stride[0], p->k_stride[1], c.kv->k_page_stride)) != FFPA_OK)
+    return rc;
+  cp->mla = mla;
+  cp->fp8 = e4m3 ? c.fp8 : nullptr;
+  cp->launch_mla = build->launch[c.variant - ffpa::kMlaVariants];
+  cp->byte_pool = esz == 1;
+  return FFPA_OK;
+}
+
 // EVERY check of a call that precedes the device, family by family and in the family's order — this is the one place where that order is written down — and the
 // plan the launch and the queries read.  The words it is written in: varlen_plan (validates the params it is given and plans them; `paged`: 64-key tiles where the
-// packed kernel takes 128; `mla`: every group packed into rows), check_paged, check_tree, check_window, check_softcap, check_mla, check_sparse / check_sparse_pool.
+// packed kernel takes 128; `mla`: every group packed into rows), check_paged, check_tree, check_window, check_softcap and — plan_latent — check_mla, check_mla_fp8,
+// check_sparse / check_sparse_pool.
 int plan_call(const VarlenCall& c, CallPlan* cp) {
   const ffpa_varlen_fwd_params* p = c.p;
   VarlenPlan* pl = &cp->pl;
-  const MlaBuild* build = nullptr;
   const bool paged = c.kv != nullptr;
   int rc;
   cp->p = p;
@@ -1457,7 +1468,6 @@ int plan_call(const VarlenCall& c, CallPlan* cp) {
   cp->mla = nullptr;
   cp->launch_mla = nullptr;
   cp->fp8 = nullptr;
-  cp->launch_mla_fp8 = nullptr;
   cp->byte_pool = false;
   switch (c.family) {
     case Family::kPacked:
@@ -1479,77 +1489,23 @@ int plan_call(const VarlenCall& c, CallPlan* cp) {
       price_window(p, w, *pl, cp);
       return varlen_plan(cp->p, pl, paged);
     }
-    case Family::kMlaTree:  // the latent call UNDER THE CAUSAL FLAG, whatever p->causal says (the tree launch walks the causal launch's tiles), then the mask
-      if (p != nullptr && p->struct_size == sizeof(ffpa_varlen_fwd_params)) {  // (anything else: varlen_plan refuses it by name)
-        cp->priced = *p;
-        cp->priced.causal = 1;
-        cp->p = p = &cp->priced;
-      }
-      [[fallthrough]];
-    case Family::kMla:
-      if ((rc = varlen_plan(p, pl, true, true)) != FFPA_OK) return rc;
-      if ((rc = check_paged(p, c.kv)) != FFPA_OK) return rc;
-      if ((rc = check_mla(p, c.mla, &build)) != FFPA_OK) return rc;
-      if (c.family == Family::kMlaTree && (rc = check_tree(p, c.tree)) != FFPA_OK) return rc;
-      cp->mla = c.mla;
-      cp->launch_mla = c.family == Family::kMlaTree ? build->tree : build->latent;
-      return FFPA_OK;
-    case Family::kMlaFp8:  // its own struct first, then the latent call's checks with the cache priced at one byte per element, then the pool's geometry
-      if ((rc = check_mla_fp8(c.fp8)) != FFPA_OK) return rc;
-      if ((rc = varlen_plan(p, pl, true, true, 1)) != FFPA_OK) return rc;
-      if ((rc = check_paged(p, c.kv)) != FFPA_OK) return rc;
-      if ((rc = check_mla(p, c.mla, &build)) != FFPA_OK) return rc;
-      if ((rc = check_fp8_strides(p->k_stride[0], p->k_stride[1], c.kv->k_page_stride)) != FFPA_OK) return rc;
-      cp->mla = c.mla;
-      cp->fp8 = c.fp8;
-      cp->launch_mla_fp8 = build->fp8;
-      return FFPA_OK;
-    case Family::kSparse:
-      if ((rc = check_sparse(p, c.sparse)) != FFPA_OK) return rc;
-      price_sparse(p, c.sparse, cp);
-      if ((rc = varlen_plan(cp->p, pl, true, true)) != FFPA_OK) return rc;
-      if ((rc = check_mla(cp->p, cp->mla, &build)) != FFPA_OK) return rc;
-      if ((rc = check_sparse_pool(p, c.sparse)) != FFPA_OK) return rc;
-      cp->launch_mla = build->sparse;
-      return FFPA_OK;
-    case Family::kMlaTreeFp8:  // kMlaFp8's order under kMlaTree's causal flag, the mask where kMlaTree checks it: behind the latent struct, in front of the pool's geometry
-      if ((rc = check_mla_fp8(c.fp8)) != FFPA_OK) return rc;
-      if (p != nullptr && p->struct_size == sizeof(ffpa_varlen_fwd_params)) {  // (anything else: varlen_plan refuses it by name)
-        cp->priced = *p;
-        cp->priced.causal = 1;
-        cp->p = p = &cp->priced;
-      }
-      if ((rc = varlen_plan(p, pl, true, true, 1)) != FFPA_OK) return rc;
-      if ((rc = check_paged(p, c.kv)) != FFPA_OK) return rc;
-      if ((rc = check_mla(p, c.mla, &build)) != FFPA_OK) return rc;
-      if ((rc = check_tree(p, c.tree)) != FFPA_OK) return rc;
-      if ((rc = check_fp8_strides(p->k_stride[0], p->k_stride[1], c.kv->k_page_stride)) != FFPA_OK) return rc;
-      cp->mla = c.mla;
-      cp->fp8 = c.fp8;
-      cp->launch_mla_fp8 = build->tree_fp8;
-      return FFPA_OK;
-    case Family::kSparseFp8:  // kSparse's order with the FP8 struct in front and the stride rule behind; the plan and the span count one byte per element
-      if ((rc = check_mla_fp8(c.fp8)) != FFPA_OK) return rc;
-      if ((rc = check_sparse(p, c.sparse)) != FFPA_OK) return rc;
-      price_sparse(p, c.sparse, cp);
-      if ((rc = varlen_plan(cp->p, pl, true, true, 1)) != FFPA_OK) return rc;
-      if ((rc = check_mla(cp->p, cp->mla, &build)) != FFPA_OK) return rc;
-      if ((rc = check_sparse_pool(p, c.sparse, 1)) != FFPA_OK) return rc;
-      if ((rc = check_fp8_strides(c.sparse->kv_stride[0], c.sparse->kv_stride[1], 0)) != FFPA_OK) return rc;
-      cp->fp8 = c.fp8;
-      cp->launch_mla_fp8 = build->sparse_fp8;
-      return FFPA_OK;
-    case Family::kSparseDs:  // kSparseFp8's order without the FP8 struct — the scales lie in the rows —, its plan, then the row format's own rules
-      if ((rc = check_sparse(p, c.sparse)) != FFPA_OK) return rc;
-      price_sparse(p, c.sparse, cp);
-      if ((rc = varlen_plan(cp->p, pl, true, true, 1)) != FFPA_OK) return rc;
-      if ((rc = check_mla(cp->p, cp->mla, &build)) != FFPA_OK) return rc;
-      if ((rc = check_sparse_ds_pool(p, c.sparse)) != FFPA_OK) return rc;
-      cp->launch_mla = build->sparse_ds;
-      cp->byte_pool = true;
-      return FFPA_OK;
+    case Family::kLatent:
+      return plan_latent(c, cp);
   }
   return fail(FFPA_ERR_UNSUPPORTED, "unknown call family %d", (int)c.family);
+}
+
+// What every latent append takes of its pool — the 16-bit and the quantising one, of a [B, S] and of a ragged step —: the caller adds the new rows' strides
+// (s_new) and, for a [B, S] step, Snew.  `stride`: elements between two rows / heads of the pool.
+ffpa::MlaAppendArgs mla_append_args(const void* kv_new, void* cache, const int* seqlens, int* used, const int64_t stride[2], const ffpa_paged_kv* kv, int B, int Hkv, int D) {
+  ffpa::MlaAppendArgs a;
+  memset(&a, 0, sizeof(a));
+  a.kv_new = kv_new, a.cache = cache;
+  a.seqlens = seqlens, a.used = used, a.table = kv->block_table;
+  a.s_row = stride[0], a.s_head = stride[1], a.s_page = kv->k_page_stride, a.bt_stride = kv->bt_stride;
+  a.B = B, a.Hkv = Hkv, a.D = D;
+  a.cap = kv->pages_per_row * kv->page_size, a.page_size = kv->page_size, a.num_pages = kv->num_pages;
+  return a;
 }
 
 // Plan the call, then launch the plan: the checks every family shares (in front of the device), the argument blocks, the append in front of a latent launch, the
@@ -1562,7 +1518,7 @@ int varlen_launch(const VarlenCall& c, void* stream) {
   const VarlenPlan& pl = cp.pl;
   const ffpa_paged_kv* kv = c.kv;
   const ffpa_mla* mla = cp.mla;
-  const ffpa_mla_sparse* sparse = is_sparse(c.family) ? c.sparse : nullptr;
+  const ffpa_mla_sparse* sparse = is_sparse(c) ? c.sparse : nullptr;
   const bool latent = mla != nullptr;                   // k is the one cache: it serves as v too, p->v is not read
   const bool paged = kv != nullptr || sparse != nullptr;  // the keys are found through a table: cu_seqlens_kv is not read
   if (!p->q || !p->k || (!latent && !p->v) || !p->o) return fail(FFPA_ERR_NULL_POINTER, "q/k/v/o must be non-NULL");
@@ -1641,7 +1597,7 @@ int varlen_launch(const VarlenCall& c, void* stream) {
     if (p->max_seqlen_q == 1) a.causal = 0;  // (a single token sees every key of its sequence; more tokens: the kernel sets causal_row_mod per sequence)
     va.head_chunk = 1;  // (the rows of a tile ARE the group: KV heads share nothing)
   }
-  if (is_tree(c.family)) {
+  if (is_tree(c)) {
     // the causal launch's walk with causal_offset = Nkv_i - ntok_i (the kernel, per sequence): the last token's limit is the last key, so every tile is walked and
     // the KV ranges share out all of them; one token per sequence keeps the flag here — its word may hide its own key
     a.causal = 1;
@@ -1678,7 +1634,7 @@ int varlen_launch(const VarlenCall& c, void* stream) {
   if (paged) {
     ffpa::PagedArgs pa;
     if (sparse != nullptr) {
-      // a token's "block table" is its index row, its "pages" are single rows of the pool (ffpa_mla_sparse.h)
+      // a token's "block table" is its index row, its "pages" are single rows of the pool (the gather: ffpa_mla_variant.inc)
       memset(&pa, 0, sizeof(pa));
       pa.table = sparse->indices;
       pa.bt_stride = sparse->indices_stride;
@@ -1695,46 +1651,24 @@ int varlen_launch(const VarlenCall& c, void* stream) {
       pa.tiles_per_page = kv->page_size / pl.bc;
       pa.num_pages = kv->num_pages;
     }
-    if (cp.fp8 != nullptr) {
-      // the FP8 latent launch: the quantising append in front (the pool's strides in its elements: bytes), then the kernel — whose text doubles every cache
-      // stride — with the strides in units of two bytes (check_fp8_strides: exact)
+    if (latent) {
       st = 0;
       if (mla->seqlen_new > 0) {
+        // the step's latent rows first, ONE store per element (there is one cache; an e4m3 pool: quantised on their way in), and the lengths the attention launch
+        // behind it reads
         ffpa::MlaFp8AppendArgs fa;
         memset(&fa, 0, sizeof(fa));
-        ffpa::MlaAppendArgs& ap = fa.a;
-        ap.kv_new = mla->kv_new, ap.cache = const_cast<void*>(p->k);
-        ap.seqlens = mla->cache_seqlens, ap.used = const_cast<int*>(p->seqused_kv), ap.table = kv->block_table;
-        for (int i = 0; i < 3; ++i) ap.s_new[i] = mla->kv_new_stride[i];
-        ap.s_row = p->k_stride[0], ap.s_head = p->k_stride[1], ap.s_page = kv->k_page_stride, ap.bt_stride = kv->bt_stride;
-        ap.B = p->batch, ap.Snew = mla->seqlen_new, ap.Hkv = p->heads_kv, ap.D = p->head_dim;
-        ap.cap = pa.cap, ap.page_size = kv->page_size, ap.num_pages = kv->num_pages;
-        fa.inv = 1.f / cp.fp8->kv_scale;
-        st = ffpa::launch_mla_fp8_append(p->dtype, fa, static_cast<hipStream_t>(stream));
+        fa.a = mla_append_args(mla->kv_new, const_cast<void*>(p->k), mla->cache_seqlens, const_cast<int*>(p->seqused_kv), p->k_stride, kv, p->batch, p->heads_kv, p->head_dim);
+        for (int i = 0; i < 3; ++i) fa.a.s_new[i] = mla->kv_new_stride[i];
+        fa.a.Snew = mla->seqlen_new;
+        if (cp.fp8 != nullptr) fa.inv = 1.f / cp.fp8->kv_scale;
+        st = cp.fp8 != nullptr ? ffpa::launch_mla_fp8_append(p->dtype, fa, static_cast<hipStream_t>(stream)) : ffpa::launch_mla_append(fa.a, static_cast<hipStream_t>(stream));
       }
-      a.sk[1] /= 2, a.sk[2] /= 2, a.sv[1] /= 2, a.sv[2] /= 2;
-      pa.k_page_stride /= 2, pa.v_page_stride /= 2;
+      // a pool counted in bytes: the kernel's text doubles every cache stride, so it takes them in units of two bytes (multiples of 16: exact)
+      if (cp.byte_pool) a.sk[1] /= 2, a.sk[2] /= 2, a.sv[1] /= 2, a.sv[2] /= 2, pa.k_page_stride /= 2, pa.v_page_stride /= 2;
       ffpa::MlaFp8Args ma;
       ma.dv = mla->head_dim_v;
-      ma.kv_scale = cp.fp8->kv_scale;
-      if (st == 0) st = cp.launch_mla_fp8(p->dtype, pl.nt, a, va, pa, ma, static_cast<hipStream_t>(stream));
-    } else if (latent) {
-      st = 0;
-      if (cp.byte_pool) a.sk[1] /= 2, a.sk[2] /= 2, a.sv[1] /= 2, a.sv[2] /= 2;  // (strides in bytes, multiples of 16: the kernel's text doubles them)
-      if (mla->seqlen_new > 0) {
-        // the step's latent rows first, ONE store per element (there is one cache), and the lengths the attention launch behind it reads
-        ffpa::MlaAppendArgs ap;
-        memset(&ap, 0, sizeof(ap));
-        ap.kv_new = mla->kv_new, ap.cache = const_cast<void*>(p->k);
-        ap.seqlens = mla->cache_seqlens, ap.used = const_cast<int*>(p->seqused_kv), ap.table = kv->block_table;
-        for (int i = 0; i < 3; ++i) ap.s_new[i] = mla->kv_new_stride[i];
-        ap.s_row = p->k_stride[0], ap.s_head = p->k_stride[1], ap.s_page = kv->k_page_stride, ap.bt_stride = kv->bt_stride;
-        ap.B = p->batch, ap.Snew = mla->seqlen_new, ap.Hkv = p->heads_kv, ap.D = p->head_dim;
-        ap.cap = pa.cap, ap.page_size = kv->page_size, ap.num_pages = kv->num_pages;
-        st = ffpa::launch_mla_append(ap, static_cast<hipStream_t>(stream));
-      }
-      ffpa::MlaArgs ma;
-      ma.dv = mla->head_dim_v;
+      ma.kv_scale = cp.fp8 != nullptr ? cp.fp8->kv_scale : 1.f;  // (read by the kernels over an e4m3 pool alone)
       if (st == 0) st = cp.launch_mla(p->dtype, pl.nt, a, va, pa, ma, static_cast<hipStream_t>(stream));
     } else {
       st = pl.ve->paged(p->dtype, pl.nt, a, va, pa, static_cast<hipStream_t>(stream));
@@ -1789,19 +1723,12 @@ int call_kernel(const VarlenCall& c, char* buf, size_t n) {
   const char* merge = pl.splits > 1 ? " + ffpa_varlen_merge_kernel" : "";
   if (cp.mla != nullptr) {
     // (a latent call's name is formatted from the caller's params; the sparse call — a uniform batch — has never named the compact grid)
-    const char* kind = c.family == Family::kSparse       ? "_sparse"
-                       : c.family == Family::kMlaTree    ? "_tree"
-                       : c.family == Family::kMlaFp8     ? "_fp8"
-                       : c.family == Family::kSparseFp8  ? "_sparse_fp8"
-                       : c.family == Family::kSparseDs   ? "_sparse_ds"
-                       : c.family == Family::kMlaTreeFp8 ? "_tree_fp8"
-                                                         : "";
-    snprintf(buf, n, "ffpa_fwd_m16_mla%s_kernel<%s, %d, dv=%d%s>%s%s%s", kind, c.p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", c.p->head_dim, cp.mla->head_dim_v, nt,
+    snprintf(buf, n, "ffpa_fwd_m16_%s_kernel<%s, %d, dv=%d%s>%s%s%s", c.variant->stem, c.p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", c.p->head_dim, cp.mla->head_dim_v, nt,
              pl.pack ? (pl.nqt > 1 ? " (heads packed into rows, chunked)" : " (heads packed into rows)") : "",
-             pl.compact > 0 && !is_sparse(c.family) ? " (compact grid)" : "", merge);
+             pl.compact > 0 && !is_sparse(c) ? " (compact grid)" : "", merge);
   } else {
     // (a window / soft-cap call's name is formatted from the priced params)
-    const char* kind = is_tree(c.family) ? "_tree" : c.family == Family::kSoftcap ? "_softcap" : c.family == Family::kWindow ? "_window" : "";
+    const char* kind = is_tree(c) ? "_tree" : c.family == Family::kSoftcap ? "_softcap" : c.family == Family::kWindow ? "_window" : "";
     snprintf(buf, n, "ffpa_fwd_m16_%s%s_kernel<%s, %d%s>%s%s", c.kv != nullptr ? "paged" : "varlen", kind, cp.p->dtype == FFPA_DTYPE_BF16 ? "bf16" : "fp16", pl.ve->d, nt,
              pl.pack ? " (GQA heads packed into rows)" : "", merge);
   }
@@ -1878,97 +1805,103 @@ size_t ffpa_attn_varlen_softcap_fwd_workspace_bytes(const ffpa_varlen_fwd_params
 
 // ---- the MLA latent-cache call (include/ffpa_attn.h: ffpa_mla): the paged call on ONE pool, every group packed into rows, the append in front
 int ffpa_attn_varlen_mla_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, void* stream) {
-  return varlen_launch(mla_call(p, kv, m), stream);
+  return varlen_launch(latent_call(ffpa::kMlaVariant_mla, p, kv, m), stream);
 }
-int ffpa_attn_varlen_mla_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int out[5]) { return call_plan(mla_call(p, kv, m), out); }
+int ffpa_attn_varlen_mla_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int out[5]) {
+  return call_plan(latent_call(ffpa::kMlaVariant_mla, p, kv, m), out);
+}
 int ffpa_attn_varlen_mla_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, char* buf, size_t n) {
-  return call_kernel(mla_call(p, kv, m), buf, n);
+  return call_kernel(latent_call(ffpa::kMlaVariant_mla, p, kv, m), buf, n);
 }
 size_t ffpa_attn_varlen_mla_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m) {
-  return call_workspace_bytes(mla_call(p, kv, m));
+  return call_workspace_bytes(latent_call(ffpa::kMlaVariant_mla, p, kv, m));
 }
 int ffpa_attn_varlen_mla_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, int* slots) {
-  return call_compact_slots(mla_call(p, kv, m), slots);
+  return call_compact_slots(latent_call(ffpa::kMlaVariant_mla, p, kv, m), slots);
 }
 
 // ---- the tree-mask latent call (include/ffpa_attn.h): the latent launch under the causal flag, the element test of the draft tiles reads the mask words
 int ffpa_attn_varlen_mla_tree_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, void* stream) {
-  return varlen_launch(mla_tree_call(p, kv, m, tree), stream);
+  return varlen_launch(latent_call(ffpa::kMlaVariant_mla_tree, p, kv, m, tree), stream);
 }
 int ffpa_attn_varlen_mla_tree_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, int out[5]) {
-  return call_plan(mla_tree_call(p, kv, m, tree), out);
+  return call_plan(latent_call(ffpa::kMlaVariant_mla_tree, p, kv, m, tree), out);
 }
 int ffpa_attn_varlen_mla_tree_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, char* buf, size_t n) {
-  return call_kernel(mla_tree_call(p, kv, m, tree), buf, n);
+  return call_kernel(latent_call(ffpa::kMlaVariant_mla_tree, p, kv, m, tree), buf, n);
 }
 size_t ffpa_attn_varlen_mla_tree_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree) {
-  return call_workspace_bytes(mla_tree_call(p, kv, m, tree));
+  return call_workspace_bytes(latent_call(ffpa::kMlaVariant_mla_tree, p, kv, m, tree));
 }
 int ffpa_attn_varlen_mla_tree_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, int* slots) {
-  return call_compact_slots(mla_tree_call(p, kv, m, tree), slots);
+  return call_compact_slots(latent_call(ffpa::kMlaVariant_mla_tree, p, kv, m, tree), slots);
 }
 
 // ---- the FP8 latent call (include/ffpa_attn.h: ffpa_mla_fp8): the latent call over a pool of e4m3 codes with one per-tensor scale
 int ffpa_attn_varlen_mla_fp8_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, void* stream) {
-  return varlen_launch(mla_fp8_call(p, kv, m, f8), stream);
+  return varlen_launch(latent_call(ffpa::kMlaVariant_mla_fp8, p, kv, m, nullptr, f8), stream);
 }
 int ffpa_attn_varlen_mla_fp8_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, int out[5]) {
-  return call_plan(mla_fp8_call(p, kv, m, f8), out);
+  return call_plan(latent_call(ffpa::kMlaVariant_mla_fp8, p, kv, m, nullptr, f8), out);
 }
 int ffpa_attn_varlen_mla_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, char* buf, size_t n) {
-  return call_kernel(mla_fp8_call(p, kv, m, f8), buf, n);
+  return call_kernel(latent_call(ffpa::kMlaVariant_mla_fp8, p, kv, m, nullptr, f8), buf, n);
 }
 size_t ffpa_attn_varlen_mla_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8) {
-  return call_workspace_bytes(mla_fp8_call(p, kv, m, f8));
+  return call_workspace_bytes(latent_call(ffpa::kMlaVariant_mla_fp8, p, kv, m, nullptr, f8));
 }
 int ffpa_attn_varlen_mla_fp8_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_mla_fp8* f8, int* slots) {
-  return call_compact_slots(mla_fp8_call(p, kv, m, f8), slots);
+  return call_compact_slots(latent_call(ffpa::kMlaVariant_mla_fp8, p, kv, m, nullptr, f8), slots);
 }
 
 // ---- the FP8 tree-mask latent call: the tree-mask latent call over a pool of e4m3 codes (the FP8 latent call's plan, append and scale)
 int ffpa_attn_varlen_mla_tree_fp8_fwd(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, const ffpa_mla_fp8* f8,
                                       void* stream) {
-  return varlen_launch(mla_tree_fp8_call(p, kv, m, tree, f8), stream);
+  return varlen_launch(latent_call(ffpa::kMlaVariant_mla_tree_fp8, p, kv, m, tree, f8), stream);
 }
 int ffpa_attn_varlen_mla_tree_fp8_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree, const ffpa_mla_fp8* f8,
                                            int out[5]) {
-  return call_plan(mla_tree_fp8_call(p, kv, m, tree, f8), out);
+  return call_plan(latent_call(ffpa::kMlaVariant_mla_tree_fp8, p, kv, m, tree, f8), out);
 }
 int ffpa_attn_varlen_mla_tree_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree,
                                              const ffpa_mla_fp8* f8, char* buf, size_t n) {
-  return call_kernel(mla_tree_fp8_call(p, kv, m, tree, f8), buf, n);
+  return call_kernel(latent_call(ffpa::kMlaVariant_mla_tree_fp8, p, kv, m, tree, f8), buf, n);
 }
 size_t ffpa_attn_varlen_mla_tree_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree,
                                                          const ffpa_mla_fp8* f8) {
-  return call_workspace_bytes(mla_tree_fp8_call(p, kv, m, tree, f8));
+  return call_workspace_bytes(latent_call(ffpa::kMlaVariant_mla_tree_fp8, p, kv, m, tree, f8));
 }
 int ffpa_attn_varlen_mla_tree_fp8_fwd_compact_slots(const ffpa_varlen_fwd_params* p, const ffpa_paged_kv* kv, const ffpa_mla* m, const ffpa_tree_mask* tree,
                                                     const ffpa_mla_fp8* f8, int* slots) {
-  return call_compact_slots(mla_tree_fp8_call(p, kv, m, tree, f8), slots);
+  return call_compact_slots(latent_call(ffpa::kMlaVariant_mla_tree_fp8, p, kv, m, tree, f8), slots);
 }
 
 // ---- the FP8 sparse latent call: the sparse latent call over a pool of e4m3 codes
 int ffpa_attn_varlen_mla_sparse_fp8_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, void* stream) {
-  return varlen_launch(sparse_fp8_call(p, s, f8), stream);
+  return varlen_launch(gather_call(ffpa::kMlaVariant_mla_sparse_fp8, p, s, f8), stream);
 }
 int ffpa_attn_varlen_mla_sparse_fp8_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, int out[5]) {
-  return call_plan(sparse_fp8_call(p, s, f8), out);
+  return call_plan(gather_call(ffpa::kMlaVariant_mla_sparse_fp8, p, s, f8), out);
 }
 int ffpa_attn_varlen_mla_sparse_fp8_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, char* buf, size_t n) {
-  return call_kernel(sparse_fp8_call(p, s, f8), buf, n);
+  return call_kernel(gather_call(ffpa::kMlaVariant_mla_sparse_fp8, p, s, f8), buf, n);
 }
 size_t ffpa_attn_varlen_mla_sparse_fp8_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8) {
-  return call_workspace_bytes(sparse_fp8_call(p, s, f8));
+  return call_workspace_bytes(gather_call(ffpa::kMlaVariant_mla_sparse_fp8, p, s, f8));
 }
 
 // ---- the sparse latent call over the 656-byte FP8 rows of DeepSeek-V3.2, and the store that writes such rows by slot
-int ffpa_attn_varlen_mla_sparse_ds_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream) { return varlen_launch(sparse_ds_call(p, s), stream); }
-int ffpa_attn_varlen_mla_sparse_ds_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]) { return call_plan(sparse_ds_call(p, s), out); }
+int ffpa_attn_varlen_mla_sparse_ds_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream) {
+  return varlen_launch(gather_call(ffpa::kMlaVariant_mla_sparse_ds, p, s), stream);
+}
+int ffpa_attn_varlen_mla_sparse_ds_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]) {
+  return call_plan(gather_call(ffpa::kMlaVariant_mla_sparse_ds, p, s), out);
+}
 int ffpa_attn_varlen_mla_sparse_ds_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n) {
-  return call_kernel(sparse_ds_call(p, s), buf, n);
+  return call_kernel(gather_call(ffpa::kMlaVariant_mla_sparse_ds, p, s), buf, n);
 }
 size_t ffpa_attn_varlen_mla_sparse_ds_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
-  return call_workspace_bytes(sparse_ds_call(p, s));
+  return call_workspace_bytes(gather_call(ffpa::kMlaVariant_mla_sparse_ds, p, s));
 }
 int ffpa_attn_mla_ds_store(const ffpa_mla_ds_store_params* p, void* stream) {
   if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
@@ -2000,12 +1933,18 @@ int ffpa_attn_mla_ds_store(const ffpa_mla_ds_store_params* p, void* stream) {
 }
 
 // ---- the sparse latent call (include/ffpa_attn.h: ffpa_mla_sparse): the latent launch over per-token index lists
-int ffpa_attn_varlen_mla_sparse_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream) { return varlen_launch(sparse_call(p, s), stream); }
-int ffpa_attn_varlen_mla_sparse_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]) { return call_plan(sparse_call(p, s), out); }
-int ffpa_attn_varlen_mla_sparse_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n) {
-  return call_kernel(sparse_call(p, s), buf, n);
+int ffpa_attn_varlen_mla_sparse_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream) {
+  return varlen_launch(gather_call(ffpa::kMlaVariant_mla_sparse, p, s), stream);
 }
-size_t ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) { return call_workspace_bytes(sparse_call(p, s)); }
+int ffpa_attn_varlen_mla_sparse_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]) {
+  return call_plan(gather_call(ffpa::kMlaVariant_mla_sparse, p, s), out);
+}
+int ffpa_attn_varlen_mla_sparse_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n) {
+  return call_kernel(gather_call(ffpa::kMlaVariant_mla_sparse, p, s), buf, n);
+}
+size_t ffpa_attn_varlen_mla_sparse_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
+  return call_workspace_bytes(gather_call(ffpa::kMlaVariant_mla_sparse, p, s));
+}
 
 // ---- the latent append of a ragged step (include/ffpa_attn.h: ffpa_mla_append_varlen_params): token rows packed by cu_seqlens_q into the ONE paged pool
 // (one body for the 16-bit pool and — f8 non-NULL, checked by the caller — the FP8 pool, whose rows are quantised on their way in)
@@ -2037,12 +1976,8 @@ static int mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_
   memset(&fa, 0, sizeof(fa));
   ffpa::MlaAppendVarlenArgs& va = fa.va;
   ffpa::MlaAppendArgs& a = va.a;
-  a.kv_new = p->kv_new, a.cache = p->kv_cache;
-  a.seqlens = p->cache_seqlens, a.used = p->seqused, a.table = kv->block_table;
+  a = mla_append_args(p->kv_new, p->kv_cache, p->cache_seqlens, p->seqused, p->kv_cache_stride, kv, p->batch, p->heads_kv, p->head_dim);
   a.s_new[1] = p->kv_new_stride[0], a.s_new[2] = p->kv_new_stride[1];
-  a.s_row = p->kv_cache_stride[0], a.s_head = p->kv_cache_stride[1], a.s_page = kv->k_page_stride, a.bt_stride = kv->bt_stride;
-  a.B = p->batch, a.Hkv = p->heads_kv, a.D = p->head_dim;
-  a.cap = kv->pages_per_row * kv->page_size, a.page_size = kv->page_size, a.num_pages = kv->num_pages;
   va.cu_q = p->cu_seqlens_q, va.T = p->total_q;
   if (f8 != nullptr) fa.inv = 1.f / f8->kv_scale;
   const int st = f8 != nullptr ? ffpa::launch_mla_fp8_append_varlen(p->dtype, fa, static_cast<hipStream_t>(stream))

@@ -1,5 +1,6 @@
-// ffpa_mla.h — MLA latent-cache attention (ffpa_attn_varlen_mla_fwd, ffpa_capi.hip): what its kernels take beyond FwdArgs / VarlenArgs / PagedArgs and the launchers
-// of ffpa_mla_inst.hip.  A header of its own so that the dense, packed and paged objects see nothing of it.
+// ffpa_mla.h — MLA latent-cache attention (the ffpa_attn_varlen_mla*_fwd calls, ffpa_capi.hip): THE LIST OF ITS KERNEL VARIANTS, what the kernels take beyond
+// FwdArgs / VarlenArgs / PagedArgs, the launchers of the seven ffpa_mla*_inst.hip units (one shell: ffpa_mla_variant.inc) and the 16-bit appends.  A header of its
+// own so that the dense, packed and paged objects see nothing of it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,8 +11,41 @@ struct FwdArgs;
 struct VarlenArgs;
 struct PagedArgs;
 
-// The (head dim, value width) pairs ffpa_mla_inst.hip is built for: one line per pair here, one -DFFPA_INST_D=<D> unit in build.py.
+// The (head dim, value width) pairs every variant is built for: one line per pair here, one entry of MLA_BUILDS in build.py.
 #define FFPA_FOR_EACH_MLA_BUILD(X) X(576, 512)
+
+// THE VARIANTS.  A latent kernel is three independent choices — is there a tree mask, how are the keys found, what does the pool hold — and one switch that was
+// found by measurement.  One row per variant, in link order (build.py's MLA_VARIANTS names the same stems in the same order); the row's stem names the unit
+// (ffpa_<stem>_inst.hip), the kernel (ffpa_fwd_m16_<stem>_kernel) and the launchers (launch_<stem>_d<D>).  X(stem, tree, gather, pool, exit refresh, ...):
+//   tree          the element test of the tiles that hold a draft key reads the row's 64-bit mask word (and the wait in front of the KV loop: ffpa_mla_variant.inc)
+//   gather        0: the keys of a sequence are found through its page table; 1: through a list of pool rows per query token (the sparse calls)
+//   pool          what a latent row is made of (FFPA_MLA_POOL_*)
+//   exit refresh  the epilogue's arguments are read again from the argument block behind the KV loop (ffpa_mla_variant.inc says why): on where the loop has no
+//                 scalar register to spare — measured per variant, not derived from the other three
+#define FFPA_MLA_POOL_16BIT 0  // bf16 / fp16 elements, q's dtype
+#define FFPA_MLA_POOL_E4M3 1   // OCP e4m3 codes under ONE per-tensor scale (MlaFp8Args::kv_scale)
+#define FFPA_MLA_POOL_DS 2     // the 656-byte rows of DeepSeek-V3.2 (ffpa_mla_sparse_ds.h): e4m3 codes, a scale per 128 columns in the row, bf16 rotary columns; q is bf16
+#define FFPA_FOR_EACH_MLA_VARIANT(X, ...)                      \
+  X(mla, 0, 0, FFPA_MLA_POOL_16BIT, 0, __VA_ARGS__)            \
+  X(mla_sparse, 0, 1, FFPA_MLA_POOL_16BIT, 0, __VA_ARGS__)     \
+  X(mla_tree, 1, 0, FFPA_MLA_POOL_16BIT, 1, __VA_ARGS__)       \
+  X(mla_fp8, 0, 0, FFPA_MLA_POOL_E4M3, 0, __VA_ARGS__)         \
+  X(mla_sparse_fp8, 0, 1, FFPA_MLA_POOL_E4M3, 1, __VA_ARGS__)  \
+  X(mla_tree_fp8, 1, 0, FFPA_MLA_POOL_E4M3, 1, __VA_ARGS__)    \
+  X(mla_sparse_ds, 0, 1, FFPA_MLA_POOL_DS, 1, __VA_ARGS__)
+
+struct MlaVariant {
+  const char* stem;
+  bool tree, gather;
+  int pool;
+  bool exit_refresh;
+};
+#define FFPA_ROW(stem, tree, gather, pool, refresh, ...) {#stem, tree != 0, gather != 0, pool, refresh != 0},
+constexpr MlaVariant kMlaVariants[] = {FFPA_FOR_EACH_MLA_VARIANT(FFPA_ROW, )};
+#undef FFPA_ROW
+#define FFPA_ROW(stem, ...) kMlaVariant_##stem,
+enum MlaVariantId { FFPA_FOR_EACH_MLA_VARIANT(FFPA_ROW, ) kMlaVariantCount };
+#undef FFPA_ROW
 
 // What the latent kernels need beyond the three shared structs (they keep their layout): the keys of a KV head are the latent rows' D columns, its values the
 // first `dv` of the same rows — only O columns < dv are stored.
@@ -75,9 +109,16 @@ __device__ __forceinline__ int mla_append_used(const MlaAppendArgs& a, int len, 
   return (int)(u < a.cap ? u : a.cap);
 }
 
-#define FFPA_DECL(D, DV) int launch_mla_paged_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaArgs& ma, hipStream_t stream);
+// ONE host signature for every variant's launcher: the fourth struct is the e4m3 builds' (ffpa_mla_fp8.h: the value width and the scale); the kernels over the
+// other pools still take MlaArgs by value — their launcher passes on the value width alone.  -4: a dtype the variant is not built for.
+struct MlaFp8Args;
+typedef int (*mla_launch_fn)(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaFp8Args& ma, hipStream_t stream);
+#define FFPA_DECL_ONE(stem, tree, gather, pool, refresh, D) \
+  int launch_##stem##_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaFp8Args& ma, hipStream_t stream);
+#define FFPA_DECL(D, DV) FFPA_FOR_EACH_MLA_VARIANT(FFPA_DECL_ONE, D)
 FFPA_FOR_EACH_MLA_BUILD(FFPA_DECL)
 #undef FFPA_DECL
+#undef FFPA_DECL_ONE
 int launch_mla_append(const MlaAppendArgs& a, hipStream_t stream);
 int launch_mla_append_varlen(const MlaAppendVarlenArgs& va, hipStream_t stream);
 

@@ -1,5 +1,5 @@
 // ffpa_mla_fp8.h — the FP8 (OCP e4m3) build of the MLA latent-cache call (ffpa_attn_varlen_mla_fp8_fwd, ffpa_capi.hip): what its kernels take beyond the latent
-// call's structs (ffpa_mla.h) and the launchers of ffpa_mla_fp8_inst.hip.  A header of its own so that the other objects see nothing of it.
+// call's structs (ffpa_mla.h) and the quantising appends' launchers (ffpa_mla_fp8_inst.hip).  The attention launchers of every variant: ffpa_mla.h.
 #pragma once
 #include "ffpa_mla.h"
 
@@ -26,10 +26,6 @@ struct MlaFp8AppendVarlenArgs {
   float inv;
 };
 
-#define FFPA_DECL(D, DV) \
-  int launch_mla_fp8_paged_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaFp8Args& ma, hipStream_t stream);
-FFPA_FOR_EACH_MLA_BUILD(FFPA_DECL)
-#undef FFPA_DECL
 int launch_mla_fp8_append(int dtype, const MlaFp8AppendArgs& a, hipStream_t stream);
 int launch_mla_fp8_append_varlen(int dtype, const MlaFp8AppendVarlenArgs& va, hipStream_t stream);
 

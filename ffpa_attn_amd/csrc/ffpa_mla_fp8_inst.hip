@@ -1,63 +1,15 @@
 // ffpa_mla_fp8_inst.hip — MLA latent-cache attention over an FP8 cache: the latent pool holds OCP e4m3 codes with ONE per-tensor scale (K = kv_scale x K8), the
-// form in which the serving engines keep the latent cache of DeepSeek-V2 / V3 / R1 and Kimi K2 (kv_cache_dtype = "fp8").  One translation unit per (D, dv) pair of
-// FFPA_FOR_EACH_MLA_BUILD (compiled with -DFFPA_INST_D=<D>, q / O in bf16 + fp16 in the same TU); a TU of its own so that every other object stays what it was.
-// Entry point: ffpa_attn_varlen_mla_fp8_fwd (ffpa_capi.hip).
-//
-// The kernel is the latent kernel's text (ffpa_mla_inst.hip: ffpa_fwd_m16_paged_body.inc + ffpa_fwd_m16_tile.inc under FFPA_M16_MLA_ON) with one more hook of the
-// tile text on, FFPA_M16_KV_FP8 (described there).  There is no FP8 arithmetic: every e4m3 value is exactly a bf16 and exactly an fp16, so the kernel stages a tile's
-// bytes in registers, widens them and writes the EXACT 16-bit image of the tile to LDS where the LDS-DMA pieces of the 16-bit build land; the MFMAs, the shared
-// image under the V swizzle, the two alternating images, the two-barrier step, row chunks, KV ranges + merge and the compact grid are that build's.  The scale
-// never touches an element: the scores are (softmax_scale x kv_scale) q.K8, and O is multiplied by kv_scale once in the epilogues' 1 / l.  With a power-of-two
-// kv_scale the call returns the bits of the 16-bit latent call on the dequantised pool.
-#include "ffpa_cu_seqlens_find.h"
-#include "ffpa_fwd_kernel.h"
-#include "ffpa_fwd_m16_kernel.h"
-#include "ffpa_launch_kernel.h"
-#include "ffpa_mla_fp8.h"
-#include "ffpa_paged.h"
-
-#ifndef FFPA_INST_D
-#error "compile with -DFFPA_INST_D=<head dim>"
-#endif
+// form in which the serving engines keep the latent cache of DeepSeek-V2 / V3 / R1 and Kimi K2 (kv_cache_dtype = "fp8").  The plain variant of the latent kernel
+// (ffpa_mla_variant.inc) over an e4m3 pool — with a power-of-two kv_scale the call returns the bits of the 16-bit latent call on the dequantised pool — and the two
+// quantising appends.  Entry point: ffpa_attn_varlen_mla_fp8_fwd (ffpa_capi.hip).
+#define FFPA_MLA_STEM mla_fp8
+#define FFPA_MLA_TREE 0
+#define FFPA_MLA_GATHER 0
+#define FFPA_MLA_POOL FFPA_MLA_POOL_E4M3
+#define FFPA_MLA_EXIT_REFRESH 0
+#include "ffpa_mla_variant.inc"
 
 namespace ffpa {
-
-template <typename T, int D, bool NT = false>
-__global__ __launch_bounds__(256) void ffpa_fwd_m16_mla_fp8_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa, const MlaFp8Args ma) {
-  static_assert(D > 512 && D % 128 == 64, "the MLA hook lives in the un-pipelined split-D loop of the tile text");
-#define FFPA_M16_VARLEN_TREE false
-#define FFPA_M16_VARLEN_WINDOW false
-#define FFPA_M16_VARLEN_SOFTCAP false
-#define FFPA_M16_MLA_ON true
-#define FFPA_M16_O_COLS ma.dv
-#define FFPA_M16_KV_FP8 true
-#define FFPA_M16_KV_SCALE ma.kv_scale
-#define FFPA_M16_KV_FP8_LOAD(rsrc_, voff_) buffer_load_8<NT>((rsrc_), (voff_))
-#include "ffpa_fwd_m16_paged_body.inc"
-#undef FFPA_M16_KV_FP8_LOAD
-#undef FFPA_M16_KV_SCALE
-#undef FFPA_M16_KV_FP8
-#undef FFPA_M16_O_COLS
-#undef FFPA_M16_MLA_ON
-#undef FFPA_M16_VARLEN_SOFTCAP
-#undef FFPA_M16_VARLEN_WINDOW
-#undef FFPA_M16_VARLEN_TREE
-}
-
-template <typename T, int D, bool NT>
-static int launch_mla_fp8(const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaFp8Args& ma, hipStream_t stream) {
-  constexpr int BC = m16_block_keys(D, true);
-  constexpr int LDS = 2 * BC * D * 2 + m16_exchange_bytes(D, 0);  // (the two 16-bit images of the latent kernel: the same LDS bytes)
-  return launch_kernel<ffpa_fwd_m16_mla_fp8_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa, ma);
-}
-
-int FFPA_CAT(launch_mla_fp8_paged_d, FFPA_INST_D)(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaFp8Args& ma,
-                                                  hipStream_t stream) {
-  return dispatch_dtype(dtype, [&](auto t) {
-    using T = typename decltype(t)::type;
-    return nt ? launch_mla_fp8<T, FFPA_INST_D, true>(a, va, pa, ma, stream) : launch_mla_fp8<T, FFPA_INST_D, false>(a, va, pa, ma, stream);
-  });
-}
 
 #if FFPA_INST_D == 576  // (one copy of the appends in the library: the first build's TU carries them)
 // THE QUANTISATION of the appends, to the bit: rne_e4m3(clamp(float32(x) * inv, -448, +448)).  +-inf saturates; NaN stays NaN — a max / min (or med3) clamp returns

@@ -1,54 +1,15 @@
 // ffpa_mla_inst.hip — MLA latent-cache attention (DeepSeek-V2 / V3 / R1, Kimi K2 in their "absorbed" decode form): every query head has D columns, all heads of a
-// group attend to ONE latent KV head, and the values are the first dv columns of the very rows that serve as keys.  One translation unit per (D, dv) pair of
-// FFPA_FOR_EACH_MLA_BUILD (ffpa_mla.h; compiled with -DFFPA_INST_D=<D>, bf16 + fp16 in the same TU); a TU of its own so that the dense, packed and paged objects
-// stay exactly what they were.  Entry point: ffpa_attn_varlen_mla_fwd (ffpa_capi.hip).
-//
-// The kernel is the paged twin of the packed-sequence kernel (ffpa_paged_inst.hip: the same sequence lookup, workgroup order, row packing, KV splits and page
-// lookahead) with the tile text's MLA hook on (FFPA_M16_MLA_ON, ffpa_fwd_m16_tile.inc): the two LDS images of the tile, Kt and Vt, alternate as the home of ONE
-// latent tile — tile j lives in image j & 1, QK^T(j) reads its K fragments there and PV(j) its V^T fragments from the same bytes.  There are no V pieces: a
-// latent row is fetched once.  A contiguous cache runs through the same kernel with one page per sequence (the Python entry's identity table).
-#include "ffpa_cu_seqlens_find.h"
-#include "ffpa_fwd_kernel.h"
-#include "ffpa_fwd_m16_kernel.h"
-#include "ffpa_launch_kernel.h"
-#include "ffpa_mla.h"
-#include "ffpa_paged.h"
-
-#ifndef FFPA_INST_D
-#error "compile with -DFFPA_INST_D=<head dim>"
-#endif
+// group attend to ONE latent KV head, and the values are the first dv columns of the very rows that serve as keys.  The plain variant of the latent kernel
+// (ffpa_mla_variant.inc: no mask, keys through the page table, a 16-bit pool; a contiguous cache runs through it with one page per sequence) and the two 16-bit
+// appends.  One unit per (D, dv) pair of FFPA_FOR_EACH_MLA_BUILD (-DFFPA_INST_D=<D>; bf16 + fp16, plain + NT).  Entry point: ffpa_attn_varlen_mla_fwd (ffpa_capi.hip).
+#define FFPA_MLA_STEM mla
+#define FFPA_MLA_TREE 0
+#define FFPA_MLA_GATHER 0
+#define FFPA_MLA_POOL FFPA_MLA_POOL_16BIT
+#define FFPA_MLA_EXIT_REFRESH 0
+#include "ffpa_mla_variant.inc"
 
 namespace ffpa {
-
-template <typename T, int D, bool NT = false>
-__global__ __launch_bounds__(256) void ffpa_fwd_m16_mla_kernel(const FwdArgs a_in, const VarlenArgs va, const PagedArgs pa, const MlaArgs ma) {
-  static_assert(D > 512 && D % 128 == 64, "the MLA hook lives in the un-pipelined split-D loop of the tile text");
-#define FFPA_M16_VARLEN_TREE false
-#define FFPA_M16_VARLEN_WINDOW false
-#define FFPA_M16_VARLEN_SOFTCAP false
-#define FFPA_M16_MLA_ON true
-#define FFPA_M16_O_COLS ma.dv
-#include "ffpa_fwd_m16_paged_body.inc"
-#undef FFPA_M16_O_COLS
-#undef FFPA_M16_MLA_ON
-#undef FFPA_M16_VARLEN_SOFTCAP
-#undef FFPA_M16_VARLEN_WINDOW
-#undef FFPA_M16_VARLEN_TREE
-}
-
-template <typename T, int D, bool NT>
-static int launch_mla(const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaArgs& ma, hipStream_t stream) {
-  constexpr int BC = m16_block_keys(D, true);
-  constexpr int LDS = 2 * BC * D * 2 + m16_exchange_bytes(D, 0);  // (the two images of the paged kernel: the same LDS bytes)
-  return launch_kernel<ffpa_fwd_m16_mla_kernel<T, D, NT>>(a.total_wg, LDS, stream, a, va, pa, ma);
-}
-
-int FFPA_CAT(launch_mla_paged_d, FFPA_INST_D)(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaArgs& ma, hipStream_t stream) {
-  return dispatch_dtype(dtype, [&](auto t) {
-    using T = typename decltype(t)::type;
-    return nt ? launch_mla<T, FFPA_INST_D, true>(a, va, pa, ma, stream) : launch_mla<T, FFPA_INST_D, false>(a, va, pa, ma, stream);
-  });
-}
 
 #if FFPA_INST_D == 576  // (one copy of the append in the library: the first build's TU carries it)
 // One new row's Hkv heads as raw bytes — 16-bit elements of either dtype —, every 16-byte chunk loaded and stored once.

@@ -1,12 +1,12 @@
 // ffpa_mla_sparse_ds.h — sparse (top-k indexed) attention over the 656-byte FP8 latent rows of DeepSeek-V3.2 (vLLM's "fp8_ds_mla", the FP8 KV layout of FlashMLA's
-// sparse decode; ffpa_attn_varlen_mla_sparse_ds_fwd, ffpa_capi.hip): the row format, the launchers of ffpa_mla_sparse_ds_inst.hip and the store kernel's launcher
-// (ffpa_mla_ds_store.hip).  A header of its own so that every other object sees nothing of it.
+// sparse decode; ffpa_attn_varlen_mla_sparse_ds_fwd, ffpa_capi.hip): the row format, the kernel's helpers for it (the hooks of the shell's 656-byte pool, ffpa_mla_variant.inc) and the store
+// kernel's launcher (ffpa_mla_ds_store.hip).  A header of its own so that every other object sees nothing of it.
 //
 // THE ROW, kDsRowBytes = 656 bytes of one latent head of one slot:
 //     bytes   0 ... 511   the 512 latent ("NoPE") columns as OCP e4m3 codes
 //     bytes 512 ... 527   four float32 scales, one per 128 columns:  column c = bf16_rne(float32(code[c]) * scale[c / 128])
 //     bytes 528 ... 655   the 64 rotary columns as bf16, as they are
-// The attention kernels take FwdArgs / VarlenArgs / PagedArgs as the sparse launch fills them with the pool's strides in units of TWO BYTES (ffpa_mla_sparse_fp8.h)
+// The attention kernels take FwdArgs / VarlenArgs / PagedArgs as the sparse launch fills them with the pool's strides in units of TWO BYTES (ffpa_mla_fp8.h)
 // and MlaArgs (the value width).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -68,10 +68,6 @@ struct MlaDsStoreArgs {
   int T, Hkv, num_rows;
 };
 
-#define FFPA_DECL(D, DV) \
-  int launch_mla_sparse_ds_d##D(int dtype, int nt, const FwdArgs& a, const VarlenArgs& va, const PagedArgs& pa, const MlaArgs& ma, hipStream_t stream);
-FFPA_FOR_EACH_MLA_BUILD(FFPA_DECL)
-#undef FFPA_DECL
 int launch_mla_ds_store(const MlaDsStoreArgs& a, hipStream_t stream);
 
 }  // namespace ffpa

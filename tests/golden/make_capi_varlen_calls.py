@@ -40,7 +40,15 @@ FORMS = {
   "mla": ("ffpa_attn_varlen_mla_fwd", ("kv", "mla"), False, True),
   "mla_tree": ("ffpa_attn_varlen_mla_tree_fwd", ("kv", "mla", "tree"), False, True),
   "sparse": ("ffpa_attn_varlen_mla_sparse_fwd", ("sparse",), False, False),
+  "mla_fp8": ("ffpa_attn_varlen_mla_fp8_fwd", ("kv", "mla", "fp8"), False, True),
+  "mla_tree_fp8": ("ffpa_attn_varlen_mla_tree_fp8_fwd", ("kv", "mla", "tree", "fp8"), False, True),
+  "sparse_fp8": ("ffpa_attn_varlen_mla_sparse_fp8_fwd", ("sparse", "fp8"), False, False),
+  "sparse_ds": ("ffpa_attn_varlen_mla_sparse_ds_fwd", ("sparse",), False, False),
 }
+# the forms over the one latent cache (their kernels are named after the call alone) and, of those, the ones recorded later than the first eight forms: their
+# entries stand behind the first eight's and are never folded into one of them, so that recording a new form leaves every older line of the list as it is
+LATENT_FORMS = ("mla", "mla_tree", "sparse", "mla_fp8", "mla_tree_fp8", "sparse_fp8", "sparse_ds")
+LATER_FORMS = ("mla_fp8", "mla_tree_fp8", "sparse_fp8", "sparse_ds")
 
 
 def _hip():
@@ -64,7 +72,8 @@ def _fill(struct, over: dict):
 
 def _structs(hip, call: dict):
   """The ctypes arguments of a call: params and the form's structs, each stamped with its size (and version) before the overrides."""
-  classes = {"kv": hip.FfpaPagedKv, "tree": hip.FfpaTreeMask, "window": hip.FfpaWindow, "mla": hip.FfpaMla, "sparse": hip.FfpaMlaSparse}
+  classes = {"kv": hip.FfpaPagedKv, "tree": hip.FfpaTreeMask, "window": hip.FfpaWindow, "mla": hip.FfpaMla, "sparse": hip.FfpaMlaSparse,
+             "fp8": hip.FfpaMlaFp8}
   keep, args = [], []
   for name, cls in [("params", hip.FfpaVarlenFwdParams)] + [(n, classes[n]) for n in FORMS[call["form"]][1]]:
     over = call.get(name, {})
@@ -119,7 +128,7 @@ QUERIES = ("plan", "kernel", "workspace_bytes", "compact_slots")
 def kernel_stem(call: dict) -> "str | None":
   """What the kernels of the calls over a K and a V cache are named after — the cache, then the call — and the one thing in which those calls' answers to one
   set of arguments differ: the list writes it ``*``, so that they stay one entry."""
-  if call["form"] in ("mla", "mla_tree", "sparse"):
+  if call["form"] in LATENT_FORMS:
     return None
   paged = call["form"] == "paged" or (call["form"] != "packed" and call.get("kv", {}) is not None)
   return "ffpa_fwd_m16_" + ("paged" if paged else "varlen") + {"packed": "", "paged": ""}.get(call["form"], "_" + call["form"]) + "_kernel"
@@ -205,6 +214,9 @@ MLA = dict(head_dim_v=512)
 SOFTCAP = 30.0
 SPARSE = dict(indices=INDICES, indices_stride=256, topk_lens=LENS, kv_stride=[576, 576], topk=256, num_rows=100000, head_dim_v=512)
 
+FP8 = dict(kv_scale=0.5)
+SPARSE_DS = dict(SPARSE, kv_stride=[656, 656])  # (a pool of 656-byte rows: its strides are bytes)
+
 STRIDES = {"q_stride": "heads_q", "k_stride": "heads_kv", "v_stride": "heads_kv", "o_stride": "heads_q"}  # a dense [T, H, D] layout: (H * D, D)
 
 
@@ -219,10 +231,10 @@ def latent_kv() -> dict:
 
 def defaults(form: str, name: str) -> dict:
   """The fields of struct ``name`` that a call of ``form`` starts from (the params without their strides: ``full`` derives them)."""
-  latent = form in ("mla", "mla_tree", "sparse")
+  latent = form in LATENT_FORMS
   if name == "params":
     return {k: v for k, v in (latent_params() if latent else params()).items() if k not in STRIDES and k != "total_q"}
-  return {"kv": latent_kv() if latent else KV, "tree": TREE, "window": WINDOW, "mla": MLA, "sparse": SPARSE}[name]
+  return {"kv": latent_kv() if latent else KV, "tree": TREE, "window": WINDOW, "mla": MLA, "sparse": SPARSE_DS if form == "sparse_ds" else SPARSE, "fp8": FP8}[name]
 
 
 def full(form: str, name: str, over: dict) -> dict:
@@ -466,9 +478,9 @@ def build_list():
         add(form, "refused: tree size and pool" + tag, base, kv=dict(kv, num_pages=0), tree=dict(TREE, struct_size=1), **structs)
 
   # ---- the latent calls
-  for form, structs in [("mla", dict()), ("mla_tree", dict(tree=TREE))]:
+  def latent_calls(form, structs):
     for label, over, cus in latent_regimes():
-      if structs and over.get("mq", 1) > 64:
+      if "tree" in structs and over.get("mq", 1) > 64:
         continue  # (a tree holds at most 64 tokens)
       add(form, label, latent_params(**over), cus, reached=REACHED[label], kv=latent_kv(), mla=MLA, **structs)
     add(form, "causal flag set by the caller", latent_params(hq=16, mq=8, causal=1), kv=latent_kv(), mla=MLA, **structs)
@@ -491,6 +503,8 @@ def build_list():
     add(form, "refused: grid of new rows", latent_params(batch=1 << 16, hq=1, mq=1), kv=latent_kv(), mla=dict(app, seqlen_new=1 << 16), **structs)
     add(form, "refused: mla NULL and pool", base, kv=dict(latent_kv(), page_size=1), mla=None, **structs)
     add(form, "refused: mla reserved and o NULL", dict(base, o=0), kv=latent_kv(), mla=dict(MLA, reserved=1), **structs)
+  for form, structs in [("mla", dict()), ("mla_tree", dict(tree=TREE))]:
+    latent_calls(form, structs)
   add("mla_tree", "refused: mla NULL and tree NULL", latent_params(), kv=latent_kv(), mla=None, tree=None)
   add("mla_tree", "refused: pair not built and tokens", latent_params(), kv=latent_kv(), mla=dict(MLA, head_dim_v=64), tree=dict(TREE, tokens=0))
   add("mla_tree", "refused: params size and tree NULL", dict(latent_params(), struct_size=16), kv=latent_kv(), mla=MLA, tree=None)
@@ -499,38 +513,123 @@ def build_list():
   def sp(**over):
     return latent_params(mq=1, **over)
 
-  fill = dict(batch=2, hq=16, **scratch())
-  for label, over, s, cus in [
-    ("heads packed", dict(hq=16), {}, None), ("heads packed chunked", dict(hq=128), {}, None), ("heads not packed by flag", dict(hq=16, flags=NO_PACK), {}, None),
-    ("nt by rule", dict(hq=16, batch=4096), dict(topk=2048, indices_stride=2048), None), ("nt forced on", dict(hq=16, flags=STREAM), {}, None),
-    ("nt forced off", dict(hq=16, batch=4096, flags=NO_STREAM), dict(topk=2048, indices_stride=2048), None),
-    ("splits by fill", fill, dict(topk=2048, indices_stride=2048), None), ("splits by fill 8 cus", fill, dict(topk=2048, indices_stride=2048), 8),
-    ("splits by balance", dict(batch=200, hq=2, **scratch()), dict(topk=2048, indices_stride=4096), None),  # (few heads: the partials stay cheap next to 2048 rows)
-    ("splits forced", dict(hq=16, num_splits=3, flags=FORCE, **scratch()), {}, None),
-    ("splits capped by num_splits", dict(fill, num_splits=2), dict(topk=2048, indices_stride=2048), None),
-    ("splits capped by workspace_bytes", dict(fill, workspace_bytes=2 * 16 * 2 * 577 * 4 + 100), dict(topk=2048, indices_stride=2048), None),
-    ("deterministic", dict(fill, flags=DET), dict(topk=2048, indices_stride=2048), None),
-    ("causal flag set by the caller", dict(hq=16, causal=1), {}, None), ("topk_lens NULL", dict(hq=16), dict(topk_lens=0), None),
-    ("fp16", dict(hq=16, dtype=1), {}, None),
-  ]:
-    add("sparse", label, sp(**over), cus, reached=REACHED.get(label), sparse=dict(SPARSE, **s))
+  def sparse_calls(form, S, geometry, structs):
+    fill = dict(batch=2, hq=16, **scratch())
+    for label, over, s, cus in [
+      ("heads packed", dict(hq=16), {}, None), ("heads packed chunked", dict(hq=128), {}, None), ("heads not packed by flag", dict(hq=16, flags=NO_PACK), {}, None),
+      ("nt by rule", dict(hq=16, batch=4096), dict(topk=2048, indices_stride=2048), None), ("nt forced on", dict(hq=16, flags=STREAM), {}, None),
+      ("nt forced off", dict(hq=16, batch=4096, flags=NO_STREAM), dict(topk=2048, indices_stride=2048), None),
+      ("splits by fill", fill, dict(topk=2048, indices_stride=2048), None), ("splits by fill 8 cus", fill, dict(topk=2048, indices_stride=2048), 8),
+      ("splits by balance", dict(batch=200, hq=2, **scratch()), dict(topk=2048, indices_stride=4096), None),  # (few heads: the partials stay cheap next to 2048 rows)
+      ("splits forced", dict(hq=16, num_splits=3, flags=FORCE, **scratch()), {}, None),
+      ("splits capped by num_splits", dict(fill, num_splits=2), dict(topk=2048, indices_stride=2048), None),
+      ("splits capped by workspace_bytes", dict(fill, workspace_bytes=2 * 16 * 2 * 577 * 4 + 100), dict(topk=2048, indices_stride=2048), None),
+      ("deterministic", dict(fill, flags=DET), dict(topk=2048, indices_stride=2048), None),
+      ("causal flag set by the caller", dict(hq=16, causal=1), {}, None), ("topk_lens NULL", dict(hq=16), dict(topk_lens=0), None),
+      ("fp16", dict(hq=16, dtype=1), {}, None),
+    ]:
+      if form == "sparse_ds" and label == "fp16":
+        add(form, "refused: fp16", sp(**over), sparse=dict(S, **s))  # (the rows' rotary columns are bf16: the pool's geometry refuses any other q)
+        continue
+      add(form, label, sp(**over), cus, reached=REACHED.get(label), sparse=dict(S, **s), **structs)
+    base = sp()
+    for label, over in common_refusals():
+      add(form, "common: " + label, None if over is None else dict(base, **over), sparse=S, **structs)
+    add(form, "NULL out / buf", base, null_out=True, sparse=S, **structs)
+    for label, s in [("sparse NULL", None), ("sparse size", dict(struct_size=48)), ("sparse reserved", dict(reserved=1)), ("sparse reserved2", dict(reserved2=1)),
+                     ("topk zero", dict(topk=0)), ("num_rows zero", dict(num_rows=0)), ("indices NULL", dict(indices=0)), ("indices misaligned", dict(indices=INDICES + 2)),
+                     ("topk_lens misaligned", dict(topk_lens=LENS + 1)), ("indices_stride", dict(indices_stride=255)), ("head_dim_v zero", dict(head_dim_v=0)),
+                     ("pair not built", dict(head_dim_v=256))] + geometry + [
+                     ("sparse size and topk", dict(struct_size=1, topk=-1)), ("indices and kv stride", dict(indices=0, kv_stride=[-1, 0]))]:
+      add(form, "refused: " + label, base, sparse=None if s is None else dict(S, **s), **structs)
+    add(form, "refused: max_seqlen_q above one", latent_params(mq=2), sparse=S, **structs)
+    add(form, "refused: sparse NULL and params NULL", None, sparse=None, **structs)
+    add(form, "refused: sparse size and params size", dict(base, struct_size=0), sparse=dict(S, struct_size=0), **structs)
+    add(form, "refused: max_seqlen_q and dtype", dict(base, max_seqlen_q=3, dtype=5), sparse=S, **structs)
+    add(form, "refused: topk and head dim", dict(base, head_dim=1), sparse=dict(S, topk=0), **structs)
+    add(form, "refused: pool span and q misaligned", dict(base, q=Q + 2), sparse=dict(S, num_rows=1 << 30), **structs)
+
+  # (the pool's geometry, counted in the pool's elements: 16-bit ones, bytes of an e4m3 pool — the same reach holds twice the rows —, bytes of 656-byte rows)
+  geometry = [("kv stride negative", dict(kv_stride=[576, -8])), ("kv stride not 16 bytes", dict(kv_stride=[580, 576])),
+              ("kv rows overlap", dict(kv_stride=[512, 576])), ("kv rows too far apart", dict(kv_stride=[1 << 24, 576]))]
+  sparse_calls("sparse", SPARSE, geometry + [("pool span", dict(num_rows=2000000))], dict())
+
+  # ---- the latent calls over pools counted in bytes (LATER_FORMS).  Every latent call applies the steps that its traits switch on, in ONE order:
+  #   1 ffpa_mla_fp8 (e4m3)  2 ffpa_mla_sparse in front of the plan (gather)  3 the causal copy (tree)  4 the plan  5 the page pool (page table)  6 ffpa_mla
+  #   7 the mask (tree)  8 the gathered pool's geometry (gather)  9 the e4m3 pool's strides (e4m3)
+  # Each form gets one refusal per step it has and, for every two steps that follow each other in it, one call that breaks both: the earlier step answers.
+  fp8s = [("fp8 NULL", None), ("fp8 size", dict(struct_size=8)), ("fp8 reserved", dict(reserved=1)), ("fp8 reserved2", dict(reserved2=1.0)),
+          ("kv_scale zero", dict(kv_scale=0.0)), ("kv_scale negative", dict(kv_scale=-1.0)), ("kv_scale nan", dict(kv_scale="nan")), ("kv_scale inf", dict(kv_scale="inf")),
+          ("fp8 size and kv_scale", dict(struct_size=0, kv_scale=0.0))]
+  odd_page = dict(latent_kv(), k_page_stride=64 * 576 + 8, v_page_stride=64 * 576 + 8)  # (16 bytes of a 16-bit pool, not 16 elements of an e4m3 one)
+  for form, structs in [("mla_fp8", dict(fp8=FP8)), ("mla_tree_fp8", dict(tree=TREE, fp8=FP8))]:
+    tree = "tree" in structs
+    rest = dict(structs, kv=latent_kv(), mla=MLA)
+    base = latent_params()
+    latent_calls(form, structs)  # (the plan — step 4 — through the common refusals, ffpa_mla — step 6 —, "mla NULL and pool": 5 + 6)
+    add(form, "power-of-two scale above one", base, **dict(rest, fp8=dict(kv_scale=4.0)))
+    for label, f in fp8s:  # step 1
+      add(form, "refused: " + label, base, **dict(rest, fp8=None if f is None else dict(FP8, **f)))
+    add(form, "refused: fp8 NULL and params NULL", None, **dict(rest, fp8=None))  # 1 + 3 / 4
+    add(form, "refused: kv_scale and dtype", dict(base, dtype=2), **dict(rest, fp8=dict(kv_scale=0.0)))  # 1 + 4
+    add(form, "refused: fp8 reserved and params size", dict(base, struct_size=16), **dict(rest, fp8=dict(FP8, reserved=7)))  # 1 + 3
+    for label, over in pool:  # step 5
+      add(form, "refused: " + label, base, **dict(rest, kv=dict(latent_kv(), **over)))
+    add(form, "refused: seqused_kv NULL", dict(base, seqused_kv=0), **rest)
+    add(form, "refused: kv NULL", base, **dict(rest, kv=None))
+    add(form, "refused: kv NULL and dtype", dict(base, dtype=9), **dict(rest, kv=None))  # 4 + 5
+    add(form, "refused: batch and page_size", dict(base, batch=0), **dict(rest, kv=dict(latent_kv(), page_size=96)))  # 4 + 5
+    # step 9, alone and behind the step in front of it
+    add(form, "refused: row stride not 16 elements", dict(base, k_stride=[584, 576]), **rest)
+    add(form, "refused: head stride not 16 elements", dict(base, k_stride=[576, 584]), **rest)
+    add(form, "refused: page stride not 16 elements", base, **dict(rest, kv=odd_page))
+    add(form, "refused: row stride and o NULL", dict(base, k_stride=[584, 576], o=0), **rest)  # (9 + the launch's own checks)
+    if tree:
+      for label, over in masks:  # step 7
+        accepted = label == "per-sequence masks"
+        add(form, ("" if accepted else "refused: ") + label, dict(base, max_seqlen_q=16, total_q=32), **dict(rest, tree=None if over is None else dict(TREE, **over)))
+      add(form, "not causal by the caller, several tokens", latent_params(hq=16, mq=8, causal=0), **rest)  # step 3: planned as the causal call is
+      add(form, "refused: params size and tree NULL", dict(base, struct_size=16), **dict(rest, tree=None))  # 3 / 4 + 7
+      add(form, "refused: pair not built and tokens", base, **dict(rest, mla=dict(MLA, head_dim_v=64), tree=dict(TREE, tokens=0)))  # 6 + 7
+      add(form, "refused: mla NULL and tree NULL", base, **dict(rest, mla=None, tree=None))  # 6 + 7
+      add(form, "refused: tree NULL and page stride", base, **dict(rest, kv=odd_page, tree=None))  # 7 + 9
+      add(form, "refused: tokens and row stride", dict(base, k_stride=[584, 576]), **dict(rest, tree=dict(TREE, tokens=65)))  # 7 + 9
+    else:
+      add(form, "refused: mla reserved and page stride", base, **dict(rest, kv=odd_page, mla=dict(MLA, reserved=1)))  # 6 + 9
+      add(form, "refused: pair not built and row stride", dict(base, k_stride=[584, 576]), **dict(rest, mla=dict(MLA, head_dim_v=256)))  # 6 + 9
+
+  # the gather over an e4m3 pool: strides and span in bytes, one per element
+  sparse_calls("sparse_fp8", SPARSE, geometry + [("pool span", dict(num_rows=4000000))], dict(fp8=FP8))  # (steps 2, 4, 6, 8; "max_seqlen_q and dtype": 2 + 4)
   base = sp()
-  for label, over in common_refusals():
-    add("sparse", "common: " + label, None if over is None else dict(base, **over), sparse=SPARSE)
-  add("sparse", "NULL out / buf", base, null_out=True, sparse=SPARSE)
-  for label, s in [("sparse NULL", None), ("sparse size", dict(struct_size=48)), ("sparse reserved", dict(reserved=1)), ("sparse reserved2", dict(reserved2=1)),
-                   ("topk zero", dict(topk=0)), ("num_rows zero", dict(num_rows=0)), ("indices NULL", dict(indices=0)), ("indices misaligned", dict(indices=INDICES + 2)),
-                   ("topk_lens misaligned", dict(topk_lens=LENS + 1)), ("indices_stride", dict(indices_stride=255)), ("head_dim_v zero", dict(head_dim_v=0)),
-                   ("pair not built", dict(head_dim_v=256)), ("kv stride negative", dict(kv_stride=[576, -8])), ("kv stride not 16 bytes", dict(kv_stride=[580, 576])),
-                   ("kv rows overlap", dict(kv_stride=[512, 576])), ("kv rows too far apart", dict(kv_stride=[1 << 24, 576])),
-                   ("pool span", dict(num_rows=2000000)), ("sparse size and topk", dict(struct_size=1, topk=-1)), ("indices and kv stride", dict(indices=0, kv_stride=[-1, 0]))]:
-    add("sparse", "refused: " + label, base, sparse=None if s is None else dict(SPARSE, **s))
-  add("sparse", "refused: max_seqlen_q above one", latent_params(mq=2), sparse=SPARSE)
-  add("sparse", "refused: sparse NULL and params NULL", None, sparse=None)
-  add("sparse", "refused: sparse size and params size", dict(base, struct_size=0), sparse=dict(SPARSE, struct_size=0))
-  add("sparse", "refused: max_seqlen_q and dtype", dict(base, max_seqlen_q=3, dtype=5), sparse=SPARSE)
-  add("sparse", "refused: topk and head dim", dict(base, head_dim=1), sparse=dict(SPARSE, topk=0))
-  add("sparse", "refused: pool span and q misaligned", dict(base, q=Q + 2), sparse=dict(SPARSE, num_rows=1 << 30))
+  for label, f in fp8s:  # step 1
+    add("sparse_fp8", "refused: " + label, base, sparse=SPARSE, fp8=None if f is None else dict(FP8, **f))
+  add("sparse_fp8", "power-of-two scale above one", base, sparse=SPARSE, fp8=dict(kv_scale=4.0))
+  add("sparse_fp8", "twice the rows of the 16-bit pool's reach", base, sparse=dict(SPARSE, num_rows=3000000), fp8=FP8)
+  add("sparse_fp8", "refused: fp8 NULL and sparse NULL", base, sparse=None, fp8=None)  # 1 + 2
+  add("sparse_fp8", "refused: kv_scale and topk", base, sparse=dict(SPARSE, topk=0), fp8=dict(kv_scale="nan"))  # 1 + 2
+  add("sparse_fp8", "refused: fp8 NULL and params NULL", None, sparse=SPARSE, fp8=None)  # 1 + 2
+  add("sparse_fp8", "refused: indices_stride and batch", dict(base, batch=0), sparse=dict(SPARSE, indices_stride=8), fp8=FP8)  # 2 + 4
+  add("sparse_fp8", "refused: dtype and pair not built", dict(base, dtype=2), sparse=dict(SPARSE, head_dim_v=256), fp8=FP8)  # 4 + 6
+  add("sparse_fp8", "refused: pair not built and kv stride", base, sparse=dict(SPARSE, head_dim_v=256, kv_stride=[576, -16]), fp8=FP8)  # 6 + 8
+  add("sparse_fp8", "refused: head_dim_v and pool span", base, sparse=dict(SPARSE, head_dim_v=0, num_rows=1 << 30), fp8=FP8)  # 6 + 8
+  add("sparse_fp8", "refused: row stride not 16 elements", base, sparse=dict(SPARSE, kv_stride=[584, 576]), fp8=FP8)  # step 9
+  add("sparse_fp8", "refused: head stride not 16 elements", base, sparse=dict(SPARSE, kv_stride=[576, 8]), fp8=FP8)
+  add("sparse_fp8", "refused: pool span and row stride", base, sparse=dict(SPARSE, kv_stride=[584, 576], num_rows=1 << 30), fp8=FP8)  # 8 + 9
+  add("sparse_fp8", "refused: rows overlap and head stride", base, sparse=dict(SPARSE, kv_stride=[520, 8]), fp8=FP8)  # 8 + 9
+  add("sparse_fp8", "refused: row stride and q NULL", dict(base, q=0), sparse=dict(SPARSE, kv_stride=[584, 576]), fp8=FP8)  # (9 + the launch's own checks)
+
+  # the gather over 656-byte rows: strides and span in bytes, bf16 only, the one (576, 512) row format
+  ds_geometry = [("kv stride negative", dict(kv_stride=[656, -16])), ("slot stride not 16 bytes", dict(kv_stride=[664, 656])), ("head stride not 16 bytes", dict(kv_stride=[656, 8])),
+                 ("slots overlap", dict(kv_stride=[640, 656])), ("slots too far apart", dict(kv_stride=[1 << 24, 656])), ("pool span", dict(num_rows=4000000))]
+  sparse_calls("sparse_ds", SPARSE_DS, ds_geometry, dict())  # (steps 2, 4, 6, 8; "max_seqlen_q and dtype": 2 + 4; its fp16 row: refused by step 8)
+  add("sparse_ds", "padded slots", base, sparse=dict(SPARSE_DS, kv_stride=[704, 704]))
+  add("sparse_ds", "refused: pool misaligned", dict(base, k=K + 8), sparse=SPARSE_DS)  # step 8
+  add("sparse_ds", "refused: fp16 and slot stride", dict(base, dtype=1), sparse=dict(SPARSE_DS, kv_stride=[600, 656]))  # (inside step 8: the dtype first)
+  add("sparse_ds", "refused: slot stride and pool misaligned", dict(base, k=K + 8), sparse=dict(SPARSE_DS, kv_stride=[600, 656]))
+  add("sparse_ds", "refused: indices NULL and heads", dict(base, heads_q=5, heads_kv=2), sparse=dict(SPARSE_DS, indices=0))  # 2 + 4
+  add("sparse_ds", "refused: dtype and pair not built", dict(base, dtype=2), sparse=dict(SPARSE_DS, head_dim_v=256))  # 4 + 6
+  add("sparse_ds", "refused: pair not built and slot stride", base, sparse=dict(SPARSE_DS, head_dim_v=256, kv_stride=[600, 656]))  # 6 + 8
+  add("sparse_ds", "refused: head_dim_v and fp16", dict(base, dtype=1), sparse=dict(SPARSE_DS, head_dim_v=0))  # 6 + 8
 
 
 def main(argv):
@@ -568,7 +667,7 @@ def main(argv):
     form = call.pop("form")
     if form == "packed":
       call["kv"] = None
-    merged.setdefault(json.dumps(call, sort_keys=True), (call, []))[1].append(form)
+    merged.setdefault(json.dumps(call, sort_keys=True) + str(form in LATER_FORMS), (call, []))[1].append(form)
   entries = [dict({"form": forms[0] if len(forms) == 1 else forms}, **call) for call, forms in merged.values()]
   with open(OUT, "w") as f:
     f.write("[\n" + ",\n".join(json.dumps(c, separators=(",", ":")) for c in entries) + "\n]\n")

@@ -1,7 +1,10 @@
-"""The packed call and its seven relatives (paged, tree, window, soft-cap, MLA, MLA tree, sparse) answer what tests/golden/capi_varlen_calls.json records,
+"""The packed call and its eleven relatives (paged, tree, window, soft-cap and the seven latent calls: MLA, MLA tree, sparse, and over pools counted in bytes MLA
+FP8, MLA tree FP8, sparse FP8, sparse over 656-byte rows) answer what tests/golden/capi_varlen_calls.json records,
 call by call and exactly: status and message of *_plan, the plan, the *_kernel string, *_workspace_bytes, *_compact_slots, and status and message of the
 launch export for everything it refuses before it touches the device (no GPU needed).  The list was recorded by tests/golden/make_capi_varlen_calls.py from the
-library BEFORE the host layer was rewritten around one call descriptor and one plan per call: order and wording of every refusal are pinned to that.
+library BEFORE the host layer was rewritten around one call descriptor and one plan per call: order and wording of every refusal are pinned to that.  The four forms
+over byte pools were recorded later, from the library before the seven latent families became one planner over a variant's traits; for each of them the list holds one
+refusal per step of that planner's order and, for every two steps that follow each other, one call that breaks both (the earlier step answers).
 
 One answer is not the recorded library's: *_workspace_bytes of the packed, paged and tree calls for arguments their plan refuses.  Those three sized a launch that
 the launch itself refuses (a bad pool, a bad mask); the list holds the contract instead, 0, which is what the other families always answered there."""
