@@ -122,6 +122,13 @@
 // A DMA piece and the MFMA in front of it are one asm statement (Mfma16::with_dma): the MFMA is the wait state between the M0 write and the piece,
 // no s_nop.  Interleaved A/B against separate statements, bit-identical (profiles/r04_pipe.txt): config 2 + 1.0 %, cross + 1.7 %, causal + 1.3 %, D = 320 + 1.4 %, config 4 + 0.9 %, D = 1024 +- 0
 
+// What the softmax of the single-tile builds (D <= 512) leaves out on a KV step where no row maximum grows — one bit per part, for the per-part A/B of
+// profiles/r29_softmax_diet.md: 1 = the growth test per lane, the 4-lane reduction of the row maxima only inside the rescale branch; 2 = the lane-local maximum
+// as bare v_max3_f32 / v_max_f32 instructions (m16_max_2x8 below).  Every combination computes the same bits.
+#ifndef FFPA_M16_LANE_GROW
+#define FFPA_M16_LANE_GROW 3
+#endif
+
 
 // Developer instrumentation (-DFFPA_M16_TIMING, tools/gpu_phase_times.py; never in the shipped build): every wave accumulates the shader
 // clock cycles it spends in six phases of the KV-tile loop and lane 0 writes the totals over the LSE of its first rows.
@@ -250,6 +257,37 @@ FFPA_MFMA16_NT(__bf16, "bf16")
 FFPA_MFMA16_NT(_Float16, "f16")
 #undef FFPA_MFMA16_NT
 
+// The hardware maximum without hipcc's additions.  fmaxf() on a value that comes out of an inline-asm MFMA is llvm.maxnum on an operand hipcc cannot prove free
+// of signalling NaNs: it canonicalises the operand first (v_max_f32 x, x, x) — one more VALU instruction per operand and step.  V_MAX_F32 / V_MAX3_F32
+// in IEEE mode (the ISA document's pseudo-code; compute kernels run in it): an operand that is a quiet NaN loses to the other one, exactly as in fmaxf(); a
+// signalling NaN comes back quieted where fmaxf() drops it — and no score is one: the scores are results of fp32 MFMA accumulation (arithmetic results are
+// quiet), of the soft cap's arithmetic, or the -inf a mask writes.  Only for operands written by VALU / MFMA instructions long before (ordinary VALU -> VALU
+// dependencies are interlocked; the MFMA -> VALU wait states stand behind the QK^T loop), and only in front of compiler-emitted VALU: an asm result that
+// fed a v_permlane*_swap directly would hide the VALU-write -> swap-read wait states from hipcc's hazard recogniser.
+//
+// m16_max_2x8: the lane-local maxima of BOTH row halves over two key blocks (8 scores each: p / q = the lane's 4 scores of the two blocks, 0 / 1 = the row half) in one
+// statement, the two chains interleaved.  FIRST: the chains start here; otherwise d0 / d1 carry them in.  (One statement, not one per instruction: hipcc puts an
+// s_nop between asm statements of which one reads the other's result.)
+template <bool FIRST>
+__device__ __forceinline__ void m16_max_2x8(float& d0, float& d1, const float (&p0)[4], const float (&q0)[4], const float (&p1)[4], const float (&q1)[4]) {
+  if constexpr (FIRST)
+    asm("v_max3_f32 %0, %2, %3, %4\n\tv_max3_f32 %1, %10, %11, %12\n\t"
+        "v_max3_f32 %0, %0, %5, %6\n\tv_max3_f32 %1, %1, %13, %14\n\t"
+        "v_max3_f32 %0, %0, %7, %8\n\tv_max3_f32 %1, %1, %15, %16\n\t"
+        "v_max_f32 %0, %0, %9\n\tv_max_f32 %1, %1, %17"
+        : "=&v"(d0), "=&v"(d1)
+        : "v"(p0[0]), "v"(p0[1]), "v"(p0[2]), "v"(p0[3]), "v"(q0[0]), "v"(q0[1]), "v"(q0[2]), "v"(q0[3]),
+          "v"(p1[0]), "v"(p1[1]), "v"(p1[2]), "v"(p1[3]), "v"(q1[0]), "v"(q1[1]), "v"(q1[2]), "v"(q1[3]));
+  else
+    asm("v_max3_f32 %0, %0, %2, %3\n\tv_max3_f32 %1, %1, %10, %11\n\t"
+        "v_max3_f32 %0, %0, %4, %5\n\tv_max3_f32 %1, %1, %12, %13\n\t"
+        "v_max3_f32 %0, %0, %6, %7\n\tv_max3_f32 %1, %1, %14, %15\n\t"
+        "v_max3_f32 %0, %0, %8, %9\n\tv_max3_f32 %1, %1, %16, %17"
+        : "+v"(d0), "+v"(d1)
+        : "v"(p0[0]), "v"(p0[1]), "v"(p0[2]), "v"(p0[3]), "v"(q0[0]), "v"(q0[1]), "v"(q0[2]), "v"(q0[3]),
+          "v"(p1[0]), "v"(p1[1]), "v"(p1[2]), "v"(p1[3]), "v"(q1[0]), "v"(q1[1]), "v"(q1[2]), "v"(q1[3]));
+}
+
 // A query row lives in the 4 lanes n, n + 16, n + 32, n + 48, and every lane carries a value for two rows (n and 16 + n).
 // Both 4-lane reductions together in three register swaps (no LDS crossbar): v_permlane32_swap pairs row n's halves in lanes
 // 0 .. 31 and row 16 + n's in lanes 32 .. 63, v_permlane16_swap folds the remaining lane ^ 16 step, and a last
@@ -326,7 +364,7 @@ __device__ __forceinline__ int m16_v_swizzle(int key) {
 #if defined(FFPA_M16_TIMING) || FFPA_M16_PF1 != 6 || FFPA_M16_PF2 != 4 || FFPA_M16_K_PRE != 8 || \
     FFPA_M16_K_PRE_ND2 != 64 || FFPA_M16_PF_DIST != 2 || FFPA_M16_PF_WAVES != 2 || FFPA_M16_PF_WHICH != 3 || FFPA_M16_MIN_D != 128 || FFPA_M16_BC128_MIN_D != 256 || \
     FFPA_M16_PP_VQ != 6 || FFPA_M16_PP_K1Q != 2 || FFPA_M16_PP_K2S != 2 || FFPA_M16_PP_QSTEP != 2 || \
-    FFPA_M16_PP_SSTEP != 1 || FFPA_M16_PP_PSTEP != 2 || FFPA_M16_PP_PF != 3
+    FFPA_M16_PP_SSTEP != 1 || FFPA_M16_PP_PSTEP != 2 || FFPA_M16_PP_PF != 3 || FFPA_M16_LANE_GROW != 3
 #error "FFPA_PRODUCT_BUILD: a developer switch is not at its shipped default"
 #endif
 #endif

@@ -1210,18 +1210,38 @@
     }
 
     // ================= online softmax (prefill.cuh:671-870, log2 domain) =================
+    // The single-tile builds (D <= 512) test the growth of the row maxima PER LANE and reduce over a row's 4 lanes only on a step where some maximum grew.  With
+    // the lazy rescale the reduced maximum has one reader, the test m_new > m_run + thr, whose branch is wave-wide already; and "the row's maximum passed
+    // m_run + thr" holds exactly when some lane's partial maximum did.  That rests on two facts: sc > 0 (rounding is monotonic, so fl(sc max over the lanes) = max
+    // over the lanes of fl(sc lane max): the launch side only ever passes sc > 0, see above) and thr >= 0 (so that m_new = max(m_run, t) > m_run + thr is
+    // t > m_run + thr; the launch side turns a negative rescale_threshold into the default, ffpa_capi.hip — a NaN threshold never grows, here as there).  A NaN
+    // partial maximum (every score of the lane a NaN) fails the lane's test as it loses every fmaxf() of the reduction; a lane of -inf scores (masked) never passes;
+    // on the first tile m_run + thr = -inf and any finite score passes.  A step that does not take the branch leaves m_run, l_run, P and O as the reduction would
+    // have: the results are bit-identical.  (profiles/r29_softmax_diet.md)
+    constexpr bool kDiet = ND == 1 && !kRowShare;
+    constexpr bool kLaneGrow = kDiet && (FFPA_M16_LANE_GROW & 1), kAsmMax = kDiet && (FFPA_M16_LANE_GROW & 2);
     float tmax[RHS];
+    if constexpr (kAsmMax) {
+      // (m16_max_2x8: v_max3_f32 / v_max_f32 and nothing else, no canonicalising copies of the MFMA results — its header says what that means for NaNs: nothing)
+      static_assert(!kAsmMax || (RHS == 2 && NKB % 2 == 0), "two row halves, key blocks in pairs");
+      m16_max_2x8<true>(tmax[0], tmax[RHS - 1], x[0][0], x[1][0], x[0][RHS - 1], x[1][RHS - 1]);
 #pragma unroll
-    for (int rh = 0; rh < RHS; ++rh) {
-      float t = x[0][rh][0];
+      for (int kb = 2; kb + 1 < NKB; kb += 2) m16_max_2x8<false>(tmax[0], tmax[RHS - 1], x[kb][0], x[kb + 1][0], x[kb][RHS - 1], x[kb + 1][RHS - 1]);
+    } else {
 #pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
+      for (int rh = 0; rh < RHS; ++rh) {
+        float t = x[0][rh][0];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) t = fmaxf(t, x[kb][rh][r]);
-      tmax[rh] = t;
+        for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) t = fmaxf(t, x[kb][rh][r]);
+        tmax[rh] = t;
+      }
     }
-    if constexpr (RHS == 2) row4_reduce2<true>(tmax[0], tmax[1]);
-    else row4_reduce1<true>(tmax[0]);
+    if constexpr (!kLaneGrow) {
+      if constexpr (RHS == 2) row4_reduce2<true>(tmax[0], tmax[1]);
+      else row4_reduce1<true>(tmax[0]);
+    }
 #pragma unroll
     for (int rh = 0; rh < RHS; ++rh) tmax[rh] *= a.scale_log2;  // (exact: rounding is monotonic, fl(sc max x) = max fl(sc x) for sc > 0; -inf stays -inf)
     pre_k_group(std::integral_constant<int, 2>{});
@@ -1233,9 +1253,19 @@
       l_run[0] *= alpha_own;
       m_run[0] = grow ? m_new : m_run[0];
     }
-    const float m_new0 = fmaxf(m_run[0], tmax[0]), m_new1 = fmaxf(m_run[RHS - 1], tmax[RHS - 1]);
-    const bool grow0 = !kRowShare && m_new0 > m_run[0] + a.thr, grow1 = !kRowShare && m_new1 > m_run[RHS - 1] + a.thr;
-    if (!kRowShare && __any(grow0 || grow1)) {
+    float m_new0 = fmaxf(m_run[0], tmax[0]), m_new1 = fmaxf(m_run[RHS - 1], tmax[RHS - 1]);
+    bool grow0 = !kRowShare && m_new0 > m_run[0] + a.thr, grow1 = !kRowShare && m_new1 > m_run[RHS - 1] + a.thr;
+    bool any_grow;
+    if constexpr (kLaneGrow) any_grow = __any(tmax[0] > m_run[0] + a.thr || tmax[RHS - 1] > m_run[RHS - 1] + a.thr);  // (tmax: the lane's own partial maxima)
+    else any_grow = !kRowShare && __any(grow0 || grow1);
+    if (any_grow) {
+      if constexpr (kLaneGrow) {
+        // the row maxima after all, from the scaled partial maxima (the reduction of fl(sc x) is fl(sc .) of the reduction of x, bit for bit), and the rows that grew
+        if constexpr (RHS == 2) row4_reduce2<true>(tmax[0], tmax[1]);
+        else row4_reduce1<true>(tmax[0]);
+        m_new0 = fmaxf(m_run[0], tmax[0]), m_new1 = fmaxf(m_run[RHS - 1], tmax[RHS - 1]);
+        grow0 = m_new0 > m_run[0] + a.thr, grow1 = m_new1 > m_run[RHS - 1] + a.thr;
+      }
       const float alpha0 = grow0 ? __builtin_amdgcn_exp2f(m_run[0] - m_new0) : 1.f;
       const float alpha1 = grow1 ? __builtin_amdgcn_exp2f(m_run[RHS - 1] - m_new1) : 1.f;
       if (j > t0) {
