@@ -51,29 +51,31 @@ CASES += [("two_rows_one_step", [(3, 1, 7, G_FAR), (20, 1, 12, G_FAR)]), ("two_r
           ("below_threshold", [(5, 1, 7, None)])]
 
 
-def _inputs(D, dtype, spikes, nkv=None, seed=0, heads=H, nq=NQ):
+def _inputs(D, dtype, spikes, nkv=None, seed=0, heads=H, nq=NQ, bc=None):
   """Q, K, V ~ N(0, 1) in ``dtype`` (the same for every case of a head dim), K with the case's spikes.  Returns q, k, v and the log2-domain growth of every
-  spiked row's score over the row's maximum over the other keys of tile 0."""
-  nkv = nkv or _nkv(D)
+  spiked row's score over the row's maximum over the other keys of tile 0.  ``bc``: the KV tile the spikes are laid out for (default: the dense launch's
+  ``BC[D]``; the paged builds walk 64-key tiles at every D <= 512: tests/test_kvcache_family_gpu.py)."""
+  bc = bc or BC[D]
+  nkv = nkv or 3 * bc + 5
   g = torch.Generator(device="cuda").manual_seed(1000 + D + seed)
   q = torch.randn((1, heads, nq, D), dtype=dtype, device="cuda", generator=g)
   k = torch.randn((1, heads, nkv, D), dtype=dtype, device="cuda", generator=g)
   v = torch.randn((1, heads, nkv, D), dtype=dtype, device="cuda", generator=g)
   grown = []
   for row, tile, col, gain in spikes:
-    key = tile * BC[D] + col
+    key = tile * bc + col
     assert key < nkv
     qr = q[0, :, row].double()
     norm = qr.norm(dim=-1, keepdim=True)
     if gain is None:
       # the row's running maximum behind tile 0 (natural units) + half a threshold: grows, and must not rescale
-      m0 = (qr[:, None, :] * k[0, :, :BC[D]].double()).sum(-1).max(dim=-1).values * D ** -0.5
+      m0 = (qr[:, None, :] * k[0, :, :bc].double()).sum(-1).max(dim=-1).values * D ** -0.5
       gain_h = (m0 + 0.5 * THR / LOG2E)[:, None]
     else:
       gain_h = torch.full_like(norm, gain)
     k[0, :, key] = (gain_h * math.sqrt(D) * qr / (norm * norm)).to(dtype)  # score = scale q.k = gain
     s_new = (qr * k[0, :, key].double()).sum(-1) * D ** -0.5
-    s_old = (qr[:, None, :] * k[0, :, :BC[D]].double()).sum(-1) * D ** -0.5
+    s_old = (qr[:, None, :] * k[0, :, :bc].double()).sum(-1) * D ** -0.5
     if tile == 0:
       s_old[:, col] = float("-inf")  # (a spike in tile 0 is measured against the tile's OTHER keys)
     s_old = s_old.max(dim=-1).values
