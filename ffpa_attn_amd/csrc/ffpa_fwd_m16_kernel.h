@@ -128,6 +128,17 @@
 #ifndef FFPA_M16_LANE_GROW
 #define FFPA_M16_LANE_GROW 3
 #endif
+// How the MFMA loops of the single-tile builds (D <= 512, and the un-pipelined split-D builds) deal their own LDS fragment reads between the TWO MFMA gaps of a
+// fragment pair (one fragment feeds the MFMAs of both row halves) — one bit per part, for the per-part A/B of profiles/r30_gap_budget.md: 1 = PV: of the two
+// transpose reads that request V^T fragment n + PF2, the second one sits between the pair's MFMAs; 2 = QK^T: the read of K fragment n + PF1 sits between the
+// pair's MFMAs; 4 = the pairs that carry a DMA piece are dealt the same way (the read then follows the piece; without the bit they keep every read in front of the
+// first MFMA).  Pure instruction placement: every combination issues the same reads and the same MFMAs in the same order and computes the same bits.
+// Shipped: 5.  Bit 1 takes the D = 512 PV loop from 2463 to 2270 cycles per KV step (two transpose reads and their wait in ONE gap are past what a one-wave-per-SIMD
+// wave hides: tools/probes/gap_probe.hip, PAIR rows), bit 4 makes the piece pairs obey the same rule (- 1 ... 2 cycles); bit 2 measures nothing — one read per pair
+// is inside the budget wherever it sits — and stays off.
+#ifndef FFPA_M16_GAP_SPLIT
+#define FFPA_M16_GAP_SPLIT 5
+#endif
 
 
 // Developer instrumentation (-DFFPA_M16_TIMING, tools/gpu_phase_times.py; never in the shipped build): every wave accumulates the shader
@@ -364,7 +375,8 @@ __device__ __forceinline__ int m16_v_swizzle(int key) {
 #if defined(FFPA_M16_TIMING) || FFPA_M16_PF1 != 6 || FFPA_M16_PF2 != 4 || FFPA_M16_K_PRE != 8 || \
     FFPA_M16_K_PRE_ND2 != 64 || FFPA_M16_PF_DIST != 2 || FFPA_M16_PF_WAVES != 2 || FFPA_M16_PF_WHICH != 3 || FFPA_M16_MIN_D != 128 || FFPA_M16_BC128_MIN_D != 256 || \
     FFPA_M16_PP_VQ != 6 || FFPA_M16_PP_K1Q != 2 || FFPA_M16_PP_K2S != 2 || FFPA_M16_PP_QSTEP != 2 || \
-    FFPA_M16_PP_SSTEP != 1 || FFPA_M16_PP_PSTEP != 2 || FFPA_M16_PP_PF != 3 || FFPA_M16_LANE_GROW != 3
+    FFPA_M16_PP_SSTEP != 1 || FFPA_M16_PP_PSTEP != 2 || FFPA_M16_PP_PF != 3 || FFPA_M16_LANE_GROW != 3 || \
+    FFPA_M16_GAP_SPLIT != 5
 #error "FFPA_PRODUCT_BUILD: a developer switch is not at its shipped default"
 #endif
 #endif

@@ -1037,9 +1037,12 @@
       static_for<N1>([&](auto ic) {
         constexpr int n = decltype(ic)::value;
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (n + PF1 < N1) kf[n + PF1] = k_frag(n + PF1);
         constexpr int s = n / NKB, kb = n % NKB;
         constexpr bool kPiece = n % kStep1 == 0 && n / kStep1 < PPW;
+        // the gap budget (FFPA_M16_GAP_SPLIT bit 2, an A/B arm: not shipped, it measures nothing): the read of fragment n + PF1 in the pair's SECOND gap, the first
+        // one keeps the wait (and the piece's M0 write)
+        constexpr bool kReadMid = (FFPA_M16_GAP_SPLIT & 2) && (!kPiece || (FFPA_M16_GAP_SPLIT & 4));
+        if constexpr (n + PF1 < N1 && !kReadMid) kf[n + PF1] = k_frag(n + PF1);
         // (a DMA piece sits BETWEEN the fragment's two MFMAs: + 0.4 ... 1.7 % against in front of / behind them; fused with the first one where the build allows)
         if constexpr (kPiece && kFuse && FFPA_M16_MLA_ON) {  // (MLA: the pieces of latent tile j + 1, into the other image)
           issue_k_on(std::integral_constant<int, n / kStep1>{}, k0 + BC, std::integral_constant<int, (s == 0 && !kBias) ? 0 : 1>{}, sacc[kb][0], kf[n], qf[s][0]);
@@ -1050,6 +1053,11 @@
           else M::acc(sacc[kb][0], kf[n], qf[s][0]);
         }
         if constexpr (kPiece && !kFuse) issue_v(std::integral_constant<int, n / kStep1>{}, k0);
+        if constexpr (n + PF1 < N1 && kReadMid) {
+          __builtin_amdgcn_sched_barrier(0);
+          kf[n + PF1] = k_frag(n + PF1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
         if constexpr (s == 0 && !kBias) M::first(sacc[kb][1], kf[n], qf[s][1]);
         else M::acc(sacc[kb][1], kf[n], qf[s][1]);
       });
@@ -1408,27 +1416,41 @@
         // pieces of the next step's bias tile to stage (none when that step lies in the mask's neutral interior or past the last tile)
       const int b_next = (MK == 1 && j + 1 < nt && !(k0 + BC >= free_lo && k0 + 2 * BC <= free_hi)) ? b_pieces : 0;
       const u32x4 brs = bias_rsrc();
-      v8 vf[N2];
-      auto v_frag = [&](int n) -> v8 {
+      // a V^T fragment is two transpose reads (key halves `lo` / `hi` of its 32 keys), kept apart until the MFMAs so that each can be requested on its own
+      v4 vlo[N2], vhi[N2];
+      auto v_half = [&](int n, int h) -> v4 {
         const int db = n % NDB, ks = n / NDB;
         FFPA_LDS const char* vp = vaddr[ks / 2][db % VV] + mla_img + (db / VV) * VVB + (ks % 2) * 32 * RB;
-        const v4 lo = E::tr_read(vp);
-        const v4 hi = E::tr_read(vp + 16 * RB);
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        return E::tr_read(vp + h * 16 * RB);
       };
 #pragma unroll
-      for (int n = 0; n < PF2 && n < N2; ++n) vf[n] = v_frag(n);
+      for (int n = 0; n < PF2 && n < N2; ++n) {
+        vlo[n] = v_half(n, 0);
+        vhi[n] = v_half(n, 1);
+      }
       static_for<N2>([&](auto ic) {
         constexpr int n = decltype(ic)::value;
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (n + PF2 < N2) vf[n + PF2] = v_frag(n + PF2);
         constexpr bool kPiece = n % kStep2 == 0 && n / kStep2 + kPre < PPW && !FFPA_M16_MLA_ON;  // the K(j+1) pieces that did not go out between the softmax stages (MLA: none)
+        // the gap budget (FFPA_M16_GAP_SPLIT, DESIGN.md section 3): two reads and their wait (and a piece's M0 write) in front of the first MFMA are three or
+        // four issue slots in one MFMA gap and none in the next — the `hi` read of fragment n + PF2 sits in the pair's SECOND gap
+        constexpr bool kReadMid = (FFPA_M16_GAP_SPLIT & 1) && (!kPiece || (FFPA_M16_GAP_SPLIT & 4));
+        if constexpr (n + PF2 < N2) {
+          vlo[n + PF2] = v_half(n + PF2, 0);
+          if constexpr (!kReadMid) vhi[n + PF2] = v_half(n + PF2, 1);
+        }
         constexpr int kIdx = n / kStep2 + kPre;
         constexpr int db = n % NDB, ks = n / NDB;
-        if constexpr (kPiece && kFuse) issue_k_on(std::integral_constant<int, kIdx>{}, k0 + BC, std::integral_constant<int, 2>{}, oacc[db][0], vf[n], pf[ks][0]);
-        else M::acc_a(oacc[db][0], vf[n], pf[ks][0]);
+        const v8 vfn = __builtin_shufflevector(vlo[n], vhi[n], 0, 1, 2, 3, 4, 5, 6, 7);
+        if constexpr (kPiece && kFuse) issue_k_on(std::integral_constant<int, kIdx>{}, k0 + BC, std::integral_constant<int, 2>{}, oacc[db][0], vfn, pf[ks][0]);
+        else M::acc_a(oacc[db][0], vfn, pf[ks][0]);
         if constexpr (kPiece && !kFuse) issue_k(std::integral_constant<int, kIdx>{}, k0 + BC);
-        M::acc_a(oacc[db][1], vf[n], pf[ks][1]);
+        if constexpr (n + PF2 < N2 && kReadMid) {
+          __builtin_amdgcn_sched_barrier(0);
+          vhi[n + PF2] = v_half(n + PF2, 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        M::acc_a(oacc[db][1], vfn, pf[ks][1]);
         if constexpr (MK == 1) {
           // the bias tile of step j + 1 (this wave's rows, its private staging area) in the slots the K pieces leave free
           constexpr int kBStep = kStep2 >= 2 ? kStep2 : 2;
