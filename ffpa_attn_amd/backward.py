@@ -60,6 +60,10 @@ def _aten_efficient_backward(grad_out, q, k, v, o, lse, causal, scale, attn_bias
   return dq.to(q.dtype), dk, dv, dbias
 
 
+# |LSE| from which the recompute stops trusting the saved LSE for P (an fp32 LSE of that size is spaced 2^-13 and coarser; scores of a model stay far below)
+LSE_COARSE = 1024.0
+
+
 def _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_bias, want_bias_grad,
                                 budget_bytes: int = 1 << 30, dropout=None, dlse=None):
   """dV = P^T dO;  dS = P o (dO V^T - rowsum(dO o O) + dLSE);  dQ = scale dS K;  dK = scale dS^T Q, with
@@ -99,8 +103,15 @@ def _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_b
     if causal:
       rows = torch.arange(r0, r1, device=q.device).view(-1, 1)
       s = s.masked_fill(cols > rows + (Nkv - Nq), float("-inf"))
-    p = torch.exp(s - lse[:, :, r0:r1, None])
+    lse_c = lse[:, :, r0:r1, None]
+    # A row masked on EVERY key by a large finite value (finfo.min padding rows, -1e9) has its LSE down at that value, where an fp32 LSE is spaced coarser
+    # than the log(sum) it should hold — at finfo(float32).min it absorbs it whole and exp(S - LSE) is 1 per key, not 1 / Nkv; the kernel writes -2^100 / l for
+    # a saturated row (csrc/ffpa_common.h row_lse), which is no log at all.  Such a row — |LSE| >= LSE_COARSE: no sum of attention logits gets there — takes
+    # the softmax of its own recomputed scores, the whole key row being at hand here.
+    coarse = torch.isfinite(lse_c) & (lse_c.abs() >= LSE_COARSE)
+    p = torch.exp(s - torch.where(coarse, s.amax(-1, keepdim=True), lse_c.to(s.dtype)))
     p = torch.nan_to_num(p, nan=0.0)  # fully masked rows: LSE = -inf
+    p = p * torch.where(coarse, 1.0 / p.sum(-1, keepdim=True), 1.0)
     goc = go[:, :, r0:r1]
     if dropout is None:
       dv += p.transpose(-1, -2) @ goc
@@ -159,11 +170,21 @@ def _additive_bias(attn_bias, dtype):
   return attn_bias
 
 
+def _bias_wider_than(attn_bias, dtype) -> bool:
+  """An additive bias in a wider float type than q / k / v (the public call takes fp32 next to bf16 / fp16).  The kernel added it as it is, so the saved LSE
+  belongs to the unrounded values; aten's op takes the bias in q's dtype only, and P = exp(S + round(bias) - LSE) is then off by the rounding of every entry
+  (bias ~ N(0, 2): dq / dk / dv 5.4 ... 6.1 baseline errors from float64 on MI355X, tests/test_backward_dense_family_gpu.py; finfo(float32).min becomes -inf).
+  Such a call takes the recompute, which adds the bias in fp32.  The rule is the dtype, not a lossless-conversion test: that would read the whole mask and
+  synchronise in every backward, to keep on aten only biases that happen to hold 16-bit values."""
+  return attn_bias is not None and attn_bias.is_floating_point() and attn_bias.element_size() > torch.empty((), dtype=dtype).element_size()
+
+
 def attention_backward(grad_out, q, k, v, o, lse, *, causal: bool, scale: float, attn_bias=None,
                        want_bias_grad: bool = False, force: str | None = None, dropout=None, dlse=None):
   """``(dq, dk, dv, d_attn_bias)`` for the forward ``o, lse = ffpa(q, k, v)``.  ``force`` = ``"aten"`` /
   ``"recompute"`` pins one implementation (tests); otherwise aten first (head dims up to ``ATEN_MAX_HEAD_DIM``), recompute if it refuses.  ``dlse`` (the
-  gradient of a loss that used the LSE, ``[B, Hq, Nq]``) always takes the recompute: aten's op has no such input."""
+  gradient of a loss that used the LSE, ``[B, Hq, Nq]``) always takes the recompute: aten's op has no such input.  So does an fp32 ``attn_bias`` next to 16-bit
+  q / k / v (``_bias_wider_than``)."""
   key = (q.dtype, q.size(-1))
   attn_bias = _additive_bias(attn_bias, q.dtype)
   if dropout is not None or dlse is not None:
@@ -175,6 +196,10 @@ def attention_backward(grad_out, q, k, v, o, lse, *, causal: bool, scale: float,
   if q.size(-1) > ATEN_MAX_HEAD_DIM:
     if force == "aten":
       raise NotImplementedError(f"attention_backward: aten's efficient-attention backward returns NaN for head_dim {q.size(-1)} > {ATEN_MAX_HEAD_DIM}")
+    return _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_bias, want_bias_grad)
+  if _bias_wider_than(attn_bias, q.dtype):
+    if force == "aten":
+      raise NotImplementedError(f"attention_backward: aten's efficient-attention backward takes the bias in {q.dtype} only; this one is {attn_bias.dtype}")
     return _chunked_recompute_backward(grad_out, q, k, v, o, lse, causal, scale, attn_bias, want_bias_grad)
   if force != "recompute" and not _aten_unsupported.get(key, False):
     try:
