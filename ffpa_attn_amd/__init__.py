@@ -10,7 +10,7 @@ from .flops import attention_fwd_flops, attention_valid_pairs
 from .functional import FFPAAttnMeta
 from .decode import DecodeStep
 from .interface import ffpa_attn_func, ffpa_attn_varlen_func
-from .kvcache import compact_topk_indices, ffpa_attn_varlen_with_kvcache, ffpa_attn_varlen_with_kvcache_mla, ffpa_attn_varlen_with_kvcache_mla_fp8, ffpa_attn_varlen_with_kvcache_mla_tree, ffpa_attn_varlen_with_kvcache_mla_tree_fp8, ffpa_attn_with_kvcache, ffpa_attn_with_kvcache_cascade, ffpa_attn_with_kvcache_mla, ffpa_attn_with_kvcache_mla_cascade, ffpa_attn_with_kvcache_mla_cascade_fp8, ffpa_attn_with_kvcache_mla_fp8, ffpa_attn_with_kvcache_mla_sparse, ffpa_attn_with_kvcache_mla_sparse_ds, ffpa_attn_with_kvcache_mla_sparse_fp8, ffpa_attn_with_kvcache_mla_tree, ffpa_attn_with_kvcache_mla_tree_fp8, ffpa_attn_with_kvcache_softcap, ffpa_attn_with_kvcache_tree, ffpa_attn_with_kvcache_window, ffpa_merge_attn_states, mla_cascade_rule, pack_latent_rows_ds, pack_tree_mask, quantize_latent_rows, slots_from_block_table, store_latent_rows_ds, unpack_latent_rows_ds
+from .kvcache import compact_topk_indices, ffpa_attn_varlen_with_kvcache, ffpa_attn_varlen_with_kvcache_mla, ffpa_attn_varlen_with_kvcache_mla_fp8, ffpa_attn_varlen_with_kvcache_mla_tree, ffpa_attn_varlen_with_kvcache_mla_tree_fp8, ffpa_attn_with_kvcache, ffpa_attn_with_kvcache_cascade, ffpa_attn_with_kvcache_mla, ffpa_attn_with_kvcache_mla_cascade, ffpa_attn_with_kvcache_mla_cascade_fp8, ffpa_attn_with_kvcache_mla_fp8, ffpa_attn_with_kvcache_mla_sparse, ffpa_attn_with_kvcache_mla_sparse_ds, ffpa_attn_with_kvcache_mla_sparse_fp8, ffpa_attn_with_kvcache_mla_tree, ffpa_attn_with_kvcache_mla_tree_fp8, ffpa_attn_with_kvcache_softcap, ffpa_attn_with_kvcache_tree, ffpa_attn_with_kvcache_window, ffpa_merge_attn_states, mla_cascade_rule, pack_latent_rows_ds, pack_tree_mask, quantize_latent_rows, slots_from_block_table, ffpa_mla_sparse_topk_slots, ffpa_mla_sparse_slots, store_latent_rows_ds, unpack_latent_rows_ds
 
 
 
@@ -117,6 +117,8 @@ __all__ = [
   "mla_cascade_rule",
   "compact_topk_indices",
   "slots_from_block_table",
+  "ffpa_mla_sparse_topk_slots",
+  "ffpa_mla_sparse_slots",
   "ffpa_attn_varlen_with_kvcache",
   "pack_tree_mask",
   "ffpa_merge_attn_states",

@@ -75,6 +75,8 @@ def _units() -> list[Unit]:
   for stem in MLA_VARIANTS:
     units += [Unit(f"ffpa_{stem}_inst.hip", f"ffpa_{stem}_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_d{d}", d, True, True) for d, _ in MLA_BUILDS]
   units.append(Unit("ffpa_mla_ds_store.hip", "ffpa_mla_ds_store.o", [], "temps_mla_store", None, True, True))
+  # the launch that makes the sparse calls' inputs — top-k selection over an indexer's scores and the block-table translation — one small kernel (no inline asm)
+  units.append(Unit("ffpa_mla_sparse_topk.hip", "ffpa_mla_sparse_topk.o", [], "temps_mla_sparse_topk", None, True, True))
   # the KV-cache append + rotary launch (every dtype / rotary form) and the merge of two attention states (the cascade's last launch): one small TU each, no
   # inline asm — their assembly lands in directories the attention ISA rules do not read
   units.append(Unit("ffpa_kvcache_append.hip", "ffpa_kvcache_append.o", [], "temps_append", None, True, True))

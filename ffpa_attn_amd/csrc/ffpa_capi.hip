@@ -24,6 +24,7 @@
 #include "ffpa_mla.h"           // (the MLA latent-cache kernels — the list of their variants, every variant's launcher — and the 16-bit appends)
 #include "ffpa_mla_fp8.h"       // (the e4m3 variants' fourth argument struct and the quantising appends)
 #include "ffpa_mla_sparse_ds.h"   // (the 656-byte FP8 rows of DeepSeek-V3.2: the row format, and the store that writes them)
+#include "ffpa_mla_sparse_topk.h" // (the selection launch in front of the sparse latent calls)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
 #include "ffpa_merge_states.h"    // (the merge of two attention states)
 #include "ffpa_mla_cascade_plan.h"  // (the plan launch of a shared-prefix step over the MLA latent cache)
@@ -1929,6 +1930,45 @@ int ffpa_attn_mla_ds_store(const ffpa_mla_ds_store_params* p, void* stream) {
   a.T = p->tokens, a.Hkv = p->heads_kv, a.num_rows = p->num_rows;
   const int st = ffpa::launch_mla_ds_store(a, static_cast<hipStream_t>(stream));
   if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla ds store launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
+}
+
+// ---- the launch that makes the sparse latent calls' inputs (include/ffpa_attn.h: ffpa_mla_sparse_topk_params): top-k selection and the block-table translation
+int ffpa_attn_mla_sparse_topk_slots(const ffpa_mla_sparse_topk_params* p, void* stream) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_mla_sparse_topk_params))
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_sparse_topk_params ABI mismatch: size %u (want %zu)", p->struct_size, sizeof(ffpa_mla_sparse_topk_params));
+  if (p->reserved != 0 || p->reserved2 != 0)
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_sparse_topk_params.reserved=%u / reserved2=%d must be 0", p->reserved, p->reserved2);
+  if ((p->scores != nullptr) == (p->positions != nullptr))
+    return fail(FFPA_ERR_NULL_POINTER, "exactly one of scores / positions must be non-NULL (%s are)", p->scores != nullptr ? "both" : "neither");
+  if (p->T < 0 || p->N_or_topk < 1 || p->N_or_topk > (1 << 30) || p->topk < 1)
+    return fail(FFPA_ERR_BAD_SHAPE, "T=%d must not be negative, N_or_topk=%d must lie in [1, 2^30] and topk=%d must be positive", p->T, p->N_or_topk, p->topk);
+  if (p->positions != nullptr && p->topk != p->N_or_topk)
+    return fail(FFPA_ERR_BAD_SHAPE, "positions: N_or_topk=%d must equal topk=%d", p->N_or_topk, p->topk);
+  if (p->B < 1 || (p->cu_seqlens_q == nullptr && p->T % p->B != 0))
+    return fail(FFPA_ERR_BAD_SHAPE, "B=%d must be positive and, without cu_seqlens_q, divide T=%d", p->B, p->T);
+  if (p->causal != 0 && p->causal != 1) return fail(FFPA_ERR_BAD_SHAPE, "causal=%d must be 0 or 1", p->causal);
+  if (p->block_table != nullptr && (p->page_size < 1 || p->W < 1))
+    return fail(FFPA_ERR_BAD_SHAPE, "with a block_table page_size=%d and W=%d must be positive", p->page_size, p->W);
+  if (p->row_stride < 0 || p->block_table_stride < 0 || p->indices_stride < p->topk)
+    return fail(FFPA_ERR_BAD_STRIDE, "row_stride=%lld / block_table_stride=%lld must not be negative, indices_stride=%lld not smaller than topk=%d",
+                (long long)p->row_stride, (long long)p->block_table_stride, (long long)p->indices_stride, p->topk);
+  if (p->T == 0) return FFPA_OK;
+  if (!p->cache_seqlens || !p->indices || !p->topk_lens) return fail(FFPA_ERR_NULL_POINTER, "cache_seqlens / indices / topk_lens must be non-NULL");
+  for (const void* ptr : {(const void*)p->scores, (const void*)p->positions, (const void*)p->cache_seqlens, (const void*)p->cu_seqlens_q,
+                          (const void*)p->block_table, (const void*)p->indices, (const void*)p->topk_lens})
+    if (reinterpret_cast<uintptr_t>(ptr) & 3u) return fail(FFPA_ERR_MISALIGNED, "every pointer must be 4-byte aligned");
+  int rc;
+  if ((rc = check_device()) != FFPA_OK) return rc;
+  ffpa::MlaSparseTopkArgs a;
+  memset(&a, 0, sizeof(a));
+  a.scores = p->scores, a.positions = p->positions, a.cache_seqlens = p->cache_seqlens, a.cu_seqlens_q = p->cu_seqlens_q, a.block_table = p->block_table;
+  a.indices = p->indices, a.topk_lens = p->topk_lens;
+  a.s_row = p->row_stride, a.s_table = p->block_table_stride, a.s_out = p->indices_stride;
+  a.T = p->T, a.N = p->N_or_topk, a.topk = p->topk, a.B = p->B, a.W = p->W, a.page_size = p->page_size, a.causal = p->causal;
+  const int st = ffpa::launch_mla_sparse_topk(a, static_cast<hipStream_t>(stream));
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla sparse topk launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
   return FFPA_OK;
 }
 

@@ -262,6 +262,33 @@ class FfpaMlaDsStoreParams(ctypes.Structure):
   ]
 
 
+class FfpaMlaSparseTopkParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_mla_sparse_topk_params`` (include/ffpa_attn.h): the selection launch that makes the sparse latent calls' inputs."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("scores", ctypes.c_void_p),
+    ("positions", ctypes.c_void_p),
+    ("cache_seqlens", ctypes.c_void_p),
+    ("cu_seqlens_q", ctypes.c_void_p),
+    ("block_table", ctypes.c_void_p),
+    ("indices", ctypes.c_void_p),
+    ("topk_lens", ctypes.c_void_p),
+    ("row_stride", ctypes.c_int64),
+    ("block_table_stride", ctypes.c_int64),
+    ("indices_stride", ctypes.c_int64),
+    ("T", ctypes.c_int32),
+    ("N_or_topk", ctypes.c_int32),
+    ("topk", ctypes.c_int32),
+    ("B", ctypes.c_int32),
+    ("W", ctypes.c_int32),
+    ("page_size", ctypes.c_int32),
+    ("causal", ctypes.c_int32),
+    ("reserved2", ctypes.c_int32),
+  ]
+
+
 class FfpaMlaAppendVarlenParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_mla_append_varlen_params`` (include/ffpa_attn.h): the latent append of a ragged step."""
 
@@ -493,6 +520,7 @@ _BINDINGS = (
   ("ffpa_attn_varlen_mla_sparse_ds_fwd_kernel", _MLA_SPARSE + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_ds_fwd_workspace_bytes", _MLA_SPARSE, _SIZE, 7),
   ("ffpa_attn_mla_ds_store", [_P(FfpaMlaDsStoreParams), _VOID], _INT, 7),
+  ("ffpa_attn_mla_sparse_topk_slots", [_P(FfpaMlaSparseTopkParams), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
@@ -588,7 +616,7 @@ def _stamped(cls):
   """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` / ``ffpa_window`` / ``ffpa_mla`` ride next to a versioned struct), the ABI version — filled in."""
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
-  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse, FfpaMlaFp8, FfpaMlaDsStoreParams):
+  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse, FfpaMlaFp8, FfpaMlaDsStoreParams, FfpaMlaSparseTopkParams):
     p.abi_version = ABI_VERSION
   return p
 
@@ -2144,6 +2172,70 @@ def _mla_ds_store_hip_torch_op(kv_cache, kv_new, slots):
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_ds_store_hip")
 def _mla_ds_store_fake(kv_cache, kv_new, slots):
   return None
+
+
+# The launch that makes the sparse latent calls' inputs (ffpa_mla_sparse_topk_slots / ffpa_mla_sparse_slots, ffpa_attn_amd/kvcache.py, where the arguments are checked)
+def mla_sparse_topk(rows: torch.Tensor, by_score: bool, topk: int, cache_seqlens: torch.Tensor, block_table: "torch.Tensor | None", page_size: int,
+                    cu_seqlens_q: "torch.Tensor | None", causal: bool) -> "tuple[torch.Tensor, torch.Tensor]":
+  """One launch of ``ffpa_attn_mla_sparse_topk_slots``: ``rows`` is the float32 ``scores [T, N]`` (``by_score``) or the int32 ``positions [T, topk]`` ->
+  ``(indices int32 [T, topk], topk_lens int32 [T])`` on the device.  Asynchronous, nothing read back to the host."""
+  name = "ffpa_attn::_mla_sparse_topk_slots_hip" if by_score else "ffpa_attn::_mla_sparse_slots_hip"
+  if not rows.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{rows.device.type}' (the HIP kernel needs a GPU tensor)")
+  lib = load_library()
+  T = rows.size(0)
+  indices = torch.empty((T, topk), dtype=torch.int32, device=rows.device)
+  topk_lens = torch.empty((T,), dtype=torch.int32, device=rows.device)
+  if T == 0:
+    return indices, topk_lens
+  cache_seqlens = cache_seqlens.contiguous()
+  p = _stamped(FfpaMlaSparseTopkParams)
+  if by_score:
+    p.scores = rows.data_ptr()
+  else:
+    p.positions = rows.data_ptr()
+  p.cache_seqlens, p.indices, p.topk_lens = cache_seqlens.data_ptr(), indices.data_ptr(), topk_lens.data_ptr()
+  if cu_seqlens_q is not None:
+    cu_seqlens_q = cu_seqlens_q.contiguous()
+    p.cu_seqlens_q = cu_seqlens_q.data_ptr()
+  if block_table is not None:
+    p.block_table, p.block_table_stride, p.W, p.page_size = block_table.data_ptr(), block_table.stride(0), block_table.size(1), page_size
+  p.row_stride, p.indices_stride = rows.stride(0), topk
+  p.T, p.N_or_topk, p.topk, p.B, p.causal = T, rows.size(1), topk, cache_seqlens.numel(), int(bool(causal))
+  rc = _call_on_stream(lib.ffpa_attn_mla_sparse_topk_slots, rows.device, ctypes.byref(p))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_mla_sparse_topk_slots")
+  return indices, topk_lens
+
+
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_sparse_topk_slots_hip",
+  "(Tensor scores, int topk, Tensor cache_seqlens, Tensor? block_table, int page_size, Tensor? cu_seqlens_q, bool causal) -> (Tensor indices, Tensor topk_lens)",
+)
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_sparse_slots_hip",
+  "(Tensor positions, Tensor cache_seqlens, Tensor? block_table, int page_size, Tensor? cu_seqlens_q) -> (Tensor indices, Tensor topk_lens)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_sparse_topk_slots_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_sparse_topk_slots_hip_torch_op(scores, topk, cache_seqlens, block_table, page_size, cu_seqlens_q, causal):
+  return mla_sparse_topk(scores, True, int(topk), cache_seqlens, block_table, int(page_size), cu_seqlens_q, causal)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_sparse_slots_hip", "CUDA")
+def _mla_sparse_slots_hip_torch_op(positions, cache_seqlens, block_table, page_size, cu_seqlens_q):
+  return mla_sparse_topk(positions, False, positions.size(1), cache_seqlens, block_table, int(page_size), cu_seqlens_q, False)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_topk_slots_hip")
+def _mla_sparse_topk_slots_fake(scores, topk, cache_seqlens, block_table, page_size, cu_seqlens_q, causal):
+  return scores.new_empty((scores.size(0), topk), dtype=torch.int32), scores.new_empty((scores.size(0),), dtype=torch.int32)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_slots_hip")
+def _mla_sparse_slots_fake(positions, cache_seqlens, block_table, page_size, cu_seqlens_q):
+  return torch.empty_like(positions, memory_format=torch.contiguous_format), positions.new_empty((positions.size(0),))
 
 
 # The latent append of a ragged step (ffpa_attn_varlen_with_kvcache_mla(kv=)): token rows packed by cu_seqlens_q, in front of the attention launch

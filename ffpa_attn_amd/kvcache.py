@@ -977,6 +977,124 @@ def slots_from_block_table(positions: torch.Tensor, block_table: torch.Tensor, p
   return torch.where(live, page * page_size + safe % page_size, torch.full_like(pos, -1)).to(torch.int32)
 
 
+def _mla_sparse_select_check(name, rows, what, dtype, topk, cache_seqlens, block_table, page_size, cu_seqlens_q) -> int:
+  """The argument checks of ``ffpa_mla_sparse_topk_slots`` / ``ffpa_mla_sparse_slots`` under their own ``name`` (``rows``: the scores or the positions, ``what``
+  its name) -> ``page_size`` as the op takes it (1 without a table).  ``TypeError`` for types and dtypes, ``NotImplementedError`` for a tensor that requires grad,
+  ``ValueError`` for shapes, devices and strides; nothing is read from the device."""
+  tensors = ((what, rows), ("cache_seqlens", cache_seqlens)) + ((("block_table", block_table),) if block_table is not None else ()) + \
+            ((("cu_seqlens_q", cu_seqlens_q),) if cu_seqlens_q is not None else ())
+  for nm, t in tensors:
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  if rows.dtype != dtype:
+    raise TypeError(f"{name}: {what} must be {dtype}, got {rows.dtype}" + (" (bf16 / fp16 scores are not served: hand over .float())" if rows.is_floating_point() else ""))
+  for nm, t in tensors[1:]:
+    if t.dtype != torch.int32:
+      raise TypeError(f"{name}: {nm} must be an int32 tensor, got {t.dtype}")
+  if isinstance(topk, bool) or not isinstance(topk, int):
+    raise TypeError(f"{name}: topk must be an int, got {topk!r}")
+  if block_table is not None and (isinstance(page_size, bool) or not isinstance(page_size, int)):
+    raise TypeError(f"{name}: with a block_table page_size must be an int, got {page_size!r}")
+  if rows.dim() != 2 or rows.size(1) < 1:
+    raise ValueError(f"{name}: {what} must be [T, {'N' if what == 'scores' else 'topk'}] with at least one column, got {tuple(rows.shape)}")
+  T, N = rows.shape
+  if topk < 1 or topk > N:
+    raise ValueError(f"{name}: topk must lie in [1, N={N}], got {topk}")
+  if N > 1 << 30:
+    raise ValueError(f"{name}: rows of more than 2^30 columns are not served, got {N}")
+  if rows.stride(1) != 1:
+    raise ValueError(f"{name}: {what} must have a contiguous last dimension (the row stride is free)")
+  if cache_seqlens.dim() != 1 or cache_seqlens.numel() < 1:
+    raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [B] with B >= 1, got {tuple(cache_seqlens.shape)}")
+  B = cache_seqlens.numel()
+  if cu_seqlens_q is not None and (cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() != B + 1):
+    raise ValueError(f"{name}: cu_seqlens_q must be an int32 tensor [B + 1 = {B + 1}], got {tuple(cu_seqlens_q.shape)}")
+  if cu_seqlens_q is None and T % B != 0:
+    raise ValueError(f"{name}: without cu_seqlens_q the T={T} rows are [B, Sq] flattened: T must be a multiple of B={B}")
+  if block_table is not None:
+    if page_size < 1:
+      raise ValueError(f"{name}: page_size must be a positive int, got {page_size!r}")
+    if block_table.dim() != 2 or block_table.size(0) != B or block_table.size(1) < 1:
+      raise ValueError(f"{name}: block_table must be [B={B}, pages_per_seq >= 1] — one row per SEQUENCE —, got {tuple(block_table.shape)}")
+    if block_table.stride(1) != 1:
+      raise ValueError(f"{name}: block_table must have a contiguous last dimension (the row stride is free)")
+  for nm, t in tensors[1:]:
+    if t.device != rows.device:
+      raise ValueError(f"{name}: {nm} must be on {what}'s device, got {t.device} and {rows.device}")
+  return page_size if block_table is not None else 1
+
+
+def ffpa_mla_sparse_topk_slots(
+  scores: torch.Tensor,
+  topk: int,
+  cache_seqlens: torch.Tensor,
+  block_table: "torch.Tensor | None" = None,
+  page_size: "int | None" = None,
+  *,
+  cu_seqlens_q: "torch.Tensor | None" = None,
+  causal: bool = True,
+) -> "tuple[torch.Tensor, torch.Tensor]":
+  """From an indexer's scores to the inputs of the sparse latent calls, in ONE launch: ``scores`` — float32 ``[T, N]`` on the GPU, unit stride in the last
+  dimension, free row stride; column ``p`` is the score of logical key position ``p`` of the token's sequence — -> ``(indices int32 [T, topk], topk_lens int32
+  [T])``, exactly the pair ``ffpa_attn_with_kvcache_mla_sparse`` / ``_sparse_fp8`` / ``_sparse_ds`` take, on the device (SGLang's ``fast_topk_transform_fused``,
+  vLLM's ``top_k_per_row`` + ``convert_req_index_to_global_index``).  It replaces ``torch.topk``, a per-token table gather, ``slots_from_block_table`` and
+  ``compact_topk_indices`` — about a dozen launches, two of them sorts — in front of every layer's attention.
+
+  Token -> sequence: ``cu_seqlens_q`` (int32 ``[B + 1]``) packs the rows as the ragged latent calls do — rows at and past ``cu_seqlens_q[B]`` are padding: count
+  0, a row of -1 —; without it ``T % B == 0``, ``Sq = T // B`` and row ``t`` is token ``t % Sq`` of sequence ``t // Sq``.  ``cache_seqlens``: int32 ``[B]``, the
+  lengths WITH the step's rows in the cache (the sparse call has no ``kv=``).  Token ``i`` of a sequence of ``S`` query tokens and length ``L`` sees the columns
+  ``[0, n)``, ``n = clamp(L - (S - 1 - i), 0, N)`` under ``causal`` (the bottom-right alignment of every ragged call here), ``clamp(L, 0, N)`` otherwise; columns
+  at and past ``n`` are never selected, whatever they hold.
+
+  The selection is a pure function of its inputs: ``n <= topk`` selects all of ``0 ... n - 1``; otherwise the ``topk`` largest of the first ``n`` scores in the
+  order of ``torch.sort(descending=True, stable=True)`` — NaN counts as the largest value, -0.0 equals +0.0, among equal scores the lower position wins.  The
+  selected positions are written in ASCENDING position order (the pages are walked front to back; with ``n <= topk`` the row lists the sequence's slots in order,
+  the case in which the sparse call returns the dense latent call's bits), entries at and past the count are -1, ``topk_lens[t] = min(n, topk)``.  ``topk``: a
+  host int in ``[1, N]``, no power-of-two requirement.
+
+  Translation: position ``p`` of sequence ``b`` becomes ``block_table[b, min(p // page_size, W - 1)] * page_size + p % page_size`` — ``block_table`` int32
+  ``[B, W]``, one row per SEQUENCE (not per token, as ``slots_from_block_table`` wants it), free row stride; ``page_size`` any positive int.  ``block_table=None``
+  writes the positions themselves.  Page ids are not validated: the sparse call clamps slots into the pool.
+
+  One HIP kernel, a workgroup per row (a long row is not split over workgroups); nothing is read back to the host, so the call captures into a HIP graph in front
+  of the sparse call and a replay follows ``scores``, ``cache_seqlens``, ``cu_seqlens_q`` and ``block_table`` written in place.  ``T == 0`` returns empty tensors
+  and launches nothing.  Not served: bf16 scores (``TypeError``), per-head index rows."""
+  name = "ffpa_mla_sparse_topk_slots"
+  page_size = _mla_sparse_select_check(name, scores, "scores", torch.float32, topk, cache_seqlens, block_table, page_size, cu_seqlens_q)
+  from . import hip  # noqa: F401  (registers the ffpa_attn ops)
+
+  if scores.size(0) == 0:
+    return scores.new_empty((0, topk), dtype=torch.int32), scores.new_empty((0,), dtype=torch.int32)
+  return torch.ops.ffpa_attn._mla_sparse_topk_slots_hip(scores, topk, cache_seqlens, block_table, page_size, cu_seqlens_q, bool(causal))
+
+
+def ffpa_mla_sparse_slots(
+  positions: torch.Tensor,
+  cache_seqlens: torch.Tensor,
+  block_table: "torch.Tensor | None" = None,
+  page_size: "int | None" = None,
+  *,
+  cu_seqlens_q: "torch.Tensor | None" = None,
+) -> "tuple[torch.Tensor, torch.Tensor]":
+  """``ffpa_mla_sparse_topk_slots``'s last phase for an engine that keeps its own top-k: ``positions`` — int32 ``[T, topk]`` on the GPU, logical key positions
+  with negative entries ("no key") anywhere in a row — -> ``(indices int32 [T, topk], topk_lens int32 [T])``: the entries ``>= 0`` keep their order and move to the
+  front, translated through the sequence's row of ``block_table`` (as there; ``None``: as they are), the count is their number, the tail is -1.  On the front
+  entries and the counts that is ``compact_topk_indices(slots_from_block_table(positions, block_table[sequence of each token], page_size))`` in ONE launch of the
+  same kernel, with the table indexed per sequence on the device.  Token -> sequence is ``ffpa_mla_sparse_topk_slots``'s rule (``cu_seqlens_q``, or ``T % B == 0``;
+  padding rows: count 0, a row of -1); ``cache_seqlens`` (int32 ``[B]``) names the sequences — no length is applied, the caller's top-k has chosen visible keys.
+  Nothing is read back to the host; ``T == 0`` returns empty tensors and launches nothing."""
+  name = "ffpa_mla_sparse_slots"
+  topk = positions.size(1) if isinstance(positions, torch.Tensor) and positions.dim() == 2 and positions.size(1) >= 1 else 1
+  page_size = _mla_sparse_select_check(name, positions, "positions", torch.int32, topk, cache_seqlens, block_table, page_size, cu_seqlens_q)
+  from . import hip  # noqa: F401  (registers the ffpa_attn ops)
+
+  if positions.size(0) == 0:
+    return positions.new_empty((0, topk)), positions.new_empty((0,))
+  return torch.ops.ffpa_attn._mla_sparse_slots_hip(positions, cache_seqlens, block_table, page_size, cu_seqlens_q)
+
+
 def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=False, ds=False):
   """The argument checks of the sparse latent calls under their own ``name``, every rule written once and in the order ``ffpa_attn_with_kvcache_mla_sparse`` has
   always made them -> ``(T, Hq)``.  ``fp8``: the pool is ``torch.float8_e4m3fn`` (``ffpa_attn_with_kvcache_mla_sparse_fp8``) — the dtype rule is the FP8 latent

@@ -700,6 +700,51 @@ typedef struct ffpa_mla_ds_store_params {
 int ffpa_attn_mla_ds_store(const ffpa_mla_ds_store_params* p, void* stream);
 
 /*
+ * THE INPUTS OF THE SPARSE LATENT CALLS, MADE ON THE DEVICE — from an indexer's float32 score per (query token, logical key position) to (indices [T, topk],
+ * topk_lens [T]) of ffpa_mla_sparse, in ONE kernel on `stream`, a workgroup per token row.  Exactly one of `scores` and `positions` is non-NULL.
+ *   Token t -> (sequence b, token i of its S): cu_seqlens_q [B + 1] and the ragged calls' binary search (rows at and past cu_seqlens_q[B] are padding: count 0, a
+ *     row of -1), or — cu_seqlens_q NULL — T % B == 0, S = T / B, b = t / S, i = t % S.
+ *   scores [T, N_or_topk] (row_stride in elements, unit stride inside a row): token t sees the columns [0, n), n = clamp(cache_seqlens[b] - (S - 1 - i), 0, N)
+ *     with `causal`, clamp(cache_seqlens[b], 0, N) without; columns at and past n are never selected, whatever they hold.  n <= topk: all of [0, n) are selected.
+ *     Otherwise the topk largest in the order of a stable descending sort in which NaN is the largest value, -0.0 equals +0.0 and, among equal scores, the
+ *     lower position wins.  The selected positions are written in ASCENDING position order; topk_lens[t] = min(n, topk).
+ *   positions [T, topk] (N_or_topk == topk): the entries >= 0 keep their order and move to the front; topk_lens[t] is their number.  cache_seqlens is not read
+ *     for a length here (the caller's own top-k has applied it).
+ *   Either way position p of sequence b is written as block_table[b * block_table_stride + min(p / page_size, W - 1)] * page_size + p % page_size (int32, page
+ *     ids not validated: the sparse call clamps slots into the pool) — block_table NULL: as p itself —, and the entries at and past the count are -1.
+ * Nothing is read back: the launch captures into a graph in front of the sparse call.  Checks, in this order: p NULL (FFPA_ERR_NULL_POINTER); struct_size,
+ * reserved (FFPA_ERR_BAD_ABI); both or neither of scores / positions (FFPA_ERR_NULL_POINTER); T < 0, N_or_topk outside [1, 2^30], topk < 1, positions with
+ * topk != N_or_topk, B < 1, T % B != 0 without cu_seqlens_q, causal outside {0, 1}, and — with a block_table — page_size < 1 or W < 1 (FFPA_ERR_BAD_SHAPE);
+ * negative strides, indices_stride < topk (FFPA_ERR_BAD_STRIDE); then, T > 0: cache_seqlens / indices / topk_lens NULL (FFPA_ERR_NULL_POINTER), a pointer not
+ * 4-byte aligned (FFPA_ERR_MISALIGNED), the device.
+ */
+typedef struct ffpa_mla_sparse_topk_params {
+  uint32_t struct_size;          /* sizeof(ffpa_mla_sparse_topk_params), checked */
+  uint32_t reserved;             /* 0, checked */
+  const float* scores;           /* device [T, N_or_topk] float32, or NULL */
+  const int32_t* positions;      /* device [T, topk] int32, or NULL */
+  const int32_t* cache_seqlens;  /* device [B]: the lengths with the step's rows in the cache */
+  const int32_t* cu_seqlens_q;   /* device [B + 1], or NULL: T / B tokens per sequence */
+  const int32_t* block_table;    /* device [B, W], or NULL: positions are written as they are */
+  int32_t* indices;              /* device [T, topk], written */
+  int32_t* topk_lens;            /* device [T], written */
+  int64_t row_stride;            /* elements: rows of scores / positions */
+  int64_t block_table_stride;    /* elements: rows of block_table */
+  int64_t indices_stride;        /* elements: rows of indices (>= topk) */
+  int32_t T;                     /* >= 0 */
+  int32_t N_or_topk;             /* columns of scores / of positions */
+  int32_t topk;
+  int32_t B;
+  int32_t W;                     /* columns of block_table */
+  int32_t page_size;
+  int32_t causal;                /* 0 / 1 */
+  int32_t reserved2;             /* 0, checked */
+} ffpa_mla_sparse_topk_params;
+
+/* Launch the selection on `stream` of the CURRENT device.  Asynchronous; every bad argument returns a status before any device work.  Returns an ffpa_status. */
+int ffpa_attn_mla_sparse_topk_slots(const ffpa_mla_sparse_topk_params* p, void* stream);
+
+/*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
  * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
  *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position

@@ -1,6 +1,7 @@
 """Per-kernel register / scratch statistics from the --save-temps assembly (python -m ffpa_attn_amd.build --save-temps).
 
-Usage: python tools/isa_stats.py [D ...]     (default: every head dim found)
+Usage: python tools/isa_stats.py [D ...]     (default: every head dim found; an argument that is not a number names a small unit's directory,
+                                              e.g. mla_sparse_topk for temps_mla_sparse_topk)
 Prints, per kernel instantiation: VGPRs, AGPRs, SGPRs, scratch bytes, and how many scratch / v_readlane
 instructions sit inside the KV-tile loop (between the first and the last MFMA of the kernel).
 """
@@ -13,7 +14,7 @@ ROOT = os.environ.get("FFPA_ISA_ROOT") or os.path.join(os.path.dirname(os.path.a
 def isa_files(d):
   """The device assembly of head dim d's TU: kept gzip-compressed by ffpa_attn_amd.build (10 : 1 — the repo snapshot travels to the GPU box on every
   run), plain while a developer build (tools/dev_compile.sh) is being looked at."""
-  base = os.path.join(ROOT, f"temps_d{d}")
+  base = os.path.join(ROOT, f"temps_d{d}" if str(d).isdigit() else f"temps_{d}")
   return glob.glob(os.path.join(base, "*gfx950.s")) or glob.glob(os.path.join(base, "*gfx950.s.gz"))
 
 
