@@ -1509,6 +1509,84 @@ ffpa::MlaAppendArgs mla_append_args(const void* kv_new, void* cache, const int* 
   return a;
 }
 
+// What the two K / V appends — of a [B, S] step (ffpa_kv_append_params) and of a ragged one (ffpa_kv_append_varlen_params) — check and fill alike; P is either
+// struct: the fields read here have one name in both.  The exports keep their own checks between these, in the order tests/golden/capi_append_calls.json holds.
+extern "C++" {  // (templates: this file's helpers stand inside the header's extern "C")
+template <class P>
+int check_kv_append_dims(const P* p) {
+  if (p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
+  if (p->batch <= 0 || p->heads_q <= 0 || p->heads_kv <= 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "non-positive dimension: batch=%d Hq=%d Hkv=%d", p->batch, p->heads_q, p->heads_kv);
+  if (p->heads_q % p->heads_kv != 0) return fail(FFPA_ERR_BAD_SHAPE, "num_heads: Hq=%d is not a multiple of Hkv=%d", p->heads_q, p->heads_kv);
+  if (p->head_dim <= 0 || p->head_dim % 8 != 0 || p->head_dim > 1024)
+    return fail(FFPA_ERR_BAD_HEADDIM, "headdim not support! D=%d (supported: multiples of 8 in [8, 1024])", p->head_dim);
+  return FFPA_OK;
+}
+
+// The pool (or the slab's capacity) and the rotary tables against it -> *cap, the keys a sequence can hold.
+template <class P>
+int check_kv_append_cache(const P* p, const ffpa_paged_kv* kv, int* cap) {
+  *cap = p->capacity;
+  if (kv != nullptr) {
+    const int rc = check_pool(kv);
+    if (rc != FFPA_OK) return rc;
+    *cap = kv->pages_per_row * kv->page_size;
+  } else if (*cap <= 0) {
+    return fail(FFPA_ERR_BAD_SHAPE, "capacity=%d of the contiguous cache must be positive", *cap);
+  }
+  const int rd = p->rotary_dim;
+  if (rd < 0 || rd % 16 != 0 || rd > p->head_dim)
+    return fail(FFPA_ERR_BAD_SHAPE, "rotary_dim=%d must be a multiple of 16 in [0, head_dim=%d]", rd, p->head_dim);
+  if (rd > 0 && p->seqlen_ro < *cap) return fail(FFPA_ERR_BAD_SHAPE, "seqlen_ro=%d rows of rotary_cos / rotary_sin is less than the capacity %d", p->seqlen_ro, *cap);
+  return FFPA_OK;
+}
+
+// Base pointers and strides of what the launch reads: the caches always, k / v, q / q_rot and the tables where it uses them; `n`: the strides of a row tensor.
+template <class P>
+int check_kv_append_layout(const P* p, bool use_kv, bool use_q, bool use_rot, int n) {
+  if (!aligned16(p->k_cache) || !aligned16(p->v_cache) || (use_kv && (!aligned16(p->k) || !aligned16(p->v))) ||
+      (use_q && (!aligned16(p->q) || !aligned16(p->q_rot))) || (use_rot && (!aligned16(p->rotary_cos) || !aligned16(p->rotary_sin))))
+    return fail(FFPA_ERR_MISALIGNED, "q / k / v / caches / q_rot / rotary_cos / rotary_sin base pointers must be 16-byte aligned");
+  int rc;
+  if ((rc = check_strides("k_cache", p->k_cache_stride, 3)) || (rc = check_strides("v_cache", p->v_cache_stride, 3))) return rc;
+  if (use_kv && ((rc = check_strides("k", p->k_stride, n)) || (rc = check_strides("v", p->v_stride, n)))) return rc;
+  if (use_q && ((rc = check_strides("q", p->q_stride, n)) || (rc = check_strides("q_rot", p->q_rot_stride, n)))) return rc;
+  return FFPA_OK;
+}
+
+// Everything of KvAppendArgs but the token rows' own (their strides, Sq / Snew, T), and the workgroups per token row of a grid of `grid_rows` token rows.
+template <class P>
+unsigned fill_kv_append(ffpa::KvAppendArgs& a, const P* p, const ffpa_paged_kv* kv, int cap, int64_t grid_rows, bool* interleaved) {
+  a.q = p->q, a.k = p->k, a.v = p->v;
+  a.kc = p->k_cache, a.vc = p->v_cache, a.q_rot = p->q_rot;
+  a.used = p->seqused, a.seqlens = p->cache_seqlens;
+  a.cos = p->rotary_cos, a.sin = p->rotary_sin;
+  a.skc[0] = p->k_cache_stride[1], a.skc[1] = p->k_cache_stride[2];
+  a.svc[0] = p->v_cache_stride[1], a.svc[1] = p->v_cache_stride[2];
+  if (kv != nullptr) {
+    a.table = kv->block_table, a.bt_stride = kv->bt_stride;
+    a.kc_page_stride = kv->k_page_stride, a.vc_page_stride = kv->v_page_stride;
+    a.page_size = kv->page_size, a.num_pages = kv->num_pages;
+  } else {
+    // one page per sequence: the slab of sequence b
+    a.kc_page_stride = p->k_cache_stride[0], a.vc_page_stride = p->v_cache_stride[0];
+    a.page_size = cap, a.num_pages = p->batch;
+  }
+  const int rd = p->rotary_dim;
+  a.B = p->batch, a.Hq = p->heads_q, a.Hkv = p->heads_kv, a.D = p->head_dim;
+  a.cap = cap, a.seqlen_ro = p->seqlen_ro, a.rd = rd, a.causal = p->causal ? 1 : 0;
+  *interleaved = rd == 0 || p->rotary_interleaved != 0;
+  a.units = *interleaved ? p->head_dim / 8 : rd / 16 + (p->head_dim - rd) / 8;
+  a.slots = 256 / a.units;
+  const int heads = rd > 0 ? std::max(p->heads_q, p->heads_kv) : p->heads_kv;
+  // workgroups per token row: as few as let a lane walk kAppendHeadsPerLane heads with one set of cos / sin registers — but a decode batch has few token
+  // rows (32 x 1 token: 32 workgroups on 256 CUs at D = 512), so spread the heads over up to one per lane until the grid covers the CUs
+  const int per_wg = a.slots * ffpa::kAppendHeadsPerLane;
+  const int64_t fill = ((int64_t)device_cu_count() + grid_rows - 1) / grid_rows;
+  return (unsigned)std::max((heads + per_wg - 1) / per_wg, (int)std::min<int64_t>((heads + a.slots - 1) / a.slots, fill));
+}
+}  // extern "C++"
+
 // Plan the call, then launch the plan: the checks every family shares (in front of the device), the argument blocks, the append in front of a latent launch, the
 // kernel, the merge behind a split one.
 int varlen_launch(const VarlenCall& c, void* stream) {
@@ -2037,25 +2115,11 @@ int ffpa_attn_kvcache_append(const ffpa_kv_append_params* p, const ffpa_paged_kv
   if (p->struct_size != sizeof(ffpa_kv_append_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
     return fail(FFPA_ERR_BAD_ABI, "ffpa_kv_append_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size, sizeof(ffpa_kv_append_params),
                 p->abi_version, FFPA_ATTN_ABI_VERSION);
-  if (p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
-  if (p->batch <= 0 || p->heads_q <= 0 || p->heads_kv <= 0)
-    return fail(FFPA_ERR_BAD_SHAPE, "non-positive dimension: batch=%d Hq=%d Hkv=%d", p->batch, p->heads_q, p->heads_kv);
-  if (p->heads_q % p->heads_kv != 0) return fail(FFPA_ERR_BAD_SHAPE, "num_heads: Hq=%d is not a multiple of Hkv=%d", p->heads_q, p->heads_kv);
-  if (p->head_dim <= 0 || p->head_dim % 8 != 0 || p->head_dim > 1024)
-    return fail(FFPA_ERR_BAD_HEADDIM, "headdim not support! D=%d (supported: multiples of 8 in [8, 1024])", p->head_dim);
+  int rc, cap;
+  if ((rc = check_kv_append_dims(p)) != FFPA_OK) return rc;
   if (p->seqlen_q < 0 || p->seqlen_new < 0) return fail(FFPA_ERR_BAD_SHAPE, "seqlen_q=%d / seqlen_new=%d must not be negative", p->seqlen_q, p->seqlen_new);
-  int rc;
-  int cap = p->capacity;
-  if (kv != nullptr) {
-    if ((rc = check_pool(kv)) != FFPA_OK) return rc;
-    cap = kv->pages_per_row * kv->page_size;
-  } else if (cap <= 0) {
-    return fail(FFPA_ERR_BAD_SHAPE, "capacity=%d of the contiguous cache must be positive", cap);
-  }
+  if ((rc = check_kv_append_cache(p, kv, &cap)) != FFPA_OK) return rc;
   const int rd = p->rotary_dim;
-  if (rd < 0 || rd % 16 != 0 || rd > p->head_dim)
-    return fail(FFPA_ERR_BAD_SHAPE, "rotary_dim=%d must be a multiple of 16 in [0, head_dim=%d]", rd, p->head_dim);
-  if (rd > 0 && p->seqlen_ro < cap) return fail(FFPA_ERR_BAD_SHAPE, "seqlen_ro=%d rows of rotary_cos / rotary_sin is less than the capacity %d", p->seqlen_ro, cap);
   const bool use_q = rd > 0 && p->seqlen_q > 0, use_kv = p->seqlen_new > 0;
   const bool use_rot = rd > 0 && (use_q || use_kv);  // (the tables are read for every rotated q row AND every appended K row)
   if (!p->k_cache || !p->v_cache || !p->seqused || !p->cache_seqlens)
@@ -2067,46 +2131,18 @@ int ffpa_attn_kvcache_append(const ffpa_kv_append_params* p, const ffpa_paged_kv
   if (p->seqused == p->cache_seqlens) return fail(FFPA_ERR_BAD_SHAPE, "seqused must not be cache_seqlens (the kernel reads one while it writes the other)");
   if ((reinterpret_cast<uintptr_t>(p->seqused) & 3u) || (reinterpret_cast<uintptr_t>(p->cache_seqlens) & 3u))
     return fail(FFPA_ERR_MISALIGNED, "seqused / cache_seqlens must be 4-byte aligned");
-  if (!aligned16(p->k_cache) || !aligned16(p->v_cache) || (use_kv && (!aligned16(p->k) || !aligned16(p->v))) ||
-      (use_q && (!aligned16(p->q) || !aligned16(p->q_rot))) || (use_rot && (!aligned16(p->rotary_cos) || !aligned16(p->rotary_sin))))
-    return fail(FFPA_ERR_MISALIGNED, "q / k / v / caches / q_rot / rotary_cos / rotary_sin base pointers must be 16-byte aligned");
-  if ((rc = check_strides("k_cache", p->k_cache_stride, 3)) || (rc = check_strides("v_cache", p->v_cache_stride, 3))) return rc;
-  if (use_kv && ((rc = check_strides("k", p->k_stride, 3)) || (rc = check_strides("v", p->v_stride, 3)))) return rc;
-  if (use_q && ((rc = check_strides("q", p->q_stride, 3)) || (rc = check_strides("q_rot", p->q_rot_stride, 3)))) return rc;
+  if ((rc = check_kv_append_layout(p, use_kv, use_q, use_rot, 3)) != FFPA_OK) return rc;
   const int rows = std::max(1, std::max(p->seqlen_new, rd > 0 ? p->seqlen_q : 0));
   if ((int64_t)p->batch * rows > 0x7fffffffLL) return fail(FFPA_ERR_BAD_SHAPE, "grid of %lld token rows is too large", (long long)p->batch * rows);
   if ((rc = check_device()) != FFPA_OK) return rc;
 
   ffpa::KvAppendArgs a;
   memset(&a, 0, sizeof(a));
-  a.q = p->q, a.k = p->k, a.v = p->v;
-  a.kc = p->k_cache, a.vc = p->v_cache, a.q_rot = p->q_rot;
-  a.used = p->seqused, a.seqlens = p->cache_seqlens;
-  a.cos = p->rotary_cos, a.sin = p->rotary_sin;
+  bool interleaved;
+  const unsigned grid_y = fill_kv_append(a, p, kv, cap, (int64_t)p->batch * rows, &interleaved);
   for (int i = 0; i < 3; ++i) a.sq[i] = p->q_stride[i], a.sk[i] = p->k_stride[i], a.sv[i] = p->v_stride[i], a.sqr[i] = p->q_rot_stride[i];
-  a.skc[0] = p->k_cache_stride[1], a.skc[1] = p->k_cache_stride[2];
-  a.svc[0] = p->v_cache_stride[1], a.svc[1] = p->v_cache_stride[2];
-  if (kv != nullptr) {
-    a.table = kv->block_table, a.bt_stride = kv->bt_stride;
-    a.kc_page_stride = kv->k_page_stride, a.vc_page_stride = kv->v_page_stride;
-    a.page_size = kv->page_size, a.num_pages = kv->num_pages;
-  } else {
-    // one page per sequence: the slab of sequence b
-    a.kc_page_stride = p->k_cache_stride[0], a.vc_page_stride = p->v_cache_stride[0];
-    a.page_size = cap, a.num_pages = p->batch;
-  }
-  a.B = p->batch, a.Hq = p->heads_q, a.Hkv = p->heads_kv, a.D = p->head_dim, a.Sq = p->seqlen_q, a.Snew = p->seqlen_new;
-  a.cap = cap, a.seqlen_ro = p->seqlen_ro, a.rd = rd, a.causal = p->causal ? 1 : 0, a.T = rows;
-  const bool interleaved = rd == 0 || p->rotary_interleaved != 0;
-  a.units = interleaved ? p->head_dim / 8 : rd / 16 + (p->head_dim - rd) / 8;
-  a.slots = 256 / a.units;
-  const int heads = rd > 0 ? std::max(p->heads_q, p->heads_kv) : p->heads_kv;
-  // workgroups per token row: as few as let a lane walk kAppendHeadsPerLane heads with one set of cos / sin registers — but a decode batch has few token
-  // rows (32 x 1 token: 32 workgroups on 256 CUs at D = 512), so spread the heads over up to one per lane until the grid covers the CUs
-  const int per_wg = a.slots * ffpa::kAppendHeadsPerLane;
-  const int64_t fill = ((int64_t)device_cu_count() + (int64_t)p->batch * rows - 1) / ((int64_t)p->batch * rows);
-  const int grid_y = std::max((heads + per_wg - 1) / per_wg, (int)std::min<int64_t>((heads + a.slots - 1) / a.slots, fill));
-  const int st = ffpa::launch_kv_append(p->dtype, interleaved, a, (unsigned)grid_y, static_cast<hipStream_t>(stream));
+  a.Sq = p->seqlen_q, a.Snew = p->seqlen_new, a.T = rows;
+  const int st = ffpa::launch_kv_append(p->dtype, interleaved, a, grid_y, static_cast<hipStream_t>(stream));
   if (st != 0) return fail(FFPA_ERR_LAUNCH, "kv append launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
   return FFPA_OK;
 }
@@ -2117,25 +2153,11 @@ int ffpa_attn_kvcache_append_varlen(const ffpa_kv_append_varlen_params* p, const
   if (p->struct_size != sizeof(ffpa_kv_append_varlen_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
     return fail(FFPA_ERR_BAD_ABI, "ffpa_kv_append_varlen_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size,
                 sizeof(ffpa_kv_append_varlen_params), p->abi_version, FFPA_ATTN_ABI_VERSION);
-  if (p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
-  if (p->batch <= 0 || p->heads_q <= 0 || p->heads_kv <= 0)
-    return fail(FFPA_ERR_BAD_SHAPE, "non-positive dimension: batch=%d Hq=%d Hkv=%d", p->batch, p->heads_q, p->heads_kv);
-  if (p->heads_q % p->heads_kv != 0) return fail(FFPA_ERR_BAD_SHAPE, "num_heads: Hq=%d is not a multiple of Hkv=%d", p->heads_q, p->heads_kv);
-  if (p->head_dim <= 0 || p->head_dim % 8 != 0 || p->head_dim > 1024)
-    return fail(FFPA_ERR_BAD_HEADDIM, "headdim not support! D=%d (supported: multiples of 8 in [8, 1024])", p->head_dim);
+  int rc, cap;
+  if ((rc = check_kv_append_dims(p)) != FFPA_OK) return rc;
   if (p->total_q < 0) return fail(FFPA_ERR_BAD_SHAPE, "total_q=%d must not be negative", p->total_q);
-  int rc;
-  int cap = p->capacity;
-  if (kv != nullptr) {
-    if ((rc = check_pool(kv)) != FFPA_OK) return rc;
-    cap = kv->pages_per_row * kv->page_size;
-  } else if (cap <= 0) {
-    return fail(FFPA_ERR_BAD_SHAPE, "capacity=%d of the contiguous cache must be positive", cap);
-  }
+  if ((rc = check_kv_append_cache(p, kv, &cap)) != FFPA_OK) return rc;
   const int rd = p->rotary_dim;
-  if (rd < 0 || rd % 16 != 0 || rd > p->head_dim)
-    return fail(FFPA_ERR_BAD_SHAPE, "rotary_dim=%d must be a multiple of 16 in [0, head_dim=%d]", rd, p->head_dim);
-  if (rd > 0 && p->seqlen_ro < cap) return fail(FFPA_ERR_BAD_SHAPE, "seqlen_ro=%d rows of rotary_cos / rotary_sin is less than the capacity %d", p->seqlen_ro, cap);
   const bool rows = p->total_q > 0, use_rot = rd > 0 && rows;
   if (!p->k_cache || !p->v_cache || !p->seqused || !p->cache_seqlens || !p->cu_seqlens_q)
     return fail(FFPA_ERR_NULL_POINTER, "k_cache / v_cache / seqused / cache_seqlens / cu_seqlens_q must be non-NULL");
@@ -2148,46 +2170,18 @@ int ffpa_attn_kvcache_append_varlen(const ffpa_kv_append_varlen_params* p, const
   if ((reinterpret_cast<uintptr_t>(p->seqused) & 3u) || (reinterpret_cast<uintptr_t>(p->cache_seqlens) & 3u) ||
       (reinterpret_cast<uintptr_t>(p->cu_seqlens_q) & 3u) || (reinterpret_cast<uintptr_t>(p->positions) & 3u))
     return fail(FFPA_ERR_MISALIGNED, "seqused / cache_seqlens / cu_seqlens_q / positions must be 4-byte aligned");
-  if (!aligned16(p->k_cache) || !aligned16(p->v_cache) || (rows && (!aligned16(p->k) || !aligned16(p->v))) ||
-      (use_rot && (!aligned16(p->q) || !aligned16(p->q_rot) || !aligned16(p->rotary_cos) || !aligned16(p->rotary_sin))))
-    return fail(FFPA_ERR_MISALIGNED, "q / k / v / caches / q_rot / rotary_cos / rotary_sin base pointers must be 16-byte aligned");
-  if ((rc = check_strides("k_cache", p->k_cache_stride, 3)) || (rc = check_strides("v_cache", p->v_cache_stride, 3))) return rc;
-  if (rows && ((rc = check_strides("k", p->k_stride, 2)) || (rc = check_strides("v", p->v_stride, 2)))) return rc;
-  if (use_rot && ((rc = check_strides("q", p->q_stride, 2)) || (rc = check_strides("q_rot", p->q_rot_stride, 2)))) return rc;
+  if ((rc = check_kv_append_layout(p, rows, use_rot, use_rot, 2)) != FFPA_OK) return rc;
   if ((rc = check_device()) != FFPA_OK) return rc;
 
   ffpa::KvAppendVarlenArgs va;
   memset(&va, 0, sizeof(va));
   ffpa::KvAppendArgs& a = va.a;
-  a.q = p->q, a.k = p->k, a.v = p->v;
-  a.kc = p->k_cache, a.vc = p->v_cache, a.q_rot = p->q_rot;
-  a.used = p->seqused, a.seqlens = p->cache_seqlens;
-  a.cos = p->rotary_cos, a.sin = p->rotary_sin;
+  bool interleaved;
+  const unsigned grid_y = fill_kv_append(a, p, kv, cap, std::max(1, p->total_q), &interleaved);
   va.cu_q = p->cu_seqlens_q, va.positions = p->positions;
   for (int i = 0; i < 2; ++i) a.sq[i + 1] = p->q_stride[i], a.sk[i + 1] = p->k_stride[i], a.sv[i + 1] = p->v_stride[i], a.sqr[i + 1] = p->q_rot_stride[i];
-  a.skc[0] = p->k_cache_stride[1], a.skc[1] = p->k_cache_stride[2];
-  a.svc[0] = p->v_cache_stride[1], a.svc[1] = p->v_cache_stride[2];
-  if (kv != nullptr) {
-    a.table = kv->block_table, a.bt_stride = kv->bt_stride;
-    a.kc_page_stride = kv->k_page_stride, a.vc_page_stride = kv->v_page_stride;
-    a.page_size = kv->page_size, a.num_pages = kv->num_pages;
-  } else {
-    // one page per sequence: the slab of sequence b
-    a.kc_page_stride = p->k_cache_stride[0], a.vc_page_stride = p->v_cache_stride[0];
-    a.page_size = cap, a.num_pages = p->batch;
-  }
-  a.B = p->batch, a.Hq = p->heads_q, a.Hkv = p->heads_kv, a.D = p->head_dim;
-  a.cap = cap, a.seqlen_ro = p->seqlen_ro, a.rd = rd, a.causal = p->causal ? 1 : 0, a.T = p->total_q;
-  const bool interleaved = rd == 0 || p->rotary_interleaved != 0;
-  a.units = interleaved ? p->head_dim / 8 : rd / 16 + (p->head_dim - rd) / 8;
-  a.slots = 256 / a.units;
-  const int heads = rd > 0 ? std::max(p->heads_q, p->heads_kv) : p->heads_kv;
-  // workgroups per token row: the [B, S] append's rule (few token rows: spread a row's heads over up to one per lane until the grid covers the CUs)
-  const int per_wg = a.slots * ffpa::kAppendHeadsPerLane;
-  const int64_t grid_rows = std::max(1, p->total_q);
-  const int64_t fill = ((int64_t)device_cu_count() + grid_rows - 1) / grid_rows;
-  const int grid_y = std::max((heads + per_wg - 1) / per_wg, (int)std::min<int64_t>((heads + a.slots - 1) / a.slots, fill));
-  const int st = ffpa::launch_kv_append_varlen(p->dtype, interleaved, va, (unsigned)grid_y, static_cast<hipStream_t>(stream));
+  a.T = p->total_q;
+  const int st = ffpa::launch_kv_append_varlen(p->dtype, interleaved, va, grid_y, static_cast<hipStream_t>(stream));
   if (st != 0) return fail(FFPA_ERR_LAUNCH, "kv append (varlen) launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
   return FFPA_OK;
 }

@@ -1521,7 +1521,8 @@ def _varlen_fwd_hip_torch_op(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, 
 
 
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_varlen_fwd_hip")
-def _varlen_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, softmax_scale, causal, rescale_threshold=-1.0, seqused_k=None):
+def _packed_out_fake(q, *args, **kwargs):
+  """The fake of the five attention ops over packed q (packed, paged, tree, window, softcap): ``q [T, Hq, D]`` -> ``(o [T, Hq, D], lse [Hq, T] fp32)``."""
   total_q, heads, head_dim = q.shape
   return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
 
@@ -1540,10 +1541,7 @@ def _paged_fwd_hip_torch_op(q, k, v, cu_seqlens_q, seqused_k, block_table, max_s
                         rescale_threshold=rescale_threshold, return_lse=True, seqused_k=seqused_k, num_splits=num_splits, block_table=block_table)
 
 
-@torch.library.register_fake(f"{_OP_NAMESPACE}::_paged_fwd_hip")
-def _paged_fwd_hip_fake(q, k, v, cu_seqlens_q, seqused_k, block_table, max_seqlen_q, max_seqlen_k, softmax_scale, causal, rescale_threshold=-1.0, num_splits=0):
-  total_q, heads, head_dim = q.shape
-  return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
+torch.library.register_fake(f"{_OP_NAMESPACE}::_paged_fwd_hip", _packed_out_fake)
 
 
 # The tree-mask call (ffpa_attn_with_kvcache_tree): one op for both caches — ``block_table`` None = the contiguous cache as packed rows + ``cu_seqlens_k``
@@ -1561,11 +1559,7 @@ def _tree_fwd_hip_torch_op(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block
                       return_lse=True, seqused_k=seqused_k, num_splits=num_splits, block_table=block_table)
 
 
-@torch.library.register_fake(f"{_OP_NAMESPACE}::_tree_fwd_hip")
-def _tree_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, tree_words, max_seqlen_q, max_seqlen_k, softmax_scale,
-                       rescale_threshold=-1.0, num_splits=0):
-  total_q, heads, head_dim = q.shape
-  return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
+torch.library.register_fake(f"{_OP_NAMESPACE}::_tree_fwd_hip", _packed_out_fake)
 
 
 # The sliding-window call (ffpa_attn_with_kvcache_window): one op for both caches, shaped like the tree call's — ``block_table`` None = the contiguous cache
@@ -1583,11 +1577,7 @@ def _window_fwd_hip_torch_op(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, blo
                         rescale_threshold=rescale_threshold, return_lse=True, seqused_k=seqused_k, num_splits=num_splits, block_table=block_table)
 
 
-@torch.library.register_fake(f"{_OP_NAMESPACE}::_window_fwd_hip")
-def _window_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, window_left, window_right, max_seqlen_q, max_seqlen_k, softmax_scale,
-                         causal, rescale_threshold=-1.0, num_splits=0):
-  total_q, heads, head_dim = q.shape
-  return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
+torch.library.register_fake(f"{_OP_NAMESPACE}::_window_fwd_hip", _packed_out_fake)
 
 
 # The soft-capping call (ffpa_attn_with_kvcache_softcap): the window call's op with the cap — ``block_table`` None = the contiguous cache, (-1, -1) = no window
@@ -1607,11 +1597,7 @@ def _softcap_fwd_hip_torch_op(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, bl
                          block_table=block_table)
 
 
-@torch.library.register_fake(f"{_OP_NAMESPACE}::_softcap_fwd_hip")
-def _softcap_fwd_hip_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, block_table, softcap, window_left, window_right, max_seqlen_q, max_seqlen_k,
-                          softmax_scale, causal, rescale_threshold=-1.0, num_splits=0):
-  total_q, heads, head_dim = q.shape
-  return q.new_empty((total_q, heads, head_dim)), q.new_empty((heads, total_q), dtype=torch.float32)
+torch.library.register_fake(f"{_OP_NAMESPACE}::_softcap_fwd_hip", _packed_out_fake)
 
 
 # The MLA latent-cache call (ffpa_attn_with_kvcache_mla): ONE pool whose rows are the keys and, in their first ``head_dim_v`` columns, the values
@@ -2334,48 +2320,40 @@ def _mla_fp8_append_varlen_hip_fake(kv_cache, kv_new, kv_scale, cu_seqlens_q, ca
 
 
 # The KV-cache append + rotary (ffpa_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)): the prepare launch in front of the attention launch
-def kvcache_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: "torch.Tensor | None", v: "torch.Tensor | None", cache_seqlens: torch.Tensor,
-                   block_table: "torch.Tensor | None" = None, rotary_cos: "torch.Tensor | None" = None, rotary_sin: "torch.Tensor | None" = None,
-                   rotary_interleaved: bool = True, causal: bool = False):
-  """One launch of ``ffpa_attn_kvcache_append``: ``k`` / ``v [B, Snew, Hkv, D]`` written into the caches in place at ``cache_seqlens[b] + i`` (``k`` rotated when
-  ``rotary_cos`` / ``rotary_sin [seqlen_ro, rotary_dim / 2]`` are given), -> ``(q_rot, seqused)``: ``q [B, Sq, Hq, D]`` rotated (an empty tensor without rotary) and
-  the int32 ``[B]`` post-append lengths ``min(max(cache_seqlens, 0) + Snew, capacity)``.  Contiguous caches ``[B, capacity, Hkv, D]``, or page pools
-  ``[num_pages, page_size, Hkv, D]`` with ``block_table``.  Asynchronous, nothing read back to the host."""
-  name = "ffpa_attn::_kvcache_append_hip"
+def _kvcache_append(name: str, export: str, p, B: int, new_rows: int, q, k_cache, v_cache, k, v, cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved,
+                    causal):
+  """What the two appends share — every field ``ffpa_kv_append_params`` and ``ffpa_kv_append_varlen_params`` have in common, the outputs and the call of ``export``.
+  ``p``: the export's params with the caller's own fields set (the tensors behind its pointers alive in the caller); ``q`` / ``k`` / ``v``: token rows ``[B, S, H, D]`` or
+  packed ``[T, H, D]`` — a row tensor hands over every stride but its last; ``new_rows``: the rows ``k`` / ``v`` hold per sequence (uniform) or in all (ragged)."""
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
-  B, Sq, Hq, D = q.shape
-  Hkv = k_cache.size(2)
   rot = rotary_cos is not None
-  q_rot = torch.empty((B, Sq, Hq, D) if rot else (0,), dtype=q.dtype, device=q.device)
+  q_rot = torch.empty(tuple(q.shape) if rot else (0,), dtype=q.dtype, device=q.device)
   seqused = torch.empty((B,), dtype=torch.int32, device=q.device)
-  if B == 0:
+  if B <= 0:
     return q_rot, seqused
   for nm, t in (("k_cache", k_cache), ("v_cache", v_cache)):
     if not _layout_ok(t):
       raise ValueError(f"{name}: {nm} is written in place and needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base")
-  if k is None:
-    k = v = q.new_empty((B, 0, Hkv, D))
   k, v = _rows(k), _rows(v)
   if rot:
     q = _rows(q)
   cache_seqlens = cache_seqlens.contiguous()
-  p = _stamped(FfpaKvAppendParams)
+  n = q.dim() - 1
   p.k_cache, p.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
   p.seqused, p.cache_seqlens = seqused.data_ptr(), cache_seqlens.data_ptr()
-  p.batch, p.heads_q, p.heads_kv, p.head_dim = B, Hq, Hkv, D
-  p.seqlen_q, p.seqlen_new = Sq, k.size(1)
+  p.batch, p.heads_q, p.heads_kv, p.head_dim = B, q.size(-2), k_cache.size(2), q.size(-1)
   p.k_cache_stride[:] = list(k_cache.stride()[:3])
   p.v_cache_stride[:] = list(v_cache.stride()[:3])
-  if k.size(1) > 0:
+  if new_rows > 0:
     p.k, p.v = k.data_ptr(), v.data_ptr()
-    p.k_stride[:] = list(k.stride()[:3])
-    p.v_stride[:] = list(v.stride()[:3])
+    p.k_stride[:] = list(k.stride()[:n])
+    p.v_stride[:] = list(v.stride()[:n])
   if rot:
     p.q, p.q_rot = q.data_ptr(), q_rot.data_ptr()
-    p.q_stride[:] = list(q.stride()[:3])
-    p.q_rot_stride[:] = list(q_rot.stride()[:3])
+    p.q_stride[:] = list(q.stride()[:n])
+    p.q_rot_stride[:] = list(q_rot.stride()[:n])
     p.rotary_cos, p.rotary_sin = rotary_cos.data_ptr(), rotary_sin.data_ptr()
     p.seqlen_ro = rotary_cos.size(0)
     p.rotary_dim = 2 * rotary_cos.size(1)
@@ -2387,10 +2365,26 @@ def kvcache_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor
     kv, block_table = _paged_kv_of(block_table, k_cache, v_cache)
   else:
     p.capacity = k_cache.size(1)
-  rc = _call_on_stream(lib.ffpa_attn_kvcache_append, q.device, ctypes.byref(p), ctypes.byref(kv) if kv is not None else None)
+  rc = _call_on_stream(getattr(lib, export), q.device, ctypes.byref(p), ctypes.byref(kv) if kv is not None else None)
   if rc != 0:
-    _raise_status(lib, rc, "ffpa_attn_kvcache_append")
+    _raise_status(lib, rc, export)
   return q_rot, seqused
+
+
+def kvcache_append(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k: "torch.Tensor | None", v: "torch.Tensor | None", cache_seqlens: torch.Tensor,
+                   block_table: "torch.Tensor | None" = None, rotary_cos: "torch.Tensor | None" = None, rotary_sin: "torch.Tensor | None" = None,
+                   rotary_interleaved: bool = True, causal: bool = False):
+  """One launch of ``ffpa_attn_kvcache_append``: ``k`` / ``v [B, Snew, Hkv, D]`` written into the caches in place at ``cache_seqlens[b] + i`` (``k`` rotated when
+  ``rotary_cos`` / ``rotary_sin [seqlen_ro, rotary_dim / 2]`` are given), -> ``(q_rot, seqused)``: ``q [B, Sq, Hq, D]`` rotated (an empty tensor without rotary) and
+  the int32 ``[B]`` post-append lengths ``min(max(cache_seqlens, 0) + Snew, capacity)``.  Contiguous caches ``[B, capacity, Hkv, D]``, or page pools
+  ``[num_pages, page_size, Hkv, D]`` with ``block_table``.  Asynchronous, nothing read back to the host."""
+  B, Sq = q.shape[:2]
+  if k is None:
+    k = v = q.new_empty((B, 0, k_cache.size(2), q.size(-1)))
+  p = _stamped(FfpaKvAppendParams)
+  p.seqlen_q, p.seqlen_new = Sq, k.size(1)
+  return _kvcache_append("ffpa_attn::_kvcache_append_hip", "ffpa_attn_kvcache_append", p, B, k.size(1), q, k_cache, v_cache, k, v, cache_seqlens, block_table, rotary_cos,
+                         rotary_sin, rotary_interleaved, causal)
 
 
 # k_cache / v_cache are written in place: the schema says so (Tensor(a!) / Tensor(b!)), so that functionalization and torch.compile see the writes
@@ -2421,57 +2415,14 @@ def kvcache_append_varlen(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
   ``positions[t]`` with the int32 ``positions [T]``) -> ``(q_rot, seqused)``: ``q`` rotated (an empty tensor without rotary) and the int32 ``[B]`` post-append lengths
   ``min(max(cache_seqlens, 0) + Sq_b, capacity)``.  Contiguous caches ``[B, capacity, Hkv, D]``, or page pools with ``block_table``.  Token rows at or past
   ``cu_seqlens_q[B]`` write nothing.  Asynchronous, nothing read back to the host."""
-  name = "ffpa_attn::_kvcache_append_varlen_hip"
-  if not q.is_cuda:
-    raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
-  lib = load_library()
-  T, Hq, D = q.shape
-  Hkv = k_cache.size(2)
-  B = cu_seqlens_q.numel() - 1
-  rot = rotary_cos is not None
-  q_rot = torch.empty((T, Hq, D) if rot else (0,), dtype=q.dtype, device=q.device)
-  seqused = torch.empty((B,), dtype=torch.int32, device=q.device)
-  if B <= 0:
-    return q_rot, seqused
-  for nm, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-    if not _layout_ok(t):
-      raise ValueError(f"{name}: {nm} is written in place and needs head-dim stride 1, strides that are multiples of 8 elements and a 16-byte aligned base")
-  k, v = _rows(k), _rows(v)
-  if rot:
-    q = _rows(q)
-  cache_seqlens, cu_seqlens_q = cache_seqlens.contiguous(), cu_seqlens_q.contiguous()
+  cu_seqlens_q = cu_seqlens_q.contiguous()
   p = _stamped(FfpaKvAppendVarlenParams)
-  p.k_cache, p.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
-  p.seqused, p.cache_seqlens, p.cu_seqlens_q = seqused.data_ptr(), cache_seqlens.data_ptr(), cu_seqlens_q.data_ptr()
-  p.batch, p.heads_q, p.heads_kv, p.head_dim, p.total_q = B, Hq, Hkv, D, T
-  p.k_cache_stride[:] = list(k_cache.stride()[:3])
-  p.v_cache_stride[:] = list(v_cache.stride()[:3])
-  if T > 0:
-    p.k, p.v = k.data_ptr(), v.data_ptr()
-    p.k_stride[:] = list(k.stride()[:2])
-    p.v_stride[:] = list(v.stride()[:2])
-  if rot:
-    p.q, p.q_rot = q.data_ptr(), q_rot.data_ptr()
-    p.q_stride[:] = list(q.stride()[:2])
-    p.q_rot_stride[:] = list(q_rot.stride()[:2])
-    p.rotary_cos, p.rotary_sin = rotary_cos.data_ptr(), rotary_sin.data_ptr()
-    p.seqlen_ro = rotary_cos.size(0)
-    p.rotary_dim = 2 * rotary_cos.size(1)
-    p.rotary_interleaved = 1 if rotary_interleaved else 0
-    if positions is not None:
-      positions = positions.contiguous()
-      p.positions = positions.data_ptr()
-  p.causal = 1 if causal else 0
-  p.dtype = _DTYPE[q.dtype]
-  kv = None
-  if block_table is not None:
-    kv, block_table = _paged_kv_of(block_table, k_cache, v_cache)
-  else:
-    p.capacity = k_cache.size(1)
-  rc = _call_on_stream(lib.ffpa_attn_kvcache_append_varlen, q.device, ctypes.byref(p), ctypes.byref(kv) if kv is not None else None)
-  if rc != 0:
-    _raise_status(lib, rc, "ffpa_attn_kvcache_append_varlen")
-  return q_rot, seqused
+  p.cu_seqlens_q, p.total_q = cu_seqlens_q.data_ptr(), q.size(0)
+  if rotary_cos is not None and positions is not None:
+    positions = positions.contiguous()
+    p.positions = positions.data_ptr()
+  return _kvcache_append("ffpa_attn::_kvcache_append_varlen_hip", "ffpa_attn_kvcache_append_varlen", p, cu_seqlens_q.numel() - 1, q.size(0), q, k_cache, v_cache, k, v,
+                         cache_seqlens, block_table, rotary_cos, rotary_sin, rotary_interleaved, causal)
 
 
 torch.library.define(

@@ -42,14 +42,12 @@ import torch
 _DTYPES = (torch.float16, torch.bfloat16)
 
 
-def _unsupported(k, v, rotary_cos, rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes) -> list[str]:
-  names = []
-  append = k is not None and v is not None
-  rotary = rotary_cos is not None and rotary_sin is not None
-  for name, value, ok in (("k", k, append), ("v", v, append), ("rotary_cos", rotary_cos, rotary and append), ("rotary_sin", rotary_sin, rotary and append),
-                          ("cache_batch_idx", cache_batch_idx, False), ("cache_leftpad", cache_leftpad, False)):
-    if value is not None and not ok:
-      names.append(name)
+_UNIFORM, _RAGGED = "ffpa_attn_with_kvcache", "ffpa_attn_varlen_with_kvcache"  # the names the five uniform calls and the ragged call speak under
+
+
+def _unsupported(cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes) -> list[str]:
+  """The options of ffpa_attn_with_kvcache's signature that no kernel serves, where the caller has set them."""
+  names = [name for name, value in (("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad)) if value is not None]
   if window_size is None or tuple(window_size) != (-1, -1):
     names.append("window_size")
   if softcap not in (None, 0, 0.0):
@@ -59,141 +57,209 @@ def _unsupported(k, v, rotary_cos, rotary_sin, cache_batch_idx, cache_leftpad, w
   return names
 
 
-def _check_append(q, k_cache, k, v, rotary_cos, rotary_sin, capacity: int) -> None:
-  """Host-side checks of the new keys and the rotary tables (shapes, dtypes, devices: nothing read from the device)."""
-  B, Sq, Hq, D = q.shape
-  Hkv = k_cache.size(2)
-  for name, t in (("k", k), ("v", v)):
-    if not isinstance(t, torch.Tensor):
-      raise TypeError(f"ffpa_attn_with_kvcache: {name} must be a tensor, got {type(t).__name__}")
-    if t.requires_grad and torch.is_grad_enabled():
-      raise NotImplementedError(f"ffpa_attn_with_kvcache is inference only: {name} requires grad and there is no backward")
-    if t.dtype != q.dtype:
-      raise TypeError(f"ffpa_attn_with_kvcache: {name} must have the cache's dtype {q.dtype}, got {t.dtype}")
-    if t.device != q.device:
-      raise ValueError(f"ffpa_attn_with_kvcache: {name} must be on q's device, got {t.device} and {q.device}")
-    if t.dim() != 4 or t.size(0) != B or t.size(2) != Hkv or t.size(3) != D:
-      raise ValueError(f"ffpa_attn_with_kvcache: {name} must be [B={B}, Snew, Hkv={Hkv}, D={D}], got {tuple(t.shape)}")
-    if t.stride(-1) != 1:
-      raise ValueError(f"ffpa_attn_with_kvcache: {name} must have a contiguous last dimension")
-  if k.shape != v.shape:
-    raise ValueError(f"ffpa_attn_with_kvcache: k {tuple(k.shape)} and v {tuple(v.shape)} must share their shape")
-  if rotary_cos is None:
-    return
-  for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
-    if not isinstance(t, torch.Tensor):
-      raise TypeError(f"ffpa_attn_with_kvcache: {name} must be a tensor, got {type(t).__name__}")
-    if t.dtype != q.dtype:
-      raise TypeError(f"ffpa_attn_with_kvcache: {name} must have q's dtype {q.dtype}, got {t.dtype}")
-    if t.device != q.device:
-      raise ValueError(f"ffpa_attn_with_kvcache: {name} must be on q's device, got {t.device} and {q.device}")
-    if t.dim() != 2 or not t.is_contiguous():
-      raise ValueError(f"ffpa_attn_with_kvcache: {name} must be a contiguous [seqlen_ro, rotary_dim / 2] tensor, got {tuple(t.shape)}")
-  if rotary_cos.shape != rotary_sin.shape:
-    raise ValueError(f"ffpa_attn_with_kvcache: rotary_cos {tuple(rotary_cos.shape)} and rotary_sin {tuple(rotary_sin.shape)} must share their shape")
-  rotary_dim = 2 * rotary_cos.size(1)
-  if rotary_dim == 0 or rotary_dim % 16 != 0 or rotary_dim > D:
-    raise ValueError(f"ffpa_attn_with_kvcache: rotary_dim ({rotary_dim}) must be a positive multiple of 16 and at most the head dim ({D})")
-  if rotary_cos.size(0) < capacity:
-    raise ValueError(f"ffpa_attn_with_kvcache: rotary_cos / rotary_sin have {rotary_cos.size(0)} rows (seqlen_ro), fewer than the cache capacity {capacity}")
+def _kv_check(name, q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, block_table, softmax_scale, num_splits, unserved=(), ragged=None):
+  """Every host-side check of the six calls (nothing read from the device, nothing launched), every rule written once, in the order the uniform calls (``ragged``
+  None; ``unserved``: what ``_unsupported`` named) and the ragged call (``ragged = (cu_seqlens_q, max_seqlen_q, positions)``) make them
+  -> ``(batch, capacity, the key lengths as an int32 [B] device tensor, softmax scale)``.  The two orders differ, and tests/golden/kv_front_calls.json holds both:
+  the uniform calls test tensor and grad per tensor, ``cache_seqlens`` behind the caches and the grad of ``k`` / ``v`` with their other rules; the ragged call tests
+  every tensor, then every grad, and ``cu_seqlens_q`` / ``max_seqlen_q`` / ``cache_seqlens`` in front of the caches."""
+  from . import hip  # noqa: F401 (registers the ffpa_attn ops the step calls)
 
-
-def _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, cache_batch_idx, cache_leftpad, block_table, softmax_scale, window_size,
-              softcap, alibi_slopes, num_splits):
-  """Every host-side check of ffpa_attn_with_kvcache (nothing read from the device, nothing launched) -> (capacity, seqused, softmax scale)."""
-  bad = _unsupported(k, v, rotary_cos, rotary_sin, cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes)
+  append = k is not None and v is not None
+  rotary = append and rotary_cos is not None and rotary_sin is not None
+  bad = [nm for nm, t, ok in (("k", k, append), ("v", v, append), ("rotary_cos", rotary_cos, rotary), ("rotary_sin", rotary_sin, rotary)) if t is not None and not ok]
+  if ragged is None:
+    bad += unserved
+    served = "; no leftpad, batch index, local window, softcap or ALiBi"
+  else:
+    cu_seqlens_q, max_seqlen_q, positions = ragged
+    bad += ["positions"] if positions is not None and not rotary else []
+    served = ", positions only with the rotary tables"
   if bad:
-    raise NotImplementedError(f"ffpa_attn_with_kvcache does not support: {', '.join(bad)} (k and v only together, rotary_cos and rotary_sin only together "
-                              "and with k / v; no leftpad, batch index, local window, softcap or ALiBi)")
-  for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
-    if not isinstance(t, torch.Tensor):
-      raise TypeError(f"ffpa_attn_with_kvcache: {name} must be a tensor, got {type(t).__name__}")
-    if t.requires_grad and torch.is_grad_enabled():
-      raise NotImplementedError(f"ffpa_attn_with_kvcache is inference only: {name} requires grad and there is no backward")
+    raise NotImplementedError(f"{name} does not support: {', '.join(bad)} (k and v only together, rotary_cos and rotary_sin only together and with k / v{served})")
+  caches = (("q", q), ("k_cache", k_cache), ("v_cache", v_cache))
+  if ragged is None:  # (tensor and grad, tensor by tensor; k / v below)
+    for nm, t in caches:
+      if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+      if t.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  else:  # (every tensor, then every grad)
+    for nm, t in caches + (("cu_seqlens_q", cu_seqlens_q), ("cache_seqlens", cache_seqlens)):
+      if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+    for nm, t in caches + (("k", k), ("v", v)):
+      if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
   if q.dtype not in _DTYPES or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-    raise TypeError(f"ffpa_attn_with_kvcache only supports fp16/bf16 q/k_cache/v_cache of one dtype, got {q.dtype}, {k_cache.dtype}, {v_cache.dtype}")
-  if q.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
-    raise ValueError("ffpa_attn_with_kvcache: q must be [B, Sq, Hq, D] and k_cache / v_cache 4-D")
+    raise TypeError(f"{name} only supports fp16/bf16 q/k_cache/v_cache of one dtype, got {q.dtype}, {k_cache.dtype}, {v_cache.dtype}")
+  if q.dim() != (4 if ragged is None else 3) or k_cache.dim() != 4 or v_cache.dim() != 4:
+    raise ValueError(f"{name}: q must be {'[B, Sq, Hq, D]' if ragged is None else 'packed [T, Hq, D]'} and k_cache / v_cache 4-D")
   if k_cache.shape != v_cache.shape:
-    raise ValueError(f"ffpa_attn_with_kvcache: k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} must share their shape")
-  B, Sq, Hq, D = q.shape
+    raise ValueError(f"{name}: k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} must share their shape")
+  shape = q.shape  # (read once: every .size() is a call into torch)
+  rows, Hq, D = shape[0], shape[-2], shape[-1]  # (rows: B of a uniform call, T of the ragged one)
   Hkv = k_cache.size(2)
   if k_cache.size(3) != D:
-    raise ValueError(f"ffpa_attn_with_kvcache: head dim of the cache ({k_cache.size(3)}) differs from q's ({D})")
+    raise ValueError(f"{name}: head dim of the cache ({k_cache.size(3)}) differs from q's ({D})")
   if D % 8 != 0 or D > 1024 or D <= 0:
-    raise ValueError(f"ffpa_attn_with_kvcache: head dim {D} is not a multiple of 8 in [8, 1024]")
+    raise ValueError(f"{name}: head dim {D} is not a multiple of 8 in [8, 1024]")
   if Hkv == 0 or Hq % Hkv != 0:
-    raise ValueError(f"ffpa_attn_with_kvcache: query num_heads ({Hq}) must be a multiple of key/value num_heads ({Hkv})")
+    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of key/value num_heads ({Hkv})")
   if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
-    raise ValueError(f"ffpa_attn_with_kvcache: num_splits must be a non-negative int, got {num_splits!r}")
+    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
+  if ragged is None:
+    B = rows
+  else:
+    if cu_seqlens_q.dtype != torch.int32:
+      raise TypeError(f"{name}: cu_seqlens_q must be int32, got {cu_seqlens_q.dtype}")
+    if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.stride(0) != 1 or cu_seqlens_q.device != q.device:
+      raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor [batch + 1] of unit stride on q's device, got {tuple(cu_seqlens_q.shape)} on {cu_seqlens_q.device}")
+    B = cu_seqlens_q.numel() - 1
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or (rows > 0 and max_seqlen_q < 1):
+      raise ValueError(f"{name}: max_seqlen_q must be a host int >= 1 (>= 0 without a token) that bounds every sequence's tokens, got {max_seqlen_q!r}")
+    if cache_seqlens.dtype != torch.int32:
+      raise TypeError(f"{name}: cache_seqlens must be int32, got {cache_seqlens.dtype}")
+    if cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
+      raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [batch={B}] on q's device, got {tuple(cache_seqlens.shape)} on {cache_seqlens.device}")
   if block_table is not None:
     if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B:
-      raise ValueError(f"ffpa_attn_with_kvcache: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
+      raise ValueError(f"{name}: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
     if block_table.size(1) == 0:
-      raise ValueError("ffpa_attn_with_kvcache: block_table needs at least one page per sequence")
+      raise ValueError(f"{name}: block_table needs at least one page per sequence")
     page_size = k_cache.size(1)
     if page_size <= 0 or page_size % 64 != 0:
-      raise ValueError(f"ffpa_attn_with_kvcache: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
+      raise ValueError(f"{name}: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
     if block_table.device != q.device:
-      raise ValueError(f"ffpa_attn_with_kvcache: block_table must be on q's device, got {block_table.device} and {q.device}")
+      raise ValueError(f"{name}: block_table must be on q's device, got {block_table.device} and {q.device}")
     capacity = block_table.size(1) * page_size
   else:
     if k_cache.size(0) != B:
-      raise ValueError(f"ffpa_attn_with_kvcache: k_cache [B, capacity, Hkv, D] must have q's batch ({B}), got {k_cache.size(0)}")
+      raise ValueError(f"{name}: k_cache [B, capacity, Hkv, D] must have {'q' if ragged is None else 'cu_seqlens_q'}'s batch ({B}), got {k_cache.size(0)}")
     capacity = k_cache.size(1)
   if k_cache.device != q.device or v_cache.device != q.device:
-    raise ValueError(f"ffpa_attn_with_kvcache: q / k_cache / v_cache must be on one device, got {q.device}, {k_cache.device}, {v_cache.device}")
-  if cache_seqlens is None:
-    seqused = torch.full((B,), capacity, dtype=torch.int32, device=q.device)
-  elif isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
-    if cache_seqlens < 0:
-      raise ValueError(f"ffpa_attn_with_kvcache: cache_seqlens must be non-negative, got {cache_seqlens}")
-    seqused = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
-  elif isinstance(cache_seqlens, torch.Tensor):
-    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
-      raise ValueError(f"ffpa_attn_with_kvcache: cache_seqlens must be an int or an int32 tensor [batch={B}] on q's device")
-    seqused = cache_seqlens
-  else:
-    raise TypeError(f"ffpa_attn_with_kvcache: cache_seqlens must be an int or an int32 tensor, got {type(cache_seqlens).__name__}")
-  scale = float(softmax_scale) if softmax_scale is not None else D ** -0.5
-
-  if k is not None:
+    raise ValueError(f"{name}: q / k_cache / v_cache must be on one device, got {q.device}, {k_cache.device}, {v_cache.device}")
+  lens = cache_seqlens
+  if ragged is None:  # (None, an int, or the tensor the ragged call has tested above)
     if cache_seqlens is None:
-      raise ValueError("ffpa_attn_with_kvcache: cache_seqlens is required with k / v (it gives where the new keys go)")
-    _check_append(q, k_cache, k, v, rotary_cos, rotary_sin, capacity)
-  return capacity, seqused, scale
+      lens = torch.full((B,), capacity, dtype=torch.int32, device=q.device)
+    elif isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool):
+      if cache_seqlens < 0:
+        raise ValueError(f"{name}: cache_seqlens must be non-negative, got {cache_seqlens}")
+      lens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
+    elif not isinstance(cache_seqlens, torch.Tensor):
+      raise TypeError(f"{name}: cache_seqlens must be an int or an int32 tensor, got {type(cache_seqlens).__name__}")
+    elif cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
+      raise ValueError(f"{name}: cache_seqlens must be an int or an int32 tensor [batch={B}] on q's device")
+  scale = float(softmax_scale) if softmax_scale is not None else D ** -0.5
+  if not append:
+    return B, capacity, lens, scale
+  if cache_seqlens is None:
+    raise ValueError(f"{name}: cache_seqlens is required with k / v (it gives where the new keys go)")
+  for nm, t in (("k", k), ("v", v)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+    if ragged is None and t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+    if t.dtype != q.dtype:
+      raise TypeError(f"{name}: {nm} must have the cache's dtype {q.dtype}, got {t.dtype}")
+    if t.device != q.device:
+      raise ValueError(f"{name}: {nm} must be on q's device, got {t.device} and {q.device}")
+    new = t.shape
+    if len(new) != len(shape) or new[0] != rows or new[-2] != Hkv or new[-1] != D:
+      form = f"[B={B}, Snew, Hkv={Hkv}, D={D}]" if ragged is None else f"[T={rows}, Hkv={Hkv}, D={D}] (packed by cu_seqlens_q like q)"
+      raise ValueError(f"{name}: {nm} must be {form}, got {tuple(new)}")
+    if t.stride(-1) != 1:
+      raise ValueError(f"{name}: {nm} must have a contiguous last dimension")
+  if k.shape != v.shape:  # (Snew: a ragged call's k and v have no dimension left to differ in)
+    raise ValueError(f"{name}: k {tuple(k.shape)} and v {tuple(v.shape)} must share their shape")
+  if not rotary:
+    return B, capacity, lens, scale
+  for nm, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+    if t.dtype != q.dtype:
+      raise TypeError(f"{name}: {nm} must have q's dtype {q.dtype}, got {t.dtype}")
+    if t.device != q.device:
+      raise ValueError(f"{name}: {nm} must be on q's device, got {t.device} and {q.device}")
+    if t.dim() != 2 or not t.is_contiguous():
+      raise ValueError(f"{name}: {nm} must be a contiguous [seqlen_ro, rotary_dim / 2] tensor, got {tuple(t.shape)}")
+  if rotary_cos.shape != rotary_sin.shape:
+    raise ValueError(f"{name}: rotary_cos {tuple(rotary_cos.shape)} and rotary_sin {tuple(rotary_sin.shape)} must share their shape")
+  rotary_dim = 2 * rotary_cos.size(1)
+  if rotary_dim == 0 or rotary_dim % 16 != 0 or rotary_dim > D:
+    raise ValueError(f"{name}: rotary_dim ({rotary_dim}) must be a positive multiple of 16 and at most the head dim ({D})")
+  if rotary_cos.size(0) < capacity:
+    raise ValueError(f"{name}: rotary_cos / rotary_sin have {rotary_cos.size(0)} rows (seqlen_ro), fewer than the cache capacity {capacity}")
+  if ragged is not None and positions is not None:
+    if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32:
+      raise TypeError(f"{name}: positions must be an int32 tensor, got {positions.dtype if isinstance(positions, torch.Tensor) else type(positions).__name__}")
+    if positions.dim() != 1 or positions.numel() != rows or positions.stride(0) != 1 or positions.device != q.device:
+      raise ValueError(f"{name}: positions must be int32 [T={rows}] of unit stride on q's device, got {tuple(positions.shape)} on {positions.device}")
+  return B, capacity, lens, scale
 
 
-def _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal):
-  """The prepare launch (with k / v): new keys into the cache (in place), rotated q, post-append lengths -> (q to attend with, key lengths)."""
-  from . import hip  # (registers the ffpa_attn ops)
+# The step behind _kv_check.  ``family`` names the ONE attention launch, chosen by the entry point: ("plain",) — the paged op, or hip.varlen_forward over a contiguous
+# cache —, ("tree", words), ("window", left, right) or ("softcap", cap, left, right); what follows the name are the op's own arguments, in its order.
+def _kv_append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, rotary_interleaved, causal, lens, block_table, ragged=None):
+  """The prepare launch of a call with k / v: new keys into the cache (in place), rotated q, post-append lengths — read by the attention launch on the same stream
+  -> (q to attend with, key lengths)."""
+  if ragged is None:
+    q_rot, lens = torch.ops.ffpa_attn._kvcache_append_hip(q, k_cache, v_cache, k, v, lens, block_table, rotary_cos, rotary_sin, bool(rotary_interleaved), bool(causal))
+  else:
+    q_rot, lens = torch.ops.ffpa_attn._kvcache_append_varlen_hip(q, k_cache, v_cache, k, v, ragged[0], lens, block_table, rotary_cos, rotary_sin, ragged[2],
+                                                                 bool(rotary_interleaved), bool(causal))
+  return (q_rot if rotary_cos is not None else q), lens
 
-  if k is not None:
-    # the prepare launch: new keys into the cache (in place), rotated q, post-append lengths — read by the attention launch below on the same stream
-    q_rot, seqused = torch.ops.ffpa_attn._kvcache_append_hip(q, k_cache, v_cache, k, v, seqused, block_table, rotary_cos, rotary_sin, bool(rotary_interleaved),
-                                                             bool(causal))
-    if rotary_cos is not None:
-      q = q_rot
-  return q, seqused
+
+def _kv_view(k_cache, v_cache, B, capacity):
+  """A CONTIGUOUS cache as the launch takes it -> (k, v, cu_seqlens_k): the packed call's seqused_k case — sequence b's keys are rows b * capacity ... of the cache
+  viewed as [B * capacity, Hkv, D].  (Page pools go to the launch as they are, without a cu_seqlens_k.)"""
+  Hkv, D = k_cache.size(2), k_cache.size(3)
+  kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
+  cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=k_cache.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=k_cache.device)
+  return kp, vp, cu_k
 
 
-def _attend(q, k_cache, v_cache, seqused, block_table, capacity, scale, causal, num_splits, return_lse):
-  """The attention launch of ffpa_attn_with_kvcache -> packed ``(o [B * Sq, Hq, D], lse [Hq, B * Sq] | None)``."""
+def _kv_launch(family, qp, kp, vp, cu_q, cu_k, lens, block_table, max_seqlen_q, capacity, scale, causal, num_splits, return_lse=True):
+  """The attention launch of ``family`` over packed q and ``_kv_view``'s caches -> packed ``(o [T, Hq, D], lse [Hq, T] | None)``."""
+  kind, c = family[0], 1 if causal else 0
+  if kind == "tree":
+    return torch.ops.ffpa_attn._tree_fwd_hip(qp, kp, vp, cu_q, cu_k, lens, block_table, *family[1:], max_seqlen_q, capacity, scale, -1.0, num_splits)
+  if kind == "window":
+    return torch.ops.ffpa_attn._window_fwd_hip(qp, kp, vp, cu_q, cu_k, lens, block_table, *family[1:], max_seqlen_q, capacity, scale, c, -1.0, num_splits)
+  if kind == "softcap":
+    return torch.ops.ffpa_attn._softcap_fwd_hip(qp, kp, vp, cu_q, cu_k, lens, block_table, *family[1:], max_seqlen_q, capacity, scale, c, -1.0, num_splits)
+  if block_table is not None:
+    return torch.ops.ffpa_attn._paged_fwd_hip(qp, kp, vp, cu_q, lens, block_table, max_seqlen_q, capacity, scale, c, -1.0, num_splits)
   from . import hip
 
-  B, Sq, Hq, D = q.shape
-  Hkv = k_cache.size(2)
-  qp = q.reshape(B * Sq, Hq, D)
-  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device) if Sq > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
-  if block_table is not None:
-    o, lse = torch.ops.ffpa_attn._paged_fwd_hip(qp, k_cache, v_cache, cu_q, seqused, block_table, Sq, capacity, scale, 1 if causal else 0, -1.0, num_splits)
+  return hip.varlen_forward(qp, kp, vp, cu_q, cu_k, max_seqlen_q, capacity, bool(causal), scale, return_lse=return_lse, seqused_k=lens, num_splits=num_splits)
+
+
+def _kv_step(family, q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, rotary_interleaved, lens, block_table, B, capacity, scale, causal, num_splits, return_lse,
+             ragged=None):
+  """The checked call's step: the append (``k`` / ``v``), q packed (a uniform call's as B sequences of Sq tokens), the cache view and the one attention launch of
+  ``family`` -> packed ``(o [T, Hq, D], lse [Hq, T] | None)``."""
+  if k is not None:
+    q, lens = _kv_append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, rotary_interleaved, causal, lens, block_table, ragged)
+  if ragged is None:
+    Sq, Hq, D = q.shape[1:]
+    qp = q.reshape(B * Sq, Hq, D)
+    cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device) if Sq > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
   else:
-    # the contiguous cache is the packed call's seqused_k case: sequence b's keys are rows b * capacity ... of the cache viewed as [B * capacity, Hkv, D]
-    kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
-    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
-    o, lse = hip.varlen_forward(qp, kp, vp, cu_q, cu_k, Sq, capacity, bool(causal), scale, return_lse=return_lse, seqused_k=seqused,
-                                num_splits=num_splits)
-  return o, lse
+    qp, cu_q, Sq = q, ragged[0], ragged[1]
+  kp, vp, cu_k = (k_cache, v_cache, None) if block_table is not None else _kv_view(k_cache, v_cache, B, capacity)
+  return _kv_launch(family, qp, kp, vp, cu_q, cu_k, lens, block_table, Sq, capacity, scale, causal, num_splits, return_lse)
+
+
+def _kv_unpack(o, lse, q, return_lse):
+  """A uniform call's returns: packed ``(o [B * Sq, Hq, D], lse [Hq, B * Sq])`` -> ``out [B, Sq, Hq, D]`` — and ``lse [B, Hq, Sq]``."""
+  B, Sq, Hq, D = q.shape
+  out = o.view(B, Sq, Hq, D)
+  if not return_lse:
+    return out
+  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
 
 
 def ffpa_attn_with_kvcache(
@@ -239,15 +305,11 @@ def ffpa_attn_with_kvcache(
   (q's dtype, contiguous, ``rotary_dim`` a multiple of 16 <= D, ``seqlen_ro`` >= the capacity): the first ``rotary_dim`` dims of the new keys (stored rotated) and of
   q (a rotated copy attends; q is not modified) are rotated — key i at position ``cache_seqlens[b] + i``, query token i at ``cache_seqlens[b] + i`` when
   ``causal``, at ``cache_seqlens[b]`` otherwise; ``rotary_interleaved`` pairs dims (2j, 2j + 1), else (j, j + rotary_dim / 2) (GPT-NeoX).  V is never rotated."""
-  capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, cache_batch_idx, cache_leftpad, block_table,
-                                       softmax_scale, window_size, softcap, alibi_slopes, num_splits)
-  q, seqused = _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal)
-  B, Sq, Hq, D = q.shape
-  o, lse = _attend(q, k_cache, v_cache, seqused, block_table, capacity, scale, causal, num_splits, return_softmax_lse)
-  out = o.view(B, Sq, Hq, D)
-  if not return_softmax_lse:
-    return out
-  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+  unserved = _unsupported(cache_batch_idx, cache_leftpad, window_size, softcap, alibi_slopes)
+  B, capacity, lens, scale = _kv_check(_UNIFORM, q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, block_table, softmax_scale, num_splits, unserved)
+  o, lse = _kv_step(("plain",), q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, rotary_interleaved, lens, block_table, B, capacity, scale, causal, num_splits,
+                    return_softmax_lse)
+  return _kv_unpack(o, lse, q, return_softmax_lse)
 
 
 # ---- tree-mask attention (the verification step of tree speculative decoding): ffpa_attn_with_kvcache_tree
@@ -331,27 +393,12 @@ def ffpa_attn_with_kvcache_tree(
   no per-token positions — rotate q and the draft keys before the call.  Nothing is read back to the host: the call captures into one HIP graph, and a replay
   follows ``cache_seqlens``, ``block_table`` and the mask written in place — a bool mask is packed inside the graph; hand over packed words to write words.
   Inference only: a tensor that requires grad raises ``NotImplementedError``."""
-  capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, None, None, cache_seqlens, None, None, block_table, softmax_scale, (-1, -1), 0.0, None,
-                                       num_splits)
+  B, capacity, lens, scale = _kv_check(_UNIFORM, q, k_cache, v_cache, k, v, None, None, cache_seqlens, block_table, softmax_scale, num_splits)
   if isinstance(tree_mask, torch.Tensor) and tree_mask.requires_grad and torch.is_grad_enabled():
     raise NotImplementedError("ffpa_attn_with_kvcache is inference only: tree_mask requires grad and there is no backward")
-  B, Sq, Hq, D = q.shape
-  Hkv = k_cache.size(2)
-  words = _tree_words(tree_mask, B, Sq, q.device)
-  q, seqused = _append(q, k_cache, v_cache, k, v, None, None, cache_seqlens, seqused, block_table, capacity, True, False)
-  qp = q.reshape(B * Sq, Hq, D)
-  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)
-  if block_table is not None:
-    kp, vp, cu_k = k_cache, v_cache, None
-  else:
-    # the contiguous cache as the packed call's seqused_k case (ffpa_attn_with_kvcache's view: sequence b's keys are rows b * capacity ...)
-    kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
-    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
-  o, lse = torch.ops.ffpa_attn._tree_fwd_hip(qp, kp, vp, cu_q, cu_k, seqused, block_table, words, Sq, capacity, scale, -1.0, num_splits)
-  out = o.view(B, Sq, Hq, D)
-  if not return_softmax_lse:
-    return out
-  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+  words = _tree_words(tree_mask, B, q.size(1), q.device)
+  o, lse = _kv_step(("tree", words), q, k_cache, v_cache, k, v, None, None, True, lens, block_table, B, capacity, scale, False, num_splits, True)
+  return _kv_unpack(o, lse, q, return_softmax_lse)
 
 
 # ---- sliding-window (local) attention: ffpa_attn_with_kvcache_window
@@ -422,24 +469,10 @@ def ffpa_attn_with_kvcache_window(
   A row that sees no key returns O = 0, LSE = -inf.  Nothing is read back to the host: the call captures into one HIP graph, and a replay follows
   ``cache_seqlens`` / ``block_table`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``."""
   left, right = _window_arg(window_size)
-  capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, None, None, block_table, softmax_scale, (-1, -1), 0.0,
-                                       None, num_splits)
-  q, seqused = _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal)
-  B, Sq, Hq, D = q.shape
-  Hkv = k_cache.size(2)
-  qp = q.reshape(B * Sq, Hq, D)
-  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device) if Sq > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
-  if block_table is not None:
-    kp, vp, cu_k = k_cache, v_cache, None
-  else:
-    # the contiguous cache as the packed call's seqused_k case (ffpa_attn_with_kvcache's view: sequence b's keys are rows b * capacity ...)
-    kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
-    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
-  o, lse = torch.ops.ffpa_attn._window_fwd_hip(qp, kp, vp, cu_q, cu_k, seqused, block_table, left, right, Sq, capacity, scale, 1 if causal else 0, -1.0, num_splits)
-  out = o.view(B, Sq, Hq, D)
-  if not return_softmax_lse:
-    return out
-  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+  B, capacity, lens, scale = _kv_check(_UNIFORM, q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, block_table, softmax_scale, num_splits)
+  o, lse = _kv_step(("window", left, right), q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, rotary_interleaved, lens, block_table, B, capacity, scale, causal,
+                    num_splits, True)
+  return _kv_unpack(o, lse, q, return_softmax_lse)
 
 
 # ---- logit soft-capping, with or without a sliding window: ffpa_attn_with_kvcache_softcap
@@ -483,25 +516,10 @@ def ffpa_attn_with_kvcache_softcap(
     return ffpa_attn_with_kvcache_window(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, block_table, window_size=(left, right),
                                          softmax_scale=softmax_scale, causal=causal, rotary_interleaved=rotary_interleaved, num_splits=num_splits,
                                          return_softmax_lse=return_softmax_lse)
-  capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, None, None, block_table, softmax_scale, (-1, -1), 0.0,
-                                       None, num_splits)
-  q, seqused = _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal)
-  B, Sq, Hq, D = q.shape
-  Hkv = k_cache.size(2)
-  qp = q.reshape(B * Sq, Hq, D)
-  cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device) if Sq > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
-  if block_table is not None:
-    kp, vp, cu_k = k_cache, v_cache, None
-  else:
-    # the contiguous cache as the packed call's seqused_k case (ffpa_attn_with_kvcache's view: sequence b's keys are rows b * capacity ...)
-    kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
-    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
-  o, lse = torch.ops.ffpa_attn._softcap_fwd_hip(qp, kp, vp, cu_q, cu_k, seqused, block_table, softcap, left, right, Sq, capacity, scale, 1 if causal else 0, -1.0,
-                                                num_splits)
-  out = o.view(B, Sq, Hq, D)
-  if not return_softmax_lse:
-    return out
-  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+  B, capacity, lens, scale = _kv_check(_UNIFORM, q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, block_table, softmax_scale, num_splits)
+  o, lse = _kv_step(("softcap", softcap, left, right), q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, rotary_interleaved, lens, block_table, B, capacity, scale,
+                    causal, num_splits, True)
+  return _kv_unpack(o, lse, q, return_softmax_lse)
 
 
 # ---- MLA latent-cache attention (DeepSeek-V2 / V3 / R1, Kimi K2 in their "absorbed" decode form): ffpa_attn_with_kvcache_mla
@@ -1369,107 +1387,6 @@ def ffpa_attn_with_kvcache_mla_sparse_ds(
   return (out, lse) if return_softmax_lse else out
 
 
-def _validate_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k, v, rotary_cos, rotary_sin, positions, softmax_scale, num_splits):
-  """Every host-side check of ffpa_attn_varlen_with_kvcache but ``window_size`` / ``softcap`` (nothing read from the device, nothing launched)
-  -> (batch, capacity, softmax scale)."""
-  name = "ffpa_attn_varlen_with_kvcache"
-  append = k is not None and v is not None
-  rotary = rotary_cos is not None and rotary_sin is not None
-  bad = [n for n, t, ok in (("k", k, append), ("v", v, append), ("rotary_cos", rotary_cos, rotary and append), ("rotary_sin", rotary_sin, rotary and append),
-                            ("positions", positions, rotary and append)) if t is not None and not ok]
-  if bad:
-    raise NotImplementedError(f"{name} does not support: {', '.join(bad)} (k and v only together, rotary_cos and rotary_sin only together and with k / v, "
-                              "positions only with the rotary tables)")
-  for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("cu_seqlens_q", cu_seqlens_q), ("cache_seqlens", cache_seqlens)):
-    if not isinstance(t, torch.Tensor):
-      raise TypeError(f"{name}: {n} must be a tensor, got {type(t).__name__}")
-  for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("k", k), ("v", v)):
-    if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
-      raise NotImplementedError(f"{name} is inference only: {n} requires grad and there is no backward")
-  if q.dtype not in _DTYPES or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-    raise TypeError(f"{name} only supports fp16/bf16 q/k_cache/v_cache of one dtype, got {q.dtype}, {k_cache.dtype}, {v_cache.dtype}")
-  if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
-    raise ValueError(f"{name}: q must be packed [T, Hq, D] and k_cache / v_cache 4-D")
-  if k_cache.shape != v_cache.shape:
-    raise ValueError(f"{name}: k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} must share their shape")
-  T, Hq, D = q.shape
-  Hkv = k_cache.size(2)
-  if k_cache.size(3) != D:
-    raise ValueError(f"{name}: head dim of the cache ({k_cache.size(3)}) differs from q's ({D})")
-  if D % 8 != 0 or D > 1024 or D <= 0:
-    raise ValueError(f"{name}: head dim {D} is not a multiple of 8 in [8, 1024]")
-  if Hkv == 0 or Hq % Hkv != 0:
-    raise ValueError(f"{name}: query num_heads ({Hq}) must be a multiple of key/value num_heads ({Hkv})")
-  if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
-    raise ValueError(f"{name}: num_splits must be a non-negative int, got {num_splits!r}")
-  if cu_seqlens_q.dtype != torch.int32:
-    raise TypeError(f"{name}: cu_seqlens_q must be int32, got {cu_seqlens_q.dtype}")
-  if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 2 or cu_seqlens_q.stride(0) != 1 or cu_seqlens_q.device != q.device:
-    raise ValueError(f"{name}: cu_seqlens_q must be a 1-D int32 tensor [batch + 1] of unit stride on q's device, got {tuple(cu_seqlens_q.shape)} on {cu_seqlens_q.device}")
-  B = cu_seqlens_q.numel() - 1
-  if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int) or max_seqlen_q < 0 or (T > 0 and max_seqlen_q < 1):
-    raise ValueError(f"{name}: max_seqlen_q must be a host int >= 1 (>= 0 without a token) that bounds every sequence's tokens, got {max_seqlen_q!r}")
-  if cache_seqlens.dtype != torch.int32:
-    raise TypeError(f"{name}: cache_seqlens must be int32, got {cache_seqlens.dtype}")
-  if cache_seqlens.dim() != 1 or cache_seqlens.numel() != B or cache_seqlens.device != q.device:
-    raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [batch={B}] on q's device, got {tuple(cache_seqlens.shape)} on {cache_seqlens.device}")
-  if block_table is not None:
-    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.size(0) != B:
-      raise ValueError(f"{name}: block_table must be an int32 tensor [batch={B}, pages_per_seq]")
-    if block_table.size(1) == 0:
-      raise ValueError(f"{name}: block_table needs at least one page per sequence")
-    page_size = k_cache.size(1)
-    if page_size <= 0 or page_size % 64 != 0:
-      raise ValueError(f"{name}: page_size ({page_size}) must be a positive multiple of 64 (smaller pages are not supported)")
-    if block_table.device != q.device:
-      raise ValueError(f"{name}: block_table must be on q's device, got {block_table.device} and {q.device}")
-    capacity = block_table.size(1) * page_size
-  else:
-    if k_cache.size(0) != B:
-      raise ValueError(f"{name}: k_cache [B, capacity, Hkv, D] must have cu_seqlens_q's batch ({B}), got {k_cache.size(0)}")
-    capacity = k_cache.size(1)
-  if k_cache.device != q.device or v_cache.device != q.device:
-    raise ValueError(f"{name}: q / k_cache / v_cache must be on one device, got {q.device}, {k_cache.device}, {v_cache.device}")
-  scale = float(softmax_scale) if softmax_scale is not None else D ** -0.5
-  if not append:
-    return B, capacity, scale
-  for n, t in (("k", k), ("v", v)):
-    if not isinstance(t, torch.Tensor):
-      raise TypeError(f"{name}: {n} must be a tensor, got {type(t).__name__}")
-    if t.dtype != q.dtype:
-      raise TypeError(f"{name}: {n} must have the cache's dtype {q.dtype}, got {t.dtype}")
-    if t.device != q.device:
-      raise ValueError(f"{name}: {n} must be on q's device, got {t.device} and {q.device}")
-    if t.dim() != 3 or t.size(0) != T or t.size(1) != Hkv or t.size(2) != D:
-      raise ValueError(f"{name}: {n} must be [T={T}, Hkv={Hkv}, D={D}] (packed by cu_seqlens_q like q), got {tuple(t.shape)}")
-    if t.stride(-1) != 1:
-      raise ValueError(f"{name}: {n} must have a contiguous last dimension")
-  if not rotary:
-    return B, capacity, scale
-  for n, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
-    if not isinstance(t, torch.Tensor):
-      raise TypeError(f"{name}: {n} must be a tensor, got {type(t).__name__}")
-    if t.dtype != q.dtype:
-      raise TypeError(f"{name}: {n} must have q's dtype {q.dtype}, got {t.dtype}")
-    if t.device != q.device:
-      raise ValueError(f"{name}: {n} must be on q's device, got {t.device} and {q.device}")
-    if t.dim() != 2 or not t.is_contiguous():
-      raise ValueError(f"{name}: {n} must be a contiguous [seqlen_ro, rotary_dim / 2] tensor, got {tuple(t.shape)}")
-  if rotary_cos.shape != rotary_sin.shape:
-    raise ValueError(f"{name}: rotary_cos {tuple(rotary_cos.shape)} and rotary_sin {tuple(rotary_sin.shape)} must share their shape")
-  rotary_dim = 2 * rotary_cos.size(1)
-  if rotary_dim == 0 or rotary_dim % 16 != 0 or rotary_dim > D:
-    raise ValueError(f"{name}: rotary_dim ({rotary_dim}) must be a positive multiple of 16 and at most the head dim ({D})")
-  if rotary_cos.size(0) < capacity:
-    raise ValueError(f"{name}: rotary_cos / rotary_sin have {rotary_cos.size(0)} rows (seqlen_ro), fewer than the cache capacity {capacity}")
-  if positions is not None:
-    if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32:
-      raise TypeError(f"{name}: positions must be an int32 tensor, got {positions.dtype if isinstance(positions, torch.Tensor) else type(positions).__name__}")
-    if positions.dim() != 1 or positions.numel() != T or positions.stride(0) != 1 or positions.device != q.device:
-      raise ValueError(f"{name}: positions must be int32 [T={T}] of unit stride on q's device, got {tuple(positions.shape)} on {positions.device}")
-  return B, capacity, scale
-
-
 def ffpa_attn_varlen_with_kvcache(
   q: torch.Tensor,
   k_cache: torch.Tensor,
@@ -1521,41 +1438,17 @@ def ffpa_attn_varlen_with_kvcache(
   ``cu_seqlens_q[B]`` (padding: T may exceed it) are unspecified, and nothing is appended for them.  ``T == 0`` returns empty tensors and launches nothing.
   Nothing is read back to the host: the call captures into one HIP graph, and a replay follows ``q``, ``cu_seqlens_q`` (same T, same bound), ``cache_seqlens``,
   ``block_table`` and ``positions`` written in place.  Inference only: a tensor that requires grad raises ``NotImplementedError``."""
-  from . import hip  # (registers the ffpa_attn ops)
-
   softcap = _softcap_arg(softcap)
   left, right = _window_arg(window_size)
-  B, capacity, scale = _validate_varlen(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q, cache_seqlens, block_table, k, v, rotary_cos, rotary_sin, positions,
-                                        softmax_scale, num_splits)
+  ragged = (cu_seqlens_q, max_seqlen_q, positions)
+  B, capacity, lens, scale = _kv_check(_RAGGED, q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, block_table, softmax_scale, num_splits, ragged=ragged)
   T, Hq, D = q.shape
-  Hkv = k_cache.size(2)
   if T == 0:
     out = q.new_empty((0, Hq, D))
     return (out, torch.empty((Hq, 0), dtype=torch.float32, device=q.device)) if return_softmax_lse else out
-  seqused = cache_seqlens
-  if k is not None:
-    # the prepare launch: new keys into the cache (in place), rotated q, post-append lengths — read by the attention launch below on the same stream
-    q_rot, seqused = torch.ops.ffpa_attn._kvcache_append_varlen_hip(q, k_cache, v_cache, k, v, cu_seqlens_q, cache_seqlens, block_table, rotary_cos, rotary_sin,
-                                                                    positions, bool(rotary_interleaved), bool(causal))
-    if rotary_cos is not None:
-      q = q_rot
-  if block_table is not None:
-    kp, vp, cu_k = k_cache, v_cache, None
-  else:
-    # the contiguous cache as the packed call's seqused_k case (ffpa_attn_with_kvcache's view: sequence b's keys are rows b * capacity ...)
-    kp, vp = k_cache.reshape(B * capacity, Hkv, D), v_cache.reshape(B * capacity, Hkv, D)
-    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=q.device) if capacity > 0 else torch.zeros(B + 1, dtype=torch.int32, device=q.device)
-  c = 1 if causal else 0
-  if softcap > 0.0:
-    o, lse = torch.ops.ffpa_attn._softcap_fwd_hip(q, kp, vp, cu_seqlens_q, cu_k, seqused, block_table, softcap, left, right, max_seqlen_q, capacity, scale, c, -1.0,
-                                                  num_splits)
-  elif (left, right) != (-1, -1):
-    o, lse = torch.ops.ffpa_attn._window_fwd_hip(q, kp, vp, cu_seqlens_q, cu_k, seqused, block_table, left, right, max_seqlen_q, capacity, scale, c, -1.0, num_splits)
-  elif block_table is not None:
-    o, lse = torch.ops.ffpa_attn._paged_fwd_hip(q, kp, vp, cu_seqlens_q, seqused, block_table, max_seqlen_q, capacity, scale, c, -1.0, num_splits)
-  else:
-    o, lse = hip.varlen_forward(q, kp, vp, cu_seqlens_q, cu_k, max_seqlen_q, capacity, bool(causal), scale, return_lse=return_softmax_lse, seqused_k=seqused,
-                                num_splits=num_splits)
+  family = ("softcap", softcap, left, right) if softcap > 0.0 else ("window", left, right) if (left, right) != (-1, -1) else ("plain",)
+  o, lse = _kv_step(family, q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, rotary_interleaved, lens, block_table, B, capacity, scale, causal, num_splits,
+                    return_softmax_lse, ragged)
   return (o, lse) if return_softmax_lse else o
 
 
@@ -1783,10 +1676,9 @@ def ffpa_attn_with_kvcache_cascade(
     raise ValueError(f"ffpa_attn_with_kvcache_cascade: shared_prefix_len must be non-negative, got {shared_prefix_len}")
   if cascade is not None and not isinstance(cascade, bool):
     raise TypeError(f"ffpa_attn_with_kvcache_cascade: cascade must be True, False or None, got {cascade!r}")
-  capacity, seqused, scale = _validate(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, None, None, block_table, softmax_scale, (-1, -1), 0.0,
-                                       None, num_splits)
+  B, capacity, lens, scale = _kv_check(_UNIFORM, q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, block_table, softmax_scale, num_splits)
   P = shared_prefix_len
-  B, Sq, Hq, D = q.shape
+  Sq, Hq, D = q.shape[1:]
   Hkv = k_cache.size(2)
   page_size = k_cache.size(1) if block_table is not None else 0
   if P > capacity:
@@ -1798,23 +1690,19 @@ def ffpa_attn_with_kvcache_cascade(
                                   causal=causal, rotary_interleaved=rotary_interleaved, num_splits=num_splits, return_softmax_lse=return_softmax_lse)
   use = cascade_rule(B, Sq, Hq, Hkv, D, P, page_size) if cascade is None else True
   use = use and 0 < P < capacity and B * Sq > 0
-  q, seqused = _append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, seqused, block_table, capacity, rotary_interleaved, causal)
   if not use:
-    o, lse = _attend(q, k_cache, v_cache, seqused, block_table, capacity, scale, causal, num_splits, return_softmax_lse)
+    o, lse = _kv_step(("plain",), q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, rotary_interleaved, lens, block_table, B, capacity, scale, causal, num_splits,
+                      return_softmax_lse)
   else:
-    o, lse = _cascade(q, k_cache, v_cache, seqused, block_table, capacity, P, scale, causal, num_splits)
-  out = o.view(B, Sq, Hq, D)
-  if not return_softmax_lse:
-    return out
-  return out, lse.view(Hq, B, Sq).permute(1, 0, 2).contiguous()
+    if k is not None:
+      q, lens = _kv_append(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, rotary_interleaved, causal, lens, block_table)
+    o, lse = _cascade(q, k_cache, v_cache, lens, block_table, capacity, P, scale, causal, num_splits)
+  return _kv_unpack(o, lse, q, return_softmax_lse)
 
 
 def _cascade(q, k_cache, v_cache, seqused, block_table, capacity, P, scale, causal, num_splits):
   """The prefix pass, the suffix pass and the merge -> packed ``(o [B * Sq, Hq, D], lse [Hq, B * Sq])``.  0 < P < capacity, B * Sq > 0."""
-  from . import hip
-
   B, Sq, Hq, D = q.shape
-  Hkv = k_cache.size(2)
   dev = q.device
   T = B * Sq
   qp = q.reshape(T, Hq, D)
@@ -1826,16 +1714,14 @@ def _cascade(q, k_cache, v_cache, seqused, block_table, capacity, P, scale, caus
   if block_table is not None:
     pp = P // k_cache.size(1)
     used_pre = torch.full((1,), P, dtype=torch.int32, device=dev)
-    o_p, lse_p = torch.ops.ffpa_attn._paged_fwd_hip(qp, k_cache, v_cache, cu_pre, used_pre, block_table[:1, :pp], T, P, scale, 0, -1.0, num_splits)
-    o_s, lse_s = torch.ops.ffpa_attn._paged_fwd_hip(qp, k_cache, v_cache, cu_q, used_suf, block_table[:, pp:], Sq, capacity - P, scale, 1 if causal else 0, -1.0,
-                                                    num_splits)
+    o_p, lse_p = _kv_launch(("plain",), qp, k_cache, v_cache, cu_pre, None, used_pre, block_table[:1, :pp], T, P, scale, False, num_splits)
+    o_s, lse_s = _kv_launch(("plain",), qp, k_cache, v_cache, cu_q, None, used_suf, block_table[:, pp:], Sq, capacity - P, scale, causal, num_splits)
   else:
     cu_kp = torch.arange(0, 2 * P, P, dtype=torch.int32, device=dev)
-    o_p, lse_p = hip.varlen_forward(qp, k_cache[0, :P], v_cache[0, :P], cu_pre, cu_kp, T, P, False, scale, num_splits=num_splits)
-    # sequence b's suffix: rows b * capacity + P ... of the cache viewed as [B * capacity, Hkv, D] — the same boundaries as the plain launch, shifted by P rows
-    kp, vp = k_cache.reshape(B * capacity, Hkv, D)[P:], v_cache.reshape(B * capacity, Hkv, D)[P:]
-    cu_k = torch.arange(0, (B + 1) * capacity, capacity, dtype=torch.int32, device=dev)
-    o_s, lse_s = hip.varlen_forward(qp, kp, vp, cu_q, cu_k, Sq, capacity - P, bool(causal), scale, seqused_k=used_suf, num_splits=num_splits)
+    o_p, lse_p = _kv_launch(("plain",), qp, k_cache[0, :P], v_cache[0, :P], cu_pre, cu_kp, None, None, T, P, scale, False, num_splits)
+    # sequence b's suffix: rows b * capacity + P ... of the plain launch's view — the same boundaries, shifted by P rows
+    kp, vp, cu_k = _kv_view(k_cache, v_cache, B, capacity)
+    o_s, lse_s = _kv_launch(("plain",), qp, kp[P:], vp[P:], cu_q, cu_k, used_suf, None, Sq, capacity - P, scale, causal, num_splits)
   return _merge(o_p, lse_p, o_s, lse_s)
 
 

@@ -55,7 +55,7 @@ def test_window_size_is_required_and_checked():
 
 
 def _raises_like_the_plain_call(kwargs_of, **kw):
-  """What ``_validate`` refuses is refused by the window entry with the same exception type and text."""
+  """What ``_kv_check`` refuses is refused by the window entry with the same exception type and text."""
   with pytest.raises(Exception) as plain:
     ffpa_attn_with_kvcache(*kwargs_of[0], **kwargs_of[1], **kw)
   with pytest.raises(type(plain.value)) as win:
