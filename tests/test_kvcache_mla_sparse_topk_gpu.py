@@ -1,6 +1,11 @@
 """``ffpa_mla_sparse_topk_slots`` / ``ffpa_mla_sparse_slots`` on the GPU against their definition (tests/kvcache_mla_sparse_topk_ref.py, run on the CPU copy of the
 same tensors): integer tensors, every comparison exact.  Lengths, ties and radix digits, token -> sequence, the translation, the positions mode against the two
-torch helpers, the pair feeding the sparse call (and the dense latent call's bits where every key is selected), one HIP graph, ``torch.compile``."""
+torch helpers, the pair feeding the sparse call (and the dense latent call's bits where every key is selected), one HIP graph, ``torch.compile``.
+
+Ties, special values and all four radix passes are run here at 4097 columns — ONE step of the kernel's ordered pass (8192 columns), one histogram base —, and no
+``topk`` here passes 4096.  The multi-step cases — ties carried over step edges, ``topk`` and the positions mode past 8192, several histogram bases, 257 sequences,
+``indices_stride > topk`` through the C export — live in tests/test_kvcache_mla_sparse_topk_sweep_gpu.py, their builders and conditions in
+tests/kvcache_mla_sparse_topk_cases.py."""
 
 import pytest
 import torch
