@@ -685,10 +685,11 @@ def _fwd_params(dtype: torch.dtype, batch: int, heads_q: int, heads_kv: int, seq
 
 def launch_plan(batch: int, heads_q: int, heads_kv: int, seqlen_q: int, seqlen_kv: int, head_dim: int, *, dtype: torch.dtype = torch.bfloat16,
                 causal: bool = False, bias_dtype: "torch.dtype | None" = None, dropout_p: float = 0.0, flags: int = 0, num_splits: int = 0,
-                device: "torch.device | int | None" = None) -> dict:
+                device: "torch.device | int | None" = None, bias_row_axis: bool = True) -> dict:
   """The launch plan the library would pick for a call of this shape class — tile (``block_rows`` x ``block_keys``), KV ``splits``, ``variant``
   (0 prefill, 1 short-query) and the ``kernel`` name — without launching anything (``ffpa_attn_fwd_plan`` / ``_kernel`` on a parameter block with
-  placeholder pointers; with ``device`` the plan is that GPU's: its CU count prices the split rules).  A caller that cuts a batch into pieces and needs the
+  placeholder pointers; with ``device`` the plan is that GPU's: its CU count prices the split rules).  ``bias_row_axis=False``: the bias is a KEY bias
+  ``[B | 1, Hq | 1, 1, Nkv]`` (row stride 0), which the builds that stage bias tiles through LDS do not serve.  A caller that cuts a batch into pieces and needs the
   pieces to run the plan of the whole (``sharding.attend_and_gather_units``) asks here."""
   lib = load_library()
   d8 = (int(head_dim) + 7) // 8 * 8
@@ -699,7 +700,7 @@ def launch_plan(batch: int, heads_q: int, heads_kv: int, seqlen_q: int, seqlen_k
   if bias_dtype is not None:
     p.bias = 16
     p.bias_dtype = _BIAS_DTYPE[bias_dtype]
-    p.bias_stride[:] = [0, 0, seqlen_kv, 1]
+    p.bias_stride[:] = [0, 0, seqlen_kv if bias_row_axis else 0, 1]
   if num_splits != 1:
     p.workspace, p.workspace_bytes = 16, (1 << 62)
   query = (lib, lib.ffpa_attn_fwd_plan, lib.ffpa_attn_fwd_kernel, _FWD_PLAN_KEYS, (ctypes.byref(p),), True)

@@ -27,12 +27,13 @@ def hip():
 
 
 def _family(kernel: str) -> set:
-  """'ffpa_fwd_m16_kernel<bf16, 512, MK=1, DROP=0> + ffpa_fwd_merge_kernel' -> {'ffpa_fwd_m16_kernel MK=1', 'ffpa_fwd_merge_kernel'}"""
+  """'ffpa_fwd_m16_kernel<bf16, 512, MK=1, DROP=0> + ffpa_fwd_merge_kernel' -> {'ffpa_fwd_m16_kernel MK=1', 'ffpa_fwd_merge_kernel'};
+  'ffpa_fwd_split_d_kernel<fp16, 320, ND=2, DROP>' -> {'ffpa_fwd_split_d_kernel ND=2 DROP'} (the split-D builds: ND = 1 / 2 / 4 x plain, DROP, BTILE)"""
   out = set()
   for part in kernel.split(" (")[0].split(" + "):
     name = part.split("<")[0].strip()
     tags = [t.strip(" >") for t in part.split("<")[1].split(",")] if "<" in part else []
-    out.add(" ".join([name] + [t for t in tags if t.startswith("MK=") or t == "PAIR"]))
+    out.add(" ".join([name] + [t for t in tags if t.startswith("MK=") or t.startswith("ND=") or t in ("PAIR", "DROP", "BTILE")]))
   return out
 
 
@@ -48,19 +49,23 @@ def _is_five_keys_case(case) -> bool:
   return (case["variant"], case["shape"], case["dtype"], case["causal"]) == FIVE_KEYS_CASE
 
 
-def _dense(hip, case, flags=0, builder=None, judge_absorbed_rows=False, **kw):
+def _dense(hip, case, flags=0, builder=None, judge_absorbed_rows=False, seen=None, **kw):
   """One dense launch of a case against float64 -> worst error / allowance.  Rows masked wholly by a large finite value that the kernels do not saturate
-  (-1e4, finfo(fp16).min) are asserted finite here and compared in ``test_rows_masked_wholly_by_a_large_finite_value`` alone."""
+  (-1e4, finfo(fp16).min) are asserted finite here and compared in ``test_rows_masked_wholly_by_a_large_finite_value`` alone.  ``seen`` (a dict)
+  receives the launch's plan."""
   B, hq, hkv, nq, nkv, d = case["shape"]
   probe = (builder or mv.build)(case)
   bdt = None if probe[3] is None else probe[3].dtype
-  want = hip.launch_plan(B, hq, hkv, nq, nkv, d, dtype=case["dtype"], causal=case["causal"], bias_dtype=bdt, flags=flags, device=0, **kw)
+  want = hip.launch_plan(B, hq, hkv, nq, nkv, d, dtype=case["dtype"], causal=case["causal"], bias_dtype=bdt, flags=flags, device=0,
+                         bias_row_axis=bdt is None or probe[3].size(2) > 1, **kw)
   q, k, v, bias, rows, value = (builder or mv.build)(case, want["block_keys"])
   q, k, v, bias = _cuda(q, k, v, bias)
   plan = {}
   o, lse = hip.forward(q, k, v, bias, case["causal"], d ** -0.5, plan_out=plan, flags=flags, **kw)
   assert plan["block_keys"] == want["block_keys"], (plan, want)  # (the staircases were built for this tile)
   REACHED.update(_family(plan["kernel"]))
+  if seen is not None:
+    seen.update(plan)
   fp32_rows = rows if (value is not None and np.isfinite(value) and abs(value) >= 65504.0) else None
   ref = mv.attend(q, k, v, bias, case["causal"], fp32_rows=None if fp32_rows is None else fp32_rows.cuda())
   name = f"{case['variant']} {case['shape']} {kr.DTYPE_NAME[case['dtype']]} causal={case['causal']} [{plan['kernel']}]"
@@ -68,6 +73,32 @@ def _dense(hip, case, flags=0, builder=None, judge_absorbed_rows=False, **kw):
     judge_absorbed_rows = judge_absorbed_rows or value < mv.BIAS_FLOOR  # (saturated rows are compared everywhere, KV splits included)
   return mv.check_case(o, lse, ref, case, v=v, value=value, name=name, rows=rows if builder is _key_padding_builder else None,
                        judge_absorbed_rows=judge_absorbed_rows)
+
+
+DROP_P, DROP_SEED, DROP_OFFSET = 0.25, (1 << 40) + 12345, 4 * 77 + 3
+
+
+def _dense_dropout(hip, case, seen=None, **kw):
+  """One dense launch of a bias-free case under dropout against float64 -> worst error / allowance: the reference is softmax(S) o keep / (1 - p) times V with
+  the keep mask ``ffpa_attn_amd.philox`` states, and the row statistics of the allowance are those of the matrix that multiplies V."""
+  from backward_dense_ref import element_index
+  from ffpa_attn_amd.philox import dropout_keep_mask
+
+  B, hq, hkv, nq, nkv, d = case["shape"]
+  want = hip.launch_plan(B, hq, hkv, nq, nkv, d, dtype=case["dtype"], causal=case["causal"], dropout_p=DROP_P, device=0, **kw)
+  q, k, v = _cuda(*mv.build(case, want["block_keys"])[:3])
+  plan = {}
+  o, lse = hip.forward(q, k, v, None, case["causal"], d ** -0.5, dropout_p=DROP_P, philox_seed=DROP_SEED, philox_offset=DROP_OFFSET, plan_out=plan, **kw)
+  assert plan["block_keys"] == want["block_keys"] and not plan["packed"], (plan, want)
+  REACHED.update(_family(plan["kernel"]))
+  if seen is not None:
+    seen.update(plan)
+  s = mv.scores(q, k, None, case["causal"])
+  keep = dropout_keep_mask(DROP_SEED, DROP_OFFSET, element_index(dict(B=B, heads=(hq, hkv), Nq=nq, Nkv=nkv), "cuda"), DROP_P)
+  p = torch.softmax(s, dim=-1) * keep / (1.0 - DROP_P)
+  ref = (torch.matmul(p, v.double().repeat_interleave(hq // hkv, dim=1)).transpose(1, 2).contiguous(), torch.logsumexp(s, dim=-1), p.amax(dim=-1), p.pow(2).sum(dim=-1))
+  name = f"dropout {case['variant']} {case['shape']} {kr.DTYPE_NAME[case['dtype']]} causal={case['causal']} [{plan['kernel']}]"
+  return mv.check_case(o, lse, ref, case, v=v, name=name)
 
 
 @pytest.mark.parametrize("D", mv.HEAD_DIMS)
@@ -141,6 +172,14 @@ ABSORBED_MISSES = frozenset((
   "keybias-minus_1e4-D1024-64x700-h4_1-fp16", "keybias-minus_1e4-D320-129x513-h2_2-fp16", "keybias-minus_1e4-D320-129x513-h4_1-fp16",
   "keybias-minus_1e4-D320-33x333-h4_1-fp16", "keybias-minus_1e4-D320-64x700-h2_2-fp16", "keybias-minus_1e4-D512-129x513-h2_2-fp16",
   "keybias-minus_1e4-D512-129x513-h4_1-fp16", "keybias-minus_1e4-D512-33x333-h4_1-fp16", "keybias-minus_1e4-D512-64x700-h4_1-fp16",
+  # ... and at (129, 520), the shape whose 16-bit masks are staged through LDS (profiles/r34_split_d_model_values.md)
+  "dense-finfo_min-D1024-129x520-h2_2-fp16", "dense-finfo_min-D1024-129x520-h4_1-fp16", "dense-finfo_min-D128-129x520-h2_2-fp16",
+  "dense-finfo_min-D128-129x520-h4_1-fp16", "dense-finfo_min-D320-129x520-h2_2-fp16", "dense-finfo_min-D320-129x520-h4_1-fp16",
+  "dense-finfo_min-D512-129x520-h2_2-fp16", "dense-finfo_min-D512-129x520-h4_1-fp16", "dense-minus_1e4-D1024-129x520-h2_2-fp16",
+  "dense-minus_1e4-D1024-129x520-h4_1-fp16", "keybias-finfo_min-D1024-129x520-h2_2-fp16", "keybias-finfo_min-D1024-129x520-h4_1-fp16",
+  "keybias-finfo_min-D320-129x520-h2_2-fp16", "keybias-finfo_min-D320-129x520-h4_1-fp16", "keybias-finfo_min-D512-129x520-h2_2-fp16",
+  "keybias-finfo_min-D512-129x520-h4_1-fp16", "keybias-minus_1e4-D1024-129x520-h2_2-fp16", "keybias-minus_1e4-D1024-129x520-h4_1-fp16",
+  "keybias-minus_1e4-D320-129x520-h4_1-fp16", "keybias-minus_1e4-D512-129x520-h2_2-fp16", "keybias-minus_1e4-D512-129x520-h4_1-fp16",
 ))
 
 
@@ -179,19 +218,47 @@ def test_the_other_tiles_and_bias_builds(hip, D):
   print(f"forced tiles / key bias / bool D={D}: worst error / allowance {worst:.3f}")
 
 
+def _short_query_launches(hip, case, forms, equal_in_launch_merge=False):
+  """A short-query case (``model_values.short_query_cases``) built ONCE, its property asserted on the tensors the launches read, then one launch per form
+  ``(num_splits, causal)``, each against float64 through ``check_case`` -> (worst error / allowance, the property's figures, the plans).  The launch must be
+  the short-query tile the head dim is listed with in ``SHORT_QUERY_TILES`` (the ``ND=`` tag of the kernel name, the keys per tile), GQA heads packed into
+  rows.  ``equal_in_launch_merge``: every form that splits the KV axis runs again with ``merge_in_launch=True`` and must return the merge kernel's bits."""
+  B, hq, hkv, nq, nkv, d = case["shape"]
+  nd, bc = mv.SHORT_QUERY_TILES[d]
+  assert bc == case["block_keys"]
+  q, k, v = _cuda(*mv.build(case, bc)[:3])
+  fig = mv.assert_short_query_property(case, q, k)
+  refs, worst, plans = {}, 0.0, []
+  for splits, causal in forms:
+    if causal not in refs:
+      refs[causal] = mv.attend_each_batch(q, k, v, None, causal)
+    plan = {}
+    o, lse = hip.forward(q, k, v, None, causal, d ** -0.5, num_splits=splits, plan_out=plan, merge_in_launch=False)
+    name = f"{case['variant']} {case['shape']} {kr.DTYPE_NAME[case['dtype']]} seed {case['seed']} causal={causal} splits={splits} [{plan['kernel']}]"
+    assert plan["variant"] == 1 and plan["block_keys"] == bc and f"<{kr.DTYPE_NAME[case['dtype']]}, {d}, ND={nd}>" in plan["kernel"], name
+    assert plan["packed"] == (hq != hkv), name
+    assert plan["splits"] == 1 if splits == 1 else plan["splits"] > 1 if splits else plan["splits"] >= 1, name  # (0: the plan's own count)
+    assert ("ffpa_fwd_merge_kernel" in plan["kernel"]) == (plan["splits"] > 1), name
+    REACHED.update(_family(plan["kernel"]))
+    worst = max(worst, mv.check_case(o, lse, refs[causal], dict(case, causal=causal), v=v, name=name))
+    if equal_in_launch_merge and plan["splits"] > 1:
+      plan2 = {}
+      o2, lse2 = hip.forward(q, k, v, None, causal, d ** -0.5, num_splits=splits, plan_out=plan2, merge_in_launch=True)
+      assert plan2["splits"] == plan["splits"] and "in-launch split merge" in plan2["kernel"], (name, plan2)
+      assert torch.equal(o2, o) and torch.equal(lse2, lse), f"{name}: the in-launch merge and the merge kernel differ"
+    plans.append(plan)
+  return worst, fig, plans
+
+
 @pytest.mark.parametrize("D", (128, 512, 1024))
 @pytest.mark.parametrize("variant", mv.SHORT_QUERY_VARIANTS)
 def test_short_query_split_kv_on_model_values(hip, variant, D):
   """Nq in {1, 7} against 2000 keys, the KV axis split by the plan and into 4: a sink in split 0 with nothing comparable in the others, a staircase whose top
-  sits in the last split — the merge has to weigh partials whose LSEs are dozens of units apart."""
-  family, knobs, _ = mv.VARIANTS[variant]
+  sits in the last split — the merge has to weigh partials whose LSEs are dozens of units apart.  The cases are ``model_values.short_query_cases``: each
+  asserts, on the rows it computes, that it has what this docstring says (``assert_short_query_property``)."""
   worst = 0.0
-  for nq in (1, 7):
-    for hq, hkv in mv.HEADS:
-      for dtype in mv.DTYPES:
-        for splits in (0, 4):
-          case = {"variant": variant, "family": family, "knobs": dict(knobs), "shape": (1, hq, hkv, nq, 2000, D), "dtype": dtype, "causal": False, "seed": 77 + nq + hq}
-          worst = max(worst, _dense(hip, case, num_splits=splits))
+  for case in mv.short_query_cases(variant, D):
+    worst = max(worst, _short_query_launches(hip, case, ((0, False), (4, False)))[0])
   print(f"short query {variant} D={D}: worst error / allowance {worst:.3f}")
 
 
@@ -306,7 +373,7 @@ def test_finfo_min_rows_are_sdpa_math_rows(hip, dtype, kind):
 def test_every_built_forward_family_was_reached(hip):
   """One launch per forward kernel family the library builds, each on a family of this file and inside the allowance, by the kernel name the launch itself
   reports (``plan_out``).  Self-contained: no other test has to have run.  (The library has no call that lists its kernel families; this list is the
-  ``Unit`` table of ffpa_attn_amd/build.py read by hand: dense 16x16x32 MK = 0 ... 3, paired tiles, wide-row tile, short-query split-D, the two merges,
+  ``Unit`` table of ffpa_attn_amd/build.py read by hand: dense 16x16x32 MK = 0 ... 3, paired tiles, wide-row tile, split-D with ND = 1 (prefill at head dims <= 64: plain, BTILE, DROP) / 2 / 4 (short-query: plain, DROP), the two merges,
   packed.)"""
   reached = set()
   base = {"variant": "peaked", "family": "peaked", "knobs": {}, "dtype": torch.bfloat16, "causal": False, "seed": 41}
@@ -318,12 +385,19 @@ def test_every_built_forward_family_was_reached(hip):
     (dict(mask, shape=(2, 4, 1, 64, 700, 512)), {}),                                                      # MK = 1
     (dict(mask, shape=(2, 4, 1, 64, 700, 512)), {"builder": _key_padding_builder}),                       # MK = 3
     (dict(mask, shape=(2, 4, 1, 64, 700, 512), variant="hf_mask_neg_inf", knobs={"kind": "neg_inf"}), {"builder": _bool_builder}),  # MK = 2
-    (dict(base, shape=(1, 4, 1, 7, 2000, 512)), {"num_splits": 4}),                                       # short-query split-D + merge
+    (dict(base, shape=(1, 4, 1, 7, 2000, 512)), {"num_splits": 4}),                                       # short-query split-D, ND = 4 + merge
+    (dict(base, shape=(1, 4, 1, 7, 2000, 320)), {"num_splits": 4}),                                       # ... ND = 2
+    (dict(base, shape=(1, 4, 1, 129, 513, 64)), {}),                                                      # split-D prefill (head dims <= 64): ND = 1
+    (dict(base, shape=(1, 4, 1, 129, 520, 64), variant="alibi_16bit", family="alibi", knobs={"bias_dtype": None}), {}),  # ... with LDS-staged 16-bit bias tiles
+    (dict(base, shape=(1, 4, 1, 129, 513, 64)), {"dropout": True}),                                       # the three DROP builds
+    (dict(base, shape=(1, 4, 1, 7, 2000, 320)), {"dropout": True, "num_splits": 4}),
+    (dict(base, shape=(1, 4, 1, 7, 2000, 512)), {"dropout": True, "num_splits": 4}),
   ]
   for case, kw in launches:
     before = set(REACHED)
     REACHED.clear()
-    _dense(hip, case, **kw)
+    kw = dict(kw)
+    (_dense_dropout if kw.pop("dropout", False) else _dense)(hip, case, **kw)
     reached |= REACHED
     REACHED.update(before)
   # the packed kernel, by the plan of the launch itself
@@ -336,5 +410,7 @@ def test_every_built_forward_family_was_reached(hip):
   reached |= _family(plan["kernel"])
   mv.check_case(o.transpose(0, 1)[None], None, mv.attend(q, k, v), case, v=v, name="packed")
   want = {"ffpa_fwd_m16_kernel MK=0", "ffpa_fwd_m16_kernel MK=1", "ffpa_fwd_m16_kernel MK=2", "ffpa_fwd_m16_kernel MK=3", "ffpa_fwd_m16_kernel MK=0 PAIR",
-          "ffpa_fwd_m16w_kernel MK=0", "ffpa_fwd_split_d_kernel", "ffpa_fwd_merge_kernel", "ffpa_fwd_m16_varlen_kernel"}
+          "ffpa_fwd_m16w_kernel MK=0", "ffpa_fwd_split_d_kernel ND=1", "ffpa_fwd_split_d_kernel ND=2", "ffpa_fwd_split_d_kernel ND=4",
+          "ffpa_fwd_split_d_kernel ND=1 BTILE", "ffpa_fwd_split_d_kernel ND=1 DROP", "ffpa_fwd_split_d_kernel ND=2 DROP", "ffpa_fwd_split_d_kernel ND=4 DROP",
+          "ffpa_fwd_merge_kernel", "ffpa_fwd_m16_varlen_kernel"}
   assert want <= reached, f"not reached: {sorted(want - reached)}; reached: {sorted(reached)}"

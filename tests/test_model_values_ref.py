@@ -1,7 +1,7 @@
-"""tests/model_values.py without a GPU: on every case tests/test_fwd_model_values_gpu.py runs, (1) the C oracle — the kernels' arithmetic on the CPU, blocked
+"""tests/model_values.py without a GPU: on every case tests/test_fwd_model_values_gpu.py and tests/test_fwd_split_d_gpu.py run (the short-query cases included), (1) the C oracle — the kernels' arithmetic on the CPU, blocked
 by the tile the launch plan picks — stays inside ``kvcache_ref.allowance`` of the float64 reference with no element left out, so a failure of a kernel on
 the GPU is a finding about the kernel, not about the inputs; (2) every family has the property its docstring promises; (3) the float64 reference is
-``torch`` SDPA in float64; (4) ``kvcache_ref.check`` rejects the mistakes these inputs exist to catch."""
+``torch`` SDPA in float64; (4) ``kvcache_ref.check`` rejects the mistakes these inputs exist to catch; (5) every short-query case has the property it is there for at the first seed that gives it."""
 
 import numpy as np
 import pytest
@@ -41,7 +41,7 @@ def _oracle(q, k, v, bias, causal, block_keys, threshold=mv.RESCALE_THRESHOLD):
   return out, torch.from_numpy(lse)
 
 
-@pytest.mark.parametrize("D", mv.HEAD_DIMS)
+@pytest.mark.parametrize("D", mv.HEAD_DIMS + mv.SMALL_HEAD_DIMS)
 @pytest.mark.parametrize("variant", list(mv.VARIANTS))
 def test_the_oracle_alone_stays_inside_the_allowance_on_every_case(hip, variant, D):
   worst, worst_masked = 0.0, 0.0
@@ -58,14 +58,56 @@ def test_the_oracle_alone_stays_inside_the_allowance_on_every_case(hip, variant,
   print(f"{variant} D={D}: worst error / allowance {worst:.3f}" + (f"; wholly masked rows need {worst_masked:.3f} of their margin" if worst_masked else ""))
 
 
+@pytest.mark.parametrize("D", mv.SMALL_HEAD_DIMS)
+@pytest.mark.parametrize("variant", mv.SPLIT_VARIANTS)
+def test_the_oracle_alone_stays_inside_the_allowance_on_every_split_case(hip, variant, D):
+  """The (129, 3100) cases the head dims <= 64 run with the KV axis cut into 3 ranges: the oracle in one walk over the plan's tiles."""
+  worst = 0.0
+  for case in mv.split_cases(variant, D):
+    plan = _plan(hip, case, None)
+    assert plan["block_keys"] == 128 and -(-case["shape"][4] // 128) // 8 == 3, plan  # (ffpa_capi.hip clamp_splits: at least 8 tiles per range of a prefill launch)
+    q, k, v, bias, rows, value = mv.build(case, plan["block_keys"])
+    ref = mv.attend(q, k, v, bias, case["causal"])
+    out, lse = _oracle(q, k, v, bias, case["causal"], plan["block_keys"])
+    name = f"{variant} {case['shape']} {kr.DTYPE_NAME[case['dtype']]} causal={case['causal']} [{plan['kernel']}]"
+    worst = max(worst, mv.check_case(out, lse, ref, case, v=v, name=name))
+  print(f"3 KV ranges {variant} D={D}: worst error / allowance {worst:.3f}")
+
+
+@pytest.mark.parametrize("nq", (1, 7))
+@pytest.mark.parametrize("D", mv.SHORT_QUERY_HEAD_DIMS)
+@pytest.mark.parametrize("variant", mv.SHORT_QUERY_VARIANTS)
+def test_the_oracle_alone_stays_inside_the_allowance_on_every_short_query_case(hip, variant, D, nq):
+  """The short-query cases: each has the property it is there for (``assert_short_query_property``, at the seed the case carries — the FIRST from its base
+  at which it holds), was built for the tile the plan picks, and the C oracle, blocked by that tile in one walk, stays inside the allowance."""
+  worst, figs = 0.0, []
+  for case in (c for c in mv.short_query_cases(variant, D) if c["shape"][3] == nq):
+    plan = _plan(hip, case, None)
+    assert plan["variant"] == 1 and plan["block_keys"] == case["block_keys"] == mv.SHORT_QUERY_TILES[D][1], (plan, case)
+    q, k, v, bias, _, _ = mv.build(case, plan["block_keys"])
+    fig = mv.assert_short_query_property(case, q, k, bias)
+    B, hq, hkv, nq, nkv, d = case["shape"]
+    base = 77 + nq + hq
+    for seed in range(base, case["first_seed"]):  # (a case that does not hold at its base: no earlier seed does either)
+      early = dict(case, seed=seed)
+      qe, ke = mv.build(early, plan["block_keys"])[:2]
+      assert not mv.short_query_property_holds(early, mv.short_query_property(early, qe, ke)), (variant, case["shape"], seed)
+    ref = mv.attend_each_batch(q, k, v, bias, case["causal"])
+    out, lse = _oracle(q, k, v, bias, case["causal"], plan["block_keys"])
+    name = f"{variant} {case['shape']} {kr.DTYPE_NAME[case['dtype']]} seed {case['seed']} [{plan['kernel']}]"
+    worst = max(worst, mv.check_case(out, lse, ref, case, v=v, name=name))
+    figs.append(f"Nq {nq} heads {hq}/{hkv} {kr.DTYPE_NAME[case['dtype']]} seed {case['seed']}: {fig['sink rows']} sink rows of {fig['rows']}, mean pmax {fig['mean pmax']:.2f}")
+  print(f"short query {variant} D={D} Nq={nq}: worst error / allowance {worst:.3f}\n  " + "\n  ".join(figs))
+
+
 def _mean_pmax(ref, visible=None):
   p = ref[2]
   return float(p.mean()) if visible is None else float(p[visible].mean())
 
 
-@pytest.mark.parametrize("D", mv.HEAD_DIMS)
+@pytest.mark.parametrize("D", mv.HEAD_DIMS + mv.SMALL_HEAD_DIMS)
 def test_families_have_the_properties_they_state(D):
-  for nq, nkv in mv.SEQ_SHAPES:
+  for nq, nkv in mv.SEQ_SHAPES + mv.BIAS_SEQ_SHAPES:
     for dtype in mv.DTYPES:
       shape = (1, 4, 1, nq, nkv, D)
       scale = D ** -0.5
@@ -91,7 +133,7 @@ def test_families_have_the_properties_they_state(D):
       assert 55.0 <= float(s.abs().max()) <= 140.0, float(s.abs().max())
       assert float(mv.attend(q, k, v)[1].abs().max()) >= 40.0  # (the LSE is compared at that magnitude)
       # staircases: the row maximum of consecutive KV tiles differs by the step, in log2 units
-      for bc in {128: (64,), 320: (64, 128), 512: (64,), 1024: (32, 64)}[D]:  # (the KV tiles the launches of this head dim use)
+      for bc in {40: (64, 128), 64: (64, 128), 128: (64,), 320: (64, 128), 512: (64,), 1024: (32, 64)}[D]:  # (the KV tiles the launches of this head dim use)
         for step in mv.STAIR_STEPS:
           for up in (True, False):
             q, k, v = (mv.staircase_up if up else mv.staircase_down)(shape, dtype, 3, block_keys=bc, step=step)
@@ -197,3 +239,51 @@ def test_check_rejects_the_mistakes_these_inputs_exist_to_catch(hip, dtype):
     assert _rejected(out, None, ref, case_m, v=v, value=value)      # 0 in the rows the float64 restatement leaves without a key
     out[nan_rows[:, None, :].expand(-1, 2, -1)] = float("nan")      # ... NaN as the kernels leave them
     assert _rejected(out, None, ref, case_m, v=v, value=value)
+
+
+def _as_out(o, dtype):
+  """A float64 result ``[B, Nq, Hq, D]`` as a kernel would hand it over: ``[B, Hq, Nq, D]``, 16 bits."""
+  return o.transpose(1, 2).to(dtype)
+
+
+def _two_range_merge_against_range_0(q, k, v):
+  """Float64 attention as a two-range KV split computes it — each range normalised against its OWN row maximum m_i, with row sum l_i, the merge weighing
+  range i by l_i exp(m_i - M) — but with range 0's maximum in BOTH weights: l_i exp(m_0 - M), that is, l_i alone.  -> ``[B, Nq, Hq, D]``."""
+  outs = []
+  for b in range(q.size(0)):
+    s = mv.scores(q[b:b + 1], k[b:b + 1])
+    vv = v[b:b + 1].double().repeat_interleave(q.size(1) // k.size(1), dim=1)
+    half = k.size(2) // 2
+    o, w = [], []
+    for lo, hi in ((0, half), (half, k.size(2))):
+      e = torch.exp(s[..., lo:hi] - s[..., lo:hi].amax(dim=-1, keepdim=True))
+      l = e.sum(dim=-1, keepdim=True)
+      o.append(torch.matmul(e / l, vv[:, :, lo:hi]))
+      w.append(l)
+    outs.append(((w[0] * o[0] + w[1] * o[1]) / (w[0] + w[1])).transpose(1, 2))
+  return torch.cat(outs)
+
+
+@pytest.mark.parametrize("nq", (1, 7))
+@pytest.mark.parametrize("D", mv.SHORT_QUERY_HEAD_DIMS)
+@pytest.mark.parametrize("variant", ("sink", "staircase_up_8.5", "large_logits"))
+def test_check_rejects_the_mistakes_the_short_query_cases_exist_to_catch(variant, D, nq):
+  """What a KV-split launch can get wrong that one walk cannot, on EVERY short-query case of the variant: (sink) key 0 — the first range's weight — lost;
+  (staircase_up_8.5) the last range of a 4-way split — the staircase's top — lost; (large_logits) a merge whose weights never see the second range's
+  maximum.  The honest float64 result passes, each mistake is rejected."""
+  for case in (c for c in mv.short_query_cases(variant, D) if c["shape"][3] == nq):
+    bc = case["block_keys"]
+    q, k, v = mv.build(case, bc)[:3]
+    ref = mv.attend_each_batch(q, k, v)
+    kw = dict(v=v, value=None, name=f"{variant} {case['shape']}")
+    assert not _rejected(_as_out(ref[0], case["dtype"]), ref[1].float(), ref, case, **kw)
+    if variant == "sink":
+      wrong = mv.attend_each_batch(q, k[:, :, 1:], v[:, :, 1:])[0]
+    elif variant == "staircase_up_8.5":
+      tiles = -(-k.size(2) // bc)
+      cut = 3 * -(-tiles // 4) * bc  # (ffpa_capi.hip make_plan: ranges of ceil(tiles / splits) tiles)
+      assert 0 < cut < k.size(2)
+      wrong = mv.attend_each_batch(q, k[:, :, :cut], v[:, :, :cut])[0]
+    else:
+      wrong = _two_range_merge_against_range_0(q, k, v)
+    assert _rejected(_as_out(wrong, case["dtype"]), None, ref, case, **kw), (variant, case["shape"], case["dtype"])
