@@ -289,6 +289,39 @@ class FfpaMlaSparseTopkParams(ctypes.Structure):
   ]
 
 
+class FfpaMlaIndexScoresParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_mla_index_scores_params`` (include/ffpa_attn.h): the indexer's score launch in front of the selection."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("q_index", ctypes.c_void_p),
+    ("k_index_cache", ctypes.c_void_p),
+    ("weights", ctypes.c_void_p),
+    ("cache_seqlens", ctypes.c_void_p),
+    ("cu_seqlens_q", ctypes.c_void_p),
+    ("block_table", ctypes.c_void_p),
+    ("scores", ctypes.c_void_p),
+    ("q_stride", ctypes.c_int64 * 2),
+    ("k_stride", ctypes.c_int64 * 2),
+    ("weights_stride", ctypes.c_int64),
+    ("block_table_stride", ctypes.c_int64),
+    ("scores_stride", ctypes.c_int64),
+    ("T", ctypes.c_int32),
+    ("heads", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("N", ctypes.c_int32),
+    ("B", ctypes.c_int32),
+    ("W", ctypes.c_int32),
+    ("page_size", ctypes.c_int32),
+    ("num_pages", ctypes.c_int32),
+    ("causal", ctypes.c_int32),
+    ("dtype", ctypes.c_int32),
+    ("chunk_keys", ctypes.c_int32),
+    ("reserved2", ctypes.c_int32),
+  ]
+
+
 class FfpaMlaAppendVarlenParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_mla_append_varlen_params`` (include/ffpa_attn.h): the latent append of a ragged step."""
 
@@ -521,6 +554,7 @@ _BINDINGS = (
   ("ffpa_attn_varlen_mla_sparse_ds_fwd_workspace_bytes", _MLA_SPARSE, _SIZE, 7),
   ("ffpa_attn_mla_ds_store", [_P(FfpaMlaDsStoreParams), _VOID], _INT, 7),
   ("ffpa_attn_mla_sparse_topk_slots", [_P(FfpaMlaSparseTopkParams), _VOID], _INT, 7),
+  ("ffpa_attn_mla_index_scores", [_P(FfpaMlaIndexScoresParams), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
@@ -616,7 +650,8 @@ def _stamped(cls):
   """A zeroed parameter struct with its size — and, where the struct carries one (``ffpa_paged_kv`` / ``ffpa_tree_mask`` / ``ffpa_window`` / ``ffpa_mla`` ride next to a versioned struct), the ABI version — filled in."""
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
-  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse, FfpaMlaFp8, FfpaMlaDsStoreParams, FfpaMlaSparseTopkParams):
+  if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse, FfpaMlaFp8, FfpaMlaDsStoreParams, FfpaMlaSparseTopkParams,
+                 FfpaMlaIndexScoresParams):
     p.abi_version = ABI_VERSION
   return p
 
@@ -2223,6 +2258,63 @@ def _mla_sparse_topk_slots_fake(scores, topk, cache_seqlens, block_table, page_s
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_slots_hip")
 def _mla_sparse_slots_fake(positions, cache_seqlens, block_table, page_size, cu_seqlens_q):
   return torch.empty_like(positions, memory_format=torch.contiguous_format), positions.new_empty((positions.size(0),))
+
+
+# The indexer's score launch in front of the selection (ffpa_mla_index_scores, ffpa_attn_amd/kvcache.py, where the arguments are checked)
+MLA_INDEX_CHUNK_KEYS = 1024  # key positions of a token that are one workgroup's (FFPA_MLA_INDEX_CHUNK_KEYS, include/ffpa_attn.h)
+
+
+def mla_index_scores(q_index: torch.Tensor, k_index_cache: torch.Tensor, weights: torch.Tensor, cache_seqlens: torch.Tensor, block_table: "torch.Tensor | None",
+                     max_seqlen_k: int, cu_seqlens_q: "torch.Tensor | None", causal: bool, *, chunk_keys: int = 0) -> torch.Tensor:
+  """One launch of ``ffpa_attn_mla_index_scores``: ``q_index [T, Hi, 128]``, ``k_index_cache [num_pages, page_size, (1,) 128]`` (or ``[B, capacity, 128]``
+  without a table), ``weights [T, Hi]`` float32 -> ``scores [T, max_seqlen_k]`` float32 on the device, -inf tail included.  Asynchronous, nothing read back to the
+  host.  ``chunk_keys``: the developer override of ``MLA_INDEX_CHUNK_KEYS`` (256 / 512 / 1024; tools/gpu_mla_index_scores_ab.py)."""
+  name = "ffpa_attn::_mla_index_scores_hip"
+  if not q_index.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{q_index.device.type}' (the HIP kernel needs a GPU tensor)")
+  if q_index.dtype not in _DTYPE or k_index_cache.dtype != q_index.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q_index and k_index_cache of one dtype, got {q_index.dtype}, {k_index_cache.dtype}")
+  lib = load_library()
+  T, Hi, D = q_index.shape
+  scores = torch.empty((T, max_seqlen_k), dtype=torch.float32, device=q_index.device)
+  if T == 0:
+    return scores
+  if k_index_cache.dim() == 4:  # [num_pages, page_size, 1, 128]: the one index head
+    k_index_cache = k_index_cache[:, :, 0]
+  cache_seqlens = cache_seqlens.contiguous()
+  p = _stamped(FfpaMlaIndexScoresParams)
+  p.q_index, p.k_index_cache, p.weights, p.cache_seqlens, p.scores = (q_index.data_ptr(), k_index_cache.data_ptr(), weights.data_ptr(), cache_seqlens.data_ptr(),
+                                                                      scores.data_ptr())
+  if cu_seqlens_q is not None:
+    cu_seqlens_q = cu_seqlens_q.contiguous()
+    p.cu_seqlens_q = cu_seqlens_q.data_ptr()
+  if block_table is not None:
+    p.block_table, p.block_table_stride, p.W = block_table.data_ptr(), block_table.stride(0), block_table.size(1)
+  p.q_stride[0], p.q_stride[1] = q_index.stride(0), q_index.stride(1)
+  p.k_stride[0], p.k_stride[1] = k_index_cache.stride(0), k_index_cache.stride(1)
+  p.weights_stride, p.scores_stride = weights.stride(0), max_seqlen_k
+  p.T, p.heads, p.head_dim, p.N, p.B, p.causal, p.dtype, p.chunk_keys = T, Hi, D, max_seqlen_k, cache_seqlens.numel(), int(bool(causal)), _DTYPE[q_index.dtype], chunk_keys
+  p.num_pages, p.page_size = k_index_cache.size(0), k_index_cache.size(1)
+  rc = _call_on_stream(lib.ffpa_attn_mla_index_scores, q_index.device, ctypes.byref(p))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_mla_index_scores")
+  return scores
+
+
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_index_scores_hip",
+  "(Tensor q_index, Tensor k_index_cache, Tensor weights, Tensor cache_seqlens, Tensor? block_table, int max_seqlen_k, Tensor? cu_seqlens_q, bool causal) -> Tensor",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_index_scores_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_index_scores_hip_torch_op(q_index, k_index_cache, weights, cache_seqlens, block_table, max_seqlen_k, cu_seqlens_q, causal):
+  return mla_index_scores(q_index, k_index_cache, weights, cache_seqlens, block_table, int(max_seqlen_k), cu_seqlens_q, causal)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_index_scores_hip")
+def _mla_index_scores_fake(q_index, k_index_cache, weights, cache_seqlens, block_table, max_seqlen_k, cu_seqlens_q, causal):
+  return q_index.new_empty((q_index.size(0), max_seqlen_k), dtype=torch.float32)
 
 
 # The latent append of a ragged step (ffpa_attn_varlen_with_kvcache_mla(kv=)): token rows packed by cu_seqlens_q, in front of the attention launch

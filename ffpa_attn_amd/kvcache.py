@@ -1113,6 +1113,121 @@ def ffpa_mla_sparse_slots(
   return torch.ops.ffpa_attn._mla_sparse_slots_hip(positions, cache_seqlens, block_table, page_size, cu_seqlens_q)
 
 
+_MLA_INDEX_DIM = 128      # columns of an index query head / of an index key
+_MLA_INDEX_HEADS = (32, 64)  # the index head counts the score kernel is built for
+
+
+def _mla_index_scores_check(name, q_index, k_index_cache, weights, cache_seqlens, block_table, max_seqlen_k, cu_seqlens_q) -> None:
+  """The argument checks of ``ffpa_mla_index_scores``, in ``_mla_sparse_select_check``'s style: ``TypeError`` for types and dtypes, ``NotImplementedError`` for
+  a tensor that requires grad and for a head count that is not built, ``ValueError`` for shapes, devices and strides; nothing is read from the device."""
+  tensors = (("q_index", q_index), ("k_index_cache", k_index_cache), ("weights", weights), ("cache_seqlens", cache_seqlens)) + \
+            ((("block_table", block_table),) if block_table is not None else ()) + ((("cu_seqlens_q", cu_seqlens_q),) if cu_seqlens_q is not None else ())
+  for nm, t in tensors:
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  if q_index.dtype not in (torch.bfloat16, torch.float16):
+    raise TypeError(f"{name}: q_index must be bf16 or fp16, got {q_index.dtype}")
+  if k_index_cache.dtype != q_index.dtype:
+    raise TypeError(f"{name}: k_index_cache must have q_index's dtype {q_index.dtype}, got {k_index_cache.dtype}" +
+                    (" (FP8 index keys are not served)" if k_index_cache.dtype in (torch.float8_e4m3fn, torch.uint8) else ""))
+  if weights.dtype != torch.float32:
+    raise TypeError(f"{name}: weights must be torch.float32, got {weights.dtype}")
+  for nm, t in tensors[3:]:
+    if t.dtype != torch.int32:
+      raise TypeError(f"{name}: {nm} must be an int32 tensor, got {t.dtype}")
+  if isinstance(max_seqlen_k, bool) or not isinstance(max_seqlen_k, int):
+    raise TypeError(f"{name}: max_seqlen_k must be an int, got {max_seqlen_k!r}")
+  if max_seqlen_k < 1 or max_seqlen_k > 1 << 30:
+    raise ValueError(f"{name}: max_seqlen_k must lie in [1, 2^30], got {max_seqlen_k}")
+  if q_index.dim() != 3 or q_index.size(2) != _MLA_INDEX_DIM:
+    raise ValueError(f"{name}: q_index must be [T, Hi, {_MLA_INDEX_DIM}] (the index heads are {_MLA_INDEX_DIM} wide), got {tuple(q_index.shape)}")
+  T, Hi, D = q_index.shape
+  if Hi not in _MLA_INDEX_HEADS:
+    raise NotImplementedError(f"{name}: the score kernel is built for Hi in {_MLA_INDEX_HEADS} index heads, got {Hi}")
+  if cache_seqlens.dim() != 1 or cache_seqlens.numel() < 1:
+    raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [B] with B >= 1, got {tuple(cache_seqlens.shape)}")
+  B = cache_seqlens.numel()
+  paged = block_table is not None
+  k = k_index_cache
+  if k.dim() == 4 and paged and k.size(2) != 1:
+    raise ValueError(f"{name}: the index keys have ONE head, got k_index_cache {tuple(k.shape)}")
+  if (k.dim() != 3 and not (paged and k.dim() == 4)) or k.size(-1) != D or k.size(0) < 1:
+    raise ValueError(f"{name}: k_index_cache must be " + (f"[num_pages, page_size, {D}] or [num_pages, page_size, 1, {D}]" if paged else f"[B={B}, capacity, {D}]") +
+                     f", got {tuple(k.shape)}")
+  if not paged and k.size(0) != B:
+    raise ValueError(f"{name}: without a block_table k_index_cache must be [B={B}, capacity, {D}], got {tuple(k.shape)}")
+  if k.size(1) < 64 or k.size(1) % 64 != 0:
+    raise ValueError(f"{name}: the {'page size' if paged else 'capacity'} must be a positive multiple of 64, got {k.size(1)}")
+  if weights.dim() != 2 or tuple(weights.shape) != (T, Hi):
+    raise ValueError(f"{name}: weights must be [T={T}, Hi={Hi}], got {tuple(weights.shape)}")
+  if cu_seqlens_q is not None and (cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() != B + 1):
+    raise ValueError(f"{name}: cu_seqlens_q must be an int32 tensor [B + 1 = {B + 1}], got {tuple(cu_seqlens_q.shape)}")
+  if cu_seqlens_q is None and T % B != 0:
+    raise ValueError(f"{name}: without cu_seqlens_q the T={T} rows are [B, Sq] flattened: T must be a multiple of B={B}")
+  if paged and (block_table.dim() != 2 or block_table.size(0) != B or block_table.size(1) < 1):
+    raise ValueError(f"{name}: block_table must be [B={B}, pages_per_seq >= 1] — one row per SEQUENCE —, got {tuple(block_table.shape)}")
+  for nm, t in (("q_index", q_index), ("k_index_cache", k), ("weights", weights)) + ((("block_table", block_table),) if paged else ()):
+    if t.stride(-1) != 1:
+      raise ValueError(f"{name}: {nm} must have a contiguous last dimension")
+  for nm, t, dims in (("q_index", q_index, (0, 1)), ("k_index_cache", k, (0, 1))):
+    if any(t.stride(d) % 8 != 0 or t.stride(d) < 0 for d in dims):  # (a first element off 16 bytes is the C layer's FFPA_ERR_MISALIGNED: nothing here reads data_ptr)
+      raise ValueError(f"{name}: the strides of {nm} must be multiples of 8 elements, got {t.stride()}")
+  if k.stride(1) < D:
+    raise ValueError(f"{name}: rows of k_index_cache must be at least {D} elements apart, got {k.stride()}")
+  for nm, t in tensors[1:]:
+    if t.device != q_index.device:
+      raise ValueError(f"{name}: {nm} must be on q_index's device, got {t.device} and {q_index.device}")
+
+
+def ffpa_mla_index_scores(
+  q_index: torch.Tensor,
+  k_index_cache: torch.Tensor,
+  weights: torch.Tensor,
+  cache_seqlens: torch.Tensor,
+  block_table: "torch.Tensor | None" = None,
+  *,
+  max_seqlen_k: int,
+  cu_seqlens_q: "torch.Tensor | None" = None,
+  causal: bool = True,
+) -> torch.Tensor:
+  """The scores of DeepSeek-V3.2's indexer ("lightning indexer"; DeepGEMM's ``fp8_mqa_logits`` / ``fp8_paged_mqa_logits``, on 16-bit index keys) in ONE launch:
+  ``scores`` float32 ``[T, N]``, ``N = max_seqlen_k``, exactly what ``ffpa_mla_sparse_topk_slots`` takes — the chain scores -> selection -> sparse attention is
+  three launches that capture into one HIP graph, nothing read back to the host.  It replaces the gather of every sequence's index keys out of the paged pool, an
+  ``einsum``, a ``relu``, the multiply by the head weights, the sum over heads and the -inf padding.
+
+  ``q_index``: ``[T, Hi, 128]``, bf16 or fp16, the step's query tokens, flat; ``Hi`` 32 or 64 (another count raises ``NotImplementedError``); unit stride in the
+  last dimension, the other strides free multiples of 8 elements.  ``k_index_cache``: the same dtype, ONE index head — paged ``[num_pages, page_size, 128]`` or
+  ``[num_pages, page_size, 1, 128]`` read through ``block_table`` int32 ``[B, W]`` (``page_size % 64 == 0``: the latent cache's table can be reused), or, without
+  a table, ``[B, capacity, 128]`` with ``capacity % 64 == 0``; row and page strides free multiples of 8 elements.  ``weights``: float32 ``[T, Hi]``, free row
+  stride — the model's ``n_heads ** -0.5``, the softmax scale and any q scale are folded in by the caller: there is no scale argument.  ``cache_seqlens``: int32
+  ``[B]``, the lengths WITH the step's index keys in the cache (no append in this call, as in the sparse attention call).
+
+  Token -> sequence, padding rows and the visible count ``n_t`` are ``ffpa_mla_sparse_topk_slots``'s rules to the letter: with ``cu_seqlens_q`` (int32
+  ``[B + 1]``) the rows are packed as the ragged latent calls pack them and rows at and past ``cu_seqlens_q[B]`` are padding; without it ``T % B == 0`` and row
+  ``t`` is token ``t % Sq`` of sequence ``t // Sq``; ``n_t = clamp(L - (S - 1 - i), 0, N)`` under ``causal``, ``clamp(L, 0, N)`` otherwise — and never more than
+  the keys the table (``W * page_size``) or the capacity can name.  Then::
+
+      scores[t, p] = sum_h weights[t, h] * max(0, sum_d q_index[t, h, d] * k[b_t, p, d])      for p < n_t
+      scores[t, p] = -inf                                                                     for n_t <= p < N   (a padding row: all -inf)
+
+  with fp32 products and sums (MFMA accumulation).  Key ``p`` of sequence ``b`` is row ``p % page_size`` of page ``block_table[b, min(p // page_size, W - 1)]``,
+  the page id clamped into ``[0, num_pages - 1]`` (a bad id never becomes a bad address: the latent kernel's rule).  The whole ``[T, N]`` tensor is a pure function
+  of the inputs, the -inf tail included — written by the same launch.  The contract is finite inputs: NaN / inf give unspecified values, never an access outside
+  the tensors.  ``T == 0`` returns an empty tensor and launches nothing.
+
+  One HIP kernel on ``v_mfma_f32_16x16x32``: a workgroup per (token, ``hip.MLA_INDEX_CHUNK_KEYS`` key positions), Q held in registers, K streamed from the pool
+  once, straight into the MFMA's layout.  Not served: FP8 index keys, an append of the step's index keys, bf16 scores, ``Hi`` other than 32 / 64."""
+  name = "ffpa_mla_index_scores"
+  _mla_index_scores_check(name, q_index, k_index_cache, weights, cache_seqlens, block_table, max_seqlen_k, cu_seqlens_q)
+  from . import hip  # noqa: F401  (registers the ffpa_attn ops)
+
+  if q_index.size(0) == 0:
+    return q_index.new_empty((0, max_seqlen_k), dtype=torch.float32)
+  return torch.ops.ffpa_attn._mla_index_scores_hip(q_index, k_index_cache, weights, cache_seqlens, block_table, max_seqlen_k, cu_seqlens_q, bool(causal))
+
+
 def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=False, ds=False):
   """The argument checks of the sparse latent calls under their own ``name``, every rule written once and in the order ``ffpa_attn_with_kvcache_mla_sparse`` has
   always made them -> ``(T, Hq)``.  ``fp8``: the pool is ``torch.float8_e4m3fn`` (``ffpa_attn_with_kvcache_mla_sparse_fp8``) — the dtype rule is the FP8 latent

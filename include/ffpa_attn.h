@@ -745,6 +745,61 @@ typedef struct ffpa_mla_sparse_topk_params {
 int ffpa_attn_mla_sparse_topk_slots(const ffpa_mla_sparse_topk_params* p, void* stream);
 
 /*
+ * THE SCORES THAT SELECTION TAKES, MADE ON THE DEVICE — DeepSeek-V3.2's indexer ("lightning indexer"; DeepGEMM's fp8_mqa_logits / fp8_paged_mqa_logits, here on
+ * 16-bit index keys): from the step's index queries, the pool of index keys and the per-head weights to scores [T, N] float32, in ONE kernel on `stream`.
+ *   Token t -> (sequence b, token i of its S) and the visible count n: ffpa_mla_sparse_topk_params's rules to the letter (cu_seqlens_q and the binary search,
+ *     rows at and past cu_seqlens_q[B] padding; or T % B == 0; n = clamp(cache_seqlens[b] - (S - 1 - i), 0, N) with `causal`, clamp(cache_seqlens[b], 0, N)
+ *     without), n additionally clamped to what the table (W * page_size keys) or the capacity can name.
+ *   scores[t, p] = sum_h weights[t, h] * max(0, sum_d q_index[t, h, d] * K[b, p, d])  for p < n,   -inf for n <= p < N (a padding row: all -inf),
+ *     fp32 products and sums (MFMA accumulation).  The whole [T, N] is written by this launch.  No scale argument: fold it into the weights.
+ *   K[b, p] is row p % page_size of page clamp(block_table[b * block_table_stride + min(p / page_size, W - 1)], 0, num_pages - 1) of k_index_cache
+ *     [num_pages, page_size, 128] by k_stride = {page, row}; block_table NULL: the cache is [B, page_size = capacity, 128], k_stride = {sequence, row}, and W and
+ *     num_pages are not looked at.  page_size % 64 == 0 either way.
+ *   Contract: finite inputs; NaN / inf give unspecified VALUES, never an access outside the tensors.
+ * FFPA_MLA_INDEX_CHUNK_KEYS key positions of a token are one workgroup's.  chunk_keys = 0 takes it and is what a caller passes; 256 / 512 / 1024 override it for the
+ * developer's sweep (tools/gpu_mla_index_scores_ab.py) — NOT a supported tuning parameter: the values and the field's meaning may change with the kernel.
+ * Checks, in this order: p NULL (FFPA_ERR_NULL_POINTER); struct_size, reserved (FFPA_ERR_BAD_ABI); dtype (FFPA_ERR_BAD_DTYPE); head_dim != 128
+ * (FFPA_ERR_BAD_HEADDIM); heads outside {32, 64} (FFPA_ERR_UNSUPPORTED); T < 0, N outside [1, 2^30], B < 1, T % B != 0 without cu_seqlens_q, causal outside
+ * {0, 1}, page_size < 64 or not a multiple of 64, with a block_table W < 1 or num_pages < 1, chunk_keys outside {0, 256, 512, 1024}, more than 2^24
+ * workgroups = T * ceil(N / chunk) (FFPA_ERR_BAD_SHAPE: 2^32 threads is what every HIP runtime launches); a negative stride, a q / k stride that is not a multiple of 8, rows of k closer than 128, scores_stride < N
+ * (FFPA_ERR_BAD_STRIDE); then, T > 0: a NULL q_index / k_index_cache / weights / cache_seqlens / scores (FFPA_ERR_NULL_POINTER), q_index / k_index_cache not
+ * 16-byte or another pointer not 4-byte aligned (FFPA_ERR_MISALIGNED), the device.
+ */
+#define FFPA_MLA_INDEX_CHUNK_KEYS 1024
+
+typedef struct ffpa_mla_index_scores_params {
+  uint32_t struct_size;          /* sizeof(ffpa_mla_index_scores_params), checked */
+  uint32_t reserved;             /* 0, checked */
+  const void* q_index;           /* device [T, heads, 128], bf16 / fp16 */
+  const void* k_index_cache;     /* device [num_pages, page_size, 128] (or [B, capacity, 128]), the same type */
+  const float* weights;          /* device [T, heads] float32 */
+  const int32_t* cache_seqlens;  /* device [B]: the lengths with the step's index keys in the cache */
+  const int32_t* cu_seqlens_q;   /* device [B + 1], or NULL: T / B tokens per sequence */
+  const int32_t* block_table;    /* device [B, W], or NULL: one page per sequence */
+  float* scores;                 /* device [T, N], written */
+  int64_t q_stride[2];           /* elements: {token, head}, multiples of 8 */
+  int64_t k_stride[2];           /* elements: {page, row}, multiples of 8 */
+  int64_t weights_stride;        /* elements: rows of weights */
+  int64_t block_table_stride;    /* elements: rows of block_table */
+  int64_t scores_stride;         /* elements: rows of scores (>= N) */
+  int32_t T;                     /* >= 0 */
+  int32_t heads;                 /* 32 / 64 */
+  int32_t head_dim;              /* 128 */
+  int32_t N;                     /* columns of scores (max_seqlen_k) */
+  int32_t B;
+  int32_t W;                     /* columns of block_table */
+  int32_t page_size;             /* rows of a page; without a block_table the capacity */
+  int32_t num_pages;
+  int32_t causal;                /* 0 / 1 */
+  int32_t dtype;                 /* FFPA_DTYPE_BF16 / FFPA_DTYPE_FP16 */
+  int32_t chunk_keys;            /* 0: FFPA_MLA_INDEX_CHUNK_KEYS (pass 0; other values are the developer's sweep) */
+  int32_t reserved2;             /* 0, checked */
+} ffpa_mla_index_scores_params;
+
+/* Launch the scores on `stream` of the CURRENT device.  Asynchronous; every bad argument returns a status before any device work.  Returns an ffpa_status. */
+int ffpa_attn_mla_index_scores(const ffpa_mla_index_scores_params* p, void* stream);
+
+/*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
  * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
  *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position
