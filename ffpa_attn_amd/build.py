@@ -82,6 +82,9 @@ def _units() -> list[Unit]:
   # none here with or without it.  -Xclang reaches the host compile too, which names the feature unknown and ignores it
   units.append(Unit("ffpa_mla_index_scores.hip", "ffpa_mla_index_scores.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                     "temps_mla_index_scores", None, True, True))
+  # the same launch over FP8 index keys, on the FP8 MFMA builtin, and the quantising append that fills their cache (no inline asm); the same guard
+  units.append(Unit("ffpa_mla_index_scores_fp8.hip", "ffpa_mla_index_scores_fp8.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                    "temps_mla_index_scores_fp8", None, True, True))
   # the KV-cache append + rotary launch (every dtype / rotary form) and the merge of two attention states (the cascade's last launch): one small TU each, no
   # inline asm — their assembly lands in directories the attention ISA rules do not read
   units.append(Unit("ffpa_kvcache_append.hip", "ffpa_kvcache_append.o", [], "temps_append", None, True, True))

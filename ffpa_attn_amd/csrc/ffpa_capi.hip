@@ -26,6 +26,7 @@
 #include "ffpa_mla_sparse_ds.h"   // (the 656-byte FP8 rows of DeepSeek-V3.2: the row format, and the store that writes them)
 #include "ffpa_mla_sparse_topk.h" // (the selection launch in front of the sparse latent calls)
 #include "ffpa_mla_index_scores.h" // (the indexer's score launch in front of the selection)
+#include "ffpa_mla_index_scores_fp8.h"  // (the same over FP8 index keys, and the quantising append of the step's index keys)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
 #include "ffpa_merge_states.h"    // (the merge of two attention states)
 #include "ffpa_mla_cascade_plan.h"  // (the plan launch of a shared-prefix step over the MLA latent cache)
@@ -2099,6 +2100,100 @@ int ffpa_attn_mla_index_scores(const ffpa_mla_index_scores_params* p, void* stre
   a.W = paged ? p->W : 1, a.num_pages = paged ? p->num_pages : p->B;  // (no table: one page per sequence)
   const int st = ffpa::launch_mla_index_scores(a, static_cast<hipStream_t>(stream));
   if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla index scores launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
+}
+
+// ---- the score launch over FP8 index keys (include/ffpa_attn.h: ffpa_mla_index_scores_fp8_params)
+int ffpa_attn_mla_index_scores_fp8(const ffpa_mla_index_scores_fp8_params* p, void* stream) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_mla_index_scores_fp8_params))
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_index_scores_fp8_params ABI mismatch: size %u (want %zu)", p->struct_size, sizeof(ffpa_mla_index_scores_fp8_params));
+  if (p->reserved != 0) return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_index_scores_fp8_params.reserved=%u must be 0", p->reserved);
+  if (p->head_dim != ffpa::kMlaIndexFp8Dim) return fail(FFPA_ERR_BAD_HEADDIM, "head_dim=%d: the index heads are %d wide", p->head_dim, ffpa::kMlaIndexFp8Dim);
+  if (p->heads != 32 && p->heads != 64) return fail(FFPA_ERR_UNSUPPORTED, "heads=%d: the score kernel is built for 32 and 64 index heads", p->heads);
+  const bool paged = p->block_table != nullptr;
+  if (p->T < 0 || p->N < 1 || p->N > (1 << 30)) return fail(FFPA_ERR_BAD_SHAPE, "T=%d must not be negative and N=%d must lie in [1, 2^30]", p->T, p->N);
+  if (p->B < 1 || (p->cu_seqlens_q == nullptr && p->T % p->B != 0))
+    return fail(FFPA_ERR_BAD_SHAPE, "B=%d must be positive and, without cu_seqlens_q, divide T=%d", p->B, p->T);
+  if (p->causal != 0 && p->causal != 1) return fail(FFPA_ERR_BAD_SHAPE, "causal=%d must be 0 or 1", p->causal);
+  if (p->page_size < 64 || p->page_size % 64 != 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "page_size=%d (without a block_table: the capacity) must be a positive multiple of 64", p->page_size);
+  if (paged && (p->W < 1 || p->num_pages < 1)) return fail(FFPA_ERR_BAD_SHAPE, "with a block_table W=%d and num_pages=%d must be positive", p->W, p->num_pages);
+  if (p->chunk_keys != 0 && p->chunk_keys != 256 && p->chunk_keys != 512 && p->chunk_keys != 1024)
+    return fail(FFPA_ERR_BAD_SHAPE, "chunk_keys=%d must be 0, 256, 512 or 1024", p->chunk_keys);
+  const int chunk = p->chunk_keys != 0 ? p->chunk_keys : FFPA_MLA_INDEX_CHUNK_KEYS;
+  if ((int64_t)p->T * ((p->N + chunk - 1) / chunk) > (1LL << 24))  // (256 threads each: 2^32 threads is what every HIP runtime launches)
+    return fail(FFPA_ERR_BAD_SHAPE, "grid of %lld workgroups is too large (at most 2^24)", (long long)p->T * ((p->N + chunk - 1) / chunk));
+  for (int64_t s : {p->q_stride[0], p->q_stride[1], p->k_page_stride, p->weights_stride, p->block_table_stride, p->scores_stride})
+    if (s < 0) return fail(FFPA_ERR_BAD_STRIDE, "stride %lld must not be negative", (long long)s);
+  if (p->q_stride[0] % 16 != 0 || p->q_stride[1] % 16 != 0 || p->k_page_stride % 16 != 0)
+    return fail(FFPA_ERR_BAD_STRIDE, "q_stride {%lld, %lld} / k_page_stride %lld must be multiples of 16 bytes", (long long)p->q_stride[0], (long long)p->q_stride[1],
+                (long long)p->k_page_stride);
+  if (p->k_page_stride < (int64_t)p->page_size * ffpa::kMlaIndexFp8RowBytes)
+    return fail(FFPA_ERR_BAD_STRIDE, "k_page_stride=%lld: a page of %d keys is %lld bytes", (long long)p->k_page_stride, p->page_size,
+                (long long)p->page_size * ffpa::kMlaIndexFp8RowBytes);
+  if (p->scores_stride < p->N) return fail(FFPA_ERR_BAD_STRIDE, "scores_stride=%lld is smaller than N=%d", (long long)p->scores_stride, p->N);
+  if (p->T == 0) return FFPA_OK;
+  if (!p->q_index || !p->k_index_cache || !p->weights || !p->cache_seqlens || !p->scores)
+    return fail(FFPA_ERR_NULL_POINTER, "q_index / k_index_cache / weights / cache_seqlens / scores must be non-NULL");
+  if (!aligned16(p->q_index) || !aligned16(p->k_index_cache)) return fail(FFPA_ERR_MISALIGNED, "q_index / k_index_cache must be 16-byte aligned");
+  for (const void* ptr : {(const void*)p->weights, (const void*)p->cache_seqlens, (const void*)p->cu_seqlens_q, (const void*)p->block_table, (const void*)p->scores})
+    if (reinterpret_cast<uintptr_t>(ptr) & 3u) return fail(FFPA_ERR_MISALIGNED, "weights / cache_seqlens / cu_seqlens_q / block_table / scores must be 4-byte aligned");
+  int rc;
+  if ((rc = check_device()) != FFPA_OK) return rc;
+  ffpa::MlaIndexScoresFp8Args a;
+  memset(&a, 0, sizeof(a));
+  a.q = static_cast<const uint8_t*>(p->q_index), a.k = static_cast<const uint8_t*>(p->k_index_cache), a.w = p->weights, a.cache_seqlens = p->cache_seqlens;
+  a.cu_seqlens_q = p->cu_seqlens_q, a.block_table = p->block_table, a.scores = p->scores;
+  a.s_q_tok = p->q_stride[0], a.s_q_head = p->q_stride[1], a.s_k_page = p->k_page_stride;
+  a.s_w = p->weights_stride, a.s_table = p->block_table_stride, a.s_out = p->scores_stride;
+  a.T = p->T, a.N = p->N, a.B = p->B, a.page_size = p->page_size, a.Hi = p->heads, a.causal = p->causal, a.chunk = chunk;
+  a.W = paged ? p->W : 1, a.num_pages = paged ? p->num_pages : p->B;  // (no table: one page per sequence)
+  const int st = ffpa::launch_mla_index_scores_fp8(a, static_cast<hipStream_t>(stream));
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla index scores (fp8) launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
+}
+
+// ---- the quantising append of the step's index keys (include/ffpa_attn.h: ffpa_mla_index_k_append_fp8_params)
+int ffpa_attn_mla_index_k_append_fp8(const ffpa_mla_index_k_append_fp8_params* p, void* stream) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_mla_index_k_append_fp8_params))
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_index_k_append_fp8_params ABI mismatch: size %u (want %zu)", p->struct_size, sizeof(ffpa_mla_index_k_append_fp8_params));
+  if (p->reserved != 0 || p->reserved2 != 0)
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_mla_index_k_append_fp8_params.reserved=%u / reserved2=%d must be 0", p->reserved, p->reserved2);
+  if (p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
+  if (p->head_dim != ffpa::kMlaIndexFp8Dim) return fail(FFPA_ERR_BAD_HEADDIM, "head_dim=%d: the index keys are %d wide", p->head_dim, ffpa::kMlaIndexFp8Dim);
+  const bool paged = p->block_table != nullptr;
+  if (p->T < 0 || p->T > (1 << 30)) return fail(FFPA_ERR_BAD_SHAPE, "T=%d must lie in [0, 2^30]", p->T);
+  if (p->B < 1 || p->B > (1 << 30) || (p->cu_seqlens_q == nullptr && p->T % p->B != 0))
+    return fail(FFPA_ERR_BAD_SHAPE, "B=%d must lie in [1, 2^30] and, without cu_seqlens_q, divide T=%d", p->B, p->T);
+  if (p->page_size < 64 || p->page_size % 64 != 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "page_size=%d (without a block_table: the capacity) must be a positive multiple of 64", p->page_size);
+  if (paged && (p->W < 1 || p->num_pages < 1)) return fail(FFPA_ERR_BAD_SHAPE, "with a block_table W=%d and num_pages=%d must be positive", p->W, p->num_pages);
+  for (int64_t s : {p->k_page_stride, p->k_index_stride, p->block_table_stride})
+    if (s < 0) return fail(FFPA_ERR_BAD_STRIDE, "stride %lld must not be negative", (long long)s);
+  if (p->k_page_stride % 16 != 0 || p->k_index_stride % 8 != 0)
+    return fail(FFPA_ERR_BAD_STRIDE, "k_page_stride %lld must be a multiple of 16 bytes and k_index_stride %lld of 8 elements", (long long)p->k_page_stride,
+                (long long)p->k_index_stride);
+  if (p->k_page_stride < (int64_t)p->page_size * ffpa::kMlaIndexFp8RowBytes)
+    return fail(FFPA_ERR_BAD_STRIDE, "k_page_stride=%lld: a page of %d keys is %lld bytes", (long long)p->k_page_stride, p->page_size,
+                (long long)p->page_size * ffpa::kMlaIndexFp8RowBytes);
+  if (!p->k_index_cache || !p->cache_seqlens || !p->lens_after || (p->T > 0 && !p->k_index))
+    return fail(FFPA_ERR_NULL_POINTER, "k_index_cache / cache_seqlens / lens_after (and, with T > 0, k_index) must be non-NULL");
+  if (!aligned16(p->k_index_cache) || !aligned16(p->k_index)) return fail(FFPA_ERR_MISALIGNED, "k_index_cache / k_index must be 16-byte aligned");
+  for (const void* ptr : {(const void*)p->cache_seqlens, (const void*)p->cu_seqlens_q, (const void*)p->block_table, (const void*)p->lens_after})
+    if (reinterpret_cast<uintptr_t>(ptr) & 3u) return fail(FFPA_ERR_MISALIGNED, "cache_seqlens / cu_seqlens_q / block_table / lens_after must be 4-byte aligned");
+  int rc;
+  if ((rc = check_device()) != FFPA_OK) return rc;
+  ffpa::MlaIndexKAppendFp8Args a;
+  memset(&a, 0, sizeof(a));
+  a.k = static_cast<uint8_t*>(p->k_index_cache), a.k_new = p->k_index, a.cache_seqlens = p->cache_seqlens, a.cu_seqlens_q = p->cu_seqlens_q;
+  a.block_table = p->block_table, a.lens_after = p->lens_after;
+  a.s_k_page = p->k_page_stride, a.s_new = p->k_index_stride, a.s_table = p->block_table_stride;
+  a.T = p->T, a.B = p->B, a.page_size = p->page_size, a.fp16 = p->dtype == FFPA_DTYPE_FP16;
+  a.W = paged ? p->W : 1, a.num_pages = paged ? p->num_pages : p->B;  // (no table: one page per sequence)
+  const int st = ffpa::launch_mla_index_k_append_fp8(a, static_cast<hipStream_t>(stream));
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla index k append (fp8) launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
   return FFPA_OK;
 }
 

@@ -322,6 +322,63 @@ class FfpaMlaIndexScoresParams(ctypes.Structure):
   ]
 
 
+class FfpaMlaIndexScoresFp8Params(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_mla_index_scores_fp8_params`` (include/ffpa_attn.h): the indexer's score launch over FP8 index keys."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("q_index", ctypes.c_void_p),
+    ("k_index_cache", ctypes.c_void_p),
+    ("weights", ctypes.c_void_p),
+    ("cache_seqlens", ctypes.c_void_p),
+    ("cu_seqlens_q", ctypes.c_void_p),
+    ("block_table", ctypes.c_void_p),
+    ("scores", ctypes.c_void_p),
+    ("q_stride", ctypes.c_int64 * 2),
+    ("k_page_stride", ctypes.c_int64),
+    ("weights_stride", ctypes.c_int64),
+    ("block_table_stride", ctypes.c_int64),
+    ("scores_stride", ctypes.c_int64),
+    ("T", ctypes.c_int32),
+    ("heads", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("N", ctypes.c_int32),
+    ("B", ctypes.c_int32),
+    ("W", ctypes.c_int32),
+    ("page_size", ctypes.c_int32),
+    ("num_pages", ctypes.c_int32),
+    ("causal", ctypes.c_int32),
+    ("chunk_keys", ctypes.c_int32),
+  ]
+
+
+class FfpaMlaIndexKAppendFp8Params(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_mla_index_k_append_fp8_params`` (include/ffpa_attn.h): the quantising append of the step's index keys."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("k_index_cache", ctypes.c_void_p),
+    ("k_index", ctypes.c_void_p),
+    ("cache_seqlens", ctypes.c_void_p),
+    ("cu_seqlens_q", ctypes.c_void_p),
+    ("block_table", ctypes.c_void_p),
+    ("lens_after", ctypes.c_void_p),
+    ("k_page_stride", ctypes.c_int64),
+    ("k_index_stride", ctypes.c_int64),
+    ("block_table_stride", ctypes.c_int64),
+    ("T", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("B", ctypes.c_int32),
+    ("W", ctypes.c_int32),
+    ("page_size", ctypes.c_int32),
+    ("num_pages", ctypes.c_int32),
+    ("dtype", ctypes.c_int32),
+    ("reserved2", ctypes.c_int32),
+  ]
+
+
 class FfpaMlaAppendVarlenParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_mla_append_varlen_params`` (include/ffpa_attn.h): the latent append of a ragged step."""
 
@@ -555,6 +612,8 @@ _BINDINGS = (
   ("ffpa_attn_mla_ds_store", [_P(FfpaMlaDsStoreParams), _VOID], _INT, 7),
   ("ffpa_attn_mla_sparse_topk_slots", [_P(FfpaMlaSparseTopkParams), _VOID], _INT, 7),
   ("ffpa_attn_mla_index_scores", [_P(FfpaMlaIndexScoresParams), _VOID], _INT, 7),
+  ("ffpa_attn_mla_index_scores_fp8", [_P(FfpaMlaIndexScoresFp8Params), _VOID], _INT, 7),
+  ("ffpa_attn_mla_index_k_append_fp8", [_P(FfpaMlaIndexKAppendFp8Params), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
@@ -651,7 +710,7 @@ def _stamped(cls):
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
   if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse, FfpaMlaFp8, FfpaMlaDsStoreParams, FfpaMlaSparseTopkParams,
-                 FfpaMlaIndexScoresParams):
+                 FfpaMlaIndexScoresParams, FfpaMlaIndexScoresFp8Params, FfpaMlaIndexKAppendFp8Params):
     p.abi_version = ABI_VERSION
   return p
 
@@ -2315,6 +2374,109 @@ def _mla_index_scores_hip_torch_op(q_index, k_index_cache, weights, cache_seqlen
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_index_scores_hip")
 def _mla_index_scores_fake(q_index, k_index_cache, weights, cache_seqlens, block_table, max_seqlen_k, cu_seqlens_q, causal):
   return q_index.new_empty((q_index.size(0), max_seqlen_k), dtype=torch.float32)
+
+
+# The same launch over FP8 index keys and the quantising append that fills their cache (ffpa_mla_index_scores_fp8 / ffpa_mla_index_k_append_fp8,
+# ffpa_attn_amd/kvcache.py, where the arguments are checked)
+def _index_key_pages(k_index_cache: torch.Tensor) -> torch.Tensor:
+  """``[pages, page_size, 1, 132]`` -> ``[pages, page_size, 132]``: the one index head."""
+  return k_index_cache[:, :, 0] if k_index_cache.dim() == 4 else k_index_cache
+
+
+def mla_index_scores_fp8(q_index: torch.Tensor, k_index_cache: torch.Tensor, weights: torch.Tensor, cache_seqlens: torch.Tensor, block_table: "torch.Tensor | None",
+                         max_seqlen_k: int, cu_seqlens_q: "torch.Tensor | None", causal: bool, *, chunk_keys: int = 0) -> torch.Tensor:
+  """One launch of ``ffpa_attn_mla_index_scores_fp8``: ``q_index [T, Hi, 128]`` e4m3, ``k_index_cache`` uint8 ``[num_pages, page_size, (1,) 132]`` (or
+  ``[B, capacity, 132]`` without a table) in the plane layout of ``pack_index_key_pages``, ``weights [T, Hi]`` float32 -> ``scores [T, max_seqlen_k]`` float32
+  on the device, -inf tail included.  Asynchronous, nothing read back to the host."""
+  name = "ffpa_attn::_mla_index_scores_fp8_hip"
+  if not q_index.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{q_index.device.type}' (the HIP kernel needs a GPU tensor)")
+  if q_index.dtype != torch.float8_e4m3fn or k_index_cache.dtype != torch.uint8:
+    raise TypeError(f"{name} only supports torch.float8_e4m3fn q_index and uint8 k_index_cache, got {q_index.dtype}, {k_index_cache.dtype}")
+  lib = load_library()
+  T, Hi, D = q_index.shape
+  scores = torch.empty((T, max_seqlen_k), dtype=torch.float32, device=q_index.device)
+  if T == 0:
+    return scores
+  k_index_cache = _index_key_pages(k_index_cache)
+  cache_seqlens = cache_seqlens.contiguous()
+  p = _stamped(FfpaMlaIndexScoresFp8Params)
+  p.q_index, p.k_index_cache, p.weights, p.cache_seqlens, p.scores = (q_index.data_ptr(), k_index_cache.data_ptr(), weights.data_ptr(), cache_seqlens.data_ptr(),
+                                                                      scores.data_ptr())
+  if cu_seqlens_q is not None:
+    cu_seqlens_q = cu_seqlens_q.contiguous()
+    p.cu_seqlens_q = cu_seqlens_q.data_ptr()
+  if block_table is not None:
+    p.block_table, p.block_table_stride, p.W = block_table.data_ptr(), block_table.stride(0), block_table.size(1)
+  p.q_stride[0], p.q_stride[1], p.k_page_stride = q_index.stride(0), q_index.stride(1), k_index_cache.stride(0)
+  p.weights_stride, p.scores_stride = weights.stride(0), max_seqlen_k
+  p.T, p.heads, p.head_dim, p.N, p.B, p.causal, p.chunk_keys = T, Hi, D, max_seqlen_k, cache_seqlens.numel(), int(bool(causal)), chunk_keys
+  p.num_pages, p.page_size = k_index_cache.size(0), k_index_cache.size(1)
+  rc = _call_on_stream(lib.ffpa_attn_mla_index_scores_fp8, q_index.device, ctypes.byref(p))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_mla_index_scores_fp8")
+  return scores
+
+
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_index_scores_fp8_hip",
+  "(Tensor q_index, Tensor k_index_cache, Tensor weights, Tensor cache_seqlens, Tensor? block_table, int max_seqlen_k, Tensor? cu_seqlens_q, bool causal) -> Tensor",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_index_scores_fp8_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_index_scores_fp8_hip_torch_op(q_index, k_index_cache, weights, cache_seqlens, block_table, max_seqlen_k, cu_seqlens_q, causal):
+  return mla_index_scores_fp8(q_index, k_index_cache, weights, cache_seqlens, block_table, int(max_seqlen_k), cu_seqlens_q, causal)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_index_scores_fp8_hip")
+def _mla_index_scores_fp8_fake(q_index, k_index_cache, weights, cache_seqlens, block_table, max_seqlen_k, cu_seqlens_q, causal):
+  return q_index.new_empty((q_index.size(0), max_seqlen_k), dtype=torch.float32)
+
+
+def mla_index_k_append_fp8(k_index_cache: torch.Tensor, k_index: torch.Tensor, cache_seqlens: torch.Tensor, block_table: "torch.Tensor | None",
+                           cu_seqlens_q: "torch.Tensor | None") -> torch.Tensor:
+  """One launch of ``ffpa_attn_mla_index_k_append_fp8``: the rows of ``k_index [T, 128]`` (bf16 / fp16) quantised into the pages of ``k_index_cache`` (written in
+  place) -> ``lens_after`` int32 ``[B]`` on the device.  Asynchronous, nothing read back to the host."""
+  name = "ffpa_attn::_mla_index_k_append_fp8_hip"
+  if not k_index.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{k_index.device.type}' (the HIP kernel needs a GPU tensor)")
+  if k_index.dtype not in _DTYPE or k_index_cache.dtype != torch.uint8:
+    raise TypeError(f"{name} only supports fp16/bf16 k_index and uint8 k_index_cache, got {k_index.dtype}, {k_index_cache.dtype}")
+  lib = load_library()
+  k_index_cache = _index_key_pages(k_index_cache)
+  cache_seqlens = cache_seqlens.contiguous()
+  lens_after = torch.empty_like(cache_seqlens)
+  p = _stamped(FfpaMlaIndexKAppendFp8Params)
+  p.k_index_cache, p.k_index, p.cache_seqlens, p.lens_after = k_index_cache.data_ptr(), k_index.data_ptr(), cache_seqlens.data_ptr(), lens_after.data_ptr()
+  if cu_seqlens_q is not None:
+    cu_seqlens_q = cu_seqlens_q.contiguous()
+    p.cu_seqlens_q = cu_seqlens_q.data_ptr()
+  if block_table is not None:
+    p.block_table, p.block_table_stride, p.W = block_table.data_ptr(), block_table.stride(0), block_table.size(1)
+  p.k_page_stride, p.k_index_stride = k_index_cache.stride(0), k_index.stride(0)
+  p.T, p.head_dim, p.B, p.dtype = k_index.size(0), k_index.size(-1), cache_seqlens.numel(), _DTYPE[k_index.dtype]
+  p.num_pages, p.page_size = k_index_cache.size(0), k_index_cache.size(1)
+  rc = _call_on_stream(lib.ffpa_attn_mla_index_k_append_fp8, k_index.device, ctypes.byref(p))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_mla_index_k_append_fp8")
+  return lens_after
+
+
+torch.library.define(
+  f"{_OP_NAMESPACE}::_mla_index_k_append_fp8_hip",
+  "(Tensor(a!) k_index_cache, Tensor k_index, Tensor cache_seqlens, Tensor? block_table, Tensor? cu_seqlens_q) -> Tensor",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_mla_index_k_append_fp8_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _mla_index_k_append_fp8_hip_torch_op(k_index_cache, k_index, cache_seqlens, block_table, cu_seqlens_q):
+  return mla_index_k_append_fp8(k_index_cache, k_index, cache_seqlens, block_table, cu_seqlens_q)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_index_k_append_fp8_hip")
+def _mla_index_k_append_fp8_fake(k_index_cache, k_index, cache_seqlens, block_table, cu_seqlens_q):
+  return torch.empty_like(cache_seqlens, memory_format=torch.contiguous_format)
 
 
 # The latent append of a ragged step (ffpa_attn_varlen_with_kvcache_mla(kv=)): token rows packed by cu_seqlens_q, in front of the attention launch

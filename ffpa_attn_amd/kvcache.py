@@ -1228,6 +1228,203 @@ def ffpa_mla_index_scores(
   return torch.ops.ffpa_attn._mla_index_scores_hip(q_index, k_index_cache, weights, cache_seqlens, block_table, max_seqlen_k, cu_seqlens_q, bool(causal))
 
 
+# ---- FP8 index keys: the row and page format in plain torch (these functions ARE its definition), the score call over it and the append that fills it
+_MLA_INDEX_ROW_BYTES = _MLA_INDEX_DIM + 4  # a key's share of its page: 128 e4m3 codes and one float32 scale
+
+
+def quantize_index_rows(x: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor]":
+  """The FP8 form of index rows — the engines' ``ue8m0`` recipe, for the index keys and the index queries alike: ``x [..., 128]`` (bf16 / fp16 / fp32, finite)
+  -> ``(codes [..., 128] torch.float8_e4m3fn, scale [...] float32)`` with ``x ~ scale[..., None] * codes``::
+
+      amax  = max |float32(x)| over the row
+      s     = max(amax, 1e-4) / 448                              (float32)
+      scale = s rounded UP to a power of two, on its exponent bits: a non-zero mantissa means exponent + 1, the mantissa cleared (no log2)
+      code  = rne_e4m3(clamp(float32(x) / scale, -448, +448))    (the division is exact: scale is a power of two)
+
+  For queries the caller multiplies ``weights[t, h]`` by the query row's scale, as the model does.  ``ffpa_mla_index_k_append_fp8`` writes these bytes."""
+  if not isinstance(x, torch.Tensor) or x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+    raise TypeError(f"quantize_index_rows: x must be a bf16 / fp16 / fp32 tensor, got {x.dtype if isinstance(x, torch.Tensor) else type(x).__name__}")
+  if x.dim() < 1 or x.size(-1) != _MLA_INDEX_DIM:
+    raise ValueError(f"quantize_index_rows: x must be [..., {_MLA_INDEX_DIM}], got {tuple(x.shape)}")
+  xf = x.float()
+  bits = (xf.abs().amax(-1).clamp(min=1e-4) / 448).view(torch.int32)
+  scale = ((bits & 0x7F800000) + ((bits & 0x007FFFFF) != 0).to(torch.int32) * 0x00800000).view(torch.float32)
+  return (xf / scale.unsqueeze(-1)).clamp(-448, 448).to(torch.float8_e4m3fn), scale
+
+
+def pack_index_key_pages(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+  """The engines' page layout of the FP8 index-key cache: ``codes [P, page_size, 128]`` ``torch.float8_e4m3fn`` and ``scale [P, page_size]`` float32 -> uint8
+  ``[P, page_size, 132]`` whose page ``i`` holds, as ``page_size * 132`` contiguous bytes, FIRST the ``page_size * 128`` codes row-major, THEN the ``page_size``
+  float32 scales — two planes, NOT 132 interleaved bytes per row (the last two dimensions only give the page its size)."""
+  if codes.dtype != torch.float8_e4m3fn or scale.dtype != torch.float32:
+    raise TypeError(f"pack_index_key_pages: codes must be torch.float8_e4m3fn and scale torch.float32, got {codes.dtype}, {scale.dtype}")
+  if codes.dim() != 3 or codes.size(2) != _MLA_INDEX_DIM or tuple(scale.shape) != tuple(codes.shape[:2]):
+    raise ValueError(f"pack_index_key_pages: codes must be [P, page_size, {_MLA_INDEX_DIM}] and scale [P, page_size], got {tuple(codes.shape)}, {tuple(scale.shape)}")
+  P, ps = scale.shape
+  planes = torch.cat([codes.contiguous().view(torch.uint8).reshape(P, ps * _MLA_INDEX_DIM), scale.contiguous().view(torch.uint8).reshape(P, ps * 4)], dim=1)
+  return planes.view(P, ps, _MLA_INDEX_ROW_BYTES)
+
+
+def unpack_index_key_pages(pages: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor]":
+  """The inverse of ``pack_index_key_pages``: uint8 ``[P, page_size, 132]`` -> ``(codes [P, page_size, 128] torch.float8_e4m3fn, scale [P, page_size] float32)``."""
+  if pages.dtype != torch.uint8 or pages.dim() != 3 or pages.size(2) != _MLA_INDEX_ROW_BYTES:
+    raise ValueError(f"unpack_index_key_pages: pages must be uint8 [P, page_size, {_MLA_INDEX_ROW_BYTES}], got {pages.dtype} {tuple(pages.shape)}")
+  P, ps = pages.shape[:2]
+  planes = pages.contiguous().view(P, ps * _MLA_INDEX_ROW_BYTES)
+  codes = planes[:, :ps * _MLA_INDEX_DIM].contiguous().view(torch.float8_e4m3fn).view(P, ps, _MLA_INDEX_DIM)
+  return codes, planes[:, ps * _MLA_INDEX_DIM:].contiguous().view(torch.float32).view(P, ps)
+
+
+def _mla_index_fp8_check(name, k_index_cache, rows_name, rows, cache_seqlens, block_table, cu_seqlens_q, weights=None) -> None:
+  """The shape, stride and device checks the two FP8 index calls share, in ``_mla_index_scores_check``'s style and order (``ValueError``; nothing is read from the
+  device): the pool's layout, the step's packing, the table.  ``rows``: the call's own ``[T, ...]`` tensor (``q_index`` / ``k_index``), its dtype and shape
+  already checked by the caller, as are all dtypes."""
+  B = cache_seqlens.numel()
+  paged = block_table is not None
+  k, T, R = k_index_cache, rows.size(0), _MLA_INDEX_ROW_BYTES
+  if cache_seqlens.dim() != 1 or B < 1:
+    raise ValueError(f"{name}: cache_seqlens must be an int32 tensor [B] with B >= 1, got {tuple(cache_seqlens.shape)}")
+  if k.dim() == 4 and paged and k.size(2) != 1:
+    raise ValueError(f"{name}: the index keys have ONE head, got k_index_cache {tuple(k.shape)}")
+  if (k.dim() != 3 and not (paged and k.dim() == 4)) or k.size(-1) != R or k.size(0) < 1:
+    raise ValueError(f"{name}: k_index_cache must be " + (f"[num_pages, page_size, {R}] or [num_pages, page_size, 1, {R}]" if paged else f"[B={B}, capacity, {R}]") +
+                     f" (128 codes and a float32 scale per key, in two planes per page), got {tuple(k.shape)}")
+  if not paged and k.size(0) != B:
+    raise ValueError(f"{name}: without a block_table k_index_cache must be [B={B}, capacity, {R}], got {tuple(k.shape)}")
+  if k.size(1) < 64 or k.size(1) % 64 != 0:
+    raise ValueError(f"{name}: the {'page size' if paged else 'capacity'} must be a positive multiple of 64, got {k.size(1)}")
+  if cu_seqlens_q is not None and (cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() != B + 1):
+    raise ValueError(f"{name}: cu_seqlens_q must be an int32 tensor [B + 1 = {B + 1}], got {tuple(cu_seqlens_q.shape)}")
+  if cu_seqlens_q is None and T % B != 0:
+    raise ValueError(f"{name}: without cu_seqlens_q the T={T} rows are [B, Sq] flattened: T must be a multiple of B={B}")
+  if paged and (block_table.dim() != 2 or block_table.size(0) != B or block_table.size(1) < 1):
+    raise ValueError(f"{name}: block_table must be [B={B}, pages_per_seq >= 1] — one row per SEQUENCE —, got {tuple(block_table.shape)}")
+  for nm, t in ((rows_name, rows), ("k_index_cache", k)) + ((("weights", weights),) if weights is not None else ()) + ((("block_table", block_table),) if paged else ()):
+    if t.stride(-1) != 1:
+      raise ValueError(f"{name}: {nm} must have a contiguous last dimension")
+  if k.stride(1) != R or k.stride(0) % 16 != 0 or k.stride(0) < k.size(1) * R:
+    raise ValueError(f"{name}: a page of k_index_cache must be {k.size(1)} * {R} contiguous bytes and the pages a multiple of 16 bytes apart, got strides {k.stride()}")
+  for nm, t in (("k_index_cache", k), ("cache_seqlens", cache_seqlens)) + ((("weights", weights),) if weights is not None else ()) + \
+                ((("block_table", block_table),) if paged else ()) + ((("cu_seqlens_q", cu_seqlens_q),) if cu_seqlens_q is not None else ()):
+    if t.device != rows.device:
+      raise ValueError(f"{name}: {nm} must be on {rows_name}'s device, got {t.device} and {rows.device}")
+
+
+def _mla_index_fp8_tensors(name, named) -> None:
+  """``TypeError`` for a non-tensor, ``NotImplementedError`` for a tensor that requires grad."""
+  for nm, t in named:
+    if not isinstance(t, torch.Tensor):
+      raise TypeError(f"{name}: {nm} must be a tensor, got {type(t).__name__}")
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+
+
+def ffpa_mla_index_scores_fp8(
+  q_index: torch.Tensor,
+  k_index_cache: torch.Tensor,
+  weights: torch.Tensor,
+  cache_seqlens: torch.Tensor,
+  block_table: "torch.Tensor | None" = None,
+  *,
+  max_seqlen_k: int,
+  cu_seqlens_q: "torch.Tensor | None" = None,
+  causal: bool = True,
+) -> torch.Tensor:
+  """``ffpa_mla_index_scores`` over the FP8 index-key cache the serving engines keep (DeepGEMM's ``fp8_paged_mqa_logits``), read where it lies — no dequantised
+  copy of the pool — in ONE launch on gfx950's FP8 MFMA: ``scores`` float32 ``[T, N]``, ``N = max_seqlen_k``, what ``ffpa_mla_sparse_topk_slots`` takes.
+
+  ``q_index``: ``[T, Hi, 128]`` ``torch.float8_e4m3fn`` (``quantize_index_rows``), ``Hi`` 32 or 64; unit stride in the last dimension, the other strides
+  multiples of 16.  ``k_index_cache``: uint8 in ``pack_index_key_pages``'s layout — paged ``[num_pages, page_size, 132]`` or ``[num_pages, page_size, 1, 132]``
+  read through ``block_table`` int32 ``[B, W]`` (``page_size % 64 == 0``), or, without a table, ``[B, capacity, 132]`` with ``capacity % 64 == 0``, one page per
+  sequence; a page is ``page_size * 132`` contiguous bytes, the pages a multiple of 16 bytes apart.  ``weights``: float32 ``[T, Hi]`` with EVERY scale but the
+  keys' folded in — the model's head weights, the softmax scale and the query row's quantisation scale.  ``cache_seqlens``: int32 ``[B]``, the lengths WITH the
+  step's index keys in the cache (``ffpa_mla_index_k_append_fp8`` returns them).
+
+  Token -> sequence, padding rows, ``n_t``, its clamp to what the table or the capacity can name and the clamped page ids are ``ffpa_mla_index_scores``'s rules
+  to the letter; rows at and past ``n_t`` never become an address, in the code plane or the scale plane.  Then, on the codes' values ``q8`` / ``k8``::
+
+      scores[t, p] = kscale[b_t, p] * sum_h weights[t, h] * max(0, sum_d q8[t, h, d] * k8[b_t, p, d])      for p < n_t
+      scores[t, p] = -inf                                                                                 for n_t <= p < N
+
+  Any positive finite float32 key scale is read, not only powers of two.  Finite inputs are the contract (an e4m3 NaN code gives unspecified values, never an
+  access outside the tensors).  ``T == 0`` returns an empty tensor and launches nothing.  Not served: e5m2 / fnuz codes, ``Hi`` other than 32 / 64, 16-bit
+  queries against FP8 keys."""
+  name = "ffpa_mla_index_scores_fp8"
+  named = (("q_index", q_index), ("k_index_cache", k_index_cache), ("weights", weights), ("cache_seqlens", cache_seqlens)) + \
+          ((("block_table", block_table),) if block_table is not None else ()) + ((("cu_seqlens_q", cu_seqlens_q),) if cu_seqlens_q is not None else ())
+  _mla_index_fp8_tensors(name, named)
+  if q_index.dtype != torch.float8_e4m3fn:
+    raise TypeError(f"{name}: q_index must be torch.float8_e4m3fn (quantize_index_rows), got {q_index.dtype}")
+  if k_index_cache.dtype != torch.uint8:
+    raise TypeError(f"{name}: k_index_cache must be torch.uint8 (pack_index_key_pages), got {k_index_cache.dtype}")
+  if weights.dtype != torch.float32:
+    raise TypeError(f"{name}: weights must be torch.float32, got {weights.dtype}")
+  for nm, t in named[3:]:
+    if t.dtype != torch.int32:
+      raise TypeError(f"{name}: {nm} must be an int32 tensor, got {t.dtype}")
+  if isinstance(max_seqlen_k, bool) or not isinstance(max_seqlen_k, int):
+    raise TypeError(f"{name}: max_seqlen_k must be an int, got {max_seqlen_k!r}")
+  if max_seqlen_k < 1 or max_seqlen_k > 1 << 30:
+    raise ValueError(f"{name}: max_seqlen_k must lie in [1, 2^30], got {max_seqlen_k}")
+  if q_index.dim() != 3 or q_index.size(2) != _MLA_INDEX_DIM:
+    raise ValueError(f"{name}: q_index must be [T, Hi, {_MLA_INDEX_DIM}] (the index heads are {_MLA_INDEX_DIM} wide), got {tuple(q_index.shape)}")
+  T, Hi, _ = q_index.shape
+  if Hi not in _MLA_INDEX_HEADS:
+    raise NotImplementedError(f"{name}: the score kernel is built for Hi in {_MLA_INDEX_HEADS} index heads, got {Hi}")
+  if weights.dim() != 2 or tuple(weights.shape) != (T, Hi):
+    raise ValueError(f"{name}: weights must be [T={T}, Hi={Hi}], got {tuple(weights.shape)}")
+  _mla_index_fp8_check(name, k_index_cache, "q_index", q_index, cache_seqlens, block_table, cu_seqlens_q, weights)
+  if any(q_index.stride(d) % 16 != 0 or q_index.stride(d) < 0 for d in (0, 1)):  # (a first byte off 16 is the C layer's FFPA_ERR_MISALIGNED: nothing here reads data_ptr)
+    raise ValueError(f"{name}: the strides of q_index must be multiples of 16, got {q_index.stride()}")
+  from . import hip  # noqa: F401  (registers the ffpa_attn ops)
+
+  if T == 0:
+    return q_index.new_empty((0, max_seqlen_k), dtype=torch.float32)
+  return torch.ops.ffpa_attn._mla_index_scores_fp8_hip(q_index, k_index_cache, weights, cache_seqlens, block_table, max_seqlen_k, cu_seqlens_q, bool(causal))
+
+
+def ffpa_mla_index_k_append_fp8(
+  k_index_cache: torch.Tensor,
+  k_index: torch.Tensor,
+  cache_seqlens: torch.Tensor,
+  block_table: "torch.Tensor | None" = None,
+  *,
+  cu_seqlens_q: "torch.Tensor | None" = None,
+) -> torch.Tensor:
+  """The producer of that cache (vLLM's ``indexer_k_quant_and_cache``) in ONE launch: the step's index keys ``k_index`` ``[T, 128]`` or ``[T, 1, 128]`` (bf16 /
+  fp16; unit stride in the last dimension, a row stride that is a multiple of 8) are quantised as ``quantize_index_rows`` does and written into
+  ``k_index_cache`` (uint8, ``ffpa_mla_index_scores_fp8``'s layouts, in place) — byte for byte what ``quantize_index_rows`` + ``pack_index_key_pages`` give.
+  Returns ``lens_after`` int32 ``[B]`` on the device, the lengths the score call takes; ``cache_seqlens`` (the lengths BEFORE the step) is not advanced and
+  nothing is read back to the host.
+
+  The rows are uniform (``T % B == 0``: row ``t`` is key ``t % (T // B)`` of sequence ``t // (T // B)``) or packed by ``cu_seqlens_q`` int32 ``[B + 1]``; rows at
+  and past ``cu_seqlens_q[B]`` are padding and write nothing.  Key ``i`` of sequence ``b`` goes to position ``max(cache_seqlens[b], 0) + i`` — a negative length
+  acts as 0 — through the block table, the page id clamped into ``[0, num_pages - 1]``; a position at or past what the table (``W * page_size``) or the capacity
+  can name is dropped: the latent appends' placement rule.  ``lens_after[b] = min(max(cache_seqlens[b], 0) + new keys of b, that bound)`` for every sequence,
+  empty ones included.  Finite inputs are the contract."""
+  name = "ffpa_mla_index_k_append_fp8"
+  named = (("k_index_cache", k_index_cache), ("k_index", k_index), ("cache_seqlens", cache_seqlens)) + \
+          ((("block_table", block_table),) if block_table is not None else ()) + ((("cu_seqlens_q", cu_seqlens_q),) if cu_seqlens_q is not None else ())
+  _mla_index_fp8_tensors(name, named)
+  if k_index_cache.dtype != torch.uint8:
+    raise TypeError(f"{name}: k_index_cache must be torch.uint8 (pack_index_key_pages), got {k_index_cache.dtype}")
+  if k_index.dtype not in (torch.bfloat16, torch.float16):
+    raise TypeError(f"{name}: k_index must be bf16 or fp16, got {k_index.dtype}")
+  for nm, t in named[2:]:
+    if t.dtype != torch.int32:
+      raise TypeError(f"{name}: {nm} must be an int32 tensor, got {t.dtype}")
+  if k_index.dim() == 3 and k_index.size(1) == 1:
+    k_index = k_index[:, 0]
+  if k_index.dim() != 2 or k_index.size(1) != _MLA_INDEX_DIM:
+    raise ValueError(f"{name}: k_index must be [T, {_MLA_INDEX_DIM}] or [T, 1, {_MLA_INDEX_DIM}], got {tuple(k_index.shape)}")
+  _mla_index_fp8_check(name, k_index_cache, "k_index", k_index, cache_seqlens, block_table, cu_seqlens_q)
+  if k_index.stride(0) % 8 != 0 or k_index.stride(0) < 0:
+    raise ValueError(f"{name}: the row stride of k_index must be a multiple of 8 elements, got {k_index.stride()}")
+  from . import hip  # noqa: F401  (registers the ffpa_attn ops)
+
+  return torch.ops.ffpa_attn._mla_index_k_append_fp8_hip(k_index_cache, k_index, cache_seqlens, block_table, cu_seqlens_q)
+
+
 def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=False, ds=False):
   """The argument checks of the sparse latent calls under their own ``name``, every rule written once and in the order ``ffpa_attn_with_kvcache_mla_sparse`` has
   always made them -> ``(T, Hq)``.  ``fp8``: the pool is ``torch.float8_e4m3fn`` (``ffpa_attn_with_kvcache_mla_sparse_fp8``) — the dtype rule is the FP8 latent

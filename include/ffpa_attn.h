@@ -800,6 +800,95 @@ typedef struct ffpa_mla_index_scores_params {
 int ffpa_attn_mla_index_scores(const ffpa_mla_index_scores_params* p, void* stream);
 
 /*
+ * THE SAME SCORES OVER FP8 INDEX KEYS — the form in which the engines keep DeepSeek-V3.2's index-key cache (DeepGEMM's fp8_paged_mqa_logits reads it, vLLM's
+ * indexer_k_quant_and_cache writes it), read where it lies: ONE kernel on `stream`, on the FP8 MFMA whose K dimension is the index head's 128 columns.
+ *   THE PAGE FORMAT.  A page of page_size keys is page_size * 132 bytes: first the code plane, page_size * 128 OCP e4m3 codes row-major, then the scale plane,
+ *     page_size float32 — one per key, key = scale x codes.  NOT 132 interleaved bytes per key.  Pages lie k_page_stride bytes apart (>= page_size * 132, a
+ *     multiple of 16).  block_table NULL: the cache is B such pages of page_size = capacity keys, page id = sequence.
+ *   q_index holds e4m3 codes too (the model quantises the index queries; fold each query row's scale into its weights).
+ *   scores[t, p] = kscale[b, p] * sum_h weights[t, h] * max(0, sum_d q8[t, h, d] * k8[b, p, d])  for p < n,   -inf for n <= p < N (a padding row: all -inf):
+ *     any positive finite float32 key scale is read.  Token t -> (b, i, S), n, the page of key p and the clamps: ffpa_mla_index_scores_params's rules to the
+ *     letter; a key at or past n becomes no address, in neither plane.
+ *   chunk_keys: as in ffpa_mla_index_scores_params (pass 0).
+ * Checks, in this order: p NULL (FFPA_ERR_NULL_POINTER); struct_size, reserved (FFPA_ERR_BAD_ABI); head_dim != 128 (FFPA_ERR_BAD_HEADDIM); heads outside
+ * {32, 64} (FFPA_ERR_UNSUPPORTED); T < 0, N outside [1, 2^30], B < 1, T % B != 0 without cu_seqlens_q, causal outside {0, 1}, page_size < 64 or not a multiple of
+ * 64, with a block_table W < 1 or num_pages < 1, chunk_keys outside {0, 256, 512, 1024}, more than 2^24 workgroups = T * ceil(N / chunk) (FFPA_ERR_BAD_SHAPE); a
+ * negative stride, a q stride or k_page_stride that is not a multiple of 16, k_page_stride < page_size * 132, scores_stride < N (FFPA_ERR_BAD_STRIDE); then,
+ * T > 0: a NULL q_index / k_index_cache / weights / cache_seqlens / scores (FFPA_ERR_NULL_POINTER), q_index / k_index_cache not 16-byte or another pointer not
+ * 4-byte aligned (FFPA_ERR_MISALIGNED), the device.
+ */
+typedef struct ffpa_mla_index_scores_fp8_params {
+  uint32_t struct_size;          /* sizeof(ffpa_mla_index_scores_fp8_params), checked */
+  uint32_t reserved;             /* 0, checked */
+  const void* q_index;           /* device [T, heads, 128] e4m3 codes */
+  const void* k_index_cache;     /* device: num_pages pages of the format above (or B of them, one per sequence) */
+  const float* weights;          /* device [T, heads] float32, every scale but the keys' folded in */
+  const int32_t* cache_seqlens;  /* device [B]: the lengths with the step's index keys in the cache */
+  const int32_t* cu_seqlens_q;   /* device [B + 1], or NULL: T / B tokens per sequence */
+  const int32_t* block_table;    /* device [B, W], or NULL: one page per sequence */
+  float* scores;                 /* device [T, N], written */
+  int64_t q_stride[2];           /* bytes: {token, head}, multiples of 16 */
+  int64_t k_page_stride;         /* bytes between two pages, a multiple of 16 */
+  int64_t weights_stride;        /* elements: rows of weights */
+  int64_t block_table_stride;    /* elements: rows of block_table */
+  int64_t scores_stride;         /* elements: rows of scores (>= N) */
+  int32_t T;                     /* >= 0 */
+  int32_t heads;                 /* 32 / 64 */
+  int32_t head_dim;              /* 128 */
+  int32_t N;                     /* columns of scores (max_seqlen_k) */
+  int32_t B;
+  int32_t W;                     /* columns of block_table */
+  int32_t page_size;             /* keys of a page; without a block_table the capacity */
+  int32_t num_pages;
+  int32_t causal;                /* 0 / 1 */
+  int32_t chunk_keys;            /* 0: FFPA_MLA_INDEX_CHUNK_KEYS (pass 0; other values are the developer's sweep) */
+} ffpa_mla_index_scores_fp8_params;
+
+/* Launch the scores on `stream` of the CURRENT device.  Asynchronous; every bad argument returns a status before any device work.  Returns an ffpa_status. */
+int ffpa_attn_mla_index_scores_fp8(const ffpa_mla_index_scores_fp8_params* p, void* stream);
+
+/*
+ * THE APPEND THAT FILLS THAT CACHE — the step's index keys (bf16 / fp16, [T, 128]), quantised and written into their pages in ONE kernel on `stream`.
+ *   Row t of k_index is token i of sequence b: by cu_seqlens_q and the binary search (rows at and past cu_seqlens_q[B] are padding and write nothing), or,
+ *     cu_seqlens_q NULL, b = t / (T / B), i = t % (T / B).  It goes to cache position max(cache_seqlens[b], 0) + i — a negative length acts as 0 — through the
+ *     block table, the page id clamped into [0, num_pages - 1]; a position at or past the capacity (W * page_size; without a table page_size) is dropped and
+ *     reads no table entry: the latent appends' placement rule.
+ *   The row's scale: s = max(amax, 1e-4) / 448 in float32, rounded UP to a power of two (a non-zero mantissa: exponent + 1, mantissa cleared) — the engines'
+ *     ue8m0 scale as a float32; its codes: rne_e4m3(clamp(float32(x) / scale, +-448)).  Codes into the page's code plane, the scale into its scale plane.
+ *   lens_after[b] = min(max(cache_seqlens[b], 0) + the sequence's new rows, capacity) for EVERY b < B, sequences without a row included.  cache_seqlens is not
+ *     written; nothing is read back to the host.  Finite inputs are the contract.
+ * Checks, in this order: p NULL (FFPA_ERR_NULL_POINTER); struct_size, reserved (FFPA_ERR_BAD_ABI); dtype (FFPA_ERR_BAD_DTYPE); head_dim != 128
+ * (FFPA_ERR_BAD_HEADDIM); T outside [0, 2^30], B outside [1, 2^30], T % B != 0 without cu_seqlens_q, page_size < 64 or not a multiple of 64, with a block_table
+ * W < 1 or num_pages < 1 (FFPA_ERR_BAD_SHAPE); a negative stride, k_page_stride not a multiple of 16 or k_index_stride not of 8, k_page_stride < page_size * 132
+ * (FFPA_ERR_BAD_STRIDE); a NULL k_index_cache / cache_seqlens / lens_after or, T > 0, k_index (FFPA_ERR_NULL_POINTER); k_index_cache / k_index not 16-byte or
+ * another pointer not 4-byte aligned (FFPA_ERR_MISALIGNED); the device.
+ */
+typedef struct ffpa_mla_index_k_append_fp8_params {
+  uint32_t struct_size;          /* sizeof(ffpa_mla_index_k_append_fp8_params), checked */
+  uint32_t reserved;             /* 0, checked */
+  void* k_index_cache;           /* device: the pool of ffpa_mla_index_scores_fp8_params, written */
+  const void* k_index;           /* device [T, 128], bf16 / fp16 */
+  const int32_t* cache_seqlens;  /* device [B]: the lengths BEFORE the step */
+  const int32_t* cu_seqlens_q;   /* device [B + 1], or NULL: T / B rows per sequence */
+  const int32_t* block_table;    /* device [B, W], or NULL: one page per sequence */
+  int32_t* lens_after;           /* device [B], written */
+  int64_t k_page_stride;         /* bytes between two pages, a multiple of 16 */
+  int64_t k_index_stride;        /* elements: rows of k_index, a multiple of 8 */
+  int64_t block_table_stride;    /* elements: rows of block_table */
+  int32_t T;                     /* rows of k_index, >= 0 */
+  int32_t head_dim;              /* 128 */
+  int32_t B;
+  int32_t W;                     /* columns of block_table */
+  int32_t page_size;             /* keys of a page; without a block_table the capacity */
+  int32_t num_pages;
+  int32_t dtype;                 /* FFPA_DTYPE_BF16 / FFPA_DTYPE_FP16: k_index's */
+  int32_t reserved2;             /* 0, checked */
+} ffpa_mla_index_k_append_fp8_params;
+
+/* Launch the append on `stream` of the CURRENT device.  Asynchronous; every bad argument returns a status before any device work.  Returns an ffpa_status. */
+int ffpa_attn_mla_index_k_append_fp8(const ffpa_mla_index_k_append_fp8_params* p, void* stream);
+
+/*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
  * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
  *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position
