@@ -39,7 +39,8 @@ VARLEN_HEAD_DIMS = [d for d in HEAD_DIMS if d >= 128]
 # (head dim, value width) pairs the MLA latent-cache kernel is built for (FFPA_FOR_EACH_MLA_BUILD, csrc/ffpa_mla.h)
 MLA_BUILDS = [(576, 512)]
 # the variants of that kernel, by the stem of their row in FFPA_FOR_EACH_MLA_VARIANT (csrc/ffpa_mla.h), in its order: the link order
-MLA_VARIANTS = ["mla", "mla_sparse", "mla_tree", "mla_fp8", "mla_sparse_fp8", "mla_tree_fp8", "mla_sparse_ds"]
+MLA_VARIANTS = ["mla", "mla_sparse", "mla_tree", "mla_fp8", "mla_sparse_fp8", "mla_tree_fp8", "mla_sparse_ds",
+                "mla_sparse_wide", "mla_sparse_fp8_wide", "mla_sparse_ds_wide"]
 
 ARCH = "gfx950"
 CXXFLAGS = [

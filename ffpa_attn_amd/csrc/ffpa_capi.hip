@@ -1251,18 +1251,19 @@ int check_sparse(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
 }
 
 // The reach of the sparse kernel's addressing: every lane offset is 32 bits from the head's first row and bit 31 (kDmaOob) is the "no row" sentinel, so the rows of a
-// head span at most 2^31 bytes.
+// head span at most 2^31 bytes.  That is the NARROW builds' reach; a wide variant (MlaVariant::wide: 64-bit lane addresses, no descriptor) reaches any span — num_rows
+// up to 2^31 - 1, row strides as here — and is the one thing for which the span check below is skipped.
 constexpr int64_t kSparseSpanBytes = 1LL << 31;
 
 // ... and what it checks BEHIND the plan and the (head_dim, head_dim_v) pair: the latent pool's geometry.  `esz`: bytes per pool element (2; 1: the FP8 sparse
 // call, whose span is counted in ITS bytes — the same 2^31 reach holds twice as many rows).
-int check_sparse_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int esz = 2) {
+int check_sparse_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int esz = 2, bool wide = false) {
   const int rc = check_strides("kv", s->kv_stride, 2);
   if (rc != FFPA_OK) return rc;
   if (s->kv_stride[0] < p->head_dim || s->kv_stride[0] >= (1LL << 24))
     return fail(FFPA_ERR_BAD_STRIDE, "kv row stride %lld: rows must not overlap and must be < 2^24 elements apart", (long long)s->kv_stride[0]);
   const int64_t span = ((int64_t)s->num_rows - 1) * s->kv_stride[0] * esz + (int64_t)p->head_dim * esz;
-  if (span > kSparseSpanBytes)
+  if (!wide && span > kSparseSpanBytes)
     return fail(FFPA_ERR_BAD_SHAPE, "the pool's rows span %lld bytes per head: the sparse call reaches at most 2^31 = %lld ((num_rows - 1) * row stride * %d + head_dim * %d)",
                 (long long)span, (long long)kSparseSpanBytes, esz, esz);
   return FFPA_OK;
@@ -1271,7 +1272,7 @@ int check_sparse_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s,
 // The geometry of a pool of 656-byte FP8 rows (ffpa_attn_varlen_mla_sparse_ds_fwd), behind the plan and the (head_dim, head_dim_v) pair, in this order: q's dtype
 // (the rotary bytes of a row are bf16 and reach the kernel's image as they are), the one row format there is, the strides — in BYTES; the kernel's text doubles
 // every stride and its loads are 16 bytes wide —, the base, the reach of the 32-bit offsets.
-int check_sparse_ds_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s) {
+int check_sparse_ds_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, bool wide = false) {
   if (p->dtype != FFPA_DTYPE_BF16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d: the 656-byte rows carry bf16 rotary columns, q must be bf16(0)", p->dtype);
   if (p->head_dim != ffpa::kDsNope + 64 || s->head_dim_v != ffpa::kDsNope)
     return fail(FFPA_ERR_BAD_HEADDIM, "(head_dim, head_dim_v) = (%d, %d): a 656-byte row holds (576, 512)", p->head_dim, s->head_dim_v);
@@ -1281,7 +1282,7 @@ int check_sparse_ds_pool(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse*
                 (long long)s->kv_stride[0], (long long)s->kv_stride[1], ffpa::kDsRowBytes);
   if (!aligned16(p->k)) return fail(FFPA_ERR_MISALIGNED, "the pool's base must be 16-byte aligned");
   const int64_t span = ((int64_t)s->num_rows - 1) * s->kv_stride[0] + ffpa::kDsRowBytes;
-  if (span > kSparseSpanBytes)
+  if (!wide && span > kSparseSpanBytes)
     return fail(FFPA_ERR_BAD_SHAPE, "the pool's rows span %lld bytes per head: the sparse call reaches at most 2^31 = %lld ((num_rows - 1) * slot stride + %d)",
                 (long long)span, (long long)kSparseSpanBytes, ffpa::kDsRowBytes);
   return FFPA_OK;
@@ -1298,7 +1299,7 @@ enum class Family {
   kTree,     // ffpa_attn_varlen_tree_fwd: tree; kv optional (NULL: contiguous caches) — the causal launch's plan and tile walk, the *_tree_kernel builds
   kWindow,   // ffpa_attn_varlen_window_fwd: win; kv optional — the window's own plan, the *_window_kernel builds
   kSoftcap,  // ffpa_attn_varlen_softcap_fwd: softcap; win optional (NULL: (-1, -1)), kv optional — a window launch with capped scores, the *_softcap_kernel builds
-  kLatent,   // the seven ffpa_attn_varlen_mla*_fwd calls: ONE pool — k is the latent pool and serves as v too (p->v is not read) —, every group packed into rows.
+  kLatent,   // the ffpa_attn_varlen_mla*_fwd calls: ONE pool — k is the latent pool and serves as v too (p->v is not read) —, every group packed into rows.
              // WHICH of them is VarlenCall::variant, a row of ffpa_mla.h's list: its traits say which structs the call takes (tree: tree; gather: sparse, else kv +
              // mla — with the append in front —; an e4m3 pool: fp8) and plan_latent reads nothing else of it
 };
@@ -1413,7 +1414,7 @@ void price_sparse(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, Cal
   cp->mla = &cp->own_mla;
 }
 
-// The seven latent calls are ONE order of checks, each step taken where the variant's traits ask for it (tests/golden/capi_varlen_calls.json pins the order, form
+// The latent calls are ONE order of checks, each step taken where the variant's traits ask for it (tests/golden/capi_varlen_calls.json pins the order, form
 // by form).  Tree and gather both price a copy of the params: no variant has both.
 #define FFPA_ROW(stem, tree, gather, ...) static_assert(!(tree && gather), "plan_latent prices ONE copy of the params");
 FFPA_FOR_EACH_MLA_VARIANT(FFPA_ROW, )
@@ -1445,8 +1446,8 @@ int plan_latent(const VarlenCall& c, CallPlan* cp) {
   if (!v.gather && (rc = check_paged(p, c.kv)) != FFPA_OK) return rc;
   if ((rc = check_mla(p, mla, &build)) != FFPA_OK) return rc;
   if (v.tree && (rc = check_tree(p, c.tree)) != FFPA_OK) return rc;
-  // 8. the gathered pool's geometry, 9. the stride rule of a pool of one-byte elements
-  if (v.gather && (rc = ds ? check_sparse_ds_pool(p, c.sparse) : check_sparse_pool(p, c.sparse, esz)) != FFPA_OK) return rc;
+  // 8. the gathered pool's geometry (a wide variant: all of it but the span), 9. the stride rule of a pool of one-byte elements
+  if (v.gather && (rc = ds ? check_sparse_ds_pool(p, c.sparse, v.wide) : check_sparse_pool(p, c.sparse, esz, v.wide)) != FFPA_OK) return rc;
   if (e4m3 && (rc = v.gather ? check_fp8_strides(c.sparse->kv_stride[0], c.sparse->kv_stride[1], 0)
                              : check_fp8_strides(p->k_stride[0], p->k_stride[1], c.kv->k_page_stride)) != FFPA_OK)
     return rc;
@@ -2196,6 +2197,25 @@ int ffpa_attn_mla_index_k_append_fp8(const ffpa_mla_index_k_append_fp8_params* p
   if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla index k append (fp8) launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
   return FFPA_OK;
 }
+
+// ---- the three sparse latent calls over a WIDE pool (include/ffpa_attn.h): the same calls on the wide variants — the same checks but for the span, the same plan
+#define FFPA_WIDE_CALLS(name, id, PARAMS, ARGS)                                                                                                          \
+  int ffpa_attn_varlen_##name##_fwd(PARAMS, void* stream) { return varlen_launch(gather_call(ffpa::id, ARGS), stream); }                                 \
+  int ffpa_attn_varlen_##name##_fwd_plan(PARAMS, int out[5]) { return call_plan(gather_call(ffpa::id, ARGS), out); }                                     \
+  int ffpa_attn_varlen_##name##_fwd_kernel(PARAMS, char* buf, size_t n) { return call_kernel(gather_call(ffpa::id, ARGS), buf, n); }                     \
+  size_t ffpa_attn_varlen_##name##_fwd_workspace_bytes(PARAMS) { return call_workspace_bytes(gather_call(ffpa::id, ARGS)); }
+#define FFPA_WIDE_PS const ffpa_varlen_fwd_params *p, const ffpa_mla_sparse *s
+#define FFPA_WIDE_ARGS p, s
+FFPA_WIDE_CALLS(mla_sparse_wide, kMlaVariant_mla_sparse_wide, FFPA_WIDE_PS, FFPA_WIDE_ARGS)
+FFPA_WIDE_CALLS(mla_sparse_ds_wide, kMlaVariant_mla_sparse_ds_wide, FFPA_WIDE_PS, FFPA_WIDE_ARGS)
+#undef FFPA_WIDE_ARGS
+#undef FFPA_WIDE_PS
+#define FFPA_WIDE_PS const ffpa_varlen_fwd_params *p, const ffpa_mla_sparse *s, const ffpa_mla_fp8 *f8
+#define FFPA_WIDE_ARGS p, s, f8
+FFPA_WIDE_CALLS(mla_sparse_fp8_wide, kMlaVariant_mla_sparse_fp8_wide, FFPA_WIDE_PS, FFPA_WIDE_ARGS)
+#undef FFPA_WIDE_ARGS
+#undef FFPA_WIDE_PS
+#undef FFPA_WIDE_CALLS
 
 // ---- the sparse latent call (include/ffpa_attn.h: ffpa_mla_sparse): the latent launch over per-token index lists
 int ffpa_attn_varlen_mla_sparse_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream) {

@@ -5,8 +5,17 @@
 // kernel, nothing changed.
   constexpr int MK = 0;  // no attn_bias, no mask ranges
   constexpr bool DROP = false;
+#ifndef FFPA_M16_KV_GATHER64  // (1: the gather over a WIDE pool, 64-bit lane addresses and no descriptor — ffpa_mla_sparse*_wide_inst.hip; see below)
+#define FFPA_M16_KV_GATHER64 0
+#define FFPA_M16_PAGED_GATHER64_DEFAULT
+#endif
+#if FFPA_M16_KV_GATHER64
+#define FFPA_M16_MFMA Mfma16G64<T, NT>
+#define FFPA_M16_DMA16 LdsDma16G64<NT>::template at
+#else
 #define FFPA_M16_MFMA std::conditional_t<NT, Mfma16Nt<T>, Mfma16<T>>
 #define FFPA_M16_DMA16 LdsDma16<NT>::template at
+#endif
 #define FFPA_M16_PAGED 1
 #ifndef FFPA_M16_KV_GATHER  // (1: the keys of a tile are rows picked by an index list — ffpa_mla_sparse_inst.hip; see below)
 #define FFPA_M16_KV_GATHER 0
@@ -48,7 +57,11 @@
   static_assert(FFPA_M16_MLA_ON && PPW * 64 == 8 * kGSpr, "gathered keys: a wave's pieces of a tile are whole rows, eight of them");
   using cint_ptr = __attribute__((address_space(4))) const int*;  // (constant address space: a uniform load is a scalar load)
   const cint_ptr g_idx = (cint_ptr)(pa.table + (int64_t)seq * pa.bt_stride);
+#if !FFPA_M16_KV_GATHER64
   const uint32_t g_span = (uint32_t)(pa.num_pages - 1) * ((uint32_t)a.sk[2] * 2u) + (uint32_t)FFPA_M16_GATHER_ROW_BYTES;  // bytes of a head's rows in the pool (<= 2^31: the launch side)
+#else
+  const uint64_t g_zero = (uint64_t)(uintptr_t)kGatherZeroRow;  // (the enclosing unit's block of zeros: what a lane without a row reads)
+#endif
   int g_id[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the loaded row ids: this wave's keys of the tile whose offsets are formed next
   int g_next = 0;                          // first key of the tile whose ids are loaded next
   uint32_t g_sl[PPW];
@@ -70,6 +83,36 @@
     const int ge_ = (key0_) + 8 * wave + gk_;                              \
     g_id[gk_] = g_idx[ge_ < pa.cap - 1 ? ge_ : pa.cap - 1];                \
   }
+#if FFPA_M16_KV_GATHER64
+// THE WIDE POOL (FFPA_M16_KV_GATHER64): a head's rows may span any number of bytes, so krel[] holds the lane's 64-bit global ADDRESS of each piece and the loads go
+// through no descriptor (ffpa_mla_gather64.h).  The eight row ids are read, held and clamped as above; what they are multiplied into is a 64-bit SCALAR row term
+//     head base + (uint64) row id x row bytes          (s_mul_i32 + s_mul_hi_u32 + s_add_u32 + s_addc_u32 per key, 16 SGPRs that die inside this block)
+// of which a lane picks one — two v_cndmask — and adds its slot term g_sl[i] (+ g_sd[i] at the scale load of a 656-byte row): four VALU instructions per piece
+// where the narrow build has two.  (The other form — pick the lane's id, then one v_mad_u64_u32 per piece — needs the "no row" choice per LANE: two more selects
+// per piece on the 64-bit base, and nine ids in VGPRs next to nine address pairs; the scalar form keeps the choice where the count is known, per key.)  With no
+// range check there is no zero fill: the row term of a key at or past the token's count is the address of the unit's ZERO ROW (g_zero: kGatherZeroRow,
+// ffpa_mla_variant.inc — 1152 zero bytes, a 16-bit row; every slot term and scale term stays inside it), chosen by mask arithmetic on scalars, so such a lane
+// reads zeros — codes 0 under scale 0 — and no address is formed from whatever its entry holds.
+#define FFPA_M16_GATHER_FORM(key0_)                                                                        \
+  {                                                                                                        \
+    uint64_t g_ro_[8];                                                                                     \
+    int g_left_ = a.Nkv - ((key0_) + 8 * wave); /* valid keys among the wave's eight */                    \
+    _Pragma("unroll") for (int gk_ = 0; gk_ < 8; ++gk_) {                                                  \
+      int id_ = g_id[gk_];                                                                                 \
+      id_ = id_ > 0 ? id_ : 0;                                                                             \
+      id_ = id_ < pa.num_pages - 1 ? id_ : pa.num_pages - 1;                                               \
+      int oob_ = gk_ + 1 - g_left_; /* > 0: the key lies at or past the count */                           \
+      oob_ = oob_ > 0 ? oob_ : 0;                                                                          \
+      oob_ = oob_ < 1 ? oob_ : 1;                                                                          \
+      const uint64_t no_row_ = 0ull - (uint64_t)(uint32_t)oob_; /* all ones: no row */                     \
+      g_ro_[gk_] = (((uint64_t)Kg + (uint64_t)(uint32_t)id_ * k_row_bytes) & ~no_row_) | (g_zero & no_row_); \
+    }                                                                                                      \
+    _Pragma("unroll") for (int gi_ = 0; gi_ < PPW; ++gi_) {                                                \
+      const int lo_ = gi_ * 64 / kGSpr, hi_ = (gi_ * 64 + 63) / kGSpr;                                     \
+      krel[gi_] = (lane < hi_ * kGSpr - gi_ * 64 ? g_ro_[lo_] : g_ro_[hi_]) + g_sl[gi_];                   \
+    }                                                                                                      \
+  }
+#else
 #define FFPA_M16_GATHER_FORM(key0_)                                                                        \
   {                                                                                                        \
     uint32_t g_ro_[8];                                                                                     \
@@ -88,6 +131,7 @@
       krel[gi_] = g_sl[gi_] + (lane < hi_ * kGSpr - gi_ * 64 ? g_ro_[lo_] : g_ro_[hi_]);                   \
     }                                                                                                      \
   }
+#endif
 #define FFPA_M16_KV_BEGIN(t0_)                               \
   if (nt > (t0_)) {                                          \
     FFPA_M16_GATHER_LOAD((t0_) * BC)                         \
@@ -101,7 +145,11 @@
 #define FFPA_M16_KV_STEP_END()                               \
   FFPA_M16_GATHER_LOAD(g_next)                               \
   g_next += BC;
+#if FFPA_M16_KV_GATHER64
+#define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) TileSrc{}  // (no descriptor: the piece forms of this build do not read one)
+#else
 #define FFPA_M16_KV_SRC(kind, slice, row_bytes, key0) gather_src((slice), g_span)
+#endif
 #else
   // ---- page-table state (all wave-uniform, scalar)
   using cint_ptr = __attribute__((address_space(4))) const int*;  // (constant address space: a uniform load is a scalar load)
@@ -192,6 +240,10 @@
 #ifdef FFPA_M16_PAGED_GATHER_DEFAULT
 #undef FFPA_M16_PAGED_GATHER_DEFAULT
 #undef FFPA_M16_KV_GATHER
+#endif
+#ifdef FFPA_M16_PAGED_GATHER64_DEFAULT
+#undef FFPA_M16_PAGED_GATHER64_DEFAULT
+#undef FFPA_M16_KV_GATHER64
 #endif
 #undef FFPA_M16_KV_STEP_END
 #undef FFPA_M16_KV_STEP

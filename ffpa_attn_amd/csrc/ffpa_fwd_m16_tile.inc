@@ -63,6 +63,13 @@
 #define FFPA_M16_KV_GATHER false
 #define FFPA_M16_KV_GATHER_DEFAULT_HOOKS
 #endif
+// A WIDE POOL under the gather (ffpa_mla_sparse*_wide_inst.hip): FFPA_M16_KV_GATHER64 = a constant of its build — krel[] holds 64-bit global ADDRESSES, not offsets
+// into a descriptor's range, and the enclosing kernel's piece forms (FFPA_M16_DMA16, FFPA_M16_MFMA, the register loads) take them; the descriptor of
+// FFPA_M16_KV_SRC is passed on unread.  The tile text reads the constant in ONE place, the type of krel[].  Kernels that do not define it: the text that stood here.
+#ifndef FFPA_M16_KV_GATHER64
+#define FFPA_M16_KV_GATHER64 false
+#define FFPA_M16_KV_GATHER64_DEFAULT_HOOKS
+#endif
 // AN FP8 (OCP e4m3) LATENT CACHE is the enclosing kernel's as well (ffpa_mla_fp8_inst.hip, on top of the MLA hook): FFPA_M16_KV_FP8 = a constant of its build,
 // FFPA_M16_KV_SCALE = the per-tensor dequantisation factor (K = scale x K8), FFPA_M16_KV_FP8_LOAD(rsrc, voff) = its 8-byte register load (buffer_load_8 with the
 // build's non-temporal choice).  The pool holds ONE byte per element, and every e4m3 value is exactly a T: the build's
@@ -134,7 +141,8 @@
   const int slots_valid = a.d_valid >> 3;
   uint32_t kvo[kRowDma ? 4 : 1], vvo[kRowDma ? 4 : 1];
   uint32_t kro[kRowDma ? KPW : 1], vro[kRowDma ? KPW : 1];
-  uint32_t krel[kRowDma ? 1 : PPW], vrel[kRowDma ? 1 : PPW];
+  std::conditional_t<FFPA_M16_KV_GATHER64, uint64_t, uint32_t> krel[kRowDma ? 1 : PPW];
+  uint32_t vrel[kRowDma ? 1 : PPW];
   uint32_t k_lds = 0, v_lds = 0;
   if constexpr (kRowDma) {
 #pragma unroll
@@ -1619,6 +1627,10 @@
 #undef FFPA_M16_KV_STEP
 #undef FFPA_M16_KV_BEGIN
 #undef FFPA_M16_KV_SRC
+#endif
+#ifdef FFPA_M16_KV_GATHER64_DEFAULT_HOOKS
+#undef FFPA_M16_KV_GATHER64_DEFAULT_HOOKS
+#undef FFPA_M16_KV_GATHER64
 #endif
 #ifdef FFPA_M16_KV_GATHER_DEFAULT_HOOKS
 #undef FFPA_M16_KV_GATHER_DEFAULT_HOOKS

@@ -1,5 +1,5 @@
 // ffpa_mla.h — MLA latent-cache attention (the ffpa_attn_varlen_mla*_fwd calls, ffpa_capi.hip): THE LIST OF ITS KERNEL VARIANTS, what the kernels take beyond
-// FwdArgs / VarlenArgs / PagedArgs, the launchers of the seven ffpa_mla*_inst.hip units (one shell: ffpa_mla_variant.inc) and the 16-bit appends.  A header of its
+// FwdArgs / VarlenArgs / PagedArgs, the launchers of the ffpa_mla*_inst.hip units (one shell: ffpa_mla_variant.inc) and the 16-bit appends.  A header of its
 // own so that the dense, packed and paged objects see nothing of it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,7 +18,9 @@ struct PagedArgs;
 // found by measurement.  One row per variant, in link order (build.py's MLA_VARIANTS names the same stems in the same order); the row's stem names the unit
 // (ffpa_<stem>_inst.hip), the kernel (ffpa_fwd_m16_<stem>_kernel) and the launchers (launch_<stem>_d<D>).  X(stem, tree, gather, pool, exit refresh, ...):
 //   tree          the element test of the tiles that hold a draft key reads the row's 64-bit mask word (and the wait in front of the KV loop: ffpa_mla_variant.inc)
-//   gather        0: the keys of a sequence are found through its page table; 1: through a list of pool rows per query token (the sparse calls)
+//   gather        0: the keys of a sequence are found through its page table; 1: through a list of pool rows per query token (the sparse calls), by 32-bit
+//                 offsets into one descriptor over a head's rows — a pool of at most 2^31 bytes per head; 2: through that list by 64-bit lane addresses and no
+//                 descriptor — the WIDE builds of the sparse calls, a pool of any span (MlaVariant::wide)
 //   pool          what a latent row is made of (FFPA_MLA_POOL_*)
 //   exit refresh  the epilogue's arguments are read again from the argument block behind the KV loop (ffpa_mla_variant.inc says why): on where the loop has no
 //                 scalar register to spare — measured per variant, not derived from the other three
@@ -32,15 +34,19 @@ struct PagedArgs;
   X(mla_fp8, 0, 0, FFPA_MLA_POOL_E4M3, 0, __VA_ARGS__)         \
   X(mla_sparse_fp8, 0, 1, FFPA_MLA_POOL_E4M3, 1, __VA_ARGS__)  \
   X(mla_tree_fp8, 1, 0, FFPA_MLA_POOL_E4M3, 1, __VA_ARGS__)    \
-  X(mla_sparse_ds, 0, 1, FFPA_MLA_POOL_DS, 1, __VA_ARGS__)
+  X(mla_sparse_ds, 0, 1, FFPA_MLA_POOL_DS, 1, __VA_ARGS__)     \
+  X(mla_sparse_wide, 0, 2, FFPA_MLA_POOL_16BIT, 0, __VA_ARGS__)     \
+  X(mla_sparse_fp8_wide, 0, 2, FFPA_MLA_POOL_E4M3, 1, __VA_ARGS__)  \
+  X(mla_sparse_ds_wide, 0, 2, FFPA_MLA_POOL_DS, 1, __VA_ARGS__)
 
 struct MlaVariant {
   const char* stem;
   bool tree, gather;
   int pool;
   bool exit_refresh;
+  bool wide;  // (a gather by 64-bit addresses: the launch side skips the span check for it and for nothing else)
 };
-#define FFPA_ROW(stem, tree, gather, pool, refresh, ...) {#stem, tree != 0, gather != 0, pool, refresh != 0},
+#define FFPA_ROW(stem, tree, gather, pool, refresh, ...) {#stem, tree != 0, gather != 0, pool, refresh != 0, gather == 2},
 constexpr MlaVariant kMlaVariants[] = {FFPA_FOR_EACH_MLA_VARIANT(FFPA_ROW, )};
 #undef FFPA_ROW
 #define FFPA_ROW(stem, ...) kMlaVariant_##stem,

@@ -1,0 +1,9 @@
+// ffpa_mla_sparse_ds_wide_inst.hip — ffpa_mla_sparse_ds_inst.hip for a WIDE pool: sparse (top-k indexed) attention over the 656-byte FP8 rows of DeepSeek-V3.2 (bf16 only) whose rows span more
+// than 2^31 bytes per latent head.  The gather variant of the latent kernel (ffpa_mla_variant.inc) with 64-bit lane addresses, no descriptor and a zero row for
+// the keys past a token's count (FFPA_MLA_GATHER 2).  Entry point: ffpa_attn_varlen_mla_sparse_ds_wide_fwd (ffpa_capi.hip).
+#define FFPA_MLA_STEM mla_sparse_ds_wide
+#define FFPA_MLA_TREE 0
+#define FFPA_MLA_GATHER 2
+#define FFPA_MLA_POOL FFPA_MLA_POOL_DS
+#define FFPA_MLA_EXIT_REFRESH 1
+#include "ffpa_mla_variant.inc"

@@ -4,7 +4,7 @@
 //
 //     #define FFPA_MLA_STEM mla_tree          the row's stem: ffpa_fwd_m16_<stem>_kernel, launch_<stem>_d<D>
 //     #define FFPA_MLA_TREE 1                 the tree mask
-//     #define FFPA_MLA_GATHER 0               keys through a list of pool rows, not a page table
+//     #define FFPA_MLA_GATHER 0               keys through a list of pool rows, not a page table (2: ... of a WIDE pool, by 64-bit lane addresses)
 //     #define FFPA_MLA_POOL FFPA_MLA_POOL_..  what a latent row is made of
 //     #define FFPA_MLA_EXIT_REFRESH 1         the epilogue's arguments are read again behind the KV loop
 //     #include "ffpa_mla_variant.inc"
@@ -30,12 +30,16 @@
 #if FFPA_MLA_POOL == FFPA_MLA_POOL_DS
 #include "ffpa_mla_sparse_ds.h"
 #endif
+#if FFPA_MLA_GATHER == 2
+#include "ffpa_mla_gather64.h"
+#endif
 
 namespace ffpa {
 
 #define FFPA_MLA_KERNEL FFPA_CAT(FFPA_CAT(ffpa_fwd_m16_, FFPA_MLA_STEM), _kernel)
 static_assert(kMlaVariants[FFPA_CAT(kMlaVariant_, FFPA_MLA_STEM)].tree == (FFPA_MLA_TREE != 0) &&
                   kMlaVariants[FFPA_CAT(kMlaVariant_, FFPA_MLA_STEM)].gather == (FFPA_MLA_GATHER != 0) &&
+                  kMlaVariants[FFPA_CAT(kMlaVariant_, FFPA_MLA_STEM)].wide == (FFPA_MLA_GATHER == 2) &&
                   kMlaVariants[FFPA_CAT(kMlaVariant_, FFPA_MLA_STEM)].pool == FFPA_MLA_POOL &&
                   kMlaVariants[FFPA_CAT(kMlaVariant_, FFPA_MLA_STEM)].exit_refresh == (FFPA_MLA_EXIT_REFRESH != 0),
               "the unit's switch list is not its row of FFPA_FOR_EACH_MLA_VARIANT (ffpa_mla.h)");
@@ -47,7 +51,13 @@ static_assert(kMlaVariants[FFPA_CAT(kMlaVariant_, FFPA_MLA_STEM)].tree == (FFPA_
 #define FFPA_MLA_ARGS MlaArgs
 #endif
 
-#if FFPA_MLA_GATHER
+#if FFPA_MLA_GATHER == 2
+// THE GATHER OVER A WIDE POOL (FFPA_M16_KV_GATHER64 on top of FFPA_M16_KV_GATHER, ffpa_fwd_m16_paged_body.inc): the gather below with 64-bit lane addresses and
+// no descriptor, so a head's rows may span any number of bytes.  What the range check's zero fill did for a key at or past the token's count, THE ZERO ROW does:
+// a block of zeros of one 16-bit row (1152 bytes; an e4m3 row's 576 and a 656-byte row with its scales fit inside), in the code object's own memory — no host work
+// per call, so the call still captures into a graph.  Such a lane reads ITS slot of this block: zeros, codes 0 under scale 0.
+static __device__ __attribute__((aligned(128))) const uint32_t kGatherZeroRow[FFPA_INST_D * 2 / 4] = {};
+#elif FFPA_MLA_GATHER
 // THE GATHER (FFPA_M16_KV_GATHER, ffpa_fwd_m16_paged_body.inc): a token is a sequence of ONE query token over a paged cache whose page size is one row, its block
 // table is its index row and its length the number of valid entries.  The hook replaces the page-table state and the per-tile descriptor: each wave reads the eight
 // row ids of ITS keys of a tile with scalar loads (they do not enter the vmcnt queue) and turns them into the per-lane source offsets of its pieces.  The L2 touch
@@ -121,6 +131,9 @@ __global__ __launch_bounds__(256) void FFPA_MLA_KERNEL(const FwdArgs a_in, const
 #if FFPA_MLA_GATHER
 #define FFPA_M16_KV_GATHER 1
 #endif
+#if FFPA_MLA_GATHER == 2
+#define FFPA_M16_KV_GATHER64 1
+#endif
 
 #if FFPA_MLA_POOL != FFPA_MLA_POOL_16BIT
 // A POOL OF E4M3 CODES (FFPA_M16_KV_FP8, ffpa_fwd_m16_tile.inc).  There is no FP8 arithmetic: every e4m3 value is exactly a bf16 and exactly an fp16, so the kernel
@@ -131,7 +144,11 @@ __global__ __launch_bounds__(256) void FFPA_MLA_KERNEL(const FwdArgs a_in, const
 #endif
 #if FFPA_MLA_POOL == FFPA_MLA_POOL_E4M3
 #define FFPA_M16_KV_SCALE ma.kv_scale
+#if FFPA_MLA_GATHER == 2
+#define FFPA_M16_KV_FP8_LOAD(rsrc_, voff_) global_load_at<u32x2, NT>(voff_)
+#else
 #define FFPA_M16_KV_FP8_LOAD(rsrc_, voff_) buffer_load_8<NT>((rsrc_), (voff_))
+#endif
 #elif FFPA_MLA_POOL == FFPA_MLA_POOL_DS
 // THE 656-BYTE ROWS (FFPA_M16_KV_DS; the format: ffpa_mla_sparse_ds.h) change three things.  The gather maps a lane's source slot s of the 576-wide image to the
 // row's bytes — ds_slot_off: eight codes at 8 s, or sixteen rotary bytes at 528 + 16 (s - 64) — and keeps per piece the distance from there to the slot's scale
@@ -146,8 +163,13 @@ __global__ __launch_bounds__(256) void FFPA_MLA_KERNEL(const FwdArgs a_in, const
 #define FFPA_M16_KV_DS_ROW_BYTES kDsRowBytes
 #define FFPA_M16_KV_DS_SLOT_OFF(s_) ds_slot_off(s_)
 #define FFPA_M16_KV_DS_SCALE_DELTA(s_) ds_scale_delta(s_)
+#if FFPA_MLA_GATHER == 2  // (the scale term is a difference modulo 2^32: sign-extended into the 64-bit address)
+#define FFPA_M16_KV_DS_LOAD(rsrc_, voff_) global_load_at<u32x4, NT>(voff_)
+#define FFPA_M16_KV_DS_LOAD_SCALE(rsrc_, voff_, i_) global_load_at<float, NT>((voff_) + (uint64_t)(int64_t)(int32_t)g_sd[i_])
+#else
 #define FFPA_M16_KV_DS_LOAD(rsrc_, voff_) buffer_load_16<NT>((rsrc_), (voff_))
 #define FFPA_M16_KV_DS_LOAD_SCALE(rsrc_, voff_, i_) buffer_load_f32<NT>((rsrc_), (voff_) + g_sd[i_])
+#endif
 #define FFPA_M16_KV_DS_WIDEN(raw_, scale_) ds_nope_widen((raw_), (scale_))
 #endif
 
@@ -217,6 +239,7 @@ int FFPA_CAT(FFPA_CAT(launch_, FFPA_MLA_STEM), FFPA_CAT(_d, FFPA_INST_D))(int dt
 #undef FFPA_M16_KV_FP8_LOAD
 #undef FFPA_M16_KV_SCALE
 #undef FFPA_M16_KV_FP8
+#undef FFPA_M16_KV_GATHER64
 #undef FFPA_M16_KV_GATHER
 #undef FFPA_M16_KV_LOOP_ENTRY
 #undef FFPA_M16_O_COLS

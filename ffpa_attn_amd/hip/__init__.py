@@ -609,6 +609,18 @@ _BINDINGS = (
   ("ffpa_attn_varlen_mla_sparse_ds_fwd_plan", _MLA_SPARSE + [_P(_INT)], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_ds_fwd_kernel", _MLA_SPARSE + [_STR, _SIZE], _INT, 7),
   ("ffpa_attn_varlen_mla_sparse_ds_fwd_workspace_bytes", _MLA_SPARSE, _SIZE, 7),
+  ("ffpa_attn_varlen_mla_sparse_wide_fwd", _MLA_SPARSE + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_wide_fwd_plan", _MLA_SPARSE + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_wide_fwd_kernel", _MLA_SPARSE + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_wide_fwd_workspace_bytes", _MLA_SPARSE, _SIZE, 7),
+  ("ffpa_attn_varlen_mla_sparse_fp8_wide_fwd", _MLA_SPARSE_FP8 + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fp8_wide_fwd_plan", _MLA_SPARSE_FP8 + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fp8_wide_fwd_kernel", _MLA_SPARSE_FP8 + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_fp8_wide_fwd_workspace_bytes", _MLA_SPARSE_FP8, _SIZE, 7),
+  ("ffpa_attn_varlen_mla_sparse_ds_wide_fwd", _MLA_SPARSE + [_VOID], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_ds_wide_fwd_plan", _MLA_SPARSE + [_P(_INT)], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_ds_wide_fwd_kernel", _MLA_SPARSE + [_STR, _SIZE], _INT, 7),
+  ("ffpa_attn_varlen_mla_sparse_ds_wide_fwd_workspace_bytes", _MLA_SPARSE, _SIZE, 7),
   ("ffpa_attn_mla_ds_store", [_P(FfpaMlaDsStoreParams), _VOID], _INT, 7),
   ("ffpa_attn_mla_sparse_topk_slots", [_P(FfpaMlaSparseTopkParams), _VOID], _INT, 7),
   ("ffpa_attn_mla_index_scores", [_P(FfpaMlaIndexScoresParams), _VOID], _INT, 7),
@@ -1970,24 +1982,27 @@ torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_tree_fp8_fwd_hip", _mla_out_
 
 
 # The sparse latent call (ffpa_attn_with_kvcache_mla_sparse): every query token attends to the latent rows its index list names
-MLA_SPARSE_SPAN_BYTES = 1 << 31  # what the kernel's 32-bit lane offsets reach: a head's rows of the pool span at most this many bytes (bit 31 = "no row")
+MLA_SPARSE_SPAN_BYTES = 1 << 31  # what the NARROW kernels' 32-bit lane offsets reach: a head's rows of the pool span at most this many bytes (bit 31 = "no row");
+# the wide kernels (``wide=True`` below, ``wide_pool=True`` on the three public calls) form 64-bit lane addresses and reach any span
 _MLA_SPARSE_IDENTITY: "dict[tuple, torch.Tensor]" = {}
 
 
-def mla_sparse_pool(kv_cache: torch.Tensor, name: str = "ffpa_attn::_mla_sparse_fwd_hip") -> "tuple[int, int, int]":
+def mla_sparse_pool(kv_cache: torch.Tensor, name: str = "ffpa_attn::_mla_sparse_fwd_hip", wide: bool = False) -> "tuple[int, int, int]":
   """``(num_rows, row stride, head stride)`` — elements — of a latent pool as the sparse call addresses it: the flat ``[num_rows, Hkv, D]``, or a page pool
   ``[num_pages, page_size, Hkv, D]`` of any positive ``page_size`` whose pages are evenly spaced (slot r = row ``r % page_size`` of page ``r // page_size`` then
   lies ``r`` row strides from the base).  ``ValueError``: pages that are not evenly spaced, and a pool whose rows span more than ``MLA_SPARSE_SPAN_BYTES`` —
-  from sizes and strides alone, so in front of any launch and without touching the pool's memory."""
+  from sizes and strides alone, so in front of any launch and without touching the pool's memory.  ``wide``: the pool is the wide kernels' — every rule but the
+  span's holds (up to 2^31 - 1 rows, any span)."""
   num_rows, row_stride, head_stride = _mla_sparse_slots(kv_cache, name)
   if kv_cache.element_size() == 1 and (row_stride % 16 != 0 or head_stride % 16 != 0):
     # (an FP8 pool: its loads are 8 bytes wide and the kernel's text doubles every stride; the span below counts its bytes — twice the rows of a 16-bit pool)
     raise ValueError(f"{name}: the row and head strides of an FP8 pool ({row_stride}, {head_stride}) must be multiples of 16 elements")
   span = (num_rows - 1) * row_stride * kv_cache.element_size() + kv_cache.size(-1) * kv_cache.element_size() if num_rows > 0 else 0
-  if span > MLA_SPARSE_SPAN_BYTES:
+  if span > MLA_SPARSE_SPAN_BYTES and not wide:
     raise ValueError(f"{name}: the pool's rows span {span} bytes per latent head ((num_rows - 1) * row stride + one row = ({num_rows} - 1) * "
                      f"{row_stride * kv_cache.element_size()} + {kv_cache.size(-1) * kv_cache.element_size()}); the sparse call's 32-bit offsets reach at most "
-                     f"2^31 = {MLA_SPARSE_SPAN_BYTES} bytes: hand it a view of the part of the pool the step's slots lie in")
+                     f"2^31 = {MLA_SPARSE_SPAN_BYTES} bytes: hand it a view of the part of the pool the step's slots lie in, or pass wide_pool=True (the "
+                     "build with 64-bit addresses)")
   return num_rows, row_stride, head_stride
 
 
@@ -2013,18 +2028,18 @@ def _mla_sparse_slots(kv_cache: torch.Tensor, name: str) -> "tuple[int, int, int
 MLA_DS_ROW_BYTES = 656  # a latent row of DeepSeek-V3.2's FP8 cache: 512 e4m3 codes, four float32 scales (one per 128 columns), 64 bf16 rotary columns
 
 
-def mla_sparse_ds_pool(kv_cache: torch.Tensor, name: str = "ffpa_attn::_mla_sparse_ds_fwd_hip") -> "tuple[int, int, int]":
+def mla_sparse_ds_pool(kv_cache: torch.Tensor, name: str = "ffpa_attn::_mla_sparse_ds_fwd_hip", wide: bool = False) -> "tuple[int, int, int]":
   """``mla_sparse_pool`` for a ``torch.uint8`` pool of 656-byte rows -> ``(num_rows, slot stride, head stride)`` in BYTES.  ``ValueError``: pages that are not
-  evenly spaced, a stride that is no multiple of 16 or a slot stride below 656, a pool whose rows span more than ``MLA_SPARSE_SPAN_BYTES``."""
+  evenly spaced, a stride that is no multiple of 16 or a slot stride below 656, a pool whose rows span more than ``MLA_SPARSE_SPAN_BYTES`` (not under ``wide``)."""
   num_rows, row_stride, head_stride = _mla_sparse_slots(kv_cache, name)
   if row_stride % 16 != 0 or head_stride % 16 != 0 or (num_rows > 1 and row_stride < MLA_DS_ROW_BYTES):
     raise ValueError(f"{name}: the slot and head strides of the pool ({row_stride}, {head_stride}) must be multiples of 16 bytes, slots at least "
                      f"{MLA_DS_ROW_BYTES} bytes apart")
   span = (num_rows - 1) * row_stride + MLA_DS_ROW_BYTES if num_rows > 0 else 0
-  if span > MLA_SPARSE_SPAN_BYTES:
+  if span > MLA_SPARSE_SPAN_BYTES and not wide:
     raise ValueError(f"{name}: the pool's rows span {span} bytes per latent head ((num_rows - 1) * slot stride + one row = ({num_rows} - 1) * {row_stride} + "
                      f"{MLA_DS_ROW_BYTES}); the sparse call's 32-bit offsets reach at most 2^31 = {MLA_SPARSE_SPAN_BYTES} bytes: hand it a view of the part of "
-                     "the pool the step's slots lie in")
+                     "the pool the step's slots lie in, or pass wide_pool=True (the build with 64-bit addresses)")
   return num_rows, row_stride, head_stride
 
 
@@ -2055,7 +2070,7 @@ def _mla_sparse_args(dtype, T: int, Hq: int, Hkv: int, D: int, head_dim_v: int, 
 
 def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int, indices: torch.Tensor, topk_lens: "torch.Tensor | None", softmax_scale: float, *,
                        return_lse: bool = True, flags: int = 0, plan_out: "dict | None" = None, num_splits: int = 0, kv_scale: "float | None" = None,
-                       ds: bool = False):
+                       ds: bool = False, wide: bool = False):
   """One call of ``ffpa_attn_varlen_mla_sparse_fwd``: ``q [T, Hq, D]`` (one row per query token), the latent pool ``kv_cache`` (``mla_sparse_pool``'s two forms),
   the int32 device ``indices [T, topk]`` of pool slots and the optional int32 ``topk_lens [T]`` -> ``(o [T, Hq, head_dim_v], lse [Hq, T] fp32 | None)``.  Token t
   attends to the rows ``indices[t, :clamp(topk_lens[t], 0, topk)]``; entries at and past the count are never turned into an address.  Nothing is read back to the
@@ -2065,10 +2080,13 @@ def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int,
   K8, row and head strides multiples of 16 — and the call is ``ffpa_attn_varlen_mla_sparse_fp8_fwd``, its own kernel; q and o stay bf16 / fp16.
 
   ``ds`` (``mla_sparse_ds_forward`` is this call with it): the pool is ``torch.uint8`` rows of ``MLA_DS_ROW_BYTES`` (``mla_sparse_ds_pool``'s two forms, strides in
-  bytes), q and o are bf16, and the call is ``ffpa_attn_varlen_mla_sparse_ds_fwd``."""
+  bytes), q and o are bf16, and the call is ``ffpa_attn_varlen_mla_sparse_ds_fwd``.
+
+  ``wide``: the call is the ``..._wide_fwd`` twin of whichever of the three the other arguments pick — the kernel with 64-bit lane addresses, over a pool of any
+  span; everything else, the plan and (inside the narrow reach) the bits are the narrow call's."""
   fp8 = kv_scale is not None
-  name = "ffpa_attn::_mla_sparse_ds_fwd_hip" if ds else "ffpa_attn::_mla_sparse_fp8_fwd_hip" if fp8 else "ffpa_attn::_mla_sparse_fwd_hip"
-  export = "ffpa_attn_varlen_mla_sparse_ds_fwd" if ds else "ffpa_attn_varlen_mla_sparse_fp8_fwd" if fp8 else "ffpa_attn_varlen_mla_sparse_fwd"
+  stem = ("mla_sparse_ds" if ds else "mla_sparse_fp8" if fp8 else "mla_sparse") + ("_wide" if wide else "")
+  name, export = f"ffpa_attn::_{stem}_fwd_hip", f"ffpa_attn_varlen_{stem}_fwd"
   if not q.is_cuda:
     raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
   lib = load_library()
@@ -2099,7 +2117,7 @@ def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int,
   if not _layout_ok(kv_cache, -3):
     raise ValueError(f"{name}: kv_cache needs head-dim stride 1, strides that are multiples of {16 if fp8 or ds else 8} elements and a 16-byte aligned base (it is "
                      "read in place)")
-  num_rows, row_stride, head_stride = (mla_sparse_ds_pool if ds else mla_sparse_pool)(kv_cache, name)
+  num_rows, row_stride, head_stride = (mla_sparse_ds_pool if ds else mla_sparse_pool)(kv_cache, name, wide)
   topk = indices.size(1)
   q = _rows(q, 0)
   if indices.stride(1) != 1 or indices.data_ptr() % 4 != 0 or (T > 1 and indices.stride(0) < topk):
@@ -2129,7 +2147,7 @@ def mla_sparse_forward(q: torch.Tensor, kv_cache: torch.Tensor, head_dim_v: int,
     nbytes = 0
     if not (p.num_splits == 1 or p.flags & FLAG_DETERMINISTIC):
       key = ("sparse", id(lib), q.device.index or 0, p.dtype, T, Hq, Hkv, D, s.head_dim_v, topk, p.flags, p.num_splits, os.environ.get("FFPA_HIP_FAKE_CUS")) + (
-        ("ds",) if ds else ("fp8",) if fp8 else ())
+        ("ds",) if ds else ("fp8",) if fp8 else ())  # (a wide call's plan is the narrow call's: one entry serves both)
       nbytes = _cached_scratch(_MLA_SCRATCH, key, lambda: int(getattr(lib, export + "_workspace_bytes")(*args)))
     workspace = _hand_over_workspace(p, q.device, stream, nbytes)  # (held in a local until the launch below has been enqueued)
     if plan_out is not None:
@@ -2202,6 +2220,25 @@ def _mla_sparse_ds_fwd_hip_torch_op(q, kv_cache, head_dim_v, indices, topk_lens,
 
 
 torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_sparse_ds_fwd_hip", _mla_out_fake)
+
+
+# The three sparse ops over a WIDE pool (``wide_pool=True`` on the public calls): the schemas of the three above, the ``..._wide_fwd`` launches
+def _define_mla_sparse_wide(stem: str, schema: str, forward):
+  torch.library.define(f"{_OP_NAMESPACE}::_{stem}_wide_fwd_hip", schema)
+  torch.library.impl(f"{_OP_NAMESPACE}::_{stem}_wide_fwd_hip", "CUDA")(forward)  # ROCm tensors dispatch on the CUDA key
+  torch.library.register_fake(f"{_OP_NAMESPACE}::_{stem}_wide_fwd_hip", _mla_out_fake)
+
+
+_MLA_SPARSE_SCHEMA = "(Tensor q, Tensor kv_cache, int head_dim_v, Tensor indices, Tensor? topk_lens, float softmax_scale, int num_splits=0) -> (Tensor o, Tensor softmax_lse)"
+_define_mla_sparse_wide("mla_sparse", _MLA_SPARSE_SCHEMA, lambda q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits=0: mla_sparse_forward(
+  q, kv_cache, int(head_dim_v), indices, topk_lens, softmax_scale, return_lse=True, num_splits=num_splits, wide=True))
+_define_mla_sparse_wide("mla_sparse_ds", _MLA_SPARSE_SCHEMA, lambda q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits=0: mla_sparse_forward(
+  q, kv_cache, int(head_dim_v), indices, topk_lens, softmax_scale, return_lse=True, num_splits=num_splits, ds=True, wide=True))
+_define_mla_sparse_wide(
+  "mla_sparse_fp8", "(Tensor q, Tensor kv_cache, int head_dim_v, float kv_scale, Tensor indices, Tensor? topk_lens, float softmax_scale, int num_splits=0) -> "
+  "(Tensor o, Tensor softmax_lse)", lambda q, kv_cache, head_dim_v, kv_scale, indices, topk_lens, softmax_scale, num_splits=0: mla_sparse_forward(
+    q, kv_cache, int(head_dim_v), indices, topk_lens, softmax_scale, return_lse=True, num_splits=num_splits, kv_scale=check_kv_scale(kv_scale, "ffpa_attn::_mla_sparse_fp8_wide_fwd_hip"),
+    wide=True))
 
 
 def mla_ds_store(kv_cache: torch.Tensor, kv_new: torch.Tensor, slots: torch.Tensor) -> None:

@@ -1425,11 +1425,14 @@ def ffpa_mla_index_k_append_fp8(
   return torch.ops.ffpa_attn._mla_index_k_append_fp8_hip(k_index_cache, k_index, cache_seqlens, block_table, cu_seqlens_q)
 
 
-def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=False, ds=False):
+def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=False, ds=False, wide_pool=False):
   """The argument checks of the sparse latent calls under their own ``name``, every rule written once and in the order ``ffpa_attn_with_kvcache_mla_sparse`` has
   always made them -> ``(T, Hq)``.  ``fp8``: the pool is ``torch.float8_e4m3fn`` (``ffpa_attn_with_kvcache_mla_sparse_fp8``) — the dtype rule is the FP8 latent
   calls', and ``mla_sparse_pool`` holds the pool to the FP8 stride rule and counts its span in its own bytes.  ``ds``: the pool is ``torch.uint8`` rows of 656
-  bytes (``ffpa_attn_with_kvcache_mla_sparse_ds``) under a bf16 ``q`` — its last dimension is the row's bytes, and ``mla_sparse_ds_pool`` holds its geometry."""
+  bytes (``ffpa_attn_with_kvcache_mla_sparse_ds``) under a bf16 ``q`` — its last dimension is the row's bytes, and ``mla_sparse_ds_pool`` holds its geometry.
+  ``wide_pool`` (a bool, ``TypeError`` otherwise): the pool is held to every rule but the span's."""
+  if not isinstance(wide_pool, bool):
+    raise TypeError(f"{name}: wide_pool must be a bool, got {wide_pool!r}")
   if softmax_scale is _MLA_REQUIRED or softmax_scale is None:
     raise TypeError(f"{name}: softmax_scale is required — an MLA model scales by 1 / sqrt(qk_nope_head_dim + qk_rope_head_dim) (x its YaRN factor), which is not "
                     "1 / sqrt(D) of the 576-wide absorbed head: there is no right default")
@@ -1488,7 +1491,7 @@ def _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax
     raise ValueError(f"{name}: topk_lens must be an int32 tensor [T={T}] on q's device")
   if kv_cache.numel() == 0:
     raise ValueError(f"{name}: kv_cache must be a non-empty pool")
-  (mla_sparse_ds_pool if ds else mla_sparse_pool)(kv_cache, name)  # (evenly spaced pages, the span the kernel's offsets reach, a byte pool's strides: ValueError)
+  (mla_sparse_ds_pool if ds else mla_sparse_pool)(kv_cache, name, wide_pool)  # (evenly spaced pages, the span the kernel's offsets reach, a byte pool's strides: ValueError)
   return T, Hq
 
 
@@ -1502,6 +1505,7 @@ def ffpa_attn_with_kvcache_mla_sparse(
   softmax_scale: float = _MLA_REQUIRED,
   num_splits: int = 0,
   return_softmax_lse: bool = False,
+  wide_pool: bool = False,
   **unsupported,
 ):
   """SPARSE attention over an MLA latent cache — DeepSeek-V3.2's "DeepSeek Sparse Attention" in its absorbed decode form (FlashMLA's sparse decode call): an
@@ -1515,7 +1519,12 @@ def ffpa_attn_with_kvcache_mla_sparse(
   are free, the last dimension has unit stride; keys are a row's ``D`` columns, values its first ``head_dim_v``.  ``(D, head_dim_v)`` = (576, 512), bf16 / fp16,
   ``Hq % Hkv == 0``.  The rows of a latent head may span at most 2^31 bytes — ``(num_rows - 1) * row stride + one row``, about 1.86 M dense 576-wide rows:
   the kernel's offsets are 32-bit with one bit spent on "no row" — a larger pool raises ``ValueError`` before any launch (hand over a view of the part the
-  step's slots lie in).
+  step's slots lie in, or pass ``wide_pool=True``).
+
+  ``wide_pool=True`` runs the WIDE build of the kernel on any pool: every lane forms a 64-bit address (no descriptor, no range check; a key past the count reads a
+  block of zeros the library keeps on the device), so the rows of a head may span any number of bytes — up to 2^31 - 1 rows, row strides below 2^24 elements
+  as before.  Every other rule, the plan, the one-graph call and — on a pool the narrow build accepts — the bits are the narrow build's.  It forms nine 64-bit
+  addresses per wave and KV step where the narrow build forms nine 32-bit offsets; the default ``False`` keeps the narrow build and its ``ValueError``.
 
   ``indices``: int32 ``[T, topk]`` on the device (unit stride in the last dimension, ``topk >= 1``), entry ``[t, j]`` a slot of the pool; duplicates are legal
   and count twice, as in a gather.  A 3-D ``[T, Hkv, topk]`` (per-head rows) raises ``NotImplementedError``.  ``topk_lens``: int32 ``[T]`` on the device, or
@@ -1535,13 +1544,14 @@ def ffpa_attn_with_kvcache_mla_sparse(
   if unsupported:
     raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no causal flag — the indexer has chosen visible keys —, no kv= append, "
                               "no window, soft-cap, tree mask, rotary tables, ALiBi, batch index or leftpad over the sparse latent call)")
-  T, Hq = _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits)
+  T, Hq = _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, wide_pool=wide_pool)
   from . import hip  # noqa: F401  (registers the ffpa_attn ops)
 
   if T == 0:
     out = q.new_empty((0, Hq, head_dim_v))
     return (out, q.new_empty((Hq, 0), dtype=torch.float32)) if return_softmax_lse else out
-  out, lse = torch.ops.ffpa_attn._mla_sparse_fwd_hip(q, kv_cache, head_dim_v, indices, topk_lens, float(softmax_scale), num_splits)
+  op = torch.ops.ffpa_attn._mla_sparse_wide_fwd_hip if wide_pool else torch.ops.ffpa_attn._mla_sparse_fwd_hip
+  out, lse = op(q, kv_cache, head_dim_v, indices, topk_lens, float(softmax_scale), num_splits)
   return (out, lse) if return_softmax_lse else out
 
 
@@ -1556,6 +1566,7 @@ def ffpa_attn_with_kvcache_mla_sparse_fp8(
   softmax_scale: float = _MLA_REQUIRED,
   num_splits: int = 0,
   return_softmax_lse: bool = False,
+  wide_pool: bool = False,
   **unsupported,
 ):
   """``ffpa_attn_with_kvcache_mla_sparse`` over an FP8 latent pool — DeepSeek-V3.2's top-k attention as an engine with ``kv_cache_dtype="fp8"`` issues it:
@@ -1570,7 +1581,8 @@ def ffpa_attn_with_kvcache_mla_sparse_fp8(
   are clamped into the pool), the required ``softmax_scale``, the ``(576, 512)`` build, ``num_splits``, the returns (``out [T, Hq, head_dim_v]``, fp32 ``lse [Hq,
   T]``) and the one-graph call are ``ffpa_attn_with_kvcache_mla_sparse``'s.  Two rules are the FP8 pool's own (``ValueError`` before any launch): the row and
   head strides must be multiples of 16 elements, and the rows of a latent head may span at most 2^31 BYTES — for a pool of one byte per element that is twice as
-  many rows, about 3.7 M dense 576-wide rows.  No ``kv=``: the step's rows are appended by the FP8 latent calls or by the engine
+  many rows, about 3.7 M dense 576-wide rows; ``wide_pool=True`` (``ffpa_attn_with_kvcache_mla_sparse``'s keyword, the same contract) runs the wide build of
+  this kernel, whose 8-byte loads take 64-bit addresses, on a pool of any span.  No ``kv=``: the step's rows are appended by the FP8 latent calls or by the engine
   (``quantize_latent_rows``).  Per-block scales inside the row — the 656-byte row layout of DeepSeek-V3.2 — are ``ffpa_attn_with_kvcache_mla_sparse_ds``'s.
   Not served: FP8 ``q``, a ``kv_scale`` on the device."""
   name = "ffpa_attn_with_kvcache_mla_sparse_fp8"
@@ -1580,11 +1592,12 @@ def ffpa_attn_with_kvcache_mla_sparse_fp8(
   from . import hip  # (registers the ffpa_attn ops)
 
   kv_scale = hip.check_kv_scale(kv_scale, name)
-  T, Hq = _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=True)
+  T, Hq = _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, fp8=True, wide_pool=wide_pool)
   if T == 0:
     out = q.new_empty((0, Hq, head_dim_v))
     return (out, q.new_empty((Hq, 0), dtype=torch.float32)) if return_softmax_lse else out
-  out, lse = torch.ops.ffpa_attn._mla_sparse_fp8_fwd_hip(q, kv_cache, head_dim_v, kv_scale, indices, topk_lens, float(softmax_scale), num_splits)
+  op = torch.ops.ffpa_attn._mla_sparse_fp8_wide_fwd_hip if wide_pool else torch.ops.ffpa_attn._mla_sparse_fp8_fwd_hip
+  out, lse = op(q, kv_cache, head_dim_v, kv_scale, indices, topk_lens, float(softmax_scale), num_splits)
   return (out, lse) if return_softmax_lse else out
 
 
@@ -1668,6 +1681,7 @@ def ffpa_attn_with_kvcache_mla_sparse_ds(
   softmax_scale: float = _MLA_REQUIRED,
   num_splits: int = 0,
   return_softmax_lse: bool = False,
+  wide_pool: bool = False,
   **unsupported,
 ):
   """``ffpa_attn_with_kvcache_mla_sparse`` over the 656-byte FP8 latent rows of DeepSeek-V3.2 — the format in which the engines that serve that model keep its
@@ -1682,20 +1696,22 @@ def ffpa_attn_with_kvcache_mla_sparse_ds(
   codes' —, entries in front of it are clamped into the pool), the required ``softmax_scale``, the ``(576, 512)`` build, ``num_splits``, the returns (``out [T, Hq,
   head_dim_v]``, fp32 ``lse [Hq, T]``) and the one-graph call are ``ffpa_attn_with_kvcache_mla_sparse``'s.  The pool's own rules (``ValueError`` before any
   launch): slot and head strides are multiples of 16 bytes, slots at least 656 bytes apart (a padded slot stride is fine), the base 16-byte aligned, and the rows
-  of a latent head span at most 2^31 bytes — about 3.27 M contiguous rows.  No ``kv=``: the step's rows are written by slot, ``store_latent_rows_ds``.  Not
+  of a latent head span at most 2^31 bytes — about 3.27 M contiguous rows — unless ``wide_pool=True`` (``ffpa_attn_with_kvcache_mla_sparse``'s keyword, the same
+  contract: the wide build of this kernel, both loads of a piece from 64-bit addresses, any span).  No ``kv=``: the step's rows are written by slot, ``store_latent_rows_ds``.  Not
   served: fp16 ``q``, ue8m0 / power-of-two scale variants of the row, this layout in the dense latent call and the tree call, ``-1`` holes inside an index row
   (``compact_topk_indices``)."""
   name = "ffpa_attn_with_kvcache_mla_sparse_ds"
   if unsupported:
     raise NotImplementedError(f"{name} does not support: {', '.join(sorted(unsupported))} (no causal flag — the indexer has chosen visible keys —, no kv= append, "
                               "no window, soft-cap, tree mask, rotary tables, ALiBi, batch index or leftpad over the sparse latent call)")
-  T, Hq = _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, ds=True)
+  T, Hq = _mla_sparse_check(name, q, kv_cache, head_dim_v, indices, topk_lens, softmax_scale, num_splits, ds=True, wide_pool=wide_pool)
   from . import hip  # noqa: F401  (registers the ffpa_attn ops)
 
   if T == 0:
     out = q.new_empty((0, Hq, head_dim_v))
     return (out, q.new_empty((Hq, 0), dtype=torch.float32)) if return_softmax_lse else out
-  out, lse = torch.ops.ffpa_attn._mla_sparse_ds_fwd_hip(q, kv_cache, head_dim_v, indices, topk_lens, float(softmax_scale), num_splits)
+  op = torch.ops.ffpa_attn._mla_sparse_ds_wide_fwd_hip if wide_pool else torch.ops.ffpa_attn._mla_sparse_ds_fwd_hip
+  out, lse = op(q, kv_cache, head_dim_v, indices, topk_lens, float(softmax_scale), num_splits)
   return (out, lse) if return_softmax_lse else out
 
 

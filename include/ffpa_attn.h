@@ -589,7 +589,8 @@ int ffpa_attn_mla_fp8_append_varlen(const ffpa_mla_append_varlen_params* p, cons
  *   (p->head_dim, head_dim_v) as in the latent call: (576, 512).
  * The kernel is a build of the latent kernel that reads a tile's rows where they lie: each wave reads the ids of its eight keys of a tile with scalar loads and
  * turns them into the source offsets of its LDS-DMA pieces — no gathered copy of the rows.  All offsets are 32-bit and bit 31 marks "no row", so the rows of a head
- * must span at most 2^31 bytes: (num_rows - 1) * kv_stride[0] * 2 + head_dim * 2 <= 2^31 (about 1.86 M contiguous 576-wide rows), else FFPA_ERR_BAD_SHAPE.
+ * must span at most 2^31 bytes: (num_rows - 1) * kv_stride[0] * 2 + head_dim * 2 <= 2^31 (about 1.86 M contiguous 576-wide rows), else FFPA_ERR_BAD_SHAPE — the
+ * narrow build's limit; ffpa_attn_varlen_mla_sparse_wide_fwd (below) reaches any span.
  * The plan is the latent call's for T one-token sequences of topk keys (row chunks of a group wider than the tile, KV ranges + merge, the non-temporal fetch).
  */
 typedef struct ffpa_mla_sparse {
@@ -670,6 +671,30 @@ int ffpa_attn_varlen_mla_sparse_ds_fwd(const ffpa_varlen_fwd_params* p, const ff
 size_t ffpa_attn_varlen_mla_sparse_ds_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s);
 int ffpa_attn_varlen_mla_sparse_ds_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]);
 int ffpa_attn_varlen_mla_sparse_ds_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n);
+
+/*
+ * WIDE POOLS IN THE THREE SPARSE CALLS — the 2^31-byte reach above is the reach of the NARROW builds' addressing (32-bit lane offsets into one descriptor, bit 31 =
+ * "no row"); one layer's latent pool of a serving engine holds several million rows and passes it.  ffpa_attn_varlen_mla_sparse_wide_fwd, _fp8_wide_fwd and
+ * _ds_wide_fwd are the three calls above on kernels of their own that form a 64-bit global address per lane and load through no descriptor: every argument, every
+ * check in its order and text, the plan (split count, NT, grid) and the result — to the bit, on a pool the narrow call accepts — are the narrow call's, and the
+ * one check that is skipped is the span's.  The reach: num_rows up to 2^31 - 1, slots < 2^24 elements (the 656-byte rows: bytes) apart as above, so a head's rows
+ * may span any number of bytes; alignment and "slots must not overlap" are unchanged.  Entries at and past a token's count are never turned into an address here
+ * either: such a lane reads a block of zeros the library keeps on the device (no host work per call: the calls capture into a graph as the narrow ones do).
+ * The kernel names read ffpa_fwd_m16_mla_sparse_wide_kernel<...>, ffpa_fwd_m16_mla_sparse_fp8_wide_kernel<...>, ffpa_fwd_m16_mla_sparse_ds_wide_kernel<...>.
+ * The wide kernels form nine 64-bit addresses per wave and KV step where the narrow ones form nine 32-bit offsets: take the narrow call where the pool fits it.
+ */
+int ffpa_attn_varlen_mla_sparse_wide_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream);
+size_t ffpa_attn_varlen_mla_sparse_wide_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s);
+int ffpa_attn_varlen_mla_sparse_wide_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]);
+int ffpa_attn_varlen_mla_sparse_wide_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n);
+int ffpa_attn_varlen_mla_sparse_fp8_wide_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, void* stream);
+size_t ffpa_attn_varlen_mla_sparse_fp8_wide_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8);
+int ffpa_attn_varlen_mla_sparse_fp8_wide_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, int out[5]);
+int ffpa_attn_varlen_mla_sparse_fp8_wide_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, const ffpa_mla_fp8* f8, char* buf, size_t n);
+int ffpa_attn_varlen_mla_sparse_ds_wide_fwd(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, void* stream);
+size_t ffpa_attn_varlen_mla_sparse_ds_wide_fwd_workspace_bytes(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s);
+int ffpa_attn_varlen_mla_sparse_ds_wide_fwd_plan(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, int out[5]);
+int ffpa_attn_varlen_mla_sparse_ds_wide_fwd_kernel(const ffpa_varlen_fwd_params* p, const ffpa_mla_sparse* s, char* buf, size_t n);
 
 /*
  * THE STORE OF SUCH ROWS, BY SLOT — engines write this cache through a slot mapping, not through sequence lengths.  ONE kernel on `stream`: row t of kv_new
