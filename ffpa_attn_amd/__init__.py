@@ -9,7 +9,7 @@ from .backends import Backend, CUDABackend, CuTeDSLBackend, HIPBackend, SDPABack
 from .flops import attention_fwd_flops, attention_valid_pairs
 from .functional import FFPAAttnMeta
 from .decode import DecodeStep
-from .interface import ffpa_attn_func, ffpa_attn_varlen_func
+from .interface import AttnFp8, ffpa_attn_fp8_codes, ffpa_attn_fp8_func, ffpa_attn_func, ffpa_attn_varlen_func, pack_attn_fp8_k, pack_attn_fp8_q, pack_attn_fp8_vt, quantize_attn_fp8
 from .kvcache import compact_topk_indices, ffpa_attn_varlen_with_kvcache, ffpa_attn_varlen_with_kvcache_mla, ffpa_attn_varlen_with_kvcache_mla_fp8, ffpa_attn_varlen_with_kvcache_mla_tree, ffpa_attn_varlen_with_kvcache_mla_tree_fp8, ffpa_attn_with_kvcache, ffpa_attn_with_kvcache_cascade, ffpa_attn_with_kvcache_mla, ffpa_attn_with_kvcache_mla_cascade, ffpa_attn_with_kvcache_mla_cascade_fp8, ffpa_attn_with_kvcache_mla_fp8, ffpa_attn_with_kvcache_mla_sparse, ffpa_attn_with_kvcache_mla_sparse_ds, ffpa_attn_with_kvcache_mla_sparse_fp8, ffpa_attn_with_kvcache_mla_tree, ffpa_attn_with_kvcache_mla_tree_fp8, ffpa_attn_with_kvcache_softcap, ffpa_attn_with_kvcache_tree, ffpa_attn_with_kvcache_window, ffpa_merge_attn_states, mla_cascade_rule, pack_latent_rows_ds, pack_tree_mask, quantize_latent_rows, slots_from_block_table, ffpa_mla_sparse_topk_slots, ffpa_mla_index_scores, ffpa_mla_index_scores_fp8, ffpa_mla_index_k_append_fp8, quantize_index_rows, pack_index_key_pages, unpack_index_key_pages, ffpa_mla_sparse_slots, store_latent_rows_ds, unpack_latent_rows_ds
 
 
@@ -92,6 +92,13 @@ __version__ = "0.5.0"  # = the library's ffpa_attn_version() ("ffpa-attn-amd 0.5
 __all__ = [
   "ffpa_attn_func",
   "ffpa_attn_varlen_func",
+  "ffpa_attn_fp8_func",
+  "ffpa_attn_fp8_codes",
+  "quantize_attn_fp8",
+  "pack_attn_fp8_q",
+  "pack_attn_fp8_k",
+  "pack_attn_fp8_vt",
+  "AttnFp8",
   "ffpa_attn_with_kvcache",
   "ffpa_attn_with_kvcache_cascade",
   "ffpa_attn_with_kvcache_tree",

@@ -42,6 +42,9 @@ MLA_BUILDS = [(576, 512)]
 MLA_VARIANTS = ["mla", "mla_sparse", "mla_tree", "mla_fp8", "mla_sparse_fp8", "mla_tree_fp8", "mla_sparse_ds",
                 "mla_sparse_wide", "mla_sparse_fp8_wide", "mla_sparse_ds_wide"]
 
+# head dims the FP8 attention forward is built for (FFPA_FP8_DECLARE, csrc/ffpa_fwd_fp8.h)
+FP8_HEAD_DIMS = [256, 320, 384, 448, 512]
+
 ARCH = "gfx950"
 CXXFLAGS = [
   f"--offload-arch={ARCH}",
@@ -86,6 +89,11 @@ def _units() -> list[Unit]:
   # the same launch over FP8 index keys, on the FP8 MFMA builtin, and the quantising append that fills their cache (no inline asm); the same guard
   units.append(Unit("ffpa_mla_index_scores_fp8.hip", "ffpa_mla_index_scores_fp8.o", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                     "temps_mla_index_scores_fp8", None, True, True))
+  # the FP8 attention forward: one TU per head dim (an MFMA kernel on compiler builtins, no inline asm; the same guard as the score units: its softmax VALU
+  # sits between MFMAs) and the pre-pass that quantises q, k, v into its scratch.  Their assembly lands where the attention ISA rules do not read
+  units += [Unit("ffpa_fwd_fp8_inst.hip", f"ffpa_fwd_fp8_d{d}.o", [f"-DFFPA_INST_D={d}", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                 f"temps_fwd_fp8_d{d}", d, True, True) for d in FP8_HEAD_DIMS]
+  units.append(Unit("ffpa_fwd_fp8_quant.hip", "ffpa_fwd_fp8_quant.o", [], "temps_fwd_fp8_quant", None, True, True))
   # the KV-cache append + rotary launch (every dtype / rotary form) and the merge of two attention states (the cascade's last launch): one small TU each, no
   # inline asm — their assembly lands in directories the attention ISA rules do not read
   units.append(Unit("ffpa_kvcache_append.hip", "ffpa_kvcache_append.o", [], "temps_append", None, True, True))

@@ -27,6 +27,7 @@
 #include "ffpa_mla_sparse_topk.h" // (the selection launch in front of the sparse latent calls)
 #include "ffpa_mla_index_scores.h" // (the indexer's score launch in front of the selection)
 #include "ffpa_mla_index_scores_fp8.h"  // (the same over FP8 index keys, and the quantising append of the step's index keys)
+#include "ffpa_fwd_fp8.h"               // (the FP8 attention forward: its pre-pass and its kernel)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
 #include "ffpa_merge_states.h"    // (the merge of two attention states)
 #include "ffpa_mla_cascade_plan.h"  // (the plan launch of a shared-prefix step over the MLA latent cache)
@@ -2195,6 +2196,105 @@ int ffpa_attn_mla_index_k_append_fp8(const ffpa_mla_index_k_append_fp8_params* p
   a.W = paged ? p->W : 1, a.num_pages = paged ? p->num_pages : p->B;  // (no table: one page per sequence)
   const int st = ffpa::launch_mla_index_k_append_fp8(a, static_cast<hipStream_t>(stream));
   if (st != 0) return fail(FFPA_ERR_LAUNCH, "mla index k append (fp8) launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
+}
+
+// ---- the FP8 attention forward (include/ffpa_attn.h: ffpa_fp8_quantize_params, ffpa_fp8_fwd_params): the shape checks both calls share
+static int fp8_check_shape(int dtype, int D, int B, int Hq, int Hkv, int Nq, int Nkv) {
+  if (dtype != FFPA_DTYPE_BF16 && dtype != FFPA_DTYPE_FP16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", dtype);
+  if (D != 256 && D != 320 && D != 384 && D != 448 && D != 512)
+    return fail(FFPA_ERR_BAD_HEADDIM, "head_dim=%d: the FP8 forward is built for 256, 320, 384, 448 and 512", D);
+  if (B < 1 || Hq < 1 || Hkv < 1 || Nq < 1 || Nkv < 1 || Hq % Hkv != 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "batch=%d heads_q=%d heads_kv=%d seqlen_q=%d seqlen_kv=%d must be positive, heads_q a multiple of heads_kv", B, Hq, Hkv, Nq, Nkv);
+  if ((int64_t)B * Hkv > 65535) return fail(FFPA_ERR_BAD_SHAPE, "batch * heads_kv = %lld is more than 65535", (long long)B * Hkv);
+  const int64_t rt = (Nq + ffpa::kFp8BlockRows - 1) / ffpa::kFp8BlockRows, nt = (Nkv + ffpa::kFp8BlockKeys - 1) / ffpa::kFp8BlockKeys;
+  if ((int64_t)B * Hq * rt + (int64_t)B * Hkv * nt > (1LL << 30)) return fail(FFPA_ERR_BAD_SHAPE, "more than 2^30 workgroups");
+  return FFPA_OK;
+}
+
+int ffpa_attn_fp8_quantize(const ffpa_fp8_quantize_params* p, void* stream) {
+  static_assert(FFPA_FP8_BLOCK_ROWS == ffpa::kFp8BlockRows && FFPA_FP8_BLOCK_KEYS == ffpa::kFp8BlockKeys, "the header states the kernels' tile");
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_fp8_quantize_params))
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_fp8_quantize_params ABI mismatch: size %u (want %zu)", p->struct_size, sizeof(ffpa_fp8_quantize_params));
+  if (p->reserved != 0 || p->reserved2 != 0) return fail(FFPA_ERR_BAD_ABI, "ffpa_fp8_quantize_params.reserved=%u / reserved2=%d must be 0", p->reserved, p->reserved2);
+  int rc;
+  if ((rc = fp8_check_shape(p->dtype, p->head_dim, p->batch, p->heads_q, p->heads_kv, p->seqlen_q, p->seqlen_kv)) != FFPA_OK) return rc;
+  if (p->smooth_k != 0 && p->smooth_k != 1) return fail(FFPA_ERR_BAD_SHAPE, "smooth_k=%d must be 0 or 1", p->smooth_k);
+  for (const int64_t* s : {p->q_stride, p->k_stride, p->v_stride})
+    for (int i = 0; i < 3; ++i)
+      if (s[i] < 0 || s[i] % 8 != 0) return fail(FFPA_ERR_BAD_STRIDE, "stride %lld must be a non-negative multiple of 8 elements", (long long)s[i]);
+  for (const void* ptr : {p->q, p->k, p->v, (const void*)p->q8, (const void*)p->k8, (const void*)p->v8t, (const void*)p->q_scale, (const void*)p->k_scale,
+                          (const void*)p->v_scale, (const void*)p->workspace}) {
+    if (ptr == nullptr) return fail(FFPA_ERR_NULL_POINTER, "q / k / v, the scratch and the workspace must be non-NULL");
+    if (!aligned16(ptr)) return fail(FFPA_ERR_MISALIGNED, "q / k / v, the scratch and the workspace must be 16-byte aligned");
+  }
+  if ((rc = check_device()) != FFPA_OK) return rc;
+  ffpa::Fp8QuantArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = p->q, a.k = p->k, a.v = p->v;
+  a.q8 = static_cast<uint8_t*>(p->q8), a.k8 = static_cast<uint8_t*>(p->k8), a.v8t = static_cast<uint8_t*>(p->v8t);
+  a.q_scale = p->q_scale, a.k_scale = p->k_scale, a.v_scale = p->v_scale;
+  const int64_t part = (int64_t)p->batch * p->heads_kv * ((p->seqlen_kv + ffpa::kFp8BlockKeys - 1) / ffpa::kFp8BlockKeys) * p->head_dim;
+  a.ksum_part = p->workspace, a.vamax_part = p->workspace + part, a.kmean = p->workspace + 2 * part;
+  for (int i = 0; i < 3; ++i) a.s_q[i] = p->q_stride[i], a.s_k[i] = p->k_stride[i], a.s_v[i] = p->v_stride[i];
+  a.B = p->batch, a.Hq = p->heads_q, a.Hkv = p->heads_kv, a.Nq = p->seqlen_q, a.Nkv = p->seqlen_kv, a.D = p->head_dim;
+  a.fp16 = p->dtype == FFPA_DTYPE_FP16, a.smooth_k = p->smooth_k, a.q_premul = p->q_premul;
+  const int st = ffpa::launch_fwd_fp8_quantize(a, static_cast<hipStream_t>(stream));
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "fp8 quantize launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
+}
+
+static int fp8_fwd_check(const ffpa_fp8_fwd_params* p) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_fp8_fwd_params))
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_fp8_fwd_params ABI mismatch: size %u (want %zu)", p->struct_size, sizeof(ffpa_fp8_fwd_params));
+  if (p->reserved != 0) return fail(FFPA_ERR_BAD_ABI, "ffpa_fp8_fwd_params.reserved=%u must be 0", p->reserved);
+  int rc;
+  if ((rc = fp8_check_shape(p->dtype, p->head_dim, p->batch, p->heads_q, p->heads_kv, p->seqlen_q, p->seqlen_kv)) != FFPA_OK) return rc;
+  if (p->causal != 0 && p->causal != 1) return fail(FFPA_ERR_BAD_SHAPE, "causal=%d must be 0 or 1", p->causal);
+  for (int i = 0; i < 3; ++i)
+    if (p->o_stride[i] < 0 || p->o_stride[i] % 4 != 0)
+      return fail(FFPA_ERR_BAD_STRIDE, "o_stride %lld must be a non-negative multiple of 4 elements", (long long)p->o_stride[i]);
+  return FFPA_OK;
+}
+
+int ffpa_attn_fp8_fwd(const ffpa_fp8_fwd_params* p, void* stream) {
+  int rc;
+  if ((rc = fp8_fwd_check(p)) != FFPA_OK) return rc;
+  for (const void* ptr : {p->q8, p->k8, p->v8t, (const void*)p->q_scale, (const void*)p->k_scale, (const void*)p->v_scale, (const void*)p->o}) {
+    if (ptr == nullptr) return fail(FFPA_ERR_NULL_POINTER, "the scratch and o must be non-NULL");
+    if (!aligned16(ptr)) return fail(FFPA_ERR_MISALIGNED, "the scratch and o must be 16-byte aligned");
+  }
+  if ((rc = check_device()) != FFPA_OK) return rc;
+  ffpa::Fp8FwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q8 = static_cast<const uint8_t*>(p->q8), a.k8 = static_cast<const uint8_t*>(p->k8), a.v8t = static_cast<const uint8_t*>(p->v8t);
+  a.q_scale = p->q_scale, a.k_scale = p->k_scale, a.v_scale = p->v_scale, a.o = p->o;
+  for (int i = 0; i < 3; ++i) a.s_o[i] = p->o_stride[i];
+  a.B = p->batch, a.Hq = p->heads_q, a.Hkv = p->heads_kv, a.Nq = p->seqlen_q, a.Nkv = p->seqlen_kv;
+  a.fp16 = p->dtype == FFPA_DTYPE_FP16, a.causal = p->causal;
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  int st;
+  switch (p->head_dim) {
+    case 256: st = ffpa::launch_fwd_fp8_d256(a, s); break;
+    case 320: st = ffpa::launch_fwd_fp8_d320(a, s); break;
+    case 384: st = ffpa::launch_fwd_fp8_d384(a, s); break;
+    case 448: st = ffpa::launch_fwd_fp8_d448(a, s); break;
+    default: st = ffpa::launch_fwd_fp8_d512(a, s); break;
+  }
+  if (st == -1) return fail(FFPA_ERR_NO_DEVICE, "no current HIP device");
+  if (st == -2) return fail(FFPA_ERR_LAUNCH, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (is this a gfx950?)");
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "fp8 forward launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
+}
+
+int ffpa_attn_fp8_fwd_kernel(const ffpa_fp8_fwd_params* p, char* buf, size_t n) {
+  int rc;
+  if ((rc = fp8_fwd_check(p)) != FFPA_OK) return rc;
+  if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL or empty");
+  snprintf(buf, n, "ffpa_fwd_fp8_kernel<%d, %s> rows=%d keys=%d pshift=%d mfma=16x16x128_f8f6f4", p->head_dim, p->dtype == FFPA_DTYPE_FP16 ? "fp16" : "bf16",
+           ffpa::kFp8BlockRows, ffpa::kFp8BlockKeys, ffpa::kFp8PShift);
   return FFPA_OK;
 }
 

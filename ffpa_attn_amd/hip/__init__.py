@@ -379,6 +379,63 @@ class FfpaMlaIndexKAppendFp8Params(ctypes.Structure):
   ]
 
 
+class FfpaFp8QuantizeParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_fp8_quantize_params`` (include/ffpa_attn.h): the pre-pass of the FP8 attention forward."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("q", ctypes.c_void_p),
+    ("k", ctypes.c_void_p),
+    ("v", ctypes.c_void_p),
+    ("q8", ctypes.c_void_p),
+    ("k8", ctypes.c_void_p),
+    ("v8t", ctypes.c_void_p),
+    ("q_scale", ctypes.c_void_p),
+    ("k_scale", ctypes.c_void_p),
+    ("v_scale", ctypes.c_void_p),
+    ("workspace", ctypes.c_void_p),
+    ("q_stride", ctypes.c_int64 * 3),
+    ("k_stride", ctypes.c_int64 * 3),
+    ("v_stride", ctypes.c_int64 * 3),
+    ("batch", ctypes.c_int32),
+    ("heads_q", ctypes.c_int32),
+    ("heads_kv", ctypes.c_int32),
+    ("seqlen_q", ctypes.c_int32),
+    ("seqlen_kv", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("dtype", ctypes.c_int32),
+    ("smooth_k", ctypes.c_int32),
+    ("q_premul", ctypes.c_float),
+    ("reserved2", ctypes.c_int32),
+  ]
+
+
+class FfpaFp8FwdParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_fp8_fwd_params`` (include/ffpa_attn.h): the FP8 attention kernel over quantised scratch."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("reserved", ctypes.c_uint32),
+    ("q8", ctypes.c_void_p),
+    ("k8", ctypes.c_void_p),
+    ("v8t", ctypes.c_void_p),
+    ("q_scale", ctypes.c_void_p),
+    ("k_scale", ctypes.c_void_p),
+    ("v_scale", ctypes.c_void_p),
+    ("o", ctypes.c_void_p),
+    ("o_stride", ctypes.c_int64 * 3),
+    ("batch", ctypes.c_int32),
+    ("heads_q", ctypes.c_int32),
+    ("heads_kv", ctypes.c_int32),
+    ("seqlen_q", ctypes.c_int32),
+    ("seqlen_kv", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("dtype", ctypes.c_int32),
+    ("causal", ctypes.c_int32),
+  ]
+
+
 class FfpaMlaAppendVarlenParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_mla_append_varlen_params`` (include/ffpa_attn.h): the latent append of a ragged step."""
 
@@ -626,6 +683,9 @@ _BINDINGS = (
   ("ffpa_attn_mla_index_scores", [_P(FfpaMlaIndexScoresParams), _VOID], _INT, 7),
   ("ffpa_attn_mla_index_scores_fp8", [_P(FfpaMlaIndexScoresFp8Params), _VOID], _INT, 7),
   ("ffpa_attn_mla_index_k_append_fp8", [_P(FfpaMlaIndexKAppendFp8Params), _VOID], _INT, 7),
+  ("ffpa_attn_fp8_quantize", [_P(FfpaFp8QuantizeParams), _VOID], _INT, 7),
+  ("ffpa_attn_fp8_fwd", [_P(FfpaFp8FwdParams), _VOID], _INT, 7),
+  ("ffpa_attn_fp8_fwd_kernel", [_P(FfpaFp8FwdParams), _STR, _SIZE], _INT, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
@@ -722,7 +782,7 @@ def _stamped(cls):
   p = cls()
   p.struct_size = ctypes.sizeof(cls)
   if cls not in (FfpaPagedKv, FfpaTreeMask, FfpaWindow, FfpaMla, FfpaMlaAppendVarlenParams, FfpaMlaSparse, FfpaMlaFp8, FfpaMlaDsStoreParams, FfpaMlaSparseTopkParams,
-                 FfpaMlaIndexScoresParams, FfpaMlaIndexScoresFp8Params, FfpaMlaIndexKAppendFp8Params):
+                 FfpaMlaIndexScoresParams, FfpaMlaIndexScoresFp8Params, FfpaMlaIndexKAppendFp8Params, FfpaFp8QuantizeParams, FfpaFp8FwdParams):
     p.abi_version = ABI_VERSION
   return p
 
@@ -2514,6 +2574,135 @@ def _mla_index_k_append_fp8_hip_torch_op(k_index_cache, k_index, cache_seqlens, 
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_mla_index_k_append_fp8_hip")
 def _mla_index_k_append_fp8_fake(k_index_cache, k_index, cache_seqlens, block_table, cu_seqlens_q):
   return torch.empty_like(cache_seqlens, memory_format=torch.contiguous_format)
+
+
+# The FP8 attention forward (ffpa_attn_fp8_func / ffpa_attn_fp8_codes, ffpa_attn_amd/interface.py, where the arguments are checked): the pre-pass and the kernel
+# The one Python statement of the kernel's constants (interface.py and the tests import them): the rows of a Q8 tile (one q scale each), the keys of a K8 / V8T
+# tile (one k scale each), the P factor 2^FP8_P_SHIFT; ``fp8_forward_kernel`` compares them with what the library reports (a GPU test calls it).  The head dims are
+# the build's list of translation units
+from ..build import FP8_HEAD_DIMS as _FP8_BUILD_DIMS  # noqa: E402
+
+FP8_BLOCK_ROWS, FP8_BLOCK_KEYS, FP8_P_SHIFT = 64, 128, 8
+FP8_HEAD_DIMS = tuple(_FP8_BUILD_DIMS)
+
+
+def fp8_scratch_shapes(B: int, Hq: int, Hkv: int, Nq: int, Nkv: int, D: int) -> dict:
+  """The shapes of the FP8 forward's scratch: uint8 ``q8`` / ``k8`` / ``v8t`` (one row per tile, in fragment order) and float32 ``q_scale`` / ``k_scale`` / ``v_scale``."""
+  rt, nt, dp = -(-Nq // FP8_BLOCK_ROWS), -(-Nkv // FP8_BLOCK_KEYS), -(-D // 128) * 128
+  return {"q8": (B, Hq, rt, FP8_BLOCK_ROWS * dp), "k8": (B, Hkv, nt, FP8_BLOCK_KEYS * dp), "v8t": (B, Hkv, nt, FP8_BLOCK_KEYS * D),
+          "q_scale": (B, Hq, rt), "k_scale": (B, Hkv, nt), "v_scale": (B, Hkv, D)}
+
+
+def _rows_last_dim(t: torch.Tensor) -> torch.Tensor:
+  return t if t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0 else t.contiguous()
+
+
+def fp8_quantize(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_premul: float, smooth_k: bool):
+  """The three launches of ``ffpa_attn_fp8_quantize``: bf16 / fp16 ``q [B, Hq, Nq, D]``, ``k`` / ``v [B, Hkv, Nkv, D]`` ->
+  ``(q8, q_scale, k8, k_scale, v8t, v_scale)`` (``fp8_scratch_shapes``), the bytes of ``quantize_attn_fp8``.  Asynchronous, nothing read back to the host."""
+  name = "ffpa_attn::_fp8_quantize_hip"
+  if not q.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
+  if q.dtype not in _DTYPE or k.dtype != q.dtype or v.dtype != q.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 q, k, v of one dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
+  lib = load_library()
+  B, Hq, Nq, D = q.shape
+  Hkv, Nkv = k.size(1), k.size(2)
+  shapes = fp8_scratch_shapes(B, Hq, Hkv, Nq, Nkv, D)
+  out = {n: torch.empty(s, dtype=torch.float32 if n.endswith("scale") else torch.uint8, device=q.device) for n, s in shapes.items()}
+  work = torch.empty(((2 * shapes["k_scale"][2] + 1) * B * Hkv * D,), dtype=torch.float32, device=q.device)
+  q, k, v = _rows_last_dim(q), _rows_last_dim(k), _rows_last_dim(v)
+  p = _stamped(FfpaFp8QuantizeParams)
+  p.q, p.k, p.v, p.workspace = q.data_ptr(), k.data_ptr(), v.data_ptr(), work.data_ptr()
+  for n, t in out.items():
+    setattr(p, n, t.data_ptr())
+  for i in range(3):
+    p.q_stride[i], p.k_stride[i], p.v_stride[i] = q.stride(i), k.stride(i), v.stride(i)
+  p.batch, p.heads_q, p.heads_kv, p.seqlen_q, p.seqlen_kv, p.head_dim = B, Hq, Hkv, Nq, Nkv, D
+  p.dtype, p.smooth_k, p.q_premul = _DTYPE[q.dtype], int(bool(smooth_k)), q_premul
+  rc = _call_on_stream(lib.ffpa_attn_fp8_quantize, q.device, ctypes.byref(p))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_fp8_quantize")
+  return out["q8"], out["q_scale"], out["k8"], out["k_scale"], out["v8t"], out["v_scale"]
+
+
+def _fp8_fwd_params(q8, q_scale, k8, k_scale, v8t, v_scale, o, seqlen_q: int, seqlen_kv: int, causal: bool) -> FfpaFp8FwdParams:
+  p = _stamped(FfpaFp8FwdParams)
+  p.q8, p.q_scale, p.k8, p.k_scale, p.v8t, p.v_scale = (t.data_ptr() for t in (q8, q_scale, k8, k_scale, v8t, v_scale))
+  p.batch, p.heads_q, p.heads_kv, p.seqlen_q, p.seqlen_kv, p.head_dim = q8.size(0), q8.size(1), k8.size(1), seqlen_q, seqlen_kv, v_scale.size(-1)
+  p.causal = int(bool(causal))
+  if o is not None:
+    p.o, p.dtype = o.data_ptr(), _DTYPE[o.dtype]
+    for i in range(3):
+      p.o_stride[i] = o.stride(i)
+  return p
+
+
+def fp8_forward(q8, q_scale, k8, k_scale, v8t, v_scale, seqlen_q: int, seqlen_kv: int, causal: bool, fp16: bool) -> torch.Tensor:
+  """One launch of ``ffpa_attn_fp8_fwd`` over scratch in the layout of ``fp8_scratch_shapes`` -> ``out [B, Hq, seqlen_q, D]`` (bf16, or fp16 with ``fp16``).
+  Asynchronous, nothing read back to the host."""
+  name = "ffpa_attn::_fp8_fwd_hip"
+  if not q8.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{q8.device.type}' (the HIP kernel needs a GPU tensor)")
+  B, Hq, Hkv, D = q8.size(0), q8.size(1), k8.size(1), v_scale.size(-1)
+  want = fp8_scratch_shapes(B, Hq, Hkv, seqlen_q, seqlen_kv, D)
+  for n, t in (("q8", q8), ("q_scale", q_scale), ("k8", k8), ("k_scale", k_scale), ("v8t", v8t), ("v_scale", v_scale)):
+    dt = torch.float32 if n.endswith("scale") else torch.uint8
+    if tuple(t.shape) != want[n] or t.dtype != dt or not t.is_contiguous() or t.device != q8.device:
+      raise ValueError(f"{name}: {n} must be a contiguous {dt} tensor of shape {want[n]} on {q8.device}, got {t.dtype} {tuple(t.shape)}")
+  lib = load_library()
+  o = torch.empty((B, Hq, seqlen_q, D), dtype=torch.float16 if fp16 else torch.bfloat16, device=q8.device)
+  p = _fp8_fwd_params(q8, q_scale, k8, k_scale, v8t, v_scale, o, seqlen_q, seqlen_kv, causal)
+  rc = _call_on_stream(lib.ffpa_attn_fp8_fwd, q8.device, ctypes.byref(p))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_fp8_fwd")
+  return o
+
+
+def fp8_forward_kernel(D: int, fp16: bool = False) -> str:
+  """The name ``ffpa_attn_fp8_fwd_kernel`` gives the kernel of head dim ``D``, with its tile."""
+  lib = load_library()
+  p = _stamped(FfpaFp8FwdParams)
+  p.batch = p.heads_q = p.heads_kv = p.seqlen_q = p.seqlen_kv = 1
+  p.head_dim, p.dtype = D, int(bool(fp16))
+  buf = ctypes.create_string_buffer(200)
+  rc = lib.ffpa_attn_fp8_fwd_kernel(ctypes.byref(p), buf, len(buf))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_fp8_fwd_kernel")
+  name = buf.value.decode()
+  want = f"rows={FP8_BLOCK_ROWS} keys={FP8_BLOCK_KEYS} pshift={FP8_P_SHIFT} "
+  if want not in name:
+    raise RuntimeError(f"ffpa_attn_amd: the library's FP8 kernel reports '{name}', this module states '{want.strip()}'")
+  return name
+
+
+torch.library.define(f"{_OP_NAMESPACE}::_fp8_quantize_hip", "(Tensor q, Tensor k, Tensor v, float q_premul, bool smooth_k) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+torch.library.define(
+  f"{_OP_NAMESPACE}::_fp8_fwd_hip",
+  "(Tensor q8, Tensor q_scale, Tensor k8, Tensor k_scale, Tensor v8t, Tensor v_scale, int seqlen_q, int seqlen_kv, bool causal, bool fp16) -> Tensor",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_fp8_quantize_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _fp8_quantize_hip_torch_op(q, k, v, q_premul, smooth_k):
+  return fp8_quantize(q, k, v, float(q_premul), smooth_k)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_fp8_quantize_hip")
+def _fp8_quantize_fake(q, k, v, q_premul, smooth_k):
+  shapes = fp8_scratch_shapes(q.size(0), q.size(1), k.size(1), q.size(2), k.size(2), q.size(3))
+  new = lambda n: q.new_empty(shapes[n], dtype=torch.float32 if n.endswith("scale") else torch.uint8)
+  return new("q8"), new("q_scale"), new("k8"), new("k_scale"), new("v8t"), new("v_scale")
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_fp8_fwd_hip", "CUDA")
+def _fp8_fwd_hip_torch_op(q8, q_scale, k8, k_scale, v8t, v_scale, seqlen_q, seqlen_kv, causal, fp16):
+  return fp8_forward(q8, q_scale, k8, k_scale, v8t, v_scale, int(seqlen_q), int(seqlen_kv), causal, fp16)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_fp8_fwd_hip")
+def _fp8_fwd_fake(q8, q_scale, k8, k_scale, v8t, v_scale, seqlen_q, seqlen_kv, causal, fp16):
+  return q8.new_empty((q8.size(0), q8.size(1), seqlen_q, v_scale.size(-1)), dtype=torch.float16 if fp16 else torch.bfloat16)
 
 
 # The latent append of a ragged step (ffpa_attn_varlen_with_kvcache_mla(kv=)): token rows packed by cu_seqlens_q, in front of the attention launch

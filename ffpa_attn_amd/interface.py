@@ -8,8 +8,12 @@ and — for everything else — the hand-written gfx950 kernel behind ``ffpa_att
 
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
+from . import hip  # noqa: F401  (registers the ffpa_attn:: ops the FP8 calls go through)
+from .hip import FP8_BLOCK_KEYS, FP8_BLOCK_ROWS, FP8_HEAD_DIMS, FP8_P_SHIFT  # the FP8 forward's tiles, P factor and head dims: stated once, there
 from .functional import FFPAAttnMeta
 
 
@@ -195,3 +199,166 @@ def ffpa_attn_varlen_func(
 
   return varlen_apply(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=dropout_p, softmax_scale=softmax_scale,
                       causal=causal, enable_gqa=enable_gqa, return_lse=return_lse, kwargs=dict(kwargs))
+
+
+# ----------------------------------------------------------------------------- the FP8 (e4m3 MFMA) forward, head dims 256 ... 512
+_LOG2E = 1.4426950408889634
+
+
+class AttnFp8(NamedTuple):
+  """What ``quantize_attn_fp8`` returns: the scratch the kernels compute on (``q8`` / ``k8`` / ``v8t`` uint8 in fragment order, one row per tile; float32
+  scales) and the same codes in the tensors' own layout (``*_codes [B, H, N, D]`` ``torch.float8_e4m3fn``)."""
+
+  q8: torch.Tensor
+  q_scale: torch.Tensor
+  k8: torch.Tensor
+  k_scale: torch.Tensor
+  v8t: torch.Tensor
+  v_scale: torch.Tensor
+  q_codes: torch.Tensor
+  k_codes: torch.Tensor
+  v_codes: torch.Tensor
+  k_mean: torch.Tensor
+
+
+def _pow2_up_scale(amax: torch.Tensor) -> torch.Tensor:
+  """``max(amax, 1e-4) / 448`` in float32, rounded UP to a power of two on its exponent bits (``quantize_index_rows``' rule)."""
+  bits = (amax.clamp(min=1e-4) / 448).view(torch.int32)
+  return ((bits & 0x7F800000) + ((bits & 0x007FFFFF) != 0).to(torch.int32) * 0x00800000).view(torch.float32)
+
+
+def _pad_rows(x: torch.Tensor, block: int, dp: int) -> torch.Tensor:
+  """``[B, H, N, D]`` -> ``[B, H, tiles, block, dp]``, zero rows / columns added."""
+  B, H, N, D = x.shape
+  tiles = -(-N // block)
+  out = x.new_zeros((B, H, tiles * block, dp))
+  out[:, :, :N, :D] = x
+  return out.view(B, H, tiles, block, dp)
+
+
+def _pack_fragments(codes: torch.Tensor, block: int) -> torch.Tensor:
+  """Codes ``[B, H, N, D]`` (1 byte each) -> uint8 ``[B, H, tiles, block * DP]``: per tile, fragment (row block rb, column chunk c) of 2 KiB = plane h, lane
+  16 g + r, byte e  <-  row 16 rb + r, column 128 c + 32 g + 16 h + e; rows past N and columns past D are zero codes."""
+  B, H, N, D = codes.shape
+  dp = -(-D // 128) * 128
+  x = _pad_rows(codes.view(torch.uint8), block, dp)
+  x = x.view(B, H, -1, block // 16, 16, dp // 128, 4, 2, 16)          # tile, rb, r, c, g, h, e
+  return x.permute(0, 1, 2, 3, 5, 7, 6, 4, 8).reshape(B, H, -1, block * dp)  # tile, rb, c, h, g, r, e
+
+
+def pack_attn_fp8_q(codes: torch.Tensor) -> torch.Tensor:
+  """e4m3 codes of q ``[B, Hq, Nq, D]`` -> the kernel's ``q8`` scratch (tiles of FP8_BLOCK_ROWS rows)."""
+  return _pack_fragments(codes, FP8_BLOCK_ROWS)
+
+
+def pack_attn_fp8_k(codes: torch.Tensor) -> torch.Tensor:
+  """e4m3 codes of k ``[B, Hkv, Nkv, D]`` -> the kernel's ``k8`` scratch (tiles of FP8_BLOCK_KEYS keys)."""
+  return _pack_fragments(codes, FP8_BLOCK_KEYS)
+
+
+def pack_attn_fp8_vt(codes: torch.Tensor) -> torch.Tensor:
+  """e4m3 codes of v ``[B, Hkv, Nkv, D]`` -> the kernel's ``v8t`` scratch: per key tile, fragment db = channels 16 db + r, and contraction position
+  ``p = 32 g + 16 h + e`` holds the tile's key ``16 ((p % 32) // 4) + 4 (p // 32) + p % 4`` — where the score accumulators leave that key's probability."""
+  B, H, N, D = codes.shape
+  x = _pad_rows(codes.view(torch.uint8), FP8_BLOCK_KEYS, D)
+  x = x.view(B, H, -1, 2, 4, 4, 4, D // 16, 16)                        # tile, key = 16 (4 h + e4) + 4 g + i -> h, e4, g, i; then db, r
+  return x.permute(0, 1, 2, 7, 3, 5, 8, 4, 6).reshape(B, H, -1, FP8_BLOCK_KEYS * D)  # tile, db, h, g, r, e4, i  (e = 4 e4 + i)
+
+
+def quantize_attn_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: "float | None" = None, smooth_k: bool = True) -> AttnFp8:
+  """THE definition of what the FP8 forward computes on (plain torch, any device; ``ffpa_attn_fp8_quantize`` writes these bytes).  SageAttention-2 style::
+
+      q:  x = float32(q) * float32(scale * log2(e));  one scale per tile of FP8_BLOCK_ROWS rows
+      k:  x = float32(k) - mean  (smooth_k; softmax-invariant: no correction term);  one scale per tile of FP8_BLOCK_KEYS keys
+          mean[b, h, d] = (sum over the key tiles, in tile order, of (the tile's keys added in key order)) / float32(Nkv), all in float32
+      v:  x = float32(v);  one scale per (batch, KV head, channel) over all keys
+      scale = max(amax |x|, 1e-4) / 448 rounded UP to a power of two;   code = rne_e4m3(clamp(x / scale, -448, +448))
+
+  ``q ~ q_scale * q_codes`` in exp2-domain units, ``k - mean ~ k_scale * k_codes``, ``v ~ v_scale * v_codes``."""
+  B, Hq, Nq, D = q.shape
+  scale = D ** -0.5 if scale is None else float(scale)
+  premul = torch.tensor(scale * _LOG2E, dtype=torch.float32, device=q.device)
+  f8 = torch.float8_e4m3fn
+  code = lambda x, s: (x / s).clamp(-448, 448).to(f8)
+
+  qt = _pad_rows(q.float() * premul, FP8_BLOCK_ROWS, D)
+  q_scale = _pow2_up_scale(qt.abs().amax(dim=(-1, -2)))
+  q_codes = code(qt, q_scale[..., None, None]).flatten(2, 3)[:, :, :Nq]
+
+  Nkv = k.size(2)
+  kt = _pad_rows(k.float(), FP8_BLOCK_KEYS, D)
+  part = torch.zeros_like(kt[:, :, :, 0])
+  for j in range(FP8_BLOCK_KEYS):
+    part = part + kt[:, :, :, j]
+  mean = torch.zeros_like(part[:, :, 0])
+  for t in range(part.size(2)):
+    mean = mean + part[:, :, t]
+  mean = mean / torch.tensor(float(Nkv), dtype=torch.float32, device=k.device) if smooth_k else torch.zeros_like(mean)
+  kt = _pad_rows(k.float() - mean[:, :, None, :], FP8_BLOCK_KEYS, D)
+  k_scale = _pow2_up_scale(kt.abs().amax(dim=(-1, -2)))
+  k_codes = code(kt, k_scale[..., None, None]).flatten(2, 3)[:, :, :Nkv]
+
+  vf = v.float()
+  v_scale = _pow2_up_scale(vf.abs().amax(dim=2))
+  v_codes = code(vf, v_scale[:, :, None, :])
+  return AttnFp8(pack_attn_fp8_q(q_codes), q_scale, pack_attn_fp8_k(k_codes), k_scale, pack_attn_fp8_vt(v_codes), v_scale, q_codes, k_codes, v_codes, mean)
+
+
+def _fp8_check(name: str, D: int, Hq: int, Hkv: int, enable_gqa: bool, attn_mask, dropout_p: float, return_lse: bool) -> None:
+  if attn_mask is not None:
+    raise NotImplementedError(f"{name}: attn_mask is not served by the FP8 forward (is_causal is); use ffpa_attn_func")
+  if dropout_p != 0.0:
+    raise NotImplementedError(f"{name}: dropout is not served by the FP8 forward; use ffpa_attn_func")
+  if return_lse:
+    raise NotImplementedError(f"{name}: the FP8 forward returns no LSE; use ffpa_attn_func")
+  if D not in FP8_HEAD_DIMS:
+    raise NotImplementedError(f"{name}: head dim {D} is not built; the FP8 forward serves {FP8_HEAD_DIMS} (D > 512 needs a split-D tile of its own)")
+  if Hq % Hkv != 0:
+    raise ValueError(f"query num_heads must be an integer multiple of key/value num_heads (GQA/MQA), got Nh_q={Hq}, Nh_kv={Hkv}")
+  if not enable_gqa and Hq != Hkv:
+    raise ValueError(f"enable_gqa=False but query num_heads ({Hq}) != key/value num_heads ({Hkv}). Set enable_gqa=True or use matching head counts.")
+
+
+def ffpa_attn_fp8_codes(q8: torch.Tensor, q_scale: torch.Tensor, k8: torch.Tensor, k_scale: torch.Tensor, v8t: torch.Tensor, v_scale: torch.Tensor, *,
+                        seqlen_q: int, seqlen_kv: int, is_causal: bool = False, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+  """The FP8 attention kernel alone, on scratch in the layout of ``quantize_attn_fp8`` (``pack_attn_fp8_q`` / ``_k`` / ``_vt``) -> ``out [B, Hq, seqlen_q, D]``:
+
+      s = q_scale[row tile] * k_scale[key tile] * (q8 . k8)      (exp2 domain: the softmax scale and log2(e) are in q)
+      out = v_scale * sum_j 2^(s_j - max s) v8_j / sum_j 2^(s_j - max s)
+
+  over the keys ``j < seqlen_kv`` and, with ``is_causal``, ``j <= row + seqlen_kv - seqlen_q``; a row that sees no key is 0.  A caller that keeps K / V
+  quantised across calls (the denoising steps of a diffusion pipeline) quantises once and calls this."""
+  if out_dtype not in (torch.bfloat16, torch.float16):
+    raise TypeError(f"ffpa_attn_fp8_codes: out_dtype must be torch.bfloat16 or torch.float16, got {out_dtype}")
+  if q8.dim() != 4 or k8.dim() != 4 or v_scale.dim() != 3:
+    raise ValueError("ffpa_attn_fp8_codes: q8 / k8 / v8t must be [B, H, tiles, bytes] and v_scale [B, Hkv, D]")
+  _fp8_check("ffpa_attn_fp8_codes", v_scale.size(-1), q8.size(1), k8.size(1), True, None, 0.0, False)
+  return torch.ops.ffpa_attn._fp8_fwd_hip(q8, q_scale, k8, k_scale, v8t, v_scale, seqlen_q, seqlen_kv, bool(is_causal), out_dtype == torch.float16)
+
+
+def ffpa_attn_fp8_func(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, *, is_causal: bool = False, scale: "float | None" = None,
+                       enable_gqa: bool = False, smooth_k: bool = True, attn_mask=None, dropout_p: float = 0.0, return_lse: bool = False) -> torch.Tensor:
+  """Attention forward with BOTH products on the e4m3 MFMA, head dims 256 / 320 / 384 / 448 / 512, inference only: the pre-pass (three HIP launches) quantises
+  ``query [B, Hq, Nq, D]`` and ``key`` / ``value [B, Hkv, Nkv, D]`` (bf16 / fp16) as ``quantize_attn_fp8`` defines, one more launch computes
+  ``out [B, Hq, Nq, D]`` in ``query``'s dtype.  Any ``Nq``, ``Nkv >= 1``; ``is_causal`` is tail-aligned as in ``ffpa_attn_func`` (key j visible to row i iff
+  ``j <= i + Nkv - Nq``) and serves ``Nq > Nkv`` too: a row that sees no key is 0.  ``attn_mask``, dropout, an LSE and other head dims raise
+  ``NotImplementedError``; so does a tensor that requires grad.  Nothing is read back to the host."""
+  name = "ffpa_attn_fp8_func"
+  for nm, t in (("query", query), ("key", key), ("value", value)):
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+      raise ValueError(f"{name}: query/key/value must be 4-D [B, H, N, D] tensors")
+  if query.dtype not in (torch.float16, torch.bfloat16) or key.dtype != query.dtype or value.dtype != query.dtype:
+    raise TypeError(f"{name} only supports fp16/bf16 query/key/value of one dtype, got {query.dtype}, {key.dtype}, {value.dtype}")
+  if key.shape != value.shape or key.size(0) != query.size(0) or key.size(3) != query.size(3):
+    raise ValueError(f"{name}: key and value must share one shape [B, Hkv, Nkv, D], B and D query's; got {tuple(query.shape)}, {tuple(key.shape)}, {tuple(value.shape)}")
+  _fp8_check(name, query.size(3), query.size(1), key.size(1), enable_gqa, attn_mask, dropout_p, return_lse)
+  if query.size(2) < 1 or key.size(2) < 1:
+    raise ValueError(f"{name}: Nq and Nkv must be at least 1")
+  for nm, t in (("query", query), ("key", key), ("value", value)):
+    if t.requires_grad and torch.is_grad_enabled():
+      raise NotImplementedError(f"{name} is inference only: {nm} requires grad and there is no backward")
+  if not query.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{query.device.type}' (the HIP kernel needs a GPU tensor)")
+  scale = query.size(3) ** -0.5 if scale is None else float(scale)
+  scratch = torch.ops.ffpa_attn._fp8_quantize_hip(query, key, value, scale * _LOG2E, bool(smooth_k))
+  return torch.ops.ffpa_attn._fp8_fwd_hip(*scratch, query.size(2), key.size(2), bool(is_causal), query.dtype == torch.float16)

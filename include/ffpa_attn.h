@@ -914,6 +914,83 @@ typedef struct ffpa_mla_index_k_append_fp8_params {
 int ffpa_attn_mla_index_k_append_fp8(const ffpa_mla_index_k_append_fp8_params* p, void* stream);
 
 /*
+ * FP8 ATTENTION FORWARD, head dims 256 / 320 / 384 / 448 / 512 — both products on the e4m3 MFMA (v_mfma_f32_16x16x128_f8f6f4), fp32 accumulators, inference only.
+ * Two calls: the pre-pass quantises bf16 / fp16 q, k, v into scratch the caller allocates; the attention kernel runs on that scratch alone (a caller that keeps
+ * K / V quantised across calls runs the pre-pass once).  The quantisation is defined by quantize_attn_fp8 (ffpa_attn_amd/interface.py); the pre-pass writes its bytes.
+ *   THE SCRATCH (DP = head_dim rounded up to 128; RT = ceil(seqlen_q / FFPA_FP8_BLOCK_ROWS) row tiles, NT = ceil(seqlen_kv / FFPA_FP8_BLOCK_KEYS) key tiles):
+ *     q8   batch * heads_q  * RT * FFPA_FP8_BLOCK_ROWS * DP bytes      q_scale  batch * heads_q  * RT float32
+ *     k8   batch * heads_kv * NT * FFPA_FP8_BLOCK_KEYS * DP bytes      k_scale  batch * heads_kv * NT float32
+ *     v8t  batch * heads_kv * NT * FFPA_FP8_BLOCK_KEYS * head_dim bytes   v_scale  batch * heads_kv * head_dim float32
+ *   in MFMA fragment order (csrc/ffpa_fwd_fp8.h; pack_attn_fp8_q / _k / _vt in interface.py restate it): v8t is transposed per key tile and its keys are
+ *   permuted so that the score accumulators are the PV operand as they stand.
+ *   workspace (pre-pass): (2 * NT + 1) * batch * heads_kv * head_dim float32.
+ *   q holds q * softmax_scale * log2(e) (q_premul = float32(softmax_scale * log2(e))); with smooth_k the per-(batch, KV head) mean over the keys is subtracted
+ *   from k first (softmax-invariant).  Scales are powers of two: pow2_up(max(amax, 1e-4) / 448).
+ *   The attention kernel: key j is visible to row i iff j < seqlen_kv and (not causal or j <= i + seqlen_kv - seqlen_q); a row without a visible key is 0.
+ * Checks, in this order: p NULL (FFPA_ERR_NULL_POINTER); struct_size, reserved (FFPA_ERR_BAD_ABI); dtype (FFPA_ERR_BAD_DTYPE); head_dim (FFPA_ERR_BAD_HEADDIM);
+ * batch / heads / seqlens < 1, heads_q % heads_kv, batch * heads_kv > 65535, more than 2^30 workgroups, causal / smooth_k outside {0, 1} (FFPA_ERR_BAD_SHAPE);
+ * a negative stride, a stride that is not a multiple of 8 elements (o: of 4) (FFPA_ERR_BAD_STRIDE); a NULL pointer (FFPA_ERR_NULL_POINTER); a 16-bit tensor or
+ * code scratch not 16-byte aligned, a float32 buffer not 16-byte aligned (FFPA_ERR_MISALIGNED); the device.
+ */
+#define FFPA_FP8_BLOCK_ROWS 64
+#define FFPA_FP8_BLOCK_KEYS 128
+
+typedef struct ffpa_fp8_quantize_params {
+  uint32_t struct_size;  /* sizeof(ffpa_fp8_quantize_params), checked */
+  uint32_t reserved;     /* 0, checked */
+  const void* q;         /* device [batch, heads_q, seqlen_q, head_dim] by q_stride, last dim contiguous */
+  const void* k;         /* device [batch, heads_kv, seqlen_kv, head_dim] by k_stride */
+  const void* v;         /* device, as k, by v_stride */
+  void* q8;              /* device scratch, written */
+  void* k8;
+  void* v8t;
+  float* q_scale;
+  float* k_scale;
+  float* v_scale;
+  float* workspace;
+  int64_t q_stride[3];   /* elements: {batch, head, row}, multiples of 8 */
+  int64_t k_stride[3];
+  int64_t v_stride[3];
+  int32_t batch;
+  int32_t heads_q;
+  int32_t heads_kv;
+  int32_t seqlen_q;
+  int32_t seqlen_kv;
+  int32_t head_dim;      /* 256 / 320 / 384 / 448 / 512 */
+  int32_t dtype;         /* FFPA_DTYPE_BF16 / FFPA_DTYPE_FP16 */
+  int32_t smooth_k;      /* 0 / 1 */
+  float q_premul;        /* float32(softmax_scale * log2(e)) */
+  int32_t reserved2;     /* 0, checked */
+} ffpa_fp8_quantize_params;
+
+typedef struct ffpa_fp8_fwd_params {
+  uint32_t struct_size;  /* sizeof(ffpa_fp8_fwd_params), checked */
+  uint32_t reserved;     /* 0, checked */
+  const void* q8;        /* device: the scratch above */
+  const void* k8;
+  const void* v8t;
+  const float* q_scale;
+  const float* k_scale;
+  const float* v_scale;
+  void* o;               /* device [batch, heads_q, seqlen_q, head_dim] by o_stride, last dim contiguous, written */
+  int64_t o_stride[3];   /* elements: {batch, head, row}, multiples of 4 */
+  int32_t batch;
+  int32_t heads_q;
+  int32_t heads_kv;
+  int32_t seqlen_q;
+  int32_t seqlen_kv;
+  int32_t head_dim;
+  int32_t dtype;         /* o's: FFPA_DTYPE_BF16 / FFPA_DTYPE_FP16 */
+  int32_t causal;        /* 0 / 1 */
+} ffpa_fp8_fwd_params;
+
+/* Launch on `stream` of the CURRENT device.  Asynchronous; every bad argument returns a status before any device work.  Return an ffpa_status. */
+int ffpa_attn_fp8_quantize(const ffpa_fp8_quantize_params* p, void* stream);
+int ffpa_attn_fp8_fwd(const ffpa_fp8_fwd_params* p, void* stream);
+/* The name of the kernel ffpa_attn_fp8_fwd launches for p, with its tile, into buf (NUL-terminated, truncated to n). */
+int ffpa_attn_fp8_fwd_kernel(const ffpa_fp8_fwd_params* p, char* buf, size_t n);
+
+/*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
  * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
  *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position
