@@ -203,7 +203,8 @@ __global__ __launch_bounds__(256) void ffpa_fwd_fp8_kernel(const Fp8FwdArgs a) {
     __syncthreads();  // K8(t + 1) is in LDS; nobody reads V8T(t) any more
   }
 
-  // ---- O = O^T . v_scale / (l 2^8): the scale product is exact (powers of two), the division is the one rounding in front of the output's
+  // ---- O = O^T / (l 2^8) . v_scale: the division is the one rounding in front of the output's, the scale product behind it exact (a power of two).  The
+  // division comes FIRST: O^T reaches 2^8 . 448 . l and O^T . v_scale leaves fp32 once v_scale passes about 2^110 (|v| ~ 2^118, bf16 only), where the quotient (<= 448 v_scale) is still finite
   const float* const vscale = a.v_scale + kvhead * D;
 #pragma unroll
   for (int rb = 0; rb < kRB; ++rb) {
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(256) void ffpa_fwd_fp8_kernel(const Fp8FwdArgs a) {
         const f32x4 vs = *reinterpret_cast<const f32x4*>(vscale + 16 * db + 4 * g);
         out4 y;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) y[i] = (T)(lt > 0.f ? o[rb][db][i] * vs[i] / den : 0.f);
+        for (int i = 0; i < 4; ++i) y[i] = (T)(lt > 0.f ? o[rb][db][i] / den * vs[i] : 0.f);
         *reinterpret_cast<out4*>(orow + 16 * db + 4 * g) = y;
       }
     }

@@ -6,30 +6,15 @@ import numpy as np
 import pytest
 import torch
 
-import kvcache_ref as kr
 import model_values as mv
 from ffpa_attn_amd import ffpa_attn_fp8_codes, ffpa_attn_fp8_func, pack_attn_fp8_k, pack_attn_fp8_q, pack_attn_fp8_vt, quantize_attn_fp8
 from ffpa_attn_amd.interface import FP8_BLOCK_KEYS as K, FP8_BLOCK_ROWS as R, FP8_P_SHIFT
+from fwd_fp8_cases import attend2, check_against_dequantised, fp8_allowance  # noqa: F401  (moved there unchanged; the edge tests share them)
 from test_fwd_gpu import hip  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 E4M3 = torch.float8_e4m3fn
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
-
-
-def attend2(qh, kh, vh, causal):
-  """Float64 attention in the exp2 domain: ``qh [B, Hq, Nq, D]``, ``kh`` / ``vh [B, Hkv, Nkv, D]`` -> ``(o, p / l, row has a key)``; tail-aligned causal."""
-  g = qh.size(1) // kh.size(1)
-  s = qh.double() @ kh.double().repeat_interleave(g, 1).transpose(-1, -2)
-  if causal:
-    s = s.masked_fill(~mv.causal_mask(qh.size(2), kh.size(2)), float("-inf"))
-  m = s.amax(-1, keepdim=True)
-  live = torch.isfinite(m)
-  p = torch.exp2(s - torch.where(live, m, torch.zeros_like(m)))
-  l = torch.where(live, p.sum(-1, keepdim=True), torch.ones_like(m))
-  p = torch.where(live, p, torch.zeros_like(p))
-  # (numerator first, ONE division: on integer operands the float64 numerator and l are exact, and the quotient is the exact one rounded once)
-  return (p @ vh.double().repeat_interleave(g, 1)) / l, p / l, live, s
 
 
 # ----------------------------------------------------------------------------- 1. the pre-pass writes the helper's bytes
@@ -101,29 +86,6 @@ def test_exact_on_integer_codes(hip, D, causal, shape, group):
 
 
 # ----------------------------------------------------------------------------- 3. model values, the derived allowance
-def fp8_allowance(p, vh, group):
-  """``sum_j max(2^-4 p_j, 2^-(10 + shift)) |v_jd|``, p = P / l: P's rounding to three mantissa bits, and half a subnormal step of p 2^shift below 2^-6."""
-  per_key = torch.maximum(p * 2.0 ** -4, p.new_full((), 2.0 ** -(10 + FP8_P_SHIFT)))
-  return per_key @ vh.double().abs().repeat_interleave(group, 1)
-
-
-def check_against_dequantised(out, q, k, v, scale, causal, smooth_k, name):
-  """-> ``(worst error / allowance, the allowance per element, the reference)`` of ``out`` against float64 attention over the helper's dequantised operands;
-  every element judged."""
-  h = quantize_attn_fp8(q, k, v, scale, smooth_k)
-  qh = h.q_codes.double() * h.q_scale.repeat_interleave(R, -1)[..., : q.size(2), None]
-  kh = h.k_codes.double() * h.k_scale.repeat_interleave(K, -1)[..., : k.size(2), None]
-  vh = h.v_codes.double() * h.v_scale[:, :, None, :]
-  want, p, live, _ = attend2(qh, kh, vh, causal)
-  half_ulp, flip = kr.allowance(want.numpy(), p.amax(-1).numpy(), p.pow(2).sum(-1).numpy(), vh, q.dtype, noise=False)
-  bound = half_ulp + flip + fp8_allowance(p, vh, q.size(1) // k.size(1)).numpy()
-  got = out.double().cpu().numpy()
-  assert np.isfinite(got).all() and (got[~live.expand_as(want).numpy()] == 0).all(), name
-  ratio = float((np.abs(got - want.numpy()) / bound).max())
-  print(f"{name}: worst error / allowance {ratio:.3f}")
-  return ratio, bound, want
-
-
 FAMILIES = ("outliers", "sink", "peaked", "large_logits", "staircase_up", "staircase_down")
 
 
