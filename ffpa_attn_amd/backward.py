@@ -179,12 +179,37 @@ def _bias_wider_than(attn_bias, dtype) -> bool:
   return attn_bias is not None and attn_bias.is_floating_point() and attn_bias.element_size() > torch.empty((), dtype=dtype).element_size()
 
 
+def hip_backward_refusal(q, k, *, attn_bias=None, dropout=None) -> "str | None":
+  """Why the backward KERNEL (``hip.backward``: head dims 513 ... 1024, the causal flag or no mask) does not serve this call — ``None`` if it does."""
+  from .hip import BWD_MAX_HEAD_DIM, BWD_MIN_HEAD_DIM
+
+  D = q.size(-1)
+  if attn_bias is not None:
+    return "an attn_mask / bias is not served by the backward kernel (is_causal is)"
+  if dropout is not None:
+    return "dropout is not served by the backward kernel"
+  if not BWD_MIN_HEAD_DIM <= D <= BWD_MAX_HEAD_DIM or D % 8 != 0:
+    return f"head_dim {D} is outside the backward kernel's range: multiples of 8 in [{BWD_MIN_HEAD_DIM + 7}, {BWD_MAX_HEAD_DIM}]"
+  if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype:
+    return f"dtype {q.dtype} is not bf16 / fp16"
+  if q.size(1) % k.size(1) != 0:
+    return f"Hq = {q.size(1)} is not a multiple of Hkv = {k.size(1)}"
+  return None
+
+
 def attention_backward(grad_out, q, k, v, o, lse, *, causal: bool, scale: float, attn_bias=None,
                        want_bias_grad: bool = False, force: str | None = None, dropout=None, dlse=None):
   """``(dq, dk, dv, d_attn_bias)`` for the forward ``o, lse = ffpa(q, k, v)``.  ``force`` = ``"aten"`` /
-  ``"recompute"`` pins one implementation (tests); otherwise aten first (head dims up to ``ATEN_MAX_HEAD_DIM``), recompute if it refuses.  ``dlse`` (the
+  ``"recompute"`` pins one implementation (tests), ``"hip"`` the backward kernel (head dims 513 ... 1024, no mask / bias / dropout: ``NotImplementedError`` naming
+  the reason outside that envelope; ``_FFPAAttnFunc`` passes it for ``backward_backend="hip"`` inside it); otherwise aten first (head dims up to ``ATEN_MAX_HEAD_DIM``), recompute if it refuses.  ``dlse`` (the
   gradient of a loss that used the LSE, ``[B, Hq, Nq]``) always takes the recompute: aten's op has no such input.  So does an fp32 ``attn_bias`` next to 16-bit
   q / k / v (``_bias_wider_than``)."""
+  if force == "hip":
+    why = hip_backward_refusal(q, k, attn_bias=attn_bias, dropout=dropout)
+    if why is not None:
+      raise NotImplementedError(f"attention_backward: {why}")
+    dq, dk, dv = torch.ops.ffpa_attn._bwd_hip(grad_out, q, k, v, o, lse, bool(causal), float(scale), dlse)
+    return dq, dk, dv, None
   key = (q.dtype, q.size(-1))
   attn_bias = _additive_bias(attn_bias, q.dtype)
   if dropout is not None or dlse is not None:

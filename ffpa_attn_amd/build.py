@@ -44,6 +44,8 @@ MLA_VARIANTS = ["mla", "mla_sparse", "mla_tree", "mla_fp8", "mla_sparse_fp8", "m
 
 # head dims the FP8 attention forward is built for (FFPA_FP8_DECLARE, csrc/ffpa_fwd_fp8.h)
 FP8_HEAD_DIMS = [256, 320, 384, 448, 512]
+# padded head dims the attention backward is built for (FFPA_BWD_DECLARE, csrc/ffpa_bwd_kernel.h): a head dim in (512, 1024] runs in the next one
+BWD_HEAD_DIMS = [640, 768, 896, 1024]
 
 ARCH = "gfx950"
 CXXFLAGS = [
@@ -94,6 +96,9 @@ def _units() -> list[Unit]:
   units += [Unit("ffpa_fwd_fp8_inst.hip", f"ffpa_fwd_fp8_d{d}.o", [f"-DFFPA_INST_D={d}", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                  f"temps_fwd_fp8_d{d}", d, True, True) for d in FP8_HEAD_DIMS]
   units.append(Unit("ffpa_fwd_fp8_quant.hip", "ffpa_fwd_fp8_quant.o", [], "temps_fwd_fp8_quant", None, True, True))
+  # the attention backward for head dims 513 ... 1024: one TU per padded head dim (MFMA kernels on compiler builtins, no inline asm: no row in the hazard rules;
+  # their assembly lands where the attention ISA rules do not read)
+  units += [Unit("ffpa_bwd_inst.hip", f"ffpa_bwd_d{d}.o", [f"-DFFPA_INST_D={d}"], f"temps_bwd_d{d}", d, True, True) for d in BWD_HEAD_DIMS]
   # the KV-cache append + rotary launch (every dtype / rotary form) and the merge of two attention states (the cascade's last launch): one small TU each, no
   # inline asm — their assembly lands in directories the attention ISA rules do not read
   units.append(Unit("ffpa_kvcache_append.hip", "ffpa_kvcache_append.o", [], "temps_append", None, True, True))

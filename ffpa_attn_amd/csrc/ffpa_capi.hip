@@ -28,6 +28,7 @@
 #include "ffpa_mla_index_scores.h" // (the indexer's score launch in front of the selection)
 #include "ffpa_mla_index_scores_fp8.h"  // (the same over FP8 index keys, and the quantising append of the step's index keys)
 #include "ffpa_fwd_fp8.h"               // (the FP8 attention forward: its pre-pass and its kernel)
+#include "ffpa_bwd_kernel.h"            // (the attention backward for head dims 513 ... 1024: its arguments and launchers)
 #include "ffpa_kvcache_append.h"  // (the KV-cache append + rotary launch)
 #include "ffpa_merge_states.h"    // (the merge of two attention states)
 #include "ffpa_mla_cascade_plan.h"  // (the plan launch of a shared-prefix step over the MLA latent cache)
@@ -2374,6 +2375,88 @@ int ffpa_attn_mla_append_varlen(const ffpa_mla_append_varlen_params* p, const ff
 int ffpa_attn_mla_fp8_append_varlen(const ffpa_mla_append_varlen_params* p, const ffpa_paged_kv* kv, const ffpa_mla_fp8* f8, void* stream) {
   const int rc = check_mla_fp8(f8);
   return rc != FFPA_OK ? rc : mla_append_varlen(p, kv, f8, stream);
+}
+
+// ---- the attention backward for head dims 513 ... 1024 (include/ffpa_attn.h: ffpa_bwd_params): the checks that need no pointer, shared by the three exports
+static int bwd_check_shape(const ffpa_bwd_params* p) {
+  if (p == nullptr) return fail(FFPA_ERR_NULL_POINTER, "params is NULL");
+  if (p->struct_size != sizeof(ffpa_bwd_params) || p->abi_version != FFPA_ATTN_ABI_VERSION)
+    return fail(FFPA_ERR_BAD_ABI, "ffpa_bwd_params ABI mismatch: size %u (want %zu), version %u (want %d)", p->struct_size, sizeof(ffpa_bwd_params), p->abi_version,
+                FFPA_ATTN_ABI_VERSION);
+  if (p->reserved != 0) return fail(FFPA_ERR_BAD_ABI, "ffpa_bwd_params.reserved=%u must be 0", p->reserved);
+  if (p->dtype != FFPA_DTYPE_BF16 && p->dtype != FFPA_DTYPE_FP16) return fail(FFPA_ERR_BAD_DTYPE, "dtype %d is not bf16(0)/fp16(1)", p->dtype);
+  if (p->head_dim <= 512 || p->head_dim > 1024 || p->head_dim % 8 != 0)
+    return fail(FFPA_ERR_BAD_HEADDIM, "head_dim=%d: the backward kernel serves multiples of 8 in (512, 1024]", p->head_dim);
+  if (p->batch < 1 || p->heads_q < 1 || p->heads_kv < 1 || p->seqlen_q < 1 || p->seqlen_kv < 1 || p->heads_q % p->heads_kv != 0)
+    return fail(FFPA_ERR_BAD_SHAPE, "batch=%d heads_q=%d heads_kv=%d seqlen_q=%d seqlen_kv=%d must be positive, heads_q a multiple of heads_kv", p->batch, p->heads_q,
+                p->heads_kv, p->seqlen_q, p->seqlen_kv);
+  const int64_t limit = (1LL << 31) - 64;
+  if ((int64_t)p->batch * p->heads_q * p->seqlen_q > limit || (int64_t)p->batch * p->heads_kv * ((p->seqlen_kv + ffpa::kBwdKeysDkdv - 1) / ffpa::kBwdKeysDkdv) > limit)
+    return fail(FFPA_ERR_BAD_SHAPE, "more than 2^31 - 64 rows or key tiles in one call");
+  if (p->causal != 0 && p->causal != 1) return fail(FFPA_ERR_BAD_SHAPE, "causal=%d must be 0 or 1", p->causal);
+  if (!isfinite(p->softmax_scale)) return fail(FFPA_ERR_BAD_SHAPE, "softmax_scale must be finite");
+  return FFPA_OK;
+}
+
+static int64_t bwd_padded_rows(const ffpa_bwd_params* p) { return ((int64_t)p->seqlen_q + ffpa::kBwdRows - 1) / ffpa::kBwdRows * ffpa::kBwdRows; }
+
+size_t ffpa_attn_bwd_workspace_bytes(const ffpa_bwd_params* p) {
+  if (bwd_check_shape(p) != FFPA_OK) return 0;
+  return (size_t)(2 * sizeof(float) * p->batch * p->heads_q * bwd_padded_rows(p));
+}
+
+int ffpa_attn_bwd_kernel(const ffpa_bwd_params* p, char* buf, size_t n) {
+  int rc;
+  if ((rc = bwd_check_shape(p)) != FFPA_OK) return rc;
+  if (buf == nullptr || n == 0) return fail(FFPA_ERR_NULL_POINTER, "buf is NULL or empty");
+  const int D = ffpa::bwd_padded_dim(p->head_dim);
+  const char* t = p->dtype == FFPA_DTYPE_FP16 ? "fp16" : "bf16";
+  snprintf(buf, n, "ffpa_bwd_delta_kernel<%s> + ffpa_bwd_dkdv_kernel<%s, %d> keys=%d rows=%d + ffpa_bwd_dq_kernel<%s, %d> rows=%d keys=%d d_valid=%d mfma=16x16x32", t, t, D,
+           ffpa::kBwdKeysDkdv, ffpa::kBwdRows, t, D, ffpa::kBwdRows, ffpa::kBwdKeysDq, p->head_dim);
+  return FFPA_OK;
+}
+
+int ffpa_attn_bwd(const ffpa_bwd_params* p, void* stream) {
+  int rc;
+  if ((rc = bwd_check_shape(p)) != FFPA_OK) return rc;
+  for (const int64_t* s : {p->q_stride, p->k_stride, p->v_stride, p->o_stride, p->dout_stride, p->dq_stride, p->dk_stride, p->dv_stride})
+    for (int i = 0; i < 3; ++i)
+      if (s[i] < 0 || s[i] % 8 != 0) return fail(FFPA_ERR_BAD_STRIDE, "stride %lld must be a non-negative multiple of 8 elements", (long long)s[i]);
+  for (const void* ptr : {p->q, p->k, p->v, p->o, p->dout, (const void*)p->dq, (const void*)p->dk, (const void*)p->dv, (const void*)p->workspace}) {
+    if (ptr == nullptr) return fail(FFPA_ERR_NULL_POINTER, "q / k / v / o / dout / dq / dk / dv and the workspace must be non-NULL");
+    if (!aligned16(ptr)) return fail(FFPA_ERR_MISALIGNED, "q / k / v / o / dout / dq / dk / dv and the workspace must be 16-byte aligned");
+  }
+  if (p->lse == nullptr) return fail(FFPA_ERR_NULL_POINTER, "lse must be non-NULL");
+  if (((uintptr_t)p->lse | (uintptr_t)p->dlse) % 4 != 0) return fail(FFPA_ERR_MISALIGNED, "lse / dlse must be 4-byte aligned");
+  const size_t need = ffpa_attn_bwd_workspace_bytes(p);
+  if (p->workspace_bytes < need)
+    return fail(FFPA_ERR_BAD_SHAPE, "workspace_bytes=%llu is less than the %zu bytes ffpa_attn_bwd_workspace_bytes asks for", (unsigned long long)p->workspace_bytes, need);
+  if ((rc = check_device()) != FFPA_OK) return rc;
+  ffpa::BwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = p->q, a.k = p->k, a.v = p->v, a.o = p->o, a.dout = p->dout, a.lse = p->lse, a.dlse = p->dlse;
+  a.dq = p->dq, a.dk = p->dk, a.dv = p->dv;
+  a.NqP = (int)bwd_padded_rows(p);
+  a.lse2 = static_cast<float*>(p->workspace), a.delta = a.lse2 + (int64_t)p->batch * p->heads_q * a.NqP;
+  for (int i = 0; i < 3; ++i) {
+    a.sq[i] = p->q_stride[i], a.sk[i] = p->k_stride[i], a.sv[i] = p->v_stride[i], a.so[i] = p->o_stride[i], a.sdo[i] = p->dout_stride[i];
+    a.sdq[i] = p->dq_stride[i], a.sdk[i] = p->dk_stride[i], a.sdv[i] = p->dv_stride[i];
+  }
+  a.B = p->batch, a.Hq = p->heads_q, a.Hkv = p->heads_kv, a.Nq = p->seqlen_q, a.Nkv = p->seqlen_kv, a.d_valid = p->head_dim;
+  a.causal = p->causal, a.fp16 = p->dtype == FFPA_DTYPE_FP16;
+  a.scale = p->softmax_scale, a.scale_log2 = (float)((double)p->softmax_scale * 1.4426950408889634);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  int st;
+  switch (ffpa::bwd_padded_dim(p->head_dim)) {
+    case 640: st = ffpa::launch_bwd_d640(a, s); break;
+    case 768: st = ffpa::launch_bwd_d768(a, s); break;
+    case 896: st = ffpa::launch_bwd_d896(a, s); break;
+    default: st = ffpa::launch_bwd_d1024(a, s); break;
+  }
+  if (st == -1) return fail(FFPA_ERR_NO_DEVICE, "no current HIP device");
+  if (st == -2) return fail(FFPA_ERR_LAUNCH, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed (is this a gfx950?)");
+  if (st != 0) return fail(FFPA_ERR_LAUNCH, "backward launch failed: %s", hipGetErrorString(static_cast<hipError_t>(st)));
+  return FFPA_OK;
 }
 
 // ---- the KV-cache append + rotary (include/ffpa_attn.h: ffpa_kv_append_params)

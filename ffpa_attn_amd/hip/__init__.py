@@ -436,6 +436,45 @@ class FfpaFp8FwdParams(ctypes.Structure):
   ]
 
 
+class FfpaBwdParams(ctypes.Structure):
+  """ctypes mirror of ``struct ffpa_bwd_params`` (include/ffpa_attn.h): the attention backward for head dims 513 ... 1024."""
+
+  _fields_ = [
+    ("struct_size", ctypes.c_uint32),
+    ("abi_version", ctypes.c_uint32),
+    ("q", ctypes.c_void_p),
+    ("k", ctypes.c_void_p),
+    ("v", ctypes.c_void_p),
+    ("o", ctypes.c_void_p),
+    ("dout", ctypes.c_void_p),
+    ("lse", ctypes.c_void_p),
+    ("dlse", ctypes.c_void_p),
+    ("dq", ctypes.c_void_p),
+    ("dk", ctypes.c_void_p),
+    ("dv", ctypes.c_void_p),
+    ("workspace", ctypes.c_void_p),
+    ("workspace_bytes", ctypes.c_uint64),
+    ("q_stride", ctypes.c_int64 * 3),
+    ("k_stride", ctypes.c_int64 * 3),
+    ("v_stride", ctypes.c_int64 * 3),
+    ("o_stride", ctypes.c_int64 * 3),
+    ("dout_stride", ctypes.c_int64 * 3),
+    ("dq_stride", ctypes.c_int64 * 3),
+    ("dk_stride", ctypes.c_int64 * 3),
+    ("dv_stride", ctypes.c_int64 * 3),
+    ("batch", ctypes.c_int32),
+    ("heads_q", ctypes.c_int32),
+    ("heads_kv", ctypes.c_int32),
+    ("seqlen_q", ctypes.c_int32),
+    ("seqlen_kv", ctypes.c_int32),
+    ("head_dim", ctypes.c_int32),
+    ("dtype", ctypes.c_int32),
+    ("causal", ctypes.c_int32),
+    ("softmax_scale", ctypes.c_float),
+    ("reserved", ctypes.c_uint32),
+  ]
+
+
 class FfpaMlaAppendVarlenParams(ctypes.Structure):
   """ctypes mirror of ``struct ffpa_mla_append_varlen_params`` (include/ffpa_attn.h): the latent append of a ragged step."""
 
@@ -686,6 +725,9 @@ _BINDINGS = (
   ("ffpa_attn_fp8_quantize", [_P(FfpaFp8QuantizeParams), _VOID], _INT, 7),
   ("ffpa_attn_fp8_fwd", [_P(FfpaFp8FwdParams), _VOID], _INT, 7),
   ("ffpa_attn_fp8_fwd_kernel", [_P(FfpaFp8FwdParams), _STR, _SIZE], _INT, 7),
+  ("ffpa_attn_bwd", [_P(FfpaBwdParams), _VOID], _INT, 7),
+  ("ffpa_attn_bwd_workspace_bytes", [_P(FfpaBwdParams)], _SIZE, 7),
+  ("ffpa_attn_bwd_kernel", [_P(FfpaBwdParams), _STR, _SIZE], _INT, 7),
   ("ffpa_attn_kvcache_append", [_P(FfpaKvAppendParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_kvcache_append_varlen", [_P(FfpaKvAppendVarlenParams), _P(FfpaPagedKv), _VOID], _INT, 7),
   ("ffpa_attn_merge_states", [_P(FfpaMergeStatesParams), _VOID], _INT, 7),
@@ -2703,6 +2745,84 @@ def _fp8_fwd_hip_torch_op(q8, q_scale, k8, k_scale, v8t, v_scale, seqlen_q, seql
 @torch.library.register_fake(f"{_OP_NAMESPACE}::_fp8_fwd_hip")
 def _fp8_fwd_fake(q8, q_scale, k8, k_scale, v8t, v_scale, seqlen_q, seqlen_kv, causal, fp16):
   return q8.new_empty((q8.size(0), q8.size(1), seqlen_q, v_scale.size(-1)), dtype=torch.float16 if fp16 else torch.bfloat16)
+
+
+# The attention backward for head dims 513 ... 1024 (backward.attention_backward(force="hip"), where the envelope is checked): ffpa_attn_bwd's three launches
+BWD_MIN_HEAD_DIM, BWD_MAX_HEAD_DIM = 513, 1024
+
+
+def _bwd_params(dtype: torch.dtype, B: int, Hq: int, Hkv: int, Nq: int, Nkv: int, D: int, causal: bool, scale: float) -> FfpaBwdParams:
+  p = _stamped(FfpaBwdParams)
+  p.batch, p.heads_q, p.heads_kv, p.seqlen_q, p.seqlen_kv, p.head_dim = B, Hq, Hkv, Nq, Nkv, D
+  p.dtype, p.causal, p.softmax_scale = _DTYPE[dtype], int(bool(causal)), float(scale)
+  return p
+
+
+def backward_kernel(D: int, dtype: torch.dtype = torch.bfloat16) -> str:
+  """The names ``ffpa_attn_bwd_kernel`` gives the kernels of head dim ``D``, with their tiles and the padded head dim they are built for."""
+  lib = load_library()
+  p = _bwd_params(dtype, 1, 1, 1, 1, 1, D, False, 1.0)
+  buf = ctypes.create_string_buffer(300)
+  rc = lib.ffpa_attn_bwd_kernel(ctypes.byref(p), buf, len(buf))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_bwd_kernel")
+  return buf.value.decode()
+
+
+def backward(grad_out: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, lse: torch.Tensor, causal: bool, scale: float,
+             dlse: "torch.Tensor | None" = None):
+  """The three launches of ``ffpa_attn_bwd``: ``(dq, dk, dv)`` in the inputs' dtype for ``o, lse = attention(q, k, v)`` — ``q`` / ``o`` / ``grad_out``
+  ``[B, Hq, Nq, D]``, ``k`` / ``v`` ``[B, Hkv, Nkv, D]`` bf16 / fp16 with 512 < D <= 1024, ``lse`` (natural log) and the optional ``dlse`` ``[B, Hq, Nq]``.  The
+  tail-aligned causal mask or none; rows whose LSE is -inf get dq = 0.  Strided inputs are read in place (last dim contiguous, strides multiples of 8 elements;
+  anything else is copied).  No atomics: the same bits on every run.  Asynchronous, nothing read back to the host."""
+  name = "ffpa_attn::_bwd_hip"
+  if not q.is_cuda:
+    raise NotImplementedError(f"{name} has no implementation for device '{q.device.type}' (the HIP kernel needs a GPU tensor)")
+  if q.dtype not in _DTYPE or any(t.dtype != q.dtype for t in (k, v, o, grad_out)):
+    raise TypeError(f"{name} only supports fp16/bf16 q, k, v, o, grad_out of one dtype, got {[t.dtype for t in (q, k, v, o, grad_out)]}")
+  B, Hq, Nq, D = q.shape
+  Hkv, Nkv = k.size(1), k.size(2)
+  if k.shape != v.shape or o.shape != q.shape or grad_out.shape != q.shape or k.size(0) != B or k.size(3) != D or tuple(lse.shape) != (B, Hq, Nq):
+    raise ValueError(f"{name}: q / o / grad_out [B, Hq, Nq, D], k / v [B, Hkv, Nkv, D], lse [B, Hq, Nq]; got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, "
+                     f"{tuple(o.shape)}, {tuple(grad_out.shape)}, {tuple(lse.shape)}")
+  if dlse is not None and tuple(dlse.shape) != (B, Hq, Nq):
+    raise ValueError(f"{name}: dlse must be [B, Hq, Nq] = {(B, Hq, Nq)}, got {tuple(dlse.shape)}")
+  lib = load_library()
+  q, k, v, o, grad_out = (_rows_last_dim(t) for t in (q, k, v, o, grad_out))
+  lse = lse.to(torch.float32).contiguous()
+  dlse = None if dlse is None else dlse.to(torch.float32).contiguous()
+  dq, dk, dv = torch.empty(q.shape, dtype=q.dtype, device=q.device), torch.empty(k.shape, dtype=q.dtype, device=q.device), torch.empty(k.shape, dtype=q.dtype, device=q.device)
+  p = _bwd_params(q.dtype, B, Hq, Hkv, Nq, Nkv, D, causal, scale)
+  need = lib.ffpa_attn_bwd_workspace_bytes(ctypes.byref(p))
+  if need == 0:
+    _raise_status(lib, 4, "ffpa_attn_bwd_workspace_bytes")
+  work = torch.empty((need // 4,), dtype=torch.float32, device=q.device)
+  p.q, p.k, p.v, p.o, p.dout, p.lse = (t.data_ptr() for t in (q, k, v, o, grad_out, lse))
+  p.dlse = None if dlse is None else dlse.data_ptr()
+  p.dq, p.dk, p.dv, p.workspace, p.workspace_bytes = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), work.data_ptr(), need
+  for i in range(3):
+    p.q_stride[i], p.k_stride[i], p.v_stride[i], p.o_stride[i], p.dout_stride[i] = q.stride(i), k.stride(i), v.stride(i), o.stride(i), grad_out.stride(i)
+    p.dq_stride[i], p.dk_stride[i], p.dv_stride[i] = dq.stride(i), dk.stride(i), dv.stride(i)
+  rc = _call_on_stream(lib.ffpa_attn_bwd, q.device, ctypes.byref(p))
+  if rc != 0:
+    _raise_status(lib, rc, "ffpa_attn_bwd")
+  return dq, dk, dv
+
+
+torch.library.define(
+  f"{_OP_NAMESPACE}::_bwd_hip",
+  "(Tensor grad_out, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, float scale, Tensor? dlse) -> (Tensor, Tensor, Tensor)",
+)
+
+
+@torch.library.impl(f"{_OP_NAMESPACE}::_bwd_hip", "CUDA")  # ROCm tensors dispatch on the CUDA key
+def _bwd_hip_torch_op(grad_out, q, k, v, o, lse, causal, scale, dlse):
+  return backward(grad_out, q, k, v, o, lse, causal, float(scale), dlse)
+
+
+@torch.library.register_fake(f"{_OP_NAMESPACE}::_bwd_hip")
+def _bwd_fake(grad_out, q, k, v, o, lse, causal, scale, dlse):
+  return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
 
 
 # The latent append of a ragged step (ffpa_attn_varlen_with_kvcache_mla(kv=)): token rows packed by cu_seqlens_q, in front of the attention launch

@@ -63,17 +63,20 @@ class _FFPAAttnFunc(torch.autograd.Function):
       ctx.causal = meta.attn_meta.is_causal
       ctx.scale = meta.attn_meta.scale
       ctx.dropout = (meta.attn_meta.dropout_p, seed, offset) if meta.attn_meta.dropout_p > 0.0 else None
+      ctx.backward_backend = meta.backward_meta.name
     return out
 
   @staticmethod
   def backward(ctx, grad_out):
-    from .backward import attention_backward
+    from .backward import attention_backward, hip_backward_refusal
 
     query, key, value, out, lse, attn_bias = ctx.saved_tensors
     want_bias = attn_bias is not None and ctx.needs_input_grad[3]
+    # backward_backend="hip": the backward kernel where it serves the call (head dims 513 ... 1024, no mask / dropout), today's route everywhere else
+    force = "hip" if ctx.backward_backend == "hip" and hip_backward_refusal(query, key, attn_bias=attn_bias, dropout=ctx.dropout) is None else None
     dq, dk, dv, dbias = attention_backward(
       grad_out.contiguous(), query, key, value, out, lse, causal=ctx.causal, scale=ctx.scale, attn_bias=attn_bias,
-      want_bias_grad=want_bias, dropout=ctx.dropout,
+      want_bias_grad=want_bias, dropout=ctx.dropout, force=force,
     )
     return dq, dk, dv, dbias, None
 

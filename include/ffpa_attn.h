@@ -991,6 +991,63 @@ int ffpa_attn_fp8_fwd(const ffpa_fp8_fwd_params* p, void* stream);
 int ffpa_attn_fp8_fwd_kernel(const ffpa_fp8_fwd_params* p, char* buf, size_t n);
 
 /*
+ * ATTENTION BACKWARD, head dims 513 ... 1024 (csrc/ffpa_bwd_kernel.h) — dq, dk, dv of o, lse = attention(q, k, v) from the saved o and the natural-log lse
+ * [batch, heads_q, seqlen_q] of ffpa_attn_fwd, the gradient dout of o and, optionally, the gradient dlse of lse.  q, o, dout, dq are
+ * [batch, heads_q, seqlen_q, head_dim], k, v, dk, dv [batch, heads_kv, seqlen_kv, head_dim], 16-bit of one dtype, by element strides {batch, head, row} with
+ * the last dim contiguous; lse and dlse are float32 and contiguous.  Key j is visible to row i iff j < seqlen_kv and (not causal or j <= i + seqlen_kv -
+ * seqlen_q); a row whose lse is -inf (it saw no key) ignores dlse and gets dq = 0.  No mask, bias or dropout.  head_dim is a multiple of 8 in (512, 1024] and runs
+ * in the build of the next of 640 / 768 / 896 / 1024.  Three launches on `stream` of the CURRENT device (row statistics; dk and dv; dq), no atomics — the same
+ * bits on every run — no allocation, no synchronisation.  workspace: ffpa_attn_bwd_workspace_bytes(p) bytes of device scratch, 16-byte aligned (float32
+ * lse log2(e) and delta = sum_d dout . o - dlse per row of the row axis padded to 32).
+ * Checks, in this order, before any device work: p NULL (FFPA_ERR_NULL_POINTER); struct_size, abi_version, reserved (FFPA_ERR_BAD_ABI); dtype
+ * (FFPA_ERR_BAD_DTYPE); head_dim <= 512, > 1024 or not a multiple of 8 (FFPA_ERR_BAD_HEADDIM); batch / heads / seqlens < 1, heads_q % heads_kv, more than 2^31 - 64
+ * rows batch * heads_q * seqlen_q or workgroups batch * heads_kv * ceil(seqlen_kv / 16), causal outside {0, 1}, a scale that is not finite (FFPA_ERR_BAD_SHAPE); a
+ * negative stride or one that is not a multiple of 8 elements (FFPA_ERR_BAD_STRIDE); a NULL tensor or workspace (FFPA_ERR_NULL_POINTER); a 16-bit tensor or the
+ * workspace not 16-byte, lse / dlse not 4-byte aligned (FFPA_ERR_MISALIGNED); workspace_bytes smaller than ffpa_attn_bwd_workspace_bytes(p)
+ * (FFPA_ERR_BAD_SHAPE); the device.
+ */
+typedef struct ffpa_bwd_params {
+  uint32_t struct_size;  /* sizeof(ffpa_bwd_params), checked */
+  uint32_t abi_version;  /* FFPA_ATTN_ABI_VERSION, checked */
+  const void* q;
+  const void* k;
+  const void* v;
+  const void* o;
+  const void* dout;
+  const float* lse;
+  const float* dlse;     /* optional (NULL: none) */
+  void* dq;              /* written */
+  void* dk;
+  void* dv;
+  void* workspace;
+  uint64_t workspace_bytes;
+  int64_t q_stride[3];   /* elements: {batch, head, row}, multiples of 8 */
+  int64_t k_stride[3];
+  int64_t v_stride[3];
+  int64_t o_stride[3];
+  int64_t dout_stride[3];
+  int64_t dq_stride[3];
+  int64_t dk_stride[3];
+  int64_t dv_stride[3];
+  int32_t batch;
+  int32_t heads_q;
+  int32_t heads_kv;
+  int32_t seqlen_q;
+  int32_t seqlen_kv;
+  int32_t head_dim;
+  int32_t dtype;         /* FFPA_DTYPE_BF16 / FFPA_DTYPE_FP16 */
+  int32_t causal;        /* 0 / 1 */
+  float softmax_scale;
+  uint32_t reserved;     /* 0, checked */
+} ffpa_bwd_params;
+
+int ffpa_attn_bwd(const ffpa_bwd_params* p, void* stream);
+/* The scratch ffpa_attn_bwd needs for p's shape (0 with last_error set if the shape is refused; pointers are not looked at). */
+size_t ffpa_attn_bwd_workspace_bytes(const ffpa_bwd_params* p);
+/* The names of the kernels ffpa_attn_bwd launches for p, with their tiles, into buf (NUL-terminated, truncated to n); pointers are not looked at. */
+int ffpa_attn_bwd_kernel(const ffpa_bwd_params* p, char* buf, size_t n);
+
+/*
  * KV-CACHE APPEND + ROTARY (FlashAttention's flash_attn_with_kvcache(k=, v=, rotary_cos=, rotary_sin=)) — the launch that goes in front of the attention
  * launch of a decode / chunked-prefill step.  ONE kernel on `stream`:
  *   * new key i of sequence b (k, v: [batch, seqlen_new, heads_kv, D] by k_stride / v_stride = {batch, row, head}) is written at cache position
